@@ -228,6 +228,33 @@ def time_extract(ctx, desc, out_p, ids_p, cap, t_lo, t_hi, steps, warmup, expect
     return (time.perf_counter() - t0) / steps, n_s, (enq, fin)
 
 
+DUMP_BUDGET = 64_000_000  # bytes --dump-outputs may write in all (.npy headers included)
+
+
+def dump_outputs(out_dir, surf, ids, budget=DUMP_BUDGET, prefix=""):
+    """--dump-outputs: what the timed extraction handed its caller in the last step - the wc_surfel records field by field and
+    their wc_surfel_id keys - as float64 .npy files, so that two builds can be compared output for output (the library returns
+    the surfels in a canonical order: timestamp, ties by id).  Above `budget` bytes a fixed, seeded sample of the surfels is
+    written, in output order, with its indices (sample_index)."""
+    from wildcat_slam_amd import synth
+
+    n = len(surf)
+    cols = {"surfel_t": surf["t"], "surfel_center": surf["center"], "surfel_cov": surf["cov"], "surfel_normal": surf["normal"],
+            "surfel_resolution": surf["resolution"], "surfel_sigma": surf["sigma"],
+            "surfel_id": np.stack([ids["kx"], ids["ky"], ids["kz"], ids["node"]], axis=-1)}  # int32 / uint32: exact in float64
+    per = 8 * sum(int(np.prod(c.shape[1:])) for c in cols.values())
+    budget -= 4096  # the files' headers and n_surfels
+    if n * per > budget:
+        k = budget // (per + 8)  # (+ 8: the sample's own index)
+        idx = np.sort(np.random.Generator(np.random.PCG64(synth.SEED)).choice(n, size=k, replace=False))
+        cols = {name: c[idx] for name, c in cols.items()}
+        cols["sample_index"] = idx
+    cols["n_surfels"] = np.array([n])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, c in cols.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.ascontiguousarray(c, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -243,7 +270,11 @@ def main():
     ap.add_argument("--no-clouds", action="store_true", help="skip firing_order / cloud_10m only (profiling the odometry step)")
     ap.add_argument("--extras-timeout", type=float, default=420.0, help="N > 1: seconds the sections after the headline may take")
     ap.add_argument("--in-flight", type=int, default=3, help="sweeps in flight (contexts) of the extra pipelined measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed extraction returned in its last step as DIR/<name>.npy "
+                                                          "(float64, <= 64 MB in all; N > 1: rank<r>_<name>.npy per rank)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if (args.gpus > 1 or os.environ.get("WC_BENCH_FORCE_DIST") == "1") and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as typed: become the launcher - one rank per GPU through torch.distributed.run (rendezvous on
@@ -349,7 +380,7 @@ def main():
 
     for _ in range(args.warmup):
         n_s = step()
-    assert os.environ.get("WC_BENCH_NO_ASSERT") or n_s == exp_surfels, (n_s, exp_surfels)
+    assert os.environ.get("WC_BENCH_NO_ASSERT") or args.warmup == 0 or n_s == exp_surfels, (n_s, exp_surfels)
 
     ctx.sync()
     barrier()
@@ -361,6 +392,10 @@ def main():
     elapsed = max_over_ranks(time.perf_counter() - t0)
     ms_per_step = elapsed / args.steps * 1e3
     value = world * n_pts / (elapsed / args.steps) / 1e6  # Mpts/s, whole job
+    assert os.environ.get("WC_BENCH_NO_ASSERT") or n_s == exp_surfels, (n_s, exp_surfels)
+    if args.dump_outputs:  # the last timed step's output, before the sections below reuse d_out / d_ids
+        dump_outputs(args.dump_outputs, d_out[: n_s * 144].cpu().numpy().view(R.SURFEL), d_ids[: n_s * 16].cpu().numpy().view(R.SURFEL_ID),
+                     budget=DUMP_BUDGET // world, prefix="rank%d_" % rank if world > 1 else "")
 
     stages, roofline = extraction_stage(ctx, step, n_pts, exp_surfels, args.steps, measure_roots=args.roots if (rank == 0 and world == 1) else -1)
     # measured ceiling of this device: a 1 GiB device-to-device copy, bytes read + written per second
