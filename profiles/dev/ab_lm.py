@@ -1,6 +1,6 @@
 """A/B of the LM solve under development options (round 6): the C4 window (bench.py's), the odometry step's window and a small one; per
 setting: iterations, termination, final cost, ms per LM iteration (median of the solves), crc32 of x, max |x - x_first_setting|.
-python profiles/dev/ab_lm.py "lm_back_chunks=1" "lm_back_chunks=0" [...]   (each argument: comma-separated name=value pairs; "" = defaults)
+python profiles/dev/ab_lm.py "lm_dense=1" "" [...]   (each argument: comma-separated name=value pairs; "" = defaults)
 env AB_LM_CASES=c4,small,step: which windows"""
 import os, sys, time, zlib
 ROOT_ = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
@@ -17,7 +17,7 @@ ctx.warmup() if hasattr(ctx, "warmup") else None
 def apply(spec, on):
     for kv in [s for s in spec.split(",") if s]:
         k, v = kv.split("=")
-        ctx.set_dev_option(k, int(v) if on else {"lin_pair": 1, "lm_side_stream": 1, "pcr_ahead": 1, "fx_split": -1, "knn_group": -1}.get(k, 0))
+        ctx.set_dev_option(k, int(v) if on else {"lm_side_stream": 1, "lm_dense_radius": 10, "fx_split": -1, "knn_group": -1}.get(k, 0))
 
 
 def c4_like(scans, patches, seed):

@@ -9,7 +9,7 @@ feat = [i for i, r in enumerate(rows) if "k_features" in r["Kernel_Name"]]
 i_feat = feat[-back]
 # back to the previous sweep's last LM kernel
 i0 = i_feat
-while i0 > 0 and not any(s in rows[i0 - 1]["Kernel_Name"] for s in ("k_lm_step", "k_chol_back", "k_gather", "k_lin_fused")):
+while i0 > 0 and not any(s in rows[i0 - 1]["Kernel_Name"] for s in ("k_schur_bias_y_step", "k_chol_back", "k_gather", "k_lin_fused")):
     i0 -= 1
 i1 = i_feat
 while i1 < len(rows) and "k_pcr_init" not in rows[i1]["Kernel_Name"]:

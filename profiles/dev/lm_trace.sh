@@ -1,5 +1,5 @@
 #!/bin/bash
-# composition of one LM iteration under development options (round 6): gpurun -- 'bash profiles/dev/lm_trace.sh c4 "lm_back_chunks=1"'
+# composition of one LM iteration under development options (round 6), on a GPU box: bash profiles/dev/lm_trace.sh c4 "lm_dense=1"
 # $1: case (c4 | small | step), $2: option spec for profiles/dev/ab_lm.py, $3: iteration from the end (default 3)
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}

@@ -359,12 +359,18 @@ def test_batched_sweeps_equal_single_sweeps(gpu, oracle):
 
 def test_development_options_and_warmup(gpu, oracle):
     """wc_ctx_set_dev_option replaces the environment knobs of rounds 2 - 4 (nothing in the release library reads the environment to
-    decide what to execute): an unknown name is an argument error; both forms of the default path's node stage (fx_split 0 / 1) give the
-    oracle's surfels on the same cloud; wc_ctx_warmup can be called on a used context (and twice)"""
+    decide what to execute): an unknown name is an argument error, and so is the name of a retired window-solver form; every kept window
+    option is accepted; both forms of the default path's node stage (fx_split 0 / 1) give the oracle's surfels on the same cloud;
+    wc_ctx_warmup can be called on a used context (and twice)"""
     from wildcat_slam_amd import lib
 
-    with pytest.raises(lib.WildcatError):
-        gpu.set_dev_option("no_such_option", 1)
+    retired = ("lm_eval_pass", "lm_sync", "pcr_ahead", "pcr_full_width", "lm_back_chunks", "dbg_lm", "lin_imu_apart", "lin_unary_apart",
+               "lin_post_apart", "lin_pair", "lin_unary_chunks")
+    for name in ("no_such_option",) + retired:
+        with pytest.raises(lib.WildcatError):
+            gpu.set_dev_option(name, 1)
+    for name, default in (("exact_sums", 0), ("lm_dense", 0), ("lm_dense_radius", 10), ("lm_one_collective", 0), ("lm_side_stream", 1)):
+        gpu.set_dev_option(name, default)  # (the defaults: the shared context is left as it was)
     pts, _ = synth.g2_lattice(300, m=32)
     s_ref, id_ref, _ = oracle.extract_surfels(pts)
     try:

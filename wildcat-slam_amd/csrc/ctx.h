@@ -22,18 +22,11 @@ struct wc_buf {
 };
 
 // Knock-out bits of the extraction kernels (development option debug_skip) exist in a -DWC_DEV_KNOBS build only: the release kernels
-// carry no profiling branch; the same switch gates the compile-time instrumentation of window.hip
-// (WC_LIN_KNOCK, WC_GATHER_KNOCK, WC_PROF_LIN, WC_PROF_CHOL, WC_PCR_NOINV, WC_PCR_NOR).
+// carry no profiling branch.
 #ifdef WC_DEV_KNOBS
 #define WC_DBG(P, bit) ((P).dbg & (bit))
 #else
 #define WC_DBG(P, bit) 0
-#undef WC_LIN_KNOCK
-#undef WC_GATHER_KNOCK
-#undef WC_PROF_LIN
-#undef WC_PROF_CHOL
-#undef WC_PCR_NOINV
-#undef WC_PCR_NOR
 #endif
 
 // Development options of a context (wc_ctx_set_dev_option; include/wildcat_hip.h lists them).  They pin choices the library
@@ -54,18 +47,9 @@ struct wc_dev_opts {
   int match_pair_serial = 0; // wc_match_pair runs its searches one after the other on the ctx
   int match_pair_swap = 0;   // the sliding-window search on the helper instead of the fixed-window one
   int match_pair_hold = 1;   // wc_match_pair: the fixed-window search's walk waits for the sliding-window search's tree (match.hip: wc_pair_sync)
-  int lin_imu_apart = 0, lin_unary_apart = 0, lin_post_apart = 0;  // the linearisation's families / mailbox as launches of their own
   int lm_dense = 0;          // round 2's LM step: dense Cholesky of all 12 ns unknowns
-  int lin_pair = 1;          // binary assembly pieces of at most 128 records two to a workgroup (0: one each, rounds 2 - 5)
-  int lin_unary_chunks = 0;  // chunks of 256 records per unary piece (0: the library's 4; 1: rounds 2 - 5's pieces)
-  int pcr_full_width = 0;    // bias elimination: every reduction level over all columns of the right-hand sides (rounds 3 - 5) instead of their bands
   int lm_side_stream = 1;    // two-collective form: the large collective on a side stream (1: with the in-library RCCL binding; 0: never; 2: always - tests)
   int lm_one_collective = 0; // sharded windows: rounds 3 - 5's ONE all-reduce per linearisation (IMU triples sharded too) instead of the two-collective form
-  int dbg_lm = 0;            // experiment bits of the LM solve's kernels (timing runs of a development session; results may be WRONG)
-  int lm_back_chunks = 0;    // rounds 2 - 5's back substitution (chunk solves + products) and tail launches instead of k_back_mul + the fused tail
-  int lm_sync = 0;           // wait for the stream instead of the mailbox ticket
-  int lm_eval_pass = 0;      // a cost-only pass for the candidate instead of a linearisation
-  int pcr_ahead = 1;         // the bias elimination's level 0 of the NEXT iteration enqueued behind the candidate's linearisation (0: at the iteration's start)
   int lm_dense_radius = 10;  // iterations whose trust-region radius exceeds 10^value take the dense step (0: never)
 };
 // logging-only switches (they print; they never change a result): read once per process from the environment in every build

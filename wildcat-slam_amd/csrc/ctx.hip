@@ -74,20 +74,9 @@ const DevOpt kDevOpts[] = {
     {"match_pair_serial", "WC_MATCH_PAIR_SERIAL", &wc_dev_opts::match_pair_serial, true},
     {"match_pair_swap", "WC_MATCH_PAIR_SWAP", &wc_dev_opts::match_pair_swap, true},
     {"match_pair_hold", "WC_MATCH_PAIR_HOLD", &wc_dev_opts::match_pair_hold, false},
-    {"lin_imu_apart", "WC_LIN_IMU_APART", &wc_dev_opts::lin_imu_apart, true},
-    {"lin_unary_apart", "WC_LIN_UNARY_APART", &wc_dev_opts::lin_unary_apart, true},
-    {"lin_post_apart", "WC_LIN_POST_APART", &wc_dev_opts::lin_post_apart, true},
     {"lm_dense", "WC_LM_DENSE", &wc_dev_opts::lm_dense, true},
-    {"lm_back_chunks", "WC_LM_BACK_CHUNKS", &wc_dev_opts::lm_back_chunks, true},
-    {"dbg_lm", "WC_DBG_LM", &wc_dev_opts::dbg_lm, false},
     {"lm_one_collective", "WC_LM_ONE_COLLECTIVE", &wc_dev_opts::lm_one_collective, true},
     {"lm_side_stream", "WC_LM_SIDE_STREAM", &wc_dev_opts::lm_side_stream, false},
-    {"pcr_full_width", "WC_PCR_FULL_WIDTH", &wc_dev_opts::pcr_full_width, true},
-    {"lin_unary_chunks", "WC_LIN_UNARY_CHUNKS", &wc_dev_opts::lin_unary_chunks, false},
-    {"lin_pair", "WC_LIN_PAIR", &wc_dev_opts::lin_pair, false},
-    {"lm_sync", "WC_LM_SYNC", &wc_dev_opts::lm_sync, true},
-    {"lm_eval_pass", "WC_LM_EVAL_PASS", &wc_dev_opts::lm_eval_pass, true},
-    {"pcr_ahead", "WC_PCR_AHEAD", &wc_dev_opts::pcr_ahead, true},
     {"lm_dense_radius", "WC_LM_DENSE_RADIUS", &wc_dev_opts::lm_dense_radius, false},
 };
 }  // namespace

@@ -47,12 +47,8 @@ using namespace wc;
 
 namespace {
 
-#ifndef WC_PIECE
-#define WC_PIECE 256
-#endif
-constexpr int kPiece = WC_PIECE;   // records per piece (= threads per assembly workgroup)
+constexpr int kPiece = 256;   // records per piece (= threads per assembly workgroup)
 constexpr int kNB = 32;       // Cholesky block size
-constexpr int kLinChunksU = 4;  // chunks of kPiece records a unary piece may hold (round 6)
 constexpr uint32_t kHeavySrc = 24;  // block pairs with more gather sources than this get the multi-group gather
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -105,7 +101,6 @@ struct wc_window_state {
   // reach that far, cost_functor.h:264-355), 36 - the pose x pose corner - for the others (surfel factors only, :16-179)
   bool sharded = false;
   uint32_t npiece_b_big = 0;  // binary pieces of more than kPiece / 2 records (a prefix of the family): the others are paired in k_lin_fused
-  bool unary_multi = false;  // unary pieces hold several chunks of kPiece records: the family is a launch of its own (k_lin_surfel<12, true, true>)
   uint32_t lin_count = 0;  // linearisations enqueued in the two-collective form (parity of the late max |g| slot)
   // the large collective + k_expand_corners on a stream of their own, beside the bias elimination (ordered by events; joined in front of
   // whatever reads pose blocks or writes the buffers again)
@@ -496,7 +491,7 @@ __global__ void __launch_bounds__(1024) k_seg_heads(const uint32_t *keys, uint32
 // ---- assembly: one workgroup per piece ------------------------------------------------------------------------------
 // (tried: workgroups of 256 / 128 / 64 threads by the size of the piece - a third of C4's binary pieces holds <= 64 records.
 // No gain: phase A is bound by its fp64 arithmetic per WAVEFRONT, and a small piece already keeps only one wavefront busy.
-// Round 3, -DWC_PIECE=128: pieces of <= 128 records, 128 threads and half the LDS each, six workgroups per CU instead of
+// Round 3, pieces of <= 128 records, 128 threads and half the LDS each, six workgroups per CU instead of
 // three - 0.182 ms per linearisation at C4 against 0.178 with 256 (19 879 pieces against 12 299): not the pieces in flight
 // either.)
 // Phase A: thread k evaluates record k of the piece (residual + W-wide Jacobian row) into LDS (row k of V = [J r]).
@@ -535,12 +530,7 @@ __constant__ const LinTailTable<12> kLinTail12{};
 // until its round comes: 50 VGPRs) and the slices' partial blocks are folded in groups of NSH - a full piece took 53 KB, which
 // capped a CU at three pieces = 12 wavefronts of dependent fp64 chains (the kernel is bound by how many such
 // chains a CU interleaves, not by their instruction count).
-#ifndef WC_LIN_ROUNDS
-#define WC_LIN_ROUNDS 2
-#endif
-#ifndef WC_LIN_WG_PER_CU
-#define WC_LIN_WG_PER_CU 4
-#endif
+constexpr int kLinRounds = 2;     // rounds of a binary piece's rows through LDS
 template <int W>
 struct LinSurfelLds {
   static constexpr int T = W + 1;
@@ -548,27 +538,21 @@ struct LinSurfelLds {
   static constexpr int NBLK = NB * (NB + 1) / 2;    // blocks (bi <= bj) of the Gram matrix
   static constexpr int NS = kPiece / NBLK;          // record slices
   static constexpr int TS = T + (T & 1);            // row stride in LDS: even, so that a row's 4-column blocks are 16-byte aligned (ds_read_b128)
-#ifdef WC_LIN_RH
-  static constexpr int RH = W == 24 ? WC_LIN_RH : kPiece;  // rows per round
-#else
-  static constexpr int RND = W == 24 ? WC_LIN_ROUNDS : 1;  // rounds of rows through LDS
+  static constexpr int RND = W == 24 ? kLinRounds : 1;  // rounds of rows through LDS
   static constexpr int RH = kPiece / RND;           // rows per round
-#endif
   static constexpr int VSZ = RH * TS + 4;           // + 4: the padded columns of the last block read past the last row
   static constexpr int PB = 17;                     // doubles per partial block in LDS: 16 + 1 (a stride of 16 doubles puts every second lane on the same banks)
   // (four pieces per CU leave 40 KB each: the partial blocks of all slices fit - 34.3 KB - and are not folded; with V's 26.7 KB
   // as the budget, nine slices in folds of 7 + 2, the kernel took 4 us longer at C4: a barrier and a read-modify-write round more)
-#ifndef WC_LIN_LDS_DOUBLES
-#define WC_LIN_LDS_DOUBLES 4300
-#endif
-  static constexpr int BUD = WC_LIN_LDS_DOUBLES > VSZ ? WC_LIN_LDS_DOUBLES : VSZ;   // doubles the partial blocks may take
+  static constexpr int LDS_DOUBLES = 4300;
+  static constexpr int BUD = LDS_DOUBLES > VSZ ? LDS_DOUBLES : VSZ;   // doubles the partial blocks may take
   static constexpr int NSH = BUD / (NBLK * PB) > NS ? NS : BUD / (NBLK * PB);  // slices per fold of the partial blocks (they take V's storage)
   static_assert(NSH >= 1, "a fold of the partial blocks fits V's storage");
   static constexpr int PSZ = NSH * NBLK * PB;
   static constexpr int VMAX = VSZ > PSZ ? VSZ : PSZ;
   static constexpr int DOUBLES = VMAX + 4;
 };
-template <int W, bool UNARY, bool MULTI = false>
+template <int W, bool UNARY>
 __device__ __forceinline__ void lin_surfel_body(const WinParams &wp, const Piece pc, const double *rec, uint32_t nrec, const double *x,
                                                 double *partial, double *smem /* 16-byte aligned, LinSurfelLds<W>::DOUBLES */,
                                                 uint32_t cost_slot /* the piece's entry of the cost array behind the partials */) {
@@ -586,19 +570,7 @@ __device__ __forceinline__ void lin_surfel_body(const WinParams &wp, const Piece
 #pragma unroll
     for (int i = 0; i < NTE; ++i) toff[i] = tid + i * kPiece < NOUT ? (int)tail_off[tid + i * kPiece] : -1;
   }
-#if defined(WC_LIN_KNOCK) && (WC_LIN_KNOCK & 16)  // timing knock-out: the launch alone
-  if (pc.count < 100000) return;
-#endif
-#ifdef WC_PROF_LIN
-  long long lt_[6];
-  lt_[0] = clock64();
-#endif
   double c = 0.0;
-#ifdef WC_PROF_LIN
-  long long la_[4] = {0, 0, 0, 0};
-  asm volatile("" ::"s"(pc.count), "s"(pc.begin));
-  la_[0] = clock64();  // descriptor has arrived
-#endif
   double acc[4][4] = {{0.0}};
   const int blk = tid % NBLK, slice = tid / NBLK;
   int bi = 0, remb = blk;
@@ -608,63 +580,30 @@ __device__ __forceinline__ void lin_surfel_body(const WinParams &wp, const Piece
   }
   const int bj = bi + remb;
   const double *pi = sV + 4 * bi, *pj = sV + 4 * bj;
-  // Round 6: a piece may hold SEVERAL chunks of kPiece records (the unary family: up to kLinChunksU; a unary key of C4 has ~7.9 k
-  // records, i.e. 31 pieces of 256 with 31 descriptors, 31 exchanges of partial blocks, 31 tails and 31 gather sources for the same
-  // two sample blocks).  The workgroup evaluates a chunk, passes its rows through LDS, adds their Gram blocks onto the SAME register
-  // accumulators, and goes on with the next chunk: partial blocks, tail and output once per piece.
-  // (MULTI only in k_lin_surfel's unary instantiation, a launch of its own with the full register file: inside k_lin_fused - 128 VGPRs at
-  // four workgroups per CU - the loop spilled 50 - 170 registers and the kernel took 112 us instead of 87 at C4)
-  constexpr uint32_t kMaxCh = (UNARY && MULTI) ? (uint32_t)kLinChunksU : 1u;
-#pragma unroll 1
-  for (uint32_t chi = 0; chi < kMaxCh; ++chi) {
-  const uint32_t ch0 = chi * (uint32_t)kPiece;
-  if (chi && ch0 >= pc.count) break;
-  const int ccount = (int)min((uint32_t)kPiece, pc.count - ch0);  // records of this chunk (uniform over the workgroup)
-  if (chi) __syncthreads();  // (the rows of the chunk before have been read)
+  // (Round 6 tried unary pieces of up to four chunks of kPiece records, the chunks' Gram blocks added onto the same accumulators: fewer
+  // descriptors, partial blocks, tails and gather sources.  Inside k_lin_fused - 128 VGPRs at four workgroups per CU - the chunk loop
+  // spilled 50 - 170 registers, so the long pieces were a launch of their own, and that lost in the LM loop: 0.406 -> 0.417 ms per
+  // LM iteration at C4.  A piece is one chunk.)
+  const int ccount = (int)min((uint32_t)kPiece, pc.count);  // records of the piece (uniform over the workgroup)
   double v[W], r = 0.0;
   if (tid < ccount) {
-    const uint32_t k = pc.begin + ch0 + tid;
+    const uint32_t k = pc.begin + tid;
     constexpr int NF = UNARY ? 11 : 15;
     double rv[NF];
-#if defined(WC_LIN_KNOCK) && (WC_LIN_KNOCK & 4)  // timing knock-out: no record loads
-#pragma unroll
-    for (int f = 0; f < NF; ++f) rv[f] = 1e-3 * (double)(k + f);
-#else
 #pragma unroll
     for (int f = 0; f < NF; ++f) rv[f] = rec[(size_t)f * nrec + k];
-#endif
-#ifdef WC_PROF_LIN
-    asm volatile("" ::"v"(rv[0]), "v"(rv[NF - 1]), "v"(rv[5]));
-    la_[1] = clock64();  // records have arrived
-#endif
-#if defined(WC_LIN_KNOCK) && (WC_LIN_KNOCK & 2)  // timing knock-out: no evaluation (the loads stay)
-    for (int i = 0; i < W; ++i) v[i] = rv[i % NF];
-    r = rv[1], c = rv[2];
-#else
-    double cc_ = 0.0;  // (a thread's costs of all chunks are added in chunk order)
-    // (the sample blocks' corrections are read again in every chunk: hoisted out of the chunk loop the compiler kept their 24 doubles
-    // in VGPRs across it and spilled ~18 of them - k_lin_fused 87 -> 112 us at C4; the pointer is made opaque per chunk)
-    const double *xq = x;
+    double cc_ = 0.0;
     if (UNARY)
-      eval_unary(wp, rv, 1, 0, pc.key, xq, r, cc_, v);  // one key per piece: the sample blocks are wave-uniform
+      eval_unary(wp, rv, 1, 0, pc.key, x, r, cc_, v);  // one key per piece: the sample blocks are wave-uniform
     else
-      eval_binary(wp, rv, 1, 0, pc.key, xq, r, cc_, v);
+      eval_binary(wp, rv, 1, 0, pc.key, x, r, cc_, v);
     c += cc_;
-#endif
   }
-#ifdef WC_PROF_LIN
-  lt_[1] = clock64();
-  lt_[2] = lt_[1];
-#endif
-  // the rows go through LDS in rounds of RH (the chunk's count is uniform over the workgroup: so are the rounds and their barriers)
+  // the rows go through LDS in rounds of RH (the piece's count is uniform over the workgroup: so are the rounds and their barriers)
 #pragma unroll 1
   for (int h = 0; h * RH < ccount; ++h) {
     if (h) __syncthreads();  // the round before has been read
-#if defined(WC_LIN_KNOCK) && (WC_LIN_KNOCK & 32)  // timing knock-out: no row writes
-    if (tid < ccount && tid / RH == h && v[0] == 12345.0) {
-#else
     if (tid < ccount && tid / RH == h) {
-#endif
       const int row = tid - h * RH;
 #pragma unroll
       for (int i = 0; i < W; ++i) sV[row * TS + i] = v[i];
@@ -676,11 +615,7 @@ __device__ __forceinline__ void lin_surfel_body(const WinParams &wp, const Piece
       // row, to unwritten storage): those products land in accumulator entries that are never read
       const int cnt = min(ccount - h * RH, RH);
       const int sl = ((cnt + NS - 1) / NS) | 1;  // odd: the slices that share a wavefront then start on different banks
-#if defined(WC_LIN_KNOCK) && (WC_LIN_KNOCK & 1)  // timing knock-out: no Gram loop
-      const int k0 = min(slice * sl, cnt), k1 = min(k0 + 1, cnt);
-#else
       const int k0 = min(slice * sl, cnt), k1 = min(k0 + sl, cnt);
-#endif
       for (int k = k0; k < k1; ++k) {
         double a[4], c4[4];
         {
@@ -696,17 +631,10 @@ __device__ __forceinline__ void lin_surfel_body(const WinParams &wp, const Piece
       }
     }
   }
-  }  // (chunks)
   // cost of the piece: fixed shuffle tree per wavefront, the four wavefront sums are added in the tail
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) c += __shfl_down(c, d, 64);
   if ((tid & 63) == 0) sC[tid >> 6] = c;
-#ifdef WC_PROF_LIN
-  lt_[3] = clock64();
-#endif
-#if defined(WC_LIN_KNOCK) && (WC_LIN_KNOCK & 64)  // timing knock-out: no partial blocks, no tail
-  if (acc[0][0] != 12345.0) return;
-#endif
   // everybody is done with V: its storage takes the partial blocks, NSH slices at a time (slice s is added onto slot s % NSH in
   // the order of s: fixed, bitwise reproducible)
 #pragma unroll 1
@@ -721,18 +649,13 @@ __device__ __forceinline__ void lin_surfel_body(const WinParams &wp, const Piece
     }
   }
   __syncthreads();
-#if defined(WC_LIN_KNOCK) && (WC_LIN_KNOCK & 8)  // timing knock-out: one output entry per piece
-  for (int i = 0; i < 1; ++i) {
-    const int e = tid + i * kPiece, off = e < 1 ? toff[i] : -1;
-#else
 #pragma unroll
   for (int i = 0; i < NTE; ++i) {
     const int e = tid + i * kPiece, off = toff[i];
-#endif
     if (off < 0) continue;
     double out = 0.0;
     if (off == 0xFFFF) {
-      out = kPiece == 256 ? (sC[0] + sC[1]) + (sC[2] + sC[3]) : kPiece == 128 ? sC[0] + sC[1] : sC[0];
+      out = (sC[0] + sC[1]) + (sC[2] + sC[3]);
       partial[cost_slot] = out;  // (k_gather's cost workgroup reads the costs as ONE contiguous array)
     } else {
 #pragma unroll
@@ -740,13 +663,6 @@ __device__ __forceinline__ void lin_surfel_body(const WinParams &wp, const Piece
     }
     partial[pc.part_off + e] = out;
   }
-#ifdef WC_PROF_LIN
-  lt_[4] = clock64();
-  if (tid == 0 && (blockIdx.x % 997) == 500)
-    printf("lin W=%d blk %u count %u: A %lld (descriptor %lld records %lld evaluate %lld) sync %lld B %lld tail %lld total %lld\n", W, blockIdx.x,
-           pc.count, lt_[1] - lt_[0], la_[0] - lt_[0], la_[1] - la_[0], lt_[1] - la_[1], lt_[2] - lt_[1], lt_[3] - lt_[2], lt_[4] - lt_[3],
-           lt_[4] - lt_[0]);
-#endif
 }
 // Round 6: TWO binary pieces of at most 128 records each in one workgroup.  A binary key of C4 holds ~125 records: as a
 // piece of its own it keeps half a workgroup idle through the evaluation and pays a descriptor round trip and a launch slot for it.  Here
@@ -761,7 +677,7 @@ __device__ __forceinline__ void lin_binary_pair_body(const WinParams &wp, const 
   constexpr int W = 24;
   using L = LinSurfelLds<W>;
   constexpr int T = L::T, NB = L::NB, NBLK = L::NBLK, NS = L::NS, TS = L::TS, PB = L::PB, RH = L::RH, NSH = L::NSH;
-  static_assert(RH == kPiece / 2 && kPiece == 256, "a piece of the pair is one round of rows");
+  static_assert(RH == kPiece / 2, "a piece of the pair is one round of rows");
   double *sV = smem, *sC = smem + L::VMAX;
   const int tid = threadIdx.x;
   constexpr int NOUT = T * (T + 1) / 2, NTE = (NOUT + kPiece - 1) / kPiece;
@@ -852,11 +768,11 @@ __device__ __forceinline__ void lin_binary_pair_body(const WinParams &wp, const 
   }
 }
 
-template <int W, bool UNARY, bool MULTI = false>
+template <int W, bool UNARY>
 __global__ void __launch_bounds__(kPiece) k_lin_surfel(WinParams wp, const Piece *pieces, const double *rec, const uint32_t *keys,
                                                       uint32_t nrec, const double *x, double *partial, uint32_t cost_slot0) {
   __shared__ __attribute__((aligned(16))) double smem[LinSurfelLds<W>::DOUBLES];
-  lin_surfel_body<W, UNARY, MULTI>(wp, pieces[blockIdx.x], rec, nrec, x, partial, smem, cost_slot0 + blockIdx.x);
+  lin_surfel_body<W, UNARY>(wp, pieces[blockIdx.x], rec, nrec, x, partial, smem, cost_slot0 + blockIdx.x);
 }
 
 using f64x4 = __attribute__((ext_vector_type(4))) double;
@@ -972,7 +888,6 @@ __global__ void __launch_bounds__(256) k_lin_imu(WinParams wp, const Piece *piec
 // launch 0.177 -> 0.166 - 0.172 ms per linearisation at C4 (1 775 -> 1 795 - 1 820 LM it/s), odometry-step solve 2.42 -> 2.30 ms;
 // the unary pieces inside too (at the binary pieces' LDS: three workgroups per CU instead of four, but no drain between the
 // families): solve 2.30 -> 2.25 ms, C4 unchanged.
-// (k_lin_imu's workgroups have 256 threads: with -DWC_PIECE below 256, an experiment, the families are launches of their own)
 // OCC = workgroups per CU the register budget is cut for: 4 (128 VGPRs - the IMU body, a latency chain of a few hundred workgroups,
 // then spills 47 registers) when the surfel pieces outnumber the chip's workgroup slots, 3 (168 VGPRs, no spills) for the small windows
 // of a real stream, where the IMU chain IS the kernel (facade: 15.7 -> 13.5 us)
@@ -1149,9 +1064,6 @@ __global__ void __launch_bounds__(144 * kGG, 8) k_gather(GatherArgs a) {
     // kept 108 lanes idle on them and wrote the 108 zeros of the rest of the block (and of its mirror) on every linearisation: three
     // quarters of H's 18.6 MB at C4.  Those entries are zero from the build (window_build_impl clears both linearisation buffers)
     // and nobody writes them.  Sources in list order, as everywhere.
-#ifdef WC_GATHER_KNOCK
-    if (WC_GATHER_KNOCK & 2) return;
-#endif
     if (a.only == 2) return;  // (far pairs have surfel sources only)
     const int grp = tid / 36, e = tid % 36, u = e / 6, v = e % 6;
     const uint2 *src2 = (const uint2 *)a.src;
@@ -1216,10 +1128,6 @@ __global__ void __launch_bounds__(144 * kGG, 8) k_gather(GatherArgs a) {
   if (blk >= a.nheavy + nlight) blk -= nfarwg;
   if (blk < a.nheavy + nlight) {
     const bool heavy = blk < a.nheavy;
-#ifdef WC_GATHER_KNOCK  // timing knock-outs (results wrong on purpose): 1 no heavy pairs, 2 no light pairs, 4 no g, 8 no cost
-    if ((WC_GATHER_KNOCK & 1) && heavy) return;
-    if ((WC_GATHER_KNOCK & 2) && !heavy) return;
-#endif
     const int grp = tid / 144, e = tid % 144;
     const int u = e / 12, v = e % 12;
     const uint32_t want_w = a.only == 1 ? 6u : (a.only == 2 ? 12u : 0u);
@@ -1343,16 +1251,6 @@ __global__ void __launch_bounds__(144 * kGG, 8) k_gather(GatherArgs a) {
     return;
   }
   blk -= a.nheavy + nlight;
-#ifdef WC_GATHER_KNOCK
-  if ((WC_GATHER_KNOCK & 4) && blk < (uint32_t)a.ns) {
-    if (a.post) gather_post(a, 0.0);
-    return;
-  }
-  if ((WC_GATHER_KNOCK & 8) && blk >= (uint32_t)a.ns) {
-    if (a.post) gather_post(a, 0.0);
-    return;
-  }
-#endif
   if (blk < (uint32_t)a.ns) {  // g = J^T r of sample block blk
     // all 84 groups of 12 lanes stride over the block's source list (~320 sources: one trip of four each)
     constexpr int NGg = 144 * kGG / 12;
@@ -2004,21 +1902,12 @@ __global__ void __launch_bounds__(256) k_damp_first(const double *H, const doubl
   A[(size_t)i * ld + j] = damped_entry(H, g, scale, n, radius, i, j, diag);
 }
 
-#ifdef WC_PROF_CHOL  // -DWC_PROF_CHOL: phase timers of the lead tile (the critical path of the factorisation), printed at step 20
-#define WC_CT(i) ct_[i] = clock64()
-#else
-#define WC_CT(i)
-#endif
 // Lead workgroup of a step (see k_chol_step): L rows of the next diagonal block, its trailing update, factor + inverse.
 // sP: panel rows of the block, later L^-1 of the block; sXk: L_kk^-1; sD: old diagonal block -> updated -> L; sL: the
 // block's rows of L (panel solve).  The four arrays alias the tile path's LDS (two workgroups per CU stay resident).
 __device__ __forceinline__ void chol_lead(const double *A, int ld, int k, int nblk, double *Lmat, double *Linv, int *fail,
                                           double (*sP)[kNB + 1], double (*sXk)[kNB + 1], double (*sD)[kNB + 1],
                                           double (*sL)[kNB + 1]) {
-#ifdef WC_PROF_CHOL
-  long long ct_[8];
-#endif
-  WC_CT(0);
   const int tid = threadIdx.x;
   const int first = (k + 1) * kNB;
   const size_t pc = (size_t)k * kNB;
@@ -2031,7 +1920,6 @@ __device__ __forceinline__ void chol_lead(const double *A, int ld, int k, int nb
     sD[r][c] = A[(size_t)(first + r) * ld + first + (c <= r ? c : r)];
   }
   __syncthreads();
-  WC_CT(1);
   if (failed) return;
   const int w = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
   const int rt = w >> 1, ct = w & 1;  // wavefront = one 16 x 16 tile of the 32 x 32 block
@@ -2044,7 +1932,6 @@ __device__ __forceinline__ void chol_lead(const double *A, int ld, int k, int nb
     for (int r4 = 0; r4 < 4; ++r4) sL[16 * rt + lk + 4 * r4][16 * ct + li] = t[r4];
   }
   __syncthreads();
-  WC_CT(2);
   {
     f64x4 t = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -2054,15 +1941,8 @@ __device__ __forceinline__ void chol_lead(const double *A, int ld, int k, int nb
     for (int r4 = 0; r4 < 4; ++r4) sD[16 * rt + lk + 4 * r4][16 * ct + li] -= t[r4];
   }
   __syncthreads();
-  WC_CT(3);
   const bool ok = factor_inv32_roles(sD, sP);  // in: lower part of sD; out: sD = L, sP = L^-1
   __syncthreads();
-  WC_CT(4);
-#ifdef WC_PROF_CHOL
-  if (tid == 0 && k == 20)
-    printf("chol step 20, lead workgroup, shader clocks: loads %lld trsm %lld update %lld factor %lld\n", ct_[1] - ct_[0], ct_[2] - ct_[1],
-           ct_[3] - ct_[2], ct_[4] - ct_[3]);
-#endif
   if (tid == 0 && !ok) atomicOr(fail, 1);
   for (int e = tid; e < kNB * kNB; e += 256) {
     const int r = e / kNB, c = e % kNB;
@@ -2080,8 +1960,7 @@ __device__ __forceinline__ void chol_lead(const double *A, int ld, int k, int nb
 // workgroup's chain); k_back_mul then forms y = L^-T z - one launch of ~5 us for the three chunk solves + two products (52 us at 127
 // sample states, 25 at 64) of rounds 2 - 5, whose block rows were a chain of 1.8 us steps through one compute unit.
 __device__ __forceinline__ void chol_extra_tile(double *A, int ld, int k, int nblk, double *Lmat, const double *Linv, const int *fail, int te, int tj,
-                                                double (*sA)[kNB + 1], double (*sLi)[kNB + 1], double (*sLj)[kNB + 1], double (*sX)[kNB + 1], int dbg) {
-  if (dbg & 1) return;
+                                                double (*sA)[kNB + 1], double (*sLi)[kNB + 1], double (*sLj)[kNB + 1], double (*sX)[kNB + 1]) {
   const int tid = threadIdx.x;
   const int w = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
   const int nrow = nblk * kNB, first = (k + 1) * kNB;
@@ -2095,7 +1974,7 @@ __device__ __forceinline__ void chol_extra_tile(double *A, int ld, int k, int nb
 #pragma unroll
     for (int r4 = 0; r4 < 4; ++r4) {
       const int re = re0 + 16 * w + lk + 4 * r4, c = col0 + 16 * tq + li;
-      const bool in = re < oldlim && c < nrow && !(dbg & 2);
+      const bool in = re < oldlim && c < nrow;
       const double v = A[in ? (size_t)(nrow + re) * ld + c : (size_t)first * ld + first];
       old[tq][r4] = in ? v : 0.0;
     }
@@ -2170,35 +2049,21 @@ __device__ __forceinline__ void chol_extra_tile(double *A, int ld, int k, int nb
 #pragma unroll
     for (int r4 = 0; r4 < 4; ++r4) {
       const int re = re0 + 16 * w + lk + 4 * r4, c = col0 + 16 * tq + li;
-      if (re < act && c < nrow && !(dbg & 4)) A[(size_t)(nrow + re) * ld + c] = old[tq][r4] - acc[tq][r4];
+      if (re < act && c < nrow) A[(size_t)(nrow + re) * ld + c] = old[tq][r4] - acc[tq][r4];
     }
 }
 
 // n_tri: workgroups of the factorisation proper (1 + tiles (tiles + 1) / 2); the grid's remaining workgroups are tiles of the appended
 // identity rows (chol_extra_tile), `tiles` per tile row
 __global__ void __launch_bounds__(256) k_chol_step(double *A, int ld, int k, int nblk, double *Lmat, double *Linv, int *fail, int n_real, int n_tri,
-                                                   int tiles, int dbg_in = 0, long long *dbgbuf = nullptr) {
-#ifdef WC_DEV_KNOBS  // (development option dbg_lm: per-workgroup wall-clock stamps (8), phase clocks of one tile (16), knock-outs of the appended tiles (1, 2, 4))
-  const int dbg = dbg_in;
-#else
-  constexpr int dbg = 0;  // (the release kernel carries none of it)
-#endif
-  struct Stamp {
-    long long *p;
-    __device__ Stamp(long long *q) : p(q) {
-      if (p && threadIdx.x == 0) p[0] = wall_clock64();
-    }
-    __device__ ~Stamp() {
-      if (p && threadIdx.x == 0) p[1] = wall_clock64();
-    }
-  } stamp_((dbg & 8) ? dbgbuf + ((size_t)k * 512 + blockIdx.x) * 2 : nullptr);
+                                                   int tiles) {
   __shared__ double sA[64][kNB + 1];
   __shared__ double sLi[64][kNB + 1];
   __shared__ double sLj[64][kNB + 1];
   __shared__ double sX[kNB][kNB + 1];
   if ((int)blockIdx.x >= n_tri) {
     const int x = (int)blockIdx.x - n_tri;
-    chol_extra_tile(A, ld, k, nblk, Lmat, Linv, fail, x / tiles, x % tiles, sA, sLi, sLj, sX, dbg);
+    chol_extra_tile(A, ld, k, nblk, Lmat, Linv, fail, x / tiles, x % tiles, sA, sLi, sLj, sX);
     return;
   }
   // row 0 of the grid holds the lead workgroup (x == 0): the critical path of the factorisation.  It redoes the 32 x 32
@@ -2216,7 +2081,6 @@ __global__ void __launch_bounds__(256) k_chol_step(double *A, int ld, int k, int
     chol_lead(A, ld, k, nblk, Lmat, Linv, fail, sA, sX, sLi, sLj);
     return;
   }
-  const long long t_start_ = clock64();
   const int b_ = (int)blockIdx.x - 1;
   int ti = (int)((sqrtf(8.0f * (float)b_ + 1.0f) - 1.0f) * 0.5f);
   while ((ti + 1) * (ti + 2) / 2 <= b_) ++ti;
@@ -2275,9 +2139,6 @@ __global__ void __launch_bounds__(256) k_chol_step(double *A, int ld, int k, int
     }
   }
   __syncthreads();
-  long long pc_[6];
-  const bool prof_ = (dbg & 16) && b_ == 1 && k == 5;
-  if (prof_) pc_[0] = clock64();
   if (failed) return;
   // The two small GEMMs of a tile run on the fp64 matrix cores: v_mfma_f64_16x16x4 takes A[i = l & 15][k = l >> 4] and
   // B[k = l >> 4][j = l & 15] as ONE double per lane, i.e. one LDS read per lane feeds 16 x 16 x 4 products; the scalar
@@ -2304,7 +2165,6 @@ __global__ void __launch_bounds__(256) k_chol_step(double *A, int ld, int k, int
     }
   }
   __syncthreads();
-  if (prof_) pc_[1] = clock64();
   if (ti != tj) {  // the tile's columns: their panel rows were staged in sLj with the first loads; solved in place (a
                    // wavefront reads and writes only its own 16 rows, and writes after its last read)
     f64x4 t0 = {0.0, 0.0, 0.0, 0.0}, t1 = {0.0, 0.0, 0.0, 0.0};
@@ -2323,7 +2183,6 @@ __global__ void __launch_bounds__(256) k_chol_step(double *A, int ld, int k, int
     for (int e = tid; e < 64 * kNB; e += 256) sLj[e / kNB][e % kNB] = sLi[e / kNB][e % kNB];
   }
   __syncthreads();
-  if (prof_) pc_[2] = clock64();
   // trailing update of this tile: A_ij -= Li Lj^T (64 x 64, K = 32)
   f64x4 acc[4];
 #pragma unroll
@@ -2334,7 +2193,6 @@ __global__ void __launch_bounds__(256) k_chol_step(double *A, int ld, int k, int
 #pragma unroll
     for (int tq = 0; tq < 4; ++tq) acc[tq] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, sLj[16 * tq + li][4 * ks + lk], acc[tq], 0, 0, 0);
   }
-  if (prof_) pc_[3] = clock64();
   const bool corner = (ti == 0 && tj == 0);  // the next diagonal block belongs to the lead workgroup (which reads its old values)
 #pragma unroll
   for (int tq = 0; tq < 4; ++tq)
@@ -2344,14 +2202,6 @@ __global__ void __launch_bounds__(256) k_chol_step(double *A, int ld, int k, int
       const int r = row0 + rl, c = col0 + cl;
       if (r < nrow && c <= r && !(corner && rl < kNB)) A[(size_t)r * ld + c] = old[tq][r4] - acc[tq][r4];
     }
-  if (prof_) {
-    pc_[4] = clock64();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    pc_[5] = clock64();
-    if (tid == 0)
-      printf("tile (1,0) step 5, shader clocks from the first barrier: Li %lld  Lj %lld  update %lld  stores issued %lld  stores done %lld ; kernel start -> first barrier %lld\n",
-             pc_[1] - pc_[0], pc_[2] - pc_[1], pc_[3] - pc_[2], pc_[4] - pc_[3], pc_[5] - pc_[4], pc_[0] - t_start_);
-  }
 }
 
 // workgroup barrier that only waits for this wavefront's LDS traffic: __syncthreads() also drains the outstanding global
@@ -2816,10 +2666,10 @@ static int window_build_impl(wc_ctx *ctx, const wc_surfel *d_sld_surf, const wc_
   auto t_b = tnow();
   // pieces + the CSR source lists of the gather
   uint32_t off = 0;
-  auto cut = [&](const std::vector<Seg> &segs, uint32_t T, bool split, uint32_t piece_max = kPiece) {
+  auto cut = [&](const std::vector<Seg> &segs, uint32_t T, bool split) {
     for (const Seg &s : segs) {
-      for (uint32_t b = 0; b < s.count; b += split ? piece_max : s.count) {
-        const uint32_t c = split ? std::min<uint32_t>(piece_max, s.count - b) : s.count;
+      for (uint32_t b = 0; b < s.count; b += split ? (uint32_t)kPiece : s.count) {
+        const uint32_t c = split ? std::min<uint32_t>(kPiece, s.count - b) : s.count;
         pieces.push_back({s.start + b, c, s.key, off});
         off += T * (T + 1) / 2;
       }
@@ -2827,12 +2677,13 @@ static int window_build_impl(wc_ctx *ctx, const wc_surfel *d_sld_surf, const wc_
   };
   // (longest pieces first inside a family: workgroups are dispatched in piece order, and a full piece started last would
   // run alone at the end of the launch)
-  auto by_size = [&](size_t first, uint32_t piece_max = kPiece) {  // stable counting sort of pieces[first..) by count, descending (counts are 1..piece_max)
-    std::vector<uint32_t> pos(piece_max + 2, 0);
-    for (size_t i = first; i < pieces.size(); ++i) pos[piece_max - pieces[i].count + 1]++;
-    for (uint32_t c = 0; c <= piece_max; ++c) pos[c + 1] += pos[c];
+  auto by_size = [&](size_t first) {  // stable counting sort of pieces[first..) by count, descending (counts are 1..kPiece)
+    constexpr uint32_t pmax = kPiece;
+    std::vector<uint32_t> pos(pmax + 2, 0);
+    for (size_t i = first; i < pieces.size(); ++i) pos[pmax - pieces[i].count + 1]++;
+    for (uint32_t c = 0; c <= pmax; ++c) pos[c + 1] += pos[c];
     std::vector<Piece> out(pieces.size() - first);
-    for (size_t i = first; i < pieces.size(); ++i) out[pos[piece_max - pieces[i].count]++] = pieces[i];
+    for (size_t i = first; i < pieces.size(); ++i) out[pos[pmax - pieces[i].count]++] = pieces[i];
     std::copy(out.begin(), out.end(), pieces.begin() + first);
   };
   WC_TRY(collect_families(ctx, job, segs_b, segs_u));
@@ -2860,26 +2711,12 @@ static int window_build_impl(wc_ctx *ctx, const wc_surfel *d_sld_surf, const wc_
       for (int q = p; q < nblk; ++q) src_begin[pair_id(blk[p], blk[q]) + 1]++;
     }
   }
-  // (unary pieces of up to kLinChunksU chunks of kPiece records - lin_surfel_body; development option lin_unary_chunks: 1 = rounds 2 - 5's
-  // pieces of one chunk)
-  // Measured (profiles/dev/ab_lin2.py, device time of one linearisation): C4's 12 299 pieces 0.124 -> 0.110 ms with four chunks (9 329
-  // pieces; two chunks 0.115, eight 0.118: a piece of 2 048 records is the launch's tail), the step-sized window's 3 492 pieces 0.044
-  // either way, a window of 1 336 pieces 0.0230 -> 0.0238: the long pieces are for windows whose launch is several rounds of the chip's
-  // workgroup slots.
-  uint32_t nrec_u = 0;
-  for (const Seg &sg : segs_u) nrec_u += sg.count;
-  const bool many = pieces.size() + nrec_u / kPiece > 6000u;
-  // In the LM loop (x != 0, the solve's kernels between two linearisations) the long pieces LOSE: they only fit the register file as a launch
-  // of their own (k_lin_surfel<12, true, true>; inside k_lin_fused the chunk loop spilled), and k_lin_fused without the unary family +
-  // that launch last 99 us + a boundary against 87 fused - C4 0.406 -> 0.417 ms per LM iteration.  Default: one chunk; the option keeps
-  // the long pieces for A/B runs.
-  (void)many;
-  const int want_ch = ctx->dev.lin_unary_chunks > 0 ? ctx->dev.lin_unary_chunks : 1;
-  const uint32_t upiece = (uint32_t)kPiece * (uint32_t)std::max(1, std::min(kLinChunksU, want_ch));
-  W->unary_multi = upiece > (uint32_t)kPiece;
-  cut(segs_u, 13, true, upiece);
+  // (unary pieces of one chunk of kPiece records: round 6 measured pieces of up to four chunks - profiles/dev/ab_lin2.py, device time of
+  // one linearisation: C4's 12 299 pieces 0.124 -> 0.110 ms with four chunks (9 329 pieces), the step-sized window's 3 492 pieces 0.044
+  // either way - but they lost in the LM loop, see lin_surfel_body)
+  cut(segs_u, 13, true);
   W->npiece_u = (uint32_t)pieces.size() - W->npiece_b;
-  by_size(W->npiece_b, upiece);
+  by_size(W->npiece_b);
   cut(segs_i, 37, false);
   W->npiece_i = (uint32_t)pieces.size() - W->npiece_b - W->npiece_u;
   W->npart_doubles = off;
@@ -3189,6 +3026,9 @@ __global__ void __launch_bounds__(1024) k_post_reduce(const double *g, const dou
 bool multi_gpu(const wc_ctx *ctx, const wc_window_state *W) {
   return W->allreduce != nullptr || (W->sharded && ctx->have_comm && ctx->comm.world > 1 && ctx->comm.allreduce_f64 != nullptr);
 }
+// the two-collective form: the window was sharded by wc_window_build_sharded with the IMU factors replicated, and the ctx's
+// communicator reduces it
+inline bool two_collectives(const wc_ctx *ctx, const wc_window_state *W) { return multi_gpu(ctx, W) && W->two_coll && !W->allreduce; }
 int do_allreduce(wc_ctx *ctx, wc_window_state *W, double *d_buf, size_t count) {
   if (W->allreduce) {
     WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -3210,8 +3050,8 @@ int join_side(wc_ctx *ctx, wc_window_state *W) {
 }
 
 // all kernels of one linearisation at x (device): partials -> H, g ; cost -> mail[slot], max|g| -> mail[slot+1]
-int enqueue_linearize(wc_ctx *ctx, wc_window_state *W, const double *d_x, int mail_slot, bool post = true, bool other = false,
-                      double *host_mail = nullptr, unsigned long long ticket = 0) {
+int enqueue_linearize(wc_ctx *ctx, wc_window_state *W, const double *d_x, int mail_slot, bool other = false, double *host_mail = nullptr,
+                      unsigned long long ticket = 0) {
   hipStream_t st = ctx->stream;
   WC_TRY(join_side(ctx, W));  // (the reduction buffer and the linearisation buffers are written again below)
   const Piece *pcs = (const Piece *)W->pieces.p;
@@ -3219,46 +3059,32 @@ int enqueue_linearize(wc_ctx *ctx, wc_window_state *W, const double *d_x, int ma
   // (Round 3, tried: k_lin_imu - 14.5 us of dependent fp64 chains in a few hundred workgroups - on a stream of its own beside the
   // surfel families, fork / join by events: 1 650 LM it/s against 1 790 at C4, odometry-step solve 2.58 against 2.39 ms - the two
   // cross-stream waits cost more than the launch they hide.  One stream.)
-  const bool imu_apart = ctx->dev.lin_imu_apart != 0;  // (A/B: the IMU family as a launch of its own)
-  const bool unary_in = ctx->dev.lin_unary_apart == 0 && !W->unary_multi;  // (A/B: the unary family as a launch of its own; multi-chunk pieces: always)
-  const bool fused = W->npiece_b && W->npiece_i && !imu_apart && kPiece == 256;
-  const bool fused_u = fused && unary_in && W->npiece_u;
-#ifndef WC_LIN_FEW
-#define WC_LIN_FEW (6u * 256u)  // two rounds of the chip's slots at three per CU (facade, 244 linearisations: 13.4 us on average with OCC = 4 throughout, 12.2 with 768, 11.9 - 12.4 with 1 536 / 3 072; the step's 2 989 pieces: 26.8 us with OCC = 4, 29.1 with 3)
-#endif
-  const bool few = W->npiece_b + W->npiece_u <= WC_LIN_FEW;
-  // (binary pieces of at most 128 records go two to a workgroup - lin_binary_pair_body; development option lin_pair = 0: one each)
-  const uint32_t n_big = ctx->dev.lin_pair != 0 ? W->npiece_b_big : W->npiece_b;
-  const uint32_t n_bwg = n_big + (W->npiece_b - n_big + 1u) / 2u;
-  auto fused_launch = [&](auto kern, uint32_t grid) {
-    kern<<<grid, 256, 0, st>>>(W->wp, pcs, W->npiece_i, W->npiece_b, W->npiece_u, (const double *)W->brec.p, W->nb, (const double *)W->urec.p, W->nu,
-                               (const ImuRec *)W->irec.p, (const double *)W->times_d.p, d_x, partial, W->npart_doubles, n_big, n_bwg);
-  };
-  if (fused_u) {
-    if (few)
-      fused_launch(k_lin_fused<true, 3>, W->npiece_i + n_bwg + W->npiece_u);
+  if (W->npiece_b && W->npiece_i) {  // every family in one launch (k_lin_fused)
+    // OCC = 3 up to kFew surfel pieces: two rounds of the chip's slots at three per CU (facade, 244 linearisations: 13.4 us on average
+    // with OCC = 4 throughout, 12.2 with kFew = 768, 11.9 - 12.4 with 1 536 / 3 072; the step's 2 989 pieces: 26.8 us with OCC = 4, 29.1 with 3)
+    constexpr uint32_t kFew = 6u * 256u;
+    const bool few = W->npiece_b + W->npiece_u <= kFew;
+    // (binary pieces of at most 128 records go two to a workgroup - lin_binary_pair_body)
+    const uint32_t n_big = W->npiece_b_big, n_bwg = n_big + (W->npiece_b - n_big + 1u) / 2u;
+    auto fused_launch = [&](auto kern, uint32_t grid) {
+      kern<<<grid, 256, 0, st>>>(W->wp, pcs, W->npiece_i, W->npiece_b, W->npiece_u, (const double *)W->brec.p, W->nb, (const double *)W->urec.p,
+                                 W->nu, (const ImuRec *)W->irec.p, (const double *)W->times_d.p, d_x, partial, W->npart_doubles, n_big, n_bwg);
+    };
+    if (W->npiece_u)
+      fused_launch(few ? k_lin_fused<true, 3> : k_lin_fused<true, 4>, W->npiece_i + n_bwg + W->npiece_u);
     else
-      fused_launch(k_lin_fused<true, WC_LIN_WG_PER_CU>, W->npiece_i + n_bwg + W->npiece_u);
-  } else if (fused) {
-    if (few)
-      fused_launch(k_lin_fused<false, 3>, W->npiece_i + n_bwg);
-    else
-      fused_launch(k_lin_fused<false, WC_LIN_WG_PER_CU>, W->npiece_i + n_bwg);
-  }
-  else if (W->npiece_b)
-    k_lin_surfel<24, false><<<W->npiece_b, kPiece, 0, st>>>(W->wp, pcs, (const double *)W->brec.p, (const uint32_t *)W->bkey.p, W->nb,
-                                                          d_x, partial, W->npart_doubles);
-  if (W->npiece_u && !fused_u) {
-    if (W->unary_multi)
-      k_lin_surfel<12, true, true><<<W->npiece_u, kPiece, 0, st>>>(W->wp, pcs + W->npiece_b, (const double *)W->urec.p,
-                                                                 (const uint32_t *)W->ukey.p, W->nu, d_x, partial, W->npart_doubles + W->npiece_b);
-    else
+      fused_launch(few ? k_lin_fused<false, 3> : k_lin_fused<false, 4>, W->npiece_i + n_bwg);
+  } else {  // a window without binary or without IMU pieces: a launch per family
+    if (W->npiece_b)
+      k_lin_surfel<24, false><<<W->npiece_b, kPiece, 0, st>>>(W->wp, pcs, (const double *)W->brec.p, (const uint32_t *)W->bkey.p, W->nb,
+                                                            d_x, partial, W->npart_doubles);
+    if (W->npiece_u)
       k_lin_surfel<12, true><<<W->npiece_u, kPiece, 0, st>>>(W->wp, pcs + W->npiece_b, (const double *)W->urec.p,
                                                            (const uint32_t *)W->ukey.p, W->nu, d_x, partial, W->npart_doubles + W->npiece_b);
+    if (W->npiece_i)
+      k_lin_imu<<<W->npiece_i, 256, 0, st>>>(W->wp, pcs + W->npiece_b + W->npiece_u, (const ImuRec *)W->irec.p, d_x,
+                                            (const double *)W->times_d.p, partial, W->npart_doubles + W->npiece_b + W->npiece_u);
   }
-  if (W->npiece_i && !fused)
-    k_lin_imu<<<W->npiece_i, 256, 0, st>>>(W->wp, pcs + W->npiece_b + W->npiece_u, (const ImuRec *)W->irec.p, d_x,
-                                          (const double *)W->times_d.p, partial, W->npart_doubles + W->npiece_b + W->npiece_u);
   GatherArgs ga;
   ga.src = (const Src *)W->src.p, ga.src_begin = (const uint32_t *)W->src_begin.p;
   ga.gsrc = (const GSrc *)W->gsrc.p, ga.gsrc_begin = (const uint32_t *)W->gsrc_begin.p;
@@ -3267,7 +3093,7 @@ int enqueue_linearize(wc_ctx *ctx, wc_window_state *W, const double *d_x, int ma
   // multi-GPU: the ranks reduce the upper block triangle only (pair order, 144 doubles per block pair, then g and the cost):
   // half the bytes of the dense matrix on the wire; one more kernel spreads the sum into both triangles
   const bool packed = multi_gpu(ctx, W);
-  const bool two = packed && W->two_coll && !W->allreduce;  // (the two-collective form: IMU factors replicated by wc_window_build_sharded)
+  const bool two = two_collectives(ctx, W);
   double *red = nullptr;
   const size_t red_count = two ? (size_t)36 * W->npairs + 6 * (size_t)W->ns : (size_t)W->red_H + W->np + 2;
   if (packed) {
@@ -3283,8 +3109,7 @@ int enqueue_linearize(wc_ctx *ctx, wc_window_state *W, const double *d_x, int ma
   ga.nb_pieces = W->npiece_b, ga.nu_pieces = W->npiece_u, ga.ns = W->ns, ga.fix_first = W->wp.fix_first;
   ga.cost_base = W->npart_doubles;
   // max |g| + the mailbox by the last of k_gather's g / cost workgroups (one GPU; behind an all-reduce k_post_reduce stays a launch)
-  const bool post_apart = ctx->dev.lin_post_apart != 0;
-  ga.post = (post && !packed && !post_apart) ? 1 : 0;
+  ga.post = packed ? 0 : 1;
   ga.mail_slot = mail_slot, ga.done = (uint32_t *)((double *)W->mail.p + 60), ga.mail = (double *)W->mail.p, ga.host_mail = host_mail, ga.ticket = ticket;
   const uint32_t gather_grid = W->nheavy + (W->nnear + kGG * kLightSets - 1) / (kGG * kLightSets) + (W->nfar + kFarGroups * kFarSets - 1) / (kFarGroups * kFarSets) + W->ns + 1;
   ga.only = 0;
@@ -3299,7 +3124,7 @@ int enqueue_linearize(wc_ctx *ctx, wc_window_state *W, const double *d_x, int ma
     k_gather<<<gather_grid, 144 * kGG, 0, st>>>(ga);
     WC_HIP(ctx, hipGetLastError());
     WC_TRY(do_allreduce(ctx, W, mail + 52, 2));  // collective 1: {cost of the surfel factors, spare}
-    k_post_cost<<<1, 64, 0, st>>>(mail, mail_slot, lin_cost(W, other), post ? host_mail : nullptr, post ? ticket : 0ull);
+    k_post_cost<<<1, 64, 0, st>>>(mail, mail_slot, lin_cost(W, other), host_mail, ticket);
     double *late = nullptr;
     if (host_mail) late = host_mail + 40 + (W->lin_count & 1u);
     ++W->lin_count;
@@ -3339,9 +3164,8 @@ int enqueue_linearize(wc_ctx *ctx, wc_window_state *W, const double *d_x, int ma
   if (packed) {
     WC_TRY(do_allreduce(ctx, W, red, red_count));  // the ONE collective of a linearisation
     k_expand_pairs<<<W->npairs + 1, 144, 0, st>>>(red, W->npairs, W->ns, W->np, lin_H(W, other), lin_g(W, other), (const uint32_t *)W->pair_off.p, W->red_H);
+    k_post_reduce<<<1, 1024, 0, st>>>(lin_g(W, other), lin_cost(W, other), W->n, (double *)W->mail.p, mail_slot, host_mail, ticket);
   }
-  // (inside the LM loop the next lm_step forms cost / max |g| of this linearisation itself: post = false)
-  if (post && !ga.post) k_post_reduce<<<1, 1024, 0, st>>>(lin_g(W, other), lin_cost(W, other), W->n, (double *)W->mail.p, mail_slot, host_mail, ticket);
   WC_HIP(ctx, hipGetLastError());
   return WC_OK;
 }
@@ -3364,7 +3188,7 @@ int wait_mail(wc_ctx *ctx, unsigned long long ticket) {
 }
 
 // cost (and optionally residuals in the reference's block order: binary, unary, imu x 12) at x -> mail[slot]
-int enqueue_evaluate(wc_ctx *ctx, wc_window_state *W, const double *d_x, double *d_res, int mail_slot, double *host_mail = nullptr) {
+int enqueue_evaluate(wc_ctx *ctx, wc_window_state *W, const double *d_x, double *d_res, int mail_slot) {
   hipStream_t st = ctx->stream;
   double *cp = (double *)W->cost_part.p;
   const uint32_t gb = (W->nb + 255) / 256, gu = (W->nu + 255) / 256, gi = (W->ni + 255) / 256;
@@ -3377,7 +3201,7 @@ int enqueue_evaluate(wc_ctx *ctx, wc_window_state *W, const double *d_x, double 
   if (gi)
     k_eval_imu<<<gi, 256, 0, st>>>(W->wp, (const ImuRec *)W->irec.p, W->ni, d_x, (const double *)W->times_d.p,
                                   d_res ? d_res + W->nb + W->nu : nullptr, cp + gb + gu);
-  if (multi_gpu(ctx, W) && W->two_coll && !W->allreduce) {  // (the IMU factors are on every rank: their cost is added behind the sum of the surfel factors')
+  if (two_collectives(ctx, W)) {  // (the IMU factors are on every rank: their cost is added behind the sum of the surfel factors')
     double *mail = (double *)W->mail.p;
     k_sum_blocks<<<1, 1024, 0, st>>>(cp, gb + gu, mail, 52, nullptr);
     k_sum_blocks<<<1, 1024, 0, st>>>(cp + gb + gu, gi, mail, 54, nullptr);
@@ -3387,7 +3211,7 @@ int enqueue_evaluate(wc_ctx *ctx, wc_window_state *W, const double *d_x, double 
     WC_HIP(ctx, hipGetLastError());
     return WC_OK;
   }
-  k_sum_blocks<<<1, 1024, 0, st>>>(cp, gb + gu + gi, (double *)W->mail.p, mail_slot, multi_gpu(ctx, W) ? nullptr : host_mail);
+  k_sum_blocks<<<1, 1024, 0, st>>>(cp, gb + gu + gi, (double *)W->mail.p, mail_slot, nullptr);
   WC_HIP(ctx, hipGetLastError());
   WC_TRY(do_allreduce(ctx, W, (double *)W->mail.p + mail_slot, 1));
   return WC_OK;
@@ -3411,7 +3235,7 @@ extern "C" int wc_window_counts(wc_ctx *ctx, uint64_t counts[4]) {
 
 extern "C" uint64_t wc_window_reduce_bytes(wc_ctx *ctx) {
   if (!ctx || !ctx->win || !ctx->win->built || !multi_gpu(ctx, ctx->win)) return 0;
-  if (ctx->win->two_coll && !ctx->win->allreduce) return ((uint64_t)36 * ctx->win->npairs + 6 * (uint64_t)ctx->win->ns + 2) * 8;  // (+ the 16-byte cost collective)
+  if (two_collectives(ctx, ctx->win)) return ((uint64_t)36 * ctx->win->npairs + 6 * (uint64_t)ctx->win->ns + 2) * 8;  // (+ the 16-byte cost collective)
   return ((uint64_t)ctx->win->red_H + ctx->win->np + 2) * 8;
 }
 
@@ -3503,7 +3327,6 @@ extern "C" int wc_window_solve(wc_ctx *ctx, double *h_x_inout, wc_solve_summary 
     WC_TRY(wc_ensure(ctx, W->yred, (size_t)(12 * ns_al + 2 * kNB + 128) * 8));  // (y of the pose half; behind it the fused tail's partial sums: four per workgroup)
   }
 
-  const bool poll_mail = ctx->dev.lm_sync == 0;  // (development option lm_sync: wait for the stream instead of the ticket)
   double *h_mail_dev = nullptr, *h_stage_dev = nullptr;  // device addresses of the pinned mailbox and of its staging area
   {
     void *dp = nullptr;
@@ -3513,13 +3336,16 @@ extern "C" int wc_window_solve(wc_ctx *ctx, double *h_x_inout, wc_solve_summary 
   }
   // the two-collective form of a sharded window: the cost of a linearisation reaches the host behind the 16-byte collective (ticket), its
   // max |g| behind the large one - in a late slot of the pinned mailbox the loop reads with the NEXT ticket (two_late)
-  const bool two = multi_gpu(ctx, W) && W->two_coll && !W->allreduce;
+  const bool multi = multi_gpu(ctx, W), two = two_collectives(ctx, W);
+  // the candidate's linearisation posts its cost (and, but for the two-collective form, its max |g|) to the pinned mailbox itself, with a
+  // ticket: one GPU, or the two-collective form's k_post_cost.  Behind the one all-reduce of the other sharded forms, the mailbox is copied
+  const bool mailed = !multi || two;
   WC_HIP(ctx, hipMemcpyAsync(x, cur.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
-  if (poll_mail && !multi_gpu(ctx, W)) {
+  if (!multi) {
     // the first linearisation's cost / max |g| through the pinned mailbox and its ticket, like every later one (the stream
     // wait of rounds 1 - 3 added the end-of-kernel signal and the runtime's wake-up, ~20 us per solve; k_scale_init runs behind it)
     const unsigned long long ticket = ++ctx->mail_ticket;
-    WC_TRY(enqueue_linearize(ctx, W, x, 0, /*post=*/true, /*other=*/false, h_mail_dev, ticket));
+    WC_TRY(enqueue_linearize(ctx, W, x, 0, /*other=*/false, h_mail_dev, ticket));
     k_scale_init<<<(n + 255) / 256, 256, 0, st>>>(H, n, scale);
     WC_HIP(ctx, hipGetLastError());
     WC_TRY(wait_mail(ctx, ticket));
@@ -3537,29 +3363,13 @@ extern "C" int wc_window_solve(wc_ctx *ctx, double *h_x_inout, wc_solve_summary 
   x_norm = std::sqrt(x_norm);
   int iter = 0, consecutive_invalid = 0;
   bool first_recorded = false;
-  // ONE host round trip per iteration: the linearisation at an accepted point is enqueued without waiting for it; its
-  // cost, max |g| and the accepted x are read back with the NEXT iteration's mailbox (the next step only needs the trust
-  // region radius, which is known).  If that read-back shows a gradient below tolerance, the iteration that was enqueued
-  // on top of it is discarded - the reference stops before it.
-  bool lin_pending = false;
   bool two_late = false;  // (two-collective form) max |g| of the accepted point has not been looked at yet: it sits in h_mail[40 + two_at]
   int two_slot = 0, two_at = 0;
   // Round 3: the candidate's cost comes from a LINEARISATION at the candidate (into the other {H, g, cost} buffer) instead of a
-  // cost-only pass over the same records: an accepted step - the rule - then needs no second pass (one pass over the factors
+  // cost-only pass over the same records (round 2): an accepted step - the rule - then needs no second pass (one pass over the factors
   // per iteration instead of two, -0.05 ms of 0.6 at C4), a rejected one has formed an H nobody uses (+0.1 ms).  Its cost and
-  // max |g| arrive with the iteration's mailbox, so nothing is pending between iterations.  Development option lm_eval_pass: round 2's flow.
-  const bool cand_lin = ctx->dev.lm_eval_pass == 0;
-  const bool spec_ok = ctx->dev.pcr_ahead != 0;  // (development option pcr_ahead: 0 = level 0 formed at the start of every iteration, as in rounds 3 - 4)
-  const void *pcr_ready_for = nullptr;           // the H whose undamped level-0 blocks sit in pcr_D / A / R [0]
-  auto resolve_pending = [&]() {
-    cost = ctx->h_mail[0];
-    gmax = ctx->h_mail[1];
-    if (cost < min_cost) {
-      min_cost = cost;
-      best = cur;
-    }
-    lin_pending = false;
-  };
+  // max |g| arrive with the iteration's mailbox, so nothing is pending between iterations: ONE host round trip per iteration.
+  const void *pcr_ready_for = nullptr;  // the H whose undamped level-0 blocks sit in pcr_D / A / R [0]
   summary->termination = 1;
   if (gmax <= 1e-10) {
     summary->termination = 0;
@@ -3569,7 +3379,7 @@ extern "C" int wc_window_solve(wc_ctx *ctx, double *h_x_inout, wc_solve_summary 
         summary->termination = 1;
         break;
       }
-      if ((!lin_pending && !two_late && gmax <= 1e-10) || radius <= 1e-32) {
+      if ((!two_late && gmax <= 1e-10) || radius <= 1e-32) {
         summary->termination = 0;
         break;
       }
@@ -3589,8 +3399,8 @@ extern "C" int wc_window_solve(wc_ctx *ctx, double *h_x_inout, wc_solve_summary 
           for (int s = 1; s < M; s *= 2) ++nlev;
           double *X = nullptr;
           // level 0 from H, UNDAMPED (radius 0) - unless it is there already: enqueued behind the linearisation this H came from,
-          // before the host knew that its step would be accepted (pcr_ahead below)
-          if (pcr_ready_for != (const void *)H || !spec_ok) {
+          // before the host knew that its step would be accepted (see behind the candidate's linearisation below)
+          if (pcr_ready_for != (const void *)H) {
             const PcrSrc src{H, g, scale, n, ns, 0.0, diag};
             k_pcr_init<<<dim3(M, nch), 256, 0, st>>>(src, Dp[0], Ap[0], Rp[0], ldr, fail);
           }
@@ -3598,10 +3408,10 @@ extern "C" int wc_window_solve(wc_ctx *ctx, double *h_x_inout, wc_solve_summary 
           const PcrDamp damp{radius, ns, diag}, nodamp{0.0, ns, diag};
           for (int s = 1, lev = 0; lev < nlev; s *= 2, ++lev) {  // (ns >= 4: at least one level)
             const bool last = lev == nlev - 1, first = lev == 0;
-            // (the levels of small stride work on banded right-hand sides: fewer column chunks per row - k_pcr_level; development option
-            // pcr_full_width: every level over all columns, as in rounds 3 - 5)
+            // (the levels of small stride work on banded right-hand sides: fewer column chunks per row - k_pcr_level; rounds 3 - 5 ran
+            // every level over all columns)
             const int band_chunks = (kSB * (4 * s + 1) + 255) / 256;
-            const int limited = (ctx->dev.pcr_full_width == 0 && band_chunks < nch) ? band_chunks : 0;
+            const int limited = band_chunks < nch ? band_chunks : 0;
             const dim3 grid(M * (limited ? limited : nch));
             if (last && first)
               k_pcr_level<true, true><<<grid, 256, 0, st>>>(s, M, Dp[cur], Ap[cur], Rp[cur], Dp[cur ^ 1], Ap[cur ^ 1], Rp[cur ^ 1], ldr, fail, damp, npz, limited);
@@ -3616,57 +3426,17 @@ extern "C" int wc_window_solve(wc_ctx *ctx, double *h_x_inout, wc_solve_summary 
           X = Rp[cur];  // the last level wrote X = T^-1 [C | bB] where the others write R'
           WC_TRY(join_side(ctx, W));  // (the pose blocks and the pose half of g: summed over the ranks on the side stream)
           k_schur_form<<<((np2 + 255) / 256) * (1 + ns + (np2 - npz)), 256, 0, st>>>(H, g, scale, X, n, ns, ldr, np2, ld2, radius, A, diag, Lmat, (double *)W->Linv.p, fail, (np2 + 255) / 256);
-          // (development option lm_back_chunks: rounds 2 - 5's back substitution - chunk solves + products - and k_schur_bias_y / k_lm_step
-          // as launches of their own, for A/B runs; default: identity rows appended to the factorisation, k_back_mul, one fused tail)
-          const bool back_mul = ctx->dev.lm_back_chunks == 0;
-#ifdef WC_DEV_KNOBS
-          if (ctx->dev.dbg_lm & 8) WC_TRY(wc_ensure(ctx, W->reduce, (size_t)nblk2 * 1024 * 8));
-#endif
+          // the back substitution: identity rows appended to the factorisation (chol_extra_tile), k_back_mul, one fused tail (rounds 2 - 5:
+          // chunk solves + products and two tail launches)
           for (int k = 0; k + 1 < nblk2; ++k) {
             const int tiles = ((nblk2 - k - 1) * kNB + 63) / 64;
             const int n_tri = 1 + tiles * (tiles + 1) / 2;
-            const int n_extra = back_mul ? (((k + 1) * kNB + 63) / 64) * tiles : 0;
-            k_chol_step<<<n_tri + n_extra, 256, 0, st>>>(A, ld2, k, nblk2, Lmat, (double *)W->Linv.p, fail, npz, n_tri, tiles, ctx->dev.dbg_lm,
-                                                         (long long *)W->reduce.p);
+            const int n_extra = (((k + 1) * kNB + 63) / 64) * tiles;
+            k_chol_step<<<n_tri + n_extra, 256, 0, st>>>(A, ld2, k, nblk2, Lmat, (double *)W->Linv.p, fail, npz, n_tri, tiles);
           }
-#ifdef WC_DEV_KNOBS
-          if (ctx->dev.dbg_lm & 8) {  // (development session: wall-clock stamps of every workgroup of every step, 100 MHz)
-            static int calls = 0;
-            if (++calls == 3) {
-              std::vector<long long> hb((size_t)nblk2 * 1024);
-              (void)hipStreamSynchronize(st);
-              (void)hipMemcpy(hb.data(), W->reduce.p, hb.size() * 8, hipMemcpyDeviceToHost);
-              for (int k = 0; k + 1 < nblk2; ++k) {
-                const int tiles = ((nblk2 - k - 1) * kNB + 63) / 64, n_tri = 1 + tiles * (tiles + 1) / 2;
-                const int n_extra = back_mul ? (((k + 1) * kNB + 63) / 64) * tiles : 0;
-                long long t0 = hb[(size_t)k * 1024], le = hb[(size_t)k * 1024 + 1], ts = 0, te = 0, xs = 0, xe = 0, tl = 0, xl = 0;
-                for (int b = 1; b < n_tri + n_extra; ++b) {
-                  const long long a = hb[((size_t)k * 512 + b) * 2], e = hb[((size_t)k * 512 + b) * 2 + 1];
-                  if (b < n_tri) ts = std::max(ts, a - t0), te = std::max(te, e - t0), tl = std::max(tl, e - a);
-                  else xs = std::max(xs, a - t0), xe = std::max(xe, e - t0), xl = std::max(xl, e - a);
-                }
-                fprintf(stderr, "step %2d: lead %5.2f us | tiles: last start %5.2f longest %5.2f last end %5.2f | extra: last start %5.2f longest %5.2f last end %5.2f\n", k,
-                        (le - t0) * 0.01, ts * 0.01, tl * 0.01, te * 0.01, xs * 0.01, xl * 0.01, xe * 0.01);
-              }
-            }
-          }
-#endif
           const StepArgs sa{x, scale, g, diag, lin_cost(W), xc, mail, h_stage_dev, 0};
-          if (back_mul) {
-            k_back_mul<<<(npz + 7) / 8, 256, 0, st>>>(A, Lmat, ld2, nblk2, npz, (const double *)W->Linv.p, yred);
-            k_schur_bias_y_step<<<(npz + 3) / 4, 256, 0, st>>>(X, yred, ns, ldr, y, sa, n, (uint32_t *)(mail + 62), yred + npz + kNB);
-          } else {
-            const double *zsrc = Lmat + (size_t)npz * ld2;
-            for (int hi = (npz + kNB - 1) / kNB; hi > 0;) {
-              const int lo = std::max(0, hi - kBackChunk);
-              k_chol_back_chunk<<<1, 1024, 0, st>>>(Lmat, ld2, npz, (const double *)W->Linv.p, zsrc, yred, lo, hi, sa);
-              if (lo > 0) k_chol_back_gemv<<<lo, 1024, 0, st>>>(Lmat, ld2, npz, zsrc, yred, lo, hi);
-              zsrc = yred;
-              hi = lo;
-            }
-            k_schur_bias_y<<<(npz + 3) / 4, 256, 0, st>>>(X, yred, ns, ldr, y);
-            k_lm_step<<<1, 1024, 0, st>>>(sa, y, n);
-          }
+          k_back_mul<<<(npz + 7) / 8, 256, 0, st>>>(A, Lmat, ld2, nblk2, npz, (const double *)W->Linv.p, yred);
+          k_schur_bias_y_step<<<(npz + 3) / 4, 256, 0, st>>>(X, yred, ns, ldr, y, sa, n, (uint32_t *)(mail + 62), yred + npz + kNB);
         } else {
           {
             dim3 grid((np + 255) / 256, np);
@@ -3690,20 +3460,17 @@ extern "C" int wc_window_solve(wc_ctx *ctx, double *h_x_inout, wc_solve_summary 
             }
           }
         }
-        unsigned long long ticket = 0;
-        if (cand_lin && poll_mail && (!multi_gpu(ctx, W) || two) && h_mail_dev) ticket = ++ctx->mail_ticket;
-        if (cand_lin && two) two_slot = (int)(W->lin_count & 1u);  // (where this linearisation's max |g| will land)
-        if (cand_lin)
-          WC_TRY(enqueue_linearize(ctx, W, xc, 5, /*post=*/true, /*other=*/true, (multi_gpu(ctx, W) && !two) ? nullptr : h_mail_dev, ticket));  // mail[5] = cost, [6] = max |g| at the candidate
-        else
-          WC_TRY(enqueue_evaluate(ctx, W, xc, nullptr, 5, h_mail_dev));
+        const unsigned long long ticket = mailed ? ++ctx->mail_ticket : 0;
+        if (two) two_slot = (int)(W->lin_count & 1u);  // (where this linearisation's max |g| will land)
+        // mail[5] = cost, [6] = max |g| at the candidate
+        WC_TRY(enqueue_linearize(ctx, W, xc, 5, /*other=*/true, mailed ? h_mail_dev : nullptr, ticket));
         WC_HIP(ctx, hipGetLastError());
-        // (one GPU: k_sum_blocks has stored the mailbox to pinned host memory itself; with an all-reduce behind it, copy)
-        if ((multi_gpu(ctx, W) && !(two && cand_lin)) || !h_mail_dev) WC_HIP(ctx, hipMemcpyAsync(ctx->h_mail, mail, 40 * 8, hipMemcpyDeviceToHost, st));
-        if (cand_lin && use_schur && spec_ok) {
-          // pcr_ahead: the next iteration's level 0 from the CANDIDATE's H, while the host waits for this iteration's mailbox and decides
+        if (!mailed) WC_HIP(ctx, hipMemcpyAsync(ctx->h_mail, mail, 40 * 8, hipMemcpyDeviceToHost, st));
+        if (use_schur) {
+          // the next iteration's level 0 from the CANDIDATE's H, while the host waits for this iteration's mailbox and decides
           // (the blocks do not depend on the radius).  An accepted step - the rule - finds them there; a rejected one forms its own.
-          // (Behind the mailbox's copy: k_pcr_init clears the factorisation's fail flag, which that copy carries.)
+          // (Behind the mailbox's copy: k_pcr_init clears the factorisation's fail flag, which that copy carries.  Rounds 3 - 4 formed
+          // level 0 at the start of every iteration.)
           const int ns = W->ns, npz = 6 * ns, M = (ns + 1) / 2, ldr = ((npz + 1 + 63) / 64) * 64, nch = (ldr + 255) / 256;
           const PcrSrc src{lin_H(W, true), lin_g(W, true), scale, n, ns, 0.0, diag};
           k_pcr_init<<<dim3(M, nch), 256, 0, st>>>(src, (double *)W->pcr_D[0].p, (double *)W->pcr_A[0].p, (double *)W->pcr_R[0].p, ldr, fail);
@@ -3728,14 +3495,6 @@ extern "C" int wc_window_solve(wc_ctx *ctx, double *h_x_inout, wc_solve_summary 
           break;
         }
       }
-      if (lin_pending) {
-        resolve_pending();
-        if (gmax <= 1e-10) {  // GradientToleranceReached at the point this iteration started from
-          --iter;
-          summary->termination = 0;
-          break;
-        }
-      }
       summary->n_cost_evaluations++;
       int hfail;
       std::memcpy(&hfail, &ctx->h_mail[32], 4);
@@ -3747,7 +3506,7 @@ extern "C" int wc_window_solve(wc_ctx *ctx, double *h_x_inout, wc_solve_summary 
       // rejected steps the oracle (and round 2's dense path) accepted and then needed 38 iterations for the oracle's 27, or hit the
       // iteration limit.  Accepted steps - the rule: all of them in the bench's windows, the odometry step and the facade's stream - cost
       // nothing extra; a genuine rejection costs one dense step.
-      if (schur_now && cand_lin) {
+      if (schur_now) {
         const bool invalid = hfail || !(model_change > 0) || !std::isfinite(step_norm);
         const double dc = cost - cand_cost;
         const bool rejected = !invalid && step_norm > 1e-8 * (x_norm + 1e-8) && std::fabs(dc) > 1e-6 * cost && !(dc / model_change > 1e-3);
@@ -3793,18 +3552,14 @@ extern "C" int wc_window_solve(wc_ctx *ctx, double *h_x_inout, wc_solve_summary 
         x_norm = 0.0;
         for (int i = 0; i < n; ++i) x_norm += cur[i] * cur[i];
         x_norm = std::sqrt(x_norm);
-        if (cand_lin) {  // the candidate's linearisation IS the new point's
-          W->lin_sel ^= 1;
-          H = lin_H(W), g = lin_g(W);
-          cost = cand_cost, gmax = ctx->h_mail[6];
-          if (two) gmax = 1.0, two_late = true, two_at = two_slot;  // (not there yet: looked at behind the next iteration's ticket)
-          if (cost < min_cost) {
-            min_cost = cost;
-            best = cur;
-          }
-        } else {
-          WC_TRY(enqueue_linearize(ctx, W, x, 0, /*post=*/false));
-          lin_pending = true;
+        // the candidate's linearisation IS the new point's
+        W->lin_sel ^= 1;
+        H = lin_H(W), g = lin_g(W);
+        cost = cand_cost, gmax = ctx->h_mail[6];
+        if (two) gmax = 1.0, two_late = true, two_at = two_slot;  // (not there yet: looked at behind the next iteration's ticket)
+        if (cost < min_cost) {
+          min_cost = cost;
+          best = cur;
         }
         summary->n_linearizations++;
         radius = radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3));
@@ -3817,12 +3572,6 @@ extern "C" int wc_window_solve(wc_ctx *ctx, double *h_x_inout, wc_solve_summary 
         summary->unsuccessful_steps++;
       }
     }
-  }
-  if (lin_pending) {  // the last accepted point's linearisation is still in flight (and no lm_step follows it)
-    k_post_reduce<<<1, 1024, 0, st>>>(lin_g(W), lin_cost(W), W->n, mail, 0);
-    WC_HIP(ctx, hipMemcpyAsync(ctx->h_mail, mail, 2 * 8, hipMemcpyDeviceToHost, st));
-    WC_HIP(ctx, hipStreamSynchronize(st));
-    resolve_pending();
   }
   if (W->side_pending) {  // (the last linearisation's expansion may still run on the side stream: nothing of this solve outlives the call)
     WC_TRY(join_side(ctx, W));

@@ -226,10 +226,8 @@ __global__ void __launch_bounds__(256) k_pcr_level(int s, int M, const double *_
     sI[0][r][c] = dL, sI[1][r][c] = dU, sAl[r][c] = aM, sAu[r][c] = aU, sALL[r][c] = (L - s >= 0) ? aL : 0.0, sDm[r][c] = dM;
   }
   __syncthreads();
-#ifndef WC_PCR_NOINV  // (timing experiment: what a level costs without its two inverses)
   gj_inv12_wave(sI, 2, fail);
   __syncthreads();
-#endif
   for (int e = tid; e < 288; e += 256) {
     const int which = e / 144, r = (e % 144) / kSB, c = e % kSB;
     double acc = 0.0;
@@ -268,14 +266,12 @@ __global__ void __launch_bounds__(256) k_pcr_level(int s, int M, const double *_
 #pragma unroll
   for (int r = 0; r < kSB; ++r) {
     double v = rm[r];
-#ifndef WC_PCR_NOR  // (timing experiment: ... without the right-hand sides' update)
 #pragma unroll
     for (int k = 0; k < kSB; k += 2) {  // (the same sums in the same order)
       const double2 al = *(const double2 *)&sAlpha[r][k], ga = *(const double2 *)&sGamma[r][k];
       v = fma(al.x, rl[k], fma(ga.x, ru[k], v));
       v = fma(al.y, rl[k + 1], fma(ga.y, ru[k + 1], v));
     }
-#endif
     rn[r] = v;
   }
   if (LAST) {
@@ -465,28 +461,14 @@ __global__ void __launch_bounds__(256) k_schur_form(const double *__restrict__ H
   }
 }
 
-// yB = x_b - X yP, both halves of y back in the order of the unknowns; four bias rows per workgroup (64 lanes each)
-__global__ void __launch_bounds__(256) k_schur_bias_y(const double *__restrict__ X, const double *__restrict__ yred, int ns, int ldr, double *y) {
-  const int npz = 6 * ns;
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int ib = blockIdx.x * 4 + w;
-  if (blockIdx.x == 0)  // (and the pose half)
-    for (int q = threadIdx.x; q < npz; q += 256) y[schur_orig_pose(q)] = yred[q];
-  if (ib >= npz) return;  // (bias unknowns of real sample states: 6 ns of them, like the pose unknowns)
-  const double *row = X + (size_t)ib * ldr;
-  double acc = 0.0;
-  for (int q = lane; q < npz; q += 64) acc = fma(row[q], yred[q], acc);
-  for (int mm = 32; mm >= 1; mm >>= 1) acc += __shfl_xor(acc, mm);
-  if (lane == 0) y[schur_orig_bias(ib)] = row[npz] - acc;
-}
-
-// Round 6: k_schur_bias_y and k_lm_step in ONE launch, without a second look at y.  A workgroup forms its four bias rows of y (workgroup
+// yB = x_b - X yP, both halves of y back in the order of the unknowns, four bias rows per workgroup (64 lanes each), and lm_step.
+// Round 6: one launch instead of rounds 2 - 5's two, without a second look at y.  A workgroup forms its four bias rows of y (workgroup
 // 0 also moves the pose half), and right there their part of lm_step: candidate entries xc / host_xc and the partial sums of the model
 // cost change, |step|^2, |x|^2 and max |g| over the entries it owns.  The partials go to `part` (four doubles per workgroup) as
 // agent-scope atomic stores, acknowledged (vmcnt) before the workgroup is counted; the workgroup that counts last adds the partials in
 // workgroup order (fixed) and writes the mailbox's scalars.  No fence, no L2 write-back: the first form of this kernel - release fence
 // per workgroup, acquire + lm_step over all of y in the last - took 15.6 us at 127 sample states against 12.2 for the two launches.
-// (The scalars differ from k_lm_step's in the last bits - another summation order; they feed tolerances of 1e-3 and more.)
+// (The scalars differ from the two launches' in the last bits - another summation order; they feed tolerances of 1e-3 and more.)
 __global__ void __launch_bounds__(256) k_schur_bias_y_step(const double *__restrict__ X, const double *__restrict__ yred, int ns, int ldr, double *y,
                                                            StepArgs S, int n, uint32_t *done, double *part) {
   __shared__ uint32_t s_last;
@@ -572,8 +554,4 @@ __global__ void __launch_bounds__(256) k_schur_bias_y_step(const double *__restr
     S.mail[1] = fmax(fmax(sp[3][0], sp[3][1]), fmax(sp[3][2], sp[3][3]));
     __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-}
-
-__global__ void __launch_bounds__(1024) k_lm_step(StepArgs S, const double *y, int n) {
-  lm_step(S.x, y, S.scale, S.g, S.diag, n, S.xc, S.mail, S.host_xc, S.lin_cost);
 }
