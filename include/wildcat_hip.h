@@ -58,15 +58,7 @@ int wc_ctx_set_params(wc_ctx *ctx, const wc_params *params);
  *   fx_split           node stage of the default extraction: 0 fused kernel, 1 two kernels, -1 by size
  *   no_bucket_sort     exact path: radix sort instead of the run-binned sort
  *   ex_sync            wc_extract_surfels_finish waits for the stream instead of the sweep's completion ticket
- *   kd_leaf            target leaf size of the matcher's kd-tree (0 = 8)
- *   knn_group          matcher walk: 0 one lane per query, 1 eight lanes per query, -1 by the call's sizes
- *   knn_early          1 (default): the matcher's walks are bounded by the nearest gate-passing candidate as well as by the k-th distance
- *                      (same pair lists; not when the neighbour lists themselves are asked for); 0: plain k-NN walks; 2: two-set searches only
- *   knn_sort           leaf-order sort of a two-set search's queries: 0 never, 1 always, -1 (default): from 40 000 queries when the plain
- *                      k-NN walks run (neighbour lists asked for, knn_early = 0), never with the early bound
- *   match_pair_hold    1 (default): wc_match_pair holds the fixed-window search's walk back until the other search's tree is built
  *   match_pair_serial  wc_match_pair runs its two searches one after the other on the ctx
- *   match_pair_swap    the sliding-window search on the helper context instead of the fixed-window one
  *   lm_dense           round 2's LM step: dense Cholesky of all unknowns instead of the bias elimination
  *   lm_one_collective  sharded windows: rounds 3 - 5's ONE all-reduce per linearisation (IMU triples sharded too) instead of the
  *                      two-collective form (IMU factors replicated; 16-byte cost collective, then the pose corners)
@@ -227,16 +219,16 @@ int wc_reverse_copy_surfels(wc_ctx *ctx, const wc_surfel *d_src_surf, const wc_p
  *                   (older, newer) indices into that set, at most one per query, in query order
  *   same_set == 0 : fixed-window matcher; pair.first indexes the targets (fixed window), pair.second the queries
  *   d_knn_idx / d_knn_d2 (may be NULL): the raw exact k nearest neighbours per query (k = wc_params.knn_k), the output
- *                   of FLANNKNearestSearch (cc:75-89), for known-answer tests.  With them NULL a walk is bounded by the nearest
- *                   gate-passing candidate as well as by the k-th distance - Match takes the FIRST of the k neighbours that passes
- *                   the gates (cc:24-46), so the pair list is the same, byte for byte (development option knn_early = 0: off)
+ *                   of FLANNKNearestSearch (cc:75-89), for known-answer tests; asking for them gives the plain k-NN walk.  With
+ *                   them NULL the walk is bounded by the nearest gate-passing candidate as well as by the k-th distance - Match
+ *                   takes the FIRST of the k neighbours that passes the gates (cc:24-46), so the pair list is the same, byte for byte
  * Surfels must be in the body frame with poses attached (wc_update_surfel_poses). */
 int wc_match(wc_ctx *ctx, const wc_surfel *d_q_surf, const wc_pose *d_q_pose, uint64_t nq, const wc_surfel *d_t_surf,
              const wc_pose *d_t_pose, uint64_t nt, int same_set, wc_pair *d_pairs, uint64_t cap, uint64_t *h_n_pairs,
              uint32_t *d_knn_idx, double *d_knn_d2);
 
 /* What the walk of the last wc_match on this context touched (the index is a 6-D kd-tree with bounding boxes, csrc/match_tree.inc),
- * from a sample of its wavefronts: h_out[0 .. 3] = wide nodes opened, leaves scanned, points given the fp32 first look, exact
+ * from a sample of its wavefronts: h_out[0 .. 3] = wide nodes opened, leaves scanned, points looked at, exact
  * fp64 distances - sums over h_out[4] sampled queries; h_out[5] = depth of the tree, h_out[6] = levels above the buckets,
  * h_out[7] = targets.  Measurement only (bench.py's candidates-per-query figure). */
 int wc_match_stats(wc_ctx *ctx, double h_out[8]);

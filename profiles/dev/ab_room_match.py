@@ -1,11 +1,12 @@
-# the two-set search on ROOM surfels (sweeps of a spinning scanner in firing order: surfels in time-bin order), development options as in ab_match_opt.py
+# the two-set search on ROOM surfels (sweeps of a spinning scanner in firing order: surfels in time-bin order), under development option specs:
+# python profiles/dev/ab_room_match.py "" "match_pair_serial=1" ...
 import os, sys, time, zlib
 R_ = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [R_ + "/wildcat-slam_amd/python"]
 import numpy as np
 from wildcat_slam_amd import lib, synth, records as R
 ctx = lib.Context(0)
-DEF = {"knn_sort": -1, "knn_early": 1, "knn_group": -1}
+DEF = {}  # defaults of the options that are not 0
 for pps in (640_000, 1_600_000):
     msgs, _, _ = synth.raw_stream(4.0, pts_per_s=pps, t_start=1000.0)
     surf = []

@@ -29,7 +29,7 @@ for m in VALUBusy MemUnitBusy MemUnitStalled OccupancyPercent VALUUtilization SQ
 import csv, sys
 if not sys.argv[1]:
     print(sys.argv[2], "no file"); sys.exit(0)
-v = [float(r["Counter_Value"]) for r in csv.DictReader(open(sys.argv[1])) if "k_knn_tree" in r["Kernel_Name"]]
+v = [float(r["Counter_Value"]) for r in csv.DictReader(open(sys.argv[1])) if "k_knn_tree_group" in r["Kernel_Name"]]
 print("%-18s %s" % (sys.argv[2], " ".join("%.4g" % x for x in v[-3:])))
 EOP
 done

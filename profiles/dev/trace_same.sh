@@ -1,5 +1,5 @@
 #!/bin/bash
-# kernel trace of ONE same-set search of the step-like window under a development option spec: bash profiles/dev/trace_same.sh "knn_early=0" [ab_var/<tree> | .] [c4]
+# kernel trace of ONE same-set search of the step-like window under a development option spec: bash profiles/dev/trace_same.sh "<name=value,...>" [ab_var/<tree> | .] [c4]
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R

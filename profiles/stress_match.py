@@ -1,6 +1,5 @@
 """Ad-hoc stress of the matcher against the CPU oracle's kd-tree on windows larger than the unit tests use (run on the GPU
-box: python profiles/stress_match.py; the matcher takes the eight-lanes-per-query walk at these sizes, WC_KNN_GROUP=0 python
-profiles/stress_match.py runs the same windows through the lane-per-query walk).  k-NN tables and pair lists must be identical."""
+box: python profiles/stress_match.py).  k-NN tables and pair lists must be identical."""
 import os
 import sys
 import time

@@ -1,6 +1,6 @@
 """Randomised PARAMETER + window stress of the matcher's PAIRS (exact k-NN + gates + the order-dependent de-duplication,
 knn_surfel_matcher.cc:16-89) against the CPU oracle: windows of re-observed patches with perturbed poses (synth.surfel_window) of
-random size, random k / scales / gates, both walks of the tree pinned (development option knn_group), two repetitions each; the pair
+random size, random k / scales / gates, two repetitions each; the pair
 lists must be the oracle's byte for byte.  python profiles/stress_match_params.py [seconds]"""
 import os, sys, time
 R_ = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,18 +31,15 @@ while time.time() < t_end:
     ref_b = pyoracle.match(w["surf"], w["pose"], w["surf"], w["pose"], True, prm)
     fix_s, fix_p = w.get("fix_surf"), w.get("fix_pose")
     ref_u = pyoracle.match(w["surf"], w["pose"], fix_s, fix_p, False, prm) if fix_s is not None and len(fix_s) else None
-    for group in (0, 1):
-        ctx.set_dev_option("knn_group", group)
-        for rep in range(2):
-            got_b = ctx.match(w["surf"], w["pose"], w["surf"], w["pose"], True)
-            ok = got_b.tobytes() == ref_b.tobytes()
-            if ref_u is not None:
-                got_u = ctx.match(w["surf"], w["pose"], fix_s, fix_p, False)
-                ok = ok and got_u.tobytes() == ref_u.tobytes()
-            rounds += 1
-            if not ok:
-                bad += 1
-                print("MISMATCH seed", seed, "group", group, "rep", rep, "surfels", len(w["surf"]), "fixed", 0 if fix_s is None else len(fix_s), "k", prm.knn_k, "cs", prm.center_scale,
-                      "as", prm.angular_scale, "dmax", prm.surfel_dist_max, "tmin", prm.time_diff_min, "pairs", len(got_b), len(ref_b))
-ctx.set_dev_option("knn_group", -1)
+    for rep in range(2):
+        got_b = ctx.match(w["surf"], w["pose"], w["surf"], w["pose"], True)
+        ok = got_b.tobytes() == ref_b.tobytes()
+        if ref_u is not None:
+            got_u = ctx.match(w["surf"], w["pose"], fix_s, fix_p, False)
+            ok = ok and got_u.tobytes() == ref_u.tobytes()
+        rounds += 1
+        if not ok:
+            bad += 1
+            print("MISMATCH seed", seed, "rep", rep, "surfels", len(w["surf"]), "fixed", 0 if fix_s is None else len(fix_s), "k", prm.knn_k, "cs", prm.center_scale,
+                  "as", prm.angular_scale, "dmax", prm.surfel_dist_max, "tmin", prm.time_diff_min, "pairs", len(got_b), len(ref_b))
 print("rounds %d, mismatches %d, last seed %d" % (rounds, bad, seed))

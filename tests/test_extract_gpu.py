@@ -359,13 +359,13 @@ def test_batched_sweeps_equal_single_sweeps(gpu, oracle):
 
 def test_development_options_and_warmup(gpu, oracle):
     """wc_ctx_set_dev_option replaces the environment knobs of rounds 2 - 4 (nothing in the release library reads the environment to
-    decide what to execute): an unknown name is an argument error, and so is the name of a retired window-solver form; every kept window
+    decide what to execute): an unknown name is an argument error, and so is the name of a retired window-solver form or matcher option; every kept window
     option is accepted; both forms of the default path's node stage (fx_split 0 / 1) give the oracle's surfels on the same cloud;
     wc_ctx_warmup can be called on a used context (and twice)"""
     from wildcat_slam_amd import lib
 
     retired = ("lm_eval_pass", "lm_sync", "pcr_ahead", "pcr_full_width", "lm_back_chunks", "dbg_lm", "lin_imu_apart", "lin_unary_apart",
-               "lin_post_apart", "lin_pair", "lin_unary_chunks")
+               "lin_post_apart", "lin_pair", "lin_unary_chunks", "knn_group", "knn_early", "knn_sort", "kd_leaf", "match_pair_swap", "match_pair_hold")
     for name in ("no_such_option",) + retired:
         with pytest.raises(lib.WildcatError):
             gpu.set_dev_option(name, 1)

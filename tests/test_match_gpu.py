@@ -170,7 +170,7 @@ def test_random_and_coherent_normals(gpu, oracle):
 
 
 def test_single_precision_first_look_is_conservative(gpu, oracle):
-    """the fp32 first look of k_knn_tree (boxes and points) where single precision cannot tell the candidates apart: clusters of
+    """the walk's fp32 look at the boxes (its bound thr32) where single precision cannot tell the candidates apart: clusters of
     surfels ~95 m from the origin whose members differ by micrometres in position and by 1e-7 in the normal (below the fp32
     resolution of the features), so that which ten are nearest is decided far below its rounding; lists, distances and pairs
     must still be the oracle's, bit for bit"""
@@ -195,7 +195,7 @@ def test_single_precision_first_look_is_conservative(gpu, oracle):
 @pytest.mark.parametrize("nt", [1, 9, 10, 11, 600, 1024, 1025, 2100, 5000, 33000, 70000])
 def test_tree_shapes(gpu, oracle, nt):
     """every shape of the index (match_tree.inc): a single leaf, one bucket, one sample stage (> 1 024 targets), two (> 32 k);
-    other-set queries (located, sorted by leaf) and same-set ones; k-NN tables bit-exact against the oracle's kd-tree"""
+    other-set queries (in their own order) and same-set ones (in leaf order); k-NN tables bit-exact against the oracle's kd-tree"""
     rng = np.random.default_rng(1000 + nt)
     ext = max(2.0, (nt / 20.0) ** (1 / 3))
     t, tp = _random_surfels(rng, nt, ext)
@@ -342,26 +342,25 @@ def test_match_pair_equals_the_two_searches_and_the_oracle(gpu, oracle, serial):
     assert len(ref_b) > 1000 and len(ref_u) > 500
 
 
-@pytest.mark.parametrize("group", ["0", "1"], ids=["lane-per-query", "eight-lanes-per-query"])
-def test_both_walks_every_k(gpu, group):
-    """the matcher picks its walk by the call's sizes (below 750 k queries: eight lanes per query); the development option knn_group
-    (wc_ctx_set_dev_option) pins it - tests/_match_walk_worker.py runs in a process of its own under each setting: every
-    instantiated k, both kinds of search, trees of one leaf ... two sample stages, against the oracle"""
+def test_both_walks_every_k(gpu):
+    """the matcher's walk with both of its bounds - the early bound (no lists asked for) and the plain k-NN walk (lists asked for) -
+    in a process of its own (tests/_match_walk_worker.py): every instantiated k, both kinds of search, trees of one leaf ... two sample
+    stages, against the oracle"""
     import os
     import subprocess
     import sys
 
     worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_match_walk_worker.py")
-    r = subprocess.run([sys.executable, worker, group], env=dict(os.environ), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    assert r.returncode == 0 and ("walk %s ok" % group) in r.stdout.decode(), r.stdout.decode()[-3000:]
+    r = subprocess.run([sys.executable, worker], env=dict(os.environ), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    assert r.returncode == 0 and "walk ok" in r.stdout.decode(), r.stdout.decode()[-3000:]
 
 
-@pytest.mark.parametrize("group", [0, 1], ids=["lane-per-query", "eight-lanes-per-query"])
-def test_early_bound_of_the_walks_changes_no_pair(gpu, oracle, group):
-    """Round 6: a walk is bounded by the nearest candidate that passes the gates as well as by the k-th distance (the reference takes the FIRST
-    gated neighbour, knn_surfel_matcher.cc:24-46; one set: only candidates with a larger index end the scan, cc:35-38).  Gates that reject the
-    nearest neighbours (a long time gate, a narrow angle, a thin plane gate), gates that reject nothing, k of 1 ... 16, both sets, both walks,
-    the development option knn_early off (0), on (1) and for two sets only (2): every pair list is the oracle's."""
+def test_early_bound_of_the_walks_changes_no_pair(gpu, oracle):
+    """Round 6: a walk whose neighbour lists nobody asked for is bounded by the nearest candidate that passes the gates as well as by the
+    k-th distance (the reference takes the FIRST gated neighbour, knn_surfel_matcher.cc:24-46; one set: only candidates with a larger index
+    end the scan, cc:35-38).  Gates that reject the nearest neighbours (a long time gate, a narrow angle, a thin plane gate), gates that
+    reject nothing, k of 1 ... 16, both sets: the pair list of the call without lists (early bound) and of the call with them (plain k-NN
+    walk, pairs of the same call) is the oracle's."""
     rng = np.random.default_rng(77)
     w = synth.surfel_window(5, 220, seed=31, fixed_patches=150)
     # jitter the normals and centres a little so that the gates cut THROUGH the neighbour lists
@@ -373,7 +372,6 @@ def test_early_bound_of_the_walks_changes_no_pair(gpu, oracle, group):
                 dict(knn_k=1), dict(knn_k=3, time_diff_min=0.3 * dt), dict(knn_k=16, surfel_dist_max=0.01)]
     seen_cut = 0
     try:
-        gpu.set_dev_option("knn_group", group)
         for kw in settings:
             params = oracle.default_params()
             for k_, v in kw.items():
@@ -382,12 +380,10 @@ def test_early_bound_of_the_walks_changes_no_pair(gpu, oracle, group):
             ref_s = oracle.match(w["surf"], w["pose"], w["surf"], w["pose"], True, params)
             ref_f = oracle.match(w["surf"], w["pose"], w["fix_surf"], w["fix_pose"], False, params)
             seen_cut += int(0 < len(ref_s) < len(w["surf"]))
-            for early in (0, 1, 2):
-                gpu.set_dev_option("knn_early", early)
-                assert np.array_equal(gpu.match(w["surf"], w["pose"], w["surf"], w["pose"], True), ref_s), (kw, early)
-                assert np.array_equal(gpu.match(w["surf"], w["pose"], w["fix_surf"], w["fix_pose"], False), ref_f), (kw, early)
+            assert np.array_equal(gpu.match(w["surf"], w["pose"], w["surf"], w["pose"], True), ref_s), (kw, "early")
+            assert np.array_equal(gpu.match(w["surf"], w["pose"], w["fix_surf"], w["fix_pose"], False), ref_f), (kw, "early")
+            assert np.array_equal(gpu.match(w["surf"], w["pose"], w["surf"], w["pose"], True, want_knn=True)[0], ref_s), (kw, "plain")
+            assert np.array_equal(gpu.match(w["surf"], w["pose"], w["fix_surf"], w["fix_pose"], False, want_knn=True)[0], ref_f), (kw, "plain")
         assert seen_cut >= 3
     finally:
-        gpu.set_dev_option("knn_early", 1)
-        gpu.set_dev_option("knn_group", -1)
         gpu.set_params(oracle.default_params())

@@ -40,13 +40,7 @@ struct wc_dev_opts {
   int fx_split = -1;         // node stage of the default extraction: 0 fused, 1 two kernels, -1 by size
   int no_bucket_sort = 0;    // exact path: radix sort instead of the run-binned sort
   int ex_sync = 0;           // extraction: finish waits for the stream instead of the completion ticket
-  int kd_leaf = 0;           // matcher: target leaf size of the kd-tree (0: 8)
-  int knn_group = -1;        // matcher walk: 0 one lane per query, 1 eight lanes per query, -1 by size
-  int knn_sort = -1;         // two-set searches order their queries by leaf: 0 never, 1 always, -1 by the rule in match.hip
-  int knn_early = 1;         // two-set searches bound their walks by the nearest gate-passing candidate too (0: plain k-NN walks, rounds 4 - 5)
   int match_pair_serial = 0; // wc_match_pair runs its searches one after the other on the ctx
-  int match_pair_swap = 0;   // the sliding-window search on the helper instead of the fixed-window one
-  int match_pair_hold = 1;   // wc_match_pair: the fixed-window search's walk waits for the sliding-window search's tree (match.hip: wc_pair_sync)
   int lm_dense = 0;          // round 2's LM step: dense Cholesky of all 12 ns unknowns
   int lm_side_stream = 1;    // two-collective form: the large collective on a side stream (1: with the in-library RCCL binding; 0: never; 2: always - tests)
   int lm_one_collective = 0; // sharded windows: rounds 3 - 5's ONE all-reduce per linearisation (IMU triples sharded too) instead of the two-collective form
@@ -69,12 +63,12 @@ struct wc_ctx {
   wc_buf b_ex_ctrl;  // the extraction's control block (status words, bucket / bin counters): never shared, cleared ahead of time
   wc_buf b_keys[2], b_vals[2], b_sorttmp, b_slots, b_slot_ids, b_slot_keys[2], b_slot_idx[2], b_cand, b_cand_meta,
       b_status, b_misc[8], b_route[4], b_fx[10];
-  // wc_match: what the last search's traversal touched (sampled, see k_knn_tree): wide nodes, leaves, points, exact distances, queries
+  // wc_match: what the last search's traversal touched (sampled, see k_knn_tree_group): wide nodes, leaves, points, exact distances, queries
   double match_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   wc_buf b_kd[10];  // match_tree.inc: planes (dim, value), bucket ids, padded counters, starts x 2, index lists x 2, box heap, leaf ranges
   std::vector<wc_ctx *> batch_subs;  // sub-contexts of wc_extract_surfels_batch_* (own scratch, the parent's stream)
   wc_buf b_batch;
-  wc_buf b_match_half;  // match.hip: the sorted features in single precision, 32 bytes per target (the first look of k_knn_tree)
+  wc_buf b_match_half;  // match.hip: the sorted features in single precision, 32 bytes per target (k_kd_bottom forms the leaf boxes of an over-large bucket from them)
   hipEvent_t ev_knn[2] = {nullptr, nullptr};
   // multi-GPU: the job's communicator (wc_ctx_set_comm / wc_comm_rccl_init)
   wc_comm comm{};

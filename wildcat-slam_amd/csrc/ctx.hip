@@ -67,13 +67,7 @@ const DevOpt kDevOpts[] = {
     {"fx_split", "WC_FX_SPLIT", &wc_dev_opts::fx_split, false},
     {"no_bucket_sort", "WC_NO_BUCKET_SORT", &wc_dev_opts::no_bucket_sort, true},
     {"ex_sync", "WC_EX_SYNC", &wc_dev_opts::ex_sync, true},
-    {"kd_leaf", "WC_KD_LEAF", &wc_dev_opts::kd_leaf, false},
-    {"knn_group", "WC_KNN_GROUP", &wc_dev_opts::knn_group, false},
-    {"knn_early", "WC_KNN_EARLY", &wc_dev_opts::knn_early, false},
-    {"knn_sort", "WC_KNN_SORT", &wc_dev_opts::knn_sort, false},
     {"match_pair_serial", "WC_MATCH_PAIR_SERIAL", &wc_dev_opts::match_pair_serial, true},
-    {"match_pair_swap", "WC_MATCH_PAIR_SWAP", &wc_dev_opts::match_pair_swap, true},
-    {"match_pair_hold", "WC_MATCH_PAIR_HOLD", &wc_dev_opts::match_pair_hold, false},
     {"lm_dense", "WC_LM_DENSE", &wc_dev_opts::lm_dense, true},
     {"lm_one_collective", "WC_LM_ONE_COLLECTIVE", &wc_dev_opts::lm_one_collective, true},
     {"lm_side_stream", "WC_LM_SIDE_STREAM", &wc_dev_opts::lm_side_stream, false},

@@ -4,8 +4,8 @@
 //   * EXACT k = 10 nearest neighbours in squared L2 (FLANN SearchParams(-1, 0.0): exact, sorted), ties by index
 //   * first neighbour passing |dt| >= 0.06, acos(n.n) <= 5deg, |n.(c - c')| <= 0.1 and "pair not seen yet" (cc:25-47)
 // Index: a kd-tree with bounding boxes over the 6-D features, built on the device for every call (match_tree.inc); a query
-// walks it three levels at a time, nearest box first, and prunes against its k-th distance in ALL six dimensions; the first
-// look at a box or a point is fp32 and conservative, the distances that enter the list are summed in fp64 in
+// walks it three levels at a time, eight lanes per query, nearest box first, and prunes against its k-th distance in ALL six
+// dimensions; the look at a box is fp32 and conservative, the distances that enter the list are summed in fp64 in
 // flann::L2_Simple's order, so indices and distances are the reference's bit for bit.  The reference's order dependence
 // (std::set of already-paired surfels, queries visited in order) is a recurrence choice(q) = f(choice(c) : c < q); it is
 // solved by fixed-point iteration on the device.  Latency-bound gather work; no MFMA.
@@ -102,7 +102,7 @@ constexpr uint32_t kNone = 0xFFFFFFFFu;
 struct MatchParams {
   double cs, as;        // centre / angular scale
   double time_min, ang_max, dist_max;
-  double cos_acc, plane_acc;  // EARLY walks (match_tree.inc): accept a candidate when cos >= cos_acc and the plane distance <= plane_acc - ...
+  double cos_acc, plane_acc;  // the EARLY walk (match_tree.inc): accept a candidate when cos >= cos_acc and the plane distance <= plane_acc - ...
   int k, same_set;
 };
 
@@ -204,17 +204,16 @@ __global__ void __launch_bounds__(256) k_emit_pairs(const uint32_t *choice, cons
 
 // ---- the tree of one call: plan on the host (sizes only depend on nt), build on the device --------------------------------------
 struct KdPlan {
-  int T = 0, Bd = 0, D = 0, first = 3;
+  int T = 0, Bd = 0, D = 0;
   int stages[4] = {0, 0, 0, 0}, nstage = 0;
 };
-static KdPlan kd_plan(uint32_t nt, int leaf_opt) {  // leaf_opt: the development option kd_leaf (0: leaves of 4 - 8 points)
+static KdPlan kd_plan(uint32_t nt) {  // leaves of 4 - 8 points
   KdPlan p;
-  const double leaf = leaf_opt > 0 ? (double)leaf_opt : 8.0;
+  const double leaf = 8.0;
   if (nt > 1024u) p.T = std::min(kKdTMax, (int)std::ceil(std::log2((double)nt / 512.0)));
   const double avg = (double)nt / (double)(1u << p.T);
   p.Bd = std::max(0, std::min(kKdBdMax, (int)std::ceil(std::log2(std::max(avg / leaf, 1.0)))));
   p.D = p.T + p.Bd;
-  p.first = p.D % kW ? p.D % kW : kW;
   for (int rem = p.T; rem > 0;) {  // top stages of at most kKdStageMax levels, as even as possible
     const int nst = (rem + kKdStageMax - 1) / kKdStageMax, ts = (rem + nst - 1) / nst;
     p.stages[p.nstage++] = ts;
@@ -274,9 +273,9 @@ static int kd_build(wc_ctx *ctx, const double *d_feat, uint32_t nt, const KdPlan
   k_kd_bottom<1024><<<1u << pl.T, kKdBotNT, 0, st>>>(d_feat, idx_prev, starts_prev, nt, pl.T, pl.Bd, out);
   if (pl.T > 0) k_kd_top_boxes<<<1, 1024, 0, st>>>((float4 *)B[8].p, pl.T);
   WC_HIP(ctx, hipGetLastError());
-  tree.box = (const float4 *)B[8].p, tree.leaf_begin = (const uint32_t *)B[9].p, tree.pts32 = (const float4 *)ctx->b_match_half.p;
+  tree.box = (const float4 *)B[8].p, tree.leaf_begin = (const uint32_t *)B[9].p;
   tree.sfeat = (const double *)ctx->b_misc[3].p, tree.sorig = (const uint32_t *)ctx->b_vals[1].p;
-  tree.D = pl.D, tree.first = pl.first;
+  tree.D = pl.D;
   return WC_OK;
 }
 
@@ -346,8 +345,6 @@ static int match_impl(wc_ctx *ctx, const wc_surfel *d_q_surf, const wc_pose *d_q
   WC_TRY(wc_ensure(ctx, b_world, (size_t)nt * 7 * 8));
   WC_TRY(wc_ensure(ctx, b_gated, (size_t)nq * P.knn_k * 4));
   WC_TRY(wc_ensure(ctx, b_choice, (size_t)nq * 4 * 4));  // choice[2], flags, offsets
-  WC_TRY(wc_ensure(ctx, ctx->b_keys[0], (size_t)nq * 4));
-  WC_TRY(wc_ensure(ctx, ctx->b_vals[0], (size_t)nq * 4));
   WC_TRY(wc_ensure(ctx, ctx->b_status, 64 * 4));
   // ONE control block - [0] pairs, [1] flags, [32..39] "round r changed something", [40..55] the walk's sampled counts (8 x u64) -:
   // one memset in front of the call's first kernel, one copy to pinned memory behind its last
@@ -358,7 +355,7 @@ static int match_impl(wc_ctx *ctx, const wc_surfel *d_q_surf, const wc_pose *d_q
   // 1. features of the targets, 2. their tree - no host round trip: the tree's shape only depends on nt
   WC_HIP(ctx, hipMemsetAsync(status, 0, 64 * 4, st));
   k_features<<<(nt + 255) / 256, 256, 0, st>>>(d_t_surf, d_t_pose, nt, P.center_scale, P.angular_scale, (double *)b_feat.p, (double *)b_world.p, status);
-  const KdPlan plan = kd_plan(nt, ctx->dev.kd_leaf);
+  const KdPlan plan = kd_plan(nt);
   KdTree tree;
   WC_TRY(kd_build(ctx, (const double *)b_feat.p, nt, plan, tree));
   if (psync && same_set && psync->ev && hipEventRecord(psync->ev, st) == hipSuccess) psync->post(true);
@@ -369,34 +366,15 @@ static int match_impl(wc_ctx *ctx, const wc_surfel *d_q_surf, const wc_pose *d_q
   // (margins of the early acceptance: 1e-9 in the angle and relative 1e-9 in the distance, against ~1e-15 between the walk's operands and the gates')
   M.cos_acc = M.ang_max > 1e-8 ? std::cos(std::min(M.ang_max, 3.141592653589793) - 1e-9) + 1e-12 : 2.0;
   M.plane_acc = M.dist_max * (1.0 - 1e-9) - 1e-12;
-  // 3. exact k-NN + gates.  Queries are processed in the order of the tree's leaves, so that the lanes of a wavefront walk the same
-  // nodes: same-set queries through the sorted target permutation, queries of another set (sliding window against fixed window)
-  // by the leaf they would be looked for in first (in time order their walks are unrelated and the loads diverge)
-  const uint32_t *qorder = tree.sorig;
-  // (below ~40 k queries the two passes - locate, radix sort: ~70 us - cost more than the walks gain from them: 16 k queries against 4 k
-  // targets 0.38 -> 0.31 ms in query order, 64 k the same, 250 k 1.23 -> 1.36; the rule depends on the call's sizes alone)
-  // (round 6: NOT with the early bound - its walks are a descent and two or three leaves, and the two passes cost more than coherent
-  // descents save even for queries in RANDOM order: 250 k queries against 62 k targets 0.74 -> 0.69 ms (own order 0.77 -> 0.70), C4's 1 M
-  // against 50 k 1.07 -> 0.98 (0.95), room surfels 0.57 -> 0.56; profiles/dev/ab_sort_random.py, ab_room_match.py)
-  const bool early_walk = !d_knn_idx && ctx->dev.knn_early != 0;
-  const bool sort_queries = !same_set && (ctx->dev.knn_sort >= 0 ? ctx->dev.knn_sort != 0 : (nq >= 40000u && !early_walk));
-  if (!same_set && !sort_queries) qorder = nullptr;
-  if (sort_queries) {
-    uint32_t *k0 = (uint32_t *)ctx->b_keys[0].p, *v0 = (uint32_t *)ctx->b_vals[0].p;
-    uint32_t *qk = (uint32_t *)b_choice.p + 2 * (size_t)nq, *qo = (uint32_t *)b_choice.p + 3 * (size_t)nq;  // (flags / offsets: free until step 5)
-    k_tree_locate<<<(nq + 255) / 256, 256, 0, st>>>(d_q_surf, d_q_pose, nq, tree, M.cs, M.as, k0, v0);
-    // (the Onesweep radix path at every size: rocPRIM's default below 2^20 items is a merge sort of ~19 launches)
-    using cfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 0>;
-    const unsigned end_bit = (unsigned)std::max(1, plan.D);
-    size_t tmp = 0;
-    WC_HIP(ctx, rocprim::radix_sort_pairs<cfg>(nullptr, tmp, k0, qk, v0, qo, (size_t)nq, 0u, end_bit, st));
-    WC_TRY(wc_ensure(ctx, ctx->b_sorttmp, tmp));
-    tmp = ctx->b_sorttmp.cap;
-    WC_HIP(ctx, rocprim::radix_sort_pairs<cfg>(ctx->b_sorttmp.p, tmp, k0, qk, v0, qo, (size_t)nq, 0u, end_bit, st));
-    qorder = qo;
-  }
+  // 3. exact k-NN + gates.  Same-set queries are processed in the order of the tree's leaves (the sorted target permutation), so
+  // that the groups of a wavefront walk the same nodes; queries of another set in their own order.  (Rounds 4 - 5 sorted those by the
+  // leaf they would be looked for in first - a locate pass and a radix sort: with the early bound the walks are a descent
+  // and two or three leaves, and the two passes cost more than coherent descents save: DESIGN 3.3.)
+  const uint32_t *qorder = same_set ? tree.sorig : nullptr;
+  // two sets, nobody asked for the neighbour lists: the walk may stop at the nearest gate-passing candidate (match_tree.inc, EARLY)
+  const bool early = !d_knn_idx;
   // several GPUs: the queries are independent (knn_surfel_matcher.cc:22-48), the targets are replicated;
-  // every rank searches a contiguous share of the queries (in leaf order) and ONE all-gather of the gated lists (4 k bytes per
+  // every rank searches a contiguous share of the queries (in the order of qorder) and ONE all-gather of the gated lists (4 k bytes per
   // query) gives every rank the whole table; the order-dependent de-duplication below then runs replicated
   // (`sharded` is decided at the top, from the replicated arguments alone)
   uint32_t q_begin = 0, q_end = nq;
@@ -410,49 +388,29 @@ static int match_impl(wc_ctx *ctx, const wc_surfel *d_q_surf, const wc_pose *d_q
   WC_TRY(wc_ensure(ctx, ctx->b_route[3], (size_t)(q_end - q_begin + 1) * P.knn_k * 4));
   // (a search of few queries writes the planes of b_gated straight from the walk - ten scattered 4-byte stores per query, what the
   // transposition below exists to avoid at a million queries, are nothing at 100 k, and two launches of the call's tail go)
-  const bool direct_planes = !sharded && (nq < 131072u || (early_walk && ctx->dev.knn_group != 0 && (!same_set || ctx->dev.knn_early == 1)));  // (the group walk stores what k_resolve can read, no more)
+  const bool direct_planes = !sharded && (nq < 131072u || early);  // (the early-bounded walk stores what k_resolve can read, no more)
   uint32_t *gated_shard = sharded ? (uint32_t *)ctx->b_route[3].p : (direct_planes ? nullptr : (uint32_t *)ctx->b_route[2].p);
   const uint32_t nq_mine = q_end - q_begin;
   for (hipEvent_t &e : ctx->ev_knn)
     if (!e) WC_HIP(ctx, hipEventCreate(&e));
-  // pending nodes of a walk: the children of the root's step, then 2^kW - 1 more per further step above the leaves
-  const int wide_steps = plan.D > 0 ? 1 + (plan.D - plan.first) / kW : 0, stack_cap = std::max(1, (1 << plan.first) + (kNch - 1) * std::max(0, wide_steps - 2));
   static const bool tdbg = wc_log_env("WC_MATCH_TIMING");
   const auto t_prep = std::chrono::steady_clock::now();
   if (tdbg) WC_HIP(ctx, hipEventRecord(ctx->ev_knn[0], st));
-  // Which walk: eight lanes per query (match_tree.inc: k_knn_tree_group; every round trip coalesced, eight independent walks per
-  // wavefront, VALU-bound at ~87 % busy) or one lane per query (k_knn_tree).  The two searches of a step-like window at 16 k / 64 k /
-  // 128 k / 250 k / 500 k queries, lane-per-query against group walk: same-set 0.59 / 0.77 / 0.88 / 1.18 / 2.09 against 0.33 / 0.48 /
-  // 0.62 / 0.94 / 1.77 ms, fixed-window 0.62 / 0.96 / 1.13 / 1.35 / 2.28 against 0.31 / 0.54 / 0.80 / 1.23 / 2.15 ms; at a million
-  // queries (C4) 2.06 against 2.02 and 3.50 against 3.96 (profiles/dev/time_match_sizes.py, time_match.py).  The rule depends on the
-  // call's sizes and kind alone - no timing, no history.
   if (psync && !same_set && psync->wait()) WC_HIP(ctx, hipStreamWaitEvent(st, psync->ev, 0));  // (wc_pair_sync: behind the other search's build)
-  const int group_opt = ctx->dev.knn_group;  // (development option: 0 / 1 pins the walk)
-  // (round 6: with the early bound the group walk at every size - its short walks are a descent and two or three leaves, what the lane
-  // walk's fp32 first look and four-wide steps were built to shorten is gone: C4's fixed-window search, 1 M queries, 0.95 -> 0.80 ms)
-  const bool group_walk = group_opt >= 0 ? group_opt != 0 : (early_walk || nq_mine < 750000u || (same_set && nq_mine < 1500000u));
   const int first3 = plan.D % 3 ? plan.D % 3 : 3;
   // Workgroups of ONE wavefront (eight queries): the groups of a workgroup share nothing, and a 256-thread workgroup holds its four
   // wavefront slots and its LDS until the slowest of its 32 walks has ended - the next workgroup waits for all of them.  Measured
   // (profiles/dev/time_match.py pair, time_room_match.py): the step-like pair of searches 1.674 -> 1.605 ms, a room search 0.444 -> 0.439.
   constexpr int kGroupNT = 64;
-  // two sets, nobody asked for the neighbour lists: the walk may stop at the nearest gate-passing candidate (match_tree.inc, EARLY)
-  const bool early = !d_knn_idx && ctx->dev.knn_early != 0 && (!same_set || ctx->dev.knn_early != 2);
-#define WC_KNN_LAUNCH(KK)                                                                                                                            \
-  if (nq_mine && group_walk && early)                                                                                                                \
-    k_knn_tree_group<KK, kGroupNT, true><<<(nq_mine + kGroupNT / 8 - 1) / (kGroupNT / 8), kGroupNT, 0, st>>>(                                        \
-        d_q_surf, d_q_pose, nq, tree, first3, (const double *)b_world.p, nt, M, (uint32_t *)b_gated.p, d_knn_idx, d_knn_d2, qorder, q_begin, q_end,  \
-        gated_shard, stats, status);                                                                                                                 \
-  else if (nq_mine && group_walk)                                                                                                                    \
-    k_knn_tree_group<KK, kGroupNT, false><<<(nq_mine + kGroupNT / 8 - 1) / (kGroupNT / 8), kGroupNT, 0, st>>>(                                       \
-        d_q_surf, d_q_pose, nq, tree, first3, (const double *)b_world.p, nt, M, (uint32_t *)b_gated.p, d_knn_idx, d_knn_d2, qorder, q_begin, q_end,  \
-        gated_shard, stats, status);                                                                                                                 \
-  else if (nq_mine && early)                                                                                                                         \
-    k_knn_tree<KK, true><<<(nq_mine + 63) / 64, 64, (size_t)(kNch + 1 + stack_cap) * 64 * 4, st>>>(d_q_surf, d_q_pose, nq, tree, (const double *)b_world.p, nt, M, (uint32_t *)b_gated.p, d_knn_idx, \
-                                                       d_knn_d2, qorder, q_begin, q_end, gated_shard, stats, status, stack_cap);                     \
-  else if (nq_mine)                                                                                                                                  \
-    k_knn_tree<KK, false><<<(nq_mine + 63) / 64, 64, (size_t)(kNch + 1 + stack_cap) * 64 * 4, st>>>(d_q_surf, d_q_pose, nq, tree, (const double *)b_world.p, nt, M, (uint32_t *)b_gated.p, d_knn_idx, \
-                                                       d_knn_d2, qorder, q_begin, q_end, gated_shard, stats, status, stack_cap);
+#define WC_KNN_LAUNCH(KK)                                                                                                                           \
+  if (nq_mine && early)                                                                                                                             \
+    k_knn_tree_group<KK, kGroupNT, true><<<(nq_mine + kGroupNT / 8 - 1) / (kGroupNT / 8), kGroupNT, 0, st>>>(                                       \
+        d_q_surf, d_q_pose, nq, tree, first3, (const double *)b_world.p, nt, M, (uint32_t *)b_gated.p, d_knn_idx, d_knn_d2, qorder, q_begin, q_end, \
+        gated_shard, stats, status);                                                                                                                \
+  else if (nq_mine)                                                                                                                                 \
+    k_knn_tree_group<KK, kGroupNT, false><<<(nq_mine + kGroupNT / 8 - 1) / (kGroupNT / 8), kGroupNT, 0, st>>>(                                      \
+        d_q_surf, d_q_pose, nq, tree, first3, (const double *)b_world.p, nt, M, (uint32_t *)b_gated.p, d_knn_idx, d_knn_d2, qorder, q_begin, q_end, \
+        gated_shard, stats, status);
   switch (P.knn_k) {  // the reference's k = 10 gets its own instantiation (top-k in 30 registers)
     case 10: WC_KNN_LAUNCH(10); break;
     case 1: WC_KNN_LAUNCH(1); break;
@@ -557,7 +515,7 @@ static int match_impl(wc_ctx *ctx, const wc_surfel *d_q_surf, const wc_pose *d_q
     (void)hipEventElapsedTime(&ms, ctx->ev_knn[0], ctx->ev_knn[1]);
     auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
     const auto t_end = std::chrono::steady_clock::now();
-    fprintf(stderr, "[match] same %d nq %u nt %u: host enqueue of the build %.0f us, launch %.0f us, launch -> done %.0f us (k_knn_tree by events %.0f us)\n",
+    fprintf(stderr, "[match] same %d nq %u nt %u: host enqueue of the build %.0f us, launch %.0f us, launch -> done %.0f us (k_knn_tree_group by events %.0f us)\n",
             same_set, nq, nt, us(t_entry, t_prep), us(t_prep, t_launched), us(t_launched, t_end), ms * 1e3);
   }
   const uint32_t n_found = h_ctl[0], fl = h_ctl[1];
@@ -605,7 +563,7 @@ int wc_match_pair_prepare(wc_ctx *ctx) {
     const int rc = wc_ctx_create(&ctx->P, ctx->device, &ctx->aux);
     if (rc != WC_OK) return wc_fail(ctx, rc, "wc_match_pair: no helper context");
     ctx->aux->dev = ctx->dev;
-    // The helper's stream gets the device's highest priority: its search is prepared (tree, locate, radix passes - small launches)
+    // The helper's stream gets the device's highest priority: its search is prepared (the tree's build - small launches)
     // while the other search's walk fills the chip, and those launches wait for slots behind the walk's workgroups.  What a kernel
     // trace of the odometry step shows with it: launches of 256- and 512-thread workgroups get through (k_kd_bottom 77 us next to the
     // other tree's 127), a launch of 1 024-thread workgroups does not - a CU whose slots are refilled four wavefronts at a time never
@@ -662,7 +620,7 @@ extern "C" int wc_match_pair(wc_ctx *ctx, const wc_surfel *d_sld_surf, const wc_
   } pair_scope(ctx, aux, &psync);
   // (A rendezvous of the two searches in front of their walk kernels was tried in round 3 - grid kernels: 2.50 - 2.76 ms against
   // 2.45 - 2.50 - and again in round 4 with the tree: a kernel trace showed the fixed-window search's locate + radix passes waiting
-  // for wavefront slots behind the other search's k_knn_tree - one Onesweep pass of 250 k keys took 446 us - and its walk starting
+  // for wavefront slots behind the other search's walk - one Onesweep pass of 250 k keys took 446 us - and its walk starting
   // when the other was nearly over; with the first walk held back until the second preparation is through both walks start together
   // at 0.39 ms, last 1.31 / 1.47 ms instead of 1.02 / 1.03, and the pair ends at the same 2.04 ms: the walks are bound by
   // wavefront-slot time (3 906 wavefronts each for 4 096 slots), not by when they start.  Not kept.)
@@ -675,38 +633,26 @@ extern "C" int wc_match_pair(wc_ctx *ctx, const wc_surfel *d_sld_surf, const wc_
       rc = WC_ERR_HIP;
     }
   };
-  // which search runs where: the one on the ctx stream starts at once, the helper's a thread start later (WC_MATCH_PAIR_SWAP: A/B)
-  const bool swap = ctx->dev.match_pair_swap != 0;  // (development option)
-  wc_ctx *c_fix = swap ? ctx : aux, *c_sld = swap ? aux : ctx;
-  auto search_fix = [&] { return wc_match(c_fix, d_sld_surf, d_sld_pose, n_sld, d_fix_surf, d_fix_pose, n_fix, 0, d_pairs_fix, cap_fix, h_n_pairs_fix, nullptr, nullptr); };
-  auto search_sld = [&] { return wc_match(c_sld, d_sld_surf, d_sld_pose, n_sld, d_sld_surf, d_sld_pose, n_sld, 1, d_pairs_sld, cap_sld, h_n_pairs_sld, nullptr, nullptr); };
+  // the sliding-window search on the ctx stream starts at once, the fixed-window search on the helper a thread start later
+  auto search_fix = [&] { return wc_match(aux, d_sld_surf, d_sld_pose, n_sld, d_fix_surf, d_fix_pose, n_fix, 0, d_pairs_fix, cap_fix, h_n_pairs_fix, nullptr, nullptr); };
+  auto search_sld = [&] { return wc_match(ctx, d_sld_surf, d_sld_pose, n_sld, d_sld_surf, d_sld_pose, n_sld, 1, d_pairs_sld, cap_sld, h_n_pairs_sld, nullptr, nullptr); };
   wc_pair_worker *worker = (wc_pair_worker *)ctx->pair_worker;  // (wc_match_pair_prepare; null: no thread could be started)
   bool threaded = worker != nullptr;
   if (threaded) {
     try {
-      worker->start([&] {
-        if (swap)
-          guarded(rc_sld, search_sld);
-        else
-          guarded(rc_fix, search_fix);
-      });
+      worker->start([&] { guarded(rc_fix, search_fix); });
     } catch (...) {
       threaded = false;
     }
   }
-  if (!threaded || ctx->dev.match_pair_hold == 0) psync.post(false);  // (one thread, one search after the other: nothing to hold back, and nobody to wait for)
-  if (swap)
-    guarded(rc_fix, search_fix);
-  else
-    guarded(rc_sld, search_sld);
+  if (!threaded) psync.post(false);  // (one thread, one search after the other: nothing to hold back, and nobody to wait for)
+  guarded(rc_sld, search_sld);
   if (threaded)
     worker->wait();
-  else if (swap)
-    guarded(rc_sld, search_sld);
   else
     guarded(rc_fix, search_fix);
-  if (rc_sld != WC_OK) return c_sld == ctx ? rc_sld : wc_fail(ctx, rc_sld, "wc_match_pair (sliding window): %s", wc_last_error(aux));
-  if (rc_fix != WC_OK) return c_fix == ctx ? rc_fix : wc_fail(ctx, rc_fix, "wc_match_pair (fixed window): %s", wc_last_error(aux));
+  if (rc_sld != WC_OK) return rc_sld;
+  if (rc_fix != WC_OK) return wc_fail(ctx, rc_fix, "wc_match_pair (fixed window): %s", wc_last_error(aux));
   return WC_OK;
 }
 

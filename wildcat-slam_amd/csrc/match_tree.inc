@@ -6,9 +6,9 @@
 // dimensions: ~170 points in ~20 leaves behind ~25 node visits for the same query (profiles/dev/sim_tree.py).
 //
 // Shape: a COMPLETE binary tree of depth D in heap order (node (d, i) = (1 << d) + i), every node a box (6 x [lo, hi], fp32);
-// leaf i holds the sorted targets [leaf_begin[i], leaf_begin[i + 1]).  The walks step two or three levels at a time: the 4 / 8
-// boxes that far below a node are contiguous (192 / 384 bytes).  Exactness never depends on how the tree was built - the boxes
-// are formed from what the leaves really hold - only the speed does.
+// leaf i holds the sorted targets [leaf_begin[i], leaf_begin[i + 1]).  The walk steps three levels at a time: the 8 boxes that
+// far below a node are contiguous (384 bytes).  Exactness never depends on how the tree was built - the boxes are formed from what
+// the leaves really hold - only the speed does.
 // Build (all on the device, no host round trip):
 //   top T levels  split planes from a SAMPLE of the node's points (<= 1024 - every k-th point of the call's order in the first
 //                 stage, the points whose index is a multiple of m in the later ones -, one workgroup per node of the previous
@@ -31,10 +31,9 @@ constexpr int kKdPad = 32;         // bucket counters one per 128-byte line (ato
 struct KdTree {
   const float4 *box;           // heap of boxes, 3 x float4 per node: lo0..lo3 | lo4 lo5 hi0 hi1 | hi2..hi5; empty node: lo0 > hi0
   const uint32_t *leaf_begin;  // 2^D + 1
-  const float4 *pts32;         // 2 x float4 per sorted target: f0..f3 | f4 f5 <target index> 0
   const double *sfeat;         // the sorted features in fp64 (what the exact distance is summed from)
   const uint32_t *sorig;       // sorted position -> target index
-  int D, first;                // depth; levels of the step out of the root (the others take kW)
+  int D;                       // depth
 };
 
 __device__ __forceinline__ uint32_t f2ord(float v) {
@@ -373,7 +372,7 @@ __device__ __forceinline__ void kd_box_store(float4 *box, uint32_t h, const floa
 struct KdOut {
   float4 *box;
   uint32_t *leaf_begin;
-  float4 *pts32;
+  float4 *pts32;  // 2 x float4 per sorted target: f0..f3 | f4 f5 <target index> 0 (the in-place path reads them back for its leaf boxes)
   double *sfeat;
   uint32_t *sorig;
 };
@@ -545,315 +544,16 @@ __device__ __forceinline__ float kd_box_d2(const float4 b0, const float4 b1, con
   return d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3 + d4 * d4 + d5 * d5;
 }
 
-// levels per step of the walk: 2 = the 4 boxes two levels below a node (192 contiguous bytes).  Measured on the odometry step's two
-// searches / a C4 window's: 3 levels (8 boxes, 384 bytes) 2.06 / 5.20 ms, 2 levels 1.99 / 4.84 ms, 1 level 2.30 / 5.47 ms.
-constexpr int kW = 2;
-constexpr int kNch = 1 << kW;
-#define WC_CSWAP(a, b)            \
-  {                               \
-    const uint32_t lo_ = min(a, b); \
-    b = max(a, b);                \
-    a = lo_;                      \
-  }
-// Batcher's odd-even merge sort of 8 keys (19 comparators)
-#define WC_SORT8(k)                                                                                              \
-  WC_CSWAP(k[0], k[1]) WC_CSWAP(k[2], k[3]) WC_CSWAP(k[4], k[5]) WC_CSWAP(k[6], k[7]) WC_CSWAP(k[0], k[2])        \
-  WC_CSWAP(k[1], k[3]) WC_CSWAP(k[4], k[6]) WC_CSWAP(k[5], k[7]) WC_CSWAP(k[1], k[2]) WC_CSWAP(k[5], k[6])        \
-  WC_CSWAP(k[0], k[4]) WC_CSWAP(k[1], k[5]) WC_CSWAP(k[2], k[6]) WC_CSWAP(k[3], k[7]) WC_CSWAP(k[2], k[4])        \
-  WC_CSWAP(k[3], k[5]) WC_CSWAP(k[1], k[2]) WC_CSWAP(k[3], k[4]) WC_CSWAP(k[5], k[6])
-
-__device__ __forceinline__ void kd_sort_keys(uint32_t (&k)[kNch]) {
-  if constexpr (kNch == 8) {
-    WC_SORT8(k)
-  } else if constexpr (kNch == 4) {
-    WC_CSWAP(k[0], k[1]) WC_CSWAP(k[2], k[3]) WC_CSWAP(k[0], k[2]) WC_CSWAP(k[1], k[3]) WC_CSWAP(k[1], k[2])
-  } else {
-    WC_CSWAP(k[0], k[1])
-  }
-}
-
-// the 8 (or 2^ws) children `ws` levels below heap node h: keys = squared box distance (fp32 bits, low 3 bits = child), sorted
-// ascending; children that do not exist or hold nothing: 0xFFFFFFFF
-__device__ __forceinline__ void kd_children(const KdTree &T, uint32_t c0, int nchild, const float *qf, uint32_t (&key)[kNch]) {
-#pragma unroll
-  for (int u = 0; u < kNch; ++u) {
-    key[u] = 0xFFFFFFFFu;
-    if (u < nchild) {
-      const float4 *bp = T.box + (size_t)(c0 + (uint32_t)u) * 3;
-      const float4 b0 = bp[0], b1 = bp[1], b2 = bp[2];
-      if (!(b0.x > b1.z)) key[u] = (__float_as_uint(kd_box_d2(b0, b1, b2, qf)) & ~7u) | (uint32_t)u;
-    }
-  }
-  kd_sort_keys(key);
-}
-
-// the leaf of the tree a query would be looked for in first (nearest child box at every step): the order other-set queries are
-// processed in - neighbouring lanes then walk the same nodes.  (Ordering them by the BUCKET they fall into - a walk through the top
-// planes, 10 us instead of 100 - leaves the lanes of a wavefront ~500 targets apart: the fixed-window search of the odometry step
-// 1.41 -> 1.69 ms, of a C4 window 3.8 -> 5.2 ms.)
-__global__ void __launch_bounds__(256) k_tree_locate(const wc_surfel *q_surf, const wc_pose *q_pose, uint32_t nq, KdTree T, double cs, double as,
-                                                    uint32_t *keys, uint32_t *vals) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nq) return;
-  double f[6];
-  V3 cw, nw;
-  feature6(q_surf[i], q_pose[i], cs, as, f, cw, nw);
-  float qf[6];
-  for (int d = 0; d < 6; ++d) qf[d] = (float)f[d];
-  uint32_t h = 1u;
-  for (int depth = 0; depth < T.D;) {
-    const int ws = depth == 0 ? T.first : kW;
-    uint32_t key[kNch];
-    kd_children(T, h << ws, 1 << ws, qf, key);
-    h = (h << ws) + (key[0] == 0xFFFFFFFFu ? 0u : (key[0] & 7u));
-    depth += ws;
-  }
-  keys[i] = h - (1u << T.D);
-  vals[i] = i;
-}
-
-// exact k-NN + gates through the tree, ONE LANE PER QUERY: a depth-first walk, two levels per step (the 4 boxes below a node
-// are 192 contiguous bytes), nearest child first, pruned against the k-th distance in all six dimensions; above the leaves the
-// 5 range words of the 4 leaves are requested together with their boxes, the leaves that can still hold a neighbour are scanned
-// nearest first (fp32 first look at 4 points per trip, the survivors summed exactly and inserted at ONE code site).
-// Other shapes of this walk were built and measured on the odometry step's 250 k queries (62 k / 250 k targets) and dropped, all
-// exact: (2) eight lanes per query (lane = child box / leaf point, the list spread over the group's registers, one stack per
-// group): every round trip coalesced, but ~500 instructions of control per item for ONE query - issue-bound, 1.7 ms against
-// 1.2 - 1.3, though the best on the room stream (0.76 ms per 40 k queries); (3) packets of eight neighbouring queries sharing one
-// walk: in this metric neighbouring queries are as far apart as their own 10th neighbours, the shared box opens 7 x the nodes -
-// 10 to 30 ms; (4) a wavefront alternating between a node phase and a leaf phase (leaves queued per lane) with a greedy first
-// descent: the phases are half empty and the greedy descent's leaves are scanned twice - 1.2 - 1.5 ms; (5) the points that pass the
-// first look only noted, exact sums and insertions of all lanes together when some lane holds four notes (what round 2's grid
-// kernel gained 15 % with): 128 registers instead of 112, 2.09 against 1.99 ms.
-// Per lane: 2^first + 3 per further step above the leaves stack words in LDS (node << 13 | upper 13 bits of its distance,
-// rounded towards zero: conservative; a pending node lies at least two levels above the leaves: 19 bits hold it up to D = 20).
-// stats (sampled: one wavefront in 64): [0] nodes opened, [1] leaves scanned, [2] points looked at (fp32), [3] exact
-// distances, [4] queries
-template <int K>
-struct TopK {
-  double d[K];
-  uint32_t id[K];
-  int cnt;
-  __device__ __forceinline__ double worst() const { return cnt < K ? 1e300 : d[K - 1]; }
-  // sorted insertion with static indexing (keeps the arrays in registers); order = (distance, index)
-  __device__ __forceinline__ void push(double dist, uint32_t idx) {
-    if (cnt == K && !(dist < d[K - 1] || (dist == d[K - 1] && idx < id[K - 1]))) return;
-    double cd = dist;
-    uint32_t ci = idx;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-      const bool before = cd < d[i] || (cd == d[i] && ci < id[i]);  // empty slots hold (1e300, ~0): always "after"
-      if (before) {
-        const double td = d[i];
-        const uint32_t ti = id[i];
-        d[i] = cd, id[i] = ci;
-        cd = td, ci = ti;
-      }
-    }
-    if (cnt < K) ++cnt;
-  }
-};
-
-// (four wavefronts per SIMD: 112 registers.  Five or six - 102 / 85 registers, the list spilling - are slower: 2.25 / 2.53 ms against
-// 1.99 for the odometry step's two searches)
-// EARLY: see k_knn_tree_group
-template <int K, bool EARLY>
-__global__ void __launch_bounds__(64, K <= 10 ? 4 : 1) k_knn_tree(const wc_surfel *q_surf, const wc_pose *q_pose, uint32_t nq, KdTree T, const double *tworld,
-                                                                 uint32_t nt, MatchParams M, uint32_t *gated, uint32_t *knn_idx, double *knn_d2,
-                                                                 const uint32_t *__restrict__ qorder, uint32_t q_begin, uint32_t q_end,
-                                                                 uint32_t *gated_shard, unsigned long long *stats, uint32_t *status, int stack_cap) {
-  extern __shared__ uint32_t s_dyn[];  // (kNch + 1 + stack_cap) x 64 words: the stack is sized for THIS tree
-  uint32_t (*s_lb)[64] = (uint32_t (*)[64])s_dyn;
-  uint32_t (*s_stack)[64] = (uint32_t (*)[64])(s_dyn + (kNch + 1) * 64);
-  const int lane = threadIdx.x;
-  const uint32_t qi = q_begin + blockIdx.x * 64u + threadIdx.x;
-  const bool live = qi < q_end;
-  const uint32_t q = live ? (qorder ? qorder[qi] : qi) : 0u;
-  double f[6];
-  {
-    V3 cq0, nq0;
-    feature6(q_surf[q], q_pose[q], M.cs, M.as, f, cq0, nq0);
-  }
-  float qf[6];
-  double qmax = 0.0;
-#pragma unroll
-  for (int d = 0; d < 6; ++d) qf[d] = (float)f[d], qmax = fmax(qmax, fabs(f[d]));
-  TopK<K> top;
-  top.cnt = 0;
-#pragma unroll
-  for (int i = 0; i < K; ++i) top.d[i] = 1e300, top.id[i] = 0xFFFFFFFFu;
-  // The first look at a box or a point is taken in fp32 and only has to be conservative: whoever passes is summed exactly, in
-  // fp64 and in flann::L2_Simple's order.  A target on the list has |d_i| <= sqrt(w) in every component (w = the k-th
-  // distance), so its components are at most qmax + sqrt(w) in magnitude; the fp32 images of query and target are off by
-  // 2^-24 of their magnitudes, a difference by delta = 2^-23 (2 qmax + sqrt(w)) including its own rounding, a square by
-  // 2 sqrt(w) delta + delta^2, the six-term fp32 sum by a few 2^-24 of itself.  A box bound is the fp32 image of a target
-  // coordinate: the same bound holds.  (sqrt(w) is bounded by (w + 1) / 2.)
-  auto thr32_of = [&](double w) -> float {
-    if (!(w < 1e30)) return __builtin_inff();
-    const double sw = 0.5 * (w + 1.0), delta = 1.1920928955078125e-7 * (2.0 * qmax + sw) * 1.01;
-    return __double2float_ru(w * (1.0 + 4e-6) + 6.2 * (2.0 * sw * delta + delta * delta) + 1e-30);
-  };
-  float thr32 = __builtin_inff();
-  double ad = 1e300;  // EARLY: the nearest accepted candidate
-  uint32_t ai = 0xFFFFFFFFu;
-  const double tq_e = EARLY ? q_surf[q].t : 0.0;
-  uint32_t st_nodes = 0, st_leaves = 0, st_pts = 0, st_exact = 0;
-  auto scan_leaf = [&](uint32_t b, uint32_t cnt) {
-    ++st_leaves;
-    st_pts += cnt;
-    for (uint32_t off = 0; off < cnt; off += 4u) {
-      float4 pa[4], pb[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const uint32_t ii = b + min(off + (uint32_t)u, cnt - 1u);
-        pa[u] = T.pts32[(size_t)ii * 2], pb[u] = T.pts32[(size_t)ii * 2 + 1];
-      }
-      uint32_t pm = 0;  // which of the four pass the first look
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float d0 = qf[0] - pa[u].x, d1 = qf[1] - pa[u].y, d2 = qf[2] - pa[u].z, d3 = qf[3] - pa[u].w, d4 = qf[4] - pb[u].x, d5 = qf[5] - pb[u].y;
-        const float s32 = d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3 + d4 * d4 + d5 * d5;
-        if (off + (uint32_t)u < cnt && !(s32 > thr32)) pm |= 1u << u;
-      }
-      while (pm) {  // (ONE site for the exact sum and the insertion)
-        const int u = __ffs((int)pm) - 1;
-        pm &= pm - 1u;
-        const float idf = u == 0 ? pb[0].z : (u == 1 ? pb[1].z : (u == 2 ? pb[2].z : pb[3].z));
-        const double *p = T.sfeat + (size_t)(b + off + (uint32_t)u) * 6;
-        double s = 0.0, dn = 0.0, dp = 0.0;
-#pragma unroll
-        for (int d = 0; d < 6; ++d) {
-          const double pv = p[d], df = f[d] - pv;
-          s += df * df;
-          if (EARLY && d >= 3) dn += f[d] * pv;
-          if (EARLY && d < 3) dp += f[d + 3] * df;
-        }
-        ++st_exact;
-        const uint32_t cid = __float_as_uint(idf);
-        bool take = !(s > top.worst());
-        if (EARLY) take = take && (s < ad || (s == ad && cid < ai));
-        if (take) {
-          top.push(s, cid);
-          double bw = top.worst();
-          if (EARLY) {
-            bool acc = dn * M.as * M.as >= M.cos_acc && fabs(dp) * M.as * M.cs <= M.plane_acc - 1e-9 * qmax * M.cs && (!M.same_set || cid > q);
-            if (acc) acc = !(fabs(tworld[(size_t)cid * 7 + 6] - tq_e) < M.time_min);
-            if (acc) ad = s, ai = cid;  // (taken: in front of the accepted one so far)
-            bw = fmin(bw, ad);
-          }
-          thr32 = thr32_of(bw);
-        }
-      }
-    }
-  };
-  if (live) {
-    if (T.D == 0) {
-      scan_leaf(0u, nt);
-    } else {
-      int sp = 0;
-      s_stack[sp++][lane] = 1u << 13;  // the root, distance 0
-      while (sp > 0) {
-        const uint32_t en = s_stack[--sp][lane];
-        if (__uint_as_float((en & 0x1FFFu) << 18) > thr32) continue;
-        const uint32_t h = en >> 13;
-        const int depth = 31 - __clz((int)h);
-        const int ws = depth == 0 ? T.first : kW;
-        const int nchild = 1 << ws;
-        const uint32_t c0 = h << ws;
-        const bool bottom = depth + ws == T.D;
-        ++st_nodes;
-        uint32_t key[kNch];
-#pragma unroll
-        for (int u = 0; u < kNch; ++u) {
-          key[u] = 0xFFFFFFFFu;
-          if (u < nchild) {
-            const float4 *bp = T.box + (size_t)(c0 + (uint32_t)u) * 3;
-            const float4 b0 = bp[0], b1 = bp[1], b2 = bp[2];
-            if (!(b0.x > b1.z)) key[u] = (__float_as_uint(kd_box_d2(b0, b1, b2, qf)) & ~7u) | (uint32_t)u;
-          }
-        }
-        if (bottom) {
-          // (the leaves' ranges arrive with their boxes; they are looked up by child through LDS: a register array would need a
-          // dynamic index)
-          const uint32_t l0 = c0 - (1u << T.D);
-#pragma unroll
-          for (int u = 0; u <= kNch; ++u)
-            if (u <= nchild) s_lb[u][lane] = T.leaf_begin[l0 + (uint32_t)u];
-        }
-        kd_sort_keys(key);
-        if (bottom) {
-          // leaves: nearest first, each against the k-th distance as it stands (ONE scan site: the keys move down a place per leaf)
-#pragma unroll 1
-          for (int s = 0; s < kNch; ++s) {
-            const uint32_t kk = key[0];
-            if (kk == 0xFFFFFFFFu || __uint_as_float(kk & ~7u) > thr32) break;
-            const uint32_t u = kk & 7u, lb = s_lb[u][lane], le = s_lb[u + 1u][lane];
-            if (le > lb) scan_leaf(lb, le - lb);
-#pragma unroll
-            for (int u = 0; u + 1 < kNch; ++u) key[u] = key[u + 1];
-            key[kNch - 1] = 0xFFFFFFFFu;
-          }
-        } else {
-          // farthest first onto the stack: the nearest is opened next
-#pragma unroll
-          for (int s = kNch - 1; s >= 0; --s) {
-            if (key[s] == 0xFFFFFFFFu || __uint_as_float(key[s] & ~7u) > thr32) continue;
-            if (sp < stack_cap)
-              s_stack[sp++][lane] = ((c0 + (key[s] & 7u)) << 13) | ((key[s] >> 18) & 0x1FFFu);
-            else
-              atomicOr(&status[1], 8u);  // (cannot happen: the host sizes the stack for the tree's depth)
-          }
-        }
-      }
-    }
-  }
-  if (stats && (blockIdx.x & 63u) == 0u) {
-    unsigned long long v[5] = {st_nodes, st_leaves, st_pts, st_exact, live ? 1ull : 0ull};
-    for (int j = 0; j < 5; ++j) {
-      for (int m = 1; m < 64; m <<= 1) v[j] += __shfl_xor(v[j], m);
-      if (lane == 0) atomicAdd(&stats[j], v[j]);
-    }
-  }
-  if (!live) return;
-  // (the world-frame centre / normal of the query are formed again here rather than kept in 14 registers through the walk)
-  V3 cq, nq_w;
-  feature6(q_surf[q], q_pose[q], M.cs, M.as, f, cq, nq_w);
-  const double tq = q_surf[q].t;
-  // Q10: FLANN leaves the tail of the result untouched (zero-initialised) when fewer than k targets exist
-  uint32_t out = 0;
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    const uint32_t c = (j < top.cnt) ? top.id[j] : 0u;
-    if (knn_idx) {
-      knn_idx[(size_t)q * K + j] = c;
-      knn_d2[(size_t)q * K + j] = (j < top.cnt) ? top.d[j] : 0.0;
-    }
-    const double *w = tworld + (size_t)c * 7;
-    if (fabs(w[6] - tq) < M.time_min) continue;                                      // cc:26
-    const V3 nc = mk3(w[3], w[4], w[5]);
-    if (acos(dot(nq_w, nc)) > M.ang_max) continue;                                    // cc:29, surfel.h:105-107
-    if (fabs(dot(nq_w, cq - mk3(w[0], w[1], w[2]))) > M.dist_max) continue;           // cc:32
-    if (gated_shard)
-      gated_shard[(size_t)(qi - q_begin) * K + (out++)] = c;
-    else
-      gated[(size_t)(out++) * nq + q] = c;
-  }
-  for (; out < (uint32_t)K; ++out) {
-    if (gated_shard)
-      gated_shard[(size_t)(qi - q_begin) * K + out] = kNone;
-    else
-      gated[(size_t)out * nq + q] = kNone;
-  }
-}
-
-// The same walk with EIGHT LANES PER QUERY.  A search of 40 k queries is 630 wavefronts on a chip with
-// 4 096 slots: the lane-per-query walk then lasts as long as ONE wavefront's chain of ~80 steps of up to ten dependent round trips
-// (0.9 ms of the room stream's 1.12 ms search, whatever the number of queries).  Here the group's lane j takes child j of a node
-// (three levels per step: the 8 boxes are 384 contiguous bytes, 48 per lane) or point j of a leaf (its fp64 feature, 48 bytes per
-// lane, summed exactly at once: a fp32 first look would be a second dependent round trip for whoever passes), the survivors
-// are ranked inside the group, the k best live in the group's registers (two entries per lane) and the pending work is ONE stack per group in LDS (nodes and leaves alike, farthest
-// pushed first): every round trip is one coalesced load, a wavefront is eight independent walks, and eight times as many
-// wavefronts hide each other's latency.  It is VALU-bound (87 % busy on the odometry step's fixed-window search): ~260 vector
+// exact k-NN + gates through the tree, EIGHT LANES PER QUERY: a depth-first walk, nearest box first, pruned against the k-th
+// distance in all six dimensions.  The group's lane j takes child j of a node (three levels per step: the 8 boxes are 384 contiguous
+// bytes, 48 per lane) or point j of a leaf (its fp64 feature, 48 bytes per lane, summed exactly at once: a fp32 first look would be a
+// second dependent round trip for whoever passes), the survivors are ranked inside the group, the k best live in the group's registers
+// (two entries per lane) and the pending work is ONE stack per group in LDS (nodes and leaves alike, farthest pushed first): every
+// round trip is one coalesced load, a wavefront is eight independent walks, and eight times as many wavefronts hide each other's
+// latency.  (Rounds 4 - 5 also had a walk of ONE lane per query: a search of 40 k queries is 630 of its
+// wavefronts on a chip with 4 096 slots, and it lasted as long as ONE wavefront's chain of ~80 steps of up to ten dependent round
+// trips - 0.9 ms of the room stream's 1.12 ms search.  That walk and the other shapes that were built and measured: DESIGN 3.3.)
+// It is VALU-bound (87 % busy on the odometry step's fixed-window search): ~260 vector
 // instructions per round of a wavefront, in which each of its eight groups takes ONE item - so both the node and the leaf code run
 // in nearly every round.  What the round costs was found in the ISA (llvm-objdump): a sorted list was ~125 instructions and twelve
 // ds_bpermute per insertion - now unsorted, the k-th entry looked for again after an insertion (find_worst: ~25) and sorted once at
@@ -865,8 +565,8 @@ __global__ void __launch_bounds__(64, K <= 10 ? 4 : 1) k_knn_tree(const wc_surfe
 // the rounds of a wavefront per query 67 -> 41 and 80 -> 62, the time unchanged - such a round was cheap already, the branches of a
 // group that has nothing to do are skipped when no other group takes them); ONE kind of item per round, the kind most of the
 // wavefront's groups have on top, the others waiting (0.98 / 1.23 against 0.96 / 1.24 ms: the rounds get cheaper and more).
-// match_impl takes this walk below 750 k queries (1.5 M for a same-set search).  Exact, same lists: the order (distance, index) is
-// total.
+// Exact: the order (distance, index) is total, so the list does not depend on the order in which the walk meets the targets.
+// stats (sampled: one wavefront in 64): [0] nodes opened, [1] leaves scanned, [2] points looked at, [3] exact distances, [4] queries
 // Round 5, built, measured and taken out again - a REFILLING launch: one wavefront per slot of the chip (6 144), a group whose walk has
 // ended stores its list as it stands (a second kernel, one lane per query, sorts and gates: 50 - 69 us at 250 k queries) and takes the
 // next place of the walk order from the wavefront's range, the wavefront chunks of 8 - 64 places from one counter; the features by place
@@ -952,7 +652,13 @@ __global__ void __launch_bounds__(NT, 6) k_knn_tree_group(const wc_surfel *q_sur
     i = max(i, kd_dpp<0x141>(i));
     ld_worst = d, li_worst = i;
   };
-  auto thr32_of = [&](double w) -> float {  // (the bound of k_knn_tree's first look)
+  // The look at a box is taken in fp32 and only has to be conservative: whatever passes is summed exactly, in fp64 and in
+  // flann::L2_Simple's order.  A target the walk still needs has |d_i| <= sqrt(w) in every component (w = the walk's bound), so its
+  // components are at most qmax + sqrt(w) in magnitude; a box bound is the fp32 image of a target coordinate, and the fp32 images of
+  // query and bound are off by 2^-24 of their magnitudes: a difference by delta = 2^-23 (2 qmax + sqrt(w)) including its own
+  // rounding, a square by 2 sqrt(w) delta + delta^2, the six-term fp32 sum by a few 2^-24 of itself.  (sqrt(w) is bounded by
+  // (w + 1) / 2.)
+  auto thr32_of = [&](double w) -> float {
     if (!(w < 1e30)) return __builtin_inff();
     const double sw = 0.5 * (w + 1.0), delta = 1.1920928955078125e-7 * (2.0 * qmax + sw) * 1.01;
     return __double2float_ru(w * (1.0 + 4e-6) + 6.2 * (2.0 * sw * delta + delta * delta) + 1e-30);
