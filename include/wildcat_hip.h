@@ -317,6 +317,40 @@ int wc_window_solve(wc_ctx *ctx, double *h_x_inout, wc_solve_summary *summary, d
  * buffer (layout: wc_window_build_sharded above) and once per candidate-cost evaluation (one double).  NULL removes it. */
 int wc_window_set_allreduce(wc_ctx *ctx, int (*fn)(void *user, double *d_buf, uint64_t count), void *user);
 
+/* voxel-downsampled point map (device resident) ------------------------------------------------------------------------------- */
+/* The accumulated map of the reference's README (pics/point_cloud_accumulated.jpg): every sweep undistorted with its final poses and
+ * published on /scan_in_imu_frame (lidar_odometry.cc:584-595), gathered in world coordinates, thinned by DownSamplingVoxel
+ * (src/odometry/surfel_extraction.cc:228-261: every occupied voxel replaced by the centroid of its points).  The reference leaves the
+ * accumulation to RViz and DownSamplingVoxel has no callers; here the map is a hash table in HBM that every insert grows (csrc/map.hip).
+ *   voxel of a point  VoxelLoc(p, v) = floor((double)p / v) per axis (surfel_extraction.h:59-64)
+ *   centroid          center / count (:258) from per-voxel 64-bit fixed-point sums (unit 2^-32 m, relative to a point of the voxel on
+ *                     the 2^-10 m grid) rounded to float once: order independent, so the map after inserting A, B, C is, bit for bit,
+ *                     the map of A u B u C inserted in any split, order or schedule
+ *   limits            0.01 <= v <= 4.0 (below 0.01 the reference does nothing, :232-234) else WC_ERR_ARG; |k| < 2^20 per axis (keys
+ *                     packed 21 bits per axis).  A point with a non-finite coordinate or a key out of range is NOT inserted and is
+ *                     counted (the reference's int32 cast has no range check); at most 2^30 points per voxel
+ * Several maps per context are independent.  Every call works on the ctx's stream. */
+typedef struct wc_map wc_map;
+/* reserve_voxels: voxels the table holds before its first growth (0: none) */
+int wc_map_create(wc_ctx *ctx, double voxel, uint64_t reserve_voxels, wc_map **out);
+int wc_map_destroy(wc_ctx *ctx, wc_map *m);
+/* DownSamplingVoxel's accumulation (:236-254) for the points of `pts` (DEVICE pointers, any xyz_stride >= 12 that is a multiple of 4:
+ * the 48-byte hilti_ros::Point or packed xyz; pts->time is ignored and may be NULL).  h_n_rejected (may be NULL) receives the number
+ * of this call's points that were not inserted; asking for it waits for the call, passing NULL returns without waiting.  The table
+ * grows on the device before an insert that could fill more than half of it. */
+int wc_map_insert(wc_ctx *ctx, wc_map *m, const wc_points *pts, uint64_t *h_n_rejected);
+/* occupied voxels and points inserted so far (both may be NULL); waits for the ctx stream */
+int wc_map_size(wc_ctx *ctx, wc_map *m, uint64_t *h_voxels, uint64_t *h_points);
+/* h_info[4] = {table slots, growths so far, points rejected so far, bytes of HBM the table holds}; waits for the ctx stream */
+int wc_map_info(wc_ctx *ctx, wc_map *m, uint64_t h_info[4]);
+/* the map as DownSamplingVoxel's output (:255-260), in ascending (kx, ky, kz) order (the reference's is hash-map order):
+ * d_xyz = n x 3 float centroids, d_count = n point counts, d_keys (may be NULL) = n x 3 voxel indices; *h_n = n.
+ * WC_ERR_CAPACITY with *h_n = the needed count when cap < n.  Reads the size back, then enqueues its kernels on the ctx stream and
+ * returns: the outputs are complete for whatever is ordered behind it on that stream (wc_d2h, wc_sync) */
+int wc_map_export(wc_ctx *ctx, wc_map *m, float *d_xyz, uint32_t *d_count, int32_t *d_keys, uint64_t cap, uint64_t *h_n);
+/* empties the map (the table keeps its size) */
+int wc_map_clear(wc_ctx *ctx, wc_map *m);
+
 #ifdef __cplusplus
 }
 #endif

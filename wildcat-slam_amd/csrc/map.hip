@@ -1,0 +1,459 @@
+// map.hip — device-resident voxel-downsampled point map: the reference's DownSamplingVoxel (src/odometry/surfel_extraction.cc:228-261,
+// every occupied voxel of side `voxel_size` replaced by the centroid of its points) applied to the union of every cloud inserted so
+// far - the accumulated map the reference's RViz builds from /scan_in_imu_frame (lidar_odometry.cc:584-595).
+//
+// Table (one per wc_map): open addressing, linear probing, a power-of-two number of slots.
+//   keys[cap]     u64 packed voxel key (21 bits per axis, offset 2^20: ascending packed key = ascending (kx, ky, kz)); ~0 = empty
+//   pay[cap][4]   i64 moments of the voxel's points: sum of q = round((p - r) * 2^32) per axis, count
+// r is the voxel centre rounded to 1/1024 m, a function of the key alone, so every point's q is a deterministic function of the point:
+// integer addition is associative, and the map is bit-identical however the same points are split across calls, ordered or
+// scheduled.  |p - r| <= v / 2 + 2^-11 <= 2.0005 m, so a voxel holds up to 2^30 points before a sum could overflow.
+// Kernels (all on the ctx's stream):
+//   k_map_insert    tiles of 512 consecutive points per workgroup: each lane folds its 2 points into a run while the voxel stays the
+//                   same, the tile's voxels are pre-aggregated in an LDS hash (1024 slots, at most half full), then ONE global probe
+//                   and four integer atomic adds per distinct voxel of the tile; counters once per workgroup
+//   k_map_rehash    growth: every occupied slot of the old table into the new one (distinct keys: plain stores of the payload)
+//   k_map_compact   export: occupied slots -> (key, slot) pairs (LDS staging, one atomic per workgroup); rocPRIM radix sort by key
+//   k_map_centroids export: centroid = r + sum / (count * 2^32) in fp64, rounded once to float; count; key (optional)
+// Growth policy: before an insert of n points the host takes an upper bound B of the occupied slots (the exact count of the last
+// completed insert's read-back plus every point inserted after it); when 2 (B + n) > cap the table is rehashed into the smallest power
+// of two >= 2 (B + n) slots.  The table is therefore at most half full at every probe, and an insert never runs out of room.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+
+#include <rocprim/rocprim.hpp>
+
+#include "ctx.h"
+
+struct wc_map {
+  wc_ctx *ctx = nullptr;
+  double voxel = 0;
+  uint64_t cap = 0;                  // slots (power of two)
+  unsigned long long *keys = nullptr;
+  long long *pay = nullptr;          // 4 per slot: sum qx, qy, qz, count
+  unsigned long long *ctr = nullptr; // device counters, each on a 128-byte line of its own (see kCtr*)
+  unsigned long long *h_ctr = nullptr;  // pinned copy of the counters, written after every insert
+  hipEvent_t ev_ctr = nullptr;       // recorded after that copy
+  bool ctr_pending = false;          // an insert's copy has been enqueued and not yet taken into occ_known
+  uint64_t occ_known = 0;            // occupied slots at the last completed read-back ...
+  uint64_t pts_since = 0;            // ... plus the points of every insert after it bound the occupied slots
+  uint64_t pts_after_copy = 0;       // points of the inserts enqueued behind the pending copy
+  uint64_t growths = 0;
+  int cus = 256;
+  wc_buf b_pairs[4], b_tmp, b_cnt;   // export scratch: keys in / out, slot indices in / out; rocPRIM temporary; compaction counter
+};
+
+namespace {
+
+constexpr int kMapThreads = 256;
+constexpr int kMapPts = 2;                         // consecutive points per lane
+constexpr int kMapTile = kMapThreads * kMapPts;    // points per tile
+constexpr int kMapLds = 2 * kMapTile;              // LDS hash slots: a tile's voxels fill at most half of it
+constexpr unsigned long long kMapEmpty = ~0ull;
+constexpr double kMapUnit = 4294967296.0;          // fixed-point unit: 2^-32 m
+constexpr double kMapKeyLim = 1048576.0;           // |k| < 2^20
+constexpr int kMapKeyOff = 1 << 20;
+constexpr int kCtrOcc = 0, kCtrPts = 16, kCtrRej = 32, kCtrRejCall = 48, kCtrLost = 56, kCtrWords = 64;  // u64 word of each counter
+constexpr int kCompactChunk = 2048;                // slots per workgroup of k_map_compact
+
+__device__ __forceinline__ unsigned long long map_hash(unsigned long long k) {  // splitmix64 finaliser
+  k ^= k >> 30;
+  k *= 0xbf58476d1ce4e5b9ull;
+  k ^= k >> 27;
+  k *= 0x94d049bb133111ebull;
+  k ^= k >> 31;
+  return k;
+}
+// reference point of a voxel on the 2^-10 m grid: the voxel centre, rounded; a function of (k, v) alone
+__device__ __forceinline__ double map_ref(int k, double v) { return rint(((double)k + 0.5) * v * 1024.0) * (1.0 / 1024.0); }
+__device__ __forceinline__ int map_unpack(unsigned long long key, int axis) {
+  return (int)((key >> (42 - 21 * axis)) & 0x1FFFFFull) - kMapKeyOff;
+}
+
+// one global probe: the slot of `key`, claimed if it is new (fresh += 1).  The table is at most half full, so the loop ends; the bound
+// on its length only guards against a broken invariant (the key is then dropped and ctr[kCtrLost] counts it)
+__device__ __forceinline__ unsigned long long map_slot(unsigned long long *keys, unsigned long long mask, unsigned long long key, unsigned &fresh) {
+  unsigned long long h = map_hash(key) & mask;
+  for (unsigned long long probe = 0; probe <= mask; ++probe) {
+    unsigned long long cur = keys[h];  // (a stale EMPTY is settled by the CAS; a key once written never changes during an insert)
+    if (cur == kMapEmpty) {
+      cur = atomicCAS(&keys[h], kMapEmpty, key);
+      if (cur == kMapEmpty) {
+        ++fresh;
+        return h;
+      }
+    }
+    if (cur == key) return h;
+    h = (h + 1) & mask;
+  }
+  return kMapEmpty;
+}
+
+__device__ __forceinline__ void lds_add(unsigned long long *lk, unsigned long long *ls, unsigned *lc, unsigned long long key,
+                                        long long qx, long long qy, long long qz, unsigned n) {
+  unsigned s = (unsigned)map_hash(key) & (kMapLds - 1);
+  while (true) {
+    unsigned long long cur = lk[s];
+    if (cur == kMapEmpty) cur = atomicCAS(&lk[s], kMapEmpty, key);
+    if (cur == kMapEmpty || cur == key) break;
+    s = (s + 1) & (kMapLds - 1);
+  }
+  atomicAdd(&ls[s], (unsigned long long)qx);
+  atomicAdd(&ls[kMapLds + s], (unsigned long long)qy);
+  atomicAdd(&ls[2 * kMapLds + s], (unsigned long long)qz);
+  atomicAdd(&lc[s], n);
+}
+
+__global__ void __launch_bounds__(kMapThreads) k_map_insert(wc_points pts, double v, unsigned long long *keys, long long *pay,
+                                                            unsigned long long mask, unsigned long long *ctr) {
+  __shared__ unsigned long long lk[kMapLds];
+  __shared__ unsigned long long ls[3 * kMapLds];
+  __shared__ unsigned lc[kMapLds];
+  __shared__ unsigned c_fresh, c_pts, c_rej;
+  const int t = threadIdx.x;
+  for (int s = t; s < kMapLds; s += kMapThreads) {
+    lk[s] = kMapEmpty;
+    ls[s] = ls[kMapLds + s] = ls[2 * kMapLds + s] = 0;
+    lc[s] = 0;
+  }
+  if (t == 0) c_fresh = c_pts = c_rej = 0;
+  unsigned fresh = 0, n_ok = 0, n_rej = 0;
+  const uint64_t tiles = (pts.n + kMapTile - 1) / kMapTile;
+  for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    __syncthreads();
+    // pass 1: the lane's consecutive points as runs of one voxel, each run into the LDS hash
+    unsigned long long run_key = kMapEmpty;
+    long long sx = 0, sy = 0, sz = 0;
+    unsigned rn = 0;
+    const uint64_t i0 = tile * kMapTile + (uint64_t)t * kMapPts;
+#pragma unroll
+    for (int j = 0; j < kMapPts; ++j) {
+      const uint64_t i = i0 + j;
+      if (i >= pts.n) break;
+      const float *f = (const float *)((const char *)pts.xyz + i * pts.xyz_stride);
+      const double x = (double)f[0], y = (double)f[1], z = (double)f[2];
+      // VoxelLoc (surfel_extraction.h:59-64): floor((double)p / v), true fp64 division; NaN / inf / |k| >= 2^20 fail the compares
+      const double fx = floor(x / v), fy = floor(y / v), fz = floor(z / v);
+      if (!(fx > -kMapKeyLim && fx < kMapKeyLim && fy > -kMapKeyLim && fy < kMapKeyLim && fz > -kMapKeyLim && fz < kMapKeyLim)) {
+        ++n_rej;
+        continue;
+      }
+      ++n_ok;
+      const int kx = (int)fx, ky = (int)fy, kz = (int)fz;
+      const unsigned long long key = ((unsigned long long)(kx + kMapKeyOff) << 42) | ((unsigned long long)(ky + kMapKeyOff) << 21) |
+                                     (unsigned long long)(kz + kMapKeyOff);
+      const long long qx = llrint((x - map_ref(kx, v)) * kMapUnit), qy = llrint((y - map_ref(ky, v)) * kMapUnit),
+                      qz = llrint((z - map_ref(kz, v)) * kMapUnit);
+      if (key != run_key) {
+        if (rn) lds_add(lk, ls, lc, run_key, sx, sy, sz, rn);
+        run_key = key, sx = sy = sz = 0, rn = 0;
+      }
+      sx += qx, sy += qy, sz += qz, ++rn;
+    }
+    if (rn) lds_add(lk, ls, lc, run_key, sx, sy, sz, rn);
+    __syncthreads();
+    // pass 2: one global probe and four integer atomics per distinct voxel of the tile; the LDS hash is cleared behind it
+    for (int s = t; s < kMapLds; s += kMapThreads) {
+      const unsigned long long key = lk[s];
+      if (key == kMapEmpty) continue;
+      const unsigned long long h = map_slot(keys, mask, key, fresh);
+      if (h != kMapEmpty) {
+        unsigned long long *p = (unsigned long long *)pay + 4 * h;
+        atomicAdd(p + 0, ls[s]);
+        atomicAdd(p + 1, ls[kMapLds + s]);
+        atomicAdd(p + 2, ls[2 * kMapLds + s]);
+        atomicAdd(p + 3, (unsigned long long)lc[s]);
+      } else {
+        atomicAdd(ctr + kCtrLost, 1ull);
+      }
+      lk[s] = kMapEmpty;
+      ls[s] = ls[kMapLds + s] = ls[2 * kMapLds + s] = 0;
+      lc[s] = 0;
+    }
+  }
+  if (fresh) atomicAdd(&c_fresh, fresh);
+  if (n_ok) atomicAdd(&c_pts, n_ok);
+  if (n_rej) atomicAdd(&c_rej, n_rej);
+  __syncthreads();
+  if (t == 0) {
+    if (c_fresh) atomicAdd(ctr + kCtrOcc, (unsigned long long)c_fresh);
+    if (c_pts) atomicAdd(ctr + kCtrPts, (unsigned long long)c_pts);
+    if (c_rej) {
+      atomicAdd(ctr + kCtrRej, (unsigned long long)c_rej);
+      atomicAdd(ctr + kCtrRejCall, (unsigned long long)c_rej);
+    }
+  }
+}
+
+// growth: the old table's occupied slots into the new one (empty keys, zero payload); keys are distinct, so the payload is stored plainly
+__global__ void __launch_bounds__(256) k_map_rehash(const unsigned long long *okeys, const long long *opay, uint64_t ocap,
+                                                    unsigned long long *keys, long long *pay, unsigned long long mask) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ocap) return;
+  const unsigned long long key = okeys[i];
+  if (key == kMapEmpty) return;
+  unsigned fresh = 0;
+  const unsigned long long h = map_slot(keys, mask, key, fresh);
+  if (h == kMapEmpty) return;  // (cannot happen: the new table has room for every old key)
+  const longlong2 *src = (const longlong2 *)(opay + 4 * i);
+  longlong2 *dst = (longlong2 *)(pay + 4 * h);
+  dst[0] = src[0];
+  dst[1] = src[1];
+}
+
+// export, step 1: (key, slot) of every occupied slot, staged in LDS per chunk, one atomic per workgroup for its output range
+__global__ void __launch_bounds__(256) k_map_compact(const unsigned long long *keys, uint64_t cap, unsigned long long *out_keys,
+                                                     uint32_t *out_slots, uint64_t n_out, unsigned long long *d_cnt) {
+  __shared__ unsigned long long sk[kCompactChunk];
+  __shared__ uint32_t ss[kCompactChunk];
+  __shared__ unsigned n_local;
+  __shared__ unsigned long long base;
+  if (threadIdx.x == 0) n_local = 0;
+  __syncthreads();
+  const uint64_t s0 = (uint64_t)blockIdx.x * kCompactChunk;
+  for (int j = threadIdx.x; j < kCompactChunk; j += blockDim.x) {
+    const uint64_t s = s0 + j;
+    if (s >= cap) break;
+    const unsigned long long key = keys[s];
+    if (key == kMapEmpty) continue;
+    const unsigned at = atomicAdd(&n_local, 1u);
+    sk[at] = key;
+    ss[at] = (uint32_t)s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) base = n_local ? atomicAdd(d_cnt, (unsigned long long)n_local) : 0;
+  __syncthreads();
+  for (unsigned j = threadIdx.x; j < n_local && base + j < n_out; j += blockDim.x) {
+    out_keys[base + j] = sk[j];
+    out_slots[base + j] = ss[j];
+  }
+}
+
+// export, step 3: the sorted voxels' centroids - the reference's center / count (surfel_extraction.cc:258) from the exact integer
+// sums, formed in fp64 and rounded to float once
+__global__ void __launch_bounds__(256) k_map_centroids(const unsigned long long *skeys, const uint32_t *sslots, uint64_t n, const long long *pay,
+                                                       double v, float *xyz, uint32_t *count, int32_t *keys_out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long key = skeys[i];
+  const long long *p = pay + 4 * (uint64_t)sslots[i];
+  const double c = (double)p[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const int k = map_unpack(key, a);
+    xyz[3 * i + a] = (float)(map_ref(k, v) + (double)p[a] / (c * kMapUnit));
+    if (keys_out) keys_out[3 * i + a] = k;
+  }
+  count[i] = (uint32_t)p[3];
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------
+int map_alloc(wc_ctx *ctx, void **p, size_t bytes) {
+  *p = nullptr;
+  if (ctx->pool_ok && hipMallocFromPoolAsync(p, bytes, ctx->pool, ctx->stream) == hipSuccess) return WC_OK;
+  (void)hipGetLastError();
+  *p = nullptr;
+  WC_HIP(ctx, hipMalloc(p, bytes));
+  return WC_OK;
+}
+void map_free(wc_ctx *ctx, void *p) {
+  if (!p) return;
+  if (ctx->pool_ok) {  // (pool blocks and plain blocks alike: hipFreeAsync releases either, in stream order)
+    if (hipFreeAsync(p, ctx->stream) == hipSuccess) return;
+    (void)hipGetLastError();
+  }
+  (void)hipStreamSynchronize(ctx->stream);
+  (void)hipFree(p);
+}
+uint64_t pow2_at_least(uint64_t x) {
+  uint64_t c = 1;
+  while (c < x) c <<= 1;
+  return c;
+}
+// a fresh table of `cap` slots (empty keys, zero payload), enqueued on the ctx stream
+int map_table(wc_ctx *ctx, uint64_t cap, unsigned long long **keys, long long **pay) {
+  WC_TRY(map_alloc(ctx, (void **)keys, cap * 8));
+  int rc = map_alloc(ctx, (void **)pay, cap * 32);
+  if (rc != WC_OK) {
+    map_free(ctx, *keys);
+    *keys = nullptr;
+    return rc;
+  }
+  WC_HIP(ctx, hipMemsetAsync(*keys, 0xFF, cap * 8, ctx->stream));
+  WC_HIP(ctx, hipMemsetAsync(*pay, 0, cap * 32, ctx->stream));
+  return WC_OK;
+}
+// the occupied-slot bound of the growth policy; takes a completed read-back into account without waiting for one
+uint64_t map_bound(wc_map *m) {
+  if (m->ctr_pending && hipEventQuery(m->ev_ctr) == hipSuccess) {
+    m->occ_known = m->h_ctr[kCtrOcc];
+    m->pts_since = m->pts_after_copy;
+    m->ctr_pending = false;
+  }
+  return m->occ_known + m->pts_since;
+}
+int map_sync_counters(wc_ctx *ctx, wc_map *m) {
+  WC_HIP(ctx, hipMemcpyAsync(m->h_ctr, m->ctr, kCtrWords * 8, hipMemcpyDeviceToHost, ctx->stream));
+  WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  m->occ_known = m->h_ctr[kCtrOcc];
+  m->pts_since = 0;
+  m->ctr_pending = false;
+  if (m->h_ctr[kCtrLost]) return wc_fail(ctx, WC_ERR_HIP, "wc_map: %llu voxels found no slot (growth invariant broken)", m->h_ctr[kCtrLost]);
+  return WC_OK;
+}
+bool map_ok(const wc_ctx *ctx, const wc_map *m) { return ctx && m && m->ctx == ctx; }
+
+}  // namespace
+
+extern "C" int wc_map_create(wc_ctx *ctx, double voxel, uint64_t reserve_voxels, wc_map **out) {
+  wc_dev_guard dg_(ctx);
+  if (!ctx || !out || !(voxel >= 0.01 && voxel <= 4.0) || reserve_voxels > ((uint64_t)1 << 31))
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (0.01 <= voxel <= 4.0, reserve_voxels <= 2^31)", __func__);
+  *out = nullptr;
+  wc_map *m = new wc_map;
+  m->ctx = ctx;
+  m->voxel = voxel;
+  m->cap = pow2_at_least(2 * (reserve_voxels ? reserve_voxels : 1));
+  if (hipDeviceGetAttribute(&m->cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || m->cus <= 0) m->cus = 256;
+  int rc = map_table(ctx, m->cap, &m->keys, &m->pay);
+  if (rc == WC_OK) rc = map_alloc(ctx, (void **)&m->ctr, kCtrWords * 8);
+  if (rc == WC_OK && hipMemsetAsync(m->ctr, 0, kCtrWords * 8, ctx->stream) != hipSuccess) rc = wc_fail(ctx, WC_ERR_HIP, "wc_map_create: memset");
+  if (rc == WC_OK && hipHostMalloc((void **)&m->h_ctr, kCtrWords * 8) != hipSuccess) rc = wc_fail(ctx, WC_ERR_HIP, "wc_map_create: pinned counters");
+  if (rc == WC_OK && hipEventCreateWithFlags(&m->ev_ctr, hipEventDisableTiming) != hipSuccess) rc = wc_fail(ctx, WC_ERR_HIP, "wc_map_create: event");
+  if (rc != WC_OK) {
+    (void)hipGetLastError();
+    wc_map_destroy(ctx, m);
+    return rc;
+  }
+  std::memset(m->h_ctr, 0, kCtrWords * 8);
+  *out = m;
+  return WC_OK;
+}
+
+extern "C" int wc_map_destroy(wc_ctx *ctx, wc_map *m) {
+  wc_dev_guard dg_(ctx);
+  if (!m) return WC_OK;
+  if (!map_ok(ctx, m)) return wc_fail(ctx, WC_ERR_ARG, "%s: the map belongs to another context", __func__);
+  map_free(ctx, m->keys);
+  map_free(ctx, m->pay);
+  map_free(ctx, m->ctr);
+  for (wc_buf &b : m->b_pairs) wc_buf_release(ctx, b);
+  wc_buf_release(ctx, m->b_tmp);
+  wc_buf_release(ctx, m->b_cnt);
+  (void)hipStreamSynchronize(ctx->stream);  // (the pinned counters may still be the target of an enqueued copy)
+  if (m->ev_ctr) (void)hipEventDestroy(m->ev_ctr);
+  if (m->h_ctr) (void)hipHostFree(m->h_ctr);
+  delete m;
+  return WC_OK;
+}
+
+extern "C" int wc_map_insert(wc_ctx *ctx, wc_map *m, const wc_points *pts, uint64_t *h_n_rejected) {
+  wc_dev_guard dg_(ctx);
+  if (!map_ok(ctx, m) || !pts || (pts->n && (!pts->xyz || pts->xyz_stride < 12 || pts->xyz_stride % 4 || (uintptr_t)pts->xyz % 4)))
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
+  if (h_n_rejected) *h_n_rejected = 0;
+  if (pts->n == 0) return WC_OK;
+  // growth (policy at the top of the file): at most half full at every probe of this call
+  const uint64_t need = 2 * (map_bound(m) + pts->n);
+  if (need > m->cap) {
+    const uint64_t cap = pow2_at_least(need);
+    if (cap > ((uint64_t)1 << 32)) return wc_fail(ctx, WC_ERR_CAPACITY, "%s: the table would exceed 2^32 slots", __func__);
+    unsigned long long *keys = nullptr;
+    long long *pay = nullptr;
+    WC_TRY(map_table(ctx, cap, &keys, &pay));
+    k_map_rehash<<<(unsigned)((m->cap + 255) / 256), 256, 0, ctx->stream>>>(m->keys, m->pay, m->cap, keys, pay, cap - 1);
+    WC_HIP(ctx, hipGetLastError());
+    map_free(ctx, m->keys);
+    map_free(ctx, m->pay);
+    m->keys = keys, m->pay = pay, m->cap = cap;
+    ++m->growths;
+  }
+  WC_HIP(ctx, hipMemsetAsync(m->ctr + kCtrRejCall, 0, 8, ctx->stream));
+  const uint64_t tiles = (pts->n + kMapTile - 1) / kMapTile;
+  const unsigned grid = (unsigned)std::min<uint64_t>(tiles, (uint64_t)4 * m->cus);
+  k_map_insert<<<grid, kMapThreads, 0, ctx->stream>>>(*pts, m->voxel, m->keys, m->pay, m->cap - 1, m->ctr);
+  WC_HIP(ctx, hipGetLastError());
+  m->pts_since += pts->n;
+  if (h_n_rejected) {
+    WC_TRY(map_sync_counters(ctx, m));
+    *h_n_rejected = m->h_ctr[kCtrRejCall];
+    return WC_OK;
+  }
+  // (no wait: the counters travel back behind the kernel and tighten the next call's bound when they have arrived)
+  if (m->ctr_pending) {
+    m->pts_after_copy += pts->n;
+  } else {
+    WC_HIP(ctx, hipMemcpyAsync(m->h_ctr, m->ctr, kCtrWords * 8, hipMemcpyDeviceToHost, ctx->stream));
+    WC_HIP(ctx, hipEventRecord(m->ev_ctr, ctx->stream));
+    m->ctr_pending = true;
+    m->pts_after_copy = 0;
+  }
+  return WC_OK;
+}
+
+extern "C" int wc_map_size(wc_ctx *ctx, wc_map *m, uint64_t *h_voxels, uint64_t *h_points) {
+  wc_dev_guard dg_(ctx);
+  if (!map_ok(ctx, m)) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
+  WC_TRY(map_sync_counters(ctx, m));
+  if (h_voxels) *h_voxels = m->h_ctr[kCtrOcc];
+  if (h_points) *h_points = m->h_ctr[kCtrPts];
+  return WC_OK;
+}
+
+extern "C" int wc_map_info(wc_ctx *ctx, wc_map *m, uint64_t h_info[4]) {
+  wc_dev_guard dg_(ctx);
+  if (!map_ok(ctx, m) || !h_info) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
+  WC_TRY(map_sync_counters(ctx, m));
+  h_info[0] = m->cap;
+  h_info[1] = m->growths;
+  h_info[2] = m->h_ctr[kCtrRej];
+  h_info[3] = m->cap * 40;
+  return WC_OK;
+}
+
+extern "C" int wc_map_export(wc_ctx *ctx, wc_map *m, float *d_xyz, uint32_t *d_count, int32_t *d_keys, uint64_t cap, uint64_t *h_n) {
+  wc_dev_guard dg_(ctx);
+  if (!map_ok(ctx, m) || !h_n) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
+  WC_TRY(map_sync_counters(ctx, m));  // (the size read-back)
+  const uint64_t n = m->h_ctr[kCtrOcc];
+  *h_n = n;
+  if (n == 0) return WC_OK;
+  if (cap < n) return wc_fail(ctx, WC_ERR_CAPACITY, "%s: %llu voxels, capacity %llu", __func__, (unsigned long long)n, (unsigned long long)cap);
+  if (!d_xyz || !d_count) return wc_fail(ctx, WC_ERR_ARG, "%s: null output", __func__);
+  WC_TRY(wc_ensure(ctx, m->b_pairs[0], n * 8));
+  WC_TRY(wc_ensure(ctx, m->b_pairs[1], n * 8));
+  WC_TRY(wc_ensure(ctx, m->b_pairs[2], n * 4));
+  WC_TRY(wc_ensure(ctx, m->b_pairs[3], n * 4));
+  WC_TRY(wc_ensure(ctx, m->b_cnt, 8));
+  unsigned long long *kin = (unsigned long long *)m->b_pairs[0].p, *kout = (unsigned long long *)m->b_pairs[1].p;
+  uint32_t *vin = (uint32_t *)m->b_pairs[2].p, *vout = (uint32_t *)m->b_pairs[3].p;
+  WC_HIP(ctx, hipMemsetAsync(m->b_cnt.p, 0, 8, ctx->stream));
+  k_map_compact<<<(unsigned)((m->cap + kCompactChunk - 1) / kCompactChunk), 256, 0, ctx->stream>>>(m->keys, m->cap, kin, vin, n,
+                                                                                                   (unsigned long long *)m->b_cnt.p);
+  WC_HIP(ctx, hipGetLastError());
+  // the slots' order depends on the schedule; the keys are distinct, so the sorted order does not
+  using cfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 0>;
+  size_t tmp = 0;
+  WC_HIP(ctx, rocprim::radix_sort_pairs<cfg>(nullptr, tmp, kin, kout, vin, vout, (size_t)n, 0u, 63u, ctx->stream));
+  WC_TRY(wc_ensure(ctx, m->b_tmp, tmp));
+  tmp = m->b_tmp.cap;
+  WC_HIP(ctx, rocprim::radix_sort_pairs<cfg>(m->b_tmp.p, tmp, kin, kout, vin, vout, (size_t)n, 0u, 63u, ctx->stream));
+  k_map_centroids<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(kout, vout, n, m->pay, m->voxel, d_xyz, d_count, d_keys);
+  WC_HIP(ctx, hipGetLastError());
+  return WC_OK;
+}
+
+extern "C" int wc_map_clear(wc_ctx *ctx, wc_map *m) {
+  wc_dev_guard dg_(ctx);
+  if (!map_ok(ctx, m)) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
+  WC_HIP(ctx, hipMemsetAsync(m->keys, 0xFF, m->cap * 8, ctx->stream));
+  WC_HIP(ctx, hipMemsetAsync(m->pay, 0, m->cap * 32, ctx->stream));
+  WC_HIP(ctx, hipMemsetAsync(m->ctr, 0, kCtrWords * 8, ctx->stream));
+  WC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (a pending counter copy lands before the host's bookkeeping is reset)
+  m->occ_known = m->pts_since = m->pts_after_copy = 0;
+  m->ctr_pending = false;
+  std::memset(m->h_ctr, 0, kCtrWords * 8);
+  return WC_OK;
+}

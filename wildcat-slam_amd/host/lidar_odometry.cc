@@ -128,7 +128,8 @@ bool LidarOdometry::ImportState(const double *samples23, size_t ns, const wc_imu
 LidarOdometry::~LidarOdometry() {
   if (!ctx_) return;
   if (d_res_) wc_dev_free(ctx_, d_res_);
-  void *bufs[] = {d_surf_, d_pose_, d_inbody_, d_pairs_sld_, d_pairs_fix_, d_imu_, d_sweep_xyz_, d_sweep_t_, d_kept_t_, d_scan_raw_, d_pts_[0], d_pts_[1], d_fix_surf_, d_fix_pose_};
+  if (map_) wc_map_destroy(ctx_, map_);
+  void *bufs[] = {d_surf_, d_pose_, d_inbody_, d_pairs_sld_, d_pairs_fix_, d_imu_, d_sweep_xyz_, d_sweep_t_, d_kept_t_, d_scan_raw_, d_pts_[0], d_pts_[1], d_fix_surf_, d_fix_pose_, d_world_};
   for (void *b : bufs)
     if (b) wc_dev_free(ctx_, b);
   wc_ctx_destroy(ctx_);
@@ -381,8 +382,20 @@ void LidarOdometry::LogResiduals(const std::vector<double> &x, const char *when)
   }
 }
 
+// the sweep undistorted once more with the poses the solve left behind (:584-595): what FillOutputs publishes and the map takes in
+const void *LidarOdometry::UndistortFinal(const void *d_raw_sweep, size_t n_sweep) {
+  if (n_sweep > cap_world_) {
+    if (d_world_) WC_CALL(wc_dev_free(ctx_, d_world_));
+    cap_world_ = n_sweep * 2;
+    WC_CALL(wc_dev_alloc(ctx_, cap_world_ * sizeof(hilti_ros::Point), &d_world_));
+  }
+  UploadImuStates();
+  WC_CALL(wc_undistort_sweep(ctx_, d_raw_sweep, n_sweep, d_imu_, imu_states_.size(), d_world_));
+  return d_world_;
+}
+
 // what the reference hands to ROS at the end of AddLidarScan (:582-602), as plain data
-void LidarOdometry::FillOutputs(const void *d_raw_sweep, size_t n_sweep) {
+void LidarOdometry::FillOutputs(const void *d_world_sweep, size_t n_sweep) {
   // PubSurfels(surfels_sld_win_, ...) (:582, surfel_extraction.cc:360-434)
   const size_t n = n_surfels_ - sld_begin_;
   std::vector<wc_surfel> surf(n);
@@ -393,16 +406,9 @@ void LidarOdometry::FillOutputs(const void *d_raw_sweep, size_t n_sweep) {
   }
   outputs_.markers.resize(n);
   for (size_t i = 0; i < n; ++i) outputs_.markers[i] = wc_wire::MarkerFromSurfel(surf[i], pose[i]);
-  // the sweep, undistorted once more with the poses the solve left behind (:584-595)
+  // the sweep with the final poses (:584-595)
   std::vector<hilti_ros::Point> pts(n_sweep);
-  if (n_sweep) {
-    void *d_und = nullptr;
-    WC_CALL(wc_dev_alloc(ctx_, n_sweep * sizeof(hilti_ros::Point), &d_und));
-    UploadImuStates();
-    WC_CALL(wc_undistort_sweep(ctx_, d_raw_sweep, n_sweep, d_imu_, imu_states_.size(), d_und));
-    WC_CALL(wc_d2h(ctx_, pts.data(), d_und, n_sweep * sizeof(hilti_ros::Point)));
-    WC_CALL(wc_dev_free(ctx_, d_und));
-  }
+  if (n_sweep) WC_CALL(wc_d2h(ctx_, pts.data(), d_world_sweep, n_sweep * sizeof(hilti_ros::Point)));
   wc_wire::Cloud2FromPoints(pts.data(), pts.size(), outputs_.scan_in_world);
   outputs_.scan_stamp = n_sweep ? pts[0].time : 0.0;
   // tf world -> imu_link (:596-602)
@@ -410,6 +416,58 @@ void LidarOdometry::FillOutputs(const void *d_raw_sweep, size_t n_sweep) {
   outputs_.tf.stamp = b.timestamp;
   std::memcpy(outputs_.tf.origin, b.pos, 24);
   outputs_.tf.rotation_xyzw[0] = b.quat[1], outputs_.tf.rotation_xyzw[1] = b.quat[2], outputs_.tf.rotation_xyzw[2] = b.quat[3], outputs_.tf.rotation_xyzw[3] = b.quat[0];
+}
+
+// ---- the accumulated map (config().map_voxel_size) ----------------------------------------------------------------------------
+bool LidarOdometry::SetMapVoxel(double voxel) {
+  if (voxel != 0.0 && !(voxel >= 0.01 && voxel <= 4.0)) return false;
+  config_.map_voxel_size = voxel;
+  if (map_) WC_CALL(wc_map_destroy(ctx_, map_));
+  map_ = nullptr;
+  EnsureMap();
+  return true;
+}
+// the map follows config().map_voxel_size: created on first use, re-created (empty) when the size changed, removed at 0
+void LidarOdometry::EnsureMap() {
+  const double v = config_.map_voxel_size;
+  if (map_ && map_voxel_ == v) return;
+  if (map_) WC_CALL(wc_map_destroy(ctx_, map_));
+  map_ = nullptr;
+  if (v == 0.0) return;
+  WC_CALL(wc_map_create(ctx_, v, (size_t)1 << 20, &map_));
+  map_voxel_ = v;
+}
+uint64_t LidarOdometry::map_voxels() const {
+  uint64_t v = 0;
+  if (map_) WC_CALL(wc_map_size(ctx_, map_, &v, nullptr));
+  return v;
+}
+uint64_t LidarOdometry::map_points() const {
+  uint64_t p = 0;
+  if (map_) WC_CALL(wc_map_size(ctx_, map_, nullptr, &p));
+  return p;
+}
+uint64_t LidarOdometry::map_rejected() const {
+  uint64_t info[4] = {0, 0, 0, 0};
+  if (map_) WC_CALL(wc_map_info(ctx_, map_, info));
+  return info[2];
+}
+size_t LidarOdometry::ExportMap(float *xyz, uint32_t *counts, size_t cap) {
+  if (!map_) return 0;
+  uint64_t n = map_voxels();
+  if (n == 0 || cap < n || !xyz || !counts) return n;
+  void *d_xyz = nullptr, *d_cnt = nullptr;
+  WC_CALL(wc_dev_alloc(ctx_, n * 3 * sizeof(float), &d_xyz));
+  WC_CALL(wc_dev_alloc(ctx_, n * sizeof(uint32_t), &d_cnt));
+  WC_CALL(wc_map_export(ctx_, map_, (float *)d_xyz, (uint32_t *)d_cnt, nullptr, n, &n));
+  WC_CALL(wc_d2h(ctx_, xyz, d_xyz, n * 3 * sizeof(float)));
+  WC_CALL(wc_d2h(ctx_, counts, d_cnt, n * sizeof(uint32_t)));
+  WC_CALL(wc_dev_free(ctx_, d_xyz));
+  WC_CALL(wc_dev_free(ctx_, d_cnt));
+  return n;
+}
+void LidarOdometry::ClearMap() {
+  if (map_) WC_CALL(wc_map_clear(ctx_, map_));
 }
 
 void LidarOdometry::UploadImuStates() {
@@ -641,8 +699,23 @@ void LidarOdometry::AddLidarScan(const pcl::PointCloud<hilti_ros::Point>::Ptr &m
     lap(5);
   }
   ShrinkToFit();  // :574-580
-  if (config_.fill_outputs) FillOutputs(d_raw_sweep, n_sweep);  // :582-602
+  // the sweep with the final poses (:584-595) is formed once, for the outputs and for the map alike
+  const void *d_world = nullptr;
+  if (config_.fill_outputs) {
+    d_world = UndistortFinal(d_raw_sweep, n_sweep);
+    FillOutputs(d_world, n_sweep);  // :582-602
+  }
   lap(6);
+  last_map_ms_ = 0.0;
+  if (config_.map_voxel_size != 0.0) {  // (the reference accumulates in RViz; off by default: nothing allocated or launched)
+    const auto t_map = std::chrono::steady_clock::now();
+    EnsureMap();
+    if (!d_world) d_world = UndistortFinal(d_raw_sweep, n_sweep);
+    const wc_points desc{d_world, (const char *)d_world + WC_HILTI_POINT_TIME_OFFSET, WC_HILTI_POINT_BYTES, WC_HILTI_POINT_BYTES, n_sweep};
+    WC_CALL(wc_map_insert(ctx_, map_, &desc, nullptr));
+    t_prev = std::chrono::steady_clock::now();
+    last_map_ms_ = std::chrono::duration<double, std::milli>(t_prev - t_map).count();
+  }
   if (dbg_t)
     fprintf(stderr, "[odom] sweep %d: predict + undistort %.2f, extract + poses %.2f, match %.2f, build %.2f, solve %.2f (%d iterations), update %.2f, shrink %.2f ms\n",
             (int)sweep_id_, t_stage[0], t_stage[1], t_stage[2], t_stage[3], t_stage[4], (int)last_summary_.iterations, t_stage[5], t_stage[6]);

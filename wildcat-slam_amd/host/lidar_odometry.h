@@ -77,6 +77,19 @@ class LidarOdometry {
   const SweepOutputs &last_outputs() const { return outputs_; }
   // the residual histograms of the last completed sweep (config().log_residual_histograms; lidar_odometry.cc:56-94)
   const std::string &last_residual_log() const { return residual_log_; }
+  // the accumulated, voxel-downsampled map (config().map_voxel_size > 0): every sweep undistorted with its final poses - the points
+  // of last_outputs().scan_in_world - goes into a hash table in HBM (wc_map_*, DownSamplingVoxel over all sweeps).  The counts wait
+  // for the device; 0 without a map
+  bool SetMapVoxel(double voxel);  // config().map_voxel_size = voxel, the map re-created empty (0: removed); false: voxel out of range
+  uint64_t map_voxels() const;
+  uint64_t map_points() const;
+  uint64_t map_rejected() const;  // points with a non-finite coordinate or a voxel index beyond 2^20 (not inserted)
+  // centroids (n x 3 floats) and point counts in ascending voxel-index order; returns n, writes nothing when cap < n
+  size_t ExportMap(float *xyz, uint32_t *counts, size_t cap);
+  void ClearMap();
+  // wall time [ms] of the last completed sweep's map step (the undistortion when fill_outputs does not already form it, the insert's
+  // enqueue; its kernel runs behind on the stream).  Not part of last_stage_ms()
+  double last_map_ms() const { return last_map_ms_; }
   LioConfig &config() { return config_; }
   void ApplyConfig();  // push config() changes (quirks, extraction arithmetic, iteration cap, extrinsics) into the device context
   bool ImportState(const double *samples23, size_t ns, const wc_imu_state *imu, size_t n_imu);  // test hook, see .cc
@@ -147,7 +160,14 @@ class LidarOdometry {
   size_t cap_surfels_ = 0, n_surfels_ = 0, sld_begin_ = 0, cap_imu_ = 0, cap_sweep_ = 0;
   std::deque<double> surfel_times_;  // host copy of the sliding window's surfel timestamps (window bookkeeping only)
   SweepOutputs outputs_;
-  void FillOutputs(const void *d_raw_sweep, size_t n_sweep);
+  void FillOutputs(const void *d_world_sweep, size_t n_sweep);
+  const void *UndistortFinal(const void *d_raw_sweep, size_t n_sweep);  // the sweep with the final poses, 48-byte records, in d_world_
+  void EnsureMap();
+  void *d_world_ = nullptr;
+  size_t cap_world_ = 0;
+  wc_map *map_ = nullptr;
+  double map_voxel_ = 0.0;  // voxel size map_ was created with
+  double last_map_ms_ = 0.0;
   std::string residual_log_;
   void *d_res_ = nullptr;
   size_t cap_res_ = 0;

@@ -40,4 +40,8 @@ struct LioConfig {
   // not in the reference: surfel-extraction arithmetic (wc_params.exact_sums).  false (default) = the order-independent integer
   // moments every benchmark number is quoted on (ids / counts exact, geometry ~1e-9); true = every sum in the reference's order
   bool exact_sums = false;
+  // not in the reference (whose accumulated map is built by RViz from /scan_in_imu_frame, lidar_odometry.cc:584-595): voxel side [m] of
+  // the device-resident map every sweep is inserted into after its solve (DownSamplingVoxel, surfel_extraction.cc:228-261, over all
+  // sweeps; include/wildcat_hip.h: wc_map_*).  0 (default) = no map: nothing allocated or launched.  Otherwise 0.01 <= v <= 4.0
+  double map_voxel_size = 0.0;
 };

@@ -191,6 +191,33 @@ void wc_host_marker(const wc_surfel *s, const wc_pose *p, double out14[14]) {
   for (int c = 0; c < 4; ++c) out14[10 + c] = m.color[c];
 }
 
+// ---- the accumulated map (LioConfig::map_voxel_size; include/wildcat_hip.h: wc_map_*) -------------------------------------
+// voxel side [m]: 0 removes the map, 0.01 .. 4.0 (re-)creates it empty; returns 0, or WC_ERR_ARG for any other value
+int wc_odom_set_map_voxel(void *h, double voxel) { return ((LidarOdometry *)h)->SetMapVoxel(voxel) ? 0 : WC_ERR_ARG; }
+// out3 = voxels, points inserted, points rejected (non-finite or beyond 2^20 voxels from the origin)
+void wc_odom_map_size(void *h, uint64_t out3[3]) {
+  const LidarOdometry *o = (const LidarOdometry *)h;
+  out3[0] = o->map_voxels(), out3[1] = o->map_points(), out3[2] = o->map_rejected();
+}
+// centroids (n x 3 floats) and counts in ascending voxel-index order; returns n (nothing written when cap < n)
+uint64_t wc_odom_map_export(void *h, float *xyz, uint32_t *counts, uint64_t cap) { return ((LidarOdometry *)h)->ExportMap(xyz, counts, cap); }
+void wc_odom_map_clear(void *h) { ((LidarOdometry *)h)->ClearMap(); }
+double wc_odom_map_ms(void *h) { return ((const LidarOdometry *)h)->last_map_ms(); }
+// Cloud2FromXyz (host/wire_formats.h): the field table (3 x {offset, datatype, count}), point_step and the payload of n points
+int wc_host_xyz_to_cloud2(const float *xyz, uint64_t n, uint32_t table9[9], char *names_out, uint64_t cap, uint8_t *data_out) {
+  wc_wire::PointCloud2 msg;
+  wc_wire::Cloud2FromXyz(xyz, n, msg);
+  std::string names;
+  for (size_t f = 0; f < msg.fields.size() && f < 3; ++f) {
+    table9[3 * f] = msg.fields[f].offset, table9[3 * f + 1] = msg.fields[f].datatype, table9[3 * f + 2] = msg.fields[f].count;
+    names += msg.fields[f].name;
+    names.push_back('\0');
+  }
+  if (names_out && cap >= names.size()) std::memcpy(names_out, names.data(), names.size());
+  if (data_out && !msg.data.empty()) std::memcpy(data_out, msg.data.data(), msg.data.size());
+  return (int)msg.point_step;
+}
+
 // test hook: start the next sweep from another run's states (LidarOdometry::ImportState); 0 = done, 1 = the counts differ
 int wc_odom_import_state(void *h, const double *samples23, uint64_t ns, const wc_imu_state *imu, uint64_t n_imu) {
   return ((LidarOdometry *)h)->ImportState(samples23, ns, imu, n_imu) ? 0 : 1;

@@ -9,6 +9,7 @@
 //                                                      covariance made right-handed (makeRightHanded :340-358), 3-sigma scales,
 //                                                      colour from the world normal
 //   last sample state -> world->imu_link transform     lidar_odometry.cc:596-602 (tf quaternion order x, y, z, w)
+//   xyz floats -> PointCloud2                          the accumulated map (not in the reference, whose map is RViz's)
 // A node that links ROS copies these plain structs into the message types field by field; nothing here includes a ROS header.
 #pragma once
 #include <cmath>
@@ -101,6 +102,21 @@ inline void Cloud2FromPoints(const hilti_ros::Point *pts, size_t n, PointCloud2 
   msg.point_step = 48, msg.row_step = (uint32_t)(48 * n);
   msg.data.resize(48 * n);
   if (n) std::memcpy(msg.data.data(), pts, 48 * n);
+  msg.is_dense = true;
+}
+
+// a cloud of bare xyz floats (the accumulated map: wc_map_export / LidarOdometry::ExportMap) as PointCloud2: fields x, y, z FLOAT32 at
+// offsets 0, 4, 8, point_step 12 (the floats as they lie, no padding), one row, little endian, dense
+inline void Cloud2FromXyz(const float *xyz, size_t n, PointCloud2 &msg) {
+  msg.height = 1, msg.width = (uint32_t)n;
+  msg.fields.clear();
+  msg.fields.push_back({"x", 0, FLOAT32, 1});
+  msg.fields.push_back({"y", 4, FLOAT32, 1});
+  msg.fields.push_back({"z", 8, FLOAT32, 1});
+  msg.is_bigendian = false;
+  msg.point_step = 12, msg.row_step = (uint32_t)(12 * n);
+  msg.data.resize(12 * n);
+  if (n) std::memcpy(msg.data.data(), xyz, 12 * n);
   msg.is_dense = true;
 }
 

@@ -183,6 +183,10 @@ class Context:
         self._ck(self.lib.wc_timer_stop_ms(self.h, C.byref(ms)))
         return ms.value
 
+    def map_create(self, voxel, reserve_voxels=0):
+        """a voxel-downsampled point map in HBM (wc_map_create); close() it before the context"""
+        return PointMap(self, voxel, reserve_voxels)
+
     # ---- extraction ---------------------------------------------------------------------------------------------
     def points_desc(self, d_points, n):
         """descriptor for a device-resident array of 48-byte hilti_ros::Point records"""
@@ -554,6 +558,80 @@ class Context:
         return pairs
 
 
+class PointMap:
+    """wc_map: the device-resident voxel-downsampled map (DownSamplingVoxel, surfel_extraction.cc:228-261, over every insert)"""
+
+    def __init__(self, ctx, voxel, reserve_voxels=0):
+        self.ctx, self.lib, self.voxel = ctx, ctx.lib, float(voxel)
+        h = C.c_void_p(0)
+        ctx._ck(self.lib.wc_map_create(ctx.h, C.c_double(voxel), C.c_uint64(int(reserve_voxels)), C.byref(h)))
+        self.h = h
+
+    def insert_device(self, desc):
+        """points already in HBM (a wc_points descriptor) -> points of this call not inserted (non-finite / out of range)"""
+        rej = C.c_uint64(0)
+        self.ctx._ck(self.lib.wc_map_insert(self.ctx.h, self.h, C.byref(desc), C.byref(rej)))
+        return int(rej.value)
+
+    def insert(self, points):
+        """POINT records or an (n, 3) float32 array (uploaded for the call) -> points not inserted"""
+        points = np.ascontiguousarray(points)
+        if points.dtype == R.POINT:
+            stride = 48
+        else:
+            points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+            stride = 12
+        n = len(points)
+        d = self.ctx.to_device(points) if n else None
+        desc = R.Points(d.ptr if d else 0, 0, stride, 0, n)
+        try:
+            return self.insert_device(desc)
+        finally:
+            if d:
+                d.free()
+
+    def size(self):
+        """-> (voxels, points inserted)"""
+        v, p = C.c_uint64(0), C.c_uint64(0)
+        self.ctx._ck(self.lib.wc_map_size(self.ctx.h, self.h, C.byref(v), C.byref(p)))
+        return int(v.value), int(p.value)
+
+    def info(self):
+        """-> dict(slots, growths, rejected, bytes)"""
+        out = (C.c_uint64 * 4)()
+        self.ctx._ck(self.lib.wc_map_info(self.ctx.h, self.h, out))
+        return dict(zip(("slots", "growths", "rejected", "bytes"), [int(x) for x in out]))
+
+    def export_device(self, d_xyz, d_count, d_keys, cap):
+        """-> (return code, n): WC_ERR_CAPACITY leaves the needed count in n"""
+        n = C.c_uint64(0)
+        rc = self.lib.wc_map_export(self.ctx.h, self.h, C.c_void_p(d_xyz.ptr if d_xyz else 0), C.c_void_p(d_count.ptr if d_count else 0),
+                                    C.c_void_p(d_keys.ptr if d_keys else 0), C.c_uint64(int(cap)), C.byref(n))
+        return rc, int(n.value)
+
+    def export(self):
+        """-> (xyz (n, 3) float32 centroids, counts (n,) uint32, keys (n, 3) int32) in ascending (kx, ky, kz) order"""
+        n, _ = self.size()
+        if n == 0:
+            return np.zeros((0, 3), np.float32), np.zeros(0, np.uint32), np.zeros((0, 3), np.int32)
+        bx, bc, bk = self.ctx.alloc(12 * n), self.ctx.alloc(4 * n), self.ctx.alloc(12 * n)
+        try:
+            rc, m = self.export_device(bx, bc, bk, n)
+            self.ctx._ck(rc)
+            return bx.download(np.float32, 3 * m).reshape(-1, 3), bc.download(np.uint32, m), bk.download(np.int32, 3 * m).reshape(-1, 3)
+        finally:
+            for b in (bx, bc, bk):
+                b.free()
+
+    def clear(self):
+        self.ctx._ck(self.lib.wc_map_clear(self.ctx.h, self.h))
+
+    def close(self):
+        if getattr(self, "h", None) and self.ctx.h:
+            self.lib.wc_map_destroy(self.ctx.h, self.h)
+        self.h = None
+
+
 class Odometry:
     """the C++ LidarOdometry facade (host/lidar_odometry.h) through its flat C wrapper (host/odom_c_api.cc)"""
 
@@ -612,6 +690,35 @@ class Odometry:
         stamp, tf = C.c_double(0), np.zeros(8)
         self.lib.wc_odom_scan_in_world(self.h, R.ptr(pts), C.c_uint64(k), C.byref(stamp), R.ptr(tf))
         return dict(markers=m[:n], scan=pts[:k], stamp=stamp.value, tf=tf)
+
+    def set_map_voxel(self, voxel):
+        """the accumulated map (LioConfig::map_voxel_size): 0 = off, 0.01 .. 4.0 = (re-)created empty"""
+        rc = self.lib.wc_odom_set_map_voxel(self.h, C.c_double(voxel))
+        if rc != 0:
+            raise WildcatError(rc, "wc_odom_set_map_voxel(%r)" % voxel)
+
+    def map_size(self):
+        """-> (voxels, points inserted, points rejected)"""
+        out = (C.c_uint64 * 3)()
+        self.lib.wc_odom_map_size(self.h, out)
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def map_export(self):
+        """-> (xyz (n, 3) float32 centroids, counts (n,) uint32) in ascending voxel-index order"""
+        self.lib.wc_odom_map_export.restype = C.c_uint64
+        n = int(self.map_size()[0])
+        xyz, cnt = np.zeros((max(n, 1), 3), np.float32), np.zeros(max(n, 1), np.uint32)
+        m = int(self.lib.wc_odom_map_export(self.h, R.ptr(xyz), R.ptr(cnt), C.c_uint64(n)))
+        assert m == n
+        return xyz[:n], cnt[:n]
+
+    def map_clear(self):
+        self.lib.wc_odom_map_clear(self.h)
+
+    def map_ms(self):
+        """wall time [ms] of the last sweep's map step (not part of stage_ms())"""
+        self.lib.wc_odom_map_ms.restype = C.c_double
+        return float(self.lib.wc_odom_map_ms(self.h))
 
     def set_residual_log(self, on):
         """the reference's residual histograms before / after every solve (lidar_odometry.cc:56-94, :547-549, :568-570)"""
