@@ -113,17 +113,22 @@ def test_small_timestamps_and_temporal_clusters(gpu, oracle):
     assert st.clusters_total == 2 * 8 * 200  # two temporal clusters per layer-1 plane node
 
 
-@pytest.mark.parametrize("revisits,fast", [(6, True), (9, None)])
-def test_many_temporal_clusters_per_node(gpu, oracle, revisits, fast):
-    # the same lattice observed 6 / 9 times inside one sweep, 0.08 s apart: every layer-1 node is a plane with that many
-    # temporal clusters.  k_fx_nodes puts every closed cluster aside as a job (512 per wavefront of 64 nodes): 6 x 64 fit - the
-    # default path completes the sweep itself; 9 x 64 do not - the sweep must be handed to the exact path, same result
+def _revisit_lattice(revisits):
+    """the same lattice observed `revisits` times inside one sweep, 0.08 s apart"""
     parts = []
     for r in range(revisits):
         a, _ = synth.g2_lattice(150, m=32, t_start=0.08 * r, duration=0.02)
         a["x"] += np.float32(0.0005 * r)
         parts.append(a)
-    pts = synth.concat_points(*parts)
+    return synth.concat_points(*parts)
+
+
+@pytest.mark.parametrize("revisits,fast", [(6, True), (9, None)])
+def test_many_temporal_clusters_per_node(gpu, oracle, revisits, fast):
+    # the same lattice observed 6 / 9 times inside one sweep, 0.08 s apart: every layer-1 node is a plane with that many
+    # temporal clusters.  k_fx_nodes puts every closed cluster aside as a job (512 per wavefront of 64 nodes): 6 x 64 fit - the
+    # default path completes the sweep itself; 9 x 64 do not - the sweep must be handed to the exact path, same result
+    pts = _revisit_lattice(revisits)
     res, st = _run(gpu, oracle, pts, expect_fast=fast)
     assert res["n"] == revisits * 8 * 150 and st.clusters_total == revisits * 8 * 150
     if fast is None:
@@ -432,6 +437,41 @@ def test_displaced_root_keeps_its_layer2_nodes(gpu, oracle):
                 s_gpu, id_gpu = gpu.extract_surfels(pts)
                 assert gpu.extract_path_info()["fast"]
                 assert set(helpers.id_tuples(id_gpu)) == want
+    finally:
+        gpu.set_dev_option("fx_split", -1)
+        gpu.params = oracle.default_params()
+        gpu.set_params(gpu.params)
+
+
+@pytest.mark.parametrize("cloud", ["lattice_vs095", "revisits6", "room_firing_250k"])
+def test_both_node_stage_forms_give_the_same_bytes(gpu, oracle, cloud):
+    """the fused node pass (fx_split 0) and the split walk + test pair (fx_split 1) are built from the same routines: on the same cloud
+    both must match the oracle, be completed by the default path, and return the same count and the same surfel and id bytes.  The
+    clouds reach the displaced root and layer 2 (lattice at voxel size 0.95), the jobs and the root's temporal clusters (six revisits),
+    and long record lists, several clusters per node and layer 2 (a room sweep in firing order; its second sweep merges the lists)."""
+    params = oracle.default_params()
+    if cloud == "lattice_vs095":
+        params.voxel_size = 0.95
+        pts = synth.g2_lattice(120, m=40)[0]
+    elif cloud == "revisits6":
+        pts = _revisit_lattice(6)
+    else:
+        pts = synth.g1_room(250_000, seed=synth.SEED + 3)
+    gpu.set_params(params)
+    gpu.params = params
+    try:
+        s_ref, id_ref, _ = oracle.extract_surfels(pts, params)
+        got = []
+        for form in (0, 1):
+            gpu.set_dev_option("fx_split", form)
+            for _ in range(2):
+                s_gpu, id_gpu = gpu.extract_surfels(pts)
+                assert gpu.extract_path_info()["fast"], (form, gpu.extract_path_info())
+                assert len(s_gpu) == len(s_ref)
+                helpers.check_surfels(s_gpu, id_gpu, s_ref, id_ref, tol=1e-6, t_tol=1e-5)
+                got.append((form, len(s_gpu), s_gpu.tobytes(), id_gpu.tobytes()))
+        for form, n, sb, ib in got[1:]:
+            assert (n, sb, ib) == got[0][1:], (cloud, form, n, got[0][1])
     finally:
         gpu.set_dev_option("fx_split", -1)
         gpu.params = oracle.default_params()

@@ -1144,10 +1144,451 @@ __device__ __forceinline__ void fx_stepn(const FxArgs &A, int level, uint32_t (&
     ix[j] = (uint32_t)(w[j][6].y & m);
   }
 }
+// ---- the node stage's routines.  Both of its forms are built from them: k_fx_nodes below (one launch) and k_fx_walk + k_fx_test
+//      (extract_split.inc, two launches).  A "parent" is a root voxel (LEVEL 1: its node is layer 0, its children the layer-1
+//      octants) or a queued layer-1 node (LEVEL 2: already tested and found not to be a plane, cc:175-182; children = its layer-2
+//      octants).  8 lanes per parent, lane = child octant; eight parents per wavefront ----
 
-// A "parent" is a root voxel (LEVEL 1: its node is layer 0, its children the layer-1 octants) or a queued layer-1 node
-// (LEVEL 2: already tested and found not to be a plane, cc:175-182; children = its layer-2 octants).  8 lanes per parent,
-// lane = child octant; eight parents per wavefront.
+// the fx_fallback codes of a form's call sites (wc_debug_status reports which of them fired)
+struct FxWhy {
+  int gap;        // a gap between time bins too near the cluster gap to be decided on ticks
+  int slots;      // the wavefront's slot sub-range is full
+  int jobs;       // the wavefront's job staging area is full
+  int walk1;      // a list walk that does not end (one chain / several chains)
+  int walkn;
+  int big_bin;    // a time bin with more than 2^20 points
+  int job_which;  // first of the three codes naming the gate a job's PCA was near (FxPca::which); < 0: not reported
+};
+
+// the parents sit in kFxSub dense sub-lists (one counter each), handed out back to back: entry gi of them all -> block index
+template <int LEVEL>
+__device__ __forceinline__ uint32_t fx_dense_parent(const FxArgs &A, const uint32_t (&cnts)[kFxSub], uint32_t per, uint32_t gi, bool have_parent) {
+  uint32_t pidx = 0;
+  if (have_parent) {
+    uint32_t rem = gi;
+    bool found = false;
+#pragma unroll
+    for (int j = 0; j < kFxSub; ++j) {
+      const uint32_t cj = cnts[j];
+      if (!found) {
+        if (rem < cj) {
+          pidx = (uint32_t)j * per + rem;
+          found = true;
+        } else {
+          rem -= cj;
+        }
+      }
+    }
+  }
+  if (LEVEL == 1 && have_parent) pidx = A.rlist[pidx];  // dense list entry -> hash slot = block index
+  return pidx;
+}
+
+// the parent's header: its first time bin, its root key and (LEVEL 2) its layer-1 octant
+template <int LEVEL>
+__device__ __forceinline__ void fx_parent_header(const FxArgs &A, const unsigned long long *blk, uint32_t pidx, bool have_parent, uint32_t &key,
+                                                 uint32_t &o1p, uint32_t &minbin) {
+  const uint32_t *h32 = (const uint32_t *)blk;
+  key = 0, o1p = 0, minbin = 0;
+  if (have_parent) {
+    minbin = 0xFFFFFFFFu - h32[2];
+    if (LEVEL == 1) {
+      key = A.rkey[pidx] - 1u;
+    } else {  // header of a queued node (written when it was queued): word 0 = root slot | o1 << 28 | first-child flag << 31,
+      const uint32_t ro = h32[0];  // word 1 = root key + 1
+      o1p = (ro >> 28) & 7u;
+      key = h32[1] - 1u;
+    }
+  }
+}
+
+// root key -> voxel index (k0: the voxel of the sweep's first point) and the voxel centre itself (k_fx_acc's reference point)
+__device__ __forceinline__ void fx_key_voxel(const ExParams &P, uint32_t key, int k0x, int k0y, int k0z, int &kx, int &ky, int &kz, double (&cc)[3]) {
+  kx = (int)(key & 1023u) - 512 + k0x, ky = (int)((key >> 10) & 1023u) - 512 + k0y, kz = (int)(key >> 20) - 512 + k0z;
+  cc[0] = (0.5 + kx) * P.vs_f, cc[1] = (0.5 + ky) * P.vs_f, cc[2] = (0.5 + kz) * P.vs_f;
+}
+
+// the 16 list heads of this lane's child, in time order: position p holds bin minbin + p.  They live in LDS (the walks index them
+// dynamically; a register array would go to scratch memory).  Returns the positions with a list
+__device__ __forceinline__ uint32_t fx_load_heads(const unsigned long long *blk, bool have_parent, uint32_t minbin, uint32_t *heads) {
+  uint32_t occ = 0;
+  // (the loads do not wait for minbin: slot s goes to position (s - minbin) mod 16)
+  const uint4 *hq = (const uint4 *)(blk + kFxHdrW) + (threadIdx.x & 7) * (kFxSlots / 4);
+  uint32_t hv[kFxSlots];
+#pragma unroll
+  for (int q = 0; q < kFxSlots / 4; ++q) {
+    const uint4 v = have_parent ? hq[q] : make_uint4(0u, 0u, 0u, 0u);
+    hv[4 * q] = v.x, hv[4 * q + 1] = v.y, hv[4 * q + 2] = v.z, hv[4 * q + 3] = v.w;
+  }
+#pragma unroll
+  for (int s = 0; s < kFxSlots; ++s) {
+    const uint32_t p = ((uint32_t)s - minbin) & (kFxSlots - 1);
+    heads[p] = hv[s];
+    if (hv[s]) occ |= 1u << p;
+  }
+  __builtin_amdgcn_wave_barrier();
+  return occ;
+}
+
+__device__ __forceinline__ double fx_tick_time(const FxArgs &A, unsigned long long tk) { return A.t_lo + (double)tk * A.inv_tick; }  // exact inverse of k_fx_acc's tick
+// does a new temporal cluster start at a bin whose first tick is tmin, after a bin whose last tick + 1 is prev_p1 (cc:24)?
+__device__ __forceinline__ bool fx_starts(const FxArgs &A, unsigned long long tmin, unsigned long long prev_p1, int why) {
+  if (prev_p1 == 0ull) return true;
+  const double dt = fx_tick_time(A, tmin) - fx_tick_time(A, prev_p1 - 1ull);
+  if (fabs(dt - A.P.gap) <= 8.0 * A.inv_tick) fx_fallback(A.status, why);  // ticks may be rounded: do not decide here
+  return dt > A.P.gap;
+}
+
+// slots: every wavefront takes what it needs from its sub-range wsub with one atomic per round; the atomic can be issued ahead of
+// the work that decides who really needs a slot (a slot taken in vain is a hole nobody refers to)
+__device__ __forceinline__ uint32_t fx_slots_issue(const FxArgs &A, uint32_t wsub, bool want, unsigned long long &m) {
+  m = __ballot(want);
+  uint32_t base_ = 0;
+  if (m && threadIdx.x == 0) base_ = atomicAdd(fx_cnt(A, kFxStSlots, wsub), (uint32_t)__popcll(m));
+  return base_;
+}
+__device__ __forceinline__ uint32_t fx_slots_finish(const FxArgs &A, uint32_t wsub, bool want, unsigned long long m, uint32_t base_, int why) {
+  if (!m) return 0xFFFFFFFFu;
+  base_ = (uint32_t)__shfl((int)base_, 0);
+  const uint32_t local = base_ + (uint32_t)__popcll(m & ((1ull << threadIdx.x) - 1ull));
+  if (want && local >= A.slots_per) {
+    fx_fallback(A.status, why);
+    return 0xFFFFFFFFu;
+  }
+  return wsub * A.slots_per + local;
+}
+__device__ __forceinline__ uint32_t fx_take_slots(const FxArgs &A, uint32_t wsub, bool want, int why) {
+  unsigned long long m;
+  const uint32_t b = fx_slots_issue(A, wsub, want, m);
+  return fx_slots_finish(A, wsub, want, m, b, why);
+}
+
+// a closing cluster with cluster_min points or more is put aside as a job (word 11: its owner, the lane of the child or 64 + group
+// for a root) in the wavefront's staging area jb.  WAVE-UNIFORM call.  Returns the job's position in the lane that stored one,
+// kFxJobCap in every other lane
+__device__ __forceinline__ uint32_t fx_push_job(const FxArgs &A, unsigned long long *jb, uint32_t &jcnt, bool closing, const FxPart &cl, uint32_t ordv,
+                                                uint32_t owner, int why) {
+  const bool want = closing && (int)cl.n >= A.P.cluster_min;
+  const unsigned long long m = __ballot(want);
+  if (!m) return (uint32_t)kFxJobCap;
+  const uint32_t pos = jcnt + (uint32_t)__popcll(m & ((1ull << threadIdx.x) - 1ull));
+  jcnt += (uint32_t)__popcll(m);
+  if (!want) return (uint32_t)kFxJobCap;
+  if (pos >= (uint32_t)kFxJobCap) {
+    fx_fallback(A.status, why);
+    return (uint32_t)kFxJobCap;
+  }
+  ulonglong2 *o = (ulonglong2 *)(jb + (size_t)pos * kFxJobW);
+  o[0] = make_ulonglong2((unsigned long long)cl.n | ((unsigned long long)ordv << 32), (unsigned long long)cl.st);
+  o[1] = make_ulonglong2((unsigned long long)cl.s[0], (unsigned long long)cl.s[1]);
+  o[2] = make_ulonglong2((unsigned long long)cl.s[2], (unsigned long long)cl.ss[0]);
+  o[3] = make_ulonglong2((unsigned long long)cl.ss[1], (unsigned long long)cl.ss[2]);
+  o[4] = make_ulonglong2((unsigned long long)cl.ss[3], (unsigned long long)cl.ss[4]);
+  o[5] = make_ulonglong2((unsigned long long)cl.ss[5], (unsigned long long)owner);
+  return pos;
+}
+
+// Every lane walks the record lists of its node CHAINS TIME BINS AT A TIME (independent lists: that many records in flight per lane -
+// a single list is one dependent HBM round trip per record, and the busiest node of the sweep sets the kernel's duration), then
+// handles the finished bins in time order: node total, temporal clusters (ClusterSurfels' first loop, cc:19-29).  Whether the node is
+// a plane is only known at the end, so every cluster that closes with enough points is put aside as a JOB (push_job); the jobs of the
+// nodes that turn out to be planes with several clusters get their PCA afterwards, 64 at a time - one lane per job, whoever owns it.
+// add_root: every bin is also added to the parent's root node (root: its 16 time bins in LDS; ds atomics, the eight children of a
+// root share the bin).
+template <int LEVEL, int CHAINS, class PushJob>
+__device__ __forceinline__ void fx_walk_node(const FxArgs &A, uint32_t occ, uint32_t minbin, const uint32_t *heads, bool add_root,
+                                             unsigned long long (*root)[13], const FxWhy &why, PushJob &push_job, FxPart &tot, uint32_t &ncl) {
+  fx_zero(tot);
+  ncl = 0;
+  uint32_t todo = (WC_DBG(A.P, 512)) ? 0u : occ;
+  unsigned long long prev_p1 = 0ull;
+  FxPart cur;
+  fx_zero(cur);
+  uint32_t ord = 0;
+  while (__ballot(todo != 0u)) {
+    uint32_t ix[CHAINS], bn[CHAINS];
+    int pj[CHAINS];
+    FxPart b[CHAINS];
+#pragma unroll
+    for (int j = 0; j < CHAINS; ++j) {
+      fx_zero(b[j]);
+      pj[j] = 0, ix[j] = 0u;
+      if (todo) {
+        pj[j] = __ffs((int)todo) - 1;
+        todo &= todo - 1u;
+        ix[j] = heads[pj[j]];
+      }
+      bn[j] = minbin + (uint32_t)pj[j];
+    }
+    int guard = 0;
+    const bool several = __ballot(ix[1] != 0u) != 0ull;  // (a sweep with run structure: one bin per node, one list)
+    if (!several) {
+      while (__ballot(ix[0] != 0u)) {
+        fx_stepn<1, CHAINS>(A, LEVEL, ix, bn, b);
+        if (++guard > 200000) {
+          fx_fallback(A.status, why.walk1);
+          break;
+        }
+      }
+    } else {
+      for (;;) {
+        uint32_t any = 0u;
+#pragma unroll
+        for (int j = 0; j < CHAINS; ++j) any |= ix[j];
+        if (!__ballot(any != 0u)) break;
+        fx_stepn<CHAINS, CHAINS>(A, LEVEL, ix, bn, b);
+        if (++guard > 200000) {
+          fx_fallback(A.status, why.walkn);
+          break;
+        }
+      }
+      if (guard > A.P.merge_min && threadIdx.x == 0) {  // lists of more than three records: the next sweep merges them first (k_fx_merge)
+        uint32_t *hm = host_mailbox(A.status);
+        if (hm) hm[LEVEL == 1 ? 15 : 16] = 1u;  // (a word per level: the next sweep merges only the level that had long lists)
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < CHAINS; ++j) {
+      if (j > 0 && !several) break;
+      const bool have = b[j].n != 0u;
+      bool closing = false;
+      if (have) {
+        if (b[j].n > (1u << 20)) fx_fallback(A.status, why.big_bin);  // 2^42 x n must stay below 2^63
+        if (fx_starts(A, kFxTMax - b[j].tmin_inv, prev_p1, why.gap)) {
+          ++ncl;
+          closing = cur.n != 0u;
+        }
+        prev_p1 = b[j].tmax_p1;
+        fx_acc(tot, b[j]);
+        if (add_root) fx_add_cell(&root[pj[j]][0], b[j]);
+      }
+      push_job(closing, cur, ord, (uint32_t)threadIdx.x);
+      if (closing) {
+        ++ord;
+        fx_zero(cur);
+      }
+      if (have) fx_acc(cur, b[j]);
+    }
+  }
+  push_job(ncl > 1u, cur, ord, (uint32_t)threadIdx.x);  // the last of several clusters (a single one is the node itself)
+}
+
+// the temporal clusters of the root node of this lane's group (lanes with `on`) from its time bins, summed over the children in
+// LDS (root); closed clusters go to push_job.  Returns their number
+template <class PushJob>
+__device__ __forceinline__ uint32_t fx_root_clusters(const FxArgs &A, bool on, const unsigned long long (*root)[13], int why_gap, PushJob &push_job) {
+  const uint32_t owner = 64u + (uint32_t)(threadIdx.x >> 3);
+  uint32_t root_ncl = 0;
+  FxPart cur;
+  fx_zero(cur);
+  unsigned long long prev_p1 = 0ull;
+  uint32_t ord = 0;
+  for (int p = 0; p < kFxSlots; ++p) {
+    bool closing = false;
+    FxPart b;
+    fx_zero(b);
+    if (on) {
+      const unsigned long long *c = &root[p][0];
+      if ((uint32_t)c[0]) {
+        b.n = (uint32_t)c[0], b.st = (long long)c[1];
+        for (int i = 0; i < 3; ++i) b.s[i] = (long long)c[2 + i];
+        for (int i = 0; i < 6; ++i) b.ss[i] = (long long)c[5 + i];
+        b.tmin_inv = c[11], b.tmax_p1 = c[12];
+        if (fx_starts(A, kFxTMax - b.tmin_inv, prev_p1, why_gap)) {
+          ++root_ncl;
+          closing = cur.n != 0u;
+        }
+        prev_p1 = b.tmax_p1;
+      }
+    }
+    push_job(closing, cur, ord, owner);
+    if (closing) {
+      ++ord;
+      fx_zero(cur);
+    }
+    if (b.n) fx_acc(cur, b);
+  }
+  push_job(root_ncl > 1u, cur, ord, owner);
+  return root_ncl;
+}
+
+// ---- node tests (InitOctoTree cc:129-138, CutOctoTree cc:170-183) of the children (tot: a child's sums, ncl: its temporal
+//      clusters) and the emission of the plane nodes with ONE temporal cluster: the cluster's sums are the node's, so is its PCA
+//      (cc:32-64).  Out: rt = the root node (LEVEL 1: all children), parent_live, split = the group's tested non-plane children
+//      (LEVEL 1 with a layer 2).  Returns the pending emission: its bucket entry is stored after the root's test (the atomic's
+//      round trip runs beside it).  s_flag[lane]: the child is a plane with several temporal clusters, its jobs are emitted ----
+template <int LEVEL>
+__device__ __forceinline__ FxEmit fx_test_children(const FxArgs &A, bool have_parent, const FxPart &tot, uint32_t ncl, uint32_t key, uint32_t o1p, int kx,
+                                                   int ky, int kz, const double *cc, float q0, uint32_t wsub, int why_slots, uint8_t *s_flag,
+                                                   uint32_t *s_gkey, uint32_t *s_go1p, FxPart &rt, bool &parent_live, uint32_t &split) {
+  const ExParams &P = A.P;
+  const int lane = threadIdx.x, g = lane >> 3, gl = lane & 7;
+  fx_zero(rt);
+  if (LEVEL == 1) {
+    rt = tot;
+    fx_gsum8(rt);
+  }
+  parent_live = LEVEL == 1 ? (have_parent && (int)rt.n > P.min_points) : have_parent;  // nothing exists below an untested root
+  const bool children_exist = LEVEL == 1 ? (P.max_layer >= 1) : true;
+  const bool tested = parent_live && children_exist && (int)tot.n > P.min_points && !(WC_DBG(P, 256));
+  // (the slots of the nodes with ONE temporal cluster are requested before the PCA that decides whether they are planes)
+  const bool early = tested && ncl == 1u && (int)tot.n >= P.cluster_min;
+  unsigned long long early_m;
+  const uint32_t early_b = fx_slots_issue(A, wsub, early, early_m);
+  FxPca pc;
+  pc.near = false;
+  if (tested) {
+    fx_pca(A, tot, cc, pc);
+    if (pc.near) fx_fallback(A.status, 13);
+  }
+  const bool plane = tested && (pc.r.ev[0] < P.thr) && (pc.r.like > P.min_like);  // cc:106-111
+  split = (LEVEL == 1 && P.max_layer >= 2) ? ((uint32_t)(__ballot(tested && !plane) >> (g * 8)) & 0xFFu) : 0u;
+  FxEmit pend;
+  pend.on = false, pend.entry = 0, pend.bkt = 0, pend.r = 0, pend.rank = 0, pend.lead = lane;
+  {
+    const bool want = plane && ncl == 1u && (int)tot.n >= P.cluster_min && !(pc.r.ev[0] > P.thr || pc.r.like < P.min_like);
+    const uint32_t sl = fx_slots_finish(A, wsub, early, early_m, early_b, why_slots);
+    if (want && sl != 0xFFFFFFFFu) {
+      if (LEVEL == 1)
+        pend = fx_emit_begin(A, pc.r, sl, 1, (uint32_t)gl, 0u, 0u, kx, ky, kz, q0);
+      else
+        pend = fx_emit_begin(A, pc.r, sl, 2, o1p, (uint32_t)gl, 0u, kx, ky, kz, q0);
+    }
+  }
+  s_flag[lane] = (plane && ncl > 1u && !(WC_DBG(P, 128))) ? 1 : 0;
+  if (gl == 0) s_gkey[g] = key, s_go1p[g] = o1p, s_flag[64 + g] = 0;
+  return pend;
+}
+
+// ---- the root node (LEVEL 1; Q4: a plane root emits AND its children are tested): lane 0 of the group.  root_ncl_of(rpl), a
+//      WAVE-UNIFORM call, gives the number of temporal clusters of the lanes whose root is a plane ----
+template <class RootNcl>
+__device__ __forceinline__ void fx_test_root(const FxArgs &A, bool parent_live, const FxPart &rt, const double *cc, int kx, int ky, int kz, float q0,
+                                             uint32_t wsub, int why_slots, uint8_t *s_flag, RootNcl root_ncl_of) {
+  const ExParams &P = A.P;
+  if (!__ballot(parent_live)) return;
+  const int g = threadIdx.x >> 3, gl = threadIdx.x & 7;
+  // (roots that provably are no planes - fx_surely_not_plane - skip the eigen-decomposition; a wavefront whose roots all are skips it
+  // as a whole)
+  const bool rtest = parent_live && gl == 0 && !fx_surely_not_plane(A, rt, cc);
+  FxPca rp;
+  rp.near = false;
+  rp.r.ev[0] = 1e300, rp.r.like = 0.0;
+  if (rtest) {
+    fx_pca(A, rt, cc, rp);
+    if (rp.near) fx_fallback(A.status, 14);
+  }
+  const bool rpl = rtest && (rp.r.ev[0] < P.thr) && (rp.r.like > P.min_like);
+  const uint32_t root_ncl = root_ncl_of(rpl);
+  if (rpl && root_ncl > 1u && !(WC_DBG(P, 1024))) s_flag[64 + g] = 1;
+  const bool want = rpl && root_ncl == 1u && (int)rt.n >= P.cluster_min && !(rp.r.ev[0] > P.thr || rp.r.like < P.min_like);
+  const uint32_t sl = fx_take_slots(A, wsub, want, why_slots);
+  if (want && sl != 0xFFFFFFFFu) fx_emit(A, rp.r, sl, 0, 0u, 0u, 0u, kx, ky, kz, q0);
+}
+
+// ---- one job per lane (want): a cluster of a plane node with several of them.  PCA, cluster gates (cc:33, :54), emission under
+//      the owner's identity (owner: lane of the child, 64 + group for a root; s_gkey / s_go1p: the groups' keys and octants) ----
+template <int LEVEL>
+__device__ __forceinline__ void fx_run_job(const FxArgs &A, bool want, uint32_t owner, const FxPart &cl, uint32_t ordv, int k0x, int k0y, int k0z,
+                                           float q0, uint32_t wsub, const FxWhy &why, const uint32_t *s_gkey, const uint32_t *s_go1p) {
+  const ExParams &P = A.P;
+  const uint32_t og = owner < 64u ? owner >> 3 : owner - 64u;
+  int jx, jy, jz;
+  double jc[3];
+  fx_key_voxel(P, s_gkey[og], k0x, k0y, k0z, jx, jy, jz, jc);
+  FxPca cp;
+  cp.near = false;
+  if (want) {
+    fx_pca(A, cl, jc, cp);
+    if (cp.near) {
+      fx_fallback(A.status, 15);
+      if (why.job_which >= 0) fx_fallback(A.status, why.job_which + cp.which);
+    }
+    want = !(cp.r.ev[0] > P.thr || cp.r.like < P.min_like);
+  }
+  const uint32_t sl = fx_take_slots(A, wsub, want, why.slots);
+  if (want && sl != 0xFFFFFFFFu) {
+    if (owner >= 64u)
+      fx_emit(A, cp.r, sl, 0, 0u, 0u, ordv, jx, jy, jz, q0);
+    else if (LEVEL == 1)
+      fx_emit(A, cp.r, sl, 1, owner & 7u, 0u, ordv, jx, jy, jz, q0);
+    else
+      fx_emit(A, cp.r, sl, 2, s_go1p[og], owner & 7u, ordv, jx, jy, jz, q0);
+  }
+}
+
+// ---- LEVEL 1: queue the tested layer-1 nodes that are not planes (split) for the layer-2 pass (cc:175-182), one atomic per
+//      wavefront for the eight groups' demands.  Returns whether this root keeps its header and hash entry for that pass ----
+__device__ __forceinline__ bool fx_queue_layer2(const FxArgs &A, bool have_parent, uint32_t split, uint32_t pidx, uint32_t key, unsigned long long *blk,
+                                                uint32_t wsub) {
+  const int lane = threadIdx.x, g = lane >> 3, gl = lane & 7;
+  const uint32_t nq = (uint32_t)__popc(split);
+  uint32_t dem = (gl == 0 && have_parent) ? nq : 0u, pre = dem;
+  for (int d = 8; d < 64; d <<= 1) {
+    const uint32_t o = __shfl_up(pre, d);
+    if (lane >= d) pre += o;
+  }
+  const uint32_t wave_total = (uint32_t)__shfl((int)pre, 56);
+  uint32_t base_ = 0;
+  if (wave_total) {
+    if (lane == 0) base_ = atomicAdd(fx_cnt(A, kFxStNodes2, wsub), wave_total);
+    base_ = (uint32_t)__shfl((int)base_, 0);
+  }
+  const uint32_t gbase = (uint32_t)__shfl((int)(base_ + pre - dem), g * 8);  // this group's first local index
+  bool queued = false;
+  if (have_parent && nq) {
+    if (gbase + nq > A.mq_per) {
+      fx_fallback(A.status, 16);
+    } else {
+      const uint32_t first = wsub * A.mq_per + gbase;
+      queued = true;
+      if (gl == 0) {
+        uint32_t *w32 = (uint32_t *)blk;
+        w32[12] = split;
+        w32[13] = first;
+      }
+      if ((split >> gl) & 1u) {
+        const uint32_t qn = first + (uint32_t)__popc(split & ((1u << gl) - 1u));
+        uint32_t *q32 = (uint32_t *)(A.blk2 + (size_t)qn * kFxBlockW);
+        const bool first_child = (split & ((1u << gl) - 1u)) == 0u;  // this node's group cleans the root's entries after the layer-2 pass
+        q32[0] = pidx | ((uint32_t)gl << 28) | (first_child ? 0x80000000u : 0u);
+        q32[1] = key + 1u;
+      }
+    }
+  }
+  return queued;
+}
+
+// ---- the tables are zero at rest: the list heads of this lane's child; the header and the root's hash entry (lane 0 of the group).
+//      A root with queued layer-1 nodes keeps header and hash entry for the layer-2 pass (k_fx_acc<2> looks the root up and reads
+//      the split mask); the group of its first queued node clears them afterwards ----
+__device__ __forceinline__ void fx_clear_heads(unsigned long long *blk) {
+  uint4 *hz = (uint4 *)(blk + kFxHdrW) + (threadIdx.x & 7) * 4;
+  hz[0] = hz[1] = hz[2] = hz[3] = make_uint4(0u, 0u, 0u, 0u);
+}
+template <int LEVEL>
+__device__ __forceinline__ void fx_clear_header(const FxArgs &A, unsigned long long *blk, uint32_t pidx, bool queued) {
+  uint32_t *w32 = (uint32_t *)blk;
+  if (LEVEL == 1) {
+    if (!queued) {  // nothing queued (or the queue was full: flagged); (reading w32[12] back here cost a round trip)
+      w32[2] = 0u;
+      A.rkey[pidx] = 0u;
+    }
+  } else {
+    const uint32_t ro = w32[0];
+    w32[0] = w32[1] = w32[2] = 0u;
+    if (ro & 0x80000000u) {
+      const uint32_t rslot = ro & 0xFFFFFFFu;
+      uint32_t *r32 = (uint32_t *)(A.blk + (size_t)rslot * kFxBlockW);
+      r32[2] = r32[12] = r32[13] = 0u;
+      A.rkey[rslot] = 0u;
+    }
+  }
+}
+
+// ---- the node stage in ONE launch: walk, tests, jobs, layer-2 queue and clean-up of eight parents per wavefront, kept in registers
+//      from the walk to the tests ----
+constexpr FxWhy kFxWhyNodes = {7, 8, 9, 10, 11, 12, -1};
 template <int LEVEL>
 __global__ void __launch_bounds__(64) k_fx_nodes(FxArgs A) {
   __shared__ uint32_t s_heads[64][kFxSlots + 1];          // the 16 list heads of every lane's child, in time order
@@ -1184,40 +1625,9 @@ __global__ void __launch_bounds__(64) k_fx_nodes(FxArgs A) {
   const int k0x = vox(x0, P.vs), k0y = vox(y0, P.vs), k0z = vox(z0, P.vs);
   const float q0 = P.vs_f / 4;
   const uint32_t wsub = blockIdx.x & (kFxSub - 1);
-  auto tick_time = [&](unsigned long long tk) { return A.t_lo + (double)tk * A.inv_tick; };  // exact inverse of k_fx_acc's tick
-  // does a new temporal cluster start at a bin whose first tick is tmin, after a bin whose last tick + 1 is prev_p1 (cc:24)?
-  auto starts = [&](unsigned long long tmin, unsigned long long prev_p1) -> bool {
-    if (prev_p1 == 0ull) return true;
-    const double dt = tick_time(tmin) - tick_time(prev_p1 - 1ull);
-    if (fabs(dt - P.gap) <= 8.0 * A.inv_tick) fx_fallback(A.status, 7);  // ticks may be rounded: do not decide here
-    return dt > P.gap;
-  };
-  // slots: every wavefront takes what it needs from its sub-range with one atomic per round; the atomic can be issued ahead of
-  // the work that decides who really needs a slot (a slot taken in vain is a hole nobody refers to)
-  auto slots_issue = [&](bool want, unsigned long long &m) -> uint32_t {
-    m = __ballot(want);
-    uint32_t base_ = 0;
-    if (m && lane == 0) base_ = atomicAdd(fx_cnt(A, kFxStSlots, wsub), (uint32_t)__popcll(m));
-    return base_;
-  };
-  auto slots_finish = [&](bool want, unsigned long long m, uint32_t base_) -> uint32_t {
-    if (!m) return 0xFFFFFFFFu;
-    base_ = (uint32_t)__shfl((int)base_, 0);
-    const uint32_t local = base_ + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    if (want && local >= A.slots_per) {
-      fx_fallback(A.status, 8);
-      return 0xFFFFFFFFu;
-    }
-    return wsub * A.slots_per + local;
-  };
-  auto take_slots = [&](bool want) -> uint32_t {
-    unsigned long long m;
-    const uint32_t b = slots_issue(want, m);
-    return slots_finish(want, m, b);
-  };
   if (WC_DBG(P, 2048)) return;
   for (uint32_t it = 0;; ++it) {
-    uint32_t pidx = 0;  // dense index of this group's parent
+    uint32_t pidx = 0;  // block index of this group's parent
     bool have_parent;
     if (stat) {
       const uint32_t chunk = blockIdx.x / kFxSub + it * nwj;
@@ -1235,68 +1645,15 @@ __global__ void __launch_bounds__(64) k_fx_nodes(FxArgs A) {
       if (w0 >= total) break;
       const uint32_t gi = w0 + (uint32_t)g;
       have_parent = gi < total;
-      if (have_parent) {
-        uint32_t rem = gi;
-        bool found = false;
-#pragma unroll
-        for (int j = 0; j < kFxSub; ++j) {
-          const uint32_t cj = cnts[j];
-          if (!found) {
-            if (rem < cj) {
-              pidx = (uint32_t)j * per + rem;
-              found = true;
-            } else {
-              rem -= cj;
-            }
-          }
-        }
-      }
-      if (LEVEL == 1 && have_parent) pidx = A.rlist[pidx];  // dense list entry -> hash slot = block index
+      pidx = fx_dense_parent<LEVEL>(A, cnts, per, gi, have_parent);
     }
     unsigned long long *blk = (LEVEL == 1 ? A.blk : A.blk2) + (size_t)pidx * kFxBlockW;
-    const uint32_t *h32 = (const uint32_t *)blk;
-    uint32_t key = 0, o1p = 0, minbin = 0;
-    if (have_parent) {
-      minbin = 0xFFFFFFFFu - h32[2];
-      if (LEVEL == 1) {
-        key = A.rkey[pidx] - 1u;
-      } else {  // header of a queued node (written when it was queued): word 0 = root slot | o1 << 28 | first-child flag << 31,
-        const uint32_t ro = h32[0];  // word 1 = root key + 1
-        o1p = (ro >> 28) & 7u;
-        key = h32[1] - 1u;
-      }
-    }
-    const int kx = (int)(key & 1023u) - 512 + k0x, ky = (int)((key >> 10) & 1023u) - 512 + k0y, kz = (int)(key >> 20) - 512 + k0z;
+    uint32_t key, o1p, minbin;
+    fx_parent_header<LEVEL>(A, blk, pidx, have_parent, key, o1p, minbin);
+    int kx, ky, kz;
     double cc[3];
-    {
-      const double cx = (0.5 + kx) * P.vs_f, cy = (0.5 + ky) * P.vs_f, cz = (0.5 + kz) * P.vs_f;
-      cc[0] = cx, cc[1] = cy, cc[2] = cz;  // (the voxel centre itself: k_fx_acc's reference point)
-    }
-    // the 16 list heads of this lane's child, in time order: position p holds bin minbin + p.  They live in LDS (the walks
-    // below index them dynamically; a register array would go to scratch memory)
-    uint32_t occ = 0;  // positions with a list
-    {  // (the loads do not wait for minbin: slot s goes to position (s - minbin) mod 16)
-      const uint4 *hq = (const uint4 *)(blk + kFxHdrW) + gl * (kFxSlots / 4);
-      uint32_t hv[kFxSlots];
-#pragma unroll
-      for (int q = 0; q < kFxSlots / 4; ++q) {
-        const uint4 v = have_parent ? hq[q] : make_uint4(0u, 0u, 0u, 0u);
-        hv[4 * q] = v.x, hv[4 * q + 1] = v.y, hv[4 * q + 2] = v.z, hv[4 * q + 3] = v.w;
-      }
-#pragma unroll
-      for (int s = 0; s < kFxSlots; ++s) {
-        const uint32_t p = ((uint32_t)s - minbin) & (kFxSlots - 1);
-        s_heads[lane][p] = hv[s];
-        if (hv[s]) occ |= 1u << p;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    // Every lane walks the record lists of its node kFxChains TIME BINS AT A TIME (independent lists: that many records in
-    // flight per lane - a single list is one dependent HBM round trip per record, and the busiest node of the sweep sets the
-    // kernel's duration), then handles the finished bins in time order: node total, temporal clusters (ClusterSurfels' first
-    // loop, cc:19-29).  Whether the node is a plane is only known at the end, so every cluster that closes with enough
-    // points is put aside as a JOB (its sums, in this wavefront's part of A.jobs); the jobs of the nodes that turn out to be
-    // planes with several clusters get their PCA afterwards, 64 at a time - one lane per job, whoever owns it.
+    fx_key_voxel(P, key, k0x, k0y, k0z, kx, ky, kz, cc);
+    const uint32_t occ = fx_load_heads(blk, have_parent, minbin, s_heads[lane]);
     uint32_t jcnt = 0;  // jobs of this wavefront (uniform)
     // no node of the wavefront has more than one time bin (a sweep with run structure): a node's total IS its bin, and the
     // root's bins are only summed (below) if a root turns out to be a plane
@@ -1306,204 +1663,34 @@ __global__ void __launch_bounds__(64) k_fx_nodes(FxArgs A) {
       __builtin_amdgcn_wave_barrier();
     }
     unsigned long long *jb = A.jobs + (size_t)blockIdx.x * kFxJobCap * kFxJobW;
-    auto push_job = [&](bool closing, const FxPart &cl, uint32_t ordv, uint32_t owner) {  // WAVE-UNIFORM call
-      const bool want = closing && (int)cl.n >= P.cluster_min;
-      const unsigned long long m = __ballot(want);
-      if (!m) return;
-      const uint32_t pos = jcnt + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      jcnt += (uint32_t)__popcll(m);
-      if (!want) return;
-      if (pos >= (uint32_t)kFxJobCap) {
-        fx_fallback(A.status, 9);
-        return;
-      }
-      s_jown[pos] = (uint8_t)owner;
-      ulonglong2 *o = (ulonglong2 *)(jb + (size_t)pos * kFxJobW);
-      o[0] = make_ulonglong2((unsigned long long)cl.n | ((unsigned long long)ordv << 32), (unsigned long long)cl.st);
-      o[1] = make_ulonglong2((unsigned long long)cl.s[0], (unsigned long long)cl.s[1]);
-      o[2] = make_ulonglong2((unsigned long long)cl.s[2], (unsigned long long)cl.ss[0]);
-      o[3] = make_ulonglong2((unsigned long long)cl.ss[1], (unsigned long long)cl.ss[2]);
-      o[4] = make_ulonglong2((unsigned long long)cl.ss[3], (unsigned long long)cl.ss[4]);
-      o[5] = make_ulonglong2((unsigned long long)cl.ss[5], 0ull);
+    auto push_job = [&](bool closing, const FxPart &cl, uint32_t ordv, uint32_t owner) {  // (the owner in LDS too: the job loop loads only the jobs it runs)
+      const uint32_t pos = fx_push_job(A, jb, jcnt, closing, cl, ordv, owner, kFxWhyNodes.jobs);
+      if (pos < (uint32_t)kFxJobCap) s_jown[pos] = (uint8_t)owner;
     };
     FxPart tot;
-    fx_zero(tot);
-    uint32_t ncl = 0;
-    {
-      uint32_t todo = (WC_DBG(P, 512)) ? 0u : occ;
-      unsigned long long prev_p1 = 0ull;
-      FxPart cur;
-      fx_zero(cur);
-      uint32_t ord = 0;
-      while (__ballot(todo != 0u)) {
-        uint32_t ix[kFxChains], bn[kFxChains];
-        int pj[kFxChains];
-        FxPart b[kFxChains];
-#pragma unroll
-        for (int j = 0; j < kFxChains; ++j) {
-          fx_zero(b[j]);
-          pj[j] = 0, ix[j] = 0u;
-          if (todo) {
-            pj[j] = __ffs((int)todo) - 1;
-            todo &= todo - 1u;
-            ix[j] = s_heads[lane][pj[j]];
-          }
-          bn[j] = minbin + (uint32_t)pj[j];
-        }
-        int guard = 0;
-        const bool several = __ballot(ix[1] != 0u) != 0ull;  // (a sweep with run structure: one bin per node, one list)
-        if (!several) {
-          while (__ballot(ix[0] != 0u)) {
-            fx_stepn<1>(A, LEVEL, ix, bn, b);
-            if (++guard > 200000) {
-              fx_fallback(A.status, 10);
-              break;
-            }
-          }
-        } else {
-          for (;;) {
-            uint32_t any = 0u;
-#pragma unroll
-            for (int j = 0; j < kFxChains; ++j) any |= ix[j];
-            if (!__ballot(any != 0u)) break;
-            fx_stepn<kFxChains>(A, LEVEL, ix, bn, b);
-            if (++guard > 200000) {
-              fx_fallback(A.status, 11);
-              break;
-            }
-          }
-          if (guard > A.P.merge_min && lane == 0) {  // lists of more than three records: the next sweep merges them first (k_fx_merge)
-            uint32_t *hm = host_mailbox(A.status);
-            if (hm) hm[LEVEL == 1 ? 15 : 16] = 1u;  // (a word per level: the next sweep merges only the level that had long lists)
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < kFxChains; ++j) {
-          if (j > 0 && !several) break;
-          const bool have = b[j].n != 0u;
-          bool closing = false;
-          if (have) {
-            if (b[j].n > (1u << 20)) fx_fallback(A.status, 12);  // 2^42 x n must stay below 2^63
-            if (starts(kFxTMax - b[j].tmin_inv, prev_p1)) {
-              ++ncl;
-              closing = cur.n != 0u;
-            }
-            prev_p1 = b[j].tmax_p1;
-            fx_acc(tot, b[j]);
-            if (LEVEL == 1 && !one_bin) fx_add_cell(&s_root[g][pj[j]][0], b[j]);  // (ds atomics: the eight children of a root share the bin)
-          }
-          push_job(closing, cur, ord, (uint32_t)lane);
-          if (closing) {
-            ++ord;
-            fx_zero(cur);
-          }
-          if (have) fx_acc(cur, b[j]);
-        }
-      }
-      push_job(ncl > 1u, cur, ord, (uint32_t)lane);  // the last of several clusters (a single one is the node itself)
-    }
+    uint32_t ncl;
+    fx_walk_node<LEVEL, kFxChains>(A, occ, minbin, s_heads[lane], LEVEL == 1 && !one_bin, s_root[g], kFxWhyNodes, push_job, tot, ncl);
     __builtin_amdgcn_wave_barrier();
-    // ---- node tests (InitOctoTree cc:129-138, CutOctoTree cc:170-183) ----
-    FxPart rt;  // LEVEL 1: the root node = all children
-    fx_zero(rt);
+    FxPart rt;
+    bool parent_live;
+    uint32_t split;
+    const FxEmit pend = fx_test_children<LEVEL>(A, have_parent, tot, ncl, key, o1p, kx, ky, kz, cc, q0, wsub, kFxWhyNodes.slots, s_flag, s_gkey, s_go1p,
+                                                rt, parent_live, split);
     if (LEVEL == 1) {
-      rt = tot;
-      fx_gsum8(rt);
-    }
-    const bool parent_live = LEVEL == 1 ? (have_parent && (int)rt.n > P.min_points) : have_parent;  // nothing exists below an untested root
-    const bool children_exist = LEVEL == 1 ? (P.max_layer >= 1) : true;
-    const bool tested = parent_live && children_exist && (int)tot.n > P.min_points && !(WC_DBG(P, 256));
-    // (the slots of the nodes with ONE temporal cluster are requested before the PCA that decides whether they are planes)
-    const bool early = tested && ncl == 1u && (int)tot.n >= P.cluster_min;
-    unsigned long long early_m;
-    const uint32_t early_b = slots_issue(early, early_m);
-    FxPca pc;
-    pc.near = false;
-    if (tested) {
-      fx_pca(A, tot, cc, pc);
-      if (pc.near) fx_fallback(A.status, 13);
-    }
-    const bool plane = tested && (pc.r.ev[0] < P.thr) && (pc.r.like > P.min_like);  // cc:106-111
-    const int sh = g * 8;
-    const uint32_t split = (LEVEL == 1 && P.max_layer >= 2) ? ((uint32_t)(__ballot(tested && !plane) >> sh) & 0xFFu) : 0u;
-
-    // ---- emission ----
-    FxEmit pend;  // (the bucket entry of a child's surfel is stored after the root's test: the atomic's round trip runs beside it)
-    pend.on = false, pend.entry = 0, pend.bkt = 0, pend.r = 0, pend.rank = 0, pend.lead = lane;
-    {  // plane nodes with ONE temporal cluster: the cluster's sums are the node's, so is its PCA (cc:32-64)
-      const bool want = plane && ncl == 1u && (int)tot.n >= P.cluster_min && !(pc.r.ev[0] > P.thr || pc.r.like < P.min_like);
-      const uint32_t sl = slots_finish(early, early_m, early_b);
-      if (want && sl != 0xFFFFFFFFu) {
-        if (LEVEL == 1)
-          pend = fx_emit_begin(A, pc.r, sl, 1, (uint32_t)gl, 0u, 0u, kx, ky, kz, q0);
-        else
-          pend = fx_emit_begin(A, pc.r, sl, 2, o1p, (uint32_t)gl, 0u, kx, ky, kz, q0);
-      }
-    }
-    s_flag[lane] = (plane && ncl > 1u && !(WC_DBG(P, 128))) ? 1 : 0;
-    if (gl == 0) s_gkey[g] = key, s_go1p[g] = o1p, s_flag[64 + g] = 0;
-    // ---- the root node (LEVEL 1; Q4: a plane root emits AND its children are tested): lane 0 of the group; its time bins,
-    //      summed over the children, are in LDS ----
-    if (LEVEL == 1 && __ballot(parent_live)) {
-      // (roots that provably are no planes - fx_surely_not_plane - skip the eigen-decomposition; a wavefront whose roots all are skips it
-      // as a whole)
-      const bool rtest = parent_live && gl == 0 && !fx_surely_not_plane(A, rt, cc);
-      FxPca rp;
-      rp.near = false;
-      rp.r.ev[0] = 1e300, rp.r.like = 0.0;
-      if (rtest) {
-        fx_pca(A, rt, cc, rp);
-        if (rp.near) fx_fallback(A.status, 14);
-      }
-      const bool rpl = rtest && (rp.r.ev[0] < P.thr) && (rp.r.like > P.min_like);
-      uint32_t root_ncl = 0;
-      if (__ballot(rpl)) {
-        if (one_bin) {
+      fx_test_root(A, parent_live, rt, cc, kx, ky, kz, q0, wsub, kFxWhyNodes.slots, s_flag, [&](bool rpl) -> uint32_t {
+        if (!__ballot(rpl)) return 0u;
+        if (one_bin) {  // the root's bins were not summed during the walk: each child's one bin is its total
           for (int i = lane; i < 8 * kFxSlots * 13; i += 64) (&s_root[0][0][0])[i] = 0ull;
           __builtin_amdgcn_wave_barrier();
-          const bool grp = ((__ballot(rpl) >> sh) & 0xFFull) != 0ull;
+          const bool grp = ((__ballot(rpl) >> (g * 8)) & 0xFFull) != 0ull;
           if (grp && tot.n) fx_add_cell(&s_root[g][__ffs((int)occ) - 1][0], tot);
           __builtin_amdgcn_wave_barrier();
         }
-        FxPart cur;
-        fx_zero(cur);
-        unsigned long long prev_p1 = 0ull;
-        uint32_t ord = 0;
-        for (int p = 0; p < kFxSlots; ++p) {
-          bool closing = false;
-          FxPart b;
-          fx_zero(b);
-          if (rpl) {
-            const unsigned long long *c = &s_root[g][p][0];
-            if ((uint32_t)c[0]) {
-              b.n = (uint32_t)c[0], b.st = (long long)c[1];
-              for (int i = 0; i < 3; ++i) b.s[i] = (long long)c[2 + i];
-              for (int i = 0; i < 6; ++i) b.ss[i] = (long long)c[5 + i];
-              b.tmin_inv = c[11], b.tmax_p1 = c[12];
-              if (starts(kFxTMax - b.tmin_inv, prev_p1)) {
-                ++root_ncl;
-                closing = cur.n != 0u;
-              }
-              prev_p1 = b.tmax_p1;
-            }
-          }
-          push_job(closing, cur, ord, 64u + (uint32_t)g);
-          if (closing) {
-            ++ord;
-            fx_zero(cur);
-          }
-          if (b.n) fx_acc(cur, b);
-        }
-        push_job(root_ncl > 1u, cur, ord, 64u + (uint32_t)g);
-        if (rpl && root_ncl > 1u && !(WC_DBG(P, 1024))) s_flag[64 + g] = 1;
-      }
-      const bool want = rpl && root_ncl == 1u && (int)rt.n >= P.cluster_min && !(rp.r.ev[0] > P.thr || rp.r.like < P.min_like);
-      const uint32_t sl = take_slots(want);
-      if (want && sl != 0xFFFFFFFFu) fx_emit(A, rp.r, sl, 0, 0u, 0u, 0u, kx, ky, kz, q0);
+        return fx_root_clusters(A, rpl, s_root[g], kFxWhyNodes.gap, push_job);
+      });
     }
     fx_emit_end(A, pend);
-    // ---- the jobs: clusters of the plane nodes with several of them.  One lane per job: PCA, cluster gates (cc:33, :54),
-    //      emission under the owner's identity ----
+    // ---- the jobs, one lane each ----
     if (jcnt) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // the job stores of this wavefront are in L2
     __builtin_amdgcn_wave_barrier();
     for (uint32_t r0 = 0; r0 < min(jcnt, (uint32_t)kFxJobCap); r0 += 64u) {
@@ -1512,14 +1699,6 @@ __global__ void __launch_bounds__(64) k_fx_nodes(FxArgs A) {
       const uint32_t owner = want ? s_jown[ji] : 0u;
       want = want && s_flag[owner] != 0;
       if (!__ballot(want)) continue;
-      const uint32_t og = owner < 64u ? owner >> 3 : owner - 64u;
-      const uint32_t okey = s_gkey[og];
-      const int jx = (int)(okey & 1023u) - 512 + k0x, jy = (int)((okey >> 10) & 1023u) - 512 + k0y, jz = (int)(okey >> 20) - 512 + k0z;
-      double jc[3];
-      {
-        const double cx = (0.5 + jx) * P.vs_f, cy = (0.5 + jy) * P.vs_f, cz = (0.5 + jz) * P.vs_f;
-        jc[0] = cx, jc[1] = cy, jc[2] = cz;
-      }
       FxPart cl;
       fx_zero(cl);
       uint32_t ordv = 0;
@@ -1532,86 +1711,13 @@ __global__ void __launch_bounds__(64) k_fx_nodes(FxArgs A) {
         for (int i = 0; i < 3; ++i) cl.s[i] = (long long)w[2 + i];
         for (int i = 0; i < 6; ++i) cl.ss[i] = (long long)w[5 + i];
       }
-      FxPca cp;
-      cp.near = false;
-      if (want) {
-        fx_pca(A, cl, jc, cp);
-        if (cp.near) fx_fallback(A.status, 15);
-        want = !(cp.r.ev[0] > P.thr || cp.r.like < P.min_like);
-      }
-      const uint32_t sl = take_slots(want);
-      if (want && sl != 0xFFFFFFFFu) {
-        if (owner >= 64u)
-          fx_emit(A, cp.r, sl, 0, 0u, 0u, ordv, jx, jy, jz, q0);
-        else if (LEVEL == 1)
-          fx_emit(A, cp.r, sl, 1, owner & 7u, 0u, ordv, jx, jy, jz, q0);
-        else
-          fx_emit(A, cp.r, sl, 2, s_go1p[og], owner & 7u, ordv, jx, jy, jz, q0);
-      }
+      fx_run_job<LEVEL>(A, want, owner, cl, ordv, k0x, k0y, k0z, q0, wsub, kFxWhyNodes, s_gkey, s_go1p);
     }
     __builtin_amdgcn_wave_barrier();
-    // ---- LEVEL 1: queue the tested layer-1 nodes that are not planes for the layer-2 pass (cc:175-182) ----
-    bool queued = false;  // this root keeps its header and hash entry for the layer-2 pass
-    if (LEVEL == 1) {
-      const uint32_t nq = (uint32_t)__popc(split);
-      // one atomic per wavefront: the eight groups' demands
-      uint32_t dem = (gl == 0 && have_parent) ? nq : 0u, pre = dem;
-      for (int d = 8; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(pre, d);
-        if (lane >= d) pre += o;
-      }
-      const uint32_t wave_total = (uint32_t)__shfl((int)pre, 56);
-      uint32_t base_ = 0;
-      if (wave_total) {
-        if (lane == 0) base_ = atomicAdd(fx_cnt(A, kFxStNodes2, wsub), wave_total);
-        base_ = (uint32_t)__shfl((int)base_, 0);
-      }
-      const uint32_t gbase = (uint32_t)__shfl((int)(base_ + pre - dem), g * 8);  // this group's first local index
-      if (have_parent && nq) {
-        if (gbase + nq > A.mq_per) {
-          fx_fallback(A.status, 16);
-        } else {
-          const uint32_t first = wsub * A.mq_per + gbase;
-          queued = true;
-          if (gl == 0) {
-            uint32_t *w32 = (uint32_t *)blk;
-            w32[12] = split;
-            w32[13] = first;
-          }
-          if ((split >> gl) & 1u) {
-            const uint32_t qn = first + (uint32_t)__popc(split & ((1u << gl) - 1u));
-            uint32_t *q32 = (uint32_t *)(A.blk2 + (size_t)qn * kFxBlockW);
-            const bool first_child = (split & ((1u << gl) - 1u)) == 0u;  // this node's group cleans the root's entries after the layer-2 pass
-            q32[0] = pidx | ((uint32_t)gl << 28) | (first_child ? 0x80000000u : 0u);
-            q32[1] = key + 1u;
-          }
-        }
-      }
-    }
-    // ---- the tables are zero at rest: the list heads of this lane's child, the header, the root's hash entry.  A root with
-    //      queued layer-1 nodes keeps header and hash entry for the layer-2 pass (k_fx_acc<2> looks the root up and reads the
-    //      split mask); the group of its first queued node clears them afterwards ----
+    const bool queued = LEVEL == 1 && fx_queue_layer2(A, have_parent, split, pidx, key, blk, wsub);
     if (have_parent && !(WC_DBG(P, 8192))) {
-      uint4 *hz = (uint4 *)(blk + kFxHdrW) + gl * 4;
-      hz[0] = hz[1] = hz[2] = hz[3] = make_uint4(0u, 0u, 0u, 0u);
-      if (gl == 0) {
-        uint32_t *w32 = (uint32_t *)blk;
-        if (LEVEL == 1) {
-          if (!queued) {  // nothing queued (or the queue was full: flagged); (reading w32[12] back here cost a round trip)
-            w32[2] = 0u;
-            A.rkey[pidx] = 0u;
-          }
-        } else {
-          const uint32_t ro = w32[0];
-          w32[0] = w32[1] = w32[2] = 0u;
-          if (ro & 0x80000000u) {
-            const uint32_t rslot = ro & 0xFFFFFFFu;
-            uint32_t *r32 = (uint32_t *)(A.blk + (size_t)rslot * kFxBlockW);
-            r32[2] = r32[12] = r32[13] = 0u;
-            A.rkey[rslot] = 0u;
-          }
-        }
-      }
+      fx_clear_heads(blk);
+      if (gl == 0) fx_clear_header<LEVEL>(A, blk, pidx, queued);
     }
   }
 }

@@ -1,27 +1,29 @@
 // extract_split.inc — the node stage of the default extraction path as TWO kernels (included by extract.hip behind
-// extract_fast.inc, whose tables, records and helpers it uses).
+// extract_fast.inc, whose tables, records and node-stage routines it uses).
 //
 // k_fx_nodes (extract_fast.inc) does everything that follows the streaming pass in one launch: it walks the record lists,
 // finds the temporal clusters, tests the nodes (two PCAs per wavefront), emits, queues layer-2 nodes and cleans the tables.
 // That is the right shape for ONE sweep of a million points - 488 wavefronts, less than one per SIMD, three launch heads
 // per sweep - but the kernel needs 464 VGPRs: one wavefront per SIMD.  A 10 M-point cloud (or ten sweeps enqueued together)
 // has ~5 000 of them, five rounds at 5 % occupancy, and the knock-out runs (profiles/exp_knockout.sh, 10 M points) put 72 of
-// its 126 us into the node tests + emission and 50 into the walk.  Here the two halves are separate launches:
-//   k_fx_walk<L>   8 lanes per parent (lane = child octant), 8 parents per wavefront, as in k_fx_nodes: record lists -> node
-//                  totals, temporal clusters (ClusterSurfels' first loop, cc:19-29) of the children AND of the root node
-//                  (its time bins are summed in LDS), every closed cluster with >= cluster_min points put aside as a job;
-//                  per wavefront it leaves 11 words per child (n | clusters, St, Sq, Sqq; lane-contiguous), a 256-byte
-//                  descriptor (the parents' blocks and keys, the roots' cluster counts) and its jobs in a pool; list heads
-//                  are cleared behind it.  No PCA: two list chains in flight instead of four, <= 256 VGPRs.
-//   k_fx_test<L>   the same wavefront-to-parents mapping, read from the descriptor (one round of loads, nothing to search):
-//                  node tests (InitOctoTree cc:129-138, CutOctoTree cc:170-183), emission of the single-cluster planes, the
-//                  jobs of the planes with several clusters, the layer-2 queue, header + hash entry cleared behind it.
-// Same integer sums, same gates, same ids as k_fx_nodes - the output of a sweep does not depend on which form ran (tested).
+// its 126 us into the node tests + emission and 50 into the walk.  Here the two halves are separate launches, built from the
+// same routines as k_fx_nodes (fx_walk_node, fx_root_clusters, fx_test_children, fx_test_root, fx_run_job, fx_queue_layer2, ...);
+// what is their own is the hand-over between them:
+//   k_fx_walk<L>   the walk with two list chains in flight instead of four (no PCA: <= 256 VGPRs) and the root node's temporal
+//                  clusters when some root spans several bins (root_multi; its bins are summed in LDS during the walk).  Per
+//                  wavefront it leaves 11 words per child (n | clusters, St, Sq, Sqq; lane-contiguous), a 256-byte descriptor
+//                  (the parents' blocks and keys, the roots' cluster counts) and its jobs in a pool; list heads are cleared
+//                  behind it.
+//   k_fx_test<L>   the same wavefront-to-parents mapping, read from the descriptor (one round of loads, nothing to search): node
+//                  tests, emission, the jobs from the pool, the layer-2 queue, header + hash entry cleared behind it.
+// The output of a sweep does not depend on which form ran (tests/test_extract_gpu.py compares the bytes).
 
 constexpr int kFxNodeW = 11;      // u64 words per child node: n | ncl << 32, St, Sq[3], Sqq[6]
 constexpr int kFxDescW = 64;      // u32 words per wavefront descriptor: 8 x {block index, key, flags, spare} | jobs | job base
 constexpr int kFxWalkChains = 2;  // list chains in flight per lane (k_fx_merge leaves lists of one record)
 constexpr uint32_t kFxJobSub0 = 8;  // job sub-pool counters: sub-counters 8..15 of the spill bank (the spill pool uses 0..7)
+// (the codes of a job's PCA near a gate, 17 + FxPca::which, overlap the walk's own 17 ... 19)
+constexpr FxWhy kFxWhySplit = {17, 23, 18, 19, 20, 21, 17};
 
 template <int LEVEL>
 __device__ __forceinline__ void fx_walk_body(const FxArgs &A, const uint32_t bid, const uint32_t nblk) {
@@ -37,13 +39,6 @@ __device__ __forceinline__ void fx_walk_body(const FxArgs &A, const uint32_t bid
     cnts[j] = min(*fx_cnt(A, bank, j), per);
     total += cnts[j];
   }
-  auto tick_time = [&](unsigned long long tk) { return A.t_lo + (double)tk * A.inv_tick; };
-  auto starts = [&](unsigned long long tmin, unsigned long long prev_p1) -> bool {  // (k_fx_nodes: the same rule, the same margin)
-    if (prev_p1 == 0ull) return true;
-    const double dt = tick_time(tmin) - tick_time(prev_p1 - 1ull);
-    if (fabs(dt - P.gap) <= 8.0 * A.inv_tick) fx_fallback(A.status, 17);
-    return dt > P.gap;
-  };
   if (WC_DBG(P, 2048)) return;
   unsigned long long *jb = A.jobs + (size_t)bid * kFxJobCap * kFxJobW;  // staging area of this wavefront's jobs
   for (uint32_t it = 0;; ++it) {
@@ -52,54 +47,11 @@ __device__ __forceinline__ void fx_walk_body(const FxArgs &A, const uint32_t bid
     if (w0 >= total) break;
     const uint32_t gi = w0 + (uint32_t)g;
     const bool have_parent = gi < total;
-    uint32_t pidx = 0;
-    if (have_parent) {
-      uint32_t rem = gi;
-      bool found = false;
-#pragma unroll
-      for (int j = 0; j < kFxSub; ++j) {
-        const uint32_t cj = cnts[j];
-        if (!found) {
-          if (rem < cj) {
-            pidx = (uint32_t)j * per + rem;
-            found = true;
-          } else {
-            rem -= cj;
-          }
-        }
-      }
-    }
-    if (LEVEL == 1 && have_parent) pidx = A.rlist[pidx];
+    const uint32_t pidx = fx_dense_parent<LEVEL>(A, cnts, per, gi, have_parent);
     unsigned long long *blk = (LEVEL == 1 ? A.blk : A.blk2) + (size_t)pidx * kFxBlockW;
-    const uint32_t *h32 = (const uint32_t *)blk;
-    uint32_t key = 0, o1p = 0, minbin = 0;
-    if (have_parent) {
-      minbin = 0xFFFFFFFFu - h32[2];
-      if (LEVEL == 1) {
-        key = A.rkey[pidx] - 1u;
-      } else {
-        const uint32_t ro = h32[0];
-        o1p = (ro >> 28) & 7u;
-        key = h32[1] - 1u;
-      }
-    }
-    uint32_t occ = 0;
-    {
-      const uint4 *hq = (const uint4 *)(blk + kFxHdrW) + gl * (kFxSlots / 4);
-      uint32_t hv[kFxSlots];
-#pragma unroll
-      for (int q = 0; q < kFxSlots / 4; ++q) {
-        const uint4 v = have_parent ? hq[q] : make_uint4(0u, 0u, 0u, 0u);
-        hv[4 * q] = v.x, hv[4 * q + 1] = v.y, hv[4 * q + 2] = v.z, hv[4 * q + 3] = v.w;
-      }
-#pragma unroll
-      for (int s = 0; s < kFxSlots; ++s) {
-        const uint32_t p = ((uint32_t)s - minbin) & (kFxSlots - 1);
-        s_heads[lane][p] = hv[s];
-        if (hv[s]) occ |= 1u << p;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
+    uint32_t key, o1p, minbin;
+    fx_parent_header<LEVEL>(A, blk, pidx, have_parent, key, o1p, minbin);
+    const uint32_t occ = fx_load_heads(blk, have_parent, minbin, s_heads[lane]);
     uint32_t jcnt = 0;
     // the bins of the ROOT node (all children together): which ones exist is known from the children's masks
     uint32_t rocc = occ;
@@ -111,101 +63,12 @@ __device__ __forceinline__ void fx_walk_body(const FxArgs &A, const uint32_t bid
       for (int i = lane; i < 8 * kFxSlots * 13; i += 64) (&s_root[0][0][0])[i] = 0ull;
       __builtin_amdgcn_wave_barrier();
     }
-    auto push_job = [&](bool closing, const FxPart &cl, uint32_t ordv, uint32_t owner) {  // WAVE-UNIFORM call
-      const bool want = closing && (int)cl.n >= P.cluster_min;
-      const unsigned long long m = __ballot(want);
-      if (!m) return;
-      const uint32_t pos = jcnt + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      jcnt += (uint32_t)__popcll(m);
-      if (!want) return;
-      if (pos >= (uint32_t)kFxJobCap) {
-        fx_fallback(A.status, 18);
-        return;
-      }
-      ulonglong2 *o = (ulonglong2 *)(jb + (size_t)pos * kFxJobW);
-      o[0] = make_ulonglong2((unsigned long long)cl.n | ((unsigned long long)ordv << 32), (unsigned long long)cl.st);
-      o[1] = make_ulonglong2((unsigned long long)cl.s[0], (unsigned long long)cl.s[1]);
-      o[2] = make_ulonglong2((unsigned long long)cl.s[2], (unsigned long long)cl.ss[0]);
-      o[3] = make_ulonglong2((unsigned long long)cl.ss[1], (unsigned long long)cl.ss[2]);
-      o[4] = make_ulonglong2((unsigned long long)cl.ss[3], (unsigned long long)cl.ss[4]);
-      o[5] = make_ulonglong2((unsigned long long)cl.ss[5], (unsigned long long)owner);  // owner: lane of the child, 64 + group for a root
+    auto push_job = [&](bool closing, const FxPart &cl, uint32_t ordv, uint32_t owner) {
+      fx_push_job(A, jb, jcnt, closing, cl, ordv, owner, kFxWhySplit.jobs);
     };
     FxPart tot;
-    fx_zero(tot);
-    uint32_t ncl = 0;
-    {
-      uint32_t todo = (WC_DBG(P, 512)) ? 0u : occ;
-      unsigned long long prev_p1 = 0ull;
-      FxPart cur;
-      fx_zero(cur);
-      uint32_t ord = 0;
-      while (__ballot(todo != 0u)) {
-        uint32_t ix[kFxWalkChains], bn[kFxWalkChains];
-        int pj[kFxWalkChains];
-        FxPart b[kFxWalkChains];
-#pragma unroll
-        for (int j = 0; j < kFxWalkChains; ++j) {
-          fx_zero(b[j]);
-          pj[j] = 0, ix[j] = 0u;
-          if (todo) {
-            pj[j] = __ffs((int)todo) - 1;
-            todo &= todo - 1u;
-            ix[j] = s_heads[lane][pj[j]];
-          }
-          bn[j] = minbin + (uint32_t)pj[j];
-        }
-        int guard = 0;
-        const bool several = __ballot(ix[1] != 0u) != 0ull;
-        if (!several) {
-          while (__ballot(ix[0] != 0u)) {
-            fx_stepn<1, kFxWalkChains>(A, LEVEL, ix, bn, b);
-            if (++guard > 200000) {
-              fx_fallback(A.status, 19);
-              break;
-            }
-          }
-        } else {
-          for (;;) {
-            uint32_t any = 0u;
-#pragma unroll
-            for (int j = 0; j < kFxWalkChains; ++j) any |= ix[j];
-            if (!__ballot(any != 0u)) break;
-            fx_stepn<kFxWalkChains, kFxWalkChains>(A, LEVEL, ix, bn, b);
-            if (++guard > 200000) {
-              fx_fallback(A.status, 20);
-              break;
-            }
-          }
-          if (guard > A.P.merge_min && lane == 0) {
-            uint32_t *hm = host_mailbox(A.status);
-            if (hm) hm[LEVEL == 1 ? 15 : 16] = 1u;  // (a word per level: the next sweep merges only the level that had long lists)
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < kFxWalkChains; ++j) {
-          if (j > 0 && !several) break;
-          const bool have = b[j].n != 0u;
-          bool closing = false;
-          if (have) {
-            if (b[j].n > (1u << 20)) fx_fallback(A.status, 21);
-            if (starts(kFxTMax - b[j].tmin_inv, prev_p1)) {
-              ++ncl;
-              closing = cur.n != 0u;
-            }
-            prev_p1 = b[j].tmax_p1;
-            fx_acc(tot, b[j]);
-            if (root_multi) fx_add_cell(&s_root[g][pj[j]][0], b[j]);
-          }
-          push_job(closing, cur, ord, (uint32_t)lane);
-          if (closing) {
-            ++ord;
-            fx_zero(cur);
-          }
-          if (have) fx_acc(cur, b[j]);
-        }
-      }
-      push_job(ncl > 1u, cur, ord, (uint32_t)lane);
-    }
+    uint32_t ncl;
+    fx_walk_node<LEVEL, kFxWalkChains>(A, occ, minbin, s_heads[lane], root_multi, s_root[g], kFxWhySplit, push_job, tot, ncl);
     __builtin_amdgcn_wave_barrier();
     // ---- the root node's temporal clusters (LEVEL 1): only a root that holds more than min_points is ever tested, and only a
     //      root with several bins can have several clusters ----
@@ -215,39 +78,7 @@ __device__ __forceinline__ void fx_walk_body(const FxArgs &A, const uint32_t bid
       rn = fx_gsum8(rn);
       const bool rl = have_parent && gl == 0 && (int)rn > P.min_points;
       root_ncl = rl ? 1u : 0u;
-      if (root_multi && __ballot(rl && (rocc & (rocc - 1u)) != 0u)) {
-        root_ncl = 0;
-        FxPart cur;
-        fx_zero(cur);
-        unsigned long long prev_p1 = 0ull;
-        uint32_t ord = 0;
-        for (int p = 0; p < kFxSlots; ++p) {
-          bool closing = false;
-          FxPart b;
-          fx_zero(b);
-          if (rl) {
-            const unsigned long long *c = &s_root[g][p][0];
-            if ((uint32_t)c[0]) {
-              b.n = (uint32_t)c[0], b.st = (long long)c[1];
-              for (int i = 0; i < 3; ++i) b.s[i] = (long long)c[2 + i];
-              for (int i = 0; i < 6; ++i) b.ss[i] = (long long)c[5 + i];
-              b.tmin_inv = c[11], b.tmax_p1 = c[12];
-              if (starts(kFxTMax - b.tmin_inv, prev_p1)) {
-                ++root_ncl;
-                closing = cur.n != 0u;
-              }
-              prev_p1 = b.tmax_p1;
-            }
-          }
-          push_job(closing, cur, ord, 64u + (uint32_t)g);
-          if (closing) {
-            ++ord;
-            fx_zero(cur);
-          }
-          if (b.n) fx_acc(cur, b);
-        }
-        push_job(root_ncl > 1u, cur, ord, 64u + (uint32_t)g);
-      }
+      if (root_multi && __ballot(rl && (rocc & (rocc - 1u)) != 0u)) root_ncl = fx_root_clusters(A, rl, s_root[g], kFxWhySplit.gap, push_job);
     }
     // ---- what k_fx_test needs: the children's sums (word-major: every store is one 512-byte row), the descriptor, the jobs ----
     {
@@ -282,11 +113,7 @@ __device__ __forceinline__ void fx_walk_body(const FxArgs &A, const uint32_t bid
       }
       if (lane == 0) *(uint2 *)(wd + 32) = make_uint2(nj, jbase);
     }
-    // ---- the list heads of this lane's child are zero at rest ----
-    if (have_parent && !(WC_DBG(P, 8192))) {
-      uint4 *hz = (uint4 *)(blk + kFxHdrW) + gl * 4;
-      hz[0] = hz[1] = hz[2] = hz[3] = make_uint4(0u, 0u, 0u, 0u);
-    }
+    if (have_parent && !(WC_DBG(P, 8192))) fx_clear_heads(blk);
     __builtin_amdgcn_wave_barrier();  // (the staging area and s_heads are reused by the next round)
   }
 }
@@ -307,27 +134,6 @@ __device__ __forceinline__ void fx_test_body(const FxArgs &A, const uint32_t bid
   const int k0x = vox(x0, P.vs), k0y = vox(y0, P.vs), k0z = vox(z0, P.vs);
   const float q0 = P.vs_f / 4;
   const uint32_t wsub = bid & (kFxSub - 1);
-  auto slots_issue = [&](bool want, unsigned long long &m) -> uint32_t {
-    m = __ballot(want);
-    uint32_t base_ = 0;
-    if (m && lane == 0) base_ = atomicAdd(fx_cnt(A, kFxStSlots, wsub), (uint32_t)__popcll(m));
-    return base_;
-  };
-  auto slots_finish = [&](bool want, unsigned long long m, uint32_t base_) -> uint32_t {
-    if (!m) return 0xFFFFFFFFu;
-    base_ = (uint32_t)__shfl((int)base_, 0);
-    const uint32_t local = base_ + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    if (want && local >= A.slots_per) {
-      fx_fallback(A.status, 23);
-      return 0xFFFFFFFFu;
-    }
-    return wsub * A.slots_per + local;
-  };
-  auto take_slots = [&](bool want) -> uint32_t {
-    unsigned long long m;
-    const uint32_t b = slots_issue(want, m);
-    return slots_finish(want, m, b);
-  };
   if (WC_DBG(P, 2048)) return;
   for (uint32_t it = 0;; ++it) {
     const uint32_t vw = bid + it * nblk;
@@ -344,12 +150,9 @@ __device__ __forceinline__ void fx_test_body(const FxArgs &A, const uint32_t bid
     const uint32_t pidx = d4.x, key = d4.y, o1p = (d4.z >> 1) & 7u, root_ncl = (d4.z >> 8) & 0xFFu;
     const uint32_t jcnt = dj.x, jbase = dj.y;
     unsigned long long *blk = (LEVEL == 1 ? A.blk : A.blk2) + (size_t)pidx * kFxBlockW;
-    const int kx = (int)(key & 1023u) - 512 + k0x, ky = (int)((key >> 10) & 1023u) - 512 + k0y, kz = (int)(key >> 20) - 512 + k0z;
+    int kx, ky, kz;
     double cc[3];
-    {
-      const double cx = (0.5 + kx) * P.vs_f, cy = (0.5 + ky) * P.vs_f, cz = (0.5 + kz) * P.vs_f;
-      cc[0] = cx, cc[1] = cy, cc[2] = cz;  // (the voxel centre itself: k_fx_acc's reference point)
-    }
+    fx_key_voxel(P, key, k0x, k0y, k0z, kx, ky, kz, cc);
     FxPart tot;
     fx_zero(tot);
     uint32_t ncl = 0;
@@ -360,62 +163,15 @@ __device__ __forceinline__ void fx_test_body(const FxArgs &A, const uint32_t bid
 #pragma unroll
       for (int i = 0; i < 6; ++i) tot.ss[i] = (long long)nw[5 + i];
     }
-    // ---- node tests (InitOctoTree cc:129-138, CutOctoTree cc:170-183): as in k_fx_nodes ----
     FxPart rt;
-    fx_zero(rt);
-    if (LEVEL == 1) {
-      rt = tot;
-      fx_gsum8(rt);
-    }
-    const bool parent_live = LEVEL == 1 ? (have_parent && (int)rt.n > P.min_points) : have_parent;
-    const bool children_exist = LEVEL == 1 ? (P.max_layer >= 1) : true;
-    const bool tested = parent_live && children_exist && (int)tot.n > P.min_points && !(WC_DBG(P, 256));
-    const bool early = tested && ncl == 1u && (int)tot.n >= P.cluster_min;
-    unsigned long long early_m;
-    const uint32_t early_b = slots_issue(early, early_m);
-    FxPca pc;
-    pc.near = false;
-    if (tested) {
-      fx_pca(A, tot, cc, pc);
-      if (pc.near) fx_fallback(A.status, 13);
-    }
-    const bool plane = tested && (pc.r.ev[0] < P.thr) && (pc.r.like > P.min_like);
-    const int sh = g * 8;
-    const uint32_t split = (LEVEL == 1 && P.max_layer >= 2) ? ((uint32_t)(__ballot(tested && !plane) >> sh) & 0xFFu) : 0u;
-    FxEmit pend;
-    pend.on = false, pend.entry = 0, pend.bkt = 0, pend.r = 0, pend.rank = 0, pend.lead = lane;
-    {
-      const bool want = plane && ncl == 1u && (int)tot.n >= P.cluster_min && !(pc.r.ev[0] > P.thr || pc.r.like < P.min_like);
-      const uint32_t sl = slots_finish(early, early_m, early_b);
-      if (want && sl != 0xFFFFFFFFu) {
-        if (LEVEL == 1)
-          pend = fx_emit_begin(A, pc.r, sl, 1, (uint32_t)gl, 0u, 0u, kx, ky, kz, q0);
-        else
-          pend = fx_emit_begin(A, pc.r, sl, 2, o1p, (uint32_t)gl, 0u, kx, ky, kz, q0);
-      }
-    }
-    s_flag[lane] = (plane && ncl > 1u && !(WC_DBG(P, 128))) ? 1 : 0;
-    if (gl == 0) s_gkey[g] = key, s_go1p[g] = o1p, s_flag[64 + g] = 0;
-    if (LEVEL == 1 && __ballot(parent_live)) {  // the root node (Q4: a plane root emits AND its children are tested)
-      // (roots that provably are no planes - fx_surely_not_plane - skip the eigen-decomposition; a wavefront whose roots all are skips it
-      // as a whole)
-      const bool rtest = parent_live && gl == 0 && !fx_surely_not_plane(A, rt, cc);
-      FxPca rp;
-      rp.near = false;
-      rp.r.ev[0] = 1e300, rp.r.like = 0.0;
-      if (rtest) {
-        fx_pca(A, rt, cc, rp);
-        if (rp.near) fx_fallback(A.status, 14);
-      }
-      const bool rpl = rtest && (rp.r.ev[0] < P.thr) && (rp.r.like > P.min_like);
-      if (rpl && root_ncl > 1u && !(WC_DBG(P, 1024))) s_flag[64 + g] = 1;
-      const bool want = rpl && root_ncl == 1u && (int)rt.n >= P.cluster_min && !(rp.r.ev[0] > P.thr || rp.r.like < P.min_like);
-      const uint32_t sl = take_slots(want);
-      if (want && sl != 0xFFFFFFFFu) fx_emit(A, rp.r, sl, 0, 0u, 0u, 0u, kx, ky, kz, q0);
-    }
+    bool parent_live;
+    uint32_t split;
+    const FxEmit pend = fx_test_children<LEVEL>(A, have_parent, tot, ncl, key, o1p, kx, ky, kz, cc, q0, wsub, kFxWhySplit.slots, s_flag, s_gkey, s_go1p,
+                                                rt, parent_live, split);
+    if (LEVEL == 1) fx_test_root(A, parent_live, rt, cc, kx, ky, kz, q0, wsub, kFxWhySplit.slots, s_flag, [&](bool) { return root_ncl; });
     fx_emit_end(A, pend);
     __builtin_amdgcn_wave_barrier();
-    // ---- the jobs: clusters of the plane nodes with several of them ----
+    // ---- the jobs, one lane each, from the pool k_fx_walk filled ----
     const unsigned long long *jp = A.jobpool + ((size_t)(vw & 7u) * A.jobpool_per + jbase) * kFxJobW;
     for (uint32_t r0 = 0; r0 < jcnt; r0 += 64u) {
       const uint32_t ji = r0 + (uint32_t)lane;
@@ -426,14 +182,6 @@ __device__ __forceinline__ void fx_test_body(const FxArgs &A, const uint32_t bid
       const uint32_t owner = want ? min((uint32_t)w[11], 71u) : 0u;
       want = want && s_flag[owner] != 0;
       if (!__ballot(want)) continue;
-      const uint32_t og = owner < 64u ? owner >> 3 : owner - 64u;
-      const uint32_t okey = s_gkey[og];
-      const int jx = (int)(okey & 1023u) - 512 + k0x, jy = (int)((okey >> 10) & 1023u) - 512 + k0y, jz = (int)(okey >> 20) - 512 + k0z;
-      double jc[3];
-      {
-        const double cx = (0.5 + jx) * P.vs_f, cy = (0.5 + jy) * P.vs_f, cz = (0.5 + jz) * P.vs_f;
-        jc[0] = cx, jc[1] = cy, jc[2] = cz;
-      }
       FxPart cl;
       fx_zero(cl);
       cl.n = (uint32_t)w[0], cl.st = (long long)w[1];
@@ -442,80 +190,12 @@ __device__ __forceinline__ void fx_test_body(const FxArgs &A, const uint32_t bid
       for (int i = 0; i < 3; ++i) cl.s[i] = (long long)w[2 + i];
 #pragma unroll
       for (int i = 0; i < 6; ++i) cl.ss[i] = (long long)w[5 + i];
-      FxPca cp;
-      cp.near = false;
-      if (want) {
-        fx_pca(A, cl, jc, cp);
-        if (cp.near) fx_fallback(A.status, 15), fx_fallback(A.status, 17 + cp.which);  // (17 ... 19: which gate, FxPca::which)
-        want = !(cp.r.ev[0] > P.thr || cp.r.like < P.min_like);
-      }
-      const uint32_t sl = take_slots(want);
-      if (want && sl != 0xFFFFFFFFu) {
-        if (owner >= 64u)
-          fx_emit(A, cp.r, sl, 0, 0u, 0u, ordv, jx, jy, jz, q0);
-        else if (LEVEL == 1)
-          fx_emit(A, cp.r, sl, 1, owner & 7u, 0u, ordv, jx, jy, jz, q0);
-        else
-          fx_emit(A, cp.r, sl, 2, s_go1p[og], owner & 7u, ordv, jx, jy, jz, q0);
-      }
+      fx_run_job<LEVEL>(A, want, owner, cl, ordv, k0x, k0y, k0z, q0, wsub, kFxWhySplit, s_gkey, s_go1p);
     }
     __builtin_amdgcn_wave_barrier();
-    // ---- LEVEL 1: queue the tested layer-1 nodes that are not planes for the layer-2 pass (cc:175-182) ----
-    bool queued = false;
-    if (LEVEL == 1) {
-      const uint32_t nq = (uint32_t)__popc(split);
-      uint32_t dem = (gl == 0 && have_parent) ? nq : 0u, pre = dem;
-      for (int d = 8; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(pre, d);
-        if (lane >= d) pre += o;
-      }
-      const uint32_t wave_total = (uint32_t)__shfl((int)pre, 56);
-      uint32_t base_ = 0;
-      if (wave_total) {
-        if (lane == 0) base_ = atomicAdd(fx_cnt(A, kFxStNodes2, wsub), wave_total);
-        base_ = (uint32_t)__shfl((int)base_, 0);
-      }
-      const uint32_t gbase = (uint32_t)__shfl((int)(base_ + pre - dem), g * 8);
-      if (have_parent && nq) {
-        if (gbase + nq > A.mq_per) {
-          fx_fallback(A.status, 16);
-        } else {
-          const uint32_t first = wsub * A.mq_per + gbase;
-          queued = true;
-          if (gl == 0) {
-            uint32_t *w32 = (uint32_t *)blk;
-            w32[12] = split;
-            w32[13] = first;
-          }
-          if ((split >> gl) & 1u) {
-            const uint32_t qn = first + (uint32_t)__popc(split & ((1u << gl) - 1u));
-            uint32_t *q32 = (uint32_t *)(A.blk2 + (size_t)qn * kFxBlockW);
-            const bool first_child = (split & ((1u << gl) - 1u)) == 0u;
-            q32[0] = pidx | ((uint32_t)gl << 28) | (first_child ? 0x80000000u : 0u);
-            q32[1] = key + 1u;
-          }
-        }
-      }
-    }
-    // ---- header and hash entry are zero at rest (the list heads were cleared by k_fx_walk) ----
-    if (have_parent && gl == 0 && !(WC_DBG(P, 8192))) {
-      uint32_t *w32 = (uint32_t *)blk;
-      if (LEVEL == 1) {
-        if (!queued) {
-          w32[2] = 0u;
-          A.rkey[pidx] = 0u;
-        }
-      } else {
-        const uint32_t ro = w32[0];
-        w32[0] = w32[1] = w32[2] = 0u;
-        if (ro & 0x80000000u) {
-          const uint32_t rslot = ro & 0xFFFFFFFu;
-          uint32_t *r32 = (uint32_t *)(A.blk + (size_t)rslot * kFxBlockW);
-          r32[2] = r32[12] = r32[13] = 0u;
-          A.rkey[rslot] = 0u;
-        }
-      }
-    }
+    const bool queued = LEVEL == 1 && fx_queue_layer2(A, have_parent, split, pidx, key, blk, wsub);
+    // (the list heads were cleared by k_fx_walk)
+    if (have_parent && gl == 0 && !(WC_DBG(P, 8192))) fx_clear_header<LEVEL>(A, blk, pidx, queued);
     __builtin_amdgcn_wave_barrier();  // (s_flag / s_gkey are rewritten by the next round)
   }
 }
