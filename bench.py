@@ -7,7 +7,8 @@ BuildSurfels-equivalent surfel extraction of BASELINE.json config C2 (G2 patch l
 independent jobs in the reference, lidar_odometry.cc:523-525: a fresh GlobalMap per sweep), so the headline has no
 data-path collective and scaling is "weak".
 
-Prints ONE JSON line (rank 0).  Objects next to the contract keys:
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: it sets up, warms up, times the steps, writes
+--dump-outputs and prints the contract keys.  Everything else runs under --full, which adds these objects next to them:
   roofline        SURVEY §8(d): algorithmic bytes of the extraction STAGE / device time of ALL kernels of the stage (HIP events on
                   the ctx stream); the dominant kernel's own figure is a sub-object; `traffic` names the committed PMC summary it is
                   read from (it is not measured in this run)
@@ -261,6 +262,9 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--roots", type=int, default=3906, help="root voxels per sweep (C2: 3906 -> 999 936 points)")
+    ap.add_argument("--full", action="store_true", help="after the headline, run every other section (roofline, stage split, variants of the "
+                                                        "sweep, CPU baselines, clouds, LM window, odometry step, facade); the options below "
+                                                        "shape those sections")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--window-scans", type=int, default=20, help="sweeps in the LM window (C4: 20)")
@@ -340,7 +344,7 @@ def main():
 
     ctx = lib.Context(local_rank)  # raises if libwildcat_hip.so / the GPU is missing: there is no fallback path
     comm_kind = None
-    if use_dist:
+    if use_dist and args.full:  # (only the --full sections use collectives on the ctx stream)
         # the library's own RCCL communicator (csrc/comm.hip): collectives on the ctx stream, no host synchronisation; rank 0's
         # unique id travels through torch.distributed, which is plumbing here
         # (every step of the choice is agreed on by all ranks: a rank that fell back alone would leave the others in a collective)
@@ -397,6 +401,37 @@ def main():
         dump_outputs(args.dump_outputs, d_out[: n_s * 144].cpu().numpy().view(R.SURFEL), d_ids[: n_s * 16].cpu().numpy().view(R.SURFEL_ID),
                      budget=DUMP_BUDGET // world, prefix="rank%d_" % rank if world > 1 else "")
 
+    result = {
+        "metric": "surfel-extract Mpts/s",
+        "value": round(value, 2),
+        "unit": "Mpts/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 5),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": "C2: 1M-pt single scan (G2 patch lattice, %d pts -> %d surfels) per GPU, voxel-grid + 3-level octree + per-cell 3x3 PCA; "
+                               "input = the reference's 48-byte hilti_ros::Point records, consumed in place" % (n_pts, exp_surfels),
+                   "points_per_gpu": n_pts, "surfels_per_gpu": exp_surfels, "parallelism": "sweep-per-gpu x%d" % world},
+        "host": cpu_info(),
+        "communicator": comm_kind,
+    }
+
+    def finish():
+        if rank == 0:
+            real_stdout.write(json.dumps(result) + "\n")
+            real_stdout.flush()
+        ctx.close()
+        if dist.is_initialized():
+            dist.destroy_process_group()
+
+    if not args.full:
+        return finish()
+
     stages, roofline = extraction_stage(ctx, step, n_pts, exp_surfels, args.steps, measure_roots=args.roots if (rank == 0 and world == 1) else -1)
     # measured ceiling of this device: a 1 GiB device-to-device copy, bytes read + written per second
     copy_gbs = None
@@ -420,28 +455,7 @@ def main():
     roofline["frac_of_measured_copy"] = round(roofline["achieved"] / copy_gbs, 5) if copy_gbs else None
     roofline["driver_clock_frac"] = round((20 * n_pts + 144 * exp_surfels) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)  # incl. host turn-around
 
-    result = {
-        "metric": "surfel-extract Mpts/s",
-        "value": round(value, 2),
-        "unit": "Mpts/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 5),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": "C2: 1M-pt single scan (G2 patch lattice, %d pts -> %d surfels) per GPU, voxel-grid + 3-level octree + per-cell 3x3 PCA; "
-                               "input = the reference's 48-byte hilti_ros::Point records, consumed in place" % (n_pts, exp_surfels),
-                   "points_per_gpu": n_pts, "surfels_per_gpu": exp_surfels, "parallelism": "sweep-per-gpu x%d" % world},
-        "roofline": roofline,
-        "stages_ms": {k_: round(v, 5) for k_, v in stages.items()},
-        "stage_kernels": STAGE_KERNELS,
-        "host": cpu_info(),
-        "communicator": comm_kind,
-    }
+    result.update(roofline=roofline, stages_ms={k_: round(v, 5) for k_, v in stages.items()}, stage_kernels=STAGE_KERNELS)
 
     # --- several sweeps in flight (contexts = streams, each with its own scratch).  Never `value`. --------------------------
     try:
@@ -586,12 +600,7 @@ def main():
                 real_stdout.flush()
             os._exit(0)
 
-    if rank == 0:
-        real_stdout.write(json.dumps(result) + "\n")
-        real_stdout.flush()
-    ctx.close()
-    if dist.is_initialized():
-        dist.destroy_process_group()
+    finish()
 
 
 def bench_firing_order(ctx, args, world, rank, dev, torch, dist, to_dev):

@@ -14,7 +14,7 @@ rm -rf /tmp/kf; timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp
 ff=$(find /tmp/kf -name "*kernel_trace.csv" | head -1)
 python profiles/dev/facade_timeline.py $ff 3 > $O/${TAG}_facade_timeline.txt
 { echo "== facade, room stream (~50 sample states): one LM iteration"; python profiles/dev/lm_iteration.py $ff 5; } >> $O/${TAG}_lm_iterations.txt
-rm -rf /tmp/kc; timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/kc -o c -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras --in-flight 1 > /dev/null 2>&1
+rm -rf /tmp/kc; timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/kc -o c -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras --in-flight 1 > /dev/null 2>&1
 fc=$(find /tmp/kc -name "*kernel_trace.csv" | head -1)
 { echo "== C4 window (127 sample states): one LM iteration"; python profiles/dev/lm_iteration.py $fc 3; } >> $O/${TAG}_lm_iterations.txt
 cat $O/${TAG}_lm_iterations.txt

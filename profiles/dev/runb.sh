@@ -1,6 +1,6 @@
 O=${TMPDIR:-/tmp}/runb; mkdir -p $O
 timeout 600 python -m pytest tests/test_match_gpu.py -x -q -m gpu 2>&1 | tail -3
-WC_MATCH_DEBUG=1 WC_MATCH_TIMING=1 timeout 1200 python bench.py --steps 20 --no-cpu-baseline --no-clouds > $O/b1.json 2> $O/b1.err
+WC_MATCH_DEBUG=1 WC_MATCH_TIMING=1 timeout 1200 python bench.py --full --steps 20 --no-cpu-baseline --no-clouds > $O/b1.json 2> $O/b1.err
 grep "tree depth" $O/b1.err | sort -u -k3,8 | head -8; grep "k_knn_tree_group by" $O/b1.err | tail -4
 python - <<EOP
 import json

@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/kstats
 [ $# -eq 0 ] && set -- --no-extras
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kstats -o b -- python $R/bench.py --steps 50 --warmup 10 --no-cpu-baseline --in-flight 1 "$@" > /tmp/kstats.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kstats -o b -- python $R/bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --in-flight 1 "$@" > /tmp/kstats.log 2>&1
 python - "$PAT" <<'PY'
 import csv, glob, sys
 for f in glob.glob("/tmp/kstats/**/*kernel_stats.csv", recursive=True):

@@ -33,7 +33,7 @@ for r in rows:
     a[1] += float(r["TotalDurationNs"])
 tot = sum(v[1] for v in agg.values())
 with open(os.path.join(out, f"{tag}_kernel_stats.md"), "w") as f:
-    f.write(f"# rocprofv3 --kernel-trace --stats — `python bench.py --steps 100 --warmup 10 --no-cpu-baseline` ({tag})\n\n")
+    f.write(f"# rocprofv3 --kernel-trace --stats — `python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline` ({tag})\n\n")
     f.write("| kernel | calls | avg µs | total ms | % |\n|---|---:|---:|---:|---:|\n")
     for k, (c, t) in sorted(agg.items(), key=lambda kv: -kv[1][1]):
         f.write(f"| `{k}` | {c} | {t / c / 1e3:.1f} | {t / 1e6:.2f} | {100 * t / tot:.1f} |\n")
@@ -77,7 +77,7 @@ for m in ("OccupancyPercent", "MeanOccupancyPerCU", "VALUBusy", "LDSBankConflict
 if derived:
     with open(os.path.join(out, f"{tag}_occupancy.md"), "w") as f:
         f.write(f"# rocprofv3 --pmc OccupancyPercent / MeanOccupancyPerCU / VALUBusy / LDSBankConflict, one pass each ({tag})\n\n")
-        f.write("Mean over the dispatches of `python bench.py --steps 20 --warmup 5 --no-cpu-baseline --in-flight 1 --no-extras` "
+        f.write("Mean over the dispatches of `python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --in-flight 1 --no-extras` "
                 "(C2 extraction + C4 window).\n\n| kernel | OccupancyPercent | MeanOccupancyPerCU | VALUBusy % | LDSBankConflict % |\n|---|---:|---:|---:|---:|\n")
         for k in sorted(derived, key=lambda k: -agg.get(k, [0, 0.0])[1]):
             d = derived[k]
