@@ -64,7 +64,10 @@ int wc_ctx_set_params(wc_ctx *ctx, const wc_params *params);
  *                      two-collective form (IMU factors replicated; 16-byte cost collective, then the pose corners)
  *   lm_side_stream (1) two-collective form: the large collective on a side stream beside the bias elimination (1: with the in-library RCCL
  *                      binding, 0: never, 2: always - the choreography with a communicator of callbacks, for tests)
- *   lm_dense_radius    iterations whose trust-region radius exceeds 10^value take the dense step (default 10; 0 = never)
+ *   lm_dense_radius    iterations whose trust-region radius exceeds 10^value take the dense step (default 7: the largest radius at which
+ *                      the bias elimination's backward error stays below 1e-9 - tests/test_lm_step_gpu.py; 0 = never)
+ *   lm_radius0         initial trust-region radius of wc_window_solve: 10^value (default -1 = the library's 1e4); tests use it to
+ *                      look at the first step at other damping levels
  * Tests use it to run both forms of a choice on the same data.  Unknown names return WC_ERR_ARG. */
 int wc_ctx_set_dev_option(wc_ctx *ctx, const char *name, int value);
 /* Optional, for long-running callers (the facade calls it from its constructor): takes one-time costs out of the first calls - loads
@@ -314,7 +317,9 @@ int wc_window_linearize_timed(wc_ctx *ctx, const double *h_x, int reps, float *h
 int wc_window_solve(wc_ctx *ctx, double *h_x_inout, wc_solve_summary *summary, double *h_first_step);
 /* multi-GPU, for a caller that shards the factors ITSELF (each rank builds its own slices with wc_window_build): install a
  * "sum this device buffer over all ranks" callback; called once per linearisation on the packed {upper block pairs of H, g, cost}
- * buffer (layout: wc_window_build_sharded above) and once per candidate-cost evaluation (one double).  NULL removes it. */
+ * buffer (layout: wc_window_build_sharded above) and once per candidate-cost evaluation (one double).  NULL removes it.  On a
+ * problem built by wc_window_build_sharded - before or after the callback is installed - the callback runs THAT build's collectives
+ * in place of the communicator's (the two-collective form: {cost, spare}, then the pose corners); the form is the build's. */
 int wc_window_set_allreduce(wc_ctx *ctx, int (*fn)(void *user, double *d_buf, uint64_t count), void *user);
 
 /* voxel-downsampled point map (device resident) ------------------------------------------------------------------------------- */

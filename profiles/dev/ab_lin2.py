@@ -27,7 +27,7 @@ for name, (scans, patches) in (("C4 20x50000", (20, 50000)), ("10x31248", (10, 3
         ms = min(tms)
         if os.environ.get("AB_VERBOSE"): print(" ".join("%.3f" % t for t in tms))
         for kv in [s for s in spec.split(",") if s]:
-            ctx.set_dev_option(kv.split("=")[0], {"lm_side_stream": 1, "lm_dense_radius": 10}.get(kv.split("=")[0], 0))
+            ctx.set_dev_option(kv.split("=")[0], {"lm_side_stream": 1, "lm_dense_radius": 7}.get(kv.split("=")[0], 0))
         if first is None:
             first = (H, g, cost)
         print("%-12s [%-24s] %.4f ms per linearisation, pieces %d, |dH| %.1e |dg| %.1e |dcost| %.1e" % (

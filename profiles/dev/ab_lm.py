@@ -17,7 +17,7 @@ ctx.warmup() if hasattr(ctx, "warmup") else None
 def apply(spec, on):
     for kv in [s for s in spec.split(",") if s]:
         k, v = kv.split("=")
-        ctx.set_dev_option(k, int(v) if on else {"lm_side_stream": 1, "lm_dense_radius": 10, "fx_split": -1}.get(k, 0))
+        ctx.set_dev_option(k, int(v) if on else {"lm_side_stream": 1, "lm_dense_radius": 7, "fx_split": -1}.get(k, 0))
 
 
 def c4_like(scans, patches, seed):

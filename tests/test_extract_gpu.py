@@ -374,7 +374,7 @@ def test_development_options_and_warmup(gpu, oracle):
     for name in ("no_such_option",) + retired:
         with pytest.raises(lib.WildcatError):
             gpu.set_dev_option(name, 1)
-    for name, default in (("exact_sums", 0), ("lm_dense", 0), ("lm_dense_radius", 10), ("lm_one_collective", 0), ("lm_side_stream", 1)):
+    for name, default in (("exact_sums", 0), ("lm_dense", 0), ("lm_dense_radius", 7), ("lm_one_collective", 0), ("lm_side_stream", 1), ("lm_radius0", -1)):
         gpu.set_dev_option(name, default)  # (the defaults: the shared context is left as it was)
     pts, _ = synth.g2_lattice(300, m=32)
     s_ref, id_ref, _ = oracle.extract_surfels(pts)

@@ -72,6 +72,7 @@ const DevOpt kDevOpts[] = {
     {"lm_one_collective", "WC_LM_ONE_COLLECTIVE", &wc_dev_opts::lm_one_collective, true},
     {"lm_side_stream", "WC_LM_SIDE_STREAM", &wc_dev_opts::lm_side_stream, false},
     {"lm_dense_radius", "WC_LM_DENSE_RADIUS", &wc_dev_opts::lm_dense_radius, false},
+    {"lm_radius0", "WC_LM_RADIUS0", &wc_dev_opts::lm_radius0, false},
 };
 }  // namespace
 

@@ -3026,9 +3026,11 @@ __global__ void __launch_bounds__(1024) k_post_reduce(const double *g, const dou
 bool multi_gpu(const wc_ctx *ctx, const wc_window_state *W) {
   return W->allreduce != nullptr || (W->sharded && ctx->have_comm && ctx->comm.world > 1 && ctx->comm.allreduce_f64 != nullptr);
 }
-// the two-collective form: the window was sharded by wc_window_build_sharded with the IMU factors replicated, and the ctx's
-// communicator reduces it
-inline bool two_collectives(const wc_ctx *ctx, const wc_window_state *W) { return multi_gpu(ctx, W) && W->two_coll && !W->allreduce; }
+// the two-collective form: the window was sharded by wc_window_build_sharded with the IMU factors replicated.  The build
+// decides the form (W->two_coll) and nothing installed later changes it: a wc_window_set_allreduce callback only takes over the
+// collectives (do_allreduce).  Dropping to the packed form because a callback is installed summed the replicated IMU factors' H, g and
+// cost `world` times.
+inline bool two_collectives(const wc_ctx *ctx, const wc_window_state *W) { return multi_gpu(ctx, W) && W->two_coll; }
 int do_allreduce(wc_ctx *ctx, wc_window_state *W, double *d_buf, size_t count) {
   if (W->allreduce) {
     WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -3132,7 +3134,7 @@ int enqueue_linearize(wc_ctx *ctx, wc_window_state *W, const double *d_x, int ma
     // RCCL binding) - the ctx stream goes on with the bias elimination, which reads nothing of it, and waits in front of k_schur_form
     // (join_side).  Development option lm_side_stream: 0 = on the ctx stream, 2 = the side stream's choreography also with a communicator
     // of callbacks (tests: the callback then runs with both streams drained).
-    const bool rccl_side = ctx->comm.stream_ordered && ctx->rccl && ctx->comm.user == ctx->rccl;
+    const bool rccl_side = !W->allreduce && ctx->comm.stream_ordered && ctx->rccl && ctx->comm.user == ctx->rccl;  // (an installed callback carries both collectives)
     const bool side = ctx->dev.lm_side_stream == 2 || (ctx->dev.lm_side_stream == 1 && rccl_side);
     if (side) {
       if (!W->side) {
@@ -3358,7 +3360,7 @@ extern "C" int wc_window_solve(wc_ctx *ctx, double *h_x_inout, wc_solve_summary 
   summary->n_linearizations = 1;
   double cost = ctx->h_mail[0], gmax = ctx->h_mail[1];
   summary->initial_cost = cost;
-  double min_cost = cost, radius = 1e4, decrease = 2.0, x_norm = 0.0;
+  double min_cost = cost, radius = ctx->dev.lm_radius0 == -1 ? 1e4 : std::pow(10.0, (double)ctx->dev.lm_radius0), decrease = 2.0, x_norm = 0.0;
   for (int i = 0; i < n; ++i) x_norm += cur[i] * cur[i];
   x_norm = std::sqrt(x_norm);
   int iter = 0, consecutive_invalid = 0;
@@ -3479,11 +3481,12 @@ extern "C" int wc_window_solve(wc_ctx *ctx, double *h_x_inout, wc_solve_summary 
         WC_TRY(wait_mail(ctx, ticket));
         return WC_OK;
       };
-      // Above a radius of 1e10 - a dozen very successful steps in a row - the damping has all but left the bias block T, whose own
-      // conditioning (random-walk factors tying neighbouring biases, weak absolute information) then shows: the cyclic reduction's explicit
-      // 12 x 12 inverses lose digits a direct factorisation keeps.  Seen in profiles/stress_facade.py on sparse streams (a sweep of 38
-      // iterations for the oracle's 35, states 2.5e-4 apart; with the dense step from 1e10 on: 35 iterations, 1e-5).  Such iterations
-      // take round 2's dense step (development option lm_dense_radius: the exponent, 0 = never).
+      // As the radius grows the damping leaves the bias block T, whose own conditioning (random-walk factors tying neighbouring biases,
+      // weak absolute information) then shows: cond(T) grows with the radius, and the cyclic reduction's explicit 12 x 12 inverses lose
+      // digits a direct factorisation keeps - its normwise backward error in the bias rows is about cond(T) eps.  Measured on the step
+      // itself (tests/test_lm_step_gpu.py): at most 2e-10 up to a radius of 1e7, 1.4e-9 at 1e8, 1.2e-8 at 1e9 (the dense step: 1e-15).
+      // First seen in profiles/stress_facade.py on sparse streams (a sweep of 38 iterations for the oracle's 35, states 2.5e-4 apart).
+      // Iterations above 1e7 take round 2's dense step (development option lm_dense_radius: the exponent, 0 = never).
       const bool schur_now = use_schur && !(ctx->dev.lm_dense_radius > 0 && radius > std::pow(10.0, (double)ctx->dev.lm_dense_radius));
       WC_TRY(attempt(schur_now));
       if (two_late) {  // max |g| at the point this iteration started from has arrived with the iteration's ticket (its kernels ran behind that expand)
