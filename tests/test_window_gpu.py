@@ -4,6 +4,7 @@ Tolerance (north_star): pose increments within 1e-6 relative; H, g, cost far tig
 import numpy as np
 import pytest
 
+import linearize_ref as lr
 from wildcat_slam_amd import records as R
 from wildcat_slam_amd import synth
 
@@ -66,6 +67,7 @@ def _setup(gpu, oracle, n_scans=3, patches=300, fixed=120, quirks=1, fix_first=T
     gpu.window_build(d_surf, d_pose, d_pairs, len(pairs), w["imu"] if with_imu else None, w["sample_times"], w["grav"], fix_first,
                      d_fs, d_fp, d_pf, len(pf))
     keep = (d_surf, d_pose, d_pairs, d_fs, d_fp, d_pf)
+    W.spec = lr.spec(w, params, pairs, pf, fix_first, w["imu"] if with_imu else None)  # the problem as data (tests/linearize_ref.py)
     return w, W, keep
 
 
@@ -444,8 +446,10 @@ def test_c3_window_full_size(gpu, oracle):
     Wref.add_unary(w["fix_surf"], w["fix_pose"], w["surf"], w["pose"], pf)
     Wref.add_imu(w["imu"])
     x1 = 2e-3 * np.random.default_rng(23).normal(size=12 * ns)
+    scaled = []
     for xv, (Hg, gg, cg) in ((x0, (H, g, c0)), (x1, gpu.window_linearize(x1))):
         Hr, gr, cr = Wref.linearize(xv)
+        scaled.append(dict(x=xv, H=Hg, g=gg, cost=cg, oracle=(Hr, gr, cr)))
         assert abs(cg - cr) <= 1e-10 * cr
         assert np.abs(Hg - Hr).max() <= 1e-9 * np.abs(Hr).max() and np.abs(gg - gr).max() <= 1e-9 * np.abs(gr).max()
         Hb = np.abs(Hg - Hr).reshape(ns, 12, ns, 12).max(axis=(1, 3))
@@ -455,6 +459,9 @@ def test_c3_window_full_size(gpu, oracle):
     cr1, res_ref = Wref.evaluate(x1, want_residuals=True)
     c1, res1 = gpu.window_evaluate(x1, want_residuals=True)
     assert abs(c1 - cr1) <= 1e-10 * cr1 and np.abs(res1 - res_ref).max() <= 1e-9 * np.abs(res_ref).max()
+    # ... and entry by entry in each entry's own scale, against short sums (tests/linearize_ref.py; bars from the oracle's own floor)
+    scaled[1].update(eval_cost=c1, res=res1)
+    lr.check_linearization(oracle, lr.spec(w, oracle.default_params(), pairs, pf, True, w["imu"]), scaled, "C3", W=Wref)
 
 
 def test_c4_window_full_size_properties(gpu, oracle):
@@ -507,8 +514,10 @@ def test_c4_window_full_size_properties(gpu, oracle):
     Wref.add_imu(w["imu"])
     assert Wref.num_residuals() == n_b + n_u + 12 * ni_
     x1 = 2e-3 * np.random.default_rng(17).normal(size=12 * ns)
+    scaled = []
     for xv, (Hg, gg, cg) in ((x0, (H, g, c0)), (x1, gpu.window_linearize(x1))):
         Hr, gr, cr = Wref.linearize(xv)
+        scaled.append(dict(x=xv, H=Hg, g=gg, cost=cg, oracle=(Hr, gr, cr)))
         assert abs(cg - cr) <= 1e-10 * cr
         assert np.abs(Hg - Hr).max() <= 1e-9 * np.abs(Hr).max() and np.abs(gg - gr).max() <= 1e-9 * np.abs(gr).max()
         # block by block: every 12 x 12 block pair relative to ITS OWN size (small far-apart blocks are not hidden by the diagonal)
@@ -519,6 +528,10 @@ def test_c4_window_full_size_properties(gpu, oracle):
     cr1, res_ref = Wref.evaluate(x1, want_residuals=True)
     c1, res1 = gpu.window_evaluate(x1, want_residuals=True)
     assert abs(c1 - cr1) <= 1e-10 * cr1 and np.abs(res1 - res_ref).max() <= 1e-9 * np.abs(res_ref).max()
+    # ... and entry by entry in each entry's own scale, against short sums (tests/linearize_ref.py: 512 chunks of 3.9 k factors)
+    scaled[0].update(eval_cost=cost, res=res)
+    scaled[1].update(eval_cost=c1, res=res1)
+    lr.check_linearization(oracle, lr.spec(w, oracle.default_params(), pairs, pf, False, w["imu"]), scaled, "C4", W=Wref)
     x, s, _ = gpu.window_solve(x0)
     assert s.iterations >= 1 and s.successful_steps >= 1 and s.final_cost < s.initial_cost
     assert abs(s.initial_cost - c0) <= 1e-9 * c0
@@ -537,9 +550,11 @@ def test_large_windows_linearize_match_oracle(gpu, oracle, ns):
     w, W, keep = _setup(gpu, oracle, n_scans=n_scans, patches=patches, fixed=patches // 3, sample_dt=dt)
     assert W.ns == ns
     x1 = 2e-3 * np.random.default_rng(ns).normal(size=12 * ns)
+    scaled = []
     for xv in (np.zeros(12 * ns), x1):
         Hg, gg, cg = gpu.window_linearize(xv)
         Hr, gr, cr = W.linearize(xv)
+        scaled.append(dict(x=xv, H=Hg, g=gg, cost=cg, oracle=(Hr, gr, cr)))
         assert abs(cg - cr) <= 1e-10 * cr
         assert np.abs(Hg - Hr).max() <= 1e-9 * np.abs(Hr).max() and np.abs(gg - gr).max() <= 1e-9 * np.abs(gr).max()
         Hb = np.abs(Hg - Hr).reshape(ns, 12, ns, 12).max(axis=(1, 3))
@@ -547,6 +562,10 @@ def test_large_windows_linearize_match_oracle(gpu, oracle, ns):
         assert np.all(Hb <= 1e-8 * np.maximum(Hs, 1e-300) + 1e-12 * np.abs(Hr).max())
         assert np.array_equal(Hs == 0, np.abs(Hg).reshape(ns, 12, ns, 12).max(axis=(1, 3)) == 0)  # same block sparsity
         assert np.array_equal(Hg, Hg.T)
+    # ... and entry by entry in each entry's own scale, against short sums (tests/linearize_ref.py; bars from the oracle's own floor)
+    for r in scaled:
+        r["eval_cost"], r["res"] = gpu.window_evaluate(r["x"], want_residuals=True)
+    lr.check_linearization(oracle, W.spec, scaled, "large ns=%d" % ns, W=W)
 
 
 def test_largest_window_solve(gpu, oracle):
