@@ -87,6 +87,15 @@ typedef struct wc_route_point {
   double t;
 } wc_route_point;
 
+/* Answer of wc_map_nearest for one query (not a reference type).  40 bytes, 8-aligned. */
+typedef struct wc_map_hit {
+  float xyz[3];   /* centroid of the voxel found: the very float triple wc_map_export returns for it          */
+  uint32_t count; /* its point count; 0 = nothing found (then xyz = key = 0, d2 = +inf)                       */
+  int32_t key[3]; /* its voxel index                                                                          */
+  uint32_t flags; /* bit 0: the query could not be searched (non-finite coordinate or its own voxel index out of range) */
+  double d2;      /* squared distance query -> centroid                                                      */
+} wc_map_hit;
+
 /* Communicator of a multi-GPU job: one process (and one wc_ctx) per GPU.  The library calls these for its few collectives;
  * wc_comm_rccl_init() installs an in-library RCCL implementation, tests / other runtimes install callbacks.
  * All buffers are DEVICE pointers on the ctx's GPU; a callback returns 0 on success and must have completed (or be

@@ -355,6 +355,30 @@ int wc_map_info(wc_ctx *ctx, wc_map *m, uint64_t h_info[4]);
 int wc_map_export(wc_ctx *ctx, wc_map *m, float *d_xyz, uint32_t *d_count, int32_t *d_keys, uint64_t cap, uint64_t *h_n);
 /* empties the map (the table keeps its size) */
 int wc_map_clear(wc_ctx *ctx, wc_map *m);
+/* Nearest-voxel query.  For every query point q (DEVICE pointers, the wc_points rules of wc_map_insert; pts->time is ignored) d_hits
+ * receives one wc_map_hit:
+ *   voxel of the query  kq = floor((double)q / v) per axis (VoxelLoc).  A non-finite coordinate or |kq| >= 2^20 on any axis cannot be
+ *                       searched: flags = 1, count = 0, d2 = +inf
+ *   candidates          the occupied voxels with index kq + {-1, 0, 1}^3 (neighbour indices outside the key range are skipped)
+ *   distance            to a candidate's centroid c, the float triple wc_map_export returns for it:
+ *                       d2 = (dx*dx + dy*dy) + dz*dz in fp64 with dx = (double)q.x - (double)c.x, no fused multiply-add
+ *   result              the candidate of smallest d2, ties to the smaller (kx, ky, kz) lexicographically; accepted iff
+ *                       d2 <= max_dist * max_dist (the product formed once on the host in fp64), otherwise a miss (count = 0)
+ * so a restatement on the exported map reproduces every hit bit for bit.  max_dist must be > 0 (NaN or <= 0: WC_ERR_ARG); +inf means
+ * "the nearest of the 27 voxels, whatever its distance".  Consequence: a centroid within max_dist <= v of q lies in one of the 27
+ * voxels, so for max_dist <= v the result is the globally nearest centroid within max_dist - the only exception is a centroid that
+ * the rounding to float carried across a face of its own voxel.
+ * h_n_found (may be NULL) receives the number of accepted hits; asking for it waits for the stream, passing NULL returns without
+ * waiting.  queries->n == 0 is WC_OK; NULL d_hits with n > 0 or a map of another context is WC_ERR_ARG.  The map is not modified. */
+int wc_map_nearest(wc_ctx *ctx, wc_map *m, const wc_points *queries, double max_dist, wc_map_hit *d_hits, uint64_t *h_n_found);
+/* Crop and compact.  A voxel k is kept iff floor(lo[a] / v) <= k[a] <= floor(hi[a] / v) on all three axes (the voxels that intersect
+ * the box); +-inf bounds are allowed and clamped to the key range, NaN or lo[a] > hi[a] is WC_ERR_ARG.  The kept voxels keep their
+ * integer sums and counts: the result is, bit for bit, the map of exactly those inserted points whose voxel is kept.  They are
+ * rehashed into a fresh table of the smallest power of two >= 2 * max(kept, 1) slots (an all-infinite box: "shrink to fit"), and
+ * the old table's memory is released.  The voxel and point counts (wc_map_size) become those of the kept voxels; the rejected and
+ * growth counts stay.  *h_removed_voxels (may be NULL) receives the number of voxels dropped.  Waits for the ctx stream either way:
+ * the new table is sized from the kept count. */
+int wc_map_crop(wc_ctx *ctx, wc_map *m, const double lo[3], const double hi[3], uint64_t *h_removed_voxels);
 
 #ifdef __cplusplus
 }

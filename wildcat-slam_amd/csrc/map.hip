@@ -15,6 +15,9 @@
 //   k_map_rehash    growth: every occupied slot of the old table into the new one (distinct keys: plain stores of the payload)
 //   k_map_compact   export: occupied slots -> (key, slot) pairs (LDS staging, one atomic per workgroup); rocPRIM radix sort by key
 //   k_map_centroids export: centroid = r + sum / (count * 2^32) in fp64, rounded once to float; count; key (optional)
+//   k_map_nearest   query: one lane per query; the first-slot key loads of the 27 voxels around the query's own are issued nine at a
+//                   time before any is examined, payload loads and divisions only for the occupied ones; read-only probes, no CAS
+//   k_map_crop_count / k_map_rehash<true>  crop: kept voxels and points counted per workgroup, then only the kept keys rehashed
 // Growth policy: before an insert of n points the host takes an upper bound B of the occupied slots (the exact count of the last
 // completed insert's read-back plus every point inserted after it); when 2 (B + n) > cap the table is rehashed into the smallest power
 // of two >= 2 (B + n) slots.  The table is therefore at most half full at every probe, and an insert never runs out of room.
@@ -55,7 +58,9 @@ constexpr unsigned long long kMapEmpty = ~0ull;
 constexpr double kMapUnit = 4294967296.0;          // fixed-point unit: 2^-32 m
 constexpr double kMapKeyLim = 1048576.0;           // |k| < 2^20
 constexpr int kMapKeyOff = 1 << 20;
-constexpr int kCtrOcc = 0, kCtrPts = 16, kCtrRej = 32, kCtrRejCall = 48, kCtrLost = 56, kCtrWords = 64;  // u64 word of each counter
+constexpr int kCtrOcc = 0, kCtrPts = 16, kCtrRej = 32, kCtrRejCall = 48, kCtrLost = 56;  // u64 word of each counter
+constexpr int kCtrFound = 64, kCtrKeepVox = 80, kCtrKeepPts = 96, kCtrWords = 112;      // query hits; a crop's kept voxels, points
+constexpr int kNearThreads = 256;
 constexpr int kCompactChunk = 2048;                // slots per workgroup of k_map_compact
 
 __device__ __forceinline__ unsigned long long map_hash(unsigned long long k) {  // splitmix64 finaliser
@@ -70,6 +75,21 @@ __device__ __forceinline__ unsigned long long map_hash(unsigned long long k) {  
 __device__ __forceinline__ double map_ref(int k, double v) { return rint(((double)k + 0.5) * v * 1024.0) * (1.0 / 1024.0); }
 __device__ __forceinline__ int map_unpack(unsigned long long key, int axis) {
   return (int)((key >> (42 - 21 * axis)) & 0x1FFFFFull) - kMapKeyOff;
+}
+__device__ __forceinline__ unsigned long long map_pack(int kx, int ky, int kz) {
+  return ((unsigned long long)(kx + kMapKeyOff) << 42) | ((unsigned long long)(ky + kMapKeyOff) << 21) | (unsigned long long)(kz + kMapKeyOff);
+}
+// one coordinate of a voxel's centroid from its exact integer sum s and its count c: the export and the query share this expression,
+// so a hit's xyz is byte-equal to the exported centroid
+__device__ __forceinline__ float map_centroid(int k, double v, long long s, double c) {
+  return (float)(map_ref(k, v) + (double)s / (c * kMapUnit));
+}
+// the sum of a 64-lane wavefront in lane 0
+template <class T>
+__device__ __forceinline__ T wave_sum(T x) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) x += __shfl_down(x, o);
+  return x;
 }
 
 // one global probe: the slot of `key`, claimed if it is new (fresh += 1).  The table is at most half full, so the loop ends; the bound
@@ -142,8 +162,7 @@ __global__ void __launch_bounds__(kMapThreads) k_map_insert(wc_points pts, doubl
       }
       ++n_ok;
       const int kx = (int)fx, ky = (int)fy, kz = (int)fz;
-      const unsigned long long key = ((unsigned long long)(kx + kMapKeyOff) << 42) | ((unsigned long long)(ky + kMapKeyOff) << 21) |
-                                     (unsigned long long)(kz + kMapKeyOff);
+      const unsigned long long key = map_pack(kx, ky, kz);
       const long long qx = llrint((x - map_ref(kx, v)) * kMapUnit), qy = llrint((y - map_ref(ky, v)) * kMapUnit),
                       qz = llrint((z - map_ref(kz, v)) * kMapUnit);
       if (key != run_key) {
@@ -187,13 +206,30 @@ __global__ void __launch_bounds__(kMapThreads) k_map_insert(wc_points pts, doubl
   }
 }
 
-// growth: the old table's occupied slots into the new one (empty keys, zero payload); keys are distinct, so the payload is stored plainly
+// an inclusive range of voxel indices per axis (wc_map_crop)
+struct map_box {
+  int lo[3], hi[3];
+};
+__device__ __forceinline__ bool map_in_box(unsigned long long key, const map_box &b) {
+  bool in = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const int k = map_unpack(key, a);
+    in = in && k >= b.lo[a] && k <= b.hi[a];
+  }
+  return in;
+}
+
+// growth: the old table's occupied slots into the new one (empty keys, zero payload); keys are distinct, so the payload is stored plainly.
+// CROP: only the keys inside `box` move (the growth path compiles without the test)
+template <bool CROP>
 __global__ void __launch_bounds__(256) k_map_rehash(const unsigned long long *okeys, const long long *opay, uint64_t ocap,
-                                                    unsigned long long *keys, long long *pay, unsigned long long mask) {
+                                                    unsigned long long *keys, long long *pay, unsigned long long mask, map_box box) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ocap) return;
   const unsigned long long key = okeys[i];
   if (key == kMapEmpty) return;
+  if (CROP && !map_in_box(key, box)) return;
   unsigned fresh = 0;
   const unsigned long long h = map_slot(keys, mask, key, fresh);
   if (h == kMapEmpty) return;  // (cannot happen: the new table has room for every old key)
@@ -243,10 +279,108 @@ __global__ void __launch_bounds__(256) k_map_centroids(const unsigned long long 
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     const int k = map_unpack(key, a);
-    xyz[3 * i + a] = (float)(map_ref(k, v) + (double)p[a] / (c * kMapUnit));
+    xyz[3 * i + a] = map_centroid(k, v, p[a], c);
     if (keys_out) keys_out[3 * i + a] = k;
   }
   count[i] = (uint32_t)p[3];
+}
+
+// query: the nearest of the occupied voxels with index kq + {-1, 0, 1}^3 (kq = the query's own voxel), by the fp64 distance to the float
+// centroid wc_map_export returns.  One lane per query.  The 27 neighbours are visited in ascending key order (x outermost) and a later
+// one wins only on a strictly smaller distance: ties go to the smaller key.  Each x plane's nine first-slot key loads are issued together
+// before any is looked at; a lane then follows the probe chain (read-only) of whatever is not settled by its first slot, and loads the
+// 32-byte payload of the occupied ones only.  Every loop below is fully unrolled: all indices are compile-time constants, no scratch.
+__global__ void __launch_bounds__(kNearThreads) k_map_nearest(wc_points q, double v, double max_d2, const unsigned long long *keys,
+                                                              const long long *pay, unsigned long long mask, wc_map_hit *hits,
+                                                              unsigned long long *found) {
+  __shared__ unsigned s_found[kNearThreads / 64];
+  unsigned n_found = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * kNearThreads;
+  for (uint64_t i = (uint64_t)blockIdx.x * kNearThreads + threadIdx.x; i < q.n; i += stride) {
+    const float *f = (const float *)((const char *)q.xyz + i * q.xyz_stride);
+    const double x = (double)f[0], y = (double)f[1], z = (double)f[2];
+    const double fx = floor(x / v), fy = floor(y / v), fz = floor(z / v);  // VoxelLoc, as k_map_insert
+    const bool ok = fx > -kMapKeyLim && fx < kMapKeyLim && fy > -kMapKeyLim && fy < kMapKeyLim && fz > -kMapKeyLim && fz < kMapKeyLim;
+    const int kx = ok ? (int)fx : 0, ky = ok ? (int)fy : 0, kz = ok ? (int)fz : 0;
+    double best = __builtin_inf();
+    float bx = 0.f, by = 0.f, bz = 0.f;
+    unsigned bc = 0;
+    int bkx = 0, bky = 0, bkz = 0;
+#pragma unroll
+    for (int dx = -1; dx <= 1; ++dx) {
+      unsigned long long key[9], h[9], cur[9];
+#pragma unroll
+      for (int j = 0; j < 9; ++j) {
+        const int nx = kx + dx, ny = ky + (j / 3 - 1), nz = kz + (j % 3 - 1);
+        // (a neighbour beyond the key range holds nothing: its "key" is the empty mark, which the first slot read then settles)
+        const bool in = ok && nx > -kMapKeyOff && nx < kMapKeyOff && ny > -kMapKeyOff && ny < kMapKeyOff && nz > -kMapKeyOff && nz < kMapKeyOff;
+        key[j] = in ? map_pack(nx, ny, nz) : kMapEmpty;
+        h[j] = in ? map_hash(key[j]) & mask : 0;
+        cur[j] = keys[h[j]];
+      }
+#pragma unroll
+      for (int j = 0; j < 9; ++j) {
+        if (key[j] == kMapEmpty) continue;
+        unsigned long long hj = h[j], c = cur[j];
+        for (unsigned long long probe = 0; c != key[j] && c != kMapEmpty && probe < mask; ++probe) {  // linear probing past foreign keys
+          hj = (hj + 1) & mask;
+          c = keys[hj];
+        }
+        if (c != key[j]) continue;
+        const longlong2 *p = (const longlong2 *)(pay + 4 * hj);
+        const longlong2 p0 = p[0], p1 = p[1];
+        const double cnt = (double)p1.y;
+        const int nx = kx + dx, ny = ky + (j / 3 - 1), nz = kz + (j % 3 - 1);
+        const float cx = map_centroid(nx, v, p0.x, cnt), cy = map_centroid(ny, v, p0.y, cnt), cz = map_centroid(nz, v, p1.x, cnt);
+        const double ex = x - (double)cx, ey = y - (double)cy, ez = z - (double)cz;
+        const double d2 = (ex * ex + ey * ey) + ez * ez;
+        if (d2 < best) best = d2, bx = cx, by = cy, bz = cz, bc = (unsigned)p1.y, bkx = nx, bky = ny, bkz = nz;
+      }
+    }
+    const bool hit = bc != 0 && best <= max_d2;
+    n_found += hit ? 1u : 0u;
+    // the 40-byte record as five 8-byte stores (the record is 8-aligned)
+    uint2 *o = (uint2 *)(hits + i);
+    o[0] = hit ? make_uint2(__float_as_uint(bx), __float_as_uint(by)) : make_uint2(0u, 0u);
+    o[1] = hit ? make_uint2(__float_as_uint(bz), bc) : make_uint2(0u, 0u);
+    o[2] = hit ? make_uint2((unsigned)bkx, (unsigned)bky) : make_uint2(0u, 0u);
+    o[3] = make_uint2(hit ? (unsigned)bkz : 0u, ok ? 0u : 1u);
+    ((double *)o)[4] = hit ? best : __builtin_inf();
+  }
+  // the found count: per wavefront, per workgroup, then one atomic on the counter's own line
+  n_found = wave_sum(n_found);
+  if ((threadIdx.x & 63) == 0) s_found[threadIdx.x >> 6] = n_found;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned t = 0;
+#pragma unroll
+    for (int w = 0; w < kNearThreads / 64; ++w) t += s_found[w];
+    if (t) atomicAdd(found, (unsigned long long)t);
+  }
+}
+
+// crop, step 1: the voxels inside the box and their points, reduced per workgroup
+__global__ void __launch_bounds__(256) k_map_crop_count(const unsigned long long *keys, const long long *pay, uint64_t cap, map_box box,
+                                                        unsigned long long *ctr) {
+  __shared__ unsigned long long s_v[4], s_p[4];
+  unsigned long long nv = 0, np = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < cap; i += stride) {
+    const unsigned long long key = keys[i];
+    if (key == kMapEmpty || !map_in_box(key, box)) continue;
+    ++nv;
+    np += (unsigned long long)pay[4 * i + 3];
+  }
+  nv = wave_sum(nv), np = wave_sum(np);
+  if ((threadIdx.x & 63) == 0) s_v[threadIdx.x >> 6] = nv, s_p[threadIdx.x >> 6] = np;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    nv = s_v[0] + s_v[1] + s_v[2] + s_v[3], np = s_p[0] + s_p[1] + s_p[2] + s_p[3];
+    if (nv) {
+      atomicAdd(ctr + kCtrKeepVox, nv);
+      atomicAdd(ctr + kCtrKeepPts, np);
+    }
+  }
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
@@ -363,7 +497,7 @@ extern "C" int wc_map_insert(wc_ctx *ctx, wc_map *m, const wc_points *pts, uint6
     unsigned long long *keys = nullptr;
     long long *pay = nullptr;
     WC_TRY(map_table(ctx, cap, &keys, &pay));
-    k_map_rehash<<<(unsigned)((m->cap + 255) / 256), 256, 0, ctx->stream>>>(m->keys, m->pay, m->cap, keys, pay, cap - 1);
+    k_map_rehash<false><<<(unsigned)((m->cap + 255) / 256), 256, 0, ctx->stream>>>(m->keys, m->pay, m->cap, keys, pay, cap - 1, map_box{});
     WC_HIP(ctx, hipGetLastError());
     map_free(ctx, m->keys);
     map_free(ctx, m->pay);
@@ -455,5 +589,65 @@ extern "C" int wc_map_clear(wc_ctx *ctx, wc_map *m) {
   m->occ_known = m->pts_since = m->pts_after_copy = 0;
   m->ctr_pending = false;
   std::memset(m->h_ctr, 0, kCtrWords * 8);
+  return WC_OK;
+}
+
+extern "C" int wc_map_nearest(wc_ctx *ctx, wc_map *m, const wc_points *queries, double max_dist, wc_map_hit *d_hits, uint64_t *h_n_found) {
+  wc_dev_guard dg_(ctx);
+  const wc_points *q = queries;
+  if (!map_ok(ctx, m) || !q || !(max_dist > 0.0) ||
+      (q->n && (!d_hits || (uintptr_t)d_hits % 8 || !q->xyz || q->xyz_stride < 12 || q->xyz_stride % 4 || (uintptr_t)q->xyz % 4)))
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (max_dist > 0)", __func__);
+  if (h_n_found) *h_n_found = 0;
+  if (q->n == 0) return WC_OK;
+  const double max_d2 = max_dist * max_dist;  // (formed once, here: the kernel accepts d2 <= max_d2)
+  if (h_n_found) WC_HIP(ctx, hipMemsetAsync(m->ctr + kCtrFound, 0, 8, ctx->stream));
+  const uint64_t blocks = (q->n + kNearThreads - 1) / kNearThreads;
+  const unsigned grid = (unsigned)std::min<uint64_t>(blocks, (uint64_t)8 * m->cus);
+  k_map_nearest<<<grid, kNearThreads, 0, ctx->stream>>>(*q, m->voxel, max_d2, m->keys, m->pay, m->cap - 1, d_hits, m->ctr + kCtrFound);
+  WC_HIP(ctx, hipGetLastError());
+  if (h_n_found) {
+    WC_HIP(ctx, hipMemcpyAsync(m->h_ctr + kCtrFound, m->ctr + kCtrFound, 8, hipMemcpyDeviceToHost, ctx->stream));
+    WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *h_n_found = m->h_ctr[kCtrFound];
+  }
+  return WC_OK;
+}
+
+extern "C" int wc_map_crop(wc_ctx *ctx, wc_map *m, const double lo[3], const double hi[3], uint64_t *h_removed_voxels) {
+  wc_dev_guard dg_(ctx);
+  if (!map_ok(ctx, m) || !lo || !hi) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
+  map_box box;
+  for (int a = 0; a < 3; ++a) {
+    if (!(lo[a] <= hi[a])) return wc_fail(ctx, WC_ERR_ARG, "%s: NaN bound or lo > hi on axis %d", __func__, a);
+    // kept: floor(lo / v) <= k <= floor(hi / v), clamped to the key range |k| < 2^20 (+-inf included)
+    box.lo[a] = (int)std::min(std::max(std::floor(lo[a] / m->voxel), -(kMapKeyLim - 1.0)), kMapKeyLim);
+    box.hi[a] = (int)std::min(std::max(std::floor(hi[a] / m->voxel), -kMapKeyLim), kMapKeyLim - 1.0);
+  }
+  WC_HIP(ctx, hipMemsetAsync(m->ctr + kCtrKeepVox, 0, (kCtrKeepPts - kCtrKeepVox + 1) * 8, ctx->stream));
+  const unsigned grid = (unsigned)std::min<uint64_t>((m->cap + 255) / 256, (uint64_t)8 * m->cus);
+  k_map_crop_count<<<grid, 256, 0, ctx->stream>>>(m->keys, m->pay, m->cap, box, m->ctr);
+  WC_HIP(ctx, hipGetLastError());
+  WC_TRY(map_sync_counters(ctx, m));  // (the wait: the new table is sized from the kept count; a pending counter copy has landed too)
+  const uint64_t occ = m->h_ctr[kCtrOcc], kept = m->h_ctr[kCtrKeepVox], kept_pts = m->h_ctr[kCtrKeepPts];
+  if (h_removed_voxels) *h_removed_voxels = occ - kept;
+  const uint64_t cap = pow2_at_least(2 * std::max<uint64_t>(kept, 1));
+  if (kept != occ || cap != m->cap) {  // (otherwise the table already is what the crop would build)
+    unsigned long long *keys = nullptr;
+    long long *pay = nullptr;
+    WC_TRY(map_table(ctx, cap, &keys, &pay));
+    k_map_rehash<true><<<(unsigned)((m->cap + 255) / 256), 256, 0, ctx->stream>>>(m->keys, m->pay, m->cap, keys, pay, cap - 1, box);
+    WC_HIP(ctx, hipGetLastError());
+    map_free(ctx, m->keys);
+    map_free(ctx, m->pay);
+    m->keys = keys, m->pay = pay, m->cap = cap;
+    // the occupied-voxel and point counters become those of the kept voxels; rejected and growth counters stay
+    WC_HIP(ctx, hipMemcpyAsync(m->ctr + kCtrOcc, m->ctr + kCtrKeepVox, 8, hipMemcpyDeviceToDevice, ctx->stream));
+    WC_HIP(ctx, hipMemcpyAsync(m->ctr + kCtrPts, m->ctr + kCtrKeepPts, 8, hipMemcpyDeviceToDevice, ctx->stream));
+    m->h_ctr[kCtrOcc] = kept, m->h_ctr[kCtrPts] = kept_pts;
+  }
+  // the growth policy starts again from the exact count (map_sync_counters has cleared the pending copy)
+  m->occ_known = kept;
+  m->pts_since = m->pts_after_copy = 0;
   return WC_OK;
 }

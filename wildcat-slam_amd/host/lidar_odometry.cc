@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
+#include <limits>
 
 #include "../csrc/dmath.h"
 #include "cubic_bspline.h"
@@ -469,6 +470,37 @@ size_t LidarOdometry::ExportMap(float *xyz, uint32_t *counts, size_t cap) {
 void LidarOdometry::ClearMap() {
   if (map_) WC_CALL(wc_map_clear(ctx_, map_));
 }
+size_t LidarOdometry::QueryMap(const float *xyz, size_t n, double max_dist, wc_map_hit *hits) {
+  if (!n || !xyz || !hits) return 0;
+  if (!map_) {
+    for (size_t i = 0; i < n; ++i) {
+      std::memset(&hits[i], 0, sizeof(wc_map_hit));
+      hits[i].d2 = std::numeric_limits<double>::infinity();
+    }
+    return 0;
+  }
+  void *d_xyz = nullptr, *d_hits = nullptr;
+  WC_CALL(wc_dev_alloc(ctx_, n * 3 * sizeof(float), &d_xyz));
+  WC_CALL(wc_dev_alloc(ctx_, n * sizeof(wc_map_hit), &d_hits));
+  WC_CALL(wc_h2d(ctx_, d_xyz, xyz, n * 3 * sizeof(float)));
+  const wc_points desc{d_xyz, nullptr, 12, 0, n};
+  uint64_t found = 0;
+  WC_CALL(wc_map_nearest(ctx_, map_, &desc, max_dist, (wc_map_hit *)d_hits, &found));
+  WC_CALL(wc_d2h(ctx_, hits, d_hits, n * sizeof(wc_map_hit)));
+  WC_CALL(wc_dev_free(ctx_, d_xyz));
+  WC_CALL(wc_dev_free(ctx_, d_hits));
+  return found;
+}
+size_t LidarOdometry::CropMap(const double lo[3], const double hi[3]) {
+  uint64_t removed = 0;
+  if (map_) WC_CALL(wc_map_crop(ctx_, map_, lo, hi, &removed));
+  return removed;
+}
+bool LidarOdometry::SetMapKeepRadius(double radius) {
+  if (!(radius >= 0.0)) return false;
+  config_.map_keep_radius = radius;
+  return true;
+}
 
 void LidarOdometry::UploadImuStates() {
   const size_t n_imu = imu_states_.size();
@@ -713,6 +745,11 @@ void LidarOdometry::AddLidarScan(const pcl::PointCloud<hilti_ros::Point>::Ptr &m
     if (!d_world) d_world = UndistortFinal(d_raw_sweep, n_sweep);
     const wc_points desc{d_world, (const char *)d_world + WC_HILTI_POINT_TIME_OFFSET, WC_HILTI_POINT_BYTES, WC_HILTI_POINT_BYTES, n_sweep};
     WC_CALL(wc_map_insert(ctx_, map_, &desc, nullptr));
+    if (config_.map_keep_radius > 0.0) {  // the cube around this sweep's world -> imu_link origin (the tf of FillOutputs)
+      const double *c = samples_.back().pos, r = config_.map_keep_radius;
+      const double lo[3] = {c[0] - r, c[1] - r, c[2] - r}, hi[3] = {c[0] + r, c[1] + r, c[2] + r};
+      WC_CALL(wc_map_crop(ctx_, map_, lo, hi, nullptr));
+    }
     t_prev = std::chrono::steady_clock::now();
     last_map_ms_ = std::chrono::duration<double, std::milli>(t_prev - t_map).count();
   }

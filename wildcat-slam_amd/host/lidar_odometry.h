@@ -87,8 +87,14 @@ class LidarOdometry {
   // centroids (n x 3 floats) and point counts in ascending voxel-index order; returns n, writes nothing when cap < n
   size_t ExportMap(float *xyz, uint32_t *counts, size_t cap);
   void ClearMap();
+  // nearest map voxel of n host points (xyz: n x 3 floats) within max_dist (> 0, may be +inf): hits[n] as wc_map_nearest defines them;
+  // returns the number found.  Without a map: 0, every hit a miss
+  size_t QueryMap(const float *xyz, size_t n, double max_dist, wc_map_hit *hits);
+  // drops the voxels that do not intersect the box [lo, hi] and compacts the table (wc_map_crop); returns the voxels removed
+  size_t CropMap(const double lo[3], const double hi[3]);
+  bool SetMapKeepRadius(double radius);  // config().map_keep_radius = radius; false: negative or NaN
   // wall time [ms] of the last completed sweep's map step (the undistortion when fill_outputs does not already form it, the insert's
-  // enqueue; its kernel runs behind on the stream).  Not part of last_stage_ms()
+  // enqueue - its kernel runs behind on the stream - and, with map_keep_radius, the crop, which waits).  Not part of last_stage_ms()
   double last_map_ms() const { return last_map_ms_; }
   LioConfig &config() { return config_; }
   void ApplyConfig();  // push config() changes (quirks, extraction arithmetic, iteration cap, extrinsics) into the device context

@@ -44,4 +44,8 @@ struct LioConfig {
   // the device-resident map every sweep is inserted into after its solve (DownSamplingVoxel, surfel_extraction.cc:228-261, over all
   // sweeps; include/wildcat_hip.h: wc_map_*).  0 (default) = no map: nothing allocated or launched.  Otherwise 0.01 <= v <= 4.0
   double map_voxel_size = 0.0;
+  // not in the reference: half-side [m] of the axis-aligned cube, centred on the sweep's world -> imu_link origin (the tf of
+  // last_outputs()), that the map is cropped to after every sweep's insert (wc_map_crop: the voxels outside are dropped and the table
+  // is compacted).  0 (default) = the map is unbounded and nothing extra is launched.  Needs map_voxel_size > 0
+  double map_keep_radius = 0.0;
 };

@@ -203,6 +203,14 @@ void wc_odom_map_size(void *h, uint64_t out3[3]) {
 uint64_t wc_odom_map_export(void *h, float *xyz, uint32_t *counts, uint64_t cap) { return ((LidarOdometry *)h)->ExportMap(xyz, counts, cap); }
 void wc_odom_map_clear(void *h) { ((LidarOdometry *)h)->ClearMap(); }
 double wc_odom_map_ms(void *h) { return ((const LidarOdometry *)h)->last_map_ms(); }
+// nearest map voxel of n host points (n x 3 floats) within max_dist -> hits[n] (wc_map_hit); returns the number found
+uint64_t wc_odom_map_query(void *h, const float *xyz, uint64_t n, double max_dist, wc_map_hit *hits) {
+  return ((LidarOdometry *)h)->QueryMap(xyz, n, max_dist, hits);
+}
+// keeps the voxels that intersect the box [lo, hi]; returns the voxels removed
+uint64_t wc_odom_map_crop(void *h, const double lo[3], const double hi[3]) { return ((LidarOdometry *)h)->CropMap(lo, hi); }
+// LioConfig::map_keep_radius: 0 = unbounded map; returns 0, or WC_ERR_ARG for a negative or NaN radius
+int wc_odom_set_map_keep_radius(void *h, double radius) { return ((LidarOdometry *)h)->SetMapKeepRadius(radius) ? 0 : WC_ERR_ARG; }
 // Cloud2FromXyz (host/wire_formats.h): the field table (3 x {offset, datatype, count}), point_step and the payload of n points
 int wc_host_xyz_to_cloud2(const float *xyz, uint64_t n, uint32_t table9[9], char *names_out, uint64_t cap, uint8_t *data_out) {
   wc_wire::PointCloud2 msg;

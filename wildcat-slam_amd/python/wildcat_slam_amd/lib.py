@@ -573,8 +573,8 @@ class PointMap:
         self.ctx._ck(self.lib.wc_map_insert(self.ctx.h, self.h, C.byref(desc), C.byref(rej)))
         return int(rej.value)
 
-    def insert(self, points):
-        """POINT records or an (n, 3) float32 array (uploaded for the call) -> points not inserted"""
+    def _upload(self, points):
+        """POINT records or an (n, 3) float32 array -> (device buffer or None, its wc_points descriptor)"""
         points = np.ascontiguousarray(points)
         if points.dtype == R.POINT:
             stride = 48
@@ -583,12 +583,44 @@ class PointMap:
             stride = 12
         n = len(points)
         d = self.ctx.to_device(points) if n else None
-        desc = R.Points(d.ptr if d else 0, 0, stride, 0, n)
+        return d, R.Points(d.ptr if d else 0, 0, stride, 0, n)
+
+    def insert(self, points):
+        """POINT records or an (n, 3) float32 array (uploaded for the call) -> points not inserted"""
+        d, desc = self._upload(points)
         try:
             return self.insert_device(desc)
         finally:
             if d:
                 d.free()
+
+    def nearest_device(self, desc, max_dist, d_hits, want_count=True):
+        """queries already in HBM (a wc_points descriptor) -> MAP_HIT records in d_hits (wc_map_nearest); returns the number found, or
+        None without waiting when want_count is False"""
+        n = C.c_uint64(0)
+        self.ctx._ck(self.lib.wc_map_nearest(self.ctx.h, self.h, C.byref(desc), C.c_double(max_dist), C.c_void_p(d_hits.ptr if d_hits else 0),
+                                             C.byref(n) if want_count else None))
+        return int(n.value) if want_count else None
+
+    def nearest(self, queries, max_dist=np.inf):
+        """POINT records or an (n, 3) float32 array (uploaded for the call) -> MAP_HIT array: per query the nearest centroid among the
+        27 voxels around it, within max_dist (count = 0: none)"""
+        d, desc = self._upload(queries)
+        d_hits = self.ctx.alloc(R.MAP_HIT.itemsize * max(desc.n, 1))
+        try:
+            self.nearest_device(desc, max_dist, d_hits)
+            return d_hits.download(R.MAP_HIT, desc.n)
+        finally:
+            d_hits.free()
+            if d:
+                d.free()
+
+    def crop(self, lo, hi):
+        """keeps the voxels that intersect the box [lo, hi] (+-inf allowed) and compacts the table (wc_map_crop) -> voxels removed"""
+        lo, hi = (C.c_double * 3)(*[float(x) for x in lo]), (C.c_double * 3)(*[float(x) for x in hi])
+        n = C.c_uint64(0)
+        self.ctx._ck(self.lib.wc_map_crop(self.ctx.h, self.h, lo, hi, C.byref(n)))
+        return int(n.value)
 
     def size(self):
         """-> (voxels, points inserted)"""
@@ -714,6 +746,30 @@ class Odometry:
 
     def map_clear(self):
         self.lib.wc_odom_map_clear(self.h)
+
+    def map_query(self, xyz, max_dist):
+        """nearest map voxel of every row of xyz ((n, 3) float32) within max_dist -> MAP_HIT array (LidarOdometry::QueryMap)"""
+        if not max_dist > 0:
+            raise WildcatError(11, "map_query: max_dist must be > 0")
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        hits = np.zeros(len(xyz), R.MAP_HIT)
+        self.lib.wc_odom_map_query.restype = C.c_uint64
+        self.lib.wc_odom_map_query(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), C.c_double(max_dist), R.ptr(hits))
+        return hits
+
+    def map_crop(self, lo, hi):
+        """keeps the map's voxels that intersect the box [lo, hi] -> voxels removed (LidarOdometry::CropMap)"""
+        lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+        if not np.all(lo <= hi):
+            raise WildcatError(11, "map_crop: NaN bound or lo > hi")
+        self.lib.wc_odom_map_crop.restype = C.c_uint64
+        return int(self.lib.wc_odom_map_crop(self.h, (C.c_double * 3)(*lo), (C.c_double * 3)(*hi)))
+
+    def set_map_keep_radius(self, radius):
+        """LioConfig::map_keep_radius: after every sweep the map keeps the cube of this half-side around the sensor; 0 = unbounded"""
+        rc = self.lib.wc_odom_set_map_keep_radius(self.h, C.c_double(radius))
+        if rc != 0:
+            raise WildcatError(rc, "wc_odom_set_map_keep_radius(%r)" % radius)
 
     def map_ms(self):
         """wall time [ms] of the last sweep's map step (not part of stage_ms())"""

@@ -27,6 +27,9 @@ PAIR = np.dtype([("first", "i4"), ("second", "i4")])
 ROUTE_POINT = np.dtype([("x", "f4"), ("y", "f4"), ("z", "f4"), ("src", "u4"), ("t", "f8")])  # wc_route_point
 assert ROUTE_POINT.itemsize == 24
 
+MAP_HIT = np.dtype([("xyz", "f4", 3), ("count", "u4"), ("key", "i4", 3), ("flags", "u4"), ("d2", "f8")])  # wc_map_hit
+assert MAP_HIT.itemsize == 40 and MAP_HIT.fields["d2"][1] == 32
+
 assert SURFEL.itemsize == 144 and POSE.itemsize == 56 and IMU_STATE.itemsize == 112 and PAIR.itemsize == 8
 assert SURFEL_ID.itemsize == 16 and POINT.itemsize == 48
 
