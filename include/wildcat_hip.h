@@ -97,11 +97,15 @@ int wc_timer_stop_ms(wc_ctx *ctx, float *h_ms);
  *   wc_selftest_eig3: a9 symmetric row-major -> out12 = ascending eigenvalues | eigenvectors in columns (row-major)
  *   wc_selftest_quat: in12 = a(4) b(4) f p(3) -> out11 = slerp(a,f,b) | a*p (rotation) | a*b
  *   wc_selftest_so3_fused (device only): the fused forms the factor kernels evaluate (csrc/so3_fused.h) ->
- *                     out25 = Exp(v) quat | Jr(v) | Log(Exp(v)) | Jr_inv(Log(Exp(v))) */
+ *                     out25 = Exp(v) quat | Jr(v) | Log(Exp(v)) | Jr_inv(Log(Exp(v)))
+ *   wc_selftest_fx_eig3 (device only): the closed-form eigen-solver of the default extraction path (csrc/extract_fast.inc: fx_eig3,
+ *                     what every surfel's normal and sigma come from) -> out8 = ascending eigenvalues | eigenvector of the
+ *                     smallest | 1.0 closed form accepted / 0.0 the Jacobi fall-back ran | 0 */
 int wc_selftest_so3(wc_ctx *ctx, const double v[3], int on_device, double out52[52]);
 int wc_selftest_so3_fused(wc_ctx *ctx, const double v[3], double out25[25]);
 int wc_selftest_eig3(wc_ctx *ctx, const double a9[9], int on_device, double out12[12]);
 int wc_selftest_quat(wc_ctx *ctx, const double in12[12], int on_device, double out11[11]);
+int wc_selftest_fx_eig3(wc_ctx *ctx, const double a9[9], double out8[8]);
 /* the damped solve's diagonal-block kernel on its own (tests/test_kat_gpu.py, profiles/dev/factor32.py): Cholesky factor L and L^-1 of a
  * 32 x 32 SPD matrix (row-major, lower part read); variant 0 = the library's block form (256 threads, fp64 matrix-core rank-4 updates);
  * h_clk[0] = shader clocks of the fastest of `reps` runs, h_clk[1] = 1 when every pivot was positive */

@@ -100,3 +100,96 @@ def test_diagonal_block_factor_and_inverse(gpu):
         assert np.abs(np.tril(L) - Lr).max() <= 1e-13 * np.abs(Lr).max()
         assert np.abs(np.tril(X) - Xr).max() <= 1e-12 * np.abs(Xr).max()
     assert not gpu.selftest_factor32(-np.eye(32), 0, 1)[3]
+
+
+# ---- fx_eig3: the closed-form eigen-solver behind every surfel of the default extraction path ------------------------------------------
+def _rot(rng):
+    q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
+    return q
+
+
+def _sym(q, lam):
+    a = (q * np.asarray(lam, float)) @ q.T
+    return (a + a.T) / 2
+
+
+def _fx_eig3_cases():
+    """(family, matrix): what extraction hands to fx_eig3 and what could break it.  The matrices are whatever fp64 made of the recipe; the
+    reference decomposes exactly those (extract_ref.jacobi_eigh, longdouble)."""
+    rng = np.random.default_rng(41)
+    cases = []
+    for k in range(15):  # plane-like: lambda_0 / lambda_2 from 1 down to 1e-14, overall scales 1e-8 .. 1e2
+        for _ in range(10):
+            r, scale = 10.0**-k, 10 ** rng.uniform(-8, 2)
+            cases.append(("plane", _sym(_rot(rng), [r * scale, scale * rng.uniform(max(r, 0.3), 1.0), scale])))
+    for _ in range(30):  # exactly rank 2, from small-integer vectors: lambda_0 = 0
+        u, w = rng.integers(-5, 6, size=3).astype(float), rng.integers(-5, 6, size=3).astype(float)
+        if np.linalg.norm(np.cross(u, w)) > 0:
+            cases.append(("rank2", (np.outer(u, u) + np.outer(w, w)) * 2.0 ** int(rng.integers(-20, 4))))
+    perms = [np.eye(3)[list(p)] * np.array(s)[:, None] for p in ((0, 1, 2), (1, 2, 0), (2, 0, 1), (0, 2, 1)) for s in ((1, 1, 1), (-1, 1, -1))]
+    for i, pm in enumerate(perms):  # two equal eigenvalues, exactly: diagonal, rotated by a signed permutation (stays diagonal)
+        cases.append(("equal12_exact", pm @ np.diag([0.001 * (i + 1), 0.5, 0.5]) @ pm.T))
+        cases.append(("equal01_exact", pm @ np.diag([0.25, 0.25, 3.0 + i]) @ pm.T))
+    for _ in range(12):  # ... and within 1e-12, in general position
+        scale = 10 ** rng.uniform(-8, 2)
+        cases.append(("equal12_near", _sym(_rot(rng), [scale * 10 ** rng.uniform(-6, -1), scale, scale * (1 + 1e-12)])))
+        cases.append(("equal01_near", _sym(_rot(rng), [scale * 0.01, scale * 0.01 * (1 + 1e-12), scale])))
+    for _ in range(6):  # all three equal: exactly (diagonal), and as a rotation's rounding leaves it
+        scale = 10 ** rng.uniform(-8, 2)
+        cases.append(("equal_all", np.eye(3) * scale))
+        cases.append(("equal_all", _sym(_rot(rng), [scale, scale, scale])))
+    for _ in range(10):  # diagonal: p1 == 0, the fall-back by construction
+        cases.append(("diagonal", np.diag(10 ** rng.uniform(-8, 2, size=3))))
+    for i in range(12):  # axis-aligned planes with off-diagonals of 1e-20
+        d = np.roll([10 ** rng.uniform(-9, -5), 0.004 * rng.uniform(0.5, 1), 0.006], i)
+        cases.append(("axis_plane", np.diag(d) + 1e-20 * (np.ones((3, 3)) - np.eye(3)) * rng.choice([-1.0, 1.0])))
+    for _ in range(24):  # a smallest eigenvalue slightly below zero, as rounded covariances of exactly planar clusters have
+        scale = 10 ** rng.uniform(-8, 2)
+        cases.append(("negative", _sym(_rot(rng), [-scale * 10 ** rng.uniform(-17, -13), scale * rng.uniform(0.2, 1), scale])))
+    return cases
+
+
+def test_fx_eig3_against_longdouble_jacobi(gpu):
+    """wc_selftest_fx_eig3 (one thread, the routine fx_pca calls) on ~300 matrices against the longdouble Jacobi iteration of
+    tests/extract_ref.py: eigenvalues ascending and within 32 x 2^-53 of the largest magnitude; unit eigenvector; residual
+    |(A - lambda_0 I) v| <= 1e-12 (|lambda_0| + |lambda_2|), the bar at which the routine accepts its own result; where lambda_1 - lambda_0 >
+    1e-6 lambda_2 the vector within (32 x 2^-53 lambda_2 + 1e-12 (|lambda_0| + lambda_2)) / (lambda_1 - lambda_0) of the reference's (the
+    surfel bound of test_extract_precision_gpu.py with B_cov = 0); and the closed form ACCEPTED on every plane-like matrix whose likeness
+    exceeds 0.1 unless it is diagonal (p1 == 0 goes to the Jacobi iteration by construction) - those must not quietly run on the slow path."""
+    import extract_ref as X
+
+    cases = _fx_eig3_cases()
+    assert 250 <= len(cases) <= 400
+    A = np.array([c[1] for c in cases])
+    ev_ref, V_ref = X.jacobi_eigh(A)
+    worst = {}
+    fails = []
+    for i, (fam, a) in enumerate(cases):
+        ev, v, accepted = gpu.selftest_fx_eig3(a)
+        lr = ev_ref[i].astype(np.float64)
+        scale = np.abs(lr).max()
+        al, vl = a.astype(X.LD), v.astype(X.LD)
+        r_ev = float(np.abs(ev.astype(X.LD) - ev_ref[i]).max()) / (32 * 2.0**-53 * scale)
+        r_unit = abs(float(np.sqrt((vl * vl).sum()) - 1)) / (8 * 2.0**-53)
+        r_res = float(np.sqrt((((al - X.LD(ev[0]) * np.eye(3)) @ vl) ** 2).sum())) / (1e-12 * (abs(ev[0]) + abs(ev[2])))
+        r_vec = 0.0
+        if lr[1] - lr[0] > 1e-6 * lr[2]:
+            vr = V_ref[i][:, 0]
+            sgn = -1 if float((vl * vr).sum()) < 0 else 1
+            r_vec = float(np.sqrt(((sgn * vl - vr) ** 2).sum())) / ((32 * 2.0**-53 * lr[2] + 1e-12 * (abs(lr[0]) + lr[2])) / (lr[1] - lr[0]))
+        like = 2 * (lr[1] - lr[0]) / lr.sum()
+        diagonal = not np.any(a - np.diag(np.diag(a)))
+        must_accept = like > 0.1 and not diagonal and fam in ("plane", "rank2", "equal12_near", "axis_plane", "negative")
+        w = worst.setdefault(fam, dict(ev=0.0, unit=0.0, res=0.0, vec=0.0, n=0, accepted=0))
+        w["n"] += 1
+        w["accepted"] += int(accepted)
+        for k, r in (("ev", r_ev), ("unit", r_unit), ("res", r_res), ("vec", r_vec)):
+            w[k] = max(w[k], r)
+        if not (ev[0] <= ev[1] <= ev[2]) or max(r_ev, r_unit, r_res, r_vec) > 1 or not np.isfinite([r_ev, r_unit, r_res, r_vec]).all() or (must_accept and not accepted):
+            fails.append((i, fam, ev.tolist(), lr.tolist(), dict(ev=r_ev, unit=r_unit, res=r_res, vec=r_vec, accepted=accepted, like=like)))
+    print()
+    for fam, w in worst.items():
+        print("fx_eig3 %-14s %3d matrices, closed form accepted on %3d, worst error / bound: eigenvalues %.3g, unit %.3g, residual %.3g, vector %.3g"
+              % (fam, w["n"], w["accepted"], w["ev"], w["unit"], w["res"], w["vec"]))
+    assert not fails, fails[:5]
+    assert worst["diagonal"]["accepted"] == 0  # (the flag does tell the two paths apart)

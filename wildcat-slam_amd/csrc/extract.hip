@@ -1917,7 +1917,12 @@ int run_pipeline_fast(wc_ctx *ctx, const wc_points &pts, double t_lo, double t_h
   // two calls then ran on the exact path; 128 bytes per point of never-cleared memory are nothing on this card)
   A.spill_per = (uint32_t)((n <= 8000000ull || ctx->ex.fx_spill_full) ? spill_full : std::max<uint64_t>(1024, n / 32));
   A.rec_cap = tiles * (uint32_t)kFxRecTile + 8u * A.spill_per;
-  const uint64_t total_slots = (n * (uint64_t)(P.max_layer + 1)) / (uint64_t)P.cluster_min_points + 1;
+  // slots: the most surfels n points can give, in kFxSub sub-ranges (one per wavefront index mod kFxSub) - but never fewer than 256 per
+  // sub-range.  A small sweep runs on few wavefronts and takes slots ahead of the tests that decide who needs one: with 1/16 of
+  // 3 n / 20 + 1 per sub-range, a 2 880-point sweep of one-patch roots (120 surfels, 27 slots per sub-range) ran out of slots and
+  // was silently repeated on the exact path, every time (found by tests/test_extract_precision_gpu.py).  From 27 k points on the
+  // floor changes nothing.
+  const uint64_t total_slots = std::max<uint64_t>((n * (uint64_t)(P.max_layer + 1)) / (uint64_t)P.cluster_min_points + 1, (uint64_t)kFxSub * 256);
   uint32_t bin_cap = 64;
   while (bin_cap < kSlotBinMax && (uint64_t)bin_cap * kBuckets < 2 * total_slots) bin_cap *= 2;
   WC_TRY(fx_ensure_zero(ctx, ctx->b_fx[0], (size_t)tr * 4));
@@ -2617,6 +2622,43 @@ extern "C" int wc_debug_status(wc_ctx *ctx, uint32_t *h_out64) {
   for (int i = 0; i < 8; ++i) h_out64[16 + i] = cnt ? (uint32_t)(sum[i] / cnt) : 0;
   h_out64[24] = cnt;
 #endif
+  return WC_OK;
+}
+
+// fx_eig3 - the closed-form eigen-solver behind every surfel of the default path (extract_fast.inc) - on one matrix, in a one-thread
+// kernel (the pattern of selftest.hip's run_selftest; it lives here because fx_eig3 is in this file's anonymous namespace)
+namespace {
+struct FxEigOut {
+  double ev[3];   // ascending
+  double vec[3];  // eigenvector of the smallest eigenvalue
+  double accepted;  // 1: the closed form passed its own residual test, 0: wc::eig3_sym (Jacobi) ran
+  double spare;
+};
+__global__ void k_selftest_fx_eig3(const double *a9, FxEigOut *o) {
+  wc::M3 a, v;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) a.m[i][j] = a9[3 * i + j];
+  bool acc = false;
+  fx_eig3(a, o->ev, v, &acc);
+  for (int i = 0; i < 3; ++i) o->vec[i] = v.m[i][0];
+  o->accepted = acc ? 1.0 : 0.0;
+  o->spare = 0.0;
+}
+}  // namespace
+
+extern "C" int wc_selftest_fx_eig3(wc_ctx *ctx, const double a9[9], double out8[8]) {
+  if (!ctx || !a9 || !out8) return wc_fail(ctx, WC_ERR_ARG, "%s: null argument", __func__);
+  wc_dev_guard dg_(ctx);
+  WC_TRY(wc_ensure(ctx, ctx->b_status, 1024));
+  double *d_in = (double *)ctx->b_status.p;
+  FxEigOut *d_out = (FxEigOut *)((char *)ctx->b_status.p + 128);
+  FxEigOut o;
+  WC_HIP(ctx, hipMemcpyAsync(d_in, a9, 9 * 8, hipMemcpyHostToDevice, ctx->stream));
+  k_selftest_fx_eig3<<<1, 1, 0, ctx->stream>>>(d_in, d_out);
+  WC_HIP(ctx, hipGetLastError());
+  WC_HIP(ctx, hipMemcpyAsync(&o, d_out, sizeof(o), hipMemcpyDeviceToHost, ctx->stream));
+  WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::memcpy(out8, &o, sizeof(o));
   return WC_OK;
 }
 

@@ -16,7 +16,8 @@
 //   * takes every decision the reference takes (n > 20, n >= 20, lambda_0 < 0.01f, likeness > 0.1, cc:33,54,106-111,129,172)
 //     on these sums, and raises kFlagFxFallback whenever a PCA gate is closer to its threshold than the reference's own
 //     rounding noise could move it: finish() then repeats the sweep on the exact path.  Counts and ids are therefore the
-//     reference's; centre / covariance / normal / sigma agree to ~1e-9; a surfel's timestamp is the correctly rounded mean
+//     reference's; centre / covariance / normal / sigma agree with the exact values to the grids' rounding (covariance entries 2^-45 m^2,
+//     bounds and measurements per field: DESIGN.md 4.3, tests/test_extract_precision_gpu.py); a surfel's timestamp is the correctly rounded mean
 //     (the reference's running sum rounds at ~1e-5 s with epoch-sized stamps), so the OUTPUT ORDER - ascending timestamp,
 //     ties by id - can differ from the exact path's where two surfels are closer in time than that noise.
 // Kernels (C2: 3 launches):
@@ -919,7 +920,8 @@ __device__ __forceinline__ double fx_rsqrt(double a) {
   r = fma(0.5 * r, fma(-a * r, r, 1.0), r);
   return fma(0.5 * r, fma(-a * r, r, 1.0), r);
 }
-__device__ __forceinline__ void fx_eig3(const wc::M3 &A, double ev[3], wc::M3 &V) {
+// accepted (the self-test's view, wc_selftest_fx_eig3): whether the closed form's result was taken or the Jacobi iteration decided
+__device__ __forceinline__ void fx_eig3(const wc::M3 &A, double ev[3], wc::M3 &V, bool *accepted = nullptr) {
   const double a00 = A.m[0][0], a11 = A.m[1][1], a22 = A.m[2][2], a01 = A.m[0][1], a02 = A.m[0][2], a12 = A.m[1][2];
   const double p1 = a01 * a01 + a02 * a02 + a12 * a12;
   const double q = (a00 + a11 + a22) * (1.0 / 3.0);
@@ -948,10 +950,8 @@ __device__ __forceinline__ void fx_eig3(const wc::M3 &A, double ev[3], wc::M3 &V
     // with x = cos(phi): -cos(phi + 2 pi / 3) = x / 2 + sqrt(3) / 2 sin(phi) =: z.  r >= 0: largest root x, smallest -z;
     // r < 0: the roots are the negated roots of |r|: smallest -x, largest z
     const double z = 0.5 * x + 0.8660254037844386 * sqrt(fmax(1.0 - x * x, 0.0));
-    const double t = sg < 0.0 ? -x : -z, cphi = sg < 0.0 ? z : x;
-    const double e2 = q + 2.0 * p * cphi;  // largest
+    const double t = sg < 0.0 ? -x : -z;
     const double e0 = q + 2.0 * p * t;     // smallest
-    const double e1 = 3.0 * q - e0 - e2;
     // eigenvector of the smallest eigenvalue: the largest of the cross products of the rows of A - e0 I
     const double m00 = a00 - e0, m11 = a11 - e0, m22 = a22 - e0;
     const double x0 = a01 * a12 - a02 * m11, y0 = a02 * a01 - m00 * a12, z0 = m00 * m11 - a01 * a01;  // row0 x row1
@@ -964,6 +964,20 @@ __device__ __forceinline__ void fx_eig3(const wc::M3 &A, double ev[3], wc::M3 &V
     const double inv = fx_rsqrt(nn);
     vx *= inv, vy *= inv, vz *= inv;
     const double rx = m00 * vx + a01 * vy + a02 * vz, ry = a01 * vx + m11 * vy + a12 * vz, rz = a02 * vx + a12 * vy + m22 * vz;
+    // The two larger eigenvalues do NOT come from the cubic: q + 2 p cos(phi -+ 2 pi / 3) contains sin(phi) = sqrt(1 - x^2), which
+    // loses half the digits where two eigenvalues meet (lambda_1 ~ lambda_2, the isotropic patch: 1e-12 .. 1e-8 of lambda_2 against
+    // the longdouble Jacobi, tests/test_kat_gpu.py) - and lambda_1 is the likeness, whose "near" band in fx_pca allows 1e-13.  They
+    // are the eigenvalues of A restricted to the plane across v, in an orthonormal basis of it (Duff et al. 2017, branch-free): a
+    // symmetric 2 x 2 problem, mean -+ hypot, every step at rounding level.  The smallest eigenvalue and its vector are what they were.
+    const double sgn = copysign(1.0, vz), ia = -fx_rcp(sgn + vz), bxy = vx * vy * ia;
+    const double b1x = 1.0 + sgn * vx * vx * ia, b1y = sgn * bxy, b1z = -sgn * vx;
+    const double b2x = bxy, b2y = sgn + vy * vy * ia, b2z = -vy;
+    const double t1x = a00 * b1x + a01 * b1y + a02 * b1z, t1y = a01 * b1x + a11 * b1y + a12 * b1z, t1z = a02 * b1x + a12 * b1y + a22 * b1z;
+    const double t2x = a00 * b2x + a01 * b2y + a02 * b2z, t2y = a01 * b2x + a11 * b2y + a12 * b2z, t2z = a02 * b2x + a12 * b2y + a22 * b2z;
+    const double paa = b1x * t1x + b1y * t1y + b1z * t1z, pab = b1x * t2x + b1y * t2y + b1z * t2z, pdd = b2x * t2x + b2y * t2y + b2z * t2z;
+    const double hm = 0.5 * (paa + pdd), hd = 0.5 * (paa - pdd), w = hd * hd + pab * pab;
+    const double rad = w > 0.0 ? w * fx_rsqrt(w) : 0.0;
+    const double e1 = hm - rad, e2 = hm + rad;
     const double scale = fabs(e2) + fabs(e0);
     ok = nn > 0.0 && (rx * rx + ry * ry + rz * rz) <= 1e-24 * scale * scale && e0 <= e1 && e1 <= e2;
     if (ok) {
@@ -973,6 +987,7 @@ __device__ __forceinline__ void fx_eig3(const wc::M3 &A, double ev[3], wc::M3 &V
     }
   }
   if (!ok) wc::eig3_sym(A, ev, V);
+  if (accepted) *accepted = ok;
 }
 
 struct FxPca {

@@ -148,6 +148,14 @@ class Context:
         self._ck(self.lib.wc_selftest_factor32(self.h, C.c_int(variant), C.c_int(reps), R.ptr(a), R.ptr(L), R.ptr(X), clk))
         return L, X, int(clk[0]), bool(clk[1])
 
+    def selftest_fx_eig3(self, a):
+        """-> (ascending eigenvalues, eigenvector of the smallest, closed form accepted) of the symmetric 3 x 3 matrix a by the default
+        extraction path's closed-form solver on the device (wc_selftest_fx_eig3)"""
+        a = np.ascontiguousarray(a, np.float64).reshape(9)
+        out = np.zeros(8)
+        self._ck(self.lib.wc_selftest_fx_eig3(self.h, R.ptr(a), R.ptr(out)))
+        return out[0:3].copy(), out[3:6].copy(), bool(out[6])
+
     def set_dev_option(self, name, value):
         """a development option of this context (include/wildcat_hip.h: wc_ctx_set_dev_option)"""
         self._ck(self.lib.wc_ctx_set_dev_option(self.h, name.encode(), C.c_int(int(value))))
