@@ -190,7 +190,8 @@ int wc_prefilter_points(wc_ctx *ctx, const void *d_pts_in, uint64_t n, const dou
 /* The same loop including its CHECK(points_buff_.empty() || pt.time >= points_buff_.back().time) (:491), evaluated on the device
  * for EVERY incoming point against the last point buffered at that moment: prev_time = stamp of the last buffered point before this
  * message (-INFINITY: buffer empty).  *h_monotonic = 0 when the CHECK would have fired.  d_kept_times (may be NULL, capacity
- * `cap`): the survivors' stamps, packed - the only thing a host-side window bookkeeping needs back. */
+ * `cap`): the survivors' stamps, packed - the only thing a host-side window bookkeeping needs back.  The CHECK knows no capacity:
+ * with WC_ERR_CAPACITY, *h_monotonic still covers every point of the message. */
 int wc_prefilter_points_checked(wc_ctx *ctx, const void *d_pts_in, uint64_t n, const double ext_quat[4], const double ext_t[3],
                                 double min_range, double max_range, const double blind_min[3], const double blind_max[3],
                                 void *d_pts_out, uint64_t cap, uint64_t *h_n_out, double prev_time, double *d_kept_times,

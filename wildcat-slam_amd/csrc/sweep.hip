@@ -42,12 +42,13 @@ __global__ void __launch_bounds__(256) k_prefilter_flags(const Pt48 *in, uint64_
 
 __global__ void __launch_bounds__(256) k_prefilter_scatter(const Pt48 *in, uint64_t n, const float *xyz, const uint32_t *flags,
                                                           const uint32_t *offsets, Pt48 *out, uint64_t cap, uint32_t *status,
-                                                          double *kept_times) {
+                                                          double *kept_times, double *all_times) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   if (i == n - 1) status[0] = offsets[i] + flags[i];
   if (!flags[i]) return;
   const uint32_t o = offsets[i];
+  if (all_times) memcpy(&all_times[o], (const char *)(in + i) + 24, 8);  // (room for n: not bounded by cap)
   if (o >= cap) return;
   Pt48 r = in[i];
   float *f = (float *)&r;
@@ -58,15 +59,16 @@ __global__ void __launch_bounds__(256) k_prefilter_scatter(const Pt48 *in, uint6
 
 // CHECK(points_buff_.empty() || pt.time >= points_buff_.back().time) (lidar_odometry.cc:491) for EVERY incoming point, kept
 // or not, against the last point BUFFERED at that moment: the kept point in front of it in this message (the one whose output
-// index is offsets[i] - 1), or the last point buffered before the message (prev_time; -inf when the buffer is empty)
+// index is offsets[i] - 1), or the last point buffered before the message (prev_time; -inf when the buffer is empty).
+// kept_times holds the stamp of EVERY kept point, also of those that found no room in the output: the CHECK does not know `cap`
 __global__ void __launch_bounds__(256) k_prefilter_monotonic(const Pt48 *in, uint64_t n, const uint32_t *offsets, const double *kept_times,
-                                                            uint64_t cap, double prev_time, uint32_t *status) {
+                                                            double prev_time, uint32_t *status) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   double t;
   memcpy(&t, (const char *)(in + i) + 24, 8);
   const uint32_t o = offsets[i];
-  const double prev = o == 0u ? prev_time : (o - 1u < cap ? kept_times[o - 1u] : t);
+  const double prev = o == 0u ? prev_time : kept_times[o - 1u];
   if (!(t >= prev)) status[2] = 1u;
 }
 
@@ -135,13 +137,17 @@ static int prefilter_impl(wc_ctx *ctx, const void *d_pts_in, uint64_t n, const d
   WC_TRY(wc_ensure(ctx, ctx->b_misc[7], tmp + 16));
   tmp = ctx->b_misc[7].cap;
   WC_HIP(ctx, rocprim::exclusive_scan(ctx->b_misc[7].p, tmp, flags, offsets, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
-  if (check_time && !d_kept_times) {  // the check reads the kept stamps: a scratch array when the caller wants none
-    WC_TRY(wc_ensure(ctx, ctx->b_misc[4], std::min<uint64_t>(n, cap) * 8 + 8));
-    d_kept_times = (double *)ctx->b_misc[4].p;
+  // the check reads the stamp of every kept point: the caller's array where it has room for all of them whatever is kept
+  // (cap >= n), a scratch array of n otherwise
+  double *all_times = nullptr;
+  if (check_time && (!d_kept_times || cap < n)) {
+    WC_TRY(wc_ensure(ctx, ctx->b_misc[4], n * 8));
+    all_times = (double *)ctx->b_misc[4].p;
   }
   k_prefilter_scatter<<<grid, 256, 0, st>>>((const Pt48 *)d_pts_in, n, (const float *)ctx->b_misc[5].p, flags, offsets, (Pt48 *)d_pts_out,
-                                           cap, status, d_kept_times);
-  if (check_time) k_prefilter_monotonic<<<grid, 256, 0, st>>>((const Pt48 *)d_pts_in, n, offsets, d_kept_times, cap, prev_time, status);
+                                           cap, status, d_kept_times, all_times);
+  if (check_time)
+    k_prefilter_monotonic<<<grid, 256, 0, st>>>((const Pt48 *)d_pts_in, n, offsets, all_times ? all_times : d_kept_times, prev_time, status);
   WC_HIP(ctx, hipGetLastError());
   WC_HIP(ctx, hipMemcpyAsync(ctx->h_status, status, 12, hipMemcpyDeviceToHost, st));
   WC_HIP(ctx, hipStreamSynchronize(st));

@@ -391,26 +391,42 @@ class Context:
         return d_out.download(R.SURFEL, int(m.value)), d_oid.download(R.SURFEL_ID, int(m.value))
 
     # ---- sweep preparation (row f-1) -------------------------------------------------------------------------------------
-    def prefilter_points(self, points, ext_quat, ext_t, min_range, max_range, blind_min, blind_max):
-        n = len(points)
-        d_in, d_out = self.to_device(points), self.alloc(48 * max(n, 1))
-        m = C.c_uint64(0)
-        v = lambda a: R.ptr(np.ascontiguousarray(a, np.float64))  # noqa: E731
-        self._ck(self.lib.wc_prefilter_points(self.h, C.c_void_p(d_in.ptr), C.c_uint64(n), v(ext_quat), v(ext_t), C.c_double(min_range),
-                                              C.c_double(max_range), v(blind_min), v(blind_max), C.c_void_p(d_out.ptr), C.c_uint64(n), C.byref(m)))
-        return d_out.download(R.POINT, int(m.value))
-
-    def prefilter_points_checked(self, points, ext_quat, ext_t, min_range, max_range, blind_min, blind_max, prev_time=-np.inf):
-        """-> (survivors, their stamps as the library packed them, the reference's CHECK at lidar_odometry.cc:491 held)"""
-        n = len(points)
-        d_in, d_out, d_t = self.to_device(points), self.alloc(48 * max(n, 1)), self.alloc(8 * max(n, 1))
+    def prefilter_device(self, d_in, n, ext_quat, ext_t, min_range, max_range, blind_min, blind_max, d_out, cap, prev_time=None, d_kept_times=None):
+        """wc_prefilter_points (prev_time None) or wc_prefilter_points_checked on device buffers of the caller -> (return code, *h_n_out,
+        monotonic or None).  WC_ERR_CAPACITY is returned, not raised: *h_n_out and the first `cap` records are valid then."""
         m, mono = C.c_uint64(0), C.c_int(1)
         v = lambda a: R.ptr(np.ascontiguousarray(a, np.float64))  # noqa: E731
-        self._ck(self.lib.wc_prefilter_points_checked(self.h, C.c_void_p(d_in.ptr), C.c_uint64(n), v(ext_quat), v(ext_t), C.c_double(min_range),
-                                                      C.c_double(max_range), v(blind_min), v(blind_max), C.c_void_p(d_out.ptr), C.c_uint64(n),
-                                                      C.byref(m), C.c_double(prev_time), C.c_void_p(d_t.ptr), C.byref(mono)))
-        k = int(m.value)
-        return d_out.download(R.POINT, k), d_t.download(np.float64, k), bool(mono.value)
+        head = (self.h, C.c_void_p(d_in.ptr), C.c_uint64(n), v(ext_quat), v(ext_t), C.c_double(min_range), C.c_double(max_range), v(blind_min),
+                v(blind_max), C.c_void_p(d_out.ptr), C.c_uint64(cap), C.byref(m))
+        if prev_time is None:
+            rc = self.lib.wc_prefilter_points(*head)
+        else:
+            rc = self.lib.wc_prefilter_points_checked(*head, C.c_double(prev_time), C.c_void_p(d_kept_times.ptr if d_kept_times else None),
+                                                      C.byref(mono))
+        if rc not in (WC_OK, WC_ERR_CAPACITY):
+            self._ck(rc)
+        return rc, int(m.value), (None if prev_time is None else bool(mono.value))
+
+    def prefilter_points(self, points, ext_quat, ext_t, min_range, max_range, blind_min, blind_max, cap=None):
+        """-> survivors.  cap: capacity of the output (default: every point fits); WC_ERR_CAPACITY raises"""
+        n = len(points)
+        cap = n if cap is None else int(cap)
+        d_in, d_out = self.to_device(points), self.alloc(48 * max(cap, 1))
+        rc, m, _ = self.prefilter_device(d_in, n, ext_quat, ext_t, min_range, max_range, blind_min, blind_max, d_out, cap)
+        self._ck(rc)
+        return d_out.download(R.POINT, m)
+
+    def prefilter_points_checked(self, points, ext_quat, ext_t, min_range, max_range, blind_min, blind_max, prev_time=-np.inf, cap=None,
+                                 kept_times=True):
+        """-> (survivors, their stamps as the library packed them, the reference's CHECK at lidar_odometry.cc:491 held).  cap: capacity of
+        both outputs (default: every point fits); kept_times=False passes d_kept_times = NULL and returns None for the stamps"""
+        n = len(points)
+        cap = n if cap is None else int(cap)
+        d_in, d_out = self.to_device(points), self.alloc(48 * max(cap, 1))
+        d_t = self.alloc(8 * max(cap, 1)) if kept_times else None
+        rc, k, mono = self.prefilter_device(d_in, n, ext_quat, ext_t, min_range, max_range, blind_min, blind_max, d_out, cap, prev_time, d_t)
+        self._ck(rc)
+        return d_out.download(R.POINT, k), (d_t.download(np.float64, k) if kept_times else None), mono
 
     def undistort_sweep_packed(self, points, imu, keep_on_device=False):
         """-> (xyz float32 (n, 3), time float64 (n,)): the 20 bytes per point the extraction reads"""
@@ -433,6 +449,11 @@ class Context:
     def update_surfel_poses(self, d_imu, n_imu, d_surf, d_pose, d_in_body, n):
         self._ck(self.lib.wc_update_surfel_poses(self.h, C.c_void_p(d_imu.ptr), C.c_uint64(n_imu), C.c_void_p(d_surf.ptr), C.c_void_p(d_pose.ptr),
                                                  C.c_void_p(d_in_body.ptr), C.c_uint64(n)))
+
+    def reverse_copy_surfels(self, d_src_surf, d_src_pose, n, d_dst_surf, d_dst_pose):
+        """dst[j] = src[n - 1 - j] for surfels and poses (wc_reverse_copy_surfels); asynchronous on the context's stream"""
+        self._ck(self.lib.wc_reverse_copy_surfels(self.h, C.c_void_p(d_src_surf.ptr), C.c_void_p(d_src_pose.ptr), C.c_uint64(n),
+                                                  C.c_void_p(d_dst_surf.ptr), C.c_void_p(d_dst_pose.ptr)))
 
     def window_build(self, d_surf, d_pose, d_pairs, n_pairs, imu, sample_times, grav, fix_first_pos, d_fix_surf=None, d_fix_pose=None,
                      d_pairs_fix=None, n_pairs_fix=0, sharded=False):
