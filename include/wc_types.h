@@ -96,6 +96,29 @@ typedef struct wc_map_hit {
   double d2;      /* squared distance query -> centroid                                                      */
 } wc_map_hit;
 
+/* wc_map_create_ex flags */
+#define WC_MAP_MOMENTS 1u /* every voxel also accumulates the second moments of its points: surfel export and plane queries */
+
+/* One voxel of a WC_MAP_MOMENTS map as wc_map_export_surfels writes it (not a reference type).  128 bytes, 8-aligned.  The plane
+ * through the voxel's points, from exact integer moments of the points quantised to 2^-16 m (wildcat_hip.h: "map surfels"). */
+typedef struct wc_map_surfel {
+  int32_t key[3];   /* the voxel index                                                                          */
+  uint32_t count;   /* its point count                                                                          */
+  float xyz[3];     /* its centroid: the very float triple wc_map_export returns for it                         */
+  uint32_t flags;   /* bit 0 "plane": count >= 3 and ev[2] > 0                                                  */
+  double cov[6];    /* population covariance (xx, xy, xz, yy, yz, zz) of the quantised points, m^2              */
+  double ev[3];     /* its eigenvalues, ascending                                                               */
+  double normal[3]; /* unit eigenvector of ev[0]; its component of largest magnitude (lowest axis on a tie) > 0 */
+} wc_map_surfel;
+
+/* Answer of wc_map_nearest_plane for one query (not a reference type).  80 bytes, 8-aligned. */
+typedef struct wc_map_plane_hit {
+  wc_map_hit hit;   /* what wc_map_nearest writes for the query; hit.flags bit 1 is added: "the plane below is valid"          */
+  double normal[3]; /* the found voxel's wc_map_surfel.normal, byte for byte (0 without bit 1)                                */
+  double sigma2;    /* its ev[0] (0 without bit 1)                                                                            */
+  double dist;      /* signed distance of the query to the plane through the centroid: (nx ex + ny ey) + nz ez, e = q - xyz   */
+} wc_map_plane_hit;
+
 /* Communicator of a multi-GPU job: one process (and one wc_ctx) per GPU.  The library calls these for its few collectives;
  * wc_comm_rccl_init() installs an in-library RCCL implementation, tests / other runtimes install callbacks.
  * All buffers are DEVICE pointers on the ctx's GPU; a callback returns 0 on success and must have completed (or be

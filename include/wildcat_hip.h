@@ -66,6 +66,8 @@ int wc_ctx_set_params(wc_ctx *ctx, const wc_params *params);
  *                      binding, 0: never, 2: always - the choreography with a communicator of callbacks, for tests)
  *   lm_dense_radius    iterations whose trust-region radius exceeds 10^value take the dense step (default 7: the largest radius at which
  *                      the bias elimination's backward error stays below 1e-9 - tests/test_lm_step_gpu.py; 0 = never)
+ *   map_mom_pts (1)    wc_map_insert into a WC_MAP_MOMENTS map: points per lane - 1: tiles of 256 points, 54 KB of LDS; 2: the plain
+ *                      insert's tiles of 512 points, 108 KB of LDS, one workgroup per CU (same sums either way)
  *   lm_radius0         initial trust-region radius of wc_window_solve: 10^value (default -1 = the library's 1e4); tests use it to
  *                      look at the first step at other damping levels
  * Tests use it to run both forms of a choice on the same data.  Unknown names return WC_ERR_ARG. */
@@ -338,11 +340,14 @@ int wc_window_set_allreduce(wc_ctx *ctx, int (*fn)(void *user, double *d_buf, ui
  *                     the map of A u B u C inserted in any split, order or schedule
  *   limits            0.01 <= v <= 4.0 (below 0.01 the reference does nothing, :232-234) else WC_ERR_ARG; |k| < 2^20 per axis (keys
  *                     packed 21 bits per axis).  A point with a non-finite coordinate or a key out of range is NOT inserted and is
- *                     counted (the reference's int32 cast has no range check); at most 2^30 points per voxel
+ *                     counted (the reference's int32 cast has no range check); at most 2^30 points per voxel (2^28 in a map created
+ *                     with WC_MAP_MOMENTS, below)
  * Several maps per context are independent.  Every call works on the ctx's stream. */
 typedef struct wc_map wc_map;
 /* reserve_voxels: voxels the table holds before its first growth (0: none) */
 int wc_map_create(wc_ctx *ctx, double voxel, uint64_t reserve_voxels, wc_map **out);
+/* wc_map_create with flags (wc_types.h: WC_MAP_MOMENTS; 0 = wc_map_create; any other bit: WC_ERR_ARG) */
+int wc_map_create_ex(wc_ctx *ctx, double voxel, uint64_t reserve_voxels, uint32_t flags, wc_map **out);
 int wc_map_destroy(wc_ctx *ctx, wc_map *m);
 /* DownSamplingVoxel's accumulation (:236-254) for the points of `pts` (DEVICE pointers, any xyz_stride >= 12 that is a multiple of 4:
  * the 48-byte hilti_ros::Point or packed xyz; pts->time is ignored and may be NULL).  h_n_rejected (may be NULL) receives the number
@@ -384,6 +389,35 @@ int wc_map_nearest(wc_ctx *ctx, wc_map *m, const wc_points *queries, double max_
  * growth counts stay.  *h_removed_voxels (may be NULL) receives the number of voxels dropped.  Waits for the ctx stream either way:
  * the new table is sized from the kept count. */
 int wc_map_crop(wc_ctx *ctx, wc_map *m, const double lo[3], const double hi[3], uint64_t *h_removed_voxels);
+
+/* map surfels: the plane through every voxel's points (WC_MAP_MOMENTS) ------------------------------------------------------------ */
+/* A map created with WC_MAP_MOMENTS holds nine more 64-bit words per slot (112 instead of 40 bytes, wc_map_info).  Per inserted point
+ * p of voxel k, from the quantity the insert already forms:
+ *   q_a = llrint((p_a - r_a) * 2^32)      r = the voxel's reference point on the 2^-10 m grid (unchanged: the centroid's sums)
+ *   u_a = (q_a + 2^15) >> 16              arithmetic shift: the coordinate in units of 2^-16 m (about 15 um), a function of the point alone
+ *   U_a = sum u_a,  M_ab = sum u_a u_b    ab = xx, xy, xz, yy, yz, zz; two's-complement 64-bit sums
+ * |p - r| <= 2.0005 m gives |u| < 2^17.001 and products < 2^34.01: at most 2^28 points per voxel of such a map (2^30 otherwise).  All
+ * sums are integers, so the moments - like the centroids - are bit-identical however the same points are split, ordered or scheduled,
+ * and everything a plain map returns (wc_map_export, wc_map_nearest, wc_map_size) is byte-equal for a moments map of the same input.
+ * Growth, crop and clear carry, keep and clear the moments with their voxels.
+ *   covariance   population covariance of the quantised points: exactly N_ab / (n^2 2^32) m^2 with the integer N_ab = n M_ab - U_a U_b,
+ *                formed in 128 bits, rounded once and divided by n^2 (csrc/map.hip: map_plane_of): within 2 ulp of the rational.
+ *                Coincident points give exactly 0; points on one plane of the 2^-16 m grid across an axis give an exactly zero row
+ *   ev, normal   eigenvalues ascending and the unit eigenvector of ev[0], by the closed-form solver of the extraction (csrc/fx_eig3.h;
+ *                cyclic Jacobi where the matrix is diagonal or the closed form's residual exceeds 8 x 2^-53 of the scale); the normal
+ *                is negated when its component of largest magnitude is negative, the lowest axis deciding a tie in magnitude
+ *   plane bit    count >= 3 and ev[2] > 0
+ * wc_map_export_surfels writes one wc_map_surfel per occupied voxel, in the order and number of wc_map_export, under its capacity and
+ * error rules (WC_ERR_CAPACITY with *h_n = the needed count; d_out 8-aligned).  A map without moments: WC_ERR_ARG. */
+int wc_map_export_surfels(wc_ctx *ctx, wc_map *m, wc_map_surfel *d_out, uint64_t cap, uint64_t *h_n);
+/* Plane query.  The voxel is chosen as wc_map_nearest chooses it (candidates, distance, ties, max_dist, argument checks), and the first
+ * 40 bytes of a wc_map_plane_hit are that call's wc_map_hit, except that bit 1 of flags is set iff a voxel was found, its
+ * count >= min_points and its plane bit is set.  Then normal and sigma2 are the voxel's wc_map_surfel.normal and .ev[0], byte for byte, and
+ *   dist = (n_x e_x + n_y e_y) + n_z e_z,  e = (double)q - (double)xyz as in d2, no fused multiply-add;
+ * otherwise normal, sigma2 and dist are 0.  The eigen-solve runs once per query, for the winning voxel.  h_n_found counts the hits of
+ * wc_map_nearest, not the planes.  min_points < 3 or a map without moments: WC_ERR_ARG. */
+int wc_map_nearest_plane(wc_ctx *ctx, wc_map *m, const wc_points *queries, double max_dist, uint32_t min_points,
+                         wc_map_plane_hit *d_hits, uint64_t *h_n_found);
 
 #ifdef __cplusplus
 }

@@ -8,16 +8,23 @@
 // r is the voxel centre rounded to 1/1024 m, a function of the key alone, so every point's q is a deterministic function of the point:
 // integer addition is associative, and the map is bit-identical however the same points are split across calls, ordered or
 // scheduled.  |p - r| <= v / 2 + 2^-11 <= 2.0005 m, so a voxel holds up to 2^30 points before a sum could overflow.
+//   mom[cap][9]   i64, only in a map created with WC_MAP_MOMENTS: with u = (q + 2^15) >> 16 (arithmetic shift: q rounded to 2^-16 m, a
+//                 function of the point alone) the sums of u per axis (3 words) and of u_a u_b for ab = xx, xy, xz, yy, yz, zz (6 words).
+//                 |u| < 2^17.001, every product < 2^34.01: such a voxel holds up to 2^28 points before a second moment could overflow.
+//                 Integer sums again: the moments are as order independent as the centroids.  pay[] is what it is in a plain map.
 // Kernels (all on the ctx's stream):
 //   k_map_insert    tiles of 512 consecutive points per workgroup: each lane folds its 2 points into a run while the voxel stays the
 //                   same, the tile's voxels are pre-aggregated in an LDS hash (1024 slots, at most half full), then ONE global probe
-//                   and four integer atomic adds per distinct voxel of the tile; counters once per workgroup
+//                   and four integer atomic adds per distinct voxel of the tile; counters once per workgroup.  <true, .>: the nine
+//                   moment sums ride along (nine more LDS words per hash slot, thirteen global atomics per distinct voxel)
 //   k_map_rehash    growth: every occupied slot of the old table into the new one (distinct keys: plain stores of the payload)
 //   k_map_compact   export: occupied slots -> (key, slot) pairs (LDS staging, one atomic per workgroup); rocPRIM radix sort by key
 //   k_map_centroids export: centroid = r + sum / (count * 2^32) in fp64, rounded once to float; count; key (optional)
 //   k_map_nearest   query: one lane per query; the first-slot key loads of the 27 voxels around the query's own are issued nine at a
 //                   time before any is examined, payload loads and divisions only for the occupied ones; read-only probes, no CAS
 //   k_map_crop_count / k_map_rehash<true>  crop: kept voxels and points counted per workgroup, then only the kept keys rehashed
+//   k_map_surfels   surfel export: one lane per sorted voxel: map_plane_of (exact 128-bit covariance numerator, fx_eig3) -> wc_map_surfel
+//   k_map_nearest<true>  plane query: the same search, then map_plane_of for the winning voxel only -> wc_map_plane_hit
 // Growth policy: before an insert of n points the host takes an upper bound B of the occupied slots (the exact count of the last
 // completed insert's read-back plus every point inserted after it); when 2 (B + n) > cap the table is rehashed into the smallest power
 // of two >= 2 (B + n) slots.  The table is therefore at most half full at every probe, and an insert never runs out of room.
@@ -29,6 +36,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "ctx.h"
+#include "dmath.h"
 
 struct wc_map {
   wc_ctx *ctx = nullptr;
@@ -36,6 +44,8 @@ struct wc_map {
   uint64_t cap = 0;                  // slots (power of two)
   unsigned long long *keys = nullptr;
   long long *pay = nullptr;          // 4 per slot: sum qx, qy, qz, count
+  long long *mom = nullptr;          // WC_MAP_MOMENTS: 9 per slot: sum ux, uy, uz, uxux, uxuy, uxuz, uyuy, uyuz, uzuz; else NULL
+  uint32_t flags = 0;                // wc_map_create_ex's
   unsigned long long *ctr = nullptr; // device counters, each on a 128-byte line of its own (see kCtr*)
   unsigned long long *h_ctr = nullptr;  // pinned copy of the counters, written after every insert
   hipEvent_t ev_ctr = nullptr;       // recorded after that copy
@@ -50,10 +60,13 @@ struct wc_map {
 
 namespace {
 
+#include "fx_eig3.h"
+
 constexpr int kMapThreads = 256;
 constexpr int kMapPts = 2;                         // consecutive points per lane
 constexpr int kMapTile = kMapThreads * kMapPts;    // points per tile
-constexpr int kMapLds = 2 * kMapTile;              // LDS hash slots: a tile's voxels fill at most half of it
+constexpr int kMapMom = 9;                         // moment words per slot of a WC_MAP_MOMENTS map
+constexpr int kMapMomPts = 1;                      // points per lane of the moments insert (the alternative form: DESIGN, "Map surfels")
 constexpr unsigned long long kMapEmpty = ~0ull;
 constexpr double kMapUnit = 4294967296.0;          // fixed-point unit: 2^-32 m
 constexpr double kMapKeyLim = 1048576.0;           // |k| < 2^20
@@ -84,6 +97,8 @@ __device__ __forceinline__ unsigned long long map_pack(int kx, int ky, int kz) {
 __device__ __forceinline__ float map_centroid(int k, double v, long long s, double c) {
   return (float)(map_ref(k, v) + (double)s / (c * kMapUnit));
 }
+// a point's coordinate in the moments' unit, 2^-16 m: q rounded (arithmetic shift; ties up), a function of the point alone
+__device__ __forceinline__ long long map_u(long long q) { return (q + 32768) >> 16; }
 // the sum of a 64-lane wavefront in lane 0
 template <class T>
 __device__ __forceinline__ T wave_sum(T x) {
@@ -111,32 +126,49 @@ __device__ __forceinline__ unsigned long long map_slot(unsigned long long *keys,
   return kMapEmpty;
 }
 
-__device__ __forceinline__ void lds_add(unsigned long long *lk, unsigned long long *ls, unsigned *lc, unsigned long long key,
-                                        long long qx, long long qy, long long qz, unsigned n) {
-  unsigned s = (unsigned)map_hash(key) & (kMapLds - 1);
+template <int LDS>
+__device__ __forceinline__ unsigned lds_add(unsigned long long *lk, unsigned long long *ls, unsigned *lc, unsigned long long key,
+                                            long long qx, long long qy, long long qz, unsigned n) {
+  unsigned s = (unsigned)map_hash(key) & (LDS - 1);
   while (true) {
     unsigned long long cur = lk[s];
     if (cur == kMapEmpty) cur = atomicCAS(&lk[s], kMapEmpty, key);
     if (cur == kMapEmpty || cur == key) break;
-    s = (s + 1) & (kMapLds - 1);
+    s = (s + 1) & (LDS - 1);
   }
   atomicAdd(&ls[s], (unsigned long long)qx);
-  atomicAdd(&ls[kMapLds + s], (unsigned long long)qy);
-  atomicAdd(&ls[2 * kMapLds + s], (unsigned long long)qz);
+  atomicAdd(&ls[LDS + s], (unsigned long long)qy);
+  atomicAdd(&ls[2 * LDS + s], (unsigned long long)qz);
   atomicAdd(&lc[s], n);
+  return s;
+}
+// the nine moment sums of a run into the LDS slot lds_add found (word w of slot s at lm[w * LDS + s], as ls)
+template <int LDS>
+__device__ __forceinline__ void lds_add_mom(unsigned long long *lm, unsigned s, const long long (&sm)[kMapMom]) {
+#pragma unroll
+  for (int w = 0; w < kMapMom; ++w) atomicAdd(&lm[w * LDS + s], (unsigned long long)sm[w]);
 }
 
-__global__ void __launch_bounds__(kMapThreads) k_map_insert(wc_points pts, double v, unsigned long long *keys, long long *pay,
+// MOM: the map holds moments (mom != NULL); PTS: consecutive points per lane (the plain map: kMapPts)
+template <bool MOM, int PTS>
+__global__ void __launch_bounds__(kMapThreads) k_map_insert(wc_points pts, double v, unsigned long long *keys, long long *pay, long long *mom,
                                                             unsigned long long mask, unsigned long long *ctr) {
+  // (the file-scope names, per instantiation; kMapLds: LDS hash slots - a tile's voxels fill at most half of it)
+  constexpr int kMapPts = PTS, kMapTile = kMapThreads * PTS, kMapLds = 2 * kMapTile;
   __shared__ unsigned long long lk[kMapLds];
   __shared__ unsigned long long ls[3 * kMapLds];
   __shared__ unsigned lc[kMapLds];
+  __shared__ unsigned long long lm[MOM ? kMapMom * kMapLds : 1];
   __shared__ unsigned c_fresh, c_pts, c_rej;
   const int t = threadIdx.x;
   for (int s = t; s < kMapLds; s += kMapThreads) {
     lk[s] = kMapEmpty;
     ls[s] = ls[kMapLds + s] = ls[2 * kMapLds + s] = 0;
     lc[s] = 0;
+    if constexpr (MOM) {
+#pragma unroll
+      for (int w = 0; w < kMapMom; ++w) lm[w * kMapLds + s] = 0;
+    }
   }
   if (t == 0) c_fresh = c_pts = c_rej = 0;
   unsigned fresh = 0, n_ok = 0, n_rej = 0;
@@ -146,6 +178,7 @@ __global__ void __launch_bounds__(kMapThreads) k_map_insert(wc_points pts, doubl
     // pass 1: the lane's consecutive points as runs of one voxel, each run into the LDS hash
     unsigned long long run_key = kMapEmpty;
     long long sx = 0, sy = 0, sz = 0;
+    long long sm[kMapMom] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned rn = 0;
     const uint64_t i0 = tile * kMapTile + (uint64_t)t * kMapPts;
 #pragma unroll
@@ -166,12 +199,27 @@ __global__ void __launch_bounds__(kMapThreads) k_map_insert(wc_points pts, doubl
       const long long qx = llrint((x - map_ref(kx, v)) * kMapUnit), qy = llrint((y - map_ref(ky, v)) * kMapUnit),
                       qz = llrint((z - map_ref(kz, v)) * kMapUnit);
       if (key != run_key) {
-        if (rn) lds_add(lk, ls, lc, run_key, sx, sy, sz, rn);
+        if (rn) {
+          const unsigned s = lds_add<kMapLds>(lk, ls, lc, run_key, sx, sy, sz, rn);
+          if constexpr (MOM) lds_add_mom<kMapLds>(lm, s, sm);
+        }
         run_key = key, sx = sy = sz = 0, rn = 0;
+        if constexpr (MOM) {
+#pragma unroll
+          for (int w = 0; w < kMapMom; ++w) sm[w] = 0;
+        }
       }
       sx += qx, sy += qy, sz += qz, ++rn;
+      if constexpr (MOM) {
+        const long long ux = map_u(qx), uy = map_u(qy), uz = map_u(qz);
+        sm[0] += ux, sm[1] += uy, sm[2] += uz;
+        sm[3] += ux * ux, sm[4] += ux * uy, sm[5] += ux * uz, sm[6] += uy * uy, sm[7] += uy * uz, sm[8] += uz * uz;
+      }
     }
-    if (rn) lds_add(lk, ls, lc, run_key, sx, sy, sz, rn);
+    if (rn) {
+      const unsigned s = lds_add<kMapLds>(lk, ls, lc, run_key, sx, sy, sz, rn);
+      if constexpr (MOM) lds_add_mom<kMapLds>(lm, s, sm);
+    }
     __syncthreads();
     // pass 2: one global probe and four integer atomics per distinct voxel of the tile; the LDS hash is cleared behind it
     for (int s = t; s < kMapLds; s += kMapThreads) {
@@ -184,12 +232,21 @@ __global__ void __launch_bounds__(kMapThreads) k_map_insert(wc_points pts, doubl
         atomicAdd(p + 1, ls[kMapLds + s]);
         atomicAdd(p + 2, ls[2 * kMapLds + s]);
         atomicAdd(p + 3, (unsigned long long)lc[s]);
+        if constexpr (MOM) {
+          unsigned long long *pm = (unsigned long long *)mom + kMapMom * h;
+#pragma unroll
+          for (int w = 0; w < kMapMom; ++w) atomicAdd(pm + w, lm[w * kMapLds + s]);
+        }
       } else {
         atomicAdd(ctr + kCtrLost, 1ull);
       }
       lk[s] = kMapEmpty;
       ls[s] = ls[kMapLds + s] = ls[2 * kMapLds + s] = 0;
       lc[s] = 0;
+      if constexpr (MOM) {
+#pragma unroll
+        for (int w = 0; w < kMapMom; ++w) lm[w * kMapLds + s] = 0;
+      }
     }
   }
   if (fresh) atomicAdd(&c_fresh, fresh);
@@ -221,10 +278,11 @@ __device__ __forceinline__ bool map_in_box(unsigned long long key, const map_box
 }
 
 // growth: the old table's occupied slots into the new one (empty keys, zero payload); keys are distinct, so the payload is stored plainly.
-// CROP: only the keys inside `box` move (the growth path compiles without the test)
+// CROP: only the keys inside `box` move (the growth path compiles without the test).  omom / mom: NULL for a plain map
 template <bool CROP>
-__global__ void __launch_bounds__(256) k_map_rehash(const unsigned long long *okeys, const long long *opay, uint64_t ocap,
-                                                    unsigned long long *keys, long long *pay, unsigned long long mask, map_box box) {
+__global__ void __launch_bounds__(256) k_map_rehash(const unsigned long long *okeys, const long long *opay, const long long *omom, uint64_t ocap,
+                                                    unsigned long long *keys, long long *pay, long long *mom, unsigned long long mask,
+                                                    map_box box) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ocap) return;
   const unsigned long long key = okeys[i];
@@ -237,6 +295,10 @@ __global__ void __launch_bounds__(256) k_map_rehash(const unsigned long long *ok
   longlong2 *dst = (longlong2 *)(pay + 4 * h);
   dst[0] = src[0];
   dst[1] = src[1];
+  if (omom) {  // (a WC_MAP_MOMENTS map: the nine moment words travel with the voxel)
+#pragma unroll
+    for (int w = 0; w < kMapMom; ++w) mom[kMapMom * h + w] = omom[kMapMom * i + w];
+  }
 }
 
 // export, step 1: (key, slot) of every occupied slot, staged in LDS per chunk, one atomic per workgroup for its output range
@@ -285,14 +347,108 @@ __global__ void __launch_bounds__(256) k_map_centroids(const unsigned long long 
   count[i] = (uint32_t)p[3];
 }
 
+// ---- planes (WC_MAP_MOMENTS) ----------------------------------------------------------------------------------------------------
+// a non-negative 128-bit integer rounded ONCE (to nearest, ties to even) to fp64.  The device has no library conversion for __int128:
+// the top 64 bits of the normalised value, with every bit below them folded into bit 0 (eleven places under the rounding position, so it
+// only breaks ties), go through the hardware's correctly rounded u64 conversion; the scaling by a power of two is exact
+__device__ __forceinline__ double map_u128_to_double(unsigned __int128 m) {
+  const unsigned long long hi = (unsigned long long)(m >> 64), lo = (unsigned long long)m;
+  if (hi == 0) return (double)lo;
+  const int s = __clzll((long long)hi);
+  const unsigned __int128 n = m << s;
+  const unsigned long long top = (unsigned long long)(n >> 64) | ((unsigned long long)n != 0 ? 1ull : 0ull);
+  return ldexp((double)top, 64 - s);
+}
+// what wc_map_export_surfels and wc_map_nearest_plane both say about one voxel
+struct map_plane {
+  double cov[6], ev[3], nrm[3];
+  unsigned plane;  // 1: count >= 3 and ev[2] > 0
+};
+// Population covariance of the voxel's quantised points from its count n and its nine moment words: exactly N_ab / (n^2 2^32) with the
+// integer N_ab = n M_ab - U_a U_b (|N_ab| < 2^91: formed in 128 bits).  Roundings: one of the numerator (at most 1 ulp of the result:
+// half an ulp of a number that may sit at the other end of its binade), one IEEE division by hi = fp64(n^2), and - n^2 has up to 56 bits
+// - one of the quotient corrected for n^2 = hi + lo: the division's remainder r = fma(-q, hi, num) is exact, (r - q lo) / hi is the
+// rest of num / (hi + lo) to second order.  Within 1.5 ulp plus second-order terms, under the 2 ulp the interface states; a plain
+// fp64(N) / fp64(n^2) could reach 2.5 ulp for n > 2^26.  The power of two is exact.  Then fx_eig3 (closed form, Jacobi where its
+// residual test refuses or the matrix is diagonal), and the sign rule: the normal's component of largest magnitude (the lowest axis
+// on a tie) is positive.
+__device__ __forceinline__ map_plane map_plane_of(long long count, const long long *mo) {
+  map_plane r;
+  const __int128 n = (__int128)count;
+  const unsigned long long n2 = (unsigned long long)count * (unsigned long long)count;
+  const double hi = (double)n2, lo = (double)(long long)(n2 - (unsigned long long)hi);
+  const int ia[6] = {0, 0, 0, 1, 1, 2}, ib[6] = {0, 1, 2, 1, 2, 2};
+#pragma unroll
+  for (int e = 0; e < 6; ++e) {
+    const __int128 N = n * (__int128)mo[3 + e] - (__int128)mo[ia[e]] * (__int128)mo[ib[e]];
+    const bool neg = N < 0;
+    const double mag = map_u128_to_double(neg ? (unsigned __int128)(-N) : (unsigned __int128)N);
+    const double num = neg ? -mag : mag, q = num / hi;
+    r.cov[e] = (q + (fma(-q, hi, num) - q * lo) / hi) * (1.0 / 4294967296.0);
+  }
+  wc::M3 C, V;
+  C.m[0][0] = r.cov[0], C.m[0][1] = C.m[1][0] = r.cov[1], C.m[0][2] = C.m[2][0] = r.cov[2];
+  C.m[1][1] = r.cov[3], C.m[1][2] = C.m[2][1] = r.cov[4], C.m[2][2] = r.cov[5];
+  bool closed = false;
+  fx_eig3(C, r.ev, V, &closed);
+  if (closed) {
+    // fx_eig3 accepts its closed form at a residual of 1e-12 of the scale: enough for extraction, whose clusters of > 20 points are
+    // plane-like, but a voxel of three nearly collinear points (lambda_1 << lambda_2) gets ev[0] from a cancelling sqrt(1 - x^2), some
+    // 1e-13 of the scale off.  The interface promises 32 x 2^-53: the closed form stays only where |(C - ev[0] I) n| is at rounding
+    // level, 8 x 2^-53 of the scale - an eigenvalue of a symmetric matrix lies within the residual of ev[0], and n within
+    // residual / gap of its vector; the five or so ulps of rounding in the residual itself only send more voxels to the Jacobi iteration
+    const double vx = V.m[0][0], vy = V.m[1][0], vz = V.m[2][0], e0 = r.ev[0];
+    const double rx = (r.cov[0] - e0) * vx + r.cov[1] * vy + r.cov[2] * vz, ry = r.cov[1] * vx + (r.cov[3] - e0) * vy + r.cov[4] * vz,
+                 rz = r.cov[2] * vx + r.cov[4] * vy + (r.cov[5] - e0) * vz;
+    const double tol = 8.0 * 1.1102230246251565e-16 * fmax(fabs(r.ev[0]), fabs(r.ev[2]));
+    if (!(rx * rx + ry * ry + rz * rz <= tol * tol)) wc::eig3_sym(C, r.ev, V);
+  }
+  double nx = V.m[0][0], ny = V.m[1][0], nz = V.m[2][0];
+  const double ax = fabs(nx), ay = fabs(ny), az = fabs(nz);
+  const double lead = (ax >= ay && ax >= az) ? nx : (ay >= az ? ny : nz);
+  if (lead < 0.0) nx = -nx, ny = -ny, nz = -nz;
+  r.nrm[0] = nx, r.nrm[1] = ny, r.nrm[2] = nz;
+  r.plane = (count >= 3 && r.ev[2] > 0.0) ? 1u : 0u;
+  return r;
+}
+
+// surfel export, step 3: one lane per sorted voxel (the eigen-solve is a dependent chain; the export is not a per-sweep call)
+__global__ void __launch_bounds__(256) k_map_surfels(const unsigned long long *skeys, const uint32_t *sslots, uint64_t n, const long long *pay,
+                                                     const long long *mom, double v, wc_map_surfel *out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long key = skeys[i];
+  const uint64_t slot = sslots[i];
+  const long long *p = pay + 4 * slot;
+  const double c = (double)p[3];
+  const map_plane pl = map_plane_of(p[3], mom + kMapMom * slot);
+  wc_map_surfel r;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const int k = map_unpack(key, a);
+    r.key[a] = k;
+    r.xyz[a] = map_centroid(k, v, p[a], c);
+    r.ev[a] = pl.ev[a];
+    r.normal[a] = pl.nrm[a];
+  }
+  r.count = (uint32_t)p[3];
+  r.flags = pl.plane;
+#pragma unroll
+  for (int e = 0; e < 6; ++e) r.cov[e] = pl.cov[e];
+  out[i] = r;
+}
+
 // query: the nearest of the occupied voxels with index kq + {-1, 0, 1}^3 (kq = the query's own voxel), by the fp64 distance to the float
 // centroid wc_map_export returns.  One lane per query.  The 27 neighbours are visited in ascending key order (x outermost) and a later
 // one wins only on a strictly smaller distance: ties go to the smaller key.  Each x plane's nine first-slot key loads are issued together
 // before any is looked at; a lane then follows the probe chain (read-only) of whatever is not settled by its first slot, and loads the
 // 32-byte payload of the occupied ones only.  Every loop below is fully unrolled: all indices are compile-time constants, no scratch.
+// PLANE (wc_map_nearest_plane): the record is a wc_map_plane_hit - the same 40 bytes, then the winning voxel's plane from map_plane_of,
+// run once per query behind the search - and `hits` points at those records; mom and min_points are unused otherwise
+template <bool PLANE>
 __global__ void __launch_bounds__(kNearThreads) k_map_nearest(wc_points q, double v, double max_d2, const unsigned long long *keys,
-                                                              const long long *pay, unsigned long long mask, wc_map_hit *hits,
-                                                              unsigned long long *found) {
+                                                              const long long *pay, unsigned long long mask, void *hits,
+                                                              unsigned long long *found, const long long *mom, unsigned min_points) {
   __shared__ unsigned s_found[kNearThreads / 64];
   unsigned n_found = 0;
   const uint64_t stride = (uint64_t)gridDim.x * kNearThreads;
@@ -306,6 +462,7 @@ __global__ void __launch_bounds__(kNearThreads) k_map_nearest(wc_points q, doubl
     float bx = 0.f, by = 0.f, bz = 0.f;
     unsigned bc = 0;
     int bkx = 0, bky = 0, bkz = 0;
+    unsigned long long bh = 0;  // (PLANE: the winner's slot)
 #pragma unroll
     for (int dx = -1; dx <= 1; ++dx) {
       unsigned long long key[9], h[9], cur[9];
@@ -334,17 +491,35 @@ __global__ void __launch_bounds__(kNearThreads) k_map_nearest(wc_points q, doubl
         const float cx = map_centroid(nx, v, p0.x, cnt), cy = map_centroid(ny, v, p0.y, cnt), cz = map_centroid(nz, v, p1.x, cnt);
         const double ex = x - (double)cx, ey = y - (double)cy, ez = z - (double)cz;
         const double d2 = (ex * ex + ey * ey) + ez * ez;
-        if (d2 < best) best = d2, bx = cx, by = cy, bz = cz, bc = (unsigned)p1.y, bkx = nx, bky = ny, bkz = nz;
+        if (d2 < best) {
+          best = d2, bx = cx, by = cy, bz = cz, bc = (unsigned)p1.y, bkx = nx, bky = ny, bkz = nz;
+          if constexpr (PLANE) bh = hj;
+        }
       }
     }
     const bool hit = bc != 0 && best <= max_d2;
     n_found += hit ? 1u : 0u;
     // the 40-byte record as five 8-byte stores (the record is 8-aligned)
-    uint2 *o = (uint2 *)(hits + i);
+    uint2 *o = (uint2 *)((char *)hits + i * (PLANE ? sizeof(wc_map_plane_hit) : sizeof(wc_map_hit)));
+    unsigned flags = ok ? 0u : 1u;
+    if constexpr (PLANE) {
+      double pn[3] = {0.0, 0.0, 0.0}, sigma2 = 0.0, dist = 0.0;
+      if (hit && bc >= min_points) {
+        const map_plane pl = map_plane_of((long long)bc, mom + kMapMom * bh);
+        if (pl.plane) {
+          const double ex = x - (double)bx, ey = y - (double)by, ez = z - (double)bz;  // (as in d2)
+          pn[0] = pl.nrm[0], pn[1] = pl.nrm[1], pn[2] = pl.nrm[2], sigma2 = pl.ev[0];
+          dist = (pn[0] * ex + pn[1] * ey) + pn[2] * ez;
+          flags |= 2u;
+        }
+      }
+      double *od = (double *)o;
+      od[5] = pn[0], od[6] = pn[1], od[7] = pn[2], od[8] = sigma2, od[9] = dist;
+    }
     o[0] = hit ? make_uint2(__float_as_uint(bx), __float_as_uint(by)) : make_uint2(0u, 0u);
     o[1] = hit ? make_uint2(__float_as_uint(bz), bc) : make_uint2(0u, 0u);
     o[2] = hit ? make_uint2((unsigned)bkx, (unsigned)bky) : make_uint2(0u, 0u);
-    o[3] = make_uint2(hit ? (unsigned)bkz : 0u, ok ? 0u : 1u);
+    o[3] = make_uint2(hit ? (unsigned)bkz : 0u, flags);
     ((double *)o)[4] = hit ? best : __builtin_inf();
   }
   // the found count: per wavefront, per workgroup, then one atomic on the counter's own line
@@ -407,9 +582,18 @@ uint64_t pow2_at_least(uint64_t x) {
   return c;
 }
 // a fresh table of `cap` slots (empty keys, zero payload), enqueued on the ctx stream
-int map_table(wc_ctx *ctx, uint64_t cap, unsigned long long **keys, long long **pay) {
+// (moments: the nine extra words per slot of a WC_MAP_MOMENTS map, zero; *mom = NULL otherwise)
+int map_table(wc_ctx *ctx, uint64_t cap, bool moments, unsigned long long **keys, long long **pay, long long **mom) {
+  *mom = nullptr;
   WC_TRY(map_alloc(ctx, (void **)keys, cap * 8));
   int rc = map_alloc(ctx, (void **)pay, cap * 32);
+  if (rc == WC_OK && moments) {
+    rc = map_alloc(ctx, (void **)mom, cap * 8 * kMapMom);
+    if (rc != WC_OK) {
+      map_free(ctx, *pay);
+      *pay = nullptr;
+    }
+  }
   if (rc != WC_OK) {
     map_free(ctx, *keys);
     *keys = nullptr;
@@ -417,6 +601,7 @@ int map_table(wc_ctx *ctx, uint64_t cap, unsigned long long **keys, long long **
   }
   WC_HIP(ctx, hipMemsetAsync(*keys, 0xFF, cap * 8, ctx->stream));
   WC_HIP(ctx, hipMemsetAsync(*pay, 0, cap * 32, ctx->stream));
+  if (moments) WC_HIP(ctx, hipMemsetAsync(*mom, 0, cap * 8 * kMapMom, ctx->stream));
   return WC_OK;
 }
 // the occupied-slot bound of the growth policy; takes a completed read-back into account without waiting for one
@@ -442,16 +627,22 @@ bool map_ok(const wc_ctx *ctx, const wc_map *m) { return ctx && m && m->ctx == c
 }  // namespace
 
 extern "C" int wc_map_create(wc_ctx *ctx, double voxel, uint64_t reserve_voxels, wc_map **out) {
+  return wc_map_create_ex(ctx, voxel, reserve_voxels, 0u, out);
+}
+
+extern "C" int wc_map_create_ex(wc_ctx *ctx, double voxel, uint64_t reserve_voxels, uint32_t flags, wc_map **out) {
   wc_dev_guard dg_(ctx);
-  if (!ctx || !out || !(voxel >= 0.01 && voxel <= 4.0) || reserve_voxels > ((uint64_t)1 << 31))
-    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (0.01 <= voxel <= 4.0, reserve_voxels <= 2^31)", __func__);
+  if (!ctx || !out || !(voxel >= 0.01 && voxel <= 4.0) || reserve_voxels > ((uint64_t)1 << 31) || (flags & ~(uint32_t)WC_MAP_MOMENTS))
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (0.01 <= voxel <= 4.0, reserve_voxels <= 2^31, flags: WC_MAP_MOMENTS)",
+                   __func__);
   *out = nullptr;
   wc_map *m = new wc_map;
   m->ctx = ctx;
   m->voxel = voxel;
+  m->flags = flags;
   m->cap = pow2_at_least(2 * (reserve_voxels ? reserve_voxels : 1));
   if (hipDeviceGetAttribute(&m->cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || m->cus <= 0) m->cus = 256;
-  int rc = map_table(ctx, m->cap, &m->keys, &m->pay);
+  int rc = map_table(ctx, m->cap, (flags & WC_MAP_MOMENTS) != 0, &m->keys, &m->pay, &m->mom);
   if (rc == WC_OK) rc = map_alloc(ctx, (void **)&m->ctr, kCtrWords * 8);
   if (rc == WC_OK && hipMemsetAsync(m->ctr, 0, kCtrWords * 8, ctx->stream) != hipSuccess) rc = wc_fail(ctx, WC_ERR_HIP, "wc_map_create: memset");
   if (rc == WC_OK && hipHostMalloc((void **)&m->h_ctr, kCtrWords * 8) != hipSuccess) rc = wc_fail(ctx, WC_ERR_HIP, "wc_map_create: pinned counters");
@@ -472,6 +663,7 @@ extern "C" int wc_map_destroy(wc_ctx *ctx, wc_map *m) {
   if (!map_ok(ctx, m)) return wc_fail(ctx, WC_ERR_ARG, "%s: the map belongs to another context", __func__);
   map_free(ctx, m->keys);
   map_free(ctx, m->pay);
+  map_free(ctx, m->mom);
   map_free(ctx, m->ctr);
   for (wc_buf &b : m->b_pairs) wc_buf_release(ctx, b);
   wc_buf_release(ctx, m->b_tmp);
@@ -495,19 +687,31 @@ extern "C" int wc_map_insert(wc_ctx *ctx, wc_map *m, const wc_points *pts, uint6
     const uint64_t cap = pow2_at_least(need);
     if (cap > ((uint64_t)1 << 32)) return wc_fail(ctx, WC_ERR_CAPACITY, "%s: the table would exceed 2^32 slots", __func__);
     unsigned long long *keys = nullptr;
-    long long *pay = nullptr;
-    WC_TRY(map_table(ctx, cap, &keys, &pay));
-    k_map_rehash<false><<<(unsigned)((m->cap + 255) / 256), 256, 0, ctx->stream>>>(m->keys, m->pay, m->cap, keys, pay, cap - 1, map_box{});
+    long long *pay = nullptr, *mom = nullptr;
+    WC_TRY(map_table(ctx, cap, m->mom != nullptr, &keys, &pay, &mom));
+    k_map_rehash<false><<<(unsigned)((m->cap + 255) / 256), 256, 0, ctx->stream>>>(m->keys, m->pay, m->mom, m->cap, keys, pay, mom, cap - 1,
+                                                                                   map_box{});
     WC_HIP(ctx, hipGetLastError());
     map_free(ctx, m->keys);
     map_free(ctx, m->pay);
-    m->keys = keys, m->pay = pay, m->cap = cap;
+    map_free(ctx, m->mom);
+    m->keys = keys, m->pay = pay, m->mom = mom, m->cap = cap;
     ++m->growths;
   }
   WC_HIP(ctx, hipMemsetAsync(m->ctr + kCtrRejCall, 0, 8, ctx->stream));
-  const uint64_t tiles = (pts->n + kMapTile - 1) / kMapTile;
-  const unsigned grid = (unsigned)std::min<uint64_t>(tiles, (uint64_t)4 * m->cus);
-  k_map_insert<<<grid, kMapThreads, 0, ctx->stream>>>(*pts, m->voxel, m->keys, m->pay, m->cap - 1, m->ctr);
+  if (!m->mom) {
+    const uint64_t tiles = (pts->n + kMapTile - 1) / kMapTile;
+    const unsigned grid = (unsigned)std::min<uint64_t>(tiles, (uint64_t)4 * m->cus);
+    k_map_insert<false, kMapPts><<<grid, kMapThreads, 0, ctx->stream>>>(*pts, m->voxel, m->keys, m->pay, nullptr, m->cap - 1, m->ctr);
+  } else if (ctx->dev.map_mom_pts == 2) {  // (development option: the plain insert's tile, 108 KB of LDS, one workgroup per CU)
+    const uint64_t tiles = (pts->n + kMapTile - 1) / kMapTile;
+    const unsigned grid = (unsigned)std::min<uint64_t>(tiles, (uint64_t)4 * m->cus);
+    k_map_insert<true, kMapPts><<<grid, kMapThreads, 0, ctx->stream>>>(*pts, m->voxel, m->keys, m->pay, m->mom, m->cap - 1, m->ctr);
+  } else {
+    const uint64_t tiles = (pts->n + kMapThreads * kMapMomPts - 1) / (kMapThreads * kMapMomPts);
+    const unsigned grid = (unsigned)std::min<uint64_t>(tiles, (uint64_t)4 * m->cus);
+    k_map_insert<true, kMapMomPts><<<grid, kMapThreads, 0, ctx->stream>>>(*pts, m->voxel, m->keys, m->pay, m->mom, m->cap - 1, m->ctr);
+  }
   WC_HIP(ctx, hipGetLastError());
   m->pts_since += pts->n;
   if (h_n_rejected) {
@@ -543,19 +747,13 @@ extern "C" int wc_map_info(wc_ctx *ctx, wc_map *m, uint64_t h_info[4]) {
   h_info[0] = m->cap;
   h_info[1] = m->growths;
   h_info[2] = m->h_ctr[kCtrRej];
-  h_info[3] = m->cap * 40;
+  h_info[3] = m->cap * (m->mom ? 40 + 8 * kMapMom : 40);
   return WC_OK;
 }
 
-extern "C" int wc_map_export(wc_ctx *ctx, wc_map *m, float *d_xyz, uint32_t *d_count, int32_t *d_keys, uint64_t cap, uint64_t *h_n) {
-  wc_dev_guard dg_(ctx);
-  if (!map_ok(ctx, m) || !h_n) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
-  WC_TRY(map_sync_counters(ctx, m));  // (the size read-back)
-  const uint64_t n = m->h_ctr[kCtrOcc];
-  *h_n = n;
-  if (n == 0) return WC_OK;
-  if (cap < n) return wc_fail(ctx, WC_ERR_CAPACITY, "%s: %llu voxels, capacity %llu", __func__, (unsigned long long)n, (unsigned long long)cap);
-  if (!d_xyz || !d_count) return wc_fail(ctx, WC_ERR_ARG, "%s: null output", __func__);
+namespace {
+// export, steps 1 and 2: the n occupied slots as (key, slot) pairs in ascending key order, in the map's scratch
+int map_sorted_slots(wc_ctx *ctx, wc_map *m, uint64_t n, unsigned long long **skeys, uint32_t **sslots) {
   WC_TRY(wc_ensure(ctx, m->b_pairs[0], n * 8));
   WC_TRY(wc_ensure(ctx, m->b_pairs[1], n * 8));
   WC_TRY(wc_ensure(ctx, m->b_pairs[2], n * 4));
@@ -574,7 +772,42 @@ extern "C" int wc_map_export(wc_ctx *ctx, wc_map *m, float *d_xyz, uint32_t *d_c
   WC_TRY(wc_ensure(ctx, m->b_tmp, tmp));
   tmp = m->b_tmp.cap;
   WC_HIP(ctx, rocprim::radix_sort_pairs<cfg>(m->b_tmp.p, tmp, kin, kout, vin, vout, (size_t)n, 0u, 63u, ctx->stream));
+  *skeys = kout, *sslots = vout;
+  return WC_OK;
+}
+}  // namespace
+
+extern "C" int wc_map_export(wc_ctx *ctx, wc_map *m, float *d_xyz, uint32_t *d_count, int32_t *d_keys, uint64_t cap, uint64_t *h_n) {
+  wc_dev_guard dg_(ctx);
+  if (!map_ok(ctx, m) || !h_n) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
+  WC_TRY(map_sync_counters(ctx, m));  // (the size read-back)
+  const uint64_t n = m->h_ctr[kCtrOcc];
+  *h_n = n;
+  if (n == 0) return WC_OK;
+  if (cap < n) return wc_fail(ctx, WC_ERR_CAPACITY, "%s: %llu voxels, capacity %llu", __func__, (unsigned long long)n, (unsigned long long)cap);
+  if (!d_xyz || !d_count) return wc_fail(ctx, WC_ERR_ARG, "%s: null output", __func__);
+  unsigned long long *kout = nullptr;
+  uint32_t *vout = nullptr;
+  WC_TRY(map_sorted_slots(ctx, m, n, &kout, &vout));
   k_map_centroids<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(kout, vout, n, m->pay, m->voxel, d_xyz, d_count, d_keys);
+  WC_HIP(ctx, hipGetLastError());
+  return WC_OK;
+}
+
+extern "C" int wc_map_export_surfels(wc_ctx *ctx, wc_map *m, wc_map_surfel *d_out, uint64_t cap, uint64_t *h_n) {
+  wc_dev_guard dg_(ctx);
+  if (!map_ok(ctx, m) || !h_n || !m->mom)
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null argument, or a map created without WC_MAP_MOMENTS", __func__);
+  WC_TRY(map_sync_counters(ctx, m));  // (the size read-back)
+  const uint64_t n = m->h_ctr[kCtrOcc];
+  *h_n = n;
+  if (n == 0) return WC_OK;
+  if (cap < n) return wc_fail(ctx, WC_ERR_CAPACITY, "%s: %llu voxels, capacity %llu", __func__, (unsigned long long)n, (unsigned long long)cap);
+  if (!d_out || (uintptr_t)d_out % 8) return wc_fail(ctx, WC_ERR_ARG, "%s: null or misaligned output", __func__);
+  unsigned long long *kout = nullptr;
+  uint32_t *vout = nullptr;
+  WC_TRY(map_sorted_slots(ctx, m, n, &kout, &vout));
+  k_map_surfels<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(kout, vout, n, m->pay, m->mom, m->voxel, d_out);
   WC_HIP(ctx, hipGetLastError());
   return WC_OK;
 }
@@ -584,6 +817,7 @@ extern "C" int wc_map_clear(wc_ctx *ctx, wc_map *m) {
   if (!map_ok(ctx, m)) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
   WC_HIP(ctx, hipMemsetAsync(m->keys, 0xFF, m->cap * 8, ctx->stream));
   WC_HIP(ctx, hipMemsetAsync(m->pay, 0, m->cap * 32, ctx->stream));
+  if (m->mom) WC_HIP(ctx, hipMemsetAsync(m->mom, 0, m->cap * 8 * kMapMom, ctx->stream));
   WC_HIP(ctx, hipMemsetAsync(m->ctr, 0, kCtrWords * 8, ctx->stream));
   WC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (a pending counter copy lands before the host's bookkeeping is reset)
   m->occ_known = m->pts_since = m->pts_after_copy = 0;
@@ -592,19 +826,27 @@ extern "C" int wc_map_clear(wc_ctx *ctx, wc_map *m) {
   return WC_OK;
 }
 
-extern "C" int wc_map_nearest(wc_ctx *ctx, wc_map *m, const wc_points *queries, double max_dist, wc_map_hit *d_hits, uint64_t *h_n_found) {
+namespace {
+// wc_map_nearest (min_points = 0: wc_map_hit records) and wc_map_nearest_plane (min_points >= 3: wc_map_plane_hit records)
+int map_nearest(wc_ctx *ctx, wc_map *m, const wc_points *queries, double max_dist, unsigned min_points, void *d_hits, uint64_t *h_n_found,
+                const char *fn) {
   wc_dev_guard dg_(ctx);
   const wc_points *q = queries;
   if (!map_ok(ctx, m) || !q || !(max_dist > 0.0) ||
       (q->n && (!d_hits || (uintptr_t)d_hits % 8 || !q->xyz || q->xyz_stride < 12 || q->xyz_stride % 4 || (uintptr_t)q->xyz % 4)))
-    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (max_dist > 0)", __func__);
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (max_dist > 0)", fn);
   if (h_n_found) *h_n_found = 0;
   if (q->n == 0) return WC_OK;
   const double max_d2 = max_dist * max_dist;  // (formed once, here: the kernel accepts d2 <= max_d2)
   if (h_n_found) WC_HIP(ctx, hipMemsetAsync(m->ctr + kCtrFound, 0, 8, ctx->stream));
   const uint64_t blocks = (q->n + kNearThreads - 1) / kNearThreads;
   const unsigned grid = (unsigned)std::min<uint64_t>(blocks, (uint64_t)8 * m->cus);
-  k_map_nearest<<<grid, kNearThreads, 0, ctx->stream>>>(*q, m->voxel, max_d2, m->keys, m->pay, m->cap - 1, d_hits, m->ctr + kCtrFound);
+  if (min_points)
+    k_map_nearest<true><<<grid, kNearThreads, 0, ctx->stream>>>(*q, m->voxel, max_d2, m->keys, m->pay, m->cap - 1, d_hits, m->ctr + kCtrFound,
+                                                                m->mom, min_points);
+  else
+    k_map_nearest<false><<<grid, kNearThreads, 0, ctx->stream>>>(*q, m->voxel, max_d2, m->keys, m->pay, m->cap - 1, d_hits, m->ctr + kCtrFound,
+                                                                 nullptr, 0u);
   WC_HIP(ctx, hipGetLastError());
   if (h_n_found) {
     WC_HIP(ctx, hipMemcpyAsync(m->h_ctr + kCtrFound, m->ctr + kCtrFound, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -612,6 +854,20 @@ extern "C" int wc_map_nearest(wc_ctx *ctx, wc_map *m, const wc_points *queries, 
     *h_n_found = m->h_ctr[kCtrFound];
   }
   return WC_OK;
+}
+}  // namespace
+
+extern "C" int wc_map_nearest(wc_ctx *ctx, wc_map *m, const wc_points *queries, double max_dist, wc_map_hit *d_hits, uint64_t *h_n_found) {
+  return map_nearest(ctx, m, queries, max_dist, 0u, d_hits, h_n_found, __func__);
+}
+
+extern "C" int wc_map_nearest_plane(wc_ctx *ctx, wc_map *m, const wc_points *queries, double max_dist, uint32_t min_points,
+                                    wc_map_plane_hit *d_hits, uint64_t *h_n_found) {
+  if (map_ok(ctx, m) && (!m->mom || min_points < 3)) {
+    wc_dev_guard dg_(ctx);
+    return wc_fail(ctx, WC_ERR_ARG, "%s: a map created without WC_MAP_MOMENTS, or min_points < 3", __func__);
+  }
+  return map_nearest(ctx, m, queries, max_dist, min_points, d_hits, h_n_found, __func__);
 }
 
 extern "C" int wc_map_crop(wc_ctx *ctx, wc_map *m, const double lo[3], const double hi[3], uint64_t *h_removed_voxels) {
@@ -634,13 +890,14 @@ extern "C" int wc_map_crop(wc_ctx *ctx, wc_map *m, const double lo[3], const dou
   const uint64_t cap = pow2_at_least(2 * std::max<uint64_t>(kept, 1));
   if (kept != occ || cap != m->cap) {  // (otherwise the table already is what the crop would build)
     unsigned long long *keys = nullptr;
-    long long *pay = nullptr;
-    WC_TRY(map_table(ctx, cap, &keys, &pay));
-    k_map_rehash<true><<<(unsigned)((m->cap + 255) / 256), 256, 0, ctx->stream>>>(m->keys, m->pay, m->cap, keys, pay, cap - 1, box);
+    long long *pay = nullptr, *mom = nullptr;
+    WC_TRY(map_table(ctx, cap, m->mom != nullptr, &keys, &pay, &mom));
+    k_map_rehash<true><<<(unsigned)((m->cap + 255) / 256), 256, 0, ctx->stream>>>(m->keys, m->pay, m->mom, m->cap, keys, pay, mom, cap - 1, box);
     WC_HIP(ctx, hipGetLastError());
     map_free(ctx, m->keys);
     map_free(ctx, m->pay);
-    m->keys = keys, m->pay = pay, m->cap = cap;
+    map_free(ctx, m->mom);
+    m->keys = keys, m->pay = pay, m->mom = mom, m->cap = cap;
     // the occupied-voxel and point counters become those of the kept voxels; rejected and growth counters stay
     WC_HIP(ctx, hipMemcpyAsync(m->ctr + kCtrOcc, m->ctr + kCtrKeepVox, 8, hipMemcpyDeviceToDevice, ctx->stream));
     WC_HIP(ctx, hipMemcpyAsync(m->ctr + kCtrPts, m->ctr + kCtrKeepPts, 8, hipMemcpyDeviceToDevice, ctx->stream));

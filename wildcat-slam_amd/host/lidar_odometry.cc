@@ -431,12 +431,51 @@ bool LidarOdometry::SetMapVoxel(double voxel) {
 // the map follows config().map_voxel_size: created on first use, re-created (empty) when the size changed, removed at 0
 void LidarOdometry::EnsureMap() {
   const double v = config_.map_voxel_size;
-  if (map_ && map_voxel_ == v) return;
+  if (map_ && map_voxel_ == v && map_moments_ == config_.map_surfels) return;
   if (map_) WC_CALL(wc_map_destroy(ctx_, map_));
   map_ = nullptr;
   if (v == 0.0) return;
-  WC_CALL(wc_map_create(ctx_, v, (size_t)1 << 20, &map_));
+  WC_CALL(wc_map_create_ex(ctx_, v, (size_t)1 << 20, config_.map_surfels ? WC_MAP_MOMENTS : 0u, &map_));
   map_voxel_ = v;
+  map_moments_ = config_.map_surfels;
+}
+void LidarOdometry::SetMapSurfels(bool on) {
+  config_.map_surfels = on;
+  if (map_) WC_CALL(wc_map_destroy(ctx_, map_));
+  map_ = nullptr;
+  EnsureMap();
+}
+size_t LidarOdometry::ExportMapSurfels(wc_map_surfel *surfels, size_t cap) {
+  if (!map_ || !map_moments_) return 0;
+  uint64_t n = map_voxels();
+  if (n == 0 || cap < n || !surfels) return n;
+  void *d_out = nullptr;
+  WC_CALL(wc_dev_alloc(ctx_, n * sizeof(wc_map_surfel), &d_out));
+  WC_CALL(wc_map_export_surfels(ctx_, map_, (wc_map_surfel *)d_out, n, &n));
+  WC_CALL(wc_d2h(ctx_, surfels, d_out, n * sizeof(wc_map_surfel)));
+  WC_CALL(wc_dev_free(ctx_, d_out));
+  return n;
+}
+size_t LidarOdometry::QueryMapPlanes(const float *xyz, size_t n, double max_dist, uint32_t min_points, wc_map_plane_hit *hits) {
+  if (!n || !xyz || !hits) return 0;
+  if (!map_ || !map_moments_ || min_points < 3) {
+    for (size_t i = 0; i < n; ++i) {
+      std::memset(&hits[i], 0, sizeof(wc_map_plane_hit));
+      hits[i].hit.d2 = std::numeric_limits<double>::infinity();
+    }
+    return 0;
+  }
+  void *d_xyz = nullptr, *d_hits = nullptr;
+  WC_CALL(wc_dev_alloc(ctx_, n * 3 * sizeof(float), &d_xyz));
+  WC_CALL(wc_dev_alloc(ctx_, n * sizeof(wc_map_plane_hit), &d_hits));
+  WC_CALL(wc_h2d(ctx_, d_xyz, xyz, n * 3 * sizeof(float)));
+  const wc_points desc{d_xyz, nullptr, 12, 0, n};
+  uint64_t found = 0;
+  WC_CALL(wc_map_nearest_plane(ctx_, map_, &desc, max_dist, min_points, (wc_map_plane_hit *)d_hits, &found));
+  WC_CALL(wc_d2h(ctx_, hits, d_hits, n * sizeof(wc_map_plane_hit)));
+  WC_CALL(wc_dev_free(ctx_, d_xyz));
+  WC_CALL(wc_dev_free(ctx_, d_hits));
+  return found;
 }
 uint64_t LidarOdometry::map_voxels() const {
   uint64_t v = 0;

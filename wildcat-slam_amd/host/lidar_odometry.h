@@ -92,6 +92,14 @@ class LidarOdometry {
   size_t QueryMap(const float *xyz, size_t n, double max_dist, wc_map_hit *hits);
   // drops the voxels that do not intersect the box [lo, hi] and compacts the table (wc_map_crop); returns the voxels removed
   size_t CropMap(const double lo[3], const double hi[3]);
+  // config().map_surfels = on, the map re-created empty (as SetMapVoxel does)
+  void SetMapSurfels(bool on);
+  // the map's voxels as wc_map_export_surfels writes them (the order and number of ExportMap); returns the number of voxels, nothing
+  // written when cap is too small.  Without a map, or with map_surfels off: 0
+  size_t ExportMapSurfels(wc_map_surfel *surfels, size_t cap);
+  // wc_map_nearest_plane for n host points (xyz: n x 3 floats): hits[n]; returns the number of voxels found (as QueryMap).  Without a
+  // map, with map_surfels off or min_points < 3: 0, every hit a miss
+  size_t QueryMapPlanes(const float *xyz, size_t n, double max_dist, uint32_t min_points, wc_map_plane_hit *hits);
   bool SetMapKeepRadius(double radius);  // config().map_keep_radius = radius; false: negative or NaN
   // wall time [ms] of the last completed sweep's map step (the undistortion when fill_outputs does not already form it, the insert's
   // enqueue - its kernel runs behind on the stream - and, with map_keep_radius, the crop, which waits).  Not part of last_stage_ms()
@@ -173,6 +181,7 @@ class LidarOdometry {
   size_t cap_world_ = 0;
   wc_map *map_ = nullptr;
   double map_voxel_ = 0.0;  // voxel size map_ was created with
+  bool map_moments_ = false;  // ... and whether with WC_MAP_MOMENTS
   double last_map_ms_ = 0.0;
   std::string residual_log_;
   void *d_res_ = nullptr;

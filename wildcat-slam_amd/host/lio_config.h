@@ -48,4 +48,7 @@ struct LioConfig {
   // last_outputs()), that the map is cropped to after every sweep's insert (wc_map_crop: the voxels outside are dropped and the table
   // is compacted).  0 (default) = the map is unbounded and nothing extra is launched.  Needs map_voxel_size > 0
   double map_keep_radius = 0.0;
+  // the map also accumulates every voxel's second moments (wc_map_create_ex, WC_MAP_MOMENTS): ExportMapSurfels and QueryMapPlanes answer
+  // with the plane through a voxel's points.  false (default) = the plain map: nothing more allocated or launched.  Needs map_voxel_size > 0
+  bool map_surfels = false;
 };

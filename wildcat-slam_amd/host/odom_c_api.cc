@@ -209,6 +209,15 @@ uint64_t wc_odom_map_query(void *h, const float *xyz, uint64_t n, double max_dis
 }
 // keeps the voxels that intersect the box [lo, hi]; returns the voxels removed
 uint64_t wc_odom_map_crop(void *h, const double lo[3], const double hi[3]) { return ((LidarOdometry *)h)->CropMap(lo, hi); }
+// LioConfig::map_surfels: the map re-created empty, with (1) or without (0) second moments
+void wc_odom_set_map_surfels(void *h, int on) { ((LidarOdometry *)h)->SetMapSurfels(on != 0); }
+int wc_odom_map_surfels_on(void *h) { return ((LidarOdometry *)h)->config().map_surfels ? 1 : 0; }
+// the map's voxels as wc_map_surfel records (wc_map_export_surfels); returns the number of voxels (nothing written when cap is smaller)
+uint64_t wc_odom_map_surfels(void *h, wc_map_surfel *surfels, uint64_t cap) { return ((LidarOdometry *)h)->ExportMapSurfels(surfels, cap); }
+// wc_map_nearest_plane for n host points (n x 3 floats) -> hits[n] (wc_map_plane_hit); returns the number of voxels found
+uint64_t wc_odom_map_query_planes(void *h, const float *xyz, uint64_t n, double max_dist, uint32_t min_points, wc_map_plane_hit *hits) {
+  return ((LidarOdometry *)h)->QueryMapPlanes(xyz, n, max_dist, min_points, hits);
+}
 // LioConfig::map_keep_radius: 0 = unbounded map; returns 0, or WC_ERR_ARG for a negative or NaN radius
 int wc_odom_set_map_keep_radius(void *h, double radius) { return ((LidarOdometry *)h)->SetMapKeepRadius(radius) ? 0 : WC_ERR_ARG; }
 // Cloud2FromXyz (host/wire_formats.h): the field table (3 x {offset, datatype, count}), point_step and the payload of n points

@@ -191,9 +191,10 @@ class Context:
         self._ck(self.lib.wc_timer_stop_ms(self.h, C.byref(ms)))
         return ms.value
 
-    def map_create(self, voxel, reserve_voxels=0):
-        """a voxel-downsampled point map in HBM (wc_map_create); close() it before the context"""
-        return PointMap(self, voxel, reserve_voxels)
+    def map_create(self, voxel, reserve_voxels=0, moments=False):
+        """a voxel-downsampled point map in HBM (wc_map_create_ex; moments: WC_MAP_MOMENTS, for surfels() and nearest_plane()); close()
+        it before the context"""
+        return PointMap(self, voxel, reserve_voxels, moments)
 
     # ---- extraction ---------------------------------------------------------------------------------------------
     def points_desc(self, d_points, n):
@@ -590,10 +591,11 @@ class Context:
 class PointMap:
     """wc_map: the device-resident voxel-downsampled map (DownSamplingVoxel, surfel_extraction.cc:228-261, over every insert)"""
 
-    def __init__(self, ctx, voxel, reserve_voxels=0):
-        self.ctx, self.lib, self.voxel = ctx, ctx.lib, float(voxel)
+    def __init__(self, ctx, voxel, reserve_voxels=0, moments=False):
+        self.ctx, self.lib, self.voxel, self.moments = ctx, ctx.lib, float(voxel), bool(moments)
         h = C.c_void_p(0)
-        ctx._ck(self.lib.wc_map_create(ctx.h, C.c_double(voxel), C.c_uint64(int(reserve_voxels)), C.byref(h)))
+        flags = C.c_uint32(R.MAP_MOMENTS if moments else 0)
+        ctx._ck(self.lib.wc_map_create_ex(ctx.h, C.c_double(voxel), C.c_uint64(int(reserve_voxels)), flags, C.byref(h)))
         self.h = h
 
     def insert_device(self, desc):
@@ -683,6 +685,47 @@ class PointMap:
         finally:
             for b in (bx, bc, bk):
                 b.free()
+
+    def surfels_device(self, d_out, cap):
+        """MAP_SURFEL records into d_out (wc_map_export_surfels) -> (return code, n): WC_ERR_CAPACITY leaves the needed count in n"""
+        n = C.c_uint64(0)
+        rc = self.lib.wc_map_export_surfels(self.ctx.h, self.h, C.c_void_p(d_out.ptr if d_out else 0), C.c_uint64(int(cap)), C.byref(n))
+        return rc, int(n.value)
+
+    def surfels(self):
+        """-> MAP_SURFEL array: one record per occupied voxel, in export()'s order (a map created with moments=True)"""
+        rc, n = self.surfels_device(None, 0)
+        if n == 0:
+            self.ctx._ck(rc)
+            return np.zeros(0, R.MAP_SURFEL)
+        d_out = self.ctx.alloc(R.MAP_SURFEL.itemsize * n)
+        try:
+            rc, m = self.surfels_device(d_out, n)
+            self.ctx._ck(rc)
+            return d_out.download(R.MAP_SURFEL, m)
+        finally:
+            d_out.free()
+
+    def nearest_plane_device(self, desc, max_dist, min_points, d_hits, want_count=True):
+        """queries already in HBM (a wc_points descriptor) -> MAP_PLANE_HIT records in d_hits (wc_map_nearest_plane); returns the number
+        of voxels found, or None without waiting when want_count is False"""
+        n = C.c_uint64(0)
+        self.ctx._ck(self.lib.wc_map_nearest_plane(self.ctx.h, self.h, C.byref(desc), C.c_double(max_dist), C.c_uint32(int(min_points)),
+                                                   C.c_void_p(d_hits.ptr if d_hits else 0), C.byref(n) if want_count else None))
+        return int(n.value) if want_count else None
+
+    def nearest_plane(self, queries, max_dist=np.inf, min_points=3):
+        """POINT records or an (n, 3) float32 array (uploaded for the call) -> MAP_PLANE_HIT array: nearest()'s record per query, and
+        the plane of the voxel found (flags bit 1) where it holds at least min_points points"""
+        d, desc = self._upload(queries)
+        d_hits = self.ctx.alloc(R.MAP_PLANE_HIT.itemsize * max(desc.n, 1))
+        try:
+            self.nearest_plane_device(desc, max_dist, min_points, d_hits)
+            return d_hits.download(R.MAP_PLANE_HIT, desc.n)
+        finally:
+            d_hits.free()
+            if d:
+                d.free()
 
     def clear(self):
         self.ctx._ck(self.lib.wc_map_clear(self.ctx.h, self.h))
@@ -793,6 +836,29 @@ class Odometry:
             raise WildcatError(11, "map_crop: NaN bound or lo > hi")
         self.lib.wc_odom_map_crop.restype = C.c_uint64
         return int(self.lib.wc_odom_map_crop(self.h, (C.c_double * 3)(*lo), (C.c_double * 3)(*hi)))
+
+    def set_map_surfels(self, on):
+        """LioConfig::map_surfels: the map re-created empty, with (True) or without second moments"""
+        self.lib.wc_odom_set_map_surfels(self.h, C.c_int(1 if on else 0))
+
+    def map_surfels(self):
+        """-> MAP_SURFEL array of the map's voxels (LidarOdometry::ExportMapSurfels); empty without map_surfels"""
+        self.lib.wc_odom_map_surfels.restype = C.c_uint64
+        n = int(self.lib.wc_odom_map_surfels(self.h, None, C.c_uint64(0)))
+        out = np.zeros(max(n, 1), R.MAP_SURFEL)
+        m = int(self.lib.wc_odom_map_surfels(self.h, R.ptr(out), C.c_uint64(n)))
+        assert m == n
+        return out[:n]
+
+    def map_query_planes(self, xyz, max_dist, min_points=3):
+        """wc_map_nearest_plane of every row of xyz ((n, 3) float32) -> MAP_PLANE_HIT array (LidarOdometry::QueryMapPlanes)"""
+        if not max_dist > 0 or min_points < 3:
+            raise WildcatError(11, "map_query_planes: max_dist must be > 0 and min_points >= 3")
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        hits = np.zeros(len(xyz), R.MAP_PLANE_HIT)
+        self.lib.wc_odom_map_query_planes.restype = C.c_uint64
+        self.lib.wc_odom_map_query_planes(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), C.c_double(max_dist), C.c_uint32(int(min_points)), R.ptr(hits))
+        return hits
 
     def set_map_keep_radius(self, radius):
         """LioConfig::map_keep_radius: after every sweep the map keeps the cube of this half-side around the sensor; 0 = unbounded"""

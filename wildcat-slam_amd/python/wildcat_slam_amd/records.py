@@ -29,6 +29,14 @@ assert ROUTE_POINT.itemsize == 24
 
 MAP_HIT = np.dtype([("xyz", "f4", 3), ("count", "u4"), ("key", "i4", 3), ("flags", "u4"), ("d2", "f8")])  # wc_map_hit
 assert MAP_HIT.itemsize == 40 and MAP_HIT.fields["d2"][1] == 32
+MAP_MOMENTS = 1  # WC_MAP_MOMENTS
+MAP_SURFEL = np.dtype(
+    [("key", "i4", 3), ("count", "u4"), ("xyz", "f4", 3), ("flags", "u4"), ("cov", "f8", 6), ("ev", "f8", 3), ("normal", "f8", 3)]
+)  # wc_map_surfel
+assert MAP_SURFEL.itemsize == 128 and [MAP_SURFEL.fields[f][1] for f in ("count", "xyz", "flags", "cov", "ev", "normal")] == [12, 16, 28, 32, 80, 104]
+# wc_map_plane_hit: the fields of MAP_HIT (flags: bit 1 = the plane is valid), then the plane
+MAP_PLANE_HIT = np.dtype(MAP_HIT.descr + [("normal", "f8", 3), ("sigma2", "f8"), ("dist", "f8")])
+assert MAP_PLANE_HIT.itemsize == 80 and [MAP_PLANE_HIT.fields[f][1] for f in ("flags", "d2", "normal", "sigma2", "dist")] == [28, 32, 40, 64, 72]
 
 assert SURFEL.itemsize == 144 and POSE.itemsize == 56 and IMU_STATE.itemsize == 112 and PAIR.itemsize == 8
 assert SURFEL_ID.itemsize == 16 and POINT.itemsize == 48
