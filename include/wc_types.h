@@ -119,6 +119,49 @@ typedef struct wc_map_plane_hit {
   double dist;      /* signed distance of the query to the plane through the centroid: (nx ex + ny ey) + nz ez, e = q - xyz   */
 } wc_map_plane_hit;
 
+/* wc_map_linearize / wc_map_align (wildcat_hip.h: "registration against the map"; not reference types) */
+typedef struct wc_map_reg_params { /* 32 bytes */
+  double max_dist;     /* wc_map_nearest_plane's: > 0, may be +inf                                            */
+  uint32_t min_points; /* wc_map_nearest_plane's: >= 3                                                        */
+  uint32_t reserved;   /* 0, anything else WC_ERR_ARG                                                         */
+  double sigma0;       /* > 0: w2 = 1 / (sigma0^2 + sigma2)  (wc_params.surfel_sigma0)                        */
+  double cauchy_a;     /* > 0: Cauchy loss of scale a (the window's: wc_params.cauchy_a); 0: none             */
+} wc_map_reg_params;
+
+typedef struct wc_map_reg_row { /* 64 bytes: one point's share, optional output */
+  double J[6]; /* d(dist) / d(omega, upsilon) for T <- Exp(xi) T: (Q x n, n); 0 if the point is unused */
+  double d;    /* the plane hit's dist                                                                */
+  double k;    /* w2 * rho'; 0 if the point is unused                                                 */
+} wc_map_reg_row;
+
+typedef struct wc_map_normal_eq { /* 240 bytes */
+  double H[21];     /* upper triangle, row-major (00 01 .. 05 11 12 ..): sum (k J_a) J_b */
+  double g[6];      /* sum (k J_a) d                                                     */
+  double cost;      /* 0.5 * sum rho                                                     */
+  uint64_t n_used;  /* points with a valid plane (flags bit 1)                           */
+  uint64_t n_found; /* wc_map_nearest_plane's found count                                */
+} wc_map_normal_eq;
+
+typedef struct wc_map_align_opts { /* 64 bytes */
+  wc_map_reg_params reg;
+  uint32_t max_iterations; /* >= 1                                                                             */
+  uint32_t min_used;       /* >= 6: fewer used points end the loop with termination 2                          */
+  double tol_rot;          /* > 0 [rad]:  converged when |omega| <= tol_rot and ...                            */
+  double tol_trans;        /* > 0 [m]:    ... |upsilon| <= tol_trans                                           */
+  double min_pivot;        /* > 0: smallest accepted Cholesky pivot of H scaled to unit diagonal (a design
+                              choice, wildcat_hip.h: wc_map_align; the Python binding's default is 1e-9)      */
+} wc_map_align_opts;
+
+typedef struct wc_map_align_summary { /* 88 bytes */
+  double initial_cost;  /* cost at the T_io passed in                                                */
+  double final_cost;    /* cost at the T_io returned                                                 */
+  int32_t iterations;   /* pose updates applied                                                      */
+  int32_t termination;  /* as wc_solve_summary: 0 = convergence, 1 = max_iterations, 2 = failure     */
+  uint64_t n_used;      /* at the T_io returned                                                      */
+  uint64_t n_found;
+  double last_step[6];  /* the last update applied (omega, upsilon); 0 if none                       */
+} wc_map_align_summary;
+
 /* Communicator of a multi-GPU job: one process (and one wc_ctx) per GPU.  The library calls these for its few collectives;
  * wc_comm_rccl_init() installs an in-library RCCL implementation, tests / other runtimes install callbacks.
  * All buffers are DEVICE pointers on the ctx's GPU; a callback returns 0 on success and must have completed (or be

@@ -68,6 +68,8 @@ int wc_ctx_set_params(wc_ctx *ctx, const wc_params *params);
  *                      the bias elimination's backward error stays below 1e-9 - tests/test_lm_step_gpu.py; 0 = never)
  *   map_mom_pts (1)    wc_map_insert into a WC_MAP_MOMENTS map: points per lane - 1: tiles of 256 points, 54 KB of LDS; 2: the plain
  *                      insert's tiles of 512 points, 108 KB of LDS, one workgroup per CU (same sums either way)
+ *   map_lin_groups (0) wc_map_linearize: workgroups of its first kernel (0: chosen from the point count); H, g and cost are byte-equal
+ *                      whatever the value
  *   lm_radius0         initial trust-region radius of wc_window_solve: 10^value (default -1 = the library's 1e4); tests use it to
  *                      look at the first step at other damping levels
  * Tests use it to run both forms of a choice on the same data.  Unknown names return WC_ERR_ARG. */
@@ -418,6 +420,49 @@ int wc_map_export_surfels(wc_ctx *ctx, wc_map *m, wc_map_surfel *d_out, uint64_t
  * wc_map_nearest, not the planes.  min_points < 3 or a map without moments: WC_ERR_ARG. */
 int wc_map_nearest_plane(wc_ctx *ctx, wc_map *m, const wc_points *queries, double max_dist, uint32_t min_points,
                          wc_map_plane_hit *d_hits, uint64_t *h_n_found);
+
+/* registration against the map: point-to-plane normal equations on the device ------------------------------------------------------ */
+/* wc_map_linearize moves every point of `pts` (DEVICE pointers, the wc_points rules of wc_map_insert) by the pose T - row-major 3 x 4
+ * (R | t), fp64, not checked for orthonormality -, finds its plane exactly as wc_map_nearest_plane finds a query's, and reduces the
+ * point-to-plane normal equations to the 240 bytes of a wc_map_normal_eq on the host.  Nothing but those 240 bytes travels back; the
+ * call waits for them.  One point, with x, y, z its floats cast to double and no fused multiply-add anywhere:
+ *   P_a = ((T[4a] x + T[4a+1] y) + T[4a+2] z) + T[4a+3],  q_a = (float)P_a
+ *   q is searched as wc_map_nearest_plane searches a query q (same device functions: candidates, ties, max_dist, min_points, flags);
+ *   the point is USED iff that record would carry flags bit 1.  Then, with Q = (double)q, n and sigma2 the record's normal and sigma2:
+ *   d      the record's dist
+ *   J[0] = Q_y n_z - Q_z n_y,  J[1] = Q_z n_x - Q_x n_z,  J[2] = Q_x n_y - Q_y n_x  (differences of two rounded products),  J[3..5] = n:
+ *          d(dist) / d(omega, upsilon) for T <- Exp(xi) T, xi = (omega, upsilon)
+ *   w2   = 1.0 / (sigma0 * sigma0 + sigma2),  s = (w2 * d) * d         (sigma0 * sigma0, a * a, max_dist * max_dist: formed once, on the host)
+ *   no loss (cauchy_a = 0):  k = w2,  rho = s
+ *   Cauchy loss of scale a:  k = w2 / (1.0 + s / (a * a)),  rho = (a * a) * log1p(s / (a * a))
+ * k has no square root on purpose: every field of a row is a chain of IEEE multiplications, additions and divisions, so a restatement
+ * reproduces a wc_map_reg_row bit for bit.  A point that is not used contributes nothing and its row is all zero.
+ *   H_ab = sum (k J_a) J_b  (a <= b),   g_a = sum (k J_a) d,   cost = 0.5 * sum rho,   n_used, n_found (wc_map_nearest_plane's found count)
+ * d_rows (DEVICE, 8-aligned, may be NULL) receives one wc_map_reg_row per point.
+ * Order of the sums - a function of the point count alone, so H, g and cost are byte-equal from run to run, for every grid size
+ * (development option map_lin_groups), for both point layouts, with and without d_rows: tile t = points [256 t, 256 t + 256); within
+ * a tile the terms of rows 32 c .. 32 c + 31 are added in ascending order (chunk c, 31 additions), then the eight chunk sums in
+ * ascending order (7); then, level by level, partials 32 j .. 32 j + 31 in ascending order into partial j until one is left.  The
+ * largest number of floating-point additions a term passes through:
+ *   A(n) = 38 + sum over the levels of (min(32, m_l) - 1),   m_0 = ceil(n / 256),  m_(l+1) = ceil(m_l / 32),  while m_l > 1
+ * A(n) = 38 for n <= 256, <= 69 for n <= 8192, <= 100 for n <= 2^18 and A(2^20) = 38 + 31 + 31 + 3 = 103 (<= 128 for every n <= 2^20).
+ * WC_ERR_ARG: a non-finite entry of T; a T that sends a finite point to a non-finite q; a map created without WC_MAP_MOMENTS or owned by
+ * another context; max_dist not > 0 (+inf allowed), min_points < 3, reserved != 0, sigma0 not > 0 or not finite, cauchy_a < 0 or not
+ * finite; a NULL argument other than d_rows.  pts->n == 0: WC_OK, h_out all zero.  The map is not modified. */
+int wc_map_linearize(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double T[12], const wc_map_reg_params *params,
+                     wc_map_normal_eq *h_out, wc_map_reg_row *d_rows);
+/* Gauss-Newton on wc_map_linearize: T_io (host, row-major 3 x 4) in, the aligned pose out.  Each iteration: linearise at T; stop with
+ * termination 2 if n_used < min_used; scale H to unit diagonal (H_ab / sqrt(H_aa H_bb), the diagonal exactly 1) and factorise it by
+ * Cholesky in fp64 on the host; stop with termination 2 - T_io as it was before this iteration - when a pivot (the number under the
+ * square root) is not finite or below min_pivot; solve H xi = -g; R <- Rod(omega) R, t <- Rod(omega) t + upsilon with Rodrigues' formula
+ * Rod(w) = I + (sin th / th) K + ((sin(th/2) / (th/2))^2 / 2) K^2, K = [w]x, th = |w|; stop with termination 0 when |omega| <= tol_rot
+ * and |upsilon| <= tol_trans.  Termination 1: max_iterations steps were taken without meeting the tolerances.  One more linearisation at
+ * the final T gives final_cost, n_used and n_found (after termination 2 that is the iteration's own).
+ * min_pivot is a design choice, not a measurement: the pivots of the unit-diagonal matrix lie in (0, 1], and 1 / min_pivot caps how far
+ * the least-determined pose direction may be amplified (a single wall leaves three directions free: pivots at rounding level).  The
+ * Python binding's default is 1e-9.  WC_ERR_ARG: max_iterations < 1, tol_rot / tol_trans / min_pivot not > 0, min_used < 6, and
+ * whatever wc_map_linearize refuses. */
+int wc_map_align(wc_ctx *ctx, wc_map *m, const wc_points *pts, double T_io[12], const wc_map_align_opts *opts, wc_map_align_summary *h_out);
 
 #ifdef __cplusplus
 }

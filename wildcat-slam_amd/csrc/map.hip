@@ -25,12 +25,15 @@
 //   k_map_crop_count / k_map_rehash<true>  crop: kept voxels and points counted per workgroup, then only the kept keys rehashed
 //   k_map_surfels   surfel export: one lane per sorted voxel: map_plane_of (exact 128-bit covariance numerator, fx_eig3) -> wc_map_surfel
 //   k_map_nearest<true>  plane query: the same search, then map_plane_of for the winning voxel only -> wc_map_plane_hit
+//   k_map_linearize / k_map_lin_reduce  registration: the plane query behind a pose, reduced to the point-to-plane normal equations in a
+//                   fixed order (tiles of 256 points, then levels of 32 partials, one launch each): wc_map_linearize, wc_map_align
 // Growth policy: before an insert of n points the host takes an upper bound B of the occupied slots (the exact count of the last
 // completed insert's read-back plus every point inserted after it); when 2 (B + n) > cap the table is rehashed into the smallest power
 // of two >= 2 (B + n) slots.  The table is therefore at most half full at every probe, and an insert never runs out of room.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include <rocprim/rocprim.hpp>
@@ -56,6 +59,8 @@ struct wc_map {
   uint64_t growths = 0;
   int cus = 256;
   wc_buf b_pairs[4], b_tmp, b_cnt;   // export scratch: keys in / out, slot indices in / out; rocPRIM temporary; compaction counter
+  wc_buf b_lin;                      // wc_map_linearize: the tiles' partial sums and every level of their reduction (first use)
+  unsigned long long *h_lin = nullptr;  // ... and the pinned landing place of the result (first use)
 };
 
 namespace {
@@ -445,6 +450,81 @@ __global__ void __launch_bounds__(256) k_map_surfels(const unsigned long long *s
 // 32-byte payload of the occupied ones only.  Every loop below is fully unrolled: all indices are compile-time constants, no scratch.
 // PLANE (wc_map_nearest_plane): the record is a wc_map_plane_hit - the same 40 bytes, then the winning voxel's plane from map_plane_of,
 // run once per query behind the search - and `hits` points at those records; mom and min_points are unused otherwise
+// what the search says about one query: the winner's centroid, count, index, slot and squared distance
+struct map_found {
+  double best;
+  float bx, by, bz;
+  unsigned bc;
+  int bkx, bky, bkz;
+  unsigned long long bh;  // (PLANE: the winner's slot)
+  bool ok;                // the query could be searched
+};
+// the search of one query (x, y, z) - the body k_map_nearest and k_map_linearize share
+template <bool PLANE>
+__device__ __forceinline__ map_found map_search(double x, double y, double z, double v, const unsigned long long *keys, const long long *pay,
+                                                unsigned long long mask) {
+  const double fx = floor(x / v), fy = floor(y / v), fz = floor(z / v);  // VoxelLoc, as k_map_insert
+  const bool ok = fx > -kMapKeyLim && fx < kMapKeyLim && fy > -kMapKeyLim && fy < kMapKeyLim && fz > -kMapKeyLim && fz < kMapKeyLim;
+  const int kx = ok ? (int)fx : 0, ky = ok ? (int)fy : 0, kz = ok ? (int)fz : 0;
+  double best = __builtin_inf();
+  float bx = 0.f, by = 0.f, bz = 0.f;
+  unsigned bc = 0;
+  int bkx = 0, bky = 0, bkz = 0;
+  unsigned long long bh = 0;
+#pragma unroll
+  for (int dx = -1; dx <= 1; ++dx) {
+    unsigned long long key[9], h[9], cur[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+      const int nx = kx + dx, ny = ky + (j / 3 - 1), nz = kz + (j % 3 - 1);
+      // (a neighbour beyond the key range holds nothing: its "key" is the empty mark, which the first slot read then settles)
+      const bool in = ok && nx > -kMapKeyOff && nx < kMapKeyOff && ny > -kMapKeyOff && ny < kMapKeyOff && nz > -kMapKeyOff && nz < kMapKeyOff;
+      key[j] = in ? map_pack(nx, ny, nz) : kMapEmpty;
+      h[j] = in ? map_hash(key[j]) & mask : 0;
+      cur[j] = keys[h[j]];
+    }
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+      if (key[j] == kMapEmpty) continue;
+      unsigned long long hj = h[j], c = cur[j];
+      for (unsigned long long probe = 0; c != key[j] && c != kMapEmpty && probe < mask; ++probe) {  // linear probing past foreign keys
+        hj = (hj + 1) & mask;
+        c = keys[hj];
+      }
+      if (c != key[j]) continue;
+      const longlong2 *p = (const longlong2 *)(pay + 4 * hj);
+      const longlong2 p0 = p[0], p1 = p[1];
+      const double cnt = (double)p1.y;
+      const int nx = kx + dx, ny = ky + (j / 3 - 1), nz = kz + (j % 3 - 1);
+      const float cx = map_centroid(nx, v, p0.x, cnt), cy = map_centroid(ny, v, p0.y, cnt), cz = map_centroid(nz, v, p1.x, cnt);
+      const double ex = x - (double)cx, ey = y - (double)cy, ez = z - (double)cz;
+      const double d2 = (ex * ex + ey * ey) + ez * ez;
+      if (d2 < best) {
+        best = d2, bx = cx, by = cy, bz = cz, bc = (unsigned)p1.y, bkx = nx, bky = ny, bkz = nz;
+        if constexpr (PLANE) bh = hj;
+      }
+    }
+  }
+  return map_found{best, bx, by, bz, bc, bkx, bky, bkz, bh, ok};
+}
+// the plane of an accepted winner (hit: bc != 0 and best <= max_d2): normal, sigma2 and the signed distance of the query; false (and
+// all of them 0) unless the voxel holds min_points points and its plane bit is set - flags bit 1 of a wc_map_plane_hit
+__device__ __forceinline__ bool map_hit_plane(const map_found &w, bool hit, double x, double y, double z, const long long *mom, unsigned min_points,
+                                              double (&pn)[3], double &sigma2, double &dist) {
+  bool valid = false;
+  pn[0] = 0.0, pn[1] = 0.0, pn[2] = 0.0, sigma2 = 0.0, dist = 0.0;
+  if (hit && w.bc >= min_points) {
+    const map_plane pl = map_plane_of((long long)w.bc, mom + kMapMom * w.bh);
+    if (pl.plane) {
+      const double ex = x - (double)w.bx, ey = y - (double)w.by, ez = z - (double)w.bz;  // (as in d2)
+      pn[0] = pl.nrm[0], pn[1] = pl.nrm[1], pn[2] = pl.nrm[2], sigma2 = pl.ev[0];
+      dist = (pn[0] * ex + pn[1] * ey) + pn[2] * ez;
+      valid = true;
+    }
+  }
+  return valid;
+}
+
 template <bool PLANE>
 __global__ void __launch_bounds__(kNearThreads) k_map_nearest(wc_points q, double v, double max_d2, const unsigned long long *keys,
                                                               const long long *pay, unsigned long long mask, void *hits,
@@ -455,72 +535,23 @@ __global__ void __launch_bounds__(kNearThreads) k_map_nearest(wc_points q, doubl
   for (uint64_t i = (uint64_t)blockIdx.x * kNearThreads + threadIdx.x; i < q.n; i += stride) {
     const float *f = (const float *)((const char *)q.xyz + i * q.xyz_stride);
     const double x = (double)f[0], y = (double)f[1], z = (double)f[2];
-    const double fx = floor(x / v), fy = floor(y / v), fz = floor(z / v);  // VoxelLoc, as k_map_insert
-    const bool ok = fx > -kMapKeyLim && fx < kMapKeyLim && fy > -kMapKeyLim && fy < kMapKeyLim && fz > -kMapKeyLim && fz < kMapKeyLim;
-    const int kx = ok ? (int)fx : 0, ky = ok ? (int)fy : 0, kz = ok ? (int)fz : 0;
-    double best = __builtin_inf();
-    float bx = 0.f, by = 0.f, bz = 0.f;
-    unsigned bc = 0;
-    int bkx = 0, bky = 0, bkz = 0;
-    unsigned long long bh = 0;  // (PLANE: the winner's slot)
-#pragma unroll
-    for (int dx = -1; dx <= 1; ++dx) {
-      unsigned long long key[9], h[9], cur[9];
-#pragma unroll
-      for (int j = 0; j < 9; ++j) {
-        const int nx = kx + dx, ny = ky + (j / 3 - 1), nz = kz + (j % 3 - 1);
-        // (a neighbour beyond the key range holds nothing: its "key" is the empty mark, which the first slot read then settles)
-        const bool in = ok && nx > -kMapKeyOff && nx < kMapKeyOff && ny > -kMapKeyOff && ny < kMapKeyOff && nz > -kMapKeyOff && nz < kMapKeyOff;
-        key[j] = in ? map_pack(nx, ny, nz) : kMapEmpty;
-        h[j] = in ? map_hash(key[j]) & mask : 0;
-        cur[j] = keys[h[j]];
-      }
-#pragma unroll
-      for (int j = 0; j < 9; ++j) {
-        if (key[j] == kMapEmpty) continue;
-        unsigned long long hj = h[j], c = cur[j];
-        for (unsigned long long probe = 0; c != key[j] && c != kMapEmpty && probe < mask; ++probe) {  // linear probing past foreign keys
-          hj = (hj + 1) & mask;
-          c = keys[hj];
-        }
-        if (c != key[j]) continue;
-        const longlong2 *p = (const longlong2 *)(pay + 4 * hj);
-        const longlong2 p0 = p[0], p1 = p[1];
-        const double cnt = (double)p1.y;
-        const int nx = kx + dx, ny = ky + (j / 3 - 1), nz = kz + (j % 3 - 1);
-        const float cx = map_centroid(nx, v, p0.x, cnt), cy = map_centroid(ny, v, p0.y, cnt), cz = map_centroid(nz, v, p1.x, cnt);
-        const double ex = x - (double)cx, ey = y - (double)cy, ez = z - (double)cz;
-        const double d2 = (ex * ex + ey * ey) + ez * ez;
-        if (d2 < best) {
-          best = d2, bx = cx, by = cy, bz = cz, bc = (unsigned)p1.y, bkx = nx, bky = ny, bkz = nz;
-          if constexpr (PLANE) bh = hj;
-        }
-      }
-    }
-    const bool hit = bc != 0 && best <= max_d2;
+    const map_found w = map_search<PLANE>(x, y, z, v, keys, pay, mask);
+    const bool hit = w.bc != 0 && w.best <= max_d2;
     n_found += hit ? 1u : 0u;
     // the 40-byte record as five 8-byte stores (the record is 8-aligned)
     uint2 *o = (uint2 *)((char *)hits + i * (PLANE ? sizeof(wc_map_plane_hit) : sizeof(wc_map_hit)));
-    unsigned flags = ok ? 0u : 1u;
+    unsigned flags = w.ok ? 0u : 1u;
     if constexpr (PLANE) {
-      double pn[3] = {0.0, 0.0, 0.0}, sigma2 = 0.0, dist = 0.0;
-      if (hit && bc >= min_points) {
-        const map_plane pl = map_plane_of((long long)bc, mom + kMapMom * bh);
-        if (pl.plane) {
-          const double ex = x - (double)bx, ey = y - (double)by, ez = z - (double)bz;  // (as in d2)
-          pn[0] = pl.nrm[0], pn[1] = pl.nrm[1], pn[2] = pl.nrm[2], sigma2 = pl.ev[0];
-          dist = (pn[0] * ex + pn[1] * ey) + pn[2] * ez;
-          flags |= 2u;
-        }
-      }
+      double pn[3], sigma2, dist;
+      flags |= map_hit_plane(w, hit, x, y, z, mom, min_points, pn, sigma2, dist) ? 2u : 0u;
       double *od = (double *)o;
       od[5] = pn[0], od[6] = pn[1], od[7] = pn[2], od[8] = sigma2, od[9] = dist;
     }
-    o[0] = hit ? make_uint2(__float_as_uint(bx), __float_as_uint(by)) : make_uint2(0u, 0u);
-    o[1] = hit ? make_uint2(__float_as_uint(bz), bc) : make_uint2(0u, 0u);
-    o[2] = hit ? make_uint2((unsigned)bkx, (unsigned)bky) : make_uint2(0u, 0u);
-    o[3] = make_uint2(hit ? (unsigned)bkz : 0u, flags);
-    ((double *)o)[4] = hit ? best : __builtin_inf();
+    o[0] = hit ? make_uint2(__float_as_uint(w.bx), __float_as_uint(w.by)) : make_uint2(0u, 0u);
+    o[1] = hit ? make_uint2(__float_as_uint(w.bz), w.bc) : make_uint2(0u, 0u);
+    o[2] = hit ? make_uint2((unsigned)w.bkx, (unsigned)w.bky) : make_uint2(0u, 0u);
+    o[3] = make_uint2(hit ? (unsigned)w.bkz : 0u, flags);
+    ((double *)o)[4] = hit ? w.best : __builtin_inf();
   }
   // the found count: per wavefront, per workgroup, then one atomic on the counter's own line
   n_found = wave_sum(n_found);
@@ -532,6 +563,139 @@ __global__ void __launch_bounds__(kNearThreads) k_map_nearest(wc_points q, doubl
     for (int w = 0; w < kNearThreads / 64; ++w) t += s_found[w];
     if (t) atomicAdd(found, (unsigned long long)t);
   }
+}
+
+// ---- registration (wc_map_linearize) ----------------------------------------------------------------------------------------------
+// The plane query with another ending: the point goes through the pose first, and instead of an 80-byte record its 8-double row
+// (J, d, k) and its rho enter the sums of the point-to-plane normal equations.  Summation order (a function of the point count alone):
+//   tile t = points [256 t, 256 t + 256): every lane leaves row and rho in LDS (unused points and the points past n: zeros); lane
+//   (e, c), e < 28 sums, c < 8 chunks, adds the terms of rows 32 c .. 32 c + 31 in ascending order (31 additions), lane e < 28 then adds
+//   the eight chunk sums in ascending order (7 additions): 38 additions per term, whichever workgroup works on the tile.  One
+//   256-byte partial per tile: 28 doubles, then the integer counts n_used, n_found, n_bad (finite points the pose sent to a non-finite
+//   one) and a zero word, written with plain vector stores.
+//   k_map_lin_reduce: partial j of level l + 1 = partials 32 j .. 32 j + 31 of level l added in ascending order, one launch per level
+//   until one partial is left (the launch boundary is the hand-off: no ticket, no fence, no atomics on doubles).
+constexpr int kLinThreads = 256;
+constexpr int kLinSums = 28;    // H's upper triangle (21), g (6), sum rho (1)
+constexpr int kLinWords = 32;   // 8-byte words of a partial
+constexpr int kLinFan = 32;     // partials (and rows) added sequentially into one
+constexpr int kLinFields = 9;   // J[6], d, k, rho
+constexpr int kLinPitch = kLinThreads + kLinThreads / kLinFan;  // rows of one field in LDS: one word of padding per chunk of 32
+struct map_pose {
+  double T[12];
+};
+struct map_reg {
+  double max_d2, s02, a2;  // max_dist^2, sigma0^2, cauchy_a^2 (0: no loss): each product formed once on the host
+  unsigned min_points;
+};
+
+__global__ void __launch_bounds__(kLinThreads) k_map_linearize(wc_points pts, map_pose P, map_reg R, double v, const unsigned long long *keys,
+                                                               const long long *pay, const long long *mom, unsigned long long mask,
+                                                               wc_map_reg_row *rows, unsigned long long *part) {
+  __shared__ double s_row[kLinFields * kLinPitch];
+  __shared__ double s_chunk[kLinSums * 8];
+  __shared__ unsigned s_cnt[3];
+  const int t = threadIdx.x;
+  const uint64_t tiles = (pts.n + kLinThreads - 1) / kLinThreads;
+  for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    if (t < 3) s_cnt[t] = 0;
+    __syncthreads();  // (also: the previous tile's sums have been read)
+    const uint64_t i = tile * kLinThreads + t;
+    double row[kLinFields] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    bool used = false, hit = false, bad = false;
+    if (i < pts.n) {
+      const float *f = (const float *)((const char *)pts.xyz + i * pts.xyz_stride);
+      const float px = f[0], py = f[1], pz = f[2];
+      const double x0 = (double)px, y0 = (double)py, z0 = (double)pz;
+      const float qx = (float)(((P.T[0] * x0 + P.T[1] * y0) + P.T[2] * z0) + P.T[3]);
+      const float qy = (float)(((P.T[4] * x0 + P.T[5] * y0) + P.T[6] * z0) + P.T[7]);
+      const float qz = (float)(((P.T[8] * x0 + P.T[9] * y0) + P.T[10] * z0) + P.T[11]);
+      bad = isfinite(px) && isfinite(py) && isfinite(pz) && !(isfinite(qx) && isfinite(qy) && isfinite(qz));
+      const double x = (double)qx, y = (double)qy, z = (double)qz;
+      const map_found w = map_search<true>(x, y, z, v, keys, pay, mask);
+      hit = w.bc != 0 && w.best <= R.max_d2;
+      double pn[3], sigma2, dist;
+      used = map_hit_plane(w, hit, x, y, z, mom, R.min_points, pn, sigma2, dist);
+      if (used) {
+        row[0] = y * pn[2] - z * pn[1], row[1] = z * pn[0] - x * pn[2], row[2] = x * pn[1] - y * pn[0];
+        row[3] = pn[0], row[4] = pn[1], row[5] = pn[2];
+        row[6] = dist;
+        const double w2 = 1.0 / (R.s02 + sigma2), s = (w2 * dist) * dist;
+        if (R.a2 > 0.0) {
+          const double u = s / R.a2;
+          row[7] = w2 / (1.0 + u), row[8] = R.a2 * log1p(u);
+        } else {
+          row[7] = w2, row[8] = s;
+        }
+      }
+      if (rows) {  // (the record is 8-aligned: eight 8-byte stores)
+        double *o = (double *)(rows + i);
+#pragma unroll
+        for (int fld = 0; fld < 8; ++fld) o[fld] = row[fld];
+      }
+    }
+    // the counts: per wavefront, then integer adds in LDS (order independent)
+    const unsigned n_u = (unsigned)__popcll(__ballot(used)), n_h = (unsigned)__popcll(__ballot(hit)), n_b = (unsigned)__popcll(__ballot(bad));
+    if ((t & 63) == 0) {
+      if (n_u) atomicAdd(&s_cnt[0], n_u);
+      if (n_h) atomicAdd(&s_cnt[1], n_h);
+      if (n_b) atomicAdd(&s_cnt[2], n_b);
+    }
+    const int at = t + t / kLinFan;
+#pragma unroll
+    for (int fld = 0; fld < kLinFields; ++fld) s_row[fld * kLinPitch + at] = row[fld];
+    __syncthreads();
+    if (t < kLinSums * 8) {
+      const int e = t >> 3, c = t & 7;
+      // e -> the three factors of a term (k X) Y: H(a, b): X = J_a, Y = J_b; g_a: X = J_a, Y = d; sum rho: the term itself
+      int a = 0, b = e;
+      while (b >= 6 - a && a < 6) b -= 6 - a, ++a;
+      const int fx = e < 21 ? a : e - 21, fy = e < 21 ? a + b : 6;
+      const double *rk = s_row + 7 * kLinPitch + c * (kLinFan + 1), *rx = s_row + fx * kLinPitch + c * (kLinFan + 1),
+                   *ry = s_row + fy * kLinPitch + c * (kLinFan + 1), *rr = s_row + 8 * kLinPitch + c * (kLinFan + 1);
+      double acc = 0.0;
+      if (e < 27) {
+        acc = (rk[0] * rx[0]) * ry[0];
+        for (int j = 1; j < kLinFan; ++j) acc += (rk[j] * rx[j]) * ry[j];
+      } else {
+        acc = rr[0];
+        for (int j = 1; j < kLinFan; ++j) acc += rr[j];
+      }
+      s_chunk[e * 8 + c] = acc;
+    }
+    __syncthreads();
+    if (t < kLinWords) {
+      unsigned long long word = 0;
+      if (t < kLinSums) {
+        double acc = s_chunk[t * 8];
+#pragma unroll
+        for (int c = 1; c < 8; ++c) acc += s_chunk[t * 8 + c];
+        word = (unsigned long long)__double_as_longlong(acc);
+      } else if (t < kLinSums + 3) {
+        word = s_cnt[t - kLinSums];
+      }
+      part[tile * kLinWords + t] = word;
+    }
+  }
+}
+
+// one level of the second stage: out[j] = in[32 j] + in[32 j + 1] + ... in ascending order (the doubles; the counts are integers)
+__global__ void __launch_bounds__(256) k_map_lin_reduce(const unsigned long long *in, uint64_t m, unsigned long long *out) {
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint64_t j = g / kLinWords, first = j * kLinFan;
+  const int e = (int)(g % kLinWords);
+  if (first >= m) return;
+  const uint64_t cnt = m - first < (uint64_t)kLinFan ? m - first : (uint64_t)kLinFan;
+  const unsigned long long *p = in + first * kLinWords + e;
+  unsigned long long word = p[0];
+  if (e < kLinSums) {
+    double acc = __longlong_as_double((long long)word);
+    for (uint64_t r = 1; r < cnt; ++r) acc += __longlong_as_double((long long)p[r * kLinWords]);
+    word = (unsigned long long)__double_as_longlong(acc);
+  } else {
+    for (uint64_t r = 1; r < cnt; ++r) word += p[r * kLinWords];
+  }
+  out[j * kLinWords + e] = word;
 }
 
 // crop, step 1: the voxels inside the box and their points, reduced per workgroup
@@ -668,9 +832,11 @@ extern "C" int wc_map_destroy(wc_ctx *ctx, wc_map *m) {
   for (wc_buf &b : m->b_pairs) wc_buf_release(ctx, b);
   wc_buf_release(ctx, m->b_tmp);
   wc_buf_release(ctx, m->b_cnt);
+  wc_buf_release(ctx, m->b_lin);
   (void)hipStreamSynchronize(ctx->stream);  // (the pinned counters may still be the target of an enqueued copy)
   if (m->ev_ctr) (void)hipEventDestroy(m->ev_ctr);
   if (m->h_ctr) (void)hipHostFree(m->h_ctr);
+  if (m->h_lin) (void)hipHostFree(m->h_lin);
   delete m;
   return WC_OK;
 }
@@ -868,6 +1034,173 @@ extern "C" int wc_map_nearest_plane(wc_ctx *ctx, wc_map *m, const wc_points *que
     return wc_fail(ctx, WC_ERR_ARG, "%s: a map created without WC_MAP_MOMENTS, or min_points < 3", __func__);
   }
   return map_nearest(ctx, m, queries, max_dist, min_points, d_hits, h_n_found, __func__);
+}
+
+// ---- registration against the map (include/wildcat_hip.h: wc_map_linearize, wc_map_align) ------------------------------------------
+namespace {
+bool reg_params_ok(const wc_map_reg_params *p) {
+  return p && p->max_dist > 0.0 && p->min_points >= 3 && p->reserved == 0 && p->sigma0 > 0.0 && std::isfinite(p->sigma0) &&
+         p->cauchy_a >= 0.0 && std::isfinite(p->cauchy_a);
+}
+// the sizes of the reduction's levels: m_0 = tiles, m_(l+1) = ceil(m_l / 32) down to 1 (at least one level: a copy when tiles = 1)
+uint64_t lin_words(uint64_t tiles) {
+  uint64_t total = tiles, m = tiles;
+  do {
+    m = (m + kLinFan - 1) / kLinFan;
+    total += m;
+  } while (m > 1);
+  return total * kLinWords;
+}
+}  // namespace
+
+extern "C" int wc_map_linearize(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double T[12], const wc_map_reg_params *params,
+                                wc_map_normal_eq *h_out, wc_map_reg_row *d_rows) {
+  wc_dev_guard dg_(ctx);
+  if (!map_ok(ctx, m) || !m->mom || !pts || !T || !h_out || !reg_params_ok(params) || (uintptr_t)d_rows % 8 ||
+      (pts->n && (!pts->xyz || pts->xyz_stride < 12 || pts->xyz_stride % 4 || (uintptr_t)pts->xyz % 4)))
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument, a map of another context or one created without WC_MAP_MOMENTS", __func__);
+  map_pose P;
+  for (int j = 0; j < 12; ++j) {
+    if (!std::isfinite(T[j])) return wc_fail(ctx, WC_ERR_ARG, "%s: T[%d] is not finite", __func__, j);
+    P.T[j] = T[j];
+  }
+  std::memset(h_out, 0, sizeof(*h_out));
+  if (pts->n == 0) return WC_OK;
+  const uint64_t tiles = (pts->n + kLinThreads - 1) / kLinThreads;
+  WC_TRY(wc_ensure(ctx, m->b_lin, lin_words(tiles) * 8));
+  if (!m->h_lin) WC_HIP(ctx, hipHostMalloc((void **)&m->h_lin, kLinWords * 8));
+  map_reg R;
+  R.max_d2 = params->max_dist * params->max_dist;
+  R.s02 = params->sigma0 * params->sigma0;
+  R.a2 = params->cauchy_a * params->cauchy_a;
+  R.min_points = params->min_points;
+  unsigned long long *lvl = (unsigned long long *)m->b_lin.p;
+  uint64_t grid = std::min<uint64_t>(tiles, (uint64_t)8 * m->cus);
+  if (ctx->dev.map_lin_groups > 0) grid = std::min<uint64_t>(tiles, (uint64_t)ctx->dev.map_lin_groups);  // (development option)
+  k_map_linearize<<<(unsigned)grid, kLinThreads, 0, ctx->stream>>>(*pts, P, R, m->voxel, m->keys, m->pay, m->mom, m->cap - 1, d_rows, lvl);
+  WC_HIP(ctx, hipGetLastError());
+  uint64_t cnt = tiles;
+  do {
+    const uint64_t nxt = (cnt + kLinFan - 1) / kLinFan;
+    unsigned long long *out = lvl + cnt * kLinWords;
+    k_map_lin_reduce<<<(unsigned)((nxt * kLinWords + 255) / 256), 256, 0, ctx->stream>>>(lvl, cnt, out);
+    WC_HIP(ctx, hipGetLastError());
+    lvl = out, cnt = nxt;
+  } while (cnt > 1);
+  WC_HIP(ctx, hipMemcpyAsync(m->h_lin, lvl, kLinWords * 8, hipMemcpyDeviceToHost, ctx->stream));
+  WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (m->h_lin[kLinSums + 2])
+    return wc_fail(ctx, WC_ERR_ARG, "%s: T sends %llu finite points to a non-finite one", __func__, m->h_lin[kLinSums + 2]);
+  double sums[kLinSums];
+  std::memcpy(sums, m->h_lin, sizeof(sums));
+  for (int e = 0; e < 21; ++e) h_out->H[e] = sums[e];
+  for (int e = 0; e < 6; ++e) h_out->g[e] = sums[21 + e];
+  h_out->cost = 0.5 * sums[27];
+  h_out->n_used = m->h_lin[kLinSums], h_out->n_found = m->h_lin[kLinSums + 1];
+  return WC_OK;
+}
+
+namespace {
+// R <- Rod(omega) R, t <- Rod(omega) t + upsilon, Rod(w) = I + A K + B K^2, K = [w]x, A = sin(th) / th, B = (sin(th/2) / (th/2))^2 / 2
+void pose_update(double T[12], const double xi[6]) {
+  const double wx = xi[0], wy = xi[1], wz = xi[2];
+  const double th = std::sqrt((wx * wx + wy * wy) + wz * wz);
+  double A = 1.0, B = 0.5;
+  if (th > 0.0) {
+    const double h = std::sin(0.5 * th) / (0.5 * th);
+    A = std::sin(th) / th, B = 0.5 * (h * h);
+  }
+  const double K[3][3] = {{0.0, -wz, wy}, {wz, 0.0, -wx}, {-wy, wx, 0.0}};
+  double E[3][3];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) {
+      const double k2 = (K[r][0] * K[0][c] + K[r][1] * K[1][c]) + K[r][2] * K[2][c];
+      E[r][c] = ((r == c ? 1.0 : 0.0) + A * K[r][c]) + B * k2;
+    }
+  double N[12];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 4; ++c) N[4 * r + c] = ((E[r][0] * T[c] + E[r][1] * T[4 + c]) + E[r][2] * T[8 + c]) + (c == 3 ? xi[3 + r] : 0.0);
+  std::memcpy(T, N, sizeof(N));
+}
+// H xi = -g by a Cholesky factorisation of H scaled to unit diagonal; false: a pivot (the number under the square root) is not finite
+// or below min_pivot
+bool gn_step(const wc_map_normal_eq &ne, double min_pivot, double xi[6]) {
+  double A[6][6], D[6], L[6][6] = {}, y[6];
+  for (int a = 0, e = 0; a < 6; ++a)
+    for (int b = a; b < 6; ++b, ++e) A[a][b] = A[b][a] = ne.H[e];
+  for (int a = 0; a < 6; ++a) D[a] = 1.0 / std::sqrt(A[a][a]);
+  for (int i = 0; i < 6; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double s = (D[i] * A[i][j]) * D[j];
+      if (i == j) s = 1.0;
+      for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
+      if (i == j) {
+        if (!std::isfinite(s) || !std::isfinite(D[i]) || !(s >= min_pivot)) return false;
+        L[i][i] = std::sqrt(s);
+      } else {
+        L[i][j] = s / L[j][j];
+      }
+    }
+  for (int i = 0; i < 6; ++i) {
+    double s = -(D[i] * ne.g[i]);
+    for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
+    y[i] = s / L[i][i];
+  }
+  for (int i = 5; i >= 0; --i) {
+    double s = y[i];
+    for (int k = i + 1; k < 6; ++k) s -= L[k][i] * xi[k];
+    xi[i] = s / L[i][i];
+  }
+  for (int i = 0; i < 6; ++i) {
+    xi[i] *= D[i];
+    if (!std::isfinite(xi[i])) return false;
+  }
+  return true;
+}
+}  // namespace
+
+extern "C" int wc_map_align(wc_ctx *ctx, wc_map *m, const wc_points *pts, double T_io[12], const wc_map_align_opts *o,
+                            wc_map_align_summary *h_out) {
+  if (!ctx || !T_io || !h_out || !o || o->max_iterations < 1 || !(o->tol_rot > 0.0) || !(o->tol_trans > 0.0) || o->min_used < 6 ||
+      !(o->min_pivot > 0.0))
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (max_iterations >= 1, tol_rot, tol_trans, min_pivot > 0, min_used >= 6)",
+                   __func__);
+  std::memset(h_out, 0, sizeof(*h_out));
+  h_out->termination = 1;
+  wc_map_normal_eq ne;
+  bool fresh = false;  // ne is the linearisation at T_io
+  for (uint32_t it = 0; it < o->max_iterations; ++it) {
+    WC_TRY(wc_map_linearize(ctx, m, pts, T_io, &o->reg, &ne, nullptr));
+    fresh = true;
+    if (it == 0) h_out->initial_cost = ne.cost;
+    double xi[6];
+    if (ne.n_used < o->min_used || !gn_step(ne, o->min_pivot, xi)) {
+      h_out->termination = 2;
+      break;
+    }
+    double T[12];
+    std::memcpy(T, T_io, sizeof(T));
+    pose_update(T, xi);
+    bool finite = true;
+    for (int j = 0; j < 12; ++j) finite = finite && std::isfinite(T[j]);
+    if (!finite) {
+      h_out->termination = 2;
+      break;
+    }
+    std::memcpy(T_io, T, sizeof(T));
+    fresh = false;
+    std::memcpy(h_out->last_step, xi, sizeof(xi));
+    h_out->iterations = (int32_t)(it + 1);
+    const double rot = std::sqrt((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2]), tr = std::sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5]);
+    if (rot <= o->tol_rot && tr <= o->tol_trans) {
+      h_out->termination = 0;
+      break;
+    }
+  }
+  if (!fresh) WC_TRY(wc_map_linearize(ctx, m, pts, T_io, &o->reg, &ne, nullptr));
+  h_out->final_cost = ne.cost;
+  h_out->n_used = ne.n_used, h_out->n_found = ne.n_found;
+  return WC_OK;
 }
 
 extern "C" int wc_map_crop(wc_ctx *ctx, wc_map *m, const double lo[3], const double hi[3], uint64_t *h_removed_voxels) {

@@ -477,6 +477,43 @@ size_t LidarOdometry::QueryMapPlanes(const float *xyz, size_t n, double max_dist
   WC_CALL(wc_dev_free(ctx_, d_hits));
   return found;
 }
+bool LidarOdometry::AlignToMap(const float *xyz, size_t n, double T_io[12], const wc_map_align_opts &opts, wc_map_align_summary *summary) {
+  if (!map_ || !map_moments_ || !T_io || (n && !xyz)) return false;
+  void *d_xyz = nullptr;
+  if (n) {
+    WC_CALL(wc_dev_alloc(ctx_, n * 3 * sizeof(float), &d_xyz));
+    WC_CALL(wc_h2d(ctx_, d_xyz, xyz, n * 3 * sizeof(float)));
+  }
+  const wc_points desc{d_xyz, nullptr, 12, 0, n};
+  double T[12];
+  std::memcpy(T, T_io, sizeof(T));
+  wc_map_align_summary s;
+  const int rc = wc_map_align(ctx_, map_, &desc, T, &opts, &s);  // (an argument the library refuses is the caller's: no abort)
+  if (d_xyz) WC_CALL(wc_dev_free(ctx_, d_xyz));
+  if (rc != WC_OK) return false;
+  std::memcpy(T_io, T, sizeof(T));
+  if (summary) *summary = s;
+  return true;
+}
+bool LidarOdometry::LinearizeAgainstMap(const float *xyz, size_t n, const double T[12], const wc_map_reg_params &params, wc_map_normal_eq *out,
+                                        wc_map_reg_row *rows) {
+  if (!map_ || !map_moments_ || !T || !out || (n && !xyz)) return false;
+  void *d_xyz = nullptr, *d_rows = nullptr;
+  if (n) {
+    WC_CALL(wc_dev_alloc(ctx_, n * 3 * sizeof(float), &d_xyz));
+    WC_CALL(wc_h2d(ctx_, d_xyz, xyz, n * 3 * sizeof(float)));
+    if (rows) WC_CALL(wc_dev_alloc(ctx_, n * sizeof(wc_map_reg_row), &d_rows));
+  }
+  const wc_points desc{d_xyz, nullptr, 12, 0, n};
+  wc_map_normal_eq ne;
+  const int rc = wc_map_linearize(ctx_, map_, &desc, T, &params, &ne, (wc_map_reg_row *)d_rows);
+  if (rc == WC_OK && d_rows) WC_CALL(wc_d2h(ctx_, rows, d_rows, n * sizeof(wc_map_reg_row)));
+  if (d_xyz) WC_CALL(wc_dev_free(ctx_, d_xyz));
+  if (d_rows) WC_CALL(wc_dev_free(ctx_, d_rows));
+  if (rc != WC_OK) return false;
+  *out = ne;
+  return true;
+}
 uint64_t LidarOdometry::map_voxels() const {
   uint64_t v = 0;
   if (map_) WC_CALL(wc_map_size(ctx_, map_, &v, nullptr));

@@ -100,6 +100,13 @@ class LidarOdometry {
   // wc_map_nearest_plane for n host points (xyz: n x 3 floats): hits[n]; returns the number of voxels found (as QueryMap).  Without a
   // map, with map_surfels off or min_points < 3: 0, every hit a miss
   size_t QueryMapPlanes(const float *xyz, size_t n, double max_dist, uint32_t min_points, wc_map_plane_hit *hits);
+  // registration of n host points (xyz: n x 3 floats) against the map's planes (wc_map_align): T_io (row-major 3 x 4) in, the aligned
+  // pose out, *summary (may be null) as wc_map_align leaves it.  false - nothing touched - without a map, with map_surfels off, or when
+  // the library refuses the arguments.  Nothing in AddLidarScan calls it
+  bool AlignToMap(const float *xyz, size_t n, double T_io[12], const wc_map_align_opts &opts, wc_map_align_summary *summary);
+  // one linearisation at T (wc_map_linearize): *out, and rows[n] when rows is not null; false as AlignToMap
+  bool LinearizeAgainstMap(const float *xyz, size_t n, const double T[12], const wc_map_reg_params &params, wc_map_normal_eq *out,
+                           wc_map_reg_row *rows);
   bool SetMapKeepRadius(double radius);  // config().map_keep_radius = radius; false: negative or NaN
   // wall time [ms] of the last completed sweep's map step (the undistortion when fill_outputs does not already form it, the insert's
   // enqueue - its kernel runs behind on the stream - and, with map_keep_radius, the crop, which waits).  Not part of last_stage_ms()

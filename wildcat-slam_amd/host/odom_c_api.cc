@@ -218,6 +218,14 @@ uint64_t wc_odom_map_surfels(void *h, wc_map_surfel *surfels, uint64_t cap) { re
 uint64_t wc_odom_map_query_planes(void *h, const float *xyz, uint64_t n, double max_dist, uint32_t min_points, wc_map_plane_hit *hits) {
   return ((LidarOdometry *)h)->QueryMapPlanes(xyz, n, max_dist, min_points, hits);
 }
+// LidarOdometry::AlignToMap / LinearizeAgainstMap for n host points (n x 3 floats); 1 = done, 0 = no map, map_surfels off or refused arguments
+int wc_odom_map_align(void *h, const float *xyz, uint64_t n, double T_io[12], const wc_map_align_opts *opts, wc_map_align_summary *summary) {
+  return opts && ((LidarOdometry *)h)->AlignToMap(xyz, n, T_io, *opts, summary) ? 1 : 0;
+}
+int wc_odom_map_linearize(void *h, const float *xyz, uint64_t n, const double T[12], const wc_map_reg_params *params, wc_map_normal_eq *out,
+                          wc_map_reg_row *rows) {
+  return params && ((LidarOdometry *)h)->LinearizeAgainstMap(xyz, n, T, *params, out, rows) ? 1 : 0;
+}
 // LioConfig::map_keep_radius: 0 = unbounded map; returns 0, or WC_ERR_ARG for a negative or NaN radius
 int wc_odom_set_map_keep_radius(void *h, double radius) { return ((LidarOdometry *)h)->SetMapKeepRadius(radius) ? 0 : WC_ERR_ARG; }
 // Cloud2FromXyz (host/wire_formats.h): the field table (3 x {offset, datatype, count}), point_step and the payload of n points

@@ -588,6 +588,27 @@ class Context:
         return pairs
 
 
+def map_reg_params(max_dist, min_points=3, sigma0=0.05 / 6, cauchy_a=0.0):
+    """wc_map_reg_params (sigma0: wc_params.surfel_sigma0's default; cauchy_a = 0: no loss, the window's is 0.4)"""
+    return R.MapRegParams(float(max_dist), int(min_points), 0, float(sigma0), float(cauchy_a))
+
+
+def map_align_opts(params, max_iterations=20, tol_rot=1e-6, tol_trans=1e-6, min_used=6, min_pivot=1e-9):
+    """wc_map_align_opts around a wc_map_reg_params (min_pivot: a design choice, include/wildcat_hip.h: wc_map_align)"""
+    return R.MapAlignOpts(params, int(max_iterations), int(min_used), float(tol_rot), float(tol_trans), float(min_pivot))
+
+
+def _pose12(T):
+    T = np.ascontiguousarray(np.asarray(T, np.float64).reshape(-1)[:12])
+    assert T.size == 12, "T: 3 x 4 (or 4 x 4) row-major"
+    return T.copy()
+
+
+def _summary_dict(s):
+    return dict(initial_cost=s.initial_cost, final_cost=s.final_cost, iterations=s.iterations, termination=s.termination, n_used=int(s.n_used),
+                n_found=int(s.n_found), last_step=np.array(list(s.last_step)))
+
+
 class PointMap:
     """wc_map: the device-resident voxel-downsampled map (DownSamplingVoxel, surfel_extraction.cc:228-261, over every insert)"""
 
@@ -727,6 +748,51 @@ class PointMap:
             if d:
                 d.free()
 
+    def linearize_device(self, desc, T, params, d_rows=None):
+        """points already in HBM (a wc_points descriptor) moved by T (3 x 4 row-major) -> MAP_NORMAL_EQ record (wc_map_linearize: the
+        point-to-plane normal equations against the map's planes); d_rows: a DeviceBuffer for one MAP_REG_ROW per point, or None"""
+        out = np.zeros(1, R.MAP_NORMAL_EQ)
+        T = _pose12(T)
+        self.ctx._ck(self.lib.wc_map_linearize(self.ctx.h, self.h, C.byref(desc), R.ptr(T), C.byref(params), R.ptr(out),
+                                               C.c_void_p(d_rows.ptr if d_rows else 0)))
+        return out[0]
+
+    def linearize(self, points, T, params=None, want_rows=False, **kw):
+        """POINT records or an (n, 3) float32 array (uploaded for the call) -> MAP_NORMAL_EQ record, or (record, MAP_REG_ROW array)
+        with want_rows; params: a wc_map_reg_params, or its fields as keywords (max_dist defaults to the voxel size)"""
+        if params is None:
+            kw.setdefault("max_dist", self.voxel)
+            params = map_reg_params(**kw)
+        d, desc = self._upload(points)
+        d_rows = self.ctx.alloc(R.MAP_REG_ROW.itemsize * max(desc.n, 1)) if want_rows else None
+        try:
+            ne = self.linearize_device(desc, T, params, d_rows)
+            return (ne, d_rows.download(R.MAP_REG_ROW, desc.n)) if want_rows else ne
+        finally:
+            for b in (d, d_rows):
+                if b:
+                    b.free()
+
+    def align_device(self, desc, T, opts):
+        """wc_map_align on points already in HBM -> (T (3, 4), summary dict)"""
+        T = _pose12(T)
+        summ = R.MapAlignSummary()
+        self.ctx._ck(self.lib.wc_map_align(self.ctx.h, self.h, C.byref(desc), R.ptr(T), C.byref(opts), C.byref(summ)))
+        return T.reshape(3, 4), _summary_dict(summ)
+
+    def align(self, points, T, opts=None, params=None, **kw):
+        """Gauss-Newton registration of POINT records or an (n, 3) float32 array against the map, from the pose T -> (T (3, 4), summary
+        dict: initial_cost, final_cost, iterations, termination (0 converged, 1 max_iterations, 2 failure), n_used, n_found, last_step);
+        opts: a wc_map_align_opts, or params (a wc_map_reg_params, default max_dist = the voxel size) and map_align_opts' keywords"""
+        if opts is None:
+            opts = map_align_opts(params if params is not None else map_reg_params(self.voxel), **kw)
+        d, desc = self._upload(points)
+        try:
+            return self.align_device(desc, T, opts)
+        finally:
+            if d:
+                d.free()
+
     def clear(self):
         self.ctx._ck(self.lib.wc_map_clear(self.ctx.h, self.h))
 
@@ -859,6 +925,26 @@ class Odometry:
         self.lib.wc_odom_map_query_planes.restype = C.c_uint64
         self.lib.wc_odom_map_query_planes(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), C.c_double(max_dist), C.c_uint32(int(min_points)), R.ptr(hits))
         return hits
+
+    def map_linearize(self, xyz, T, params, want_rows=False):
+        """wc_map_linearize of every row of xyz ((n, 3) float32) moved by T against the map's planes (LidarOdometry::LinearizeAgainstMap)
+        -> MAP_NORMAL_EQ record (with want_rows: (record, MAP_REG_ROW array)), or None without a map or with map_surfels off"""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        out, rows, T = np.zeros(1, R.MAP_NORMAL_EQ), np.zeros(max(len(xyz), 1), R.MAP_REG_ROW), _pose12(T)
+        ok = self.lib.wc_odom_map_linearize(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), R.ptr(T), C.byref(params), R.ptr(out),
+                                            R.ptr(rows) if want_rows else None)
+        if not ok:
+            return None
+        return (out[0], rows[: len(xyz)]) if want_rows else out[0]
+
+    def map_align(self, xyz, T, opts):
+        """wc_map_align of xyz ((n, 3) float32) from the pose T (LidarOdometry::AlignToMap) -> (T (3, 4), summary dict), or None without
+        a map or with map_surfels off"""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        T, summ = _pose12(T), R.MapAlignSummary()
+        if not self.lib.wc_odom_map_align(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), R.ptr(T), C.byref(opts), C.byref(summ)):
+            return None
+        return T.reshape(3, 4), _summary_dict(summ)
 
     def set_map_keep_radius(self, radius):
         """LioConfig::map_keep_radius: after every sweep the map keeps the cube of this half-side around the sensor; 0 = unbounded"""

@@ -38,6 +38,11 @@ assert MAP_SURFEL.itemsize == 128 and [MAP_SURFEL.fields[f][1] for f in ("count"
 MAP_PLANE_HIT = np.dtype(MAP_HIT.descr + [("normal", "f8", 3), ("sigma2", "f8"), ("dist", "f8")])
 assert MAP_PLANE_HIT.itemsize == 80 and [MAP_PLANE_HIT.fields[f][1] for f in ("flags", "d2", "normal", "sigma2", "dist")] == [28, 32, 40, 64, 72]
 
+# wc_map_linearize / wc_map_align: one point's row, the 240-byte normal equations
+MAP_REG_ROW = np.dtype([("J", "f8", 6), ("d", "f8"), ("k", "f8")])  # wc_map_reg_row
+MAP_NORMAL_EQ = np.dtype([("H", "f8", 21), ("g", "f8", 6), ("cost", "f8"), ("n_used", "u8"), ("n_found", "u8")])  # wc_map_normal_eq
+assert MAP_REG_ROW.itemsize == 64 and MAP_NORMAL_EQ.itemsize == 240 and MAP_NORMAL_EQ.fields["cost"][1] == 216
+
 assert SURFEL.itemsize == 144 and POSE.itemsize == 56 and IMU_STATE.itemsize == 112 and PAIR.itemsize == 8
 assert SURFEL_ID.itemsize == 16 and POINT.itemsize == 48
 
@@ -134,3 +139,39 @@ class SweepJob(C.Structure):
 
 def ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+class MapRegParams(C.Structure):
+    """wc_map_reg_params"""
+
+    _fields_ = [("max_dist", C.c_double), ("min_points", C.c_uint32), ("reserved", C.c_uint32), ("sigma0", C.c_double), ("cauchy_a", C.c_double)]
+
+
+class MapAlignOpts(C.Structure):
+    """wc_map_align_opts"""
+
+    _fields_ = [
+        ("reg", MapRegParams),
+        ("max_iterations", C.c_uint32),
+        ("min_used", C.c_uint32),
+        ("tol_rot", C.c_double),
+        ("tol_trans", C.c_double),
+        ("min_pivot", C.c_double),
+    ]
+
+
+class MapAlignSummary(C.Structure):
+    """wc_map_align_summary"""
+
+    _fields_ = [
+        ("initial_cost", C.c_double),
+        ("final_cost", C.c_double),
+        ("iterations", C.c_int32),
+        ("termination", C.c_int32),
+        ("n_used", C.c_uint64),
+        ("n_found", C.c_uint64),
+        ("last_step", C.c_double * 6),
+    ]
+
+
+assert C.sizeof(MapRegParams) == 32 and C.sizeof(MapAlignOpts) == 64 and C.sizeof(MapAlignSummary) == 88
