@@ -162,6 +162,24 @@ typedef struct wc_map_align_summary { /* 88 bytes */
   double last_step[6];  /* the last update applied (omega, upsilon); 0 if none                       */
 } wc_map_align_summary;
 
+/* wc_map_carve (wildcat_hip.h): which rays of a call are used and what they select. */
+typedef struct wc_map_carve_params { /* 32 bytes */
+  double min_range;   /* [m] 0 <= min_range <= max_range: a ray is used iff min_range^2 <= |p - origin|^2 <= max_range^2   */
+  double max_range;   /* [m] may be +inf                                                                            */
+  uint32_t shell;     /* 0..8: Chebyshev radius, in voxels, around a ray's end voxel that the ray does not see through */
+  uint32_t min_rays;  /* >= 1: a voxel is selected when at least this many rays of THIS call saw through it         */
+  uint32_t max_steps; /* 1..65536: rays whose walk is longer are skipped and counted                                */
+  uint32_t reserved;  /* 0                                                                                          */
+} wc_map_carve_params;
+
+typedef struct wc_map_carve_result { /* 40 bytes */
+  uint64_t rays_used;      /* rays that were walked                                             */
+  uint64_t rays_skipped;   /* every other point of the call                                     */
+  uint64_t steps;          /* sum of the used rays' walk lengths M                              */
+  uint64_t voxels_removed; /* occupied voxels selected (not removed yet: wildcat_hip.h)          */
+  uint64_t points_removed; /* ... and the points they hold                                      */
+} wc_map_carve_result;
+
 /* Communicator of a multi-GPU job: one process (and one wc_ctx) per GPU.  The library calls these for its few collectives;
  * wc_comm_rccl_init() installs an in-library RCCL implementation, tests / other runtimes install callbacks.
  * All buffers are DEVICE pointers on the ctx's GPU; a callback returns 0 on success and must have completed (or be

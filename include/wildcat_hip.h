@@ -70,6 +70,8 @@ int wc_ctx_set_params(wc_ctx *ctx, const wc_params *params);
  *                      insert's tiles of 512 points, 108 KB of LDS, one workgroup per CU (same sums either way)
  *   map_lin_groups (0) wc_map_linearize: workgroups of its first kernel (0: chosen from the point count); H, g and cost are byte-equal
  *                      whatever the value
+ *   map_carve_groups (0) wc_map_carve: workgroups of its ray kernel (0: chosen from the point count); the five counts are the same
+ *                      whatever the value
  *   lm_radius0         initial trust-region radius of wc_window_solve: 10^value (default -1 = the library's 1e4); tests use it to
  *                      look at the first step at other damping levels
  * Tests use it to run both forms of a choice on the same data.  Unknown names return WC_ERR_ARG. */
@@ -391,6 +393,36 @@ int wc_map_nearest(wc_ctx *ctx, wc_map *m, const wc_points *queries, double max_
  * growth counts stay.  *h_removed_voxels (may be NULL) receives the number of voxels dropped.  Waits for the ctx stream either way:
  * the new table is sized from the kept count. */
 int wc_map_crop(wc_ctx *ctx, wc_map *m, const double lo[3], const double hi[3], uint64_t *h_removed_voxels);
+
+/* Carving: free space by visibility.  A lidar return also says that the space between the sensor and the return is empty: every point p
+ * of `pts` (DEVICE pointers, the wc_points rules of wc_map_insert: either stride, pts->time ignored; every k-th ray: a larger xyz_stride)
+ * is the end of a ray from `origin` - ONE sensor position for the whole call, in the map's frame - and an occupied voxel that enough
+ * rays of the call passed through, and in which none of them ended, is SELECTED.  This version of the call counts what it selects and
+ * leaves the map as it is: voxels_removed and points_removed say what a removal would take (DESIGN 8.4 says why the removal is not in
+ * yet).  Every expression is fp64 without fused multiply-add, so a restatement (tests/map_carve_ref.py) reproduces the counts exactly:
+ *   ray           o = origin, P = (double)p, d = P - o, len2 = (d_x d_x + d_y d_y) + d_z d_z; k0 = floor(o / v), ke = floor(P / v) per
+ *                 axis (VoxelLoc, true division); M = sum over the axes of |ke_a - k0_a|
+ *   end mark      a point with finite coordinates and |ke_a| < 2^20 marks its end voxel ke, whether or not its ray is used
+ *   used          iff p is finite, |k0_a| and |ke_a| < 2^20, min_range^2 <= len2 <= max_range^2 (the squares formed once on the host)
+ *                 and M <= max_steps; every other point counts in rays_skipped
+ *   walk          k^(0) = k0, ..., k^(M) = ke.  At a step the candidate axes are those with k_a != ke_a; for a candidate
+ *                 b_a = (double)(k_a + (ke_a > k0_a ? 1 : 0)) * v, t_a = (b_a - o_a) * inv_a, inv_a = 1.0 / d_a formed once per ray; the
+ *                 lowest candidate axis steps by sign(ke_a - k0_a) unless a later candidate's t is strictly smaller (ties: the lowest
+ *                 axis).  b_a comes from the integer at every step (nothing drifts), a non-candidate axis is never used, and
+ *                 ke_a != k0_a implies d_a != 0: the walk reaches ke after exactly M steps for any input - a counted loop
+ *   seen through  k^(i) is seen through by the ray iff max_a |k^(i)_a - ke_a| > shell; a walk visits a voxel at most once;
+ *                 through(k) = the number of used rays that see through k; steps = the sum of M over the used rays
+ *   selection     an occupied voxel is selected iff through(k) >= min_rays and no point of this call marked it as an end voxel: integer
+ *                 functions of the call's point set, independent of order, split, grid size and schedule
+ * Plain and WC_MAP_MOMENTS maps alike.  The call waits and fills *h_out.  A uint32 word per slot of scratch is taken on the first call
+ * and grows with the table.
+ * WC_ERR_ARG: a NULL argument; a non-finite origin; a NaN or negative range; min_range > max_range; shell > 8; min_rays = 0; max_steps
+ * outside 1..65536; reserved != 0; pts->n >= 2^31; a map of another context.  pts->n = 0 or an empty map: WC_OK, nothing selected.
+ * Limits: one origin per call - sensor motion within the sweep and the lever arm are ignored, `shell` is the margin for
+ * both; a ray grazing a surface passes through surface voxels no return of the call fell into (min_rays and the end marks reduce
+ * this and do not remove it). */
+int wc_map_carve(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double origin[3], const wc_map_carve_params *params,
+                 wc_map_carve_result *h_out);
 
 /* map surfels: the plane through every voxel's points (WC_MAP_MOMENTS) ------------------------------------------------------------ */
 /* A map created with WC_MAP_MOMENTS holds nine more 64-bit words per slot (112 instead of 40 bytes, wc_map_info).  Per inserted point

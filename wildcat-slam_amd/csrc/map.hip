@@ -27,6 +27,10 @@
 //   k_map_nearest<true>  plane query: the same search, then map_plane_of for the winning voxel only -> wc_map_plane_hit
 //   k_map_linearize / k_map_lin_reduce  registration: the plane query behind a pose, reduced to the point-to-plane normal equations in a
 //                   fixed order (tiles of 256 points, then levels of 32 partials, one launch each): wc_map_linearize, wc_map_align
+//   k_map_carve    carving: one lane per ray from the call's origin to a point: the end voxel's word gets its mark, then the counted voxel
+//                   walk, eight steps ahead of the probes: keys, hashes and shell tests of a batch, its first-slot key loads issued
+//                   together, then the chains (read-only) and one no-return atomic add per occupied voxel seen through;
+//                   k_map_carve_count then counts the voxels the words select: wc_map_carve (which reports and does not remove yet)
 // Growth policy: before an insert of n points the host takes an upper bound B of the occupied slots (the exact count of the last
 // completed insert's read-back plus every point inserted after it); when 2 (B + n) > cap the table is rehashed into the smallest power
 // of two >= 2 (B + n) slots.  The table is therefore at most half full at every probe, and an insert never runs out of room.
@@ -61,6 +65,8 @@ struct wc_map {
   wc_buf b_pairs[4], b_tmp, b_cnt;   // export scratch: keys in / out, slot indices in / out; rocPRIM temporary; compaction counter
   wc_buf b_lin;                      // wc_map_linearize: the tiles' partial sums and every level of their reduction (first use)
   unsigned long long *h_lin = nullptr;  // ... and the pinned landing place of the result (first use)
+  wc_buf b_carve;                    // wc_map_carve: its five counter lines, then one u32 word per slot (first use, grown with the table)
+  unsigned long long *h_carve = nullptr;  // ... and the pinned landing place of the counters (first use)
 };
 
 namespace {
@@ -80,6 +86,10 @@ constexpr int kCtrOcc = 0, kCtrPts = 16, kCtrRej = 32, kCtrRejCall = 48, kCtrLos
 constexpr int kCtrFound = 64, kCtrKeepVox = 80, kCtrKeepPts = 96, kCtrWords = 112;      // query hits; a crop's kept voxels, points
 constexpr int kNearThreads = 256;
 constexpr int kCompactChunk = 2048;                // slots per workgroup of k_map_compact
+constexpr int kCarveThreads = 256;
+constexpr int kCarveBatch = 8;                     // steps of a ray whose first-slot key loads are in flight together
+constexpr unsigned kCarveEnd = 0x80000000u;        // a slot's word: bit 31 = an end voxel of this call; low 31 bits = through(k)
+constexpr int kCarveUsed = 0, kCarveSkip = 16, kCarveSteps = 32, kCarveSelVox = 48, kCarveSelPts = 64, kCarveCtrWords = 80;  // u64 word of each of wc_map_carve's counters
 
 __device__ __forceinline__ unsigned long long map_hash(unsigned long long k) {  // splitmix64 finaliser
   k ^= k >> 30;
@@ -722,6 +732,138 @@ __global__ void __launch_bounds__(256) k_map_crop_count(const unsigned long long
   }
 }
 
+// ---- carving (wc_map_carve) -------------------------------------------------------------------------------------------------------
+// what is the same for every ray of a call; the squares and the origin's voxel are formed once, on the host
+struct map_ray_args {
+  double o[3], v, min2, max2;
+  int k0[3];      // floor(o / v) (VoxelLoc); 0 when it is out of range
+  unsigned k0_ok; // |k0_a| < 2^20 on every axis
+  unsigned shell, max_steps;
+};
+// the slot of `key` from its first slot h, whose key c has been loaded: the read-only probe chain of map_search; kMapEmpty: absent
+__device__ __forceinline__ unsigned long long map_find_from(const unsigned long long *keys, unsigned long long mask, unsigned long long key,
+                                                            unsigned long long h, unsigned long long c) {
+  for (unsigned long long probe = 0; c != key && c != kMapEmpty && probe < mask; ++probe) {
+    h = (h + 1) & mask;
+    c = keys[h];
+  }
+  return c == key ? h : kMapEmpty;
+}
+__device__ __forceinline__ int map_cheb(int ax, int ay, int az, int bx, int by, int bz) {
+  return max(max(abs(ax - bx), abs(ay - by)), abs(az - bz));
+}
+
+// One lane per point (include/wildcat_hip.h: wc_map_carve states every expression).  The end voxel's word gets bit 31; a used ray then
+// walks its M voxel steps, known before the loop, B at a time: the B positions, their keys, hashes and shell tests come first - the next
+// voxel does not depend on what a probe finds - with the B first-slot key loads issued as they are formed; only then are the loads looked
+// at, the chains followed and the words of the occupied voxels incremented (no-return atomics).  |k - ke| shrinks monotonically on
+// every axis, so the first position inside the shell ends the walk: nothing after it is seen through.  k^(M) = ke never is, and is not
+// visited.  Every index below is a compile-time constant (no scratch); the axis is chosen and applied with selects.
+template <int B>
+__global__ void __launch_bounds__(kCarveThreads) k_map_carve(wc_points pts, map_ray_args A, const unsigned long long *keys, unsigned long long mask,
+                                                             unsigned *words, unsigned long long *cctr) {
+  __shared__ unsigned long long s_used[kCarveThreads / 64], s_skip[kCarveThreads / 64], s_steps[kCarveThreads / 64];
+  unsigned long long n_used = 0, n_skip = 0, n_steps = 0;
+  const double v = A.v, ox = A.o[0], oy = A.o[1], oz = A.o[2];
+  const int shell = (int)A.shell;
+  const uint64_t stride = (uint64_t)gridDim.x * kCarveThreads;
+  for (uint64_t i = (uint64_t)blockIdx.x * kCarveThreads + threadIdx.x; i < pts.n; i += stride) {
+    const float *f = (const float *)((const char *)pts.xyz + i * pts.xyz_stride);
+    const double px = (double)f[0], py = (double)f[1], pz = (double)f[2];
+    const double fx = floor(px / v), fy = floor(py / v), fz = floor(pz / v);  // VoxelLoc, as k_map_insert: NaN / inf fail the compares
+    if (!(fx > -kMapKeyLim && fx < kMapKeyLim && fy > -kMapKeyLim && fy < kMapKeyLim && fz > -kMapKeyLim && fz < kMapKeyLim)) {
+      ++n_skip;
+      continue;
+    }
+    const int kex = (int)fx, key_ = (int)fy, kez = (int)fz;
+    {  // the end mark, whether or not the ray is used
+      const unsigned long long ekey = map_pack(kex, key_, kez), eh = map_hash(ekey) & mask;
+      const unsigned long long es = map_find_from(keys, mask, ekey, eh, keys[eh]);
+      if (es != kMapEmpty) atomicOr(&words[es], kCarveEnd);
+    }
+    const double dx = px - ox, dy = py - oy, dz = pz - oz;
+    const double len2 = (dx * dx + dy * dy) + dz * dz;
+    int kx = A.k0[0], ky = A.k0[1], kz = A.k0[2];
+    const unsigned M = (unsigned)abs(kex - kx) + (unsigned)abs(key_ - ky) + (unsigned)abs(kez - kz);
+    if (!(A.k0_ok != 0u && len2 >= A.min2 && len2 <= A.max2 && M <= A.max_steps)) {
+      ++n_skip;
+      continue;
+    }
+    ++n_used;
+    n_steps += M;
+    const int sx = kex > kx ? 1 : (kex < kx ? -1 : 0), sy = key_ > ky ? 1 : (key_ < ky ? -1 : 0), sz = kez > kz ? 1 : (kez < kz ? -1 : 0);
+    const int ux = kex > kx ? 1 : 0, uy = key_ > ky ? 1 : 0, uz = kez > kz ? 1 : 0;
+    const double ix = 1.0 / dx, iy = 1.0 / dy, iz = 1.0 / dz;  // (of a non-candidate axis: never used)
+    for (unsigned base = 0; base < M; base += B) {  // a counted loop: at most ceil(M / B) rounds
+      if (map_cheb(kx, ky, kz, kex, key_, kez) <= shell) break;
+      unsigned long long key[B], h[B], cur[B];
+#pragma unroll
+      for (int j = 0; j < B; ++j) {
+        const bool live = base + j < M;
+        const bool thru = live && map_cheb(kx, ky, kz, kex, key_, kez) > shell;
+        // (a step that is not seen through: the empty mark, which the settling loop skips; its load reads slot 0 and is dropped)
+        key[j] = thru ? map_pack(kx, ky, kz) : kMapEmpty;
+        h[j] = thru ? map_hash(key[j]) & mask : 0ull;
+        cur[j] = keys[h[j]];
+        // the step: among the axes that have not arrived, the one whose next face is crossed first; a later axis wins only on a strictly
+        // smaller parameter.  The face's coordinate comes from the integer every time: nothing drifts
+        const bool cx = kx != kex, cy = ky != key_, cz = kz != kez;
+        const double tx = ((double)(kx + ux) * v - ox) * ix, ty = ((double)(ky + uy) * v - oy) * iy, tz = ((double)(kz + uz) * v - oz) * iz;
+        int ax = cx ? 0 : (cy ? 1 : 2);
+        double bt = cx ? tx : (cy ? ty : tz);
+        if (cx && cy && ty < bt) ax = 1, bt = ty;
+        if ((cx || cy) && cz && tz < bt) ax = 2, bt = tz;
+        kx += (live && ax == 0) ? sx : 0;
+        ky += (live && ax == 1) ? sy : 0;
+        kz += (live && ax == 2) ? sz : 0;
+      }
+#pragma unroll
+      for (int j = 0; j < B; ++j) {
+        if (key[j] == kMapEmpty) continue;
+        const unsigned long long hs = map_find_from(keys, mask, key[j], h[j], cur[j]);
+        if (hs != kMapEmpty) atomicAdd(&words[hs], 1u);
+      }
+    }
+  }
+  // the counts: per wavefront, per workgroup, then one atomic each on the counter's own line
+  n_used = wave_sum(n_used), n_skip = wave_sum(n_skip), n_steps = wave_sum(n_steps);
+  if ((threadIdx.x & 63) == 0) s_used[threadIdx.x >> 6] = n_used, s_skip[threadIdx.x >> 6] = n_skip, s_steps[threadIdx.x >> 6] = n_steps;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long u = 0, s = 0, t = 0;
+#pragma unroll
+    for (int w = 0; w < kCarveThreads / 64; ++w) u += s_used[w], s += s_skip[w], t += s_steps[w];
+    if (u) atomicAdd(cctr + kCarveUsed, u);
+    if (s) atomicAdd(cctr + kCarveSkip, s);
+    if (t) atomicAdd(cctr + kCarveSteps, t);
+  }
+}
+
+// what the words select: the occupied voxels that at least min_rays rays saw through and that no point of the call marked, and their
+// points, reduced per workgroup onto counter lines of the carve's own
+__global__ void __launch_bounds__(256) k_map_carve_count(const unsigned long long *keys, const long long *pay, uint64_t cap, const unsigned *words,
+                                                         unsigned min_rays, unsigned long long *cctr) {
+  __shared__ unsigned long long s_v[4], s_p[4];
+  unsigned long long nv = 0, np = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < cap; i += stride) {
+    const unsigned w = words[i];
+    if (keys[i] == kMapEmpty || (w & kCarveEnd) != 0u || w < min_rays) continue;
+    ++nv;
+    np += (unsigned long long)pay[4 * i + 3];
+  }
+  nv = wave_sum(nv), np = wave_sum(np);
+  if ((threadIdx.x & 63) == 0) s_v[threadIdx.x >> 6] = nv, s_p[threadIdx.x >> 6] = np;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    nv = s_v[0] + s_v[1] + s_v[2] + s_v[3], np = s_p[0] + s_p[1] + s_p[2] + s_p[3];
+    if (nv) {
+      atomicAdd(cctr + kCarveSelVox, nv);
+      atomicAdd(cctr + kCarveSelPts, np);
+    }
+  }
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 int map_alloc(wc_ctx *ctx, void **p, size_t bytes) {
   *p = nullptr;
@@ -833,10 +975,12 @@ extern "C" int wc_map_destroy(wc_ctx *ctx, wc_map *m) {
   wc_buf_release(ctx, m->b_tmp);
   wc_buf_release(ctx, m->b_cnt);
   wc_buf_release(ctx, m->b_lin);
+  wc_buf_release(ctx, m->b_carve);
   (void)hipStreamSynchronize(ctx->stream);  // (the pinned counters may still be the target of an enqueued copy)
   if (m->ev_ctr) (void)hipEventDestroy(m->ev_ctr);
   if (m->h_ctr) (void)hipHostFree(m->h_ctr);
   if (m->h_lin) (void)hipHostFree(m->h_lin);
+  if (m->h_carve) (void)hipHostFree(m->h_carve);
   delete m;
   return WC_OK;
 }
@@ -1239,5 +1383,55 @@ extern "C" int wc_map_crop(wc_ctx *ctx, wc_map *m, const double lo[3], const dou
   // the growth policy starts again from the exact count (map_sync_counters has cleared the pending copy)
   m->occ_known = kept;
   m->pts_since = m->pts_after_copy = 0;
+  return WC_OK;
+}
+
+// ---- carving free space along a sweep's rays (include/wildcat_hip.h: wc_map_carve) -------------------------------------------------
+extern "C" int wc_map_carve(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double origin[3], const wc_map_carve_params *params,
+                            wc_map_carve_result *h_out) {
+  wc_dev_guard dg_(ctx);
+  const wc_map_carve_params *p = params;
+  if (!map_ok(ctx, m) || !pts || !origin || !p || !h_out || pts->n >= ((uint64_t)1 << 31) ||
+      (pts->n && (!pts->xyz || pts->xyz_stride < 12 || pts->xyz_stride % 4 || (uintptr_t)pts->xyz % 4)))
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (n < 2^31), or a map of another context", __func__);
+  if (!(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2])) || !(p->min_range >= 0.0) ||
+      !(p->max_range >= p->min_range) || p->shell > 8 || p->min_rays < 1 || p->max_steps < 1 || p->max_steps > 65536 || p->reserved != 0)
+    return wc_fail(ctx, WC_ERR_ARG,
+                   "%s: origin not finite, or params out of range (0 <= min_range <= max_range, shell <= 8, min_rays >= 1, 1 <= max_steps <= 65536, "
+                   "reserved = 0)",
+                   __func__);
+  std::memset(h_out, 0, sizeof(*h_out));
+  if (pts->n == 0) return WC_OK;  // (no ray, no end mark: nothing is removed and nothing is launched)
+  map_ray_args A;
+  A.v = m->voxel;
+  A.min2 = p->min_range * p->min_range, A.max2 = p->max_range * p->max_range;
+  A.k0_ok = 1u;
+  for (int a = 0; a < 3; ++a) {
+    A.o[a] = origin[a];
+    const double f = std::floor(origin[a] / m->voxel);
+    if (!(f > -kMapKeyLim && f < kMapKeyLim)) A.k0_ok = 0u;
+  }
+  for (int a = 0; a < 3; ++a) A.k0[a] = A.k0_ok ? (int)std::floor(origin[a] / m->voxel) : 0;
+  A.shell = p->shell, A.max_steps = p->max_steps;
+  // the scratch: five counter lines, then one word per slot; zeroed per call
+  const size_t scratch = (size_t)kCarveCtrWords * 8 + (size_t)m->cap * 4;
+  WC_TRY(wc_ensure(ctx, m->b_carve, scratch));
+  if (!m->h_carve) WC_HIP(ctx, hipHostMalloc((void **)&m->h_carve, kCarveCtrWords * 8));
+  unsigned long long *cctr = (unsigned long long *)m->b_carve.p;
+  unsigned *words = (unsigned *)(cctr + kCarveCtrWords);
+  WC_HIP(ctx, hipMemsetAsync(m->b_carve.p, 0, scratch, ctx->stream));
+  const uint64_t blocks = (pts->n + kCarveThreads - 1) / kCarveThreads;
+  uint64_t grid = std::min<uint64_t>(blocks, (uint64_t)8 * m->cus);
+  if (ctx->dev.map_carve_groups > 0) grid = std::min<uint64_t>(blocks, (uint64_t)ctx->dev.map_carve_groups);  // (development option)
+  k_map_carve<kCarveBatch><<<(unsigned)grid, kCarveThreads, 0, ctx->stream>>>(*pts, A, m->keys, m->cap - 1, words, cctr);
+  WC_HIP(ctx, hipGetLastError());
+  // what the words select (this version reports it and leaves the map as it is: DESIGN 8.4)
+  const unsigned cgrid = (unsigned)std::min<uint64_t>((m->cap + 255) / 256, (uint64_t)8 * m->cus);
+  k_map_carve_count<<<cgrid, 256, 0, ctx->stream>>>(m->keys, m->pay, m->cap, words, p->min_rays, cctr);
+  WC_HIP(ctx, hipGetLastError());
+  WC_HIP(ctx, hipMemcpyAsync(m->h_carve, cctr, kCarveCtrWords * 8, hipMemcpyDeviceToHost, ctx->stream));
+  WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  h_out->rays_used = m->h_carve[kCarveUsed], h_out->rays_skipped = m->h_carve[kCarveSkip], h_out->steps = m->h_carve[kCarveSteps];
+  h_out->voxels_removed = m->h_carve[kCarveSelVox], h_out->points_removed = m->h_carve[kCarveSelPts];
   return WC_OK;
 }

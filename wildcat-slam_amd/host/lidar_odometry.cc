@@ -572,6 +572,21 @@ size_t LidarOdometry::CropMap(const double lo[3], const double hi[3]) {
   if (map_) WC_CALL(wc_map_crop(ctx_, map_, lo, hi, &removed));
   return removed;
 }
+bool LidarOdometry::CarveMap(const float *xyz, size_t n, const double origin[3], const wc_map_carve_params &params, wc_map_carve_result *result) {
+  if (!map_ || !origin || (n && !xyz)) return false;
+  void *d_xyz = nullptr;
+  if (n) {
+    WC_CALL(wc_dev_alloc(ctx_, n * 3 * sizeof(float), &d_xyz));
+    WC_CALL(wc_h2d(ctx_, d_xyz, xyz, n * 3 * sizeof(float)));
+  }
+  const wc_points desc{d_xyz, nullptr, 12, 0, n};
+  wc_map_carve_result r;
+  const int rc = wc_map_carve(ctx_, map_, &desc, origin, &params, &r);  // (an argument the library refuses is the caller's: no abort)
+  if (d_xyz) WC_CALL(wc_dev_free(ctx_, d_xyz));
+  if (rc != WC_OK) return false;
+  if (result) *result = r;
+  return true;
+}
 bool LidarOdometry::SetMapKeepRadius(double radius) {
   if (!(radius >= 0.0)) return false;
   config_.map_keep_radius = radius;

@@ -108,6 +108,9 @@ class LidarOdometry {
   bool LinearizeAgainstMap(const float *xyz, size_t n, const double T[12], const wc_map_reg_params &params, wc_map_normal_eq *out,
                            wc_map_reg_row *rows);
   bool SetMapKeepRadius(double radius);  // config().map_keep_radius = radius; false: negative or NaN
+  // wc_map_carve for the rays origin -> each of n host points (xyz: n x 3 floats, the map's frame): *result (may be null) as the library
+  // leaves it - what the rays select; the map is not modified.  false without a map or with arguments the library refuses
+  bool CarveMap(const float *xyz, size_t n, const double origin[3], const wc_map_carve_params &params, wc_map_carve_result *result);
   // wall time [ms] of the last completed sweep's map step (the undistortion when fill_outputs does not already form it, the insert's
   // enqueue - its kernel runs behind on the stream - and, with map_keep_radius, the crop, which waits).  Not part of last_stage_ms()
   double last_map_ms() const { return last_map_ms_; }

@@ -598,6 +598,15 @@ def map_align_opts(params, max_iterations=20, tol_rot=1e-6, tol_trans=1e-6, min_
     return R.MapAlignOpts(params, int(max_iterations), int(min_used), float(tol_rot), float(tol_trans), float(min_pivot))
 
 
+def map_carve_params(max_range, min_range=0.0, shell=1, min_rays=1, max_steps=4096):
+    """wc_map_carve_params"""
+    return R.MapCarveParams(float(min_range), float(max_range), int(shell), int(min_rays), int(max_steps), 0)
+
+
+def _carve_dict(r):
+    return {k: int(getattr(r, k)) for k in ("rays_used", "rays_skipped", "steps", "voxels_removed", "points_removed")}
+
+
 def _pose12(T):
     T = np.ascontiguousarray(np.asarray(T, np.float64).reshape(-1)[:12])
     assert T.size == 12, "T: 3 x 4 (or 4 x 4) row-major"
@@ -673,6 +682,24 @@ class PointMap:
         n = C.c_uint64(0)
         self.ctx._ck(self.lib.wc_map_crop(self.ctx.h, self.h, lo, hi, C.byref(n)))
         return int(n.value)
+
+    def carve_device(self, desc, origin, params):
+        """points already in HBM (a wc_points descriptor) as the ends of rays from origin (wc_map_carve) -> the result as a dict"""
+        o = (C.c_double * 3)(*[float(x) for x in origin])
+        res = R.MapCarveResult()
+        self.ctx._ck(self.lib.wc_map_carve(self.ctx.h, self.h, C.byref(desc), o, C.byref(params), C.byref(res)))
+        return _carve_dict(res)
+
+    def carve(self, points, origin, max_range, min_range=0.0, shell=1, min_rays=1, max_steps=4096):
+        """POINT records or an (n, 3) float32 array (uploaded for the call): the voxels that at least min_rays of the rays origin -> point
+        pass through, farther than `shell` voxels from the ray's end, and in which no point of the call lies, are selected and counted
+        (wc_map_carve; this version does not remove them) -> dict(rays_used, rays_skipped, steps, voxels_removed, points_removed)"""
+        d, desc = self._upload(points)
+        try:
+            return self.carve_device(desc, origin, map_carve_params(max_range, min_range, shell, min_rays, max_steps))
+        finally:
+            if d:
+                d.free()
 
     def size(self):
         """-> (voxels, points inserted)"""
@@ -951,6 +978,16 @@ class Odometry:
         rc = self.lib.wc_odom_set_map_keep_radius(self.h, C.c_double(radius))
         if rc != 0:
             raise WildcatError(rc, "wc_odom_set_map_keep_radius(%r)" % radius)
+
+    def map_carve(self, xyz, origin, max_range, min_range=0.0, shell=1, min_rays=1, max_steps=4096):
+        """wc_map_carve of the facade's map with the rows of xyz ((n, 3) float32) as the ends of rays from origin (LidarOdometry::CarveMap)
+        -> the result as a dict (what the rays select; the map is not modified), or None without a map or with arguments the library refuses"""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        o = (C.c_double * 3)(*[float(x) for x in origin])
+        params, res = map_carve_params(max_range, min_range, shell, min_rays, max_steps), R.MapCarveResult()
+        if not self.lib.wc_odom_map_carve(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), o, C.byref(params), C.byref(res)):
+            return None
+        return _carve_dict(res)
 
     def map_ms(self):
         """wall time [ms] of the last sweep's map step (not part of stage_ms())"""

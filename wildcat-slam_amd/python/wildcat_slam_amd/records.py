@@ -174,4 +174,30 @@ class MapAlignSummary(C.Structure):
     ]
 
 
+class MapCarveParams(C.Structure):
+    """wc_map_carve_params"""
+
+    _fields_ = [
+        ("min_range", C.c_double),
+        ("max_range", C.c_double),
+        ("shell", C.c_uint32),
+        ("min_rays", C.c_uint32),
+        ("max_steps", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class MapCarveResult(C.Structure):
+    """wc_map_carve_result"""
+
+    _fields_ = [
+        ("rays_used", C.c_uint64),
+        ("rays_skipped", C.c_uint64),
+        ("steps", C.c_uint64),
+        ("voxels_removed", C.c_uint64),
+        ("points_removed", C.c_uint64),
+    ]
+
+
+assert C.sizeof(MapCarveParams) == 32 and C.sizeof(MapCarveResult) == 40
 assert C.sizeof(MapRegParams) == 32 and C.sizeof(MapAlignOpts) == 64 and C.sizeof(MapAlignSummary) == 88
