@@ -16,17 +16,9 @@ import time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "wildcat-slam_amd", "python"))
 import numpy as np  # noqa: E402
 
+from map_bench_common import timed  # noqa: E402
 from wildcat_slam_amd import lib, synth  # noqa: E402
 from wildcat_slam_amd import records as R  # noqa: E402
-
-
-def timed(ctx, fn, reps, warmup=3):
-    for _ in range(warmup):
-        fn(None)
-    out = []
-    for _ in range(reps):
-        out.append(fn(ctx))
-    return float(np.median(out)), float(np.min(out))
 
 
 def map_section(ctx, reps):
@@ -39,15 +31,14 @@ def map_section(ctx, reps):
         m = ctx.map_create(v)
         insert = ctx.lib.wc_map_insert
 
-        def one(c, prefill):
+        def one(timer, prefill):
             ctx._ck(ctx.lib.wc_map_clear(ctx.h, m.h))
             for k in range(prefill):
                 ctx._ck(insert(ctx.h, m.h, C.byref(desc[k]), None))
             m.size()  # (the occupied count exact: the timed call never grows the table after the warm-up)
-            if c:
-                c.timer_start()
+            if timer:
+                ctx.timer_start()
             ctx._ck(insert(ctx.h, m.h, C.byref(desc[10]), None))
-            return c.timer_stop_ms() if c else ctx.sync()
 
         empty = timed(ctx, lambda c: one(c, 0), reps)
         voxels_1 = m.size()[0]
@@ -61,18 +52,17 @@ def map_section(ctx, reps):
         n = m.size()[0]
         bx, bc, bk = ctx.alloc(12 * n), ctx.alloc(4 * n), ctx.alloc(12 * n)
 
-        def exp(c):
-            if c:
-                c.timer_start()
+        def exp(timer):
+            if timer:
+                ctx.timer_start()
             rc, _ = m.export_device(bx, bc, bk, n)
             ctx._ck(rc)
-            return c.timer_stop_ms() if c else ctx.sync()
 
         ex = timed(ctx, exp, reps)
         info = m.info()
         out[f"v{v}"] = dict(
-            insert_ms_empty=empty[0], insert_ms_empty_min=empty[1], insert_ms_10_sweeps=full[0], insert_ms_10_sweeps_min=full[1],
-            export_ms=ex[0], voxels_one_sweep=voxels_1, voxels_10_sweeps=voxels_10, voxels_11_sweeps=voxels_11,
+            insert_ms_empty=empty["median"], insert_ms_empty_min=empty["min"], insert_ms_10_sweeps=full["median"], insert_ms_10_sweeps_min=full["min"],
+            export_ms=ex["median"], voxels_one_sweep=voxels_1, voxels_10_sweeps=voxels_10, voxels_11_sweeps=voxels_11,
             new_voxels_in_timed_insert=voxels_11 - voxels_10, table_slots=info["slots"], table_growths=info["growths"],
             bytes_per_point_input=48, bytes_per_point_table_lower_bound=round(40.0 * voxels_1 / len(sweeps[10]), 2))
         for b in (bx, bc, bk):

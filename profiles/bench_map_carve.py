@@ -23,6 +23,7 @@ sys.path.insert(0, os.path.join(HERE, "..", "tests"))
 import numpy as np  # noqa: E402
 
 import map_carve_ref as CR  # noqa: E402
+from map_bench_common import xyz_of  # noqa: E402
 from wildcat_slam_amd import lib, synth  # noqa: E402
 from wildcat_slam_amd import records as R  # noqa: E402
 
@@ -60,7 +61,7 @@ def main():
     desc = [R.Points(d.ptr, d.ptr + 24, 48, 48, len(s)) for d, s in zip(dev, sweeps)]
     d_rays = ctx.to_device(rays)
     ray_desc = {"100k": R.Points(d_rays.ptr, 0, 480, 0, (len(rays) + 9) // 10), "1M": R.Points(d_rays.ptr, 0, 48, 0, len(rays))}
-    xyz = np.stack([rays["x"], rays["y"], rays["z"]], -1).astype(np.float32)
+    xyz = xyz_of(rays)
     out["points_per_sweep"] = len(rays)
     for v in (0.2, 0.05):
         m = ctx.map_create(v)

@@ -24,32 +24,9 @@ sys.path.insert(0, os.path.join(HERE, "..", "tests"))
 import numpy as np  # noqa: E402
 
 import map_query_ref as Q  # noqa: E402
+from map_bench_common import note, timed, xyz_of  # noqa: E402
 from wildcat_slam_amd import lib, synth  # noqa: E402
 from wildcat_slam_amd import records as R  # noqa: E402
-
-
-T0 = time.perf_counter()
-
-
-def note(*what):
-    """progress on stderr (stdout carries the JSON object alone)"""
-    print("[%7.1f s]" % (time.perf_counter() - T0), *what, file=sys.stderr, flush=True)
-
-
-def timed(ctx, fn, reps, warmup=3):
-    for _ in range(warmup):
-        fn()
-    ctx.sync()
-    out = []
-    for _ in range(reps):
-        ctx.timer_start()
-        fn()
-        out.append(ctx.timer_stop_ms())
-    return float(np.median(out)), float(np.min(out))
-
-
-def xyz_of(p):
-    return np.stack([p["x"], p["y"], p["z"]], -1).astype(np.float32)
 
 
 def map_section(ctx, reps, baseline):
@@ -72,7 +49,9 @@ def map_section(ctx, reps, baseline):
             for k in range(11):
                 ctx._ck(ctx.lib.wc_map_insert(ctx.h, m.h, C.byref(desc[k]), None))  # (back to back, as the facade inserts)
 
-        def nearest():
+        def nearest(timer):
+            if timer:
+                ctx.timer_start()
             ctx._ck(ctx.lib.wc_map_nearest(ctx.h, m.h, C.byref(q_desc), C.c_double(v), C.c_void_p(d_hits.ptr), None))
 
         fill()
@@ -92,7 +71,8 @@ def map_section(ctx, reps, baseline):
             if state == "compact":
                 m.crop((-inf,) * 3, (inf,) * 3)
             info = m.info()
-            med, mn = timed(ctx, nearest, reps)
+            t = timed(ctx, nearest, reps)
+            med, mn = t["median"], t["min"]
             found = m.nearest_device(q_desc, v, d_hits)
             note("v", v, state, "nearest_ms", med, "slots", info["slots"])
             entry[state] = dict(table_slots=info["slots"], table_bytes=info["bytes"], nearest_ms=med, nearest_ms_min=mn,

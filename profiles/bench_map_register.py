@@ -19,19 +19,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", "wildcat-slam_amd", "python"))
 import numpy as np  # noqa: E402
 
+from map_bench_common import timed, xyz_of  # noqa: E402
 from wildcat_slam_amd import lib, synth  # noqa: E402
 from wildcat_slam_amd import records as R  # noqa: E402
-
-
-def timed(ctx, fn, reps, warmup=3):
-    for _ in range(warmup):
-        fn(False)
-        ctx.sync()
-    out = []
-    for _ in range(reps):
-        fn(True)
-        out.append(ctx.timer_stop_ms())
-    return dict(median=float(np.median(out)), min=float(np.min(out)))
 
 
 def main():
@@ -54,7 +44,7 @@ def main():
     th = np.linalg.norm(w)
     Rm = np.eye(3) + np.sin(th) / th * K + (1 - np.cos(th)) / th**2 * (K @ K)
     t = np.array([0.02, -0.01, 0.005])
-    xyz = np.stack([query["x"], query["y"], query["z"]], -1).astype(np.float64)
+    xyz = xyz_of(query).astype(np.float64)
     scan = ((xyz - t) @ Rm).astype(np.float32)
     d_s = ctx.to_device(scan)
     s_desc = R.Points(d_s.ptr, 0, 12, 0, len(scan))

@@ -17,20 +17,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", "wildcat-slam_amd", "python"))
 import numpy as np  # noqa: E402
 
+from map_bench_common import timed  # noqa: E402
 from wildcat_slam_amd import lib, synth  # noqa: E402
 from wildcat_slam_amd import records as R  # noqa: E402
-
-
-def timed(ctx, fn, reps, warmup=3):
-    """fn(timer): runs its untimed preparation, starts the timer when given one, runs the timed call"""
-    for _ in range(warmup):
-        fn(False)
-        ctx.sync()
-    out = []
-    for _ in range(reps):
-        fn(True)
-        out.append(ctx.timer_stop_ms())
-    return dict(median=float(np.median(out)), min=float(np.min(out)))
 
 
 def main():

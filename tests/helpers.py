@@ -1,6 +1,29 @@
 """Shared comparison helpers for the parity tests."""
 import numpy as np
 
+from wildcat_slam_amd import records as R
+from wildcat_slam_amd import synth
+
+
+def xyz_of(points):
+    """POINT records -> their packed (n, 3) float32 coordinates"""
+    return np.stack([points["x"], points["y"], points["z"]], -1).astype(np.float32)
+
+
+def point_records(xyz):
+    """the 48-byte layout of packed xyz"""
+    return synth.make_points(np.asarray(xyz, np.float32), np.zeros(len(xyz)))
+
+
+def check_unreadable_points_refused(gpu, call, n=8):
+    """call(wc_points descriptor) -> return code of a map entry that takes a cloud: WC_ERR_ARG (11) for n points with a stride under 12
+    bytes, with a stride that is no multiple of 4 and with an xyz that is not 4-byte aligned.  (The buffer holds what any of the three
+    would address.)"""
+    d = gpu.to_device(np.zeros((n, 4), np.float32))
+    for what, desc in (("stride < 12", R.Points(d.ptr, 0, 8, 0, n)), ("stride % 4", R.Points(d.ptr, 0, 14, 0, n)), ("xyz % 4", R.Points(d.ptr + 2, 0, 12, 0, n))):
+        assert call(desc) == 11, what
+    d.free()
+
 
 def id_tuples(ids):
     return [tuple(r) for r in np.stack([ids["kx"], ids["ky"], ids["kz"], ids["node"].astype(np.int64)], -1).tolist()]

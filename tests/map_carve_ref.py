@@ -9,14 +9,9 @@ from fractions import Fraction
 
 import numpy as np
 
-KEY_LIM = 2**20
+from map_query_ref import KEY_LIM, pack
+
 RESULT_FIELDS = ("rays_used", "rays_skipped", "steps", "voxels_removed", "points_removed")
-
-
-def pack(k):
-    """(n, 3) voxel indices -> the packed 63-bit key: ascending packed key = ascending (kx, ky, kz)"""
-    k = np.asarray(k, np.int64).reshape(-1, 3)
-    return ((k[:, 0] + KEY_LIM) << 42) | ((k[:, 1] + KEY_LIM) << 21) | (k[:, 2] + KEY_LIM)
 
 
 def _keys_of(x64, v):
@@ -152,13 +147,6 @@ def carve(map_keys, map_counts, points, origin, v, max_range, min_range=0.0, she
     res = dict(rays_used=int(r["used"].sum()), rays_skipped=int(n - r["used"].sum()), steps=int(r["M"].sum()),
                voxels_removed=int((~keep).sum()), points_removed=int(cnt[~keep].sum()))
     return keep, res
-
-
-def pow2_at_least(x):
-    c = 1
-    while c < x:
-        c <<= 1
-    return c
 
 
 # ---- the scene of the tests: a box room seen from inside, and phantom points in its free space ----------------------------------------

@@ -12,7 +12,7 @@ KEY_LIM = 2**20
 
 def pack(k):
     """(n, 3) voxel indices -> the packed 63-bit key: ascending packed key = ascending (kx, ky, kz)"""
-    k = np.asarray(k, np.int64)
+    k = np.asarray(k, np.int64).reshape(-1, 3)
     return ((k[:, 0] + KEY_LIM) << 42) | ((k[:, 1] + KEY_LIM) << 21) | (k[:, 2] + KEY_LIM)
 
 

@@ -10,6 +10,7 @@ import pytest
 
 import map_carve_ref as CR
 import map_query_ref as Q
+from helpers import check_unreadable_points_refused, point_records as _records, xyz_of as _xyz
 from test_map_gpu import _drive
 from wildcat_slam_amd import lib
 from wildcat_slam_amd import records as R
@@ -20,14 +21,6 @@ pytestmark = pytest.mark.gpu
 WC_ERR_ARG = 11
 SHELLS, MIN_RAYS = (0, 1, 2), (1, 2, 5)
 BAD = np.array([[np.nan, 0, 0], [0, np.inf, 0], [0, 0, -np.inf], [3e38, 0, 0], [1, -3e6, 1]], np.float32)
-
-
-def _xyz(points):
-    return np.stack([points["x"], points["y"], points["z"]], -1).astype(np.float32)
-
-
-def _records(xyz):
-    return synth.make_points(np.asarray(xyz, np.float32), np.zeros(len(xyz)))
 
 
 @pytest.fixture(scope="module")
@@ -249,6 +242,7 @@ def test_argument_errors(gpu, room):
                    (0.0, 30.0, 1, 1, 65537, 0), (0.0, 30.0, 1, 1, 4096, 1)):
         assert call(par=C.byref(R.MapCarveParams(*fields))) == WC_ERR_ARG, fields
     assert call(pts=C.byref(R.Points(d.ptr, 0, 12, 0, 2**31))) == WC_ERR_ARG
+    check_unreadable_points_refused(gpu, lambda bad: call(pts=C.byref(bad)))
     other = lib.Context(0)
     assert gpu.lib.wc_map_carve(other.h, m.h, C.byref(desc), o, C.byref(good), C.byref(res)) == WC_ERR_ARG
     other.close()

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from helpers import check_unreadable_points_refused, xyz_of as _xyz
 from test_map_cpu import centroids_close, downsample_voxel
 from wildcat_slam_amd import records as R
 from wildcat_slam_amd import synth
@@ -14,10 +15,6 @@ pytestmark = pytest.mark.gpu
 
 VOXELS = (0.01, 0.05, 0.2, float(np.float32(0.8)), 4.0)
 WC_ERR_CAPACITY, WC_ERR_ARG = 1, 11
-
-
-def _xyz(points):
-    return np.stack([points["x"], points["y"], points["z"]], -1).astype(np.float32)
 
 
 def _check(got, points_xyz, v):
@@ -143,6 +140,8 @@ def test_map_api_edges(gpu, clouds):
     rc, got = a.export_device(d_xyz, d_cnt, None, n)
     assert rc == 0 and got == n
     assert d_xyz.download(np.float32, 3 * n).tobytes() == first[0].tobytes()
+    check_unreadable_points_refused(gpu, lambda bad: lib.wc_map_insert(gpu.h, a.h, C.byref(bad), None))
+    assert a.size()[0] == n
     a.close()
     b.close()
 

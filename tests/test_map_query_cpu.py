@@ -8,16 +8,13 @@ import numpy as np
 import pytest
 
 import map_query_ref as Q
+from helpers import xyz_of as _xyz
 from test_map_cpu import downsample_voxel
 from wildcat_slam_amd import records as R
 from wildcat_slam_amd import synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 WC_ERR_ARG = 11
-
-
-def _xyz(points):
-    return np.stack([points["x"], points["y"], points["z"]], -1).astype(np.float32)
 
 
 def test_header_declares_and_library_exports_the_query_entry_points():

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import map_query_ref as Q
+from helpers import check_unreadable_points_refused, point_records as _records, xyz_of as _xyz
 from test_map_cpu import centroids_close, downsample_voxel
 from test_map_gpu import _drive
 from wildcat_slam_amd import records as R
@@ -17,15 +18,6 @@ pytestmark = pytest.mark.gpu
 VOXELS = (0.05, 0.2, float(np.float32(0.8)))
 WC_ERR_ARG = 11
 BAD = np.array([[np.nan, 0, 0], [0, np.inf, 0], [0, 0, -np.inf], [3e38, 0, 0], [1, -3e38, 1]], np.float32)
-
-
-def _xyz(points):
-    return np.stack([points["x"], points["y"], points["z"]], -1).astype(np.float32)
-
-
-def _records(xyz):
-    """the 48-byte layout of packed xyz"""
-    return synth.make_points(np.asarray(xyz, np.float32), np.zeros(len(xyz)))
 
 
 def _same(a, b):
@@ -253,6 +245,7 @@ def test_query_and_crop_api_edges(gpu, clouds):
         assert lib.wc_map_nearest(gpu.h, a.h, C.byref(desc), C.c_double(d), C.c_void_p(d_hits.ptr), C.byref(n)) == WC_ERR_ARG
     assert lib.wc_map_nearest(gpu.h, None, C.byref(desc), C.c_double(1.0), C.c_void_p(d_hits.ptr), C.byref(n)) == WC_ERR_ARG
     assert lib.wc_map_nearest(gpu.h, a.h, C.byref(desc), C.c_double(1.0), None, C.byref(n)) == WC_ERR_ARG  # NULL d_hits, n > 0
+    check_unreadable_points_refused(gpu, lambda bad: lib.wc_map_nearest(gpu.h, a.h, C.byref(bad), C.c_double(1.0), C.c_void_p(d_hits.ptr), C.byref(n)))
     empty = R.Points(0, 0, 12, 0, 0)
     assert lib.wc_map_nearest(gpu.h, a.h, C.byref(empty), C.c_double(1.0), None, C.byref(n)) == 0 and n.value == 0
     assert len(a.nearest(np.zeros((0, 3), np.float32))) == 0

@@ -9,8 +9,8 @@ import pytest
 
 import map_register_ref as G
 from extract_ref import LD
+from helpers import check_unreadable_points_refused, point_records as _records, xyz_of as _xyz
 from test_map_gpu import _drive
-from test_map_query_gpu import _records
 from test_map_register_ref import P, scan_of, true_pose
 from wildcat_slam_amd import lib as L
 from wildcat_slam_amd import records as R
@@ -27,10 +27,6 @@ N_SCAN = 256 * 33 + 7  # 34 tiles: a second stage with more than 32 partials, a 
 LOG1P_EPS = 2
 # roundings of one term of cost besides its additions: (w2 d) d (2), s / a^2 (1), a^2 * (1), the condition number of log1p is <= 1
 COST_ROUNDINGS = 4
-
-
-def _xyz(points):
-    return np.stack([points["x"], points["y"], points["z"]], -1).astype(np.float32)
 
 
 def _params(p):
@@ -316,6 +312,7 @@ def test_refused_arguments_leave_the_context_usable(gpu, world):
     assert rc(ctx=other) == WC_ERR_ARG  # a map of another context
     other.close()
     assert rc(mp=None) == WC_ERR_ARG and rc(prm=None) == WC_ERR_ARG
+    check_unreadable_points_refused(gpu, lambda bad: rc(pts=bad))
     for kw in (dict(max_dist=0.0), dict(max_dist=-1.0), dict(max_dist=np.nan), dict(min_points=2), dict(sigma0=0.0), dict(sigma0=np.nan),
                dict(sigma0=np.inf), dict(sigma0=-1.0), dict(cauchy_a=-0.4), dict(cauchy_a=np.nan), dict(cauchy_a=np.inf)):
         base = dict(max_dist=VS, min_points=3, sigma0=0.05 / 6, cauchy_a=0.4)

@@ -11,7 +11,8 @@ import pytest
 
 import map_register_ref as G
 from extract_ref import LD
-from test_map_surfel_ref import _c_fields, _xyz
+from helpers import xyz_of as _xyz
+from test_map_surfel_ref import _c_fields
 from wildcat_slam_amd import records as R
 from wildcat_slam_amd import synth
 

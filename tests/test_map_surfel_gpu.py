@@ -10,8 +10,9 @@ import pytest
 import map_query_ref as Q
 import map_surfel_ref as S
 from extract_ref import LD
+from helpers import point_records as _records, xyz_of as _xyz
 from test_map_gpu import _drive
-from test_map_query_gpu import BAD, _queries, _records
+from test_map_query_gpu import BAD, _queries
 from wildcat_slam_amd import records as R
 from wildcat_slam_amd import synth
 
@@ -21,10 +22,6 @@ VOXELS = (0.05, 0.2, float(np.float32(0.8)))
 WC_ERR_CAPACITY, WC_ERR_ARG = 1, 11
 EPS = 2.0**-53
 FRACTION_VOXELS = 50_000  # above this many voxels the integer / longdouble steps run on a seeded subset
-
-
-def _xyz(points):
-    return np.stack([points["x"], points["y"], points["z"]], -1).astype(np.float32)
 
 
 def _map(gpu, xyz, v, **kw):

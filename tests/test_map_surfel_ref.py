@@ -8,14 +8,11 @@ import pytest
 
 import map_surfel_ref as S
 from extract_ref import LD
+from helpers import xyz_of as _xyz
 from wildcat_slam_amd import records as R
 from wildcat_slam_amd import synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def _xyz(points):
-    return np.stack([points["x"], points["y"], points["z"]], -1).astype(np.float32)
 
 
 @pytest.mark.parametrize("name,v", [("g1_room", 0.2), ("g1_room", float(np.float32(0.8))), ("g2_lattice", 0.05), ("g2_lattice", 0.2)])

@@ -17,12 +17,14 @@
 //                   same, the tile's voxels are pre-aggregated in an LDS hash (1024 slots, at most half full), then ONE global probe
 //                   and four integer atomic adds per distinct voxel of the tile; counters once per workgroup.  <true, .>: the nine
 //                   moment sums ride along (nine more LDS words per hash slot, thirteen global atomics per distinct voxel)
-//   k_map_rehash    growth: every occupied slot of the old table into the new one (distinct keys: plain stores of the payload)
+//   k_map_rehash<SEL>  growth, crop: the occupied slots of the old table that a selector (map_sel_all, map_sel_box; map_sel_carve for
+//                   the count) selects into the new one (distinct keys: plain stores of the payload) - map_replace_table
 //   k_map_compact   export: occupied slots -> (key, slot) pairs (LDS staging, one atomic per workgroup); rocPRIM radix sort by key
 //   k_map_centroids export: centroid = r + sum / (count * 2^32) in fp64, rounded once to float; count; key (optional)
 //   k_map_nearest   query: one lane per query; the first-slot key loads of the 27 voxels around the query's own are issued nine at a
 //                   time before any is examined, payload loads and divisions only for the occupied ones; read-only probes, no CAS
-//   k_map_crop_count / k_map_rehash<true>  crop: kept voxels and points counted per workgroup, then only the kept keys rehashed
+//   k_map_count<SEL>  the selected voxels and their points, counted per workgroup: a crop's kept ones (then k_map_rehash<map_sel_box>),
+//                   a carve's seen-through ones
 //   k_map_surfels   surfel export: one lane per sorted voxel: map_plane_of (exact 128-bit covariance numerator, fx_eig3) -> wc_map_surfel
 //   k_map_nearest<true>  plane query: the same search, then map_plane_of for the winning voxel only -> wc_map_plane_hit
 //   k_map_linearize / k_map_lin_reduce  registration: the plane query behind a pose, reduced to the point-to-plane normal equations in a
@@ -30,7 +32,9 @@
 //   k_map_carve    carving: one lane per ray from the call's origin to a point: the end voxel's word gets its mark, then the counted voxel
 //                   walk, eight steps ahead of the probes: keys, hashes and shell tests of a batch, its first-slot key loads issued
 //                   together, then the chains (read-only) and one no-return atomic add per occupied voxel seen through;
-//                   k_map_carve_count then counts the voxels the words select: wc_map_carve (which reports and does not remove yet)
+//                   k_map_count<map_sel_carve> then counts the voxels the words select: wc_map_carve (which reports and does not remove yet)
+// Shared pieces: map_voxel_of (the voxel-index rule, host and device), map_find_from (the read-only probe chain), block_count (a
+// workgroup's counters), map_points_ok (a wc_points argument), map_replace_table (new table, rehash, free the old one)
 // Growth policy: before an insert of n points the host takes an upper bound B of the occupied slots (the exact count of the last
 // completed insert's read-back plus every point inserted after it); when 2 (B + n) > cap the table is rehashed into the smallest power
 // of two >= 2 (B + n) slots.  The table is therefore at most half full at every probe, and an insert never runs out of room.
@@ -74,8 +78,7 @@ namespace {
 #include "fx_eig3.h"
 
 constexpr int kMapThreads = 256;
-constexpr int kMapPts = 2;                         // consecutive points per lane
-constexpr int kMapTile = kMapThreads * kMapPts;    // points per tile
+constexpr int kMapPts = 2;                         // consecutive points per lane (a tile: kMapThreads times as many)
 constexpr int kMapMom = 9;                         // moment words per slot of a WC_MAP_MOMENTS map
 constexpr int kMapMomPts = 1;                      // points per lane of the moments insert (the alternative form: DESIGN, "Map surfels")
 constexpr unsigned long long kMapEmpty = ~0ull;
@@ -121,6 +124,36 @@ __device__ __forceinline__ T wave_sum(T x) {
   for (int o = 32; o; o >>= 1) x += __shfl_down(x, o);
   return x;
 }
+// N per-lane counts of a workgroup of THREADS lanes, each onto its counter: the sum over the wavefront, one LDS word per wavefront and
+// count, thread 0 adds them, and one atomic per counter (each on a line of its own) when the sum is non-zero.  Integers: no order matters
+template <int THREADS, class T, int N>
+__device__ __forceinline__ void block_count(const T (&x)[N], unsigned long long *const (&ctr)[N]) {
+  __shared__ T s_part[N][THREADS / 64];
+#pragma unroll
+  for (int c = 0; c < N; ++c) {
+    const T w = wave_sum(x[c]);
+    if ((threadIdx.x & 63) == 0) s_part[c][threadIdx.x >> 6] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+      T t = 0;
+#pragma unroll
+      for (int w = 0; w < THREADS / 64; ++w) t += s_part[c][w];
+      if (t) atomicAdd(ctr[c], (unsigned long long)t);
+    }
+  }
+}
+
+// VoxelLoc (surfel_extraction.h:59-64): k = floor((double)p / v) per axis, true fp64 division.  false: the point has no voxel - NaN, inf
+// and |k| >= 2^20 fail the strict compares - and k is 0 on every axis
+__host__ __device__ __forceinline__ bool map_voxel_of(double x, double y, double z, double v, int &kx, int &ky, int &kz) {
+  const double fx = floor(x / v), fy = floor(y / v), fz = floor(z / v);
+  const bool ok = fx > -kMapKeyLim && fx < kMapKeyLim && fy > -kMapKeyLim && fy < kMapKeyLim && fz > -kMapKeyLim && fz < kMapKeyLim;
+  kx = ok ? (int)fx : 0, ky = ok ? (int)fy : 0, kz = ok ? (int)fz : 0;
+  return ok;
+}
 
 // one global probe: the slot of `key`, claimed if it is new (fresh += 1).  The table is at most half full, so the loop ends; the bound
 // on its length only guards against a broken invariant (the key is then dropped and ctr[kCtrLost] counts it)
@@ -139,6 +172,16 @@ __device__ __forceinline__ unsigned long long map_slot(unsigned long long *keys,
     h = (h + 1) & mask;
   }
   return kMapEmpty;
+}
+// the read-only probe chain of `key` from its first slot h, whose key c has been loaded: linear probing past foreign keys; true: h is the
+// key's slot; false: the key is absent
+__device__ __forceinline__ bool map_find_from(const unsigned long long *keys, unsigned long long mask, unsigned long long key,
+                                              unsigned long long &h, unsigned long long c) {
+  for (unsigned long long probe = 0; c != key && c != kMapEmpty && probe < mask; ++probe) {
+    h = (h + 1) & mask;
+    c = keys[h];
+  }
+  return c == key;
 }
 
 template <int LDS>
@@ -168,7 +211,7 @@ __device__ __forceinline__ void lds_add_mom(unsigned long long *lm, unsigned s, 
 template <bool MOM, int PTS>
 __global__ void __launch_bounds__(kMapThreads) k_map_insert(wc_points pts, double v, unsigned long long *keys, long long *pay, long long *mom,
                                                             unsigned long long mask, unsigned long long *ctr) {
-  // (the file-scope names, per instantiation; kMapLds: LDS hash slots - a tile's voxels fill at most half of it)
+  // (kMapTile: points per tile; kMapLds: LDS hash slots - a tile's voxels fill at most half of it)
   constexpr int kMapPts = PTS, kMapTile = kMapThreads * PTS, kMapLds = 2 * kMapTile;
   __shared__ unsigned long long lk[kMapLds];
   __shared__ unsigned long long ls[3 * kMapLds];
@@ -202,14 +245,12 @@ __global__ void __launch_bounds__(kMapThreads) k_map_insert(wc_points pts, doubl
       if (i >= pts.n) break;
       const float *f = (const float *)((const char *)pts.xyz + i * pts.xyz_stride);
       const double x = (double)f[0], y = (double)f[1], z = (double)f[2];
-      // VoxelLoc (surfel_extraction.h:59-64): floor((double)p / v), true fp64 division; NaN / inf / |k| >= 2^20 fail the compares
-      const double fx = floor(x / v), fy = floor(y / v), fz = floor(z / v);
-      if (!(fx > -kMapKeyLim && fx < kMapKeyLim && fy > -kMapKeyLim && fy < kMapKeyLim && fz > -kMapKeyLim && fz < kMapKeyLim)) {
+      int kx, ky, kz;
+      if (!map_voxel_of(x, y, z, v, kx, ky, kz)) {
         ++n_rej;
         continue;
       }
       ++n_ok;
-      const int kx = (int)fx, ky = (int)fy, kz = (int)fz;
       const unsigned long long key = map_pack(kx, ky, kz);
       const long long qx = llrint((x - map_ref(kx, v)) * kMapUnit), qy = llrint((y - map_ref(ky, v)) * kMapUnit),
                       qz = llrint((z - map_ref(kz, v)) * kMapUnit);
@@ -278,31 +319,44 @@ __global__ void __launch_bounds__(kMapThreads) k_map_insert(wc_points pts, doubl
   }
 }
 
-// an inclusive range of voxel indices per axis (wc_map_crop)
-struct map_box {
-  int lo[3], hi[3];
+// Selectors: a predicate on an occupied slot (its key, its index), passed by value to k_map_rehash (the slots that move) and k_map_count
+// (the slots that are counted).  Every occupied slot (growth: no test is compiled)
+struct map_sel_all {
+  __device__ bool operator()(unsigned long long, uint64_t) const { return true; }
 };
-__device__ __forceinline__ bool map_in_box(unsigned long long key, const map_box &b) {
-  bool in = true;
+// an inclusive range of voxel indices per axis (wc_map_crop)
+struct map_sel_box {
+  int lo[3], hi[3];
+  __device__ bool operator()(unsigned long long key, uint64_t) const {
+    bool in = true;
 #pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const int k = map_unpack(key, a);
-    in = in && k >= b.lo[a] && k <= b.hi[a];
+    for (int a = 0; a < 3; ++a) {
+      const int k = map_unpack(key, a);
+      in = in && k >= lo[a] && k <= hi[a];
+    }
+    return in;
   }
-  return in;
-}
+};
+// what a carve's words select: at least min_rays rays saw through the voxel and no point of the call marked it (wc_map_carve)
+struct map_sel_carve {
+  const unsigned *words;
+  unsigned min_rays;
+  __device__ bool operator()(unsigned long long, uint64_t i) const {
+    const unsigned w = words[i];
+    return (w & kCarveEnd) == 0u && w >= min_rays;
+  }
+};
 
-// growth: the old table's occupied slots into the new one (empty keys, zero payload); keys are distinct, so the payload is stored plainly.
-// CROP: only the keys inside `box` move (the growth path compiles without the test).  omom / mom: NULL for a plain map
-template <bool CROP>
+// the old table's occupied slots that `sel` selects into the new one (empty keys, zero payload); keys are distinct, so the payload is
+// stored plainly.  omom / mom: NULL for a plain map
+template <class SEL>
 __global__ void __launch_bounds__(256) k_map_rehash(const unsigned long long *okeys, const long long *opay, const long long *omom, uint64_t ocap,
-                                                    unsigned long long *keys, long long *pay, long long *mom, unsigned long long mask,
-                                                    map_box box) {
+                                                    unsigned long long *keys, long long *pay, long long *mom, unsigned long long mask, SEL sel) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ocap) return;
   const unsigned long long key = okeys[i];
   if (key == kMapEmpty) return;
-  if (CROP && !map_in_box(key, box)) return;
+  if (!sel(key, i)) return;
   unsigned fresh = 0;
   const unsigned long long h = map_slot(keys, mask, key, fresh);
   if (h == kMapEmpty) return;  // (cannot happen: the new table has room for every old key)
@@ -473,9 +527,8 @@ struct map_found {
 template <bool PLANE>
 __device__ __forceinline__ map_found map_search(double x, double y, double z, double v, const unsigned long long *keys, const long long *pay,
                                                 unsigned long long mask) {
-  const double fx = floor(x / v), fy = floor(y / v), fz = floor(z / v);  // VoxelLoc, as k_map_insert
-  const bool ok = fx > -kMapKeyLim && fx < kMapKeyLim && fy > -kMapKeyLim && fy < kMapKeyLim && fz > -kMapKeyLim && fz < kMapKeyLim;
-  const int kx = ok ? (int)fx : 0, ky = ok ? (int)fy : 0, kz = ok ? (int)fz : 0;
+  int kx, ky, kz;
+  const bool ok = map_voxel_of(x, y, z, v, kx, ky, kz);  // (an unsearchable query: voxel 0, found nothing - see `in`)
   double best = __builtin_inf();
   float bx = 0.f, by = 0.f, bz = 0.f;
   unsigned bc = 0;
@@ -496,12 +549,8 @@ __device__ __forceinline__ map_found map_search(double x, double y, double z, do
 #pragma unroll
     for (int j = 0; j < 9; ++j) {
       if (key[j] == kMapEmpty) continue;
-      unsigned long long hj = h[j], c = cur[j];
-      for (unsigned long long probe = 0; c != key[j] && c != kMapEmpty && probe < mask; ++probe) {  // linear probing past foreign keys
-        hj = (hj + 1) & mask;
-        c = keys[hj];
-      }
-      if (c != key[j]) continue;
+      unsigned long long hj = h[j];
+      if (!map_find_from(keys, mask, key[j], hj, cur[j])) continue;
       const longlong2 *p = (const longlong2 *)(pay + 4 * hj);
       const longlong2 p0 = p[0], p1 = p[1];
       const double cnt = (double)p1.y;
@@ -539,7 +588,6 @@ template <bool PLANE>
 __global__ void __launch_bounds__(kNearThreads) k_map_nearest(wc_points q, double v, double max_d2, const unsigned long long *keys,
                                                               const long long *pay, unsigned long long mask, void *hits,
                                                               unsigned long long *found, const long long *mom, unsigned min_points) {
-  __shared__ unsigned s_found[kNearThreads / 64];
   unsigned n_found = 0;
   const uint64_t stride = (uint64_t)gridDim.x * kNearThreads;
   for (uint64_t i = (uint64_t)blockIdx.x * kNearThreads + threadIdx.x; i < q.n; i += stride) {
@@ -563,16 +611,7 @@ __global__ void __launch_bounds__(kNearThreads) k_map_nearest(wc_points q, doubl
     o[3] = make_uint2(hit ? (unsigned)w.bkz : 0u, flags);
     ((double *)o)[4] = hit ? w.best : __builtin_inf();
   }
-  // the found count: per wavefront, per workgroup, then one atomic on the counter's own line
-  n_found = wave_sum(n_found);
-  if ((threadIdx.x & 63) == 0) s_found[threadIdx.x >> 6] = n_found;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned t = 0;
-#pragma unroll
-    for (int w = 0; w < kNearThreads / 64; ++w) t += s_found[w];
-    if (t) atomicAdd(found, (unsigned long long)t);
-  }
+  block_count<kNearThreads>({n_found}, {found});
 }
 
 // ---- registration (wc_map_linearize) ----------------------------------------------------------------------------------------------
@@ -708,47 +747,31 @@ __global__ void __launch_bounds__(256) k_map_lin_reduce(const unsigned long long
   out[j * kLinWords + e] = word;
 }
 
-// crop, step 1: the voxels inside the box and their points, reduced per workgroup
-__global__ void __launch_bounds__(256) k_map_crop_count(const unsigned long long *keys, const long long *pay, uint64_t cap, map_box box,
-                                                        unsigned long long *ctr) {
-  __shared__ unsigned long long s_v[4], s_p[4];
+// the occupied slots that `sel` selects and their points, reduced per workgroup: a crop's kept voxels, a carve's seen-through ones.  The
+// predicate is evaluated for every slot (a carve's word load does not wait for the key's)
+template <class SEL>
+__global__ void __launch_bounds__(256) k_map_count(const unsigned long long *keys, const long long *pay, uint64_t cap, SEL sel,
+                                                   unsigned long long *n_vox, unsigned long long *n_pts) {
   unsigned long long nv = 0, np = 0;
   const uint64_t stride = (uint64_t)gridDim.x * 256;
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < cap; i += stride) {
     const unsigned long long key = keys[i];
-    if (key == kMapEmpty || !map_in_box(key, box)) continue;
+    const bool selected = sel(key, i);
+    if (key == kMapEmpty || !selected) continue;
     ++nv;
     np += (unsigned long long)pay[4 * i + 3];
   }
-  nv = wave_sum(nv), np = wave_sum(np);
-  if ((threadIdx.x & 63) == 0) s_v[threadIdx.x >> 6] = nv, s_p[threadIdx.x >> 6] = np;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    nv = s_v[0] + s_v[1] + s_v[2] + s_v[3], np = s_p[0] + s_p[1] + s_p[2] + s_p[3];
-    if (nv) {
-      atomicAdd(ctr + kCtrKeepVox, nv);
-      atomicAdd(ctr + kCtrKeepPts, np);
-    }
-  }
+  block_count<256>({nv, np}, {n_vox, n_pts});
 }
 
 // ---- carving (wc_map_carve) -------------------------------------------------------------------------------------------------------
 // what is the same for every ray of a call; the squares and the origin's voxel are formed once, on the host
 struct map_ray_args {
   double o[3], v, min2, max2;
-  int k0[3];      // floor(o / v) (VoxelLoc); 0 when it is out of range
-  unsigned k0_ok; // |k0_a| < 2^20 on every axis
+  int k0[3];      // the origin's voxel and whether it has one (map_voxel_of)
+  unsigned k0_ok;
   unsigned shell, max_steps;
 };
-// the slot of `key` from its first slot h, whose key c has been loaded: the read-only probe chain of map_search; kMapEmpty: absent
-__device__ __forceinline__ unsigned long long map_find_from(const unsigned long long *keys, unsigned long long mask, unsigned long long key,
-                                                            unsigned long long h, unsigned long long c) {
-  for (unsigned long long probe = 0; c != key && c != kMapEmpty && probe < mask; ++probe) {
-    h = (h + 1) & mask;
-    c = keys[h];
-  }
-  return c == key ? h : kMapEmpty;
-}
 __device__ __forceinline__ int map_cheb(int ax, int ay, int az, int bx, int by, int bz) {
   return max(max(abs(ax - bx), abs(ay - by)), abs(az - bz));
 }
@@ -762,7 +785,6 @@ __device__ __forceinline__ int map_cheb(int ax, int ay, int az, int bx, int by, 
 template <int B>
 __global__ void __launch_bounds__(kCarveThreads) k_map_carve(wc_points pts, map_ray_args A, const unsigned long long *keys, unsigned long long mask,
                                                              unsigned *words, unsigned long long *cctr) {
-  __shared__ unsigned long long s_used[kCarveThreads / 64], s_skip[kCarveThreads / 64], s_steps[kCarveThreads / 64];
   unsigned long long n_used = 0, n_skip = 0, n_steps = 0;
   const double v = A.v, ox = A.o[0], oy = A.o[1], oz = A.o[2];
   const int shell = (int)A.shell;
@@ -770,16 +792,15 @@ __global__ void __launch_bounds__(kCarveThreads) k_map_carve(wc_points pts, map_
   for (uint64_t i = (uint64_t)blockIdx.x * kCarveThreads + threadIdx.x; i < pts.n; i += stride) {
     const float *f = (const float *)((const char *)pts.xyz + i * pts.xyz_stride);
     const double px = (double)f[0], py = (double)f[1], pz = (double)f[2];
-    const double fx = floor(px / v), fy = floor(py / v), fz = floor(pz / v);  // VoxelLoc, as k_map_insert: NaN / inf fail the compares
-    if (!(fx > -kMapKeyLim && fx < kMapKeyLim && fy > -kMapKeyLim && fy < kMapKeyLim && fz > -kMapKeyLim && fz < kMapKeyLim)) {
+    int kex, key_, kez;
+    if (!map_voxel_of(px, py, pz, v, kex, key_, kez)) {
       ++n_skip;
       continue;
     }
-    const int kex = (int)fx, key_ = (int)fy, kez = (int)fz;
     {  // the end mark, whether or not the ray is used
-      const unsigned long long ekey = map_pack(kex, key_, kez), eh = map_hash(ekey) & mask;
-      const unsigned long long es = map_find_from(keys, mask, ekey, eh, keys[eh]);
-      if (es != kMapEmpty) atomicOr(&words[es], kCarveEnd);
+      const unsigned long long ekey = map_pack(kex, key_, kez);
+      unsigned long long es = map_hash(ekey) & mask;
+      if (map_find_from(keys, mask, ekey, es, keys[es])) atomicOr(&words[es], kCarveEnd);
     }
     const double dx = px - ox, dy = py - oy, dz = pz - oz;
     const double len2 = (dx * dx + dy * dy) + dz * dz;
@@ -820,48 +841,11 @@ __global__ void __launch_bounds__(kCarveThreads) k_map_carve(wc_points pts, map_
 #pragma unroll
       for (int j = 0; j < B; ++j) {
         if (key[j] == kMapEmpty) continue;
-        const unsigned long long hs = map_find_from(keys, mask, key[j], h[j], cur[j]);
-        if (hs != kMapEmpty) atomicAdd(&words[hs], 1u);
+        if (map_find_from(keys, mask, key[j], h[j], cur[j])) atomicAdd(&words[h[j]], 1u);
       }
     }
   }
-  // the counts: per wavefront, per workgroup, then one atomic each on the counter's own line
-  n_used = wave_sum(n_used), n_skip = wave_sum(n_skip), n_steps = wave_sum(n_steps);
-  if ((threadIdx.x & 63) == 0) s_used[threadIdx.x >> 6] = n_used, s_skip[threadIdx.x >> 6] = n_skip, s_steps[threadIdx.x >> 6] = n_steps;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long u = 0, s = 0, t = 0;
-#pragma unroll
-    for (int w = 0; w < kCarveThreads / 64; ++w) u += s_used[w], s += s_skip[w], t += s_steps[w];
-    if (u) atomicAdd(cctr + kCarveUsed, u);
-    if (s) atomicAdd(cctr + kCarveSkip, s);
-    if (t) atomicAdd(cctr + kCarveSteps, t);
-  }
-}
-
-// what the words select: the occupied voxels that at least min_rays rays saw through and that no point of the call marked, and their
-// points, reduced per workgroup onto counter lines of the carve's own
-__global__ void __launch_bounds__(256) k_map_carve_count(const unsigned long long *keys, const long long *pay, uint64_t cap, const unsigned *words,
-                                                         unsigned min_rays, unsigned long long *cctr) {
-  __shared__ unsigned long long s_v[4], s_p[4];
-  unsigned long long nv = 0, np = 0;
-  const uint64_t stride = (uint64_t)gridDim.x * 256;
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < cap; i += stride) {
-    const unsigned w = words[i];
-    if (keys[i] == kMapEmpty || (w & kCarveEnd) != 0u || w < min_rays) continue;
-    ++nv;
-    np += (unsigned long long)pay[4 * i + 3];
-  }
-  nv = wave_sum(nv), np = wave_sum(np);
-  if ((threadIdx.x & 63) == 0) s_v[threadIdx.x >> 6] = nv, s_p[threadIdx.x >> 6] = np;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    nv = s_v[0] + s_v[1] + s_v[2] + s_v[3], np = s_p[0] + s_p[1] + s_p[2] + s_p[3];
-    if (nv) {
-      atomicAdd(cctr + kCarveSelVox, nv);
-      atomicAdd(cctr + kCarveSelPts, np);
-    }
-  }
+  block_count<kCarveThreads>({n_used, n_skip, n_steps}, {cctr + kCarveUsed, cctr + kCarveSkip, cctr + kCarveSteps});
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
@@ -887,8 +871,15 @@ uint64_t pow2_at_least(uint64_t x) {
   while (c < x) c <<= 1;
   return c;
 }
-// a fresh table of `cap` slots (empty keys, zero payload), enqueued on the ctx stream
-// (moments: the nine extra words per slot of a WC_MAP_MOMENTS map, zero; *mom = NULL otherwise)
+// a table of `cap` slots made empty (empty keys, zero payload; mom: NULL for a plain map), enqueued on the ctx stream
+int map_clear_table(wc_ctx *ctx, uint64_t cap, unsigned long long *keys, long long *pay, long long *mom) {
+  WC_HIP(ctx, hipMemsetAsync(keys, 0xFF, cap * 8, ctx->stream));
+  WC_HIP(ctx, hipMemsetAsync(pay, 0, cap * 32, ctx->stream));
+  if (mom) WC_HIP(ctx, hipMemsetAsync(mom, 0, cap * 8 * kMapMom, ctx->stream));
+  return WC_OK;
+}
+// a fresh, empty table of `cap` slots
+// (moments: the nine extra words per slot of a WC_MAP_MOMENTS map; *mom = NULL otherwise)
 int map_table(wc_ctx *ctx, uint64_t cap, bool moments, unsigned long long **keys, long long **pay, long long **mom) {
   *mom = nullptr;
   WC_TRY(map_alloc(ctx, (void **)keys, cap * 8));
@@ -905,10 +896,29 @@ int map_table(wc_ctx *ctx, uint64_t cap, bool moments, unsigned long long **keys
     *keys = nullptr;
     return rc;
   }
-  WC_HIP(ctx, hipMemsetAsync(*keys, 0xFF, cap * 8, ctx->stream));
-  WC_HIP(ctx, hipMemsetAsync(*pay, 0, cap * 32, ctx->stream));
-  if (moments) WC_HIP(ctx, hipMemsetAsync(*mom, 0, cap * 8 * kMapMom, ctx->stream));
+  return map_clear_table(ctx, cap, *keys, *pay, *mom);
+}
+// the map's table replaced by one of `cap` slots that holds the occupied slots `sel` selects: the new table, the rehash into it, the
+// old one freed (in stream order, behind the rehash)
+template <class SEL>
+int map_replace_table(wc_ctx *ctx, wc_map *m, uint64_t cap, SEL sel) {
+  unsigned long long *keys = nullptr;
+  long long *pay = nullptr, *mom = nullptr;
+  WC_TRY(map_table(ctx, cap, m->mom != nullptr, &keys, &pay, &mom));
+  k_map_rehash<SEL><<<(unsigned)((m->cap + 255) / 256), 256, 0, ctx->stream>>>(m->keys, m->pay, m->mom, m->cap, keys, pay, mom, cap - 1, sel);
+  WC_HIP(ctx, hipGetLastError());
+  map_free(ctx, m->keys);
+  map_free(ctx, m->pay);
+  map_free(ctx, m->mom);
+  m->keys = keys, m->pay = pay, m->mom = mom, m->cap = cap;
   return WC_OK;
+}
+// one launch of the insert: PTS consecutive points per lane, tiles of kMapThreads * PTS points
+template <bool MOM, int PTS>
+void map_launch_insert(wc_ctx *ctx, wc_map *m, const wc_points &pts) {
+  const uint64_t tiles = (pts.n + kMapThreads * PTS - 1) / (kMapThreads * PTS);
+  const unsigned grid = (unsigned)std::min<uint64_t>(tiles, (uint64_t)4 * m->cus);
+  k_map_insert<MOM, PTS><<<grid, kMapThreads, 0, ctx->stream>>>(pts, m->voxel, m->keys, m->pay, m->mom, m->cap - 1, m->ctr);
 }
 // the occupied-slot bound of the growth policy; takes a completed read-back into account without waiting for one
 uint64_t map_bound(wc_map *m) {
@@ -929,6 +939,11 @@ int map_sync_counters(wc_ctx *ctx, wc_map *m) {
   return WC_OK;
 }
 bool map_ok(const wc_ctx *ctx, const wc_map *m) { return ctx && m && m->ctx == ctx; }
+// a cloud the kernels can read: not null and, unless it is empty, float triples at a 4-byte-aligned address, a stride of at least 12 bytes
+// that is a multiple of 4
+bool map_points_ok(const wc_points *p) {
+  return p && (p->n == 0 || (p->xyz && p->xyz_stride >= 12 && p->xyz_stride % 4 == 0 && (uintptr_t)p->xyz % 4 == 0));
+}
 
 }  // namespace
 
@@ -987,8 +1002,7 @@ extern "C" int wc_map_destroy(wc_ctx *ctx, wc_map *m) {
 
 extern "C" int wc_map_insert(wc_ctx *ctx, wc_map *m, const wc_points *pts, uint64_t *h_n_rejected) {
   wc_dev_guard dg_(ctx);
-  if (!map_ok(ctx, m) || !pts || (pts->n && (!pts->xyz || pts->xyz_stride < 12 || pts->xyz_stride % 4 || (uintptr_t)pts->xyz % 4)))
-    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
+  if (!map_ok(ctx, m) || !map_points_ok(pts)) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
   if (h_n_rejected) *h_n_rejected = 0;
   if (pts->n == 0) return WC_OK;
   // growth (policy at the top of the file): at most half full at every probe of this call
@@ -996,32 +1010,16 @@ extern "C" int wc_map_insert(wc_ctx *ctx, wc_map *m, const wc_points *pts, uint6
   if (need > m->cap) {
     const uint64_t cap = pow2_at_least(need);
     if (cap > ((uint64_t)1 << 32)) return wc_fail(ctx, WC_ERR_CAPACITY, "%s: the table would exceed 2^32 slots", __func__);
-    unsigned long long *keys = nullptr;
-    long long *pay = nullptr, *mom = nullptr;
-    WC_TRY(map_table(ctx, cap, m->mom != nullptr, &keys, &pay, &mom));
-    k_map_rehash<false><<<(unsigned)((m->cap + 255) / 256), 256, 0, ctx->stream>>>(m->keys, m->pay, m->mom, m->cap, keys, pay, mom, cap - 1,
-                                                                                   map_box{});
-    WC_HIP(ctx, hipGetLastError());
-    map_free(ctx, m->keys);
-    map_free(ctx, m->pay);
-    map_free(ctx, m->mom);
-    m->keys = keys, m->pay = pay, m->mom = mom, m->cap = cap;
+    WC_TRY(map_replace_table(ctx, m, cap, map_sel_all{}));
     ++m->growths;
   }
   WC_HIP(ctx, hipMemsetAsync(m->ctr + kCtrRejCall, 0, 8, ctx->stream));
-  if (!m->mom) {
-    const uint64_t tiles = (pts->n + kMapTile - 1) / kMapTile;
-    const unsigned grid = (unsigned)std::min<uint64_t>(tiles, (uint64_t)4 * m->cus);
-    k_map_insert<false, kMapPts><<<grid, kMapThreads, 0, ctx->stream>>>(*pts, m->voxel, m->keys, m->pay, nullptr, m->cap - 1, m->ctr);
-  } else if (ctx->dev.map_mom_pts == 2) {  // (development option: the plain insert's tile, 108 KB of LDS, one workgroup per CU)
-    const uint64_t tiles = (pts->n + kMapTile - 1) / kMapTile;
-    const unsigned grid = (unsigned)std::min<uint64_t>(tiles, (uint64_t)4 * m->cus);
-    k_map_insert<true, kMapPts><<<grid, kMapThreads, 0, ctx->stream>>>(*pts, m->voxel, m->keys, m->pay, m->mom, m->cap - 1, m->ctr);
-  } else {
-    const uint64_t tiles = (pts->n + kMapThreads * kMapMomPts - 1) / (kMapThreads * kMapMomPts);
-    const unsigned grid = (unsigned)std::min<uint64_t>(tiles, (uint64_t)4 * m->cus);
-    k_map_insert<true, kMapMomPts><<<grid, kMapThreads, 0, ctx->stream>>>(*pts, m->voxel, m->keys, m->pay, m->mom, m->cap - 1, m->ctr);
-  }
+  if (!m->mom)
+    map_launch_insert<false, kMapPts>(ctx, m, *pts);
+  else if (ctx->dev.map_mom_pts == 2)  // (development option: the plain insert's tile, 108 KB of LDS, one workgroup per CU)
+    map_launch_insert<true, kMapPts>(ctx, m, *pts);
+  else
+    map_launch_insert<true, kMapMomPts>(ctx, m, *pts);
   WC_HIP(ctx, hipGetLastError());
   m->pts_since += pts->n;
   if (h_n_rejected) {
@@ -1085,16 +1083,22 @@ int map_sorted_slots(wc_ctx *ctx, wc_map *m, uint64_t n, unsigned long long **sk
   *skeys = kout, *sslots = vout;
   return WC_OK;
 }
+// what both exports begin with: the size read-back into *h_n and the capacity error.  *h_n = 0: an empty map, nothing to write
+int map_export_size(wc_ctx *ctx, wc_map *m, const char *fn, uint64_t cap, uint64_t *h_n) {
+  WC_TRY(map_sync_counters(ctx, m));
+  *h_n = m->h_ctr[kCtrOcc];
+  if (cap < *h_n && *h_n)
+    return wc_fail(ctx, WC_ERR_CAPACITY, "%s: %llu voxels, capacity %llu", fn, (unsigned long long)*h_n, (unsigned long long)cap);
+  return WC_OK;
+}
 }  // namespace
 
 extern "C" int wc_map_export(wc_ctx *ctx, wc_map *m, float *d_xyz, uint32_t *d_count, int32_t *d_keys, uint64_t cap, uint64_t *h_n) {
   wc_dev_guard dg_(ctx);
   if (!map_ok(ctx, m) || !h_n) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
-  WC_TRY(map_sync_counters(ctx, m));  // (the size read-back)
-  const uint64_t n = m->h_ctr[kCtrOcc];
-  *h_n = n;
+  WC_TRY(map_export_size(ctx, m, __func__, cap, h_n));
+  const uint64_t n = *h_n;
   if (n == 0) return WC_OK;
-  if (cap < n) return wc_fail(ctx, WC_ERR_CAPACITY, "%s: %llu voxels, capacity %llu", __func__, (unsigned long long)n, (unsigned long long)cap);
   if (!d_xyz || !d_count) return wc_fail(ctx, WC_ERR_ARG, "%s: null output", __func__);
   unsigned long long *kout = nullptr;
   uint32_t *vout = nullptr;
@@ -1108,11 +1112,9 @@ extern "C" int wc_map_export_surfels(wc_ctx *ctx, wc_map *m, wc_map_surfel *d_ou
   wc_dev_guard dg_(ctx);
   if (!map_ok(ctx, m) || !h_n || !m->mom)
     return wc_fail(ctx, WC_ERR_ARG, "%s: null argument, or a map created without WC_MAP_MOMENTS", __func__);
-  WC_TRY(map_sync_counters(ctx, m));  // (the size read-back)
-  const uint64_t n = m->h_ctr[kCtrOcc];
-  *h_n = n;
+  WC_TRY(map_export_size(ctx, m, __func__, cap, h_n));
+  const uint64_t n = *h_n;
   if (n == 0) return WC_OK;
-  if (cap < n) return wc_fail(ctx, WC_ERR_CAPACITY, "%s: %llu voxels, capacity %llu", __func__, (unsigned long long)n, (unsigned long long)cap);
   if (!d_out || (uintptr_t)d_out % 8) return wc_fail(ctx, WC_ERR_ARG, "%s: null or misaligned output", __func__);
   unsigned long long *kout = nullptr;
   uint32_t *vout = nullptr;
@@ -1125,9 +1127,7 @@ extern "C" int wc_map_export_surfels(wc_ctx *ctx, wc_map *m, wc_map_surfel *d_ou
 extern "C" int wc_map_clear(wc_ctx *ctx, wc_map *m) {
   wc_dev_guard dg_(ctx);
   if (!map_ok(ctx, m)) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
-  WC_HIP(ctx, hipMemsetAsync(m->keys, 0xFF, m->cap * 8, ctx->stream));
-  WC_HIP(ctx, hipMemsetAsync(m->pay, 0, m->cap * 32, ctx->stream));
-  if (m->mom) WC_HIP(ctx, hipMemsetAsync(m->mom, 0, m->cap * 8 * kMapMom, ctx->stream));
+  WC_TRY(map_clear_table(ctx, m->cap, m->keys, m->pay, m->mom));
   WC_HIP(ctx, hipMemsetAsync(m->ctr, 0, kCtrWords * 8, ctx->stream));
   WC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (a pending counter copy lands before the host's bookkeeping is reset)
   m->occ_known = m->pts_since = m->pts_after_copy = 0;
@@ -1142,8 +1142,7 @@ int map_nearest(wc_ctx *ctx, wc_map *m, const wc_points *queries, double max_dis
                 const char *fn) {
   wc_dev_guard dg_(ctx);
   const wc_points *q = queries;
-  if (!map_ok(ctx, m) || !q || !(max_dist > 0.0) ||
-      (q->n && (!d_hits || (uintptr_t)d_hits % 8 || !q->xyz || q->xyz_stride < 12 || q->xyz_stride % 4 || (uintptr_t)q->xyz % 4)))
+  if (!map_ok(ctx, m) || !map_points_ok(q) || !(max_dist > 0.0) || (q->n && (!d_hits || (uintptr_t)d_hits % 8)))
     return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (max_dist > 0)", fn);
   if (h_n_found) *h_n_found = 0;
   if (q->n == 0) return WC_OK;
@@ -1200,8 +1199,7 @@ uint64_t lin_words(uint64_t tiles) {
 extern "C" int wc_map_linearize(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double T[12], const wc_map_reg_params *params,
                                 wc_map_normal_eq *h_out, wc_map_reg_row *d_rows) {
   wc_dev_guard dg_(ctx);
-  if (!map_ok(ctx, m) || !m->mom || !pts || !T || !h_out || !reg_params_ok(params) || (uintptr_t)d_rows % 8 ||
-      (pts->n && (!pts->xyz || pts->xyz_stride < 12 || pts->xyz_stride % 4 || (uintptr_t)pts->xyz % 4)))
+  if (!map_ok(ctx, m) || !m->mom || !map_points_ok(pts) || !T || !h_out || !reg_params_ok(params) || (uintptr_t)d_rows % 8)
     return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument, a map of another context or one created without WC_MAP_MOMENTS", __func__);
   map_pose P;
   for (int j = 0; j < 12; ++j) {
@@ -1350,7 +1348,7 @@ extern "C" int wc_map_align(wc_ctx *ctx, wc_map *m, const wc_points *pts, double
 extern "C" int wc_map_crop(wc_ctx *ctx, wc_map *m, const double lo[3], const double hi[3], uint64_t *h_removed_voxels) {
   wc_dev_guard dg_(ctx);
   if (!map_ok(ctx, m) || !lo || !hi) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
-  map_box box;
+  map_sel_box box;
   for (int a = 0; a < 3; ++a) {
     if (!(lo[a] <= hi[a])) return wc_fail(ctx, WC_ERR_ARG, "%s: NaN bound or lo > hi on axis %d", __func__, a);
     // kept: floor(lo / v) <= k <= floor(hi / v), clamped to the key range |k| < 2^20 (+-inf included)
@@ -1359,22 +1357,14 @@ extern "C" int wc_map_crop(wc_ctx *ctx, wc_map *m, const double lo[3], const dou
   }
   WC_HIP(ctx, hipMemsetAsync(m->ctr + kCtrKeepVox, 0, (kCtrKeepPts - kCtrKeepVox + 1) * 8, ctx->stream));
   const unsigned grid = (unsigned)std::min<uint64_t>((m->cap + 255) / 256, (uint64_t)8 * m->cus);
-  k_map_crop_count<<<grid, 256, 0, ctx->stream>>>(m->keys, m->pay, m->cap, box, m->ctr);
+  k_map_count<<<grid, 256, 0, ctx->stream>>>(m->keys, m->pay, m->cap, box, m->ctr + kCtrKeepVox, m->ctr + kCtrKeepPts);
   WC_HIP(ctx, hipGetLastError());
   WC_TRY(map_sync_counters(ctx, m));  // (the wait: the new table is sized from the kept count; a pending counter copy has landed too)
   const uint64_t occ = m->h_ctr[kCtrOcc], kept = m->h_ctr[kCtrKeepVox], kept_pts = m->h_ctr[kCtrKeepPts];
   if (h_removed_voxels) *h_removed_voxels = occ - kept;
   const uint64_t cap = pow2_at_least(2 * std::max<uint64_t>(kept, 1));
   if (kept != occ || cap != m->cap) {  // (otherwise the table already is what the crop would build)
-    unsigned long long *keys = nullptr;
-    long long *pay = nullptr, *mom = nullptr;
-    WC_TRY(map_table(ctx, cap, m->mom != nullptr, &keys, &pay, &mom));
-    k_map_rehash<true><<<(unsigned)((m->cap + 255) / 256), 256, 0, ctx->stream>>>(m->keys, m->pay, m->mom, m->cap, keys, pay, mom, cap - 1, box);
-    WC_HIP(ctx, hipGetLastError());
-    map_free(ctx, m->keys);
-    map_free(ctx, m->pay);
-    map_free(ctx, m->mom);
-    m->keys = keys, m->pay = pay, m->mom = mom, m->cap = cap;
+    WC_TRY(map_replace_table(ctx, m, cap, box));
     // the occupied-voxel and point counters become those of the kept voxels; rejected and growth counters stay
     WC_HIP(ctx, hipMemcpyAsync(m->ctr + kCtrOcc, m->ctr + kCtrKeepVox, 8, hipMemcpyDeviceToDevice, ctx->stream));
     WC_HIP(ctx, hipMemcpyAsync(m->ctr + kCtrPts, m->ctr + kCtrKeepPts, 8, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1391,8 +1381,7 @@ extern "C" int wc_map_carve(wc_ctx *ctx, wc_map *m, const wc_points *pts, const 
                             wc_map_carve_result *h_out) {
   wc_dev_guard dg_(ctx);
   const wc_map_carve_params *p = params;
-  if (!map_ok(ctx, m) || !pts || !origin || !p || !h_out || pts->n >= ((uint64_t)1 << 31) ||
-      (pts->n && (!pts->xyz || pts->xyz_stride < 12 || pts->xyz_stride % 4 || (uintptr_t)pts->xyz % 4)))
+  if (!map_ok(ctx, m) || !map_points_ok(pts) || !origin || !p || !h_out || pts->n >= ((uint64_t)1 << 31))
     return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (n < 2^31), or a map of another context", __func__);
   if (!(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2])) || !(p->min_range >= 0.0) ||
       !(p->max_range >= p->min_range) || p->shell > 8 || p->min_rays < 1 || p->max_steps < 1 || p->max_steps > 65536 || p->reserved != 0)
@@ -1405,13 +1394,8 @@ extern "C" int wc_map_carve(wc_ctx *ctx, wc_map *m, const wc_points *pts, const 
   map_ray_args A;
   A.v = m->voxel;
   A.min2 = p->min_range * p->min_range, A.max2 = p->max_range * p->max_range;
-  A.k0_ok = 1u;
-  for (int a = 0; a < 3; ++a) {
-    A.o[a] = origin[a];
-    const double f = std::floor(origin[a] / m->voxel);
-    if (!(f > -kMapKeyLim && f < kMapKeyLim)) A.k0_ok = 0u;
-  }
-  for (int a = 0; a < 3; ++a) A.k0[a] = A.k0_ok ? (int)std::floor(origin[a] / m->voxel) : 0;
+  for (int a = 0; a < 3; ++a) A.o[a] = origin[a];
+  A.k0_ok = map_voxel_of(origin[0], origin[1], origin[2], m->voxel, A.k0[0], A.k0[1], A.k0[2]) ? 1u : 0u;
   A.shell = p->shell, A.max_steps = p->max_steps;
   // the scratch: five counter lines, then one word per slot; zeroed per call
   const size_t scratch = (size_t)kCarveCtrWords * 8 + (size_t)m->cap * 4;
@@ -1427,7 +1411,8 @@ extern "C" int wc_map_carve(wc_ctx *ctx, wc_map *m, const wc_points *pts, const 
   WC_HIP(ctx, hipGetLastError());
   // what the words select (this version reports it and leaves the map as it is: DESIGN 8.4)
   const unsigned cgrid = (unsigned)std::min<uint64_t>((m->cap + 255) / 256, (uint64_t)8 * m->cus);
-  k_map_carve_count<<<cgrid, 256, 0, ctx->stream>>>(m->keys, m->pay, m->cap, words, p->min_rays, cctr);
+  k_map_count<<<cgrid, 256, 0, ctx->stream>>>(m->keys, m->pay, m->cap, map_sel_carve{words, p->min_rays}, cctr + kCarveSelVox,
+                                              cctr + kCarveSelPts);
   WC_HIP(ctx, hipGetLastError());
   WC_HIP(ctx, hipMemcpyAsync(m->h_carve, cctr, kCarveCtrWords * 8, hipMemcpyDeviceToHost, ctx->stream));
   WC_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
@@ -51,13 +52,15 @@ void PredictPoseOfNewImuState(const wc_imu_state &i1, const wc_imu_state &i2, V3
   st3(i3.pos, ((qrot(q4(i1.quat), v3(i1.acc) - ba) + grav) * dt) * dt + 2 * v3(i2.pos) - v3(i1.pos));
 }
 
-}  // namespace
-
-void LidarOdometry::Fatal(const char *what, int rc) const {
-  // the reference aborts through glog CHECK / LOG(FATAL); so does the facade
-  std::fprintf(stderr, "[wildcat] FATAL %s (rc=%d): %s\n", what, rc, ctx_ ? wc_last_error(ctx_) : "");
+// a library call that failed: the reference aborts through glog CHECK / LOG(FATAL); so does the facade
+[[noreturn]] void FatalCall(const wc_ctx *ctx, const char *what, int rc) {
+  std::fprintf(stderr, "[wildcat] FATAL %s (rc=%d): %s\n", what, rc, ctx ? wc_last_error(ctx) : "");
   std::abort();
 }
+
+}  // namespace
+
+void LidarOdometry::Fatal(const char *what, int rc) const { FatalCall(ctx_, what, rc); }
 #define WC_CHECK(cond)                                                                           \
   do {                                                                                           \
     if (!(cond)) {                                                                               \
@@ -70,6 +73,47 @@ void LidarOdometry::Fatal(const char *what, int rc) const {
     int rc_ = (expr);                  \
     if (rc_ != WC_OK) Fatal(#expr, rc_); \
   } while (0)
+
+namespace {
+
+// A device allocation of the context that lives as long as its scope: freed on every path out of it.  bytes = 0: nothing is allocated
+// and p stays null.  A failing library call aborts, as WC_CALL does.
+void CheckCall(const wc_ctx *ctx, const char *what, int rc) {
+  if (rc != WC_OK) FatalCall(ctx, what, rc);
+}
+struct DevBuf {
+  wc_ctx *ctx;
+  void *p = nullptr;
+  DevBuf(wc_ctx *c, size_t bytes) : ctx(c) {
+    if (bytes) CheckCall(ctx, "wc_dev_alloc", wc_dev_alloc(ctx, bytes, &p));
+  }
+  ~DevBuf() {
+    if (p) CheckCall(ctx, "wc_dev_free", wc_dev_free(ctx, p));
+  }
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  void ToHost(void *dst, size_t bytes) const { CheckCall(ctx, "wc_d2h", wc_d2h(ctx, dst, p, bytes)); }
+};
+// n x 3 host floats into `buf` (allocated for them) and the descriptor the library takes; n = 0: an empty cloud, nothing is copied
+wc_points UploadXyz(const DevBuf &buf, const float *xyz, size_t n) {
+  if (n) CheckCall(buf.ctx, "wc_h2d", wc_h2d(buf.ctx, buf.p, xyz, n * 3 * sizeof(float)));
+  return wc_points{buf.p, nullptr, 12, 0, n};
+}
+
+// every record of a query's answer a miss: zeros, d2 = +inf (a wc_map_plane_hit begins with its wc_map_hit)
+static_assert(offsetof(wc_map_plane_hit, hit) == 0, "FillMisses writes the wc_map_hit at the start of either record");
+template <class Rec>
+void FillMisses(Rec *hits, size_t n) {
+  wc_map_hit miss;
+  std::memset(&miss, 0, sizeof(miss));
+  miss.d2 = std::numeric_limits<double>::infinity();
+  for (size_t i = 0; i < n; ++i) {
+    std::memset(&hits[i], 0, sizeof(Rec));
+    std::memcpy(&hits[i], &miss, sizeof(miss));
+  }
+}
+
+}  // namespace
 
 LidarOdometry::LidarOdometry() : LidarOdometry(0) {}
 
@@ -449,48 +493,32 @@ size_t LidarOdometry::ExportMapSurfels(wc_map_surfel *surfels, size_t cap) {
   if (!map_ || !map_moments_) return 0;
   uint64_t n = map_voxels();
   if (n == 0 || cap < n || !surfels) return n;
-  void *d_out = nullptr;
-  WC_CALL(wc_dev_alloc(ctx_, n * sizeof(wc_map_surfel), &d_out));
-  WC_CALL(wc_map_export_surfels(ctx_, map_, (wc_map_surfel *)d_out, n, &n));
-  WC_CALL(wc_d2h(ctx_, surfels, d_out, n * sizeof(wc_map_surfel)));
-  WC_CALL(wc_dev_free(ctx_, d_out));
+  const DevBuf d_out(ctx_, n * sizeof(wc_map_surfel));
+  WC_CALL(wc_map_export_surfels(ctx_, map_, (wc_map_surfel *)d_out.p, n, &n));
+  d_out.ToHost(surfels, n * sizeof(wc_map_surfel));
   return n;
 }
 size_t LidarOdometry::QueryMapPlanes(const float *xyz, size_t n, double max_dist, uint32_t min_points, wc_map_plane_hit *hits) {
   if (!n || !xyz || !hits) return 0;
   if (!map_ || !map_moments_ || min_points < 3) {
-    for (size_t i = 0; i < n; ++i) {
-      std::memset(&hits[i], 0, sizeof(wc_map_plane_hit));
-      hits[i].hit.d2 = std::numeric_limits<double>::infinity();
-    }
+    FillMisses(hits, n);
     return 0;
   }
-  void *d_xyz = nullptr, *d_hits = nullptr;
-  WC_CALL(wc_dev_alloc(ctx_, n * 3 * sizeof(float), &d_xyz));
-  WC_CALL(wc_dev_alloc(ctx_, n * sizeof(wc_map_plane_hit), &d_hits));
-  WC_CALL(wc_h2d(ctx_, d_xyz, xyz, n * 3 * sizeof(float)));
-  const wc_points desc{d_xyz, nullptr, 12, 0, n};
+  const DevBuf d_xyz(ctx_, n * 3 * sizeof(float)), d_hits(ctx_, n * sizeof(wc_map_plane_hit));
+  const wc_points desc = UploadXyz(d_xyz, xyz, n);
   uint64_t found = 0;
-  WC_CALL(wc_map_nearest_plane(ctx_, map_, &desc, max_dist, min_points, (wc_map_plane_hit *)d_hits, &found));
-  WC_CALL(wc_d2h(ctx_, hits, d_hits, n * sizeof(wc_map_plane_hit)));
-  WC_CALL(wc_dev_free(ctx_, d_xyz));
-  WC_CALL(wc_dev_free(ctx_, d_hits));
+  WC_CALL(wc_map_nearest_plane(ctx_, map_, &desc, max_dist, min_points, (wc_map_plane_hit *)d_hits.p, &found));
+  d_hits.ToHost(hits, n * sizeof(wc_map_plane_hit));
   return found;
 }
 bool LidarOdometry::AlignToMap(const float *xyz, size_t n, double T_io[12], const wc_map_align_opts &opts, wc_map_align_summary *summary) {
   if (!map_ || !map_moments_ || !T_io || (n && !xyz)) return false;
-  void *d_xyz = nullptr;
-  if (n) {
-    WC_CALL(wc_dev_alloc(ctx_, n * 3 * sizeof(float), &d_xyz));
-    WC_CALL(wc_h2d(ctx_, d_xyz, xyz, n * 3 * sizeof(float)));
-  }
-  const wc_points desc{d_xyz, nullptr, 12, 0, n};
+  const DevBuf d_xyz(ctx_, n * 3 * sizeof(float));
+  const wc_points desc = UploadXyz(d_xyz, xyz, n);
   double T[12];
   std::memcpy(T, T_io, sizeof(T));
   wc_map_align_summary s;
-  const int rc = wc_map_align(ctx_, map_, &desc, T, &opts, &s);  // (an argument the library refuses is the caller's: no abort)
-  if (d_xyz) WC_CALL(wc_dev_free(ctx_, d_xyz));
-  if (rc != WC_OK) return false;
+  if (wc_map_align(ctx_, map_, &desc, T, &opts, &s) != WC_OK) return false;  // (an argument the library refuses is the caller's: no abort)
   std::memcpy(T_io, T, sizeof(T));
   if (summary) *summary = s;
   return true;
@@ -498,19 +526,11 @@ bool LidarOdometry::AlignToMap(const float *xyz, size_t n, double T_io[12], cons
 bool LidarOdometry::LinearizeAgainstMap(const float *xyz, size_t n, const double T[12], const wc_map_reg_params &params, wc_map_normal_eq *out,
                                         wc_map_reg_row *rows) {
   if (!map_ || !map_moments_ || !T || !out || (n && !xyz)) return false;
-  void *d_xyz = nullptr, *d_rows = nullptr;
-  if (n) {
-    WC_CALL(wc_dev_alloc(ctx_, n * 3 * sizeof(float), &d_xyz));
-    WC_CALL(wc_h2d(ctx_, d_xyz, xyz, n * 3 * sizeof(float)));
-    if (rows) WC_CALL(wc_dev_alloc(ctx_, n * sizeof(wc_map_reg_row), &d_rows));
-  }
-  const wc_points desc{d_xyz, nullptr, 12, 0, n};
+  const DevBuf d_xyz(ctx_, n * 3 * sizeof(float)), d_rows(ctx_, rows ? n * sizeof(wc_map_reg_row) : 0);
+  const wc_points desc = UploadXyz(d_xyz, xyz, n);
   wc_map_normal_eq ne;
-  const int rc = wc_map_linearize(ctx_, map_, &desc, T, &params, &ne, (wc_map_reg_row *)d_rows);
-  if (rc == WC_OK && d_rows) WC_CALL(wc_d2h(ctx_, rows, d_rows, n * sizeof(wc_map_reg_row)));
-  if (d_xyz) WC_CALL(wc_dev_free(ctx_, d_xyz));
-  if (d_rows) WC_CALL(wc_dev_free(ctx_, d_rows));
-  if (rc != WC_OK) return false;
+  if (wc_map_linearize(ctx_, map_, &desc, T, &params, &ne, (wc_map_reg_row *)d_rows.p) != WC_OK) return false;  // (as in AlignToMap)
+  if (d_rows.p) d_rows.ToHost(rows, n * sizeof(wc_map_reg_row));
   *out = ne;
   return true;
 }
@@ -533,14 +553,10 @@ size_t LidarOdometry::ExportMap(float *xyz, uint32_t *counts, size_t cap) {
   if (!map_) return 0;
   uint64_t n = map_voxels();
   if (n == 0 || cap < n || !xyz || !counts) return n;
-  void *d_xyz = nullptr, *d_cnt = nullptr;
-  WC_CALL(wc_dev_alloc(ctx_, n * 3 * sizeof(float), &d_xyz));
-  WC_CALL(wc_dev_alloc(ctx_, n * sizeof(uint32_t), &d_cnt));
-  WC_CALL(wc_map_export(ctx_, map_, (float *)d_xyz, (uint32_t *)d_cnt, nullptr, n, &n));
-  WC_CALL(wc_d2h(ctx_, xyz, d_xyz, n * 3 * sizeof(float)));
-  WC_CALL(wc_d2h(ctx_, counts, d_cnt, n * sizeof(uint32_t)));
-  WC_CALL(wc_dev_free(ctx_, d_xyz));
-  WC_CALL(wc_dev_free(ctx_, d_cnt));
+  const DevBuf d_xyz(ctx_, n * 3 * sizeof(float)), d_cnt(ctx_, n * sizeof(uint32_t));
+  WC_CALL(wc_map_export(ctx_, map_, (float *)d_xyz.p, (uint32_t *)d_cnt.p, nullptr, n, &n));
+  d_xyz.ToHost(xyz, n * 3 * sizeof(float));
+  d_cnt.ToHost(counts, n * sizeof(uint32_t));
   return n;
 }
 void LidarOdometry::ClearMap() {
@@ -549,22 +565,14 @@ void LidarOdometry::ClearMap() {
 size_t LidarOdometry::QueryMap(const float *xyz, size_t n, double max_dist, wc_map_hit *hits) {
   if (!n || !xyz || !hits) return 0;
   if (!map_) {
-    for (size_t i = 0; i < n; ++i) {
-      std::memset(&hits[i], 0, sizeof(wc_map_hit));
-      hits[i].d2 = std::numeric_limits<double>::infinity();
-    }
+    FillMisses(hits, n);
     return 0;
   }
-  void *d_xyz = nullptr, *d_hits = nullptr;
-  WC_CALL(wc_dev_alloc(ctx_, n * 3 * sizeof(float), &d_xyz));
-  WC_CALL(wc_dev_alloc(ctx_, n * sizeof(wc_map_hit), &d_hits));
-  WC_CALL(wc_h2d(ctx_, d_xyz, xyz, n * 3 * sizeof(float)));
-  const wc_points desc{d_xyz, nullptr, 12, 0, n};
+  const DevBuf d_xyz(ctx_, n * 3 * sizeof(float)), d_hits(ctx_, n * sizeof(wc_map_hit));
+  const wc_points desc = UploadXyz(d_xyz, xyz, n);
   uint64_t found = 0;
-  WC_CALL(wc_map_nearest(ctx_, map_, &desc, max_dist, (wc_map_hit *)d_hits, &found));
-  WC_CALL(wc_d2h(ctx_, hits, d_hits, n * sizeof(wc_map_hit)));
-  WC_CALL(wc_dev_free(ctx_, d_xyz));
-  WC_CALL(wc_dev_free(ctx_, d_hits));
+  WC_CALL(wc_map_nearest(ctx_, map_, &desc, max_dist, (wc_map_hit *)d_hits.p, &found));
+  d_hits.ToHost(hits, n * sizeof(wc_map_hit));
   return found;
 }
 size_t LidarOdometry::CropMap(const double lo[3], const double hi[3]) {
@@ -574,16 +582,10 @@ size_t LidarOdometry::CropMap(const double lo[3], const double hi[3]) {
 }
 bool LidarOdometry::CarveMap(const float *xyz, size_t n, const double origin[3], const wc_map_carve_params &params, wc_map_carve_result *result) {
   if (!map_ || !origin || (n && !xyz)) return false;
-  void *d_xyz = nullptr;
-  if (n) {
-    WC_CALL(wc_dev_alloc(ctx_, n * 3 * sizeof(float), &d_xyz));
-    WC_CALL(wc_h2d(ctx_, d_xyz, xyz, n * 3 * sizeof(float)));
-  }
-  const wc_points desc{d_xyz, nullptr, 12, 0, n};
+  const DevBuf d_xyz(ctx_, n * 3 * sizeof(float));
+  const wc_points desc = UploadXyz(d_xyz, xyz, n);
   wc_map_carve_result r;
-  const int rc = wc_map_carve(ctx_, map_, &desc, origin, &params, &r);  // (an argument the library refuses is the caller's: no abort)
-  if (d_xyz) WC_CALL(wc_dev_free(ctx_, d_xyz));
-  if (rc != WC_OK) return false;
+  if (wc_map_carve(ctx_, map_, &desc, origin, &params, &r) != WC_OK) return false;  // (as in AlignToMap)
   if (result) *result = r;
   return true;
 }

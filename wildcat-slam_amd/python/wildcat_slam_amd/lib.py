@@ -3,6 +3,7 @@
 There is NO CPU fallback: if the HIP library is missing or no gfx950 device is visible, every compute entry
 point raises.  (`load()` alone works without a GPU so that the CPU test-suite can check the exported symbols.)
 """
+import contextlib
 import ctypes as C
 import os
 import re
@@ -634,8 +635,10 @@ class PointMap:
         self.ctx._ck(self.lib.wc_map_insert(self.ctx.h, self.h, C.byref(desc), C.byref(rej)))
         return int(rej.value)
 
-    def _upload(self, points):
-        """POINT records or an (n, 3) float32 array -> (device buffer or None, its wc_points descriptor)"""
+    @contextlib.contextmanager
+    def _uploaded(self, points, out_dtype=None):
+        """POINT records or an (n, 3) float32 array in HBM for the length of a with block -> (its wc_points descriptor, a device buffer
+        for one out_dtype record per point, or None); both are freed on the way out"""
         points = np.ascontiguousarray(points)
         if points.dtype == R.POINT:
             stride = 48
@@ -644,16 +647,18 @@ class PointMap:
             stride = 12
         n = len(points)
         d = self.ctx.to_device(points) if n else None
-        return d, R.Points(d.ptr if d else 0, 0, stride, 0, n)
+        d_out = self.ctx.alloc(out_dtype.itemsize * max(n, 1)) if out_dtype is not None else None
+        try:
+            yield R.Points(d.ptr if d else 0, 0, stride, 0, n), d_out
+        finally:
+            for b in (d_out, d):
+                if b:
+                    b.free()
 
     def insert(self, points):
         """POINT records or an (n, 3) float32 array (uploaded for the call) -> points not inserted"""
-        d, desc = self._upload(points)
-        try:
+        with self._uploaded(points) as (desc, _):
             return self.insert_device(desc)
-        finally:
-            if d:
-                d.free()
 
     def nearest_device(self, desc, max_dist, d_hits, want_count=True):
         """queries already in HBM (a wc_points descriptor) -> MAP_HIT records in d_hits (wc_map_nearest); returns the number found, or
@@ -666,15 +671,9 @@ class PointMap:
     def nearest(self, queries, max_dist=np.inf):
         """POINT records or an (n, 3) float32 array (uploaded for the call) -> MAP_HIT array: per query the nearest centroid among the
         27 voxels around it, within max_dist (count = 0: none)"""
-        d, desc = self._upload(queries)
-        d_hits = self.ctx.alloc(R.MAP_HIT.itemsize * max(desc.n, 1))
-        try:
+        with self._uploaded(queries, R.MAP_HIT) as (desc, d_hits):
             self.nearest_device(desc, max_dist, d_hits)
             return d_hits.download(R.MAP_HIT, desc.n)
-        finally:
-            d_hits.free()
-            if d:
-                d.free()
 
     def crop(self, lo, hi):
         """keeps the voxels that intersect the box [lo, hi] (+-inf allowed) and compacts the table (wc_map_crop) -> voxels removed"""
@@ -694,12 +693,8 @@ class PointMap:
         """POINT records or an (n, 3) float32 array (uploaded for the call): the voxels that at least min_rays of the rays origin -> point
         pass through, farther than `shell` voxels from the ray's end, and in which no point of the call lies, are selected and counted
         (wc_map_carve; this version does not remove them) -> dict(rays_used, rays_skipped, steps, voxels_removed, points_removed)"""
-        d, desc = self._upload(points)
-        try:
+        with self._uploaded(points) as (desc, _):
             return self.carve_device(desc, origin, map_carve_params(max_range, min_range, shell, min_rays, max_steps))
-        finally:
-            if d:
-                d.free()
 
     def size(self):
         """-> (voxels, points inserted)"""
@@ -765,15 +760,9 @@ class PointMap:
     def nearest_plane(self, queries, max_dist=np.inf, min_points=3):
         """POINT records or an (n, 3) float32 array (uploaded for the call) -> MAP_PLANE_HIT array: nearest()'s record per query, and
         the plane of the voxel found (flags bit 1) where it holds at least min_points points"""
-        d, desc = self._upload(queries)
-        d_hits = self.ctx.alloc(R.MAP_PLANE_HIT.itemsize * max(desc.n, 1))
-        try:
+        with self._uploaded(queries, R.MAP_PLANE_HIT) as (desc, d_hits):
             self.nearest_plane_device(desc, max_dist, min_points, d_hits)
             return d_hits.download(R.MAP_PLANE_HIT, desc.n)
-        finally:
-            d_hits.free()
-            if d:
-                d.free()
 
     def linearize_device(self, desc, T, params, d_rows=None):
         """points already in HBM (a wc_points descriptor) moved by T (3 x 4 row-major) -> MAP_NORMAL_EQ record (wc_map_linearize: the
@@ -790,15 +779,9 @@ class PointMap:
         if params is None:
             kw.setdefault("max_dist", self.voxel)
             params = map_reg_params(**kw)
-        d, desc = self._upload(points)
-        d_rows = self.ctx.alloc(R.MAP_REG_ROW.itemsize * max(desc.n, 1)) if want_rows else None
-        try:
+        with self._uploaded(points, R.MAP_REG_ROW if want_rows else None) as (desc, d_rows):
             ne = self.linearize_device(desc, T, params, d_rows)
             return (ne, d_rows.download(R.MAP_REG_ROW, desc.n)) if want_rows else ne
-        finally:
-            for b in (d, d_rows):
-                if b:
-                    b.free()
 
     def align_device(self, desc, T, opts):
         """wc_map_align on points already in HBM -> (T (3, 4), summary dict)"""
@@ -813,12 +796,8 @@ class PointMap:
         opts: a wc_map_align_opts, or params (a wc_map_reg_params, default max_dist = the voxel size) and map_align_opts' keywords"""
         if opts is None:
             opts = map_align_opts(params if params is not None else map_reg_params(self.voxel), **kw)
-        d, desc = self._upload(points)
-        try:
+        with self._uploaded(points) as (desc, _):
             return self.align_device(desc, T, opts)
-        finally:
-            if d:
-                d.free()
 
     def clear(self):
         self.ctx._ck(self.lib.wc_map_clear(self.ctx.h, self.h))
