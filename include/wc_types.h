@@ -180,6 +180,35 @@ typedef struct wc_map_carve_result { /* 40 bytes */
   uint64_t points_removed; /* ... and the points they hold                                      */
 } wc_map_carve_result;
 
+/* Answer of wc_map_raycast for one ray (wildcat_hip.h; not a reference type).  48 bytes, 8-aligned; the first 32 bytes are laid out as
+ * wc_map_hit's. */
+typedef struct wc_map_ray_hit {
+  float xyz[3];    /* centroid of the hit voxel: the very float triple wc_map_export returns for it                     */
+  uint32_t count;  /* its point count; 0 = no hit (then xyz = key = 0, step = 0, t = +inf)                             */
+  int32_t key[3];  /* its voxel index                                                                                  */
+  uint32_t flags;  /* bit 0: the ray was not cast (then tested = 0 too)                                                */
+  double t;        /* parameter at which the ray enters the hit voxel: origin + t (p - origin); 0 at the origin's voxel */
+  uint32_t step;   /* i: the hit voxel is k^(i) of the ray's walk                                                      */
+  uint32_t tested; /* positions of the walk this ray tested, the hit included                                          */
+} wc_map_ray_hit;
+
+/* wc_map_raycast (wildcat_hip.h): which rays of a call are cast, which positions of a walk are tested, what counts as occupied. */
+typedef struct wc_map_raycast_params { /* 32 bytes */
+  double min_range;    /* [m] 0 <= min_range <= max_range: a ray is cast iff min_range^2 <= |p - origin|^2 <= max_range^2       */
+  double max_range;    /* [m] may be +inf                                                                                  */
+  uint32_t first_step; /* 0..65536: positions k^(i) with i < first_step are not tested                                     */
+  uint32_t end_shell;  /* 0..9: positions nearer than this to the end voxel (Chebyshev, in voxels) are not tested; 0: none */
+  uint32_t min_points; /* >= 1: a voxel with fewer points does not stop a ray                                              */
+  uint32_t max_steps;  /* 1..65536: rays whose walk is longer are not cast and counted                                     */
+} wc_map_raycast_params;
+
+typedef struct wc_map_raycast_result { /* 32 bytes */
+  uint64_t rays_cast;    /* rays that were walked                             */
+  uint64_t rays_skipped; /* every other point of the call (flags bit 0)       */
+  uint64_t hits;         /* rays with count != 0                              */
+  uint64_t tested;       /* sum of the rays' `tested`                         */
+} wc_map_raycast_result;
+
 /* Communicator of a multi-GPU job: one process (and one wc_ctx) per GPU.  The library calls these for its few collectives;
  * wc_comm_rccl_init() installs an in-library RCCL implementation, tests / other runtimes install callbacks.
  * All buffers are DEVICE pointers on the ctx's GPU; a callback returns 0 on success and must have completed (or be

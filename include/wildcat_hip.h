@@ -72,6 +72,8 @@ int wc_ctx_set_params(wc_ctx *ctx, const wc_params *params);
  *                      whatever the value
  *   map_carve_groups (0) wc_map_carve: workgroups of its ray kernel (0: chosen from the point count); the five counts are the same
  *                      whatever the value
+ *   map_cast_groups (0) wc_map_raycast: workgroups of its kernel (0: chosen from the point count); every output byte is the same
+ *                      whatever the value
  *   lm_radius0         initial trust-region radius of wc_window_solve: 10^value (default -1 = the library's 1e4); tests use it to
  *                      look at the first step at other damping levels
  * Tests use it to run both forms of a choice on the same data.  Unknown names return WC_ERR_ARG. */
@@ -423,6 +425,42 @@ int wc_map_crop(wc_ctx *ctx, wc_map *m, const double lo[3], const double hi[3], 
  * this and do not remove it). */
 int wc_map_carve(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double origin[3], const wc_map_carve_params *params,
                  wc_map_carve_result *h_out);
+
+/* Ray casting: what does the map put along a ray?  Every point p of `pts` (DEVICE pointers, the wc_points rules of wc_map_insert: either
+ * stride, pts->time ignored) is the END of a ray from `origin` - ONE position for the whole call, in the map's frame; "in a direction up to
+ * a reach" is the end point origin + reach * direction, and it is the end point that defines the ray - and d_hits (DEVICE, 8-aligned)
+ * receives one wc_map_ray_hit per point: the first occupied voxel among the positions of the ray's walk that are tested.  The map is read,
+ * never written, and so is every scratch another call of the map uses.  The ray and its walk are wc_map_carve's, word for word, in fp64
+ * without fused multiply-add, so a restatement on the exported map (tests/map_raycast_ref.py) reproduces every record byte for byte:
+ *   ray      o = origin, P = (double)p, d = P - o, len2 = (d_x d_x + d_y d_y) + d_z d_z; k0 = floor(o / v), ke = floor(P / v) per axis
+ *            (VoxelLoc, true division); M = sum over the axes of |ke_a - k0_a|
+ *   cast     iff p is finite, |k0_a| and |ke_a| < 2^20, min_range^2 <= len2 <= max_range^2 (the squares formed once on the host) and
+ *            M <= max_steps - wc_map_carve's "used"; every other point counts in rays_skipped and its record has flags = 1
+ *   walk     k^(0) = k0, ..., k^(M) = ke.  At a step the candidate axes are those with k_a != ke_a; for a candidate
+ *            b_a = (double)(k_a + (ke_a > k0_a ? 1 : 0)) * v, t_a = (b_a - o_a) * inv_a, inv_a = 1.0 / d_a formed once per ray; the lowest
+ *            candidate axis steps by sign(ke_a - k0_a) unless a later candidate's t is strictly smaller (ties: the lowest axis); the walk
+ *            reaches ke after exactly M steps for any input - a counted loop
+ *   tested   position i is tested iff i >= first_step and max_a |k^(i)_a - ke_a| >= end_shell.  end_shell = 0 tests all M + 1 positions,
+ *            ke included; end_shell = s + 1 tests exactly the positions a wc_map_carve with shell = s sees through.  The distance to ke
+ *            never grows along a walk: the tested positions are one contiguous run, and the walk ends behind it
+ *   hit      the first tested position whose voxel is occupied with count >= min_points; the walk ends there
+ *   t        the parameter at which the ray enters the hit voxel, a point of the ray being o + t d: 0.0 for i = 0, otherwise the
+ *            winning t_a of the step from k^(i-1) to k^(i), the very double the step rule compared.  The range is t * |d|; it is left
+ *            to the caller and no square root is formed
+ *   record   xyz = the hit voxel's centroid, the float triple wc_map_export returns for it; count = its point count; key = k^(i);
+ *            step = i; tested = the number of positions this ray tested, the hit included.  A miss: xyz = key = 0, count = 0, step = 0,
+ *            t = +inf, tested as walked.  A ray that is not cast: the same with tested = 0 and flags = 1
+ * h_out (may be NULL): rays_cast, rays_skipped, hits and tested, the sum of the records' field - integer functions of the call, independent
+ * of grid size (development option map_cast_groups), order and schedule.  Asking for it waits for the stream; passing NULL returns
+ * without waiting, as wc_map_nearest does.  Plain and WC_MAP_MOMENTS maps alike; an empty map makes every cast ray a miss; pts->n = 0 is
+ * WC_OK.
+ * WC_ERR_ARG: a NULL argument other than h_out (d_hits with n > 0 included); d_hits not 8-aligned; a non-finite origin; a NaN or negative
+ * range; min_range > max_range; first_step > 65536; end_shell > 9; min_points = 0; max_steps outside 1..65536; pts->n >= 2^31; a wc_points
+ * the insert would refuse; a map of another context.
+ * Limits: one origin per call; a ray that grazes a surface is stopped by surface voxels well before its own return (what
+ * end_shell = 1 hits on a static scene); every step is a hash probe - no coarse level skips empty space. */
+int wc_map_raycast(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double origin[3], const wc_map_raycast_params *params,
+                   wc_map_ray_hit *d_hits, wc_map_raycast_result *h_out);
 
 /* map surfels: the plane through every voxel's points (WC_MAP_MOMENTS) ------------------------------------------------------------ */
 /* A map created with WC_MAP_MOMENTS holds nine more 64-bit words per slot (112 instead of 40 bytes, wc_map_info).  Per inserted point

@@ -33,8 +33,12 @@
 //                   walk, eight steps ahead of the probes: keys, hashes and shell tests of a batch, its first-slot key loads issued
 //                   together, then the chains (read-only) and one no-return atomic add per occupied voxel seen through;
 //                   k_map_count<map_sel_carve> then counts the voxels the words select: wc_map_carve (which reports and does not remove yet)
+//   k_map_raycast  ray casting: the carve's ray and walk, read-only: one lane per ray, its M + 1 positions eight at a time - keys, hashes and
+//                   tested-flags of a batch, its first-slot key loads issued together, then the chains in ascending order up to the first
+//                   voxel with enough points - and one 48-byte wc_map_ray_hit per ray; no atomics but its four counters': wc_map_raycast
 // Shared pieces: map_voxel_of (the voxel-index rule, host and device), map_find_from (the read-only probe chain), block_count (a
-// workgroup's counters), map_points_ok (a wc_points argument), map_replace_table (new table, rehash, free the old one)
+// workgroup's counters), map_points_ok (a wc_points argument), map_replace_table (new table, rehash, free the old one), map_ray_of /
+// map_ray_begin / map_ray_step (a ray's setup and the step rule of its voxel walk: the carve and the ray cast)
 // Growth policy: before an insert of n points the host takes an upper bound B of the occupied slots (the exact count of the last
 // completed insert's read-back plus every point inserted after it); when 2 (B + n) > cap the table is rehashed into the smallest power
 // of two >= 2 (B + n) slots.  The table is therefore at most half full at every probe, and an insert never runs out of room.
@@ -71,6 +75,8 @@ struct wc_map {
   unsigned long long *h_lin = nullptr;  // ... and the pinned landing place of the result (first use)
   wc_buf b_carve;                    // wc_map_carve: its five counter lines, then one u32 word per slot (first use, grown with the table)
   unsigned long long *h_carve = nullptr;  // ... and the pinned landing place of the counters (first use)
+  wc_buf b_cast;                     // wc_map_raycast: its four counter lines (first use); nothing another call reads or writes
+  unsigned long long *h_cast = nullptr;  // ... and their pinned landing place (first use)
 };
 
 namespace {
@@ -92,6 +98,9 @@ constexpr int kCompactChunk = 2048;                // slots per workgroup of k_m
 constexpr int kCarveThreads = 256;
 constexpr int kCarveBatch = 8;                     // steps of a ray whose first-slot key loads are in flight together
 constexpr unsigned kCarveEnd = 0x80000000u;        // a slot's word: bit 31 = an end voxel of this call; low 31 bits = through(k)
+constexpr int kCastThreads = 256;
+constexpr int kCastBatch = 8;                      // positions of a ray whose first-slot key loads are in flight together
+constexpr int kCastCast = 0, kCastSkip = 16, kCastHits = 32, kCastTested = 48, kCastCtrWords = 64;  // u64 word of each of wc_map_raycast's counters
 constexpr int kCarveUsed = 0, kCarveSkip = 16, kCarveSteps = 32, kCarveSelVox = 48, kCarveSelPts = 64, kCarveCtrWords = 80;  // u64 word of each of wc_map_carve's counters
 
 __device__ __forceinline__ unsigned long long map_hash(unsigned long long k) {  // splitmix64 finaliser
@@ -776,12 +785,54 @@ __device__ __forceinline__ int map_cheb(int ax, int ay, int az, int bx, int by, 
   return max(max(abs(ax - bx), abs(ay - by)), abs(az - bz));
 }
 
+// One ray of a call, as wc_map_carve and wc_map_raycast both define it (include/wildcat_hip.h): the walk's position k (k0 at first), the
+// end voxel e, per axis the step s = sign(e - k0), u = 1 where the walk goes up (the face ahead is then k + 1) and the reciprocal i of the
+// direction (of an axis that never is a candidate: never used; until map_ray_begin: the direction itself), and the number of steps M
+struct map_ray {
+  int kx, ky, kz, ex, ey, ez, sx, sy, sz, ux, uy, uz;
+  double ix, iy, iz;
+  unsigned M;
+};
+// the ray from the call's origin (ox, oy, oz) to the point P whose voxel is (ex, ey, ez): its k, e and M, and the direction d in r.i;
+// false: the ray is not walked (the origin has no voxel, len2 outside the ranges or M > max_steps)
+__device__ __forceinline__ bool map_ray_of(const map_ray_args &A, double ox, double oy, double oz, double px, double py, double pz, int ex, int ey, int ez,
+                                           map_ray &r) {
+  r.ix = px - ox, r.iy = py - oy, r.iz = pz - oz;
+  const double len2 = (r.ix * r.ix + r.iy * r.iy) + r.iz * r.iz;
+  r.kx = A.k0[0], r.ky = A.k0[1], r.kz = A.k0[2], r.ex = ex, r.ey = ey, r.ez = ez;
+  r.M = (unsigned)abs(ex - r.kx) + (unsigned)abs(ey - r.ky) + (unsigned)abs(ez - r.kz);
+  return A.k0_ok != 0u && len2 >= A.min2 && len2 <= A.max2 && r.M <= A.max_steps;
+}
+// ... and, for a ray that is walked, what its steps need: s, u and the reciprocals 1.0 / d, formed once per ray
+__device__ __forceinline__ void map_ray_begin(map_ray &r) {
+  r.sx = r.ex > r.kx ? 1 : (r.ex < r.kx ? -1 : 0), r.sy = r.ey > r.ky ? 1 : (r.ey < r.ky ? -1 : 0), r.sz = r.ez > r.kz ? 1 : (r.ez < r.kz ? -1 : 0);
+  r.ux = r.ex > r.kx ? 1 : 0, r.uy = r.ey > r.ky ? 1 : 0, r.uz = r.ez > r.kz ? 1 : 0;
+  r.ix = 1.0 / r.ix, r.iy = 1.0 / r.iy, r.iz = 1.0 / r.iz;
+}
+// the parameter at which a ray crosses the face ahead of voxel index k on one axis: the face's coordinate comes from the integer every
+// time, so nothing drifts
+__device__ __forceinline__ double map_face_t(int k, int u, double v, double o, double inv) { return ((double)(k + u) * v - o) * inv; }
+// the step rule: among the axes that have not arrived, the one whose next face is crossed first; a later axis wins only on a strictly
+// smaller parameter.  The position moves when `live`; returns the axis
+__device__ __forceinline__ int map_ray_step(map_ray &r, double v, double ox, double oy, double oz, bool live) {
+  const bool cx = r.kx != r.ex, cy = r.ky != r.ey, cz = r.kz != r.ez;
+  const double tx = map_face_t(r.kx, r.ux, v, ox, r.ix), ty = map_face_t(r.ky, r.uy, v, oy, r.iy), tz = map_face_t(r.kz, r.uz, v, oz, r.iz);
+  int ax = cx ? 0 : (cy ? 1 : 2);
+  double bt = cx ? tx : (cy ? ty : tz);
+  if (cx && cy && ty < bt) ax = 1, bt = ty;
+  if ((cx || cy) && cz && tz < bt) ax = 2, bt = tz;
+  r.kx += (live && ax == 0) ? r.sx : 0;
+  r.ky += (live && ax == 1) ? r.sy : 0;
+  r.kz += (live && ax == 2) ? r.sz : 0;
+  return ax;
+}
+
 // One lane per point (include/wildcat_hip.h: wc_map_carve states every expression).  The end voxel's word gets bit 31; a used ray then
 // walks its M voxel steps, known before the loop, B at a time: the B positions, their keys, hashes and shell tests come first - the next
 // voxel does not depend on what a probe finds - with the B first-slot key loads issued as they are formed; only then are the loads looked
 // at, the chains followed and the words of the occupied voxels incremented (no-return atomics).  |k - ke| shrinks monotonically on
 // every axis, so the first position inside the shell ends the walk: nothing after it is seen through.  k^(M) = ke never is, and is not
-// visited.  Every index below is a compile-time constant (no scratch); the axis is chosen and applied with selects.
+// visited.  Every index below is a compile-time constant (no scratch); the axis is chosen and applied with selects (map_ray_step).
 template <int B>
 __global__ void __launch_bounds__(kCarveThreads) k_map_carve(wc_points pts, map_ray_args A, const unsigned long long *keys, unsigned long long mask,
                                                              unsigned *words, unsigned long long *cctr) {
@@ -802,41 +853,26 @@ __global__ void __launch_bounds__(kCarveThreads) k_map_carve(wc_points pts, map_
       unsigned long long es = map_hash(ekey) & mask;
       if (map_find_from(keys, mask, ekey, es, keys[es])) atomicOr(&words[es], kCarveEnd);
     }
-    const double dx = px - ox, dy = py - oy, dz = pz - oz;
-    const double len2 = (dx * dx + dy * dy) + dz * dz;
-    int kx = A.k0[0], ky = A.k0[1], kz = A.k0[2];
-    const unsigned M = (unsigned)abs(kex - kx) + (unsigned)abs(key_ - ky) + (unsigned)abs(kez - kz);
-    if (!(A.k0_ok != 0u && len2 >= A.min2 && len2 <= A.max2 && M <= A.max_steps)) {
+    map_ray r;
+    if (!map_ray_of(A, ox, oy, oz, px, py, pz, kex, key_, kez, r)) {
       ++n_skip;
       continue;
     }
     ++n_used;
-    n_steps += M;
-    const int sx = kex > kx ? 1 : (kex < kx ? -1 : 0), sy = key_ > ky ? 1 : (key_ < ky ? -1 : 0), sz = kez > kz ? 1 : (kez < kz ? -1 : 0);
-    const int ux = kex > kx ? 1 : 0, uy = key_ > ky ? 1 : 0, uz = kez > kz ? 1 : 0;
-    const double ix = 1.0 / dx, iy = 1.0 / dy, iz = 1.0 / dz;  // (of a non-candidate axis: never used)
-    for (unsigned base = 0; base < M; base += B) {  // a counted loop: at most ceil(M / B) rounds
-      if (map_cheb(kx, ky, kz, kex, key_, kez) <= shell) break;
+    n_steps += r.M;
+    map_ray_begin(r);
+    for (unsigned base = 0; base < r.M; base += B) {  // a counted loop: at most ceil(M / B) rounds
+      if (map_cheb(r.kx, r.ky, r.kz, kex, key_, kez) <= shell) break;
       unsigned long long key[B], h[B], cur[B];
 #pragma unroll
       for (int j = 0; j < B; ++j) {
-        const bool live = base + j < M;
-        const bool thru = live && map_cheb(kx, ky, kz, kex, key_, kez) > shell;
+        const bool live = base + j < r.M;
+        const bool thru = live && map_cheb(r.kx, r.ky, r.kz, kex, key_, kez) > shell;
         // (a step that is not seen through: the empty mark, which the settling loop skips; its load reads slot 0 and is dropped)
-        key[j] = thru ? map_pack(kx, ky, kz) : kMapEmpty;
+        key[j] = thru ? map_pack(r.kx, r.ky, r.kz) : kMapEmpty;
         h[j] = thru ? map_hash(key[j]) & mask : 0ull;
         cur[j] = keys[h[j]];
-        // the step: among the axes that have not arrived, the one whose next face is crossed first; a later axis wins only on a strictly
-        // smaller parameter.  The face's coordinate comes from the integer every time: nothing drifts
-        const bool cx = kx != kex, cy = ky != key_, cz = kz != kez;
-        const double tx = ((double)(kx + ux) * v - ox) * ix, ty = ((double)(ky + uy) * v - oy) * iy, tz = ((double)(kz + uz) * v - oz) * iz;
-        int ax = cx ? 0 : (cy ? 1 : 2);
-        double bt = cx ? tx : (cy ? ty : tz);
-        if (cx && cy && ty < bt) ax = 1, bt = ty;
-        if ((cx || cy) && cz && tz < bt) ax = 2, bt = tz;
-        kx += (live && ax == 0) ? sx : 0;
-        ky += (live && ax == 1) ? sy : 0;
-        kz += (live && ax == 2) ? sz : 0;
+        map_ray_step(r, v, ox, oy, oz, live);
       }
 #pragma unroll
       for (int j = 0; j < B; ++j) {
@@ -846,6 +882,88 @@ __global__ void __launch_bounds__(kCarveThreads) k_map_carve(wc_points pts, map_
     }
   }
   block_count<kCarveThreads>({n_used, n_skip, n_steps}, {cctr + kCarveUsed, cctr + kCarveSkip, cctr + kCarveSteps});
+}
+
+// ---- ray casting (wc_map_raycast) -------------------------------------------------------------------------------------------------
+// One lane per ray (include/wildcat_hip.h: wc_map_raycast states every expression), the carve's ray (map_ray_of, map_ray_step) with another
+// ending: the M + 1 positions k^(0) .. k^(M) are taken B at a time - keys, hashes and tested-flags of a batch first, its first-slot key
+// loads issued as they are formed; an untested position carries the empty mark - and only then looked at in ascending order.  Read-only: no
+// atomics but the counters'.  A lane is done at its first hit: a tested position whose voxel is there with at least min_points points
+// (the count is a dependent load behind the chain; with min_points = 1 the first voxel found is the hit, so it is loaded once per ray).
+// The Chebyshev distance to ke never grows, so a batch that begins inside the end shell ends the walk.  Of a batch only the axis by which
+// each position was entered is kept, two bits each in one word: the hit's t is formed again from the hit voxel's index, the very
+// expression the step rule compared (map_face_t).  Every register-array index and shift is a compile-time constant; the loop is counted.
+template <int B>
+__global__ void __launch_bounds__(kCastThreads) k_map_raycast(wc_points pts, map_ray_args A, unsigned first_step, unsigned min_points,
+                                                              const unsigned long long *keys, const long long *pay, unsigned long long mask,
+                                                              wc_map_ray_hit *hits, unsigned long long *cctr) {
+  static_assert(B <= 16, "two bits per position of a batch in one 32-bit word");
+  unsigned long long n_cast = 0, n_skip = 0, n_hit = 0, n_tested = 0;
+  const double v = A.v, ox = A.o[0], oy = A.o[1], oz = A.o[2];
+  const int shell = (int)A.shell;
+  const uint64_t stride = (uint64_t)gridDim.x * kCastThreads;
+  for (uint64_t i = (uint64_t)blockIdx.x * kCastThreads + threadIdx.x; i < pts.n; i += stride) {
+    const float *f = (const float *)((const char *)pts.xyz + i * pts.xyz_stride);
+    const double px = (double)f[0], py = (double)f[1], pz = (double)f[2];
+    int kex, key_, kez;
+    map_ray r;
+    const bool cast = map_voxel_of(px, py, pz, v, kex, key_, kez) && map_ray_of(A, ox, oy, oz, px, py, pz, kex, key_, kez, r);
+    unsigned tested = 0, hstep = 0, hax = 3, hcount = 0;
+    unsigned long long hkey = kMapEmpty, hslot = 0;
+    if (cast) {
+      map_ray_begin(r);
+      int ax_in = 3;  // the axis by which the position at hand was entered; 3: it is k^(0)
+      for (unsigned base = 0; base <= r.M; base += B) {  // a counted loop: at most M / B + 1 rounds
+        if (hkey != kMapEmpty || map_cheb(r.kx, r.ky, r.kz, kex, key_, kez) < shell) break;
+        unsigned long long key[B], h[B], cur[B];
+        unsigned axes = 0;
+#pragma unroll
+        for (int j = 0; j < B; ++j) {
+          const unsigned at = base + j;
+          const bool test = at <= r.M && at >= first_step && map_cheb(r.kx, r.ky, r.kz, kex, key_, kez) >= shell;
+          // (a position that is not tested: the empty mark, which the loop below skips; its load reads slot 0 and is dropped)
+          key[j] = test ? map_pack(r.kx, r.ky, r.kz) : kMapEmpty;
+          h[j] = test ? map_hash(key[j]) & mask : 0ull;
+          cur[j] = keys[h[j]];
+          axes |= (unsigned)ax_in << (2 * j);
+          ax_in = map_ray_step(r, v, ox, oy, oz, at < r.M);
+        }
+#pragma unroll
+        for (int j = 0; j < B; ++j) {
+          if (hkey != kMapEmpty || key[j] == kMapEmpty) continue;
+          ++tested;
+          if (!map_find_from(keys, mask, key[j], h[j], cur[j])) continue;
+          const unsigned c = (unsigned)pay[4 * h[j] + 3];
+          if (c >= min_points) hkey = key[j], hslot = h[j], hcount = c, hstep = base + j, hax = (axes >> (2 * j)) & 3u;
+        }
+      }
+    }
+    const bool hit = hkey != kMapEmpty;
+    n_cast += cast ? 1u : 0u, n_skip += cast ? 0u : 1u, n_hit += hit ? 1u : 0u, n_tested += tested;
+    float cx = 0.f, cy = 0.f, cz = 0.f;
+    int hx = 0, hy = 0, hz = 0;
+    double t = __builtin_inf();
+    if (hit) {
+      const longlong2 *p = (const longlong2 *)(pay + 4 * hslot);
+      const longlong2 p0 = p[0], p1 = p[1];
+      const double cnt = (double)hcount;
+      hx = map_unpack(hkey, 0), hy = map_unpack(hkey, 1), hz = map_unpack(hkey, 2);
+      cx = map_centroid(hx, v, p0.x, cnt), cy = map_centroid(hy, v, p0.y, cnt), cz = map_centroid(hz, v, p1.x, cnt);
+      // the face through which the step into the hit voxel went: the one ahead of the voxel before it on that axis
+      const double tx = map_face_t(hx - r.sx, r.ux, v, ox, r.ix), ty = map_face_t(hy - r.sy, r.uy, v, oy, r.iy),
+                   tz = map_face_t(hz - r.sz, r.uz, v, oz, r.iz);
+      t = hax == 0u ? tx : (hax == 1u ? ty : (hax == 2u ? tz : 0.0));
+    }
+    // the 48-byte record as six 8-byte stores (the record is 8-aligned)
+    uint2 *o = (uint2 *)(hits + i);
+    o[0] = make_uint2(__float_as_uint(cx), __float_as_uint(cy));
+    o[1] = make_uint2(__float_as_uint(cz), hcount);
+    o[2] = make_uint2((unsigned)hx, (unsigned)hy);
+    o[3] = make_uint2((unsigned)hz, cast ? 0u : 1u);
+    ((double *)o)[4] = t;
+    o[5] = make_uint2(hstep, tested);
+  }
+  block_count<kCastThreads>({n_cast, n_skip, n_hit, n_tested}, {cctr + kCastCast, cctr + kCastSkip, cctr + kCastHits, cctr + kCastTested});
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
@@ -991,11 +1109,13 @@ extern "C" int wc_map_destroy(wc_ctx *ctx, wc_map *m) {
   wc_buf_release(ctx, m->b_cnt);
   wc_buf_release(ctx, m->b_lin);
   wc_buf_release(ctx, m->b_carve);
+  wc_buf_release(ctx, m->b_cast);
   (void)hipStreamSynchronize(ctx->stream);  // (the pinned counters may still be the target of an enqueued copy)
   if (m->ev_ctr) (void)hipEventDestroy(m->ev_ctr);
   if (m->h_ctr) (void)hipHostFree(m->h_ctr);
   if (m->h_lin) (void)hipHostFree(m->h_lin);
   if (m->h_carve) (void)hipHostFree(m->h_carve);
+  if (m->h_cast) (void)hipHostFree(m->h_cast);
   delete m;
   return WC_OK;
 }
@@ -1418,5 +1538,46 @@ extern "C" int wc_map_carve(wc_ctx *ctx, wc_map *m, const wc_points *pts, const 
   WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   h_out->rays_used = m->h_carve[kCarveUsed], h_out->rays_skipped = m->h_carve[kCarveSkip], h_out->steps = m->h_carve[kCarveSteps];
   h_out->voxels_removed = m->h_carve[kCarveSelVox], h_out->points_removed = m->h_carve[kCarveSelPts];
+  return WC_OK;
+}
+
+// ---- casting rays to their first occupied voxel (include/wildcat_hip.h: wc_map_raycast) --------------------------------------------
+extern "C" int wc_map_raycast(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double origin[3], const wc_map_raycast_params *params,
+                              wc_map_ray_hit *d_hits, wc_map_raycast_result *h_out) {
+  wc_dev_guard dg_(ctx);
+  const wc_map_raycast_params *p = params;
+  if (!map_ok(ctx, m) || !map_points_ok(pts) || !origin || !p || pts->n >= ((uint64_t)1 << 31) || (pts->n && (!d_hits || (uintptr_t)d_hits % 8)))
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (n < 2^31, d_hits 8-aligned), or a map of another context", __func__);
+  if (!(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2])) || !(p->min_range >= 0.0) ||
+      !(p->max_range >= p->min_range) || p->first_step > 65536 || p->end_shell > 9 || p->min_points < 1 || p->max_steps < 1 || p->max_steps > 65536)
+    return wc_fail(ctx, WC_ERR_ARG,
+                   "%s: origin not finite, or params out of range (0 <= min_range <= max_range, first_step <= 65536, end_shell <= 9, "
+                   "min_points >= 1, 1 <= max_steps <= 65536)",
+                   __func__);
+  if (h_out) std::memset(h_out, 0, sizeof(*h_out));
+  if (pts->n == 0) return WC_OK;  // (no ray: nothing is launched)
+  map_ray_args A;
+  A.v = m->voxel;
+  A.min2 = p->min_range * p->min_range, A.max2 = p->max_range * p->max_range;
+  for (int a = 0; a < 3; ++a) A.o[a] = origin[a];
+  A.k0_ok = map_voxel_of(origin[0], origin[1], origin[2], m->voxel, A.k0[0], A.k0[1], A.k0[2]) ? 1u : 0u;
+  A.shell = p->end_shell, A.max_steps = p->max_steps;
+  // the call's own four counter lines, zeroed per call: neither the map nor any scratch of another call is written
+  WC_TRY(wc_ensure(ctx, m->b_cast, (size_t)kCastCtrWords * 8));
+  if (!m->h_cast) WC_HIP(ctx, hipHostMalloc((void **)&m->h_cast, kCastCtrWords * 8));
+  unsigned long long *cctr = (unsigned long long *)m->b_cast.p;
+  WC_HIP(ctx, hipMemsetAsync(cctr, 0, (size_t)kCastCtrWords * 8, ctx->stream));
+  const uint64_t blocks = (pts->n + kCastThreads - 1) / kCastThreads;
+  uint64_t grid = std::min<uint64_t>(blocks, (uint64_t)8 * m->cus);
+  if (ctx->dev.map_cast_groups > 0) grid = std::min<uint64_t>(blocks, (uint64_t)ctx->dev.map_cast_groups);  // (development option)
+  k_map_raycast<kCastBatch><<<(unsigned)grid, kCastThreads, 0, ctx->stream>>>(*pts, A, p->first_step, p->min_points, m->keys, m->pay, m->cap - 1,
+                                                                             d_hits, cctr);
+  WC_HIP(ctx, hipGetLastError());
+  if (h_out) {
+    WC_HIP(ctx, hipMemcpyAsync(m->h_cast, cctr, kCastCtrWords * 8, hipMemcpyDeviceToHost, ctx->stream));
+    WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    h_out->rays_cast = m->h_cast[kCastCast], h_out->rays_skipped = m->h_cast[kCastSkip];
+    h_out->hits = m->h_cast[kCastHits], h_out->tested = m->h_cast[kCastTested];
+  }
   return WC_OK;
 }

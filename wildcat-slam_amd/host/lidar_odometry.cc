@@ -589,6 +589,17 @@ bool LidarOdometry::CarveMap(const float *xyz, size_t n, const double origin[3],
   if (result) *result = r;
   return true;
 }
+bool LidarOdometry::CastMap(const float *xyz, size_t n, const double origin[3], const wc_map_raycast_params &params, wc_map_ray_hit *hits,
+                            wc_map_raycast_result *result) {
+  if (!map_ || !origin || (n && (!xyz || !hits))) return false;
+  const DevBuf d_xyz(ctx_, n * 3 * sizeof(float)), d_hits(ctx_, n * sizeof(wc_map_ray_hit));
+  const wc_points desc = UploadXyz(d_xyz, xyz, n);
+  wc_map_raycast_result r;
+  if (wc_map_raycast(ctx_, map_, &desc, origin, &params, (wc_map_ray_hit *)d_hits.p, &r) != WC_OK) return false;  // (as in AlignToMap)
+  if (n) d_hits.ToHost(hits, n * sizeof(wc_map_ray_hit));
+  if (result) *result = r;
+  return true;
+}
 bool LidarOdometry::SetMapKeepRadius(double radius) {
   if (!(radius >= 0.0)) return false;
   config_.map_keep_radius = radius;

@@ -111,6 +111,11 @@ class LidarOdometry {
   // wc_map_carve for the rays origin -> each of n host points (xyz: n x 3 floats, the map's frame): *result (may be null) as the library
   // leaves it - what the rays select; the map is not modified.  false without a map or with arguments the library refuses
   bool CarveMap(const float *xyz, size_t n, const double origin[3], const wc_map_carve_params &params, wc_map_carve_result *result);
+  // wc_map_raycast for the rays origin -> each of n host points (xyz: n x 3 floats, the map's frame): hits receives n records - per ray the
+  // first occupied voxel its walk tests -, *result (may be null) the call's counters; the map is not modified.  false without a map or with
+  // arguments the library refuses.  Nothing in AddLidarScan calls it
+  bool CastMap(const float *xyz, size_t n, const double origin[3], const wc_map_raycast_params &params, wc_map_ray_hit *hits,
+               wc_map_raycast_result *result);
   // wall time [ms] of the last completed sweep's map step (the undistortion when fill_outputs does not already form it, the insert's
   // enqueue - its kernel runs behind on the stream - and, with map_keep_radius, the crop, which waits).  Not part of last_stage_ms()
   double last_map_ms() const { return last_map_ms_; }

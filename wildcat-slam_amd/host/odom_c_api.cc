@@ -230,6 +230,11 @@ int wc_odom_map_linearize(void *h, const float *xyz, uint64_t n, const double T[
 int wc_odom_map_carve(void *h, const float *xyz, uint64_t n, const double origin[3], const wc_map_carve_params *params, wc_map_carve_result *result) {
   return params && ((LidarOdometry *)h)->CarveMap(xyz, n, origin, *params, result) ? 1 : 0;
 }
+// LidarOdometry::CastMap for n host points (n x 3 floats) into n host records; 1 = done, 0 = no map or refused arguments
+int wc_odom_map_raycast(void *h, const float *xyz, uint64_t n, const double origin[3], const wc_map_raycast_params *params, wc_map_ray_hit *hits,
+                        wc_map_raycast_result *result) {
+  return params && ((LidarOdometry *)h)->CastMap(xyz, n, origin, *params, hits, result) ? 1 : 0;
+}
 // LioConfig::map_keep_radius: 0 = unbounded map; returns 0, or WC_ERR_ARG for a negative or NaN radius
 int wc_odom_set_map_keep_radius(void *h, double radius) { return ((LidarOdometry *)h)->SetMapKeepRadius(radius) ? 0 : WC_ERR_ARG; }
 // Cloud2FromXyz (host/wire_formats.h): the field table (3 x {offset, datatype, count}), point_step and the payload of n points

@@ -608,6 +608,15 @@ def _carve_dict(r):
     return {k: int(getattr(r, k)) for k in ("rays_used", "rays_skipped", "steps", "voxels_removed", "points_removed")}
 
 
+def map_raycast_params(max_range, min_range=0.0, first_step=0, end_shell=0, min_points=1, max_steps=4096):
+    """wc_map_raycast_params"""
+    return R.MapRaycastParams(float(min_range), float(max_range), int(first_step), int(end_shell), int(min_points), int(max_steps))
+
+
+def _raycast_dict(r):
+    return {k: int(getattr(r, k)) for k in ("rays_cast", "rays_skipped", "hits", "tested")}
+
+
 def _pose12(T):
     T = np.ascontiguousarray(np.asarray(T, np.float64).reshape(-1)[:12])
     assert T.size == 12, "T: 3 x 4 (or 4 x 4) row-major"
@@ -695,6 +704,33 @@ class PointMap:
         (wc_map_carve; this version does not remove them) -> dict(rays_used, rays_skipped, steps, voxels_removed, points_removed)"""
         with self._uploaded(points) as (desc, _):
             return self.carve_device(desc, origin, map_carve_params(max_range, min_range, shell, min_rays, max_steps))
+
+    def raycast_device(self, desc, origin, params, d_hits, want_result=True):
+        """points already in HBM (a wc_points descriptor) as the ends of rays from origin -> MAP_RAY_HIT records in d_hits
+        (wc_map_raycast); returns the counters as a dict, or None without waiting when want_result is False"""
+        o = (C.c_double * 3)(*[float(x) for x in origin])
+        res = R.MapRaycastResult()
+        self.ctx._ck(self.lib.wc_map_raycast(self.ctx.h, self.h, C.byref(desc), o, C.byref(params), C.c_void_p(d_hits.ptr if d_hits else 0),
+                                             C.byref(res) if want_result else None))
+        return _raycast_dict(res) if want_result else None
+
+    def raycast(self, points, origin, max_range, min_range=0.0, first_step=0, end_shell=0, min_points=1, max_steps=4096):
+        """POINT records or an (n, 3) float32 array (uploaded for the call) as the ends of rays from origin -> (MAP_RAY_HIT array: per
+        ray the first voxel with at least min_points points among the tested positions of its walk - those from first_step on and at
+        least end_shell voxels from the ray's end -, count = 0: none; dict(rays_cast, rays_skipped, hits, tested))"""
+        with self._uploaded(points, R.MAP_RAY_HIT) as (desc, d_hits):
+            res = self.raycast_device(desc, origin, map_raycast_params(max_range, min_range, first_step, end_shell, min_points, max_steps), d_hits)
+            return d_hits.download(R.MAP_RAY_HIT, desc.n), res
+
+    def raycast_dirs(self, origin, dirs, reach, **kw):
+        """cast in a direction up to a reach: raycast() of the end points origin + reach * dir (reach: one number or one per row of dirs),
+        formed in float64 on the host and cast to float32.  It is the END POINT that defines the ray - its voxel, its walk and the scale of
+        t (range = t * |end - origin|) are those of the rounded float32 end, not of the direction.  max_range defaults to +inf"""
+        o = np.asarray(origin, np.float64).reshape(3)
+        d = np.asarray(dirs, np.float64).reshape(-1, 3)
+        ends = (o + np.asarray(reach, np.float64).reshape(-1, 1) * d).astype(np.float32)
+        kw.setdefault("max_range", np.inf)
+        return self.raycast(ends, o, **kw)
 
     def size(self):
         """-> (voxels, points inserted)"""
@@ -967,6 +1003,17 @@ class Odometry:
         if not self.lib.wc_odom_map_carve(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), o, C.byref(params), C.byref(res)):
             return None
         return _carve_dict(res)
+
+    def map_raycast(self, xyz, origin, max_range, min_range=0.0, first_step=0, end_shell=0, min_points=1, max_steps=4096):
+        """wc_map_raycast of the facade's map with the rows of xyz ((n, 3) float32) as the ends of rays from origin (LidarOdometry::CastMap)
+        -> (MAP_RAY_HIT array, dict of the counters), or None without a map or with arguments the library refuses"""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        o = (C.c_double * 3)(*[float(x) for x in origin])
+        params, res = map_raycast_params(max_range, min_range, first_step, end_shell, min_points, max_steps), R.MapRaycastResult()
+        hits = np.zeros(max(len(xyz), 1), R.MAP_RAY_HIT)
+        if not self.lib.wc_odom_map_raycast(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), o, C.byref(params), R.ptr(hits), C.byref(res)):
+            return None
+        return hits[: len(xyz)], _raycast_dict(res)
 
     def map_ms(self):
         """wall time [ms] of the last sweep's map step (not part of stage_ms())"""

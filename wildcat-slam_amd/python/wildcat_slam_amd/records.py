@@ -43,6 +43,10 @@ MAP_REG_ROW = np.dtype([("J", "f8", 6), ("d", "f8"), ("k", "f8")])  # wc_map_reg
 MAP_NORMAL_EQ = np.dtype([("H", "f8", 21), ("g", "f8", 6), ("cost", "f8"), ("n_used", "u8"), ("n_found", "u8")])  # wc_map_normal_eq
 assert MAP_REG_ROW.itemsize == 64 and MAP_NORMAL_EQ.itemsize == 240 and MAP_NORMAL_EQ.fields["cost"][1] == 216
 
+# wc_map_ray_hit: the first 32 bytes as MAP_HIT's (flags: bit 0 = the ray was not cast), then the entering parameter and the walk's counts
+MAP_RAY_HIT = np.dtype([("xyz", "f4", 3), ("count", "u4"), ("key", "i4", 3), ("flags", "u4"), ("t", "f8"), ("step", "u4"), ("tested", "u4")])
+assert MAP_RAY_HIT.itemsize == 48 and [MAP_RAY_HIT.fields[f][1] for f in ("count", "key", "flags", "t", "step", "tested")] == [12, 16, 28, 32, 40, 44]
+
 assert SURFEL.itemsize == 144 and POSE.itemsize == 56 and IMU_STATE.itemsize == 112 and PAIR.itemsize == 8
 assert SURFEL_ID.itemsize == 16 and POINT.itemsize == 48
 
@@ -199,5 +203,30 @@ class MapCarveResult(C.Structure):
     ]
 
 
+class MapRaycastParams(C.Structure):
+    """wc_map_raycast_params"""
+
+    _fields_ = [
+        ("min_range", C.c_double),
+        ("max_range", C.c_double),
+        ("first_step", C.c_uint32),
+        ("end_shell", C.c_uint32),
+        ("min_points", C.c_uint32),
+        ("max_steps", C.c_uint32),
+    ]
+
+
+class MapRaycastResult(C.Structure):
+    """wc_map_raycast_result"""
+
+    _fields_ = [
+        ("rays_cast", C.c_uint64),
+        ("rays_skipped", C.c_uint64),
+        ("hits", C.c_uint64),
+        ("tested", C.c_uint64),
+    ]
+
+
 assert C.sizeof(MapCarveParams) == 32 and C.sizeof(MapCarveResult) == 40
+assert C.sizeof(MapRaycastParams) == 32 and C.sizeof(MapRaycastResult) == 32
 assert C.sizeof(MapRegParams) == 32 and C.sizeof(MapAlignOpts) == 64 and C.sizeof(MapAlignSummary) == 88
