@@ -112,5 +112,6 @@ def check_fast_and_exact(gpu, oracle, pts, params=None, expect_fast=None, **kw):
                 assert path["fast"], path
             info = check_surfels(s_gpu, id_gpu, s_ref, id_ref, tol=1e-6, t_tol=1e-5) if len(s_ref) else dict(n=0)
             info["fast_path"] = path["fast"]
+        info["path"] = path  # extract_path_info() of the sweep: runs, path bits, lds_cap, ...
         out["exact" if exact else "fast"] = info
     return out, st

@@ -12,6 +12,27 @@ from wildcat_slam_amd import synth
 pytestmark = pytest.mark.gpu
 
 
+FX, WIDE, RUN_SORT, BIN_ORDER = 1, 2, 4, 8  # extract_path_info()["path"]: bits of csrc/extract_plan.h's ExPath
+
+
+@pytest.fixture
+def fresh_gpu():
+    """a context of its own, for the tests that state which rung of the retry ladder a sweep reaches: that depends on what the
+    context remembers of earlier sweeps (general_calls, lds_cap, unordered, the back-off).  The expected `runs` / `path` / `lds_cap`
+    of those tests were RECORDED, on these very sweeps, from the library as it was before the host side moved into
+    extract_plan.h (built with the three reporting words of wc_debug_status patched in); they are not derived from the new code."""
+    from wildcat_slam_amd import lib
+
+    ctx = lib.Context(0)
+    yield ctx
+    ctx.close()
+
+
+def _rung(res):
+    """(runs, path) of the exact and of the default arithmetic of one _run"""
+    return (res["path"]["runs"], res["path"]["path"]), (res["fast"]["path"]["runs"], res["fast"]["path"]["path"])
+
+
 def _run(gpu, oracle, pts, expect_fast=None, **kw):
     """both arithmetic modes of the library against the oracle (helpers.check_fast_and_exact)"""
     info, st = helpers.check_fast_and_exact(gpu, oracle, pts, expect_fast=expect_fast, **kw)
@@ -145,12 +166,16 @@ def test_empty_and_tiny_inputs(gpu, oracle):
     assert len(s) == 0
 
 
-def test_wide_extent_falls_back_to_wide_keys(gpu, oracle):
+def test_wide_extent_falls_back_to_wide_keys(fresh_gpu, oracle):
+    gpu = fresh_gpu
     pts, _ = synth.g2_lattice(64, m=32, span=8)
     far, _ = synth.g2_lattice(64, m=32, span=8, seed=5, t_start=synth.T0 + 0.6)
     far["x"] += np.float32(2000.0)  # > 512 root voxels away from the first point
     pts = synth.concat_points(pts, far)
-    _run(gpu, oracle, pts)
+    res, _ = _run(gpu, oracle, pts)
+    # (recorded) exact: run-binned sort -> key range -> wide keys; default: default path -> exact path -> wide keys
+    assert _rung(res) == ((2, WIDE | BIN_ORDER), (3, WIDE | BIN_ORDER))
+    assert res["fast"]["path"]["fallbacks"] == 1 and res["fast"]["path"]["flags"] == 1
 
 
 def test_capacity_error(gpu):
@@ -186,33 +211,48 @@ def test_c5_cloud_full_size_on_one_gpu(gpu, oracle):
     print(res["fast"])
 
 
-def test_dense_voxels_overflow_fast_sort_and_fall_back(gpu, oracle):
+def test_dense_voxels_overflow_fast_sort_and_fall_back(fresh_gpu, oracle):
     # 3 root voxels with ~9 000 points each: a bucket of the fast (bucket) sort overflows and the general radix path
     # must take over transparently; huge roots also exercise the multi-chunk streaming of k_roots
     pts, _ = synth.g2_lattice(3, m=1100, span=4, seed=17)
     assert len(pts) == 3 * 8 * 1100
-    _run(gpu, oracle, pts)
+    res, _ = _run(fresh_gpu, oracle, pts)
+    # (recorded) on a fresh context this sweep is completed by the first pipeline in both modes: its long runs fit the bins, no
+    # bucket overflows.  The bucket-overflow rung is reached by test_layer2_pass_after_a_sweep_without_splits' room.
+    assert _rung(res) == ((1, RUN_SORT | BIN_ORDER), (1, FX | BIN_ORDER))
 
 
-def test_layer2_pass_after_a_sweep_without_splits(gpu, oracle):
+def test_layer2_pass_after_a_sweep_without_splits(fresh_gpu, oracle):
+    gpu = fresh_gpu
     # the layer-2 launch is skipped when the previous sweep queued no root for it; a sweep that does need it must then be
     # completed by the finish() side (late layer-2 pass + second ordering), and the next regular sweep must be unaffected
     regular, _ = synth.g2_lattice(300, m=32)
     room = synth.g1_room(300_000)
-    _run(gpu, oracle, regular)
+    rungs = [_rung(_run(gpu, oracle, regular)[0])]
     res, st = _run(gpu, oracle, room)
     assert st.nodes_tested[2] > 0  # the room does reach layer 2
-    _run(gpu, oracle, regular)
-    _run(gpu, oracle, room)
+    rungs.append(_rung(res))
+    rungs.append(_rung(_run(gpu, oracle, regular)[0]))
+    rungs.append(_rung(_run(gpu, oracle, room)[0]))
+    # (recorded) exact arithmetic: the room overflows a bucket of the run-binned sort and is repeated with the radix sort, on which
+    # the sweeps that follow start; the default path completes every sweep itself
+    assert [r[0] for r in rungs] == [(1, RUN_SORT | BIN_ORDER), (2, BIN_ORDER), (1, BIN_ORDER), (1, BIN_ORDER)]
+    assert [r[1] for r in rungs] == [(1, FX | BIN_ORDER)] * 4
 
 
-def test_wide_time_hint_overflows_time_bins_and_falls_back(gpu, oracle):
+def test_wide_time_hint_overflows_time_bins_and_falls_back(fresh_gpu, oracle):
+    gpu = fresh_gpu
     # a time hint a thousand times wider than the sweep puts every surfel into one of the 4096 time bins: the bin overflows and
     # the call is completed with the radix sort of the slot keys
     pts, _ = synth.g2_lattice(300, m=32)
     t0, t1 = float(pts["time"][0]), float(pts["time"][-1])
-    _run(gpu, oracle, pts, hint=(t0 - 1.0, t1 + 2000.0))
-    _run(gpu, oracle, pts)
+    res, _ = _run(gpu, oracle, pts, hint=(t0 - 1.0, t1 + 2000.0))
+    # (recorded) the default path overflows its bin and hands the sweep to the exact path; there the time keys of this hint do not
+    # fit 32 bits, so the radix sort of the slot keys runs without a bin ever being tried: one pipeline, bin_order still asked for
+    assert _rung(res) == ((1, RUN_SORT | BIN_ORDER), (2, RUN_SORT | BIN_ORDER))
+    assert res["fast"]["path"]["fallbacks"] == 1 and res["fast"]["path"]["flags"] == 16
+    res, _ = _run(gpu, oracle, pts)
+    assert _rung(res) == ((1, RUN_SORT | BIN_ORDER), (1, FX | BIN_ORDER))
 
 
 def test_unordered_sweep_uses_radix_path_and_stays_there(gpu, oracle):
@@ -226,17 +266,24 @@ def test_unordered_sweep_uses_radix_path_and_stays_there(gpu, oracle):
         _run(gpu, oracle, regular)
 
 
-def test_unordered_small_sweep_stays_on_the_run_binned_path(gpu, oracle):
+def test_unordered_small_sweep_stays_on_the_run_binned_path(fresh_gpu, oracle):
+    gpu = fresh_gpu
     # firing-order sweep small enough for the run bins (one run per point, buckets of a few hundred runs: in-wave bitonic sort,
     # LDS capacity grown on demand); the first call streams with k_roots (binary search in the run offsets), the following
     # ones with k_roots_banks (run statistics of the previous sweep) - all of them must agree with the oracle
+    first = ((1, RUN_SORT | BIN_ORDER), (1, FX | BIN_ORDER))  # (recorded) completed by the first pipeline, in both modes
     room = synth.g1_room(60_000, seed=5)
     for _ in range(3):
-        _run(gpu, oracle, room)
+        res, _ = _run(gpu, oracle, room)
+        assert _rung(res) == first and res["path"]["lds_cap"] == 256
     regular, _ = synth.g2_lattice(150, m=32)
     for _ in range(2):  # back to a sweep with run structure
-        _run(gpu, oracle, regular)
-    _run(gpu, oracle, synth.g1_room(120_000, seed=6))
+        res, _ = _run(gpu, oracle, regular)
+        assert _rung(res) == first and res["path"]["lds_cap"] == 256
+    res, _ = _run(gpu, oracle, synth.g1_room(120_000, seed=6))
+    # (recorded) twice the points: the LDS capacity of k_pt_bucket is doubled twice, the sweep stays on the run-binned sort
+    assert _rung(res) == ((3, RUN_SORT | BIN_ORDER), (1, FX | BIN_ORDER))
+    assert res["path"]["lds_cap"] == 1024 and res["fast"]["path"]["lds_cap"] == 1024
 
 
 @pytest.mark.parametrize("override", [
@@ -301,7 +348,7 @@ def test_soa_point_layouts_match_the_aos_record(gpu, oracle, xyz_stride):
             finally:
                 gpu.set_exact_sums(False)
 
-def test_default_path_backs_off_after_repeated_fall_backs(gpu, oracle):
+def test_default_path_backs_off_after_repeated_fall_backs(fresh_gpu, oracle):
     """a sweep the default (integer-moment) path cannot finish - here: every node observed again after one second, more than its 16 time bins of 0.05 s -
     is repeated on the exact path; when that keeps happening the library goes to the exact path directly for an exponentially
     growing number of sweeps, and comes back to the default path afterwards.  Results are the oracle's all along."""
@@ -309,20 +356,26 @@ def test_default_path_backs_off_after_repeated_fall_backs(gpu, oracle):
     b, _ = synth.g2_lattice(60, m=32, t_start=synth.T0 + 1.0, duration=0.1)  # the same voxels again, one second later
     b["x"] += np.float32(0.001)
     both = synth.concat_points(a, b)
+    gpu = fresh_gpu
     s_ref, i_ref, _ = oracle.extract_surfels(both)
     gpu.set_exact_sums(False)  # (also resets the adaptive state)
-    fast_flags = []
+    fast_flags, runs, paths = [], [], []
     for _ in range(8):
         s, i = gpu.extract_surfels(both)
         helpers.check_surfels(s, i, s_ref, i_ref, tol=1e-6, t_tol=1e-4)
-        fast_flags.append(gpu.extract_path_info()["fast"])
-    info = gpu.extract_path_info()
+        info = gpu.extract_path_info()
+        fast_flags.append(info["fast"]), runs.append(info["runs"]), paths.append(info["path"])
     assert not any(fast_flags)          # this cloud is never finished by the default path ...
     assert 1 <= info["fallbacks"]       # ... which was tried ...
+    # (recorded) ... in sweeps 0, 1, 3 and 7: after the n-th fall-back 2^(n-1) - 1 sweeps start on the exact path
+    assert runs == [2, 2, 1, 2, 1, 1, 1, 2] and info["fallbacks"] == 4
+    assert paths == [RUN_SORT | BIN_ORDER] * 8
     regular, _ = synth.g2_lattice(100, m=32)
     gpu.set_exact_sums(False)
     s, i = gpu.extract_surfels(regular)
-    assert gpu.extract_path_info()["fast"]  # ... and is back for a sweep it can handle
+    info = gpu.extract_path_info()
+    assert info["fast"]  # ... and is back for a sweep it can handle
+    assert (info["runs"], info["path"]) == (1, FX | BIN_ORDER)
 
 
 def test_batched_sweeps_equal_single_sweeps(gpu, oracle):

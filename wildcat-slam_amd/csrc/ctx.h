@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/wildcat_hip.h"
+#include "extract_plan.h"
 
 struct wc_window_state;  // window.hip
 
@@ -87,48 +88,9 @@ struct wc_ctx {
   void *h_stage = nullptr;        // ... and their pinned landing place
   size_t h_stage_cap = 0;
   double *h_mail = nullptr;      // pinned: 64 doubles of mailbox (costs etc.) + 4096 doubles of staging (the window's unknowns)
-  // pending extraction (enqueue/finish split)
-  struct {
-    bool active = false;
-    wc_points pts;
-    double t_lo, t_hi;
-    wc_surfel *d_out;
-    wc_surfel_id *d_ids;
-    uint64_t cap;
-    bool wide;
-    bool general;
-    bool order_general = false;  // this call orders the surfels with the radix sort (a time bin overflowed)
-    int general_calls = 0;       // upcoming calls that start on the radix-sort path right away
-    bool bucket_attr_set = false;  // hipFuncSetAttribute(k_pt_bucket) done on this ctx's device
-    uint32_t lds_cap = 256;      // runs per bucket k_pt_bucket sorts in LDS (256 / 512 / 1024, grows with the data)
-    bool unordered = false;      // the previous sweep had (almost) no run structure: stream with k_roots_banks
-    uint32_t last_splits = 256;  // roots the previous call queued for the layer-2 pass (sizes / gates that launch)
-    // the tail of the pipeline (layer-2 pass, surfel order, status read-back) is re-run by finish() when the call skipped
-    // the layer-2 launch and roots were queued for it after all
-    uint32_t ticket = 0, ticket_seq = 0;  // completion ticket of the sweep in flight (0: none - finish waits for the stream)
-    bool fx_active = false;      // this call runs on the fast (integer-moment) path
-    bool fx_dirty = false;       // the fast path's tables may hold garbage (an aborted sweep): memset before the next use
-    uint32_t fx_last_flags = 0, fx_fallbacks = 0, fx_last_why = 0;
-    bool fx_spill_full = false;
-    bool fx_split = false;
-    // batched extraction (wc_extract_surfels_batch_*): a sub-context prepares its sweep - tables, control block, kernel arguments
-    // in roots_args - and leaves the launches to the parent, which runs K sweeps' kernels as one launch chain
-    bool batch_defer = false, deferred = false;
-    unsigned fx_tiles = 0, fx_ngrid = 0;  // the node stage of the current sweep runs as k_fx_walk + k_fx_test (extract_split.inc)  // the spill pool of the fast path overflowed once: sized for the worst case from then on
-    bool fx_long_lists = false;  // the last fast sweep walked long record lists: k_fx_merge runs before k_fx_nodes
-    bool fx_long_lists2 = false;  // ... the same for the layer-2 pass
-    uint32_t fx_backoff = 0, fx_skip_calls = 0;  // sweeps that go straight to the exact path after fall-backs (exponential)
-    bool fx_ctrl_ready = false;  // the fast path's two control blocks are initialised
-    int fx_parity = 0;           // which of them the next fast sweep uses
-    bool precleared = false;     // the control block has been cleared (on the stream) by the previous finish()
-    bool layer2_done = true;
-    int (*tail)(wc_ctx *, bool) = nullptr;
-    alignas(16) unsigned char roots_args[768];
-    uint64_t total_slots;
-    uint32_t bin_cap;
-    unsigned slot_end_bit;
-    bool fast_slots;
-  } ex;
+  // extraction (extract_plan.h): the sweep in flight (enqueue / finish split) and what the context remembers between sweeps
+  ExSweep ex;
+  ExMemory ex_mem;
   wc_window_state *win = nullptr;
   wc_ctx *aux = nullptr;  // helper context of wc_match_pair (second stream + scratch), owned by this ctx
   hipEvent_t ev_aux = nullptr;  // orders the helper's stream behind the ctx stream

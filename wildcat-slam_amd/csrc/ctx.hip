@@ -183,9 +183,9 @@ extern "C" int wc_ctx_set_dev_option(wc_ctx *ctx, const char *name, int value) {
   for (const DevOpt &o : kDevOpts)
     if (strcmp(o.name, name) == 0) {
       ctx->dev.*(o.field) = value;
-      ctx->ex.fx_backoff = ctx->ex.fx_skip_calls = 0;
+      ex_reset_backoff(ctx->ex_mem);
       if (ctx->aux) ctx->aux->dev = ctx->dev;
-      for (wc_ctx *sub : ctx->batch_subs) sub->dev = ctx->dev, sub->ex.fx_backoff = sub->ex.fx_skip_calls = 0;
+      for (wc_ctx *sub : ctx->batch_subs) sub->dev = ctx->dev, ex_reset_backoff(sub->ex_mem);
       return WC_OK;
     }
   return wc_fail(ctx, WC_ERR_ARG, "wc_ctx_set_dev_option: unknown option '%s'", name);
@@ -253,7 +253,7 @@ extern "C" int wc_ctx_set_params(wc_ctx *ctx, const wc_params *params) {
   if (!ctx || !params) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
   WC_TRY(check_params(ctx, params));
   ctx->P = *params;
-  ctx->ex.fx_backoff = ctx->ex.fx_skip_calls = 0;  // new parameters: the adaptive path choice of the extraction starts afresh
+  ex_reset_backoff(ctx->ex_mem);  // new parameters: the adaptive path choice of the extraction starts afresh
   return WC_OK;
 }
 

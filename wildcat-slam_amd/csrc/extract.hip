@@ -3,9 +3,11 @@
 // everything beneath it (BuildVoxelMap :186-220, InitOctoTree :128-140, CutOctoTree :142-184, InitPlane :82-126,
 // ExtractSurfelInfo :304-314, ClusterSurfels :12-65).  Decision rules: SURVEY.md Appendix A.
 //
-// Pipeline of one sweep (all on one stream, no host synchronisation until wc_extract_surfels_finish):
-//   0. k_init        every per-call fill in one launch (status words, bucket / bin counters, mailbox address); on the fast
-//                    path it is issued by the PREVIOUS finish(), so that it runs while the host turns around
+// Two pipelines behind one interface: the default one on integer moments (extract_fast.inc, extract_split.inc) and the exact one
+// below, which forms every sum in the reference's order and also completes the sweeps the default one hands back.
+// Exact pipeline of one sweep (all on one stream, no host synchronisation until wc_extract_surfels_finish):
+//   0. k_init        every per-call fill in one launch (status words, bucket / bin counters, mailbox address); usually
+//                    issued by the PREVIOUS finish(), so that it runs while the host turns around
 //   1. k_pt_runs     the only pass over the AoS input: root-voxel key relative to the voxel of point 0
 //                    (floor(p / (double)0.8f), true fp64 division; 10 bits per axis, 21 in the wide fallback), RUNS of
 //                    consecutive points with one key, one composite per run into the bin of its bucket (4096 buckets)
@@ -19,8 +21,11 @@
 //                    split are queued
 //   5. k_roots<2>    layer 2 of the queued roots (launched only if the previous sweep needed it)
 //   6. k_slot_emit   time order (surfel_extraction.cc:334) + copy slot -> caller's buffer, count to the host mailbox
-// Fallbacks, chosen by finish() from the flags: radix-sort path (k_keygen + rocPRIM + k_heads + k_roots_banks) for
-// sweeps without run structure or with overfull bins, 21-bit keys for wide sweeps, radix sort of the slot keys.
+// Host side: what a sweep runs is an ExPath (extract_plan.h) - default or exact pipeline, 32- or 64-bit keys, run-binned or
+// radix point sort (k_keygen + rocPRIM + k_heads + k_roots_banks: sweeps without run structure or with overfull bins), time
+// bins or a radix sort of the slot keys.  wc_extract_surfels_enqueue takes ex_first_path(), finish() waits for the sweep's
+// completion ticket and repeats the sweep on ex_next_path() while the flags it raised ask for it; every decision, size and
+// the state kept between sweeps is in that header, this file only launches (enqueue_path) and waits (ex_wait).
 // The path is HBM/latency bound (20 B read per point, 144 B written per surfel); no MFMA.
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -40,9 +45,8 @@ constexpr int kProdStride = 66;  // row stride (doubles) of k_roots' moment-majo
 constexpr unsigned kRootsGrid = 256 * 16;  // wavefronts of the layer-0/1 pass (one root each from the dense work list; all resident)
 constexpr unsigned kEmitGrid = 256 * 8;   // wavefronts of the node-test + emission pass (three roots at a time each)
 constexpr unsigned kRoots2Grid = 256 * 4;  // wavefronts of the (rare) layer-2 pass
-constexpr int kBuckets = 4096;    // buckets of the composite sorts
 constexpr int kTile = 2048;       // points per workgroup of k_pt_runs
-constexpr uint32_t kFlagKeyRange = 1u, kFlagSlotOverflow = 2u, kFlagTimeRange = 4u, kFlagBucketOverflow = 8u, kFlagSlotBinOverflow = 16u, kFlagLdsOverflow = 32u;
+// (kBuckets, the kFlag* status bits, kSlotBinMax, kPtBinMax: extract_plan.h, through ctx.h)
 
 struct ExParams {
   double vs;           // (double)voxel_size
@@ -354,11 +358,11 @@ struct RootLocator {
 // and candidate clusters to k_roots_emit; roots with layer-1 nodes that were tested and are not planes (CutOctoTree
 // recursion, cc:175-182) are queued for PHASE 2, a second launch of the same streaming code over the 64 layer-2 nodes with
 // the tests and the emission fused in (rare on regular scenes, so the common case keeps a 7 KB LDS footprint).
-// Work assignment: RUNS mode takes root number blockIdx.x of the dense work list (RootLocator); the radix-sort path scans a
-// fixed range of the sparse head table.  (A device-side dequeue word serialised at ~90 dequeues/us and cost more than it
-// balanced.)
-template <typename K, int PHASE, bool RUNS>
-__global__ void __launch_bounds__(64) k_roots(RootsArgs A, const K *__restrict__ keys) {
+// Runs behind the run-binned point sort only (the radix-sort path streams with k_roots_banks): a root's points are its sorted
+// runs.  Work assignment: root number blockIdx.x of the dense work list (RootLocator).  (A device-side dequeue word
+// serialised at ~90 dequeues/us and cost more than it balanced.)
+template <typename K, int PHASE>
+__global__ void __launch_bounds__(64) k_roots(RootsArgs A) {
   constexpr int phase = PHASE;  // octree pass: 1 = root + layer 1 (streaming only, k_roots_emit finishes it), 2 = layer 2 (fused)
   constexpr int ntab = (phase == 1) ? 9 : 64;
   __shared__ double s_open[ntab * kMom];
@@ -408,25 +412,19 @@ __global__ void __launch_bounds__(64) k_roots(RootsArgs A, const K *__restrict__
     unsigned long long tick_ = __builtin_readcyclecounter();
     uint32_t prof_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
-    // RUNS: lane r < 64 keeps run r of this root (start index, root-local offset) in registers
+    // lane r < 64 keeps run r of this root (start index, root-local offset) in registers
     uint32_t r_start = 0, r_off = 0;
-    K rootkey;
-    if (RUNS) {
-      uint64_t comp = 0;
-      if ((uint32_t)lane < min(hrec.nr, 64u)) {
-        comp = A.runs[(size_t)hrec.gidx + lane];
-        r_off = A.run_off[(size_t)hrec.gidx + lane];
-      }
-      r_start = comp_start(comp);
-      r_off -= (uint32_t)__builtin_amdgcn_readfirstlane((int)r_off);
-      rootkey = (K)key_join(hrec.gidx / A.run_cap, (uint32_t)__builtin_amdgcn_readfirstlane((int)comp_rest(comp)));
-    } else {
-      rootkey = keys[head];
+    uint64_t comp = 0;
+    if ((uint32_t)lane < min(hrec.nr, 64u)) {
+      comp = A.runs[(size_t)hrec.gidx + lane];
+      r_off = A.run_off[(size_t)hrec.gidx + lane];
     }
+    r_start = comp_start(comp);
+    r_off -= (uint32_t)__builtin_amdgcn_readfirstlane((int)r_off);
+    const K rootkey = (K)key_join(hrec.gidx / A.run_cap, (uint32_t)__builtin_amdgcn_readfirstlane((int)comp_rest(comp)));
     // index of the root's p-th point (time order)
     // (called by all lanes: the register path broadcasts run descriptors with readlane)
     auto point_index = [&](uint32_t pp, bool ok_lane) -> uint32_t {
-      if (!RUNS) return ok_lane ? A.vals[head + pp] : 0u;
       if (hrec.nr <= 64u) {
         uint32_t st = (uint32_t)__builtin_amdgcn_readfirstlane((int)r_start), o = 0;
         for (uint32_t k = 1; k < hrec.nr; ++k) {
@@ -476,7 +474,7 @@ __global__ void __launch_bounds__(64) k_roots(RootsArgs A, const K *__restrict__
 
     // ---- software-pipelined chunk loop: the next 64 points are in flight while the current ones stream ----
     uint32_t pp = lane;  // position inside the root
-    bool valid = RUNS ? (pp < hrec.total) : (head + pp < A.n && keys[head + pp] == rootkey);
+    bool valid = pp < hrec.total;
     double px = 0, py = 0, pz = 0, pt = 0;
     uint32_t idx = point_index(pp, valid);
     if (valid) {
@@ -529,7 +527,7 @@ __global__ void __launch_bounds__(64) k_roots(RootsArgs A, const K *__restrict__
       bool nvalid_next = false;
       if (nvalid == 64) {
         pp += 64;
-        nvalid_next = RUNS ? (pp < hrec.total) : (head + pp < A.n && keys[head + pp] == rootkey);
+        nvalid_next = pp < hrec.total;
         idx = point_index(pp, nvalid_next);
         if (nvalid_next) {
           load_xyz(A.pts, idx, px, py, pz);
@@ -733,25 +731,12 @@ __global__ void __launch_bounds__(64) k_roots(RootsArgs A, const K *__restrict__
       const SplitJob job = A.split_jobs[it];
       do_root(A.heads[job.slot], job.slot, job.ncand, job.split1);  // split1 = layer-1 octants that get split (cc:175-182)
     }
-  } else if (RUNS) {  // compacted root list: one root per wavefront
+  } else {  // compacted root list: one root per wavefront
     RootLocator loc;
     loc.init(A, lane);
     for (uint32_t w = blockIdx.x; w < loc.total; w += gridDim.x) {
       const uint32_t tslot = loc.slot_of(A, w);
       do_root(A.heads[tslot], tslot, 0u, 0ull);
-    }
-  } else {  // sparse head table: every wavefront owns a contiguous range of slots
-    const uint32_t per_wave = (A.nslots + gridDim.x - 1) / gridDim.x;
-    const uint32_t it_end = min((blockIdx.x + 1) * per_wave, A.nslots);
-    for (uint32_t it = blockIdx.x * per_wave; it < it_end; it += 64) {
-      HeadRec my_head{0xFFFFFFFFu, 0u, 0u, 0u};
-      if (it + lane < it_end) my_head = A.heads[it + lane];
-      unsigned long long live_mask = __ballot(my_head.pos != 0xFFFFFFFFu);
-      while (live_mask) {
-        const int hb = __ffsll((long long)live_mask) - 1;
-        live_mask &= live_mask - 1;
-        do_root(HeadRec{(uint32_t)__shfl((int)my_head.pos, hb), 0u, 0u, 0u}, it + (uint32_t)hb, 0u, 0ull);
-      }
     }
   }
 }
@@ -1362,7 +1347,6 @@ __global__ void __launch_bounds__(256) k_fix_ties(const uint64_t *__restrict__ k
 // fixed-capacity bin per bucket), so what is left is: the exclusive prefix of the counts (every workgroup sums the counts
 // in front of its four buckets: 16 KB out of L2, cheaper than a separate scan launch), the order inside a bucket (rank by
 // counting, one wavefront per bucket, a handful of surfels each) and the 160-byte copy slot -> output, 16 B per lane.
-constexpr int kSlotBinMax = 512;
 struct SlotEmitArgs {
   const uint32_t *counts;
   const uint64_t *bins;
@@ -1769,8 +1753,6 @@ __global__ void __launch_bounds__(256) k_pt_bucket(uint64_t *bins, uint32_t bin_
   }
 }
 
-constexpr uint32_t kPtBinMax = 1024;  // runs per bucket the in-LDS path takes (4 wavefronts x 20 B x 1024 = 80 KB of LDS)
-
 // bin capacity for n points: 32 x the mean a cloud without any run structure would produce (voxel occupancy is heavy
 // tailed: a room sweep of 64 k points has buckets of 280 runs at a mean of 16), 64 at least
 inline uint32_t pt_bin_cap(uint64_t n) {
@@ -1805,21 +1787,21 @@ int clear_ctrl(wc_ctx *ctx) {
 }
 
 // counts (run counts | point counts) and status must be cleared by the caller.  Leaves the sorted runs in b_misc[1], their
-// point offsets in b_misc[3] and the live roots in the head slot table.  The LDS capacity per bucket (ctx->ex.lds_cap:
+// point offsets in b_misc[3] and the live roots in the head slot table.  The LDS capacity per bucket (ctx->ex_mem.lds_cap:
 // 256, 512 or 1024 runs) follows the data: a bucket above it raises kFlagLdsOverflow and the call is repeated one size up.
 int point_sort_runs(wc_ctx *ctx, const wc_points &pts, double vs, HeadRec *head_slots, int min_points, uint32_t *status) {
   hipStream_t st = ctx->stream;
   const uint64_t n = pts.n;
   const uint32_t cap = pt_bin_cap(n);
-  const uint32_t lds_cap = std::min(cap, std::max(64u, ctx->ex.lds_cap));
+  const uint32_t lds_cap = std::min(cap, std::max(64u, ctx->ex_mem.lds_cap));
   WC_TRY(wc_ensure(ctx, ctx->b_misc[1], (uint64_t)kBuckets * cap * 8));  // run bins
   WC_TRY(wc_ensure(ctx, ctx->b_misc[3], (uint64_t)kBuckets * cap * 4));  // point offsets of the sorted runs
   uint32_t *counts = (uint32_t *)ctx->b_ex_ctrl.p + kCtrlCounts;  // run counts | point counts | root_cnt | root_first
   const unsigned tiles = (unsigned)((n + kTile - 1) / kTile);
   const size_t lds = (size_t)4 * lds_cap * 20;
-  if (!ctx->ex.bucket_attr_set) {  // per ctx (= per device), not per process
+  if (!ctx->ex_mem.bucket_attr_set) {  // per ctx (= per device), not per process
     WC_HIP(ctx, hipFuncSetAttribute((const void *)k_pt_bucket, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * kPtBinMax * 20)));
-    ctx->ex.bucket_attr_set = true;
+    ctx->ex_mem.bucket_attr_set = true;
   }
   k_pt_runs<<<tiles, kRunThreads, 0, st>>>(pts, vs, n, counts, (uint64_t *)ctx->b_misc[1].p, cap, status);
   k_pt_bucket<<<kBuckets / 4, 256, lds, st>>>((uint64_t *)ctx->b_misc[1].p, cap, lds_cap, counts, (uint32_t *)ctx->b_misc[3].p, head_slots,
@@ -1862,25 +1844,47 @@ bool fx_applicable(const wc_ctx *ctx, uint64_t n, double t_lo, double t_hi) {
   return true;
 }
 
-int fx_tail(wc_ctx *ctx, bool layer2);
-
-int run_pipeline_fast(wc_ctx *ctx, const wc_points &pts, double t_lo, double t_hi, wc_surfel *d_out, wc_surfel_id *d_ids, uint64_t cap) {
+// ---- what both pipelines share ------------------------------------------------------------------------------------------------
+// the kernels' view of the context's parameters and of the sweep's time hint
+ExParams ex_params(const wc_ctx *ctx) {
   const wc_params &P = ctx->P;
-  const uint64_t n = pts.n;
-  hipStream_t st = ctx->stream;
-  FxArgs A;
-  std::memset(&A, 0, sizeof(A));
-  ExParams &E = A.P;
+  ExParams E{};
   E.vs = (double)P.voxel_size, E.vs_f = P.voxel_size, E.max_layer = P.max_layer, E.min_points = P.min_points;
   E.thr = (double)P.planer_threshold, E.min_like = P.min_plane_likeness;
   for (int i = 0; i < 3; ++i) E.view[i] = P.view_point[i];
   E.gap = P.cluster_gap, E.cluster_min = P.cluster_min_points;
-  E.t_lo_bits = ordered_bits_host(t_lo);
-  E.t_span_bits = ordered_bits_host(t_hi) - E.t_lo_bits;
+  E.t_lo_bits = ordered_bits_host(ctx->ex.t_lo);
+  E.t_span_bits = ordered_bits_host(ctx->ex.t_hi) - E.t_lo_bits;
   E.dbg = ctx->dev.debug_skip;  // (development options: wc_ctx_set_dev_option)
   E.merge_min = ctx->dev.fx_merge_min;
-  unsigned tbits = 1;
-  while (tbits < 64 && (E.t_span_bits >> tbits)) ++tbits;
+  return E;
+}
+
+// stage boundary i of wc_extract_profile (mode 2: only the bracket around the whole stage)
+void ex_mark(wc_ctx *ctx, int i) {
+  if (ctx->ex_prof && (ctx->ex_prof_mode != 2 || i == 1 || i == 5)) (void)hipEventRecord(ctx->ex_ev[i], ctx->stream);
+}
+
+// keeps what the tail needs from this enqueue: finish() may run it a second time, a batch runs it in place of the sweep
+template <typename Args>
+void ex_keep_for_tail(wc_ctx *ctx, const Args &A, int (*tail)(wc_ctx *, bool)) {
+  static_assert(sizeof(Args) <= sizeof(ctx->ex.roots_args), "extract_plan.h: roots_args too small");
+  std::memcpy(ctx->ex.roots_args, &A, sizeof(A));  // (sizes included: slot count, bin capacity, whether the time bins are in use)
+  ctx->ex.tail = tail;
+}
+
+int fx_tail(wc_ctx *ctx, bool layer2);
+
+int run_pipeline_fast(wc_ctx *ctx) {
+  const wc_params &P = ctx->P;
+  ExMemory &M = ctx->ex_mem;
+  const wc_points &pts = ctx->ex.pts;
+  const double t_lo = ctx->ex.t_lo, t_hi = ctx->ex.t_hi;
+  const uint64_t n = pts.n;
+  hipStream_t st = ctx->stream;
+  FxArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.P = ex_params(ctx);
   A.pts = pts;
   A.t_lo = t_lo;
   int e = 0;
@@ -1906,7 +1910,7 @@ int run_pipeline_fast(wc_ctx *ctx, const wc_points &pts, double t_lo, double t_h
     else if (pts.xyz_stride == 12u && pts.time_stride == 8u && px % 16u == 0u && pt % 16u == 0u)
       A.fmt = 2u;
   }
-  const unsigned tiles = (unsigned)((n + kFxTile - 1) / kFxTile);
+  const unsigned tiles = ex_fx_tiles(n);
   A.rec_tiles = tiles;
   // spill pool (partials the tile's 256-cell LDS hash could not take): eight banks by tile index.  A tile spills at most one
   // record per point, so ceil(tiles / 8) x 1024 records per bank can never overflow - used for sweeps up to 2 M points (a sparse
@@ -1915,22 +1919,21 @@ int run_pipeline_fast(wc_ctx *ctx, const wc_points &pts, double t_lo, double t_h
   const uint64_t spill_full = ((uint64_t)tiles + 7) / 8 * kFxTile;
   // (round 5: full size up to 8 M points - a 4 M-point room in firing order overflowed the n / 32 pool on every fresh context, whose first
   // two calls then ran on the exact path; 128 bytes per point of never-cleared memory are nothing on this card)
-  A.spill_per = (uint32_t)((n <= 8000000ull || ctx->ex.fx_spill_full) ? spill_full : std::max<uint64_t>(1024, n / 32));
+  A.spill_per = (uint32_t)((n <= 8000000ull || M.fx_spill_full) ? spill_full : std::max<uint64_t>(1024, n / 32));
   A.rec_cap = tiles * (uint32_t)kFxRecTile + 8u * A.spill_per;
   // slots: the most surfels n points can give, in kFxSub sub-ranges (one per wavefront index mod kFxSub) - but never fewer than 256 per
   // sub-range.  A small sweep runs on few wavefronts and takes slots ahead of the tests that decide who needs one: with 1/16 of
   // 3 n / 20 + 1 per sub-range, a 2 880-point sweep of one-patch roots (120 surfels, 27 slots per sub-range) ran out of slots and
   // was silently repeated on the exact path, every time (found by tests/test_extract_precision_gpu.py).  From 27 k points on the
   // floor changes nothing.
-  const uint64_t total_slots = std::max<uint64_t>((n * (uint64_t)(P.max_layer + 1)) / (uint64_t)P.cluster_min_points + 1, (uint64_t)kFxSub * 256);
-  uint32_t bin_cap = 64;
-  while (bin_cap < kSlotBinMax && (uint64_t)bin_cap * kBuckets < 2 * total_slots) bin_cap *= 2;
+  const uint64_t total_slots = ex_total_slots(n, P.max_layer, P.cluster_min_points, (uint64_t)kFxSub * 256);
+  const uint32_t bin_cap = ex_slot_bin_cap(total_slots);
   WC_TRY(fx_ensure_zero(ctx, ctx->b_fx[0], (size_t)tr * 4));
   WC_TRY(wc_ensure(ctx, ctx->b_fx[1], (size_t)mr * 4));  // dense root list: written before it is read
   WC_TRY(fx_ensure_zero(ctx, ctx->b_fx[2], (size_t)tr * kFxBlockW * 8));
   WC_TRY(fx_ensure_zero(ctx, ctx->b_fx[3], (size_t)A.mq_per * kFxSub * kFxBlockW * 8));
   WC_TRY(wc_ensure(ctx, ctx->b_fx[4], (size_t)2 * A.rec_cap * kFxRecW * 8));  // records: reachable through list heads only, never cleared
-  const unsigned ngrid = std::min<unsigned>(256 * 16, std::max<unsigned>(64, (unsigned)(n / 256)));  // k_fx_nodes<1>; <2> uses fewer
+  const unsigned ngrid = ex_fx_node_grid(n);  // k_fx_nodes<1>; <2> uses fewer
   WC_TRY(wc_ensure(ctx, ctx->b_fx[6], (size_t)ngrid * kFxJobCap * kFxJobW * 8));  // cluster jobs: written before they are read
   // node stage as two kernels (extract_split.inc) where one round of wavefronts does not hold the sweep's parents: above 2 M points
   // (the development option fx_split = 0 / 1 pins the choice: tests run both forms on the same clouds)
@@ -1946,25 +1949,23 @@ int run_pipeline_fast(wc_ctx *ctx, const wc_points &pts, double t_lo, double t_h
   WC_TRY(wc_ensure(ctx, ctx->b_slots, total_slots * sizeof(wc_surfel)));
   WC_TRY(wc_ensure(ctx, ctx->b_slot_ids, total_slots * sizeof(wc_surfel_id)));
   WC_TRY(wc_ensure(ctx, ctx->b_slot_keys[1], (uint64_t)kBuckets * bin_cap * 8));
-  if (ctx->ex.fx_dirty) {  // a previous sweep ended abnormally: everything back to zero
+  if (M.fx_dirty) {  // a previous sweep ended abnormally: everything back to zero
     for (int i : {0, 2, 3}) WC_HIP(ctx, hipMemsetAsync(ctx->b_fx[i].p, 0, ctx->b_fx[i].cap, st));  // (not the root list, not the records)
-    ctx->ex.fx_dirty = false;
+    M.fx_dirty = false;
   }
   // two control blocks, used alternately: k_slot_emit of a sweep clears the block of the next one
   WC_TRY(wc_ensure(ctx, ctx->b_fx[5], (size_t)2 * kCtrlWords * 4));
-  if (!ctx->ex.fx_ctrl_ready) {
+  if (!M.fx_ctrl_ready) {
     WC_HIP(ctx, hipMemsetAsync(ctx->b_fx[5].p, 0, (size_t)2 * kCtrlWords * 4, st));
-    void *dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, ctx->h_status, 0) != hipSuccess) dp = nullptr;
-    const unsigned long long a = (unsigned long long)dp;
+    const unsigned long long a = (unsigned long long)ctx->h_status_dev;  // the mailbox, as the device sees it
     const uint32_t addr[2] = {(uint32_t)a, (uint32_t)(a >> 32)};
     for (int b = 0; b < 2; ++b)
       WC_HIP(ctx, hipMemcpyAsync((uint32_t *)ctx->b_fx[5].p + (size_t)b * kCtrlWords + 8, addr, 8, hipMemcpyHostToDevice, st));
     WC_HIP(ctx, hipStreamSynchronize(st));  // (addr is a stack variable)
-    ctx->ex.fx_ctrl_ready = true;
-    ctx->ex.fx_parity = 0;
+    M.fx_ctrl_ready = true;
+    M.fx_parity = 0;
   }
-  uint32_t *ctrl = (uint32_t *)ctx->b_fx[5].p + (size_t)ctx->ex.fx_parity * kCtrlWords;
+  uint32_t *ctrl = (uint32_t *)ctx->b_fx[5].p + (size_t)M.fx_parity * kCtrlWords;
   for (int q = 0; q < 64; ++q) ctx->h_status[q] = 0;
   A.rkey = (uint32_t *)ctx->b_fx[0].p, A.rlist = (uint32_t *)ctx->b_fx[1].p;
   A.blk = (unsigned long long *)ctx->b_fx[2].p, A.blk2 = (unsigned long long *)ctx->b_fx[3].p;
@@ -1977,11 +1978,8 @@ int run_pipeline_fast(wc_ctx *ctx, const wc_points &pts, double t_lo, double t_h
   A.slot_counts = ctrl + kCtrlBins;
   A.slot_bins = (uint64_t *)ctx->b_slot_keys[1].p;
   A.slot_bin_cap = bin_cap;
-  auto mark = [&](int i) {
-    if (ctx->ex_prof && (ctx->ex_prof_mode != 2 || i == 1 || i == 5)) (void)hipEventRecord(ctx->ex_ev[i], st);
-  };
-  mark(0);
-  mark(1);
+  ex_mark(ctx, 0);
+  ex_mark(ctx, 1);
   static const bool dbg = wc_log_env("WC_FX_DEBUG");
   auto dbg_sync = [&](const char *what) {
     if (!dbg) return;
@@ -1995,25 +1993,16 @@ int run_pipeline_fast(wc_ctx *ctx, const wc_points &pts, double t_lo, double t_h
     fprintf(stderr, " %s flags=%u roots=%u nodes2=%u slots=%u spill=%u\n", hipGetErrorString(e), w[1], r, q, sl, sp);
   };
   if (dbg) fprintf(stderr, "[fx] n=%llu tiles=%u mr_per=%u mq_per=%u tr=%u slots_per=%u bin_cap=%u\n", (unsigned long long)n, tiles, A.mr_per, A.mq_per, tr, A.slots_per, bin_cap);
+  ex_keep_for_tail(ctx, A, &fx_tail);
   if (ctx->ex.batch_defer) {  // wc_extract_surfels_batch_enqueue launches this sweep's kernels together with the other sweeps'
-    static_assert(sizeof(FxArgs) <= sizeof(ctx->ex.roots_args), "ctx.h: roots_args too small");
-    std::memcpy(ctx->ex.roots_args, &A, sizeof(A));
-    ctx->ex.total_slots = total_slots;
-    ctx->ex.bin_cap = bin_cap;
-    ctx->ex.fast_slots = true;
-    ctx->ex.tail = &fx_tail;
-    ctx->ex.d_out = d_out, ctx->ex.d_ids = d_ids, ctx->ex.cap = cap;
-    ctx->ex.layer2_done = P.max_layer >= 2 && ctx->ex.last_splits > 0;
-    // (the node kernels of a batch loop over their sweep's parents, eight per wavefront: a grid of n / 256 blocks per sweep - what
-    // a single sweep's static hand-out wants - is 39 k workgroups for ten sweeps, 34 k of which find nothing to do)
-    ctx->ex.fx_tiles = tiles, ctx->ex.fx_ngrid = std::max(64u, ngrid / 8u);
+    ctx->ex.layer2_done = P.max_layer >= 2 && M.last_splits > 0;
     ctx->ex.deferred = true;
     return WC_OK;
   }
   k_fx_acc<1><<<tiles, kFxThreads, 0, st>>>(A);
   dbg_sync("k_fx_acc<1>");
-  mark(2);
-  if (ctx->ex.fx_long_lists) k_fx_merge<1><<<std::min<unsigned>(ngrid * 2u, 8192u), 128, 0, st>>>(A);
+  ex_mark(ctx, 2);
+  if (M.fx_long_lists) k_fx_merge<1><<<std::min<unsigned>(ngrid * 2u, 8192u), 128, 0, st>>>(A);
   if (ctx->ex.fx_split) {
     k_fx_walk<1><<<ngrid, 64, 0, st>>>(A);
     dbg_sync("k_fx_walk<1>");
@@ -2022,15 +2011,8 @@ int run_pipeline_fast(wc_ctx *ctx, const wc_points &pts, double t_lo, double t_h
     k_fx_nodes<1><<<ngrid, 64, 0, st>>>(A);
   }
   dbg_sync("k_fx_nodes<1>");
-  mark(3);
-  static_assert(sizeof(FxArgs) <= sizeof(ctx->ex.roots_args), "ctx.h: roots_args too small");
-  std::memcpy(ctx->ex.roots_args, &A, sizeof(A));
-  ctx->ex.total_slots = total_slots;
-  ctx->ex.bin_cap = bin_cap;
-  ctx->ex.fast_slots = true;
-  ctx->ex.tail = &fx_tail;
-  ctx->ex.d_out = d_out, ctx->ex.d_ids = d_ids, ctx->ex.cap = cap;
-  return fx_tail(ctx, P.max_layer >= 2 && ctx->ex.last_splits > 0);
+  ex_mark(ctx, 3);
+  return fx_tail(ctx, P.max_layer >= 2 && M.last_splits > 0);
 }
 
 constexpr int kMailTicket = 120;  // word of the pinned mailbox (ctx->h_status) that carries the extraction's completion ticket
@@ -2043,15 +2025,11 @@ int fx_tail(wc_ctx *ctx, bool layer2) {
   hipStream_t st = ctx->stream;
   FxArgs A;
   std::memcpy(&A, ctx->ex.roots_args, sizeof(A));
-  auto mark = [&](int i) {
-    if (ctx->ex_prof && (ctx->ex_prof_mode != 2 || i == 1 || i == 5)) (void)hipEventRecord(ctx->ex_ev[i], st);
-  };
+  ExMemory &M = ctx->ex_mem;
   if (layer2) {
-    const unsigned tiles = (unsigned)((A.pts.n + kFxTile - 1) / kFxTile);
-    k_fx_acc<2><<<tiles, kFxThreads, 0, st>>>(A);
-    const unsigned ngrid = std::min<unsigned>(256 * 16, std::max<unsigned>(64, (unsigned)(A.pts.n / 256)));  // (the job buffer's blocks)
-    if (ctx->ex.fx_long_lists2) k_fx_merge<2><<<std::min(8192u, std::max(64u, ctx->ex.last_splits)), 128, 0, st>>>(A);
-    const unsigned g2 = std::min(std::min(256u * 8u, ngrid), std::max(64u, ctx->ex.last_splits));
+    k_fx_acc<2><<<ex_fx_tiles(A.pts.n), kFxThreads, 0, st>>>(A);
+    if (M.fx_long_lists2) k_fx_merge<2><<<std::min(8192u, std::max(64u, M.last_splits)), 128, 0, st>>>(A);
+    const unsigned g2 = ex_fx_layer2_grid(ex_fx_node_grid(A.pts.n), M.last_splits);
     if (ctx->ex.fx_split) {
       k_fx_walk<2><<<g2, 64, 0, st>>>(A);
       k_fx_test<2><<<g2, 64, 0, st>>>(A);
@@ -2060,20 +2038,20 @@ int fx_tail(wc_ctx *ctx, bool layer2) {
     }
   }
   ctx->ex.layer2_done = layer2;
-  mark(4);
-  uint32_t *next_ctrl = (uint32_t *)ctx->b_fx[5].p + (size_t)(ctx->ex.fx_parity ^ 1) * kCtrlWords;
+  ex_mark(ctx, 4);
+  uint32_t *next_ctrl = (uint32_t *)ctx->b_fx[5].p + (size_t)(M.fx_parity ^ 1) * kCtrlWords;
   static_assert(kCtrlWords <= (kBuckets / 4) * 256, "k_slot_emit's grid covers the control block");
-  k_slot_emit<<<kBuckets / 4, 256, 0, st>>>(A.slot_counts, A.slot_bins, ctx->ex.bin_cap, (const wc_surfel *)ctx->b_slots.p,
+  k_slot_emit<<<kBuckets / 4, 256, 0, st>>>(A.slot_counts, A.slot_bins, A.slot_bin_cap, (const wc_surfel *)ctx->b_slots.p,
                                            (const wc_surfel_id *)ctx->b_slot_ids.p, A.status, ctx->ex.d_out, ctx->ex.d_ids, ctx->ex.cap, next_ctrl,
                                            kCtrlWords);
-  mark(5);
+  ex_mark(ctx, 5);
   // the completion ticket: ONE thread behind the sweep's last kernel stores it to the pinned mailbox and wc_extract_surfels_finish reads
   // host memory instead of waiting for the stream (the LM loop's wait_mail).  Behind a kernel boundary nothing has to be fenced inside
   // k_slot_emit (what round 3's last-workgroup ticket paid for): every store of the sweep has left its L2 when this kernel starts.
   ctx->ex.ticket = 0;
   if (ctx->h_status_dev && !ctx->ex_prof && !ctx->dev.ex_sync) {
-    if (++ctx->ex.ticket_seq == 0u) ++ctx->ex.ticket_seq;
-    ctx->ex.ticket = ctx->ex.ticket_seq;
+    if (++M.ticket_seq == 0u) ++M.ticket_seq;
+    ctx->ex.ticket = M.ticket_seq;
     k_ex_ticket<<<1, 1, 0, st>>>(ctx->h_status_dev + kMailTicket, ctx->ex.ticket);
   }
   static const bool fx_dbg = wc_log_env("WC_FX_DEBUG");
@@ -2089,28 +2067,24 @@ int pipeline_tail(wc_ctx *ctx, bool layer2) {
   RootsArgs A;
   memcpy(&A, ctx->ex.roots_args, sizeof(A));
   uint32_t *status = A.status;
-  wc_surfel *d_out = ctx->ex.d_out;
-  wc_surfel_id *d_ids = ctx->ex.d_ids;
-  const uint64_t cap = ctx->ex.cap, total_slots = ctx->ex.total_slots;
-  auto mark = [&](int i) {
-    if (ctx->ex_prof && (ctx->ex_prof_mode != 2 || i == 1 || i == 5)) (void)hipEventRecord(ctx->ex_ev[i], st);
-  };
+  const uint64_t cap = ctx->ex.cap, total_slots = A.total_slots;
+  const bool fast_slots = A.slot_counts != nullptr;  // bin_order was asked for AND the time keys fit 32 bits: the surfels sit in time bins
   if (layer2) {
-    const unsigned grid2 = std::min(kRoots2Grid, std::max(64u, ctx->ex.last_splits));  // sized by the previous call's queue
+    const unsigned grid2 = std::min(kRoots2Grid, std::max(64u, ctx->ex_mem.last_splits));  // sized by the previous call's queue
     if constexpr (RUNS) {
-      if (ctx->ex.unordered)
+      if (ctx->ex_mem.unordered)
         k_roots_banks<K, 2, true><<<grid2, 64, 0, st>>>(A, (const K *)ctx->b_keys[1].p);
       else
-        k_roots<K, 2, true><<<grid2, 64, 0, st>>>(A, (const K *)ctx->b_keys[1].p);
+        k_roots<K, 2><<<grid2, 64, 0, st>>>(A);
     } else {
       k_roots_banks<K, 2, false><<<grid2, 64, 0, st>>>(A, (const K *)ctx->b_keys[1].p);
     }
   }
   ctx->ex.layer2_done = layer2;
-  mark(4);
-  if (ctx->ex.fast_slots) {
-    k_slot_emit<<<kBuckets / 4, 256, 0, st>>>((const uint32_t *)ctx->b_ex_ctrl.p + kCtrlBins, A.slot_bins, ctx->ex.bin_cap, (const wc_surfel *)ctx->b_slots.p,
-                                             (const wc_surfel_id *)ctx->b_slot_ids.p, status, d_out, d_ids, cap, nullptr, 0u);
+  ex_mark(ctx, 4);
+  if (fast_slots) {
+    k_slot_emit<<<kBuckets / 4, 256, 0, st>>>(A.slot_counts, A.slot_bins, A.slot_bin_cap, (const wc_surfel *)ctx->b_slots.p,
+                                             (const wc_surfel_id *)ctx->b_slot_ids.p, status, ctx->ex.d_out, ctx->ex.d_ids, cap, nullptr, 0u);
   } else {
     k_iota<<<(unsigned)((total_slots + 255) / 256), 256, 0, st>>>((uint32_t *)ctx->b_slot_idx[0].p, total_slots);
     WC_TRY(sort_pairs<uint64_t>(ctx, (uint64_t *)ctx->b_slot_keys[0].p, (uint64_t *)ctx->b_slot_keys[1].p,
@@ -2121,41 +2095,28 @@ int pipeline_tail(wc_ctx *ctx, bool layer2) {
     const uint64_t gth = std::min<uint64_t>(total_slots, cap) * 10;
     if (gth)
       k_gather<<<(unsigned)((gth + 255) / 256), 256, 0, st>>>((const uint32_t *)ctx->b_slot_idx[1].p, (const wc_surfel *)ctx->b_slots.p,
-                                                             (const wc_surfel_id *)ctx->b_slot_ids.p, status, d_out, d_ids, cap);
+                                                             (const wc_surfel_id *)ctx->b_slot_ids.p, status, ctx->ex.d_out, ctx->ex.d_ids, cap);
   }
-  mark(5);
+  ex_mark(ctx, 5);
   // the time-bin path leaves count, queue length and flags in the pinned mailbox itself (k_slot_emit, raise_flag)
-  if (!ctx->ex.fast_slots) WC_HIP(ctx, hipMemcpyAsync(ctx->h_status, status, 32, hipMemcpyDeviceToHost, st));
+  if (!fast_slots) WC_HIP(ctx, hipMemcpyAsync(ctx->h_status, status, 32, hipMemcpyDeviceToHost, st));
   WC_HIP(ctx, hipGetLastError());
   return WC_OK;
 }
 
+// the exact path: K = uint32_t keys, or uint64_t for path.wide (then always behind the radix point sort)
 template <typename K>
-int run_pipeline(wc_ctx *ctx, const wc_points &pts, double t_lo, double t_hi, wc_surfel *d_out, wc_surfel_id *d_ids,
-                 uint64_t cap, bool fast, bool fast_order) {
+int run_pipeline(wc_ctx *ctx, const ExPath &path) {
   const wc_params &P = ctx->P;
+  const wc_points &pts = ctx->ex.pts;
   const uint64_t n = pts.n;
   hipStream_t st = ctx->stream;
-  ExParams E;
-  E.vs = (double)P.voxel_size;
-  E.vs_f = P.voxel_size;
-  E.max_layer = P.max_layer;
-  E.min_points = P.min_points;
-  E.thr = (double)P.planer_threshold;
-  E.min_like = P.min_plane_likeness;
-  for (int i = 0; i < 3; ++i) E.view[i] = P.view_point[i];
-  E.gap = P.cluster_gap;
-  E.cluster_min = P.cluster_min_points;
-  E.t_lo_bits = ordered_bits_host(t_lo);
-  E.dbg = ctx->dev.debug_skip;  // (development options: wc_ctx_set_dev_option)
-  E.merge_min = ctx->dev.fx_merge_min;
-  const uint64_t span = ordered_bits_host(t_hi) - E.t_lo_bits;
-  E.t_span_bits = span;
+  const ExParams E = ex_params(ctx);
   unsigned tbits = 1;
-  while (tbits < 64 && (span >> tbits)) ++tbits;
+  while (tbits < 64 && (E.t_span_bits >> tbits)) ++tbits;
   const unsigned slot_end_bit = tbits >= 63 ? 64 : tbits + 1;  // one extra bit so that ~0 (invalid) sorts last
 
-  const uint64_t total_slots = (n * (uint64_t)(P.max_layer + 1)) / (uint64_t)P.cluster_min_points + 1;
+  const uint64_t total_slots = ex_total_slots(n, P.max_layer, P.cluster_min_points, 0);
   WC_TRY(wc_ensure(ctx, ctx->b_keys[0], n * sizeof(K)));
   WC_TRY(wc_ensure(ctx, ctx->b_keys[1], n * sizeof(K)));
   WC_TRY(wc_ensure(ctx, ctx->b_vals[0], n * 4));
@@ -2170,23 +2131,18 @@ int run_pipeline(wc_ctx *ctx, const wc_points &pts, double t_lo, double t_hi, wc
   WC_TRY(wc_ensure(ctx, ctx->b_slot_idx[1], total_slots * 4));
   WC_TRY(wc_ensure(ctx, ctx->b_misc[0], (n / (uint64_t)(P.min_points + 1) + 2) * sizeof(HeadRec)));
   // the control block: cleared ahead of time by the previous finish() (see clear_ctrl) or right here
-  const bool precleared = ctx->ex.precleared && ctx->b_ex_ctrl.p;
-  ctx->ex.precleared = false;
+  const bool precleared = ctx->ex_mem.precleared && ctx->b_ex_ctrl.p;
+  ctx->ex_mem.precleared = false;
   if (!precleared) WC_TRY(clear_ctrl(ctx));
   for (int q = 0; q < 16; ++q) ctx->h_status[q] = 0;
   uint32_t *status = (uint32_t *)ctx->b_ex_ctrl.p + kCtrlStatus;
 
-  auto mark = [&](int i) {
-    if (ctx->ex_prof && (ctx->ex_prof_mode != 2 || i == 1 || i == 5)) (void)hipEventRecord(ctx->ex_ev[i], st);
-  };
-  mark(0);
-  const bool fast_slots = fast_order && tbits <= 31 && total_slots < (1ull << 31);
-  // capacity of a time bucket's bin: twice the count every bucket would get if EVERY slot held a surfel, 64 at least
-  uint32_t bin_cap = 64;
-  while (bin_cap < kSlotBinMax && (uint64_t)bin_cap * kBuckets < 2 * total_slots) bin_cap *= 2;
+  ex_mark(ctx, 0);
+  const bool fast_slots = path.bin_order && tbits <= 31 && total_slots < (1ull << 31);
+  const uint32_t bin_cap = ex_slot_bin_cap(total_slots);
   const unsigned g256 = (unsigned)((n + 255) / 256);
-  // fast path (32-bit keys): bucket sort of (voxel key, index) composites; general path: rocPRIM radix sort
-  const bool fast_pts = fast && sizeof(K) == 4;
+  // run_sort (32-bit keys): bucket sort of (voxel key, index) composites; otherwise: rocPRIM radix sort
+  const bool fast_pts = path.run_sort && sizeof(K) == 4;
   if (fast_pts || fast_slots) {
     WC_TRY(wc_ensure(ctx, ctx->b_slot_keys[1], (uint64_t)kBuckets * bin_cap * 8));  // slot bins (the general path's sort buffer)
   }
@@ -2201,7 +2157,7 @@ int run_pipeline(wc_ctx *ctx, const wc_points &pts, double t_lo, double t_hi, wc
     for (int q = 0; q < r; ++q) mx = std::max(mx, I.nw[q]);
     k_init<<<(mx + 255) / 256, 256, 0, st>>>(I);
   }
-  mark(1);
+  ex_mark(ctx, 1);
   if (fast_pts) {
     WC_TRY(point_sort_runs(ctx, pts, E.vs, (HeadRec *)ctx->b_misc[0].p, P.min_points, status));  // also fills the head slot table
   } else {
@@ -2233,7 +2189,7 @@ int run_pipeline(wc_ctx *ctx, const wc_points &pts, double t_lo, double t_hi, wc
   A.heads = (const HeadRec *)ctx->b_misc[0].p;
   A.nslots = nslots;
   if (!fast_pts) k_heads<K><<<g256, 256, 0, st>>>((const K *)ctx->b_keys[1].p, n, P.min_points, (HeadRec *)ctx->b_misc[0].p);
-  mark(2);
+  ex_mark(ctx, 2);
   WC_TRY(wc_ensure(ctx, ctx->b_misc[5], (size_t)A.nslots * sizeof(SplitJob)));
   A.split_jobs = (SplitJob *)ctx->b_misc[5].p;
   A.prof = nullptr;
@@ -2248,29 +2204,51 @@ int run_pipeline(wc_ctx *ctx, const wc_points &pts, double t_lo, double t_hi, wc
   const K *skeys = (const K *)ctx->b_keys[1].p;  // sorted keys (general path only; the run path never expands them)
   if (fast_pts) {
     if constexpr (sizeof(K) == 4) {
-      if (ctx->ex.unordered)  // the previous sweep had no run structure: order-independent streaming
+      if (ctx->ex_mem.unordered)  // the previous sweep had no run structure: order-independent streaming
         k_roots_banks<K, 1, true><<<kRootsGrid, 64, 0, st>>>(A, skeys);
       else
-        k_roots<K, 1, true><<<kRootsGrid, 64, 0, st>>>(A, skeys);  // stream root + layer 1
-      mark(3);
+        k_roots<K, 1><<<kRootsGrid, 64, 0, st>>>(A);  // stream root + layer 1
+      ex_mark(ctx, 3);
       k_roots_emit<K, true><<<kEmitGrid, 64, 0, st>>>(A, skeys);  // node tests + emission
     }
   } else {
     k_roots_banks<K, 1, false><<<kRootsGrid, 64, 0, st>>>(A, skeys);  // order-independent streaming (no run structure on this path)
-    mark(3);
+    ex_mark(ctx, 3);
     k_roots_emit<K, false><<<kEmitGrid, 64, 0, st>>>(A, skeys);
   }
-  static_assert(sizeof(RootsArgs) <= sizeof(ctx->ex.roots_args), "ctx.h: roots_args too small");
-  memcpy(ctx->ex.roots_args, &A, sizeof(A));
-  ctx->ex.total_slots = total_slots;
-  ctx->ex.bin_cap = bin_cap;
+  ex_keep_for_tail(ctx, A, fast_pts ? &pipeline_tail<K, (sizeof(K) == 4)> : &pipeline_tail<K, false>);
   ctx->ex.slot_end_bit = slot_end_bit;
-  ctx->ex.fast_slots = fast_slots;
-  ctx->ex.tail = fast_pts ? &pipeline_tail<K, (sizeof(K) == 4)> : &pipeline_tail<K, false>;
   // On regular scenes no root is queued for the layer-2 pass, and even an idle launch of it costs ~4.5 us: it is skipped
   // when the previous call queued nothing (consecutive sweeps look alike); finish() runs the tail again if that guess
   // was wrong.
-  return ctx->ex.tail(ctx, ctx->ex.last_splits > 0);
+  return ctx->ex.tail(ctx, ctx->ex_mem.last_splits > 0);
+}
+
+// one run of the sweep in flight on `path`
+int enqueue_path(wc_ctx *ctx, const ExPath &path) {
+  ctx->ex.path = path;
+  ++ctx->ex.runs;
+  const int rc = path.fx ? run_pipeline_fast(ctx) : path.wide ? run_pipeline<uint64_t>(ctx, path) : run_pipeline<uint32_t>(ctx, path);
+  if (path.fx && rc != WC_OK) ctx->ex_mem.fx_dirty = true;  // (tables half set up)
+  return rc;
+}
+
+// the sweep is done (its ticket has arrived, or the stream is idle); folds the mailbox flag words (raise_flag) into h_status[1]
+int ex_wait(wc_ctx *ctx) {
+  bool arrived = false;
+  if (const uint32_t ticket = ctx->ex.ticket) {  // (fx_tail: the ticket kernel was the last thing enqueued)
+    ctx->ex.ticket = 0;
+    const uint32_t *w = (const uint32_t *)ctx->h_status + kMailTicket;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (uint32_t spin = 0; !arrived; ++spin) {
+      arrived = __atomic_load_n(w, __ATOMIC_ACQUIRE) == ticket;
+      if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) break;
+    }
+  }
+  if (!arrived) WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int i = 0; i < 7; ++i)
+    if (ctx->h_status[8 + i]) ctx->h_status[1] |= 1u << i;
+  return WC_OK;
 }
 
 }  // namespace
@@ -2293,10 +2271,8 @@ extern "C" int wc_extract_surfels_enqueue(wc_ctx *ctx, const wc_points *pts, dou
   ctx->ex.active = true;
   ctx->ex.ticket = 0;  // (only this call's fx_tail may arm the completion ticket - a stale one would let finish skip its wait)
   ctx->ex.pts = *pts;
-  ctx->ex.d_out = d_out;
-  ctx->ex.d_ids = d_ids;
-  ctx->ex.cap = cap;
-  ctx->ex.wide = false;
+  ctx->ex.d_out = d_out, ctx->ex.d_ids = d_ids, ctx->ex.cap = cap;
+  ctx->ex.path = ExPath{}, ctx->ex.runs = 0;
   for (int q = 0; q < 16; ++q) ctx->h_status[q] = 0;
   if (pts->n == 0) return WC_OK;
   if (t_lo > t_hi) {  // no hint: read the first and last timestamp back (input is time ordered)
@@ -2316,143 +2292,62 @@ extern "C" int wc_extract_surfels_enqueue(wc_ctx *ctx, const wc_points *pts, dou
     t_lo -= m;
     t_hi += m;
   }
-  ctx->ex.t_lo = t_lo;
-  ctx->ex.t_hi = t_hi;
-  // after a bin overflow of the run-binned point sort (very many points in few voxels, or points in no spatial order)
-  // the next calls go to the radix-sort path directly; the fast path is tried again every 16th call
-  ctx->ex.general = ctx->ex.general_calls > 0 || ctx->dev.no_bucket_sort != 0;
-  if (ctx->ex.general_calls > 0) --ctx->ex.general_calls;
-  ctx->ex.order_general = false;
-  ctx->ex.fx_active = fx_applicable(ctx, pts->n, t_lo, t_hi);
-  if (ctx->ex.fx_active && ctx->ex.fx_skip_calls > 0) {  // recent sweeps had to be repeated on the exact path: go there directly for a while
-    --ctx->ex.fx_skip_calls;
-    ctx->ex.fx_active = false;
-  }
-  if (ctx->ex.fx_active) {
-    const int rc = run_pipeline_fast(ctx, *pts, t_lo, t_hi, d_out, d_ids, cap);
-    if (rc != WC_OK) ctx->ex.fx_dirty = true;
-    return rc;
-  }
-  return run_pipeline<uint32_t>(ctx, *pts, t_lo, t_hi, d_out, d_ids, cap, !ctx->ex.general, true);
+  ctx->ex.t_lo = t_lo, ctx->ex.t_hi = t_hi;
+  // which pipeline the sweep starts on (extract_plan.h): the default path unless the parameters or recent fall-backs say otherwise;
+  // on the exact path, the radix point sort for 15 sweeps after a bin overflow of the run-binned one
+  return enqueue_path(ctx, ex_first_path(ctx->ex_mem, fx_applicable(ctx, pts->n, t_lo, t_hi), ctx->dev.no_bucket_sort != 0));
 }
 
 extern "C" int wc_extract_surfels_finish(wc_ctx *ctx, uint64_t *h_n_out) {
   wc_dev_guard dg_(ctx);
   if (!ctx || !ctx->ex.active) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
-  ctx->ex.active = false;
+  ExSweep &S = ctx->ex;
+  ExMemory &M = ctx->ex_mem;
+  S.active = false;
   if (h_n_out) *h_n_out = 0;
-  if (ctx->ex.pts.n == 0) return WC_OK;
-  // (Round 3, tried: a completion ticket stored to the pinned mailbox by k_slot_emit's last workgroup, so that this wait reads host
-  // memory instead of waiting for the stream - as the LM loop does with k_post_reduce's single workgroup.  "Last of 1 024
-  // workgroups" needs a count with a device-scope release in front of every workgroup's increment, and on this chip - one L2 per
-  // XCD - that fence writes the XCD's L2 back: 43 -> 70 us per sweep with a two-stage count, 130 us with one counter.  Without the
-  // fences a copy on another stream could read the surfels before they have left L2.  The stream wait stays.)
-  auto wait = [&]() -> int {  // sweep done (its ticket has arrived, or the stream is idle); fold the mailbox flag words (raise_flag) into h_status[1]
-    bool arrived = false;
-    if (const uint32_t ticket = ctx->ex.ticket) {  // (fx_tail: the ticket kernel was the last thing enqueued)
-      ctx->ex.ticket = 0;
-      const uint32_t *w = (const uint32_t *)ctx->h_status + kMailTicket;
-      const auto t0 = std::chrono::steady_clock::now();
-      for (uint32_t spin = 0; !arrived; ++spin) {
-        arrived = __atomic_load_n(w, __ATOMIC_ACQUIRE) == ticket;
-        if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) break;
-      }
-    }
-    if (!arrived) WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 7; ++i)
-      if (ctx->h_status[8 + i]) ctx->h_status[1] |= 1u << i;
-    return WC_OK;
-  };
-  WC_TRY(wait());
-  if (ctx->ex.fx_active) {
+  if (S.pts.n == 0) return WC_OK;
+  // The wait reads the completion ticket that k_ex_ticket, one thread behind the sweep's last kernel, stores to the pinned
+  // mailbox (fx_tail); without a ticket it waits for the stream.  (Round 3, tried: the ticket stored by k_slot_emit's last
+  // workgroup.  "Last of 1 024 workgroups" needs a count with a device-scope release in front of every workgroup's increment, and
+  // on this chip - one L2 per XCD - that fence writes the XCD's L2 back: 43 -> 70 us per sweep with a two-stage count, 130 us with
+  // one counter.  Without the fences a copy on another stream could read the surfels before they have left L2.)
+  WC_TRY(ex_wait(ctx));
+  if (S.path.fx) {
     // layer-2 nodes were queued but the pair of launches was skipped (the previous sweep had none): run it now
-    if (!ctx->ex.layer2_done && ctx->P.max_layer >= 2 && ctx->h_status[4] > 0 && !(ctx->h_status[1] & (kFlagFxFallback | kFlagKeyRange))) {
-      ctx->ex.last_splits = ctx->h_status[4];
+    if (!S.layer2_done && ctx->P.max_layer >= 2 && ctx->h_status[4] > 0 && !(ctx->h_status[1] & (kFlagFxFallback | kFlagKeyRange))) {
+      M.last_splits = ctx->h_status[4];
       WC_TRY(fx_tail(ctx, true));
-      WC_TRY(wait());
+      WC_TRY(ex_wait(ctx));
     }
-    const uint32_t fl = ctx->h_status[1];
-    ctx->ex.fx_last_flags = fl;
-    ctx->ex.last_splits = ctx->h_status[4];
-    if (fl & (kFlagFxFallback | kFlagKeyRange | kFlagSlotBinOverflow | kFlagTimeRange)) {
-      // a decision too close to its threshold, a table at capacity, a node spanning > 16 time bins, ...: the tables are put
-      // back to zero and the sweep is repeated on the exact path (below)
-      ++ctx->ex.fx_fallbacks;
-      ctx->ex.fx_last_why = 0;
-      for (int i = 0; i < 24; ++i)
-        if (ctx->h_status[32 + i]) ctx->ex.fx_last_why |= 1u << i;
-      if (ctx->ex.fx_last_why & (1u << 4)) ctx->ex.fx_spill_full = true;  // the spill pool overflowed: full size from now on
-      // exponential back-off: a sweep the default path cannot finish (a node spanning more than 16 time bins, more roots than
-      // blocks, ...) is usually followed by more of its kind; a gate that merely fell inside the noise band is not
-      ctx->ex.fx_backoff = std::min(32u, std::max(1u, ctx->ex.fx_backoff * 2u));
-      ctx->ex.fx_skip_calls = ctx->ex.fx_backoff - 1u;
-      ctx->ex.fx_dirty = true;        // tables (a root at capacity, roots waiting for a layer-2 pass that never ran) ...
-      ctx->ex.fx_ctrl_ready = false;  // ... and control blocks are set up anew by the next fast sweep
-      ctx->ex.fx_active = false;
-      ctx->ex.general = ctx->ex.general_calls > 0;
-      WC_TRY(run_pipeline<uint32_t>(ctx, ctx->ex.pts, ctx->ex.t_lo, ctx->ex.t_hi, ctx->ex.d_out, ctx->ex.d_ids, ctx->ex.cap, !ctx->ex.general, true));
-      WC_TRY(wait());
-    } else {
-      const uint32_t n_fast = ctx->h_status[0];
-      ctx->ex.fx_long_lists = ctx->h_status[15] != 0u;  // lists of several records per (node, time slot): merged first next time
-      ctx->ex.fx_long_lists2 = ctx->h_status[16] != 0u;  // ... among the layer-2 nodes' lists
-      if (h_n_out) *h_n_out = n_fast;
-      ctx->ex.fx_parity ^= 1;  // the other control block has been cleared by this sweep's k_slot_emit
-      ctx->ex.fx_backoff = 0;
-      if (n_fast > ctx->ex.cap)
-        return wc_fail(ctx, WC_ERR_CAPACITY, "output capacity %llu < %u surfels", (unsigned long long)ctx->ex.cap, n_fast);
-      return WC_OK;
+    M.last_splits = ctx->h_status[4];
+  }
+  // the ladder (extract_plan.h): every repeat is judged by its own flags
+  ExPath path = S.path;
+  while (ex_next_path(path, ctx->h_status[1], ctx->h_status + 32, M)) {
+    WC_TRY(enqueue_path(ctx, path));
+    WC_TRY(ex_wait(ctx));
+  }
+  if (path.fx) {  // completed by the default path (none of the error flags below: they would have sent it to the exact path)
+    M.fx_long_lists = ctx->h_status[15] != 0u;  // lists of several records per (node, time slot): merged first next time
+    M.fx_long_lists2 = ctx->h_status[16] != 0u;  // ... among the layer-2 nodes' lists
+    M.fx_parity ^= 1;  // the other control block has been cleared by this sweep's k_slot_emit
+  } else {
+    if (!S.layer2_done && ctx->h_status[4] > 0 && S.tail) {  // roots were queued for the skipped layer-2 pass
+      M.last_splits = ctx->h_status[4];
+      WC_TRY(S.tail(ctx, true));
+      WC_TRY(ex_wait(ctx));
     }
+    M.last_splits = ctx->h_status[4];
+    ex_learn_unordered(M, path, ctx->h_status[5], S.pts.n);
+    // the control block of the NEXT call is cleared now, asynchronously: it runs while the host turns around
+    if (clear_ctrl(ctx) == WC_OK) M.precleared = true;
   }
-  // a bucket had more runs than the LDS capacity of k_pt_bucket (but fits its bin): repeat one capacity up (sticky)
-  while ((ctx->h_status[1] & kFlagLdsOverflow) && !(ctx->h_status[1] & (kFlagBucketOverflow | kFlagKeyRange)) && !ctx->ex.general &&
-         ctx->ex.lds_cap < kPtBinMax) {
-    ctx->ex.lds_cap *= 2;
-    WC_TRY(run_pipeline<uint32_t>(ctx, ctx->ex.pts, ctx->ex.t_lo, ctx->ex.t_hi, ctx->ex.d_out, ctx->ex.d_ids, ctx->ex.cap, true, true));
-    WC_TRY(wait());
-  }
-  if ((ctx->h_status[1] & kFlagLdsOverflow) && !ctx->ex.general) ctx->h_status[1] |= kFlagBucketOverflow;  // still too large
-  if ((ctx->h_status[1] & kFlagBucketOverflow) && !(ctx->h_status[1] & kFlagKeyRange) && !ctx->ex.general) {
-    // a bin of the run-binned point sort overflowed: redo with the general radix sort
-    ctx->ex.general = true;
-    ctx->ex.general_calls = 15;
-    WC_TRY(run_pipeline<uint32_t>(ctx, ctx->ex.pts, ctx->ex.t_lo, ctx->ex.t_hi, ctx->ex.d_out, ctx->ex.d_ids, ctx->ex.cap, false, true));
-    WC_TRY(wait());
-  }
-  if ((ctx->h_status[1] & kFlagKeyRange) && !ctx->ex.wide) {
-    // the sweep spans more than +-512 root voxels around its first point: redo with 21-bit-per-axis keys
-    ctx->ex.wide = true;
-    WC_TRY(run_pipeline<uint64_t>(ctx, ctx->ex.pts, ctx->ex.t_lo, ctx->ex.t_hi, ctx->ex.d_out, ctx->ex.d_ids, ctx->ex.cap, false, true));
-    WC_TRY(wait());
-  }
-  if ((ctx->h_status[1] & kFlagSlotBinOverflow) && !ctx->ex.order_general) {
-    // very many surfels inside one 1/4096 of the sweep's time span: redo with the radix sort of the slot keys
-    ctx->ex.order_general = true;
-    if (ctx->ex.wide)
-      WC_TRY(run_pipeline<uint64_t>(ctx, ctx->ex.pts, ctx->ex.t_lo, ctx->ex.t_hi, ctx->ex.d_out, ctx->ex.d_ids, ctx->ex.cap, false, false));
-    else
-      WC_TRY(run_pipeline<uint32_t>(ctx, ctx->ex.pts, ctx->ex.t_lo, ctx->ex.t_hi, ctx->ex.d_out, ctx->ex.d_ids, ctx->ex.cap, !ctx->ex.general, false));
-    WC_TRY(wait());
-  }
-  if (!ctx->ex.layer2_done && ctx->h_status[4] > 0 && ctx->ex.tail) {  // roots were queued for the skipped layer-2 pass
-    ctx->ex.last_splits = ctx->h_status[4];
-    WC_TRY(ctx->ex.tail(ctx, true));
-    WC_TRY(wait());
-  }
-  const uint32_t flags = ctx->h_status[1];
-  const uint32_t n_out = ctx->h_status[0];
-  ctx->ex.last_splits = ctx->h_status[4];
-  // run statistics of the run-binned sort: fewer than four points per run on average = no run structure (a spinning
-  // multi-beam sensor in firing order): the next sweep streams with k_roots_banks right away
-  if (!ctx->ex.general && !ctx->ex.wide && ctx->h_status[5] > 0) ctx->ex.unordered = (uint64_t)ctx->h_status[5] * 4 > ctx->ex.pts.n;
+  const uint32_t flags = ctx->h_status[1], n_out = ctx->h_status[0];
   if (h_n_out) *h_n_out = n_out;
-  // the control block of the NEXT call is cleared now, asynchronously: it runs while the host turns around
-  if (clear_ctrl(ctx) == WC_OK) ctx->ex.precleared = true;
   if (flags & kFlagKeyRange) return wc_fail(ctx, WC_ERR_ARG, "point cloud extent exceeds 2^20 root voxels");
   if (flags & kFlagSlotOverflow) return wc_fail(ctx, WC_ERR_HIP, "internal: candidate slot overflow");
   if (flags & kFlagTimeRange) return wc_fail(ctx, WC_ERR_ARG, "surfel timestamp outside the [t_lo, t_hi] hint");
-  if (n_out > ctx->ex.cap) return wc_fail(ctx, WC_ERR_CAPACITY, "output capacity %llu < %u surfels",
-                                          (unsigned long long)ctx->ex.cap, n_out);
+  if (n_out > S.cap) return wc_fail(ctx, WC_ERR_CAPACITY, "output capacity %llu < %u surfels", (unsigned long long)S.cap, n_out);
   return WC_OK;
 }
 
@@ -2478,9 +2373,14 @@ extern "C" int wc_extract_surfels_batch_enqueue(wc_ctx *ctx, const wc_sweep_job 
     ctx->batch_subs.push_back(sub);
   }
   hipStream_t st = ctx->stream;
-  std::vector<FxArgs> args;
-  std::vector<SlotEmitArgs> emit;
-  std::vector<uint32_t> s_acc(1, 0u), s_nodes(1, 0u), s_g2(1, 0u), flags;
+  // one upload, filled for the Kd <= K sweeps the default path takes: {FxArgs[K] | SlotEmitArgs[K] | three prefix tables of K + 1 | flags[K]}
+  const size_t o_emit = (sizeof(FxArgs) * K + 15) & ~(size_t)15, o_tab = (o_emit + sizeof(SlotEmitArgs) * K + 15) & ~(size_t)15;
+  const size_t bytes = o_tab + (size_t)(3 * (K + 1) + K) * 4;
+  std::vector<unsigned char> host(bytes, 0);
+  FxArgs *args = (FxArgs *)host.data();
+  SlotEmitArgs *emit = (SlotEmitArgs *)(host.data() + o_emit);
+  uint32_t *s_acc = (uint32_t *)(host.data() + o_tab), *s_nodes = s_acc + (K + 1), *s_g2 = s_nodes + (K + 1), *flags = s_g2 + (K + 1);
+  int Kd = 0;
   bool any_l2 = false, any_merge = false;
   for (int k = 0; k < K; ++k) {
     wc_ctx *sub = ctx->batch_subs[k];
@@ -2488,7 +2388,7 @@ extern "C" int wc_extract_surfels_batch_enqueue(wc_ctx *ctx, const wc_sweep_job 
     if (std::memcmp(&sub->P, &ctx->P, sizeof(wc_params)) != 0) WC_TRY(wc_ctx_set_params(sub, &ctx->P));
     if (std::memcmp(&sub->dev, &ctx->dev, sizeof(wc_dev_opts)) != 0) {  // (the parent's development options reach the sweeps)
       sub->dev = ctx->dev;
-      sub->ex.fx_backoff = sub->ex.fx_skip_calls = 0;
+      ex_reset_backoff(sub->ex_mem);
     }
     sub->ex.batch_defer = true;
     sub->ex.deferred = false;
@@ -2499,59 +2399,46 @@ extern "C" int wc_extract_surfels_batch_enqueue(wc_ctx *ctx, const wc_sweep_job 
       // tables are cleared before the next use and a later finish() has nothing to wait for
       for (int j = 0; j <= k; ++j) {
         wc_ctx *pj = ctx->batch_subs[j];
-        if (pj->ex.deferred || j == k) pj->ex.fx_dirty = true, pj->ex.active = false, pj->ex.deferred = false;
+        if (pj->ex.deferred || j == k) pj->ex_mem.fx_dirty = true, pj->ex.active = false, pj->ex.deferred = false;
       }
       return wc_fail(ctx, rc, "wc_extract_surfels_batch (sweep %d): %s", k, wc_last_error(sub));
     }
     if (!sub->ex.deferred) continue;  // (empty, or a sweep the default path does not take: enqueued on its own, on the same stream)
-    FxArgs A;
+    FxArgs &A = args[Kd];
     std::memcpy(&A, sub->ex.roots_args, sizeof(A));
-    args.push_back(A);
-    const uint32_t g2 = std::min(std::min(256u * 8u, sub->ex.fx_ngrid), std::max(64u, sub->ex.last_splits));
-    s_acc.push_back(s_acc.back() + sub->ex.fx_tiles);
-    s_nodes.push_back(s_nodes.back() + sub->ex.fx_ngrid);
-    s_g2.push_back(s_g2.back() + g2);
-    const uint32_t f = (sub->ex.layer2_done ? 1u : 0u) | ((sub->ex.fx_long_lists || sub->ex.fx_long_lists2) ? 2u : 0u);  // (a batch merges both levels or none)
-    flags.push_back(f);
+    const unsigned ngrid = ex_fx_batch_node_grid(A.pts.n);
+    s_acc[Kd + 1] = s_acc[Kd] + ex_fx_tiles(A.pts.n);
+    s_nodes[Kd + 1] = s_nodes[Kd] + ngrid;
+    s_g2[Kd + 1] = s_g2[Kd] + ex_fx_layer2_grid(ngrid, sub->ex_mem.last_splits);
+    const uint32_t f = (sub->ex.layer2_done ? 1u : 0u) | ((sub->ex_mem.fx_long_lists || sub->ex_mem.fx_long_lists2) ? 2u : 0u);  // (a batch merges both levels or none)
+    flags[Kd] = f;
     any_l2 = any_l2 || (f & 1u);
     any_merge = any_merge || (f & 2u);
-    uint32_t *next_ctrl = (uint32_t *)sub->b_fx[5].p + (size_t)(sub->ex.fx_parity ^ 1) * kCtrlWords;
-    emit.push_back(SlotEmitArgs{A.slot_counts, A.slot_bins, sub->ex.bin_cap, (const wc_surfel *)sub->b_slots.p, (const wc_surfel_id *)sub->b_slot_ids.p,
-                                A.status, sub->ex.d_out, sub->ex.d_ids, sub->ex.cap, next_ctrl, (uint32_t)kCtrlWords});
+    uint32_t *next_ctrl = (uint32_t *)sub->b_fx[5].p + (size_t)(sub->ex_mem.fx_parity ^ 1) * kCtrlWords;
+    emit[Kd++] = SlotEmitArgs{A.slot_counts, A.slot_bins, A.slot_bin_cap, (const wc_surfel *)sub->b_slots.p, (const wc_surfel_id *)sub->b_slot_ids.p,
+                              A.status, sub->ex.d_out, sub->ex.d_ids, sub->ex.cap, next_ctrl, (uint32_t)kCtrlWords};
   }
-  const int Kd = (int)args.size();
   if (Kd == 0) return WC_OK;
-  // one upload: {FxArgs[Kd] | SlotEmitArgs[Kd] | three prefix tables | flags}
-  const size_t o_emit = (sizeof(FxArgs) * Kd + 15) & ~(size_t)15, o_tab = (o_emit + sizeof(SlotEmitArgs) * Kd + 15) & ~(size_t)15;
-  const size_t bytes = o_tab + (size_t)(3 * (Kd + 1) + Kd) * 4;
-  std::vector<unsigned char> host(bytes, 0);
-  std::memcpy(host.data(), args.data(), sizeof(FxArgs) * Kd);
-  std::memcpy(host.data() + o_emit, emit.data(), sizeof(SlotEmitArgs) * Kd);
-  uint32_t *tab = (uint32_t *)(host.data() + o_tab);
-  std::memcpy(tab, s_acc.data(), (Kd + 1) * 4);
-  std::memcpy(tab + (Kd + 1), s_nodes.data(), (Kd + 1) * 4);
-  std::memcpy(tab + 2 * (Kd + 1), s_g2.data(), (Kd + 1) * 4);
-  std::memcpy(tab + 3 * (Kd + 1), flags.data(), Kd * 4);
   WC_TRY(wc_ensure(ctx, ctx->b_batch, bytes));
   WC_HIP(ctx, hipMemcpyAsync(ctx->b_batch.p, host.data(), bytes, hipMemcpyHostToDevice, st));
   WC_HIP(ctx, hipStreamSynchronize(st));  // (pageable staging: `host` dies with this scope; ~10 us once per K sweeps)
   const unsigned char *d = (const unsigned char *)ctx->b_batch.p;
   const uint32_t *dt = (const uint32_t *)(d + o_tab);
   FxBatch B;
-  B.args = (const FxArgs *)d, B.K = Kd, B.flags = dt + 3 * (Kd + 1);
+  B.args = (const FxArgs *)d, B.K = Kd, B.flags = dt + 3 * (K + 1);
   B.start = dt;
-  k_fx_acc_b<1><<<s_acc.back(), kFxThreads, 0, st>>>(B);
-  B.start = dt + (Kd + 1);
-  if (any_merge) k_fx_merge_b<1><<<s_nodes.back(), 128, 0, st>>>(B);
-  k_fx_walk_b<1><<<s_nodes.back(), 64, 0, st>>>(B);
-  k_fx_test_b<1><<<s_nodes.back(), 64, 0, st>>>(B);
+  k_fx_acc_b<1><<<s_acc[Kd], kFxThreads, 0, st>>>(B);
+  B.start = dt + (K + 1);
+  if (any_merge) k_fx_merge_b<1><<<s_nodes[Kd], 128, 0, st>>>(B);
+  k_fx_walk_b<1><<<s_nodes[Kd], 64, 0, st>>>(B);
+  k_fx_test_b<1><<<s_nodes[Kd], 64, 0, st>>>(B);
   if (any_l2) {
     B.start = dt;
-    k_fx_acc_b<2><<<s_acc.back(), kFxThreads, 0, st>>>(B);
-    B.start = dt + 2 * (Kd + 1);
-    if (any_merge) k_fx_merge_b<2><<<s_g2.back(), 128, 0, st>>>(B);
-    k_fx_walk_b<2><<<s_g2.back(), 64, 0, st>>>(B);
-    k_fx_test_b<2><<<s_g2.back(), 64, 0, st>>>(B);
+    k_fx_acc_b<2><<<s_acc[Kd], kFxThreads, 0, st>>>(B);
+    B.start = dt + 2 * (K + 1);
+    if (any_merge) k_fx_merge_b<2><<<s_g2[Kd], 128, 0, st>>>(B);
+    k_fx_walk_b<2><<<s_g2[Kd], 64, 0, st>>>(B);
+    k_fx_test_b<2><<<s_g2[Kd], 64, 0, st>>>(B);
   }
   k_slot_emit_b<<<(unsigned)Kd * (kBuckets / 4), 256, 0, st>>>((const SlotEmitArgs *)(d + o_emit), Kd);
   WC_HIP(ctx, hipGetLastError());
@@ -2602,11 +2489,14 @@ extern "C" int wc_debug_status(wc_ctx *ctx, uint32_t *h_out64) {
   if (!ctx || !h_out64) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
   // (the device copy has been cleared for the next call already: words 0..15 come from the host mailbox of the last call)
   for (int i = 0; i < 64; ++i) h_out64[i] = i < 16 ? ctx->h_status[i] : 0u;
-  h_out64[59] = ctx->ex.fx_long_lists ? 1u : 0u;  // the next fast sweep runs k_fx_merge (the last one had long record lists)
-  h_out64[60] = ctx->ex.fx_fallbacks;  // sweeps the fast path handed to the exact path so far
-  h_out64[61] = ctx->ex.fx_active ? 1u : 0u;  // the last sweep was completed by the fast (integer-moment) path
-  h_out64[62] = ctx->ex.fx_last_flags;
-  h_out64[63] = ctx->ex.fx_last_why;  // bit i: call site i of fx_fallback() fired in the last sweep that fell back
+  h_out64[56] = ctx->ex.runs;  // pipelines the last sweep enqueued (1: no repeat)
+  h_out64[57] = ex_path_bits(ctx->ex.path);  // ... and the path of the run that completed it (ExPath: fx 1, wide 2, run_sort 4, bin_order 8)
+  h_out64[58] = ctx->ex_mem.lds_cap;
+  h_out64[59] = ctx->ex_mem.fx_long_lists ? 1u : 0u;  // the next fast sweep runs k_fx_merge (the last one had long record lists)
+  h_out64[60] = ctx->ex_mem.fx_fallbacks;  // sweeps the fast path handed to the exact path so far
+  h_out64[61] = ctx->ex.path.fx ? 1u : 0u;  // the last sweep was completed by the fast (integer-moment) path
+  h_out64[62] = ctx->ex_mem.fx_last_flags;
+  h_out64[63] = ctx->ex_mem.fx_last_why;  // bit i: call site i of fx_fallback() fired in the last sweep that fell back
 #ifdef WC_PROF_ROOTS
   // average the per-root section timers into words [16, 24), number of timed roots in word 24
   const size_t nslots = ctx->ex.pts.n / (size_t)(ctx->P.min_points + 1) + 1;

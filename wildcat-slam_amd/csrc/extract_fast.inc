@@ -34,10 +34,7 @@
 // k_slot_emit clears the control block of the next sweep (two blocks, used alternately), so a sweep pays neither a bulk memset
 // nor a clean-up launch.
 
-constexpr uint32_t kFlagFxFallback = 64u;
-constexpr int kFxPts = 4;          // consecutive points per lane
-constexpr int kFxThreads = 256;
-constexpr int kFxTile = kFxPts * kFxThreads;
+// (kFxPts consecutive points per lane, kFxThreads, kFxTile, kFxSub sub-counters: extract_plan.h)
 constexpr int kFxLds = 256;        // cells of the per-tile LDS hash
 constexpr int kFxLdsProbe = 12;
 constexpr int kFxDirect = 16;     // records a wavefront may write straight to HBM per flush class (3 in-lane boundaries + run tails)
@@ -46,7 +43,6 @@ constexpr int kFxSlots = 16;       // time slots per node: bin & 15
 constexpr int kFxRecW = 16;        // u64 words per record (128 B): n | bin << 32, St, Sq[3], Sqq[6], tmin_inv, tmax_p1, next, 2 spare
 constexpr int kFxHdrW = 16;        // u64 words of a block header
 constexpr int kFxBlockW = kFxHdrW + 8 * kFxSlots / 2;  // + 128 list heads (u32): 80 words = 640 B per root / per queued node
-constexpr int kFxSub = 16;         // sub-counters (a single counter serialises at ~12 ns per atomic)
 // Counter banks (roots created, layer-2 nodes queued, surfel slots taken, spill records): 16 sub-counters each, every one on
 // its own 128-byte line - atomics on different words of ONE line serialise like atomics on one word (~11 ns each).
 constexpr uint32_t kFxStRoots = 0, kFxStNodes2 = 1, kFxStSlots = 2, kFxStSpillBank = 3;

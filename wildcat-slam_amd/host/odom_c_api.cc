@@ -4,6 +4,7 @@
 
 #include <algorithm>
 
+#include "../csrc/extract_plan.h"
 #include "cubic_bspline.h"
 #include "histogram.h"
 #include "imu_resampler.h"
@@ -259,6 +260,45 @@ int wc_odom_import_state(void *h, const double *samples23, uint64_t ns, const wc
 
 // ---- known-answer hooks for the host-side product code (the g++ instantiation of csrc/dmath.h, the facade's spline, the
 // resampler): the reference's own unit tests are run against these in tests/test_host_kat.py -------------------------------
+
+// csrc/extract_plan.h - which pipeline an extraction starts on and repeats on - driven step by step (tests/test_extract_plan_cpu.py).
+// mem11 = ExMemory's general_calls, lds_cap, unordered, fx_backoff, fx_skip_calls, fx_spill_full, fx_fallbacks, fx_last_flags,
+// fx_last_why, fx_dirty, fx_ctrl_ready; *path_bits = ex_path_bits.  op 0: ex_first_path(fx_ok = a, no_bucket_sort = b);
+// op 1: ex_next_path(flags = a, reason words set = bits of b) -> its return value; op 2: ex_learn_unordered(run count = a, n = b);
+// op 3: ex_reset_backoff
+int wc_host_ex_plan(int op, uint32_t mem11[11], uint32_t *path_bits, uint32_t a, uint64_t b) {
+  ExMemory m;
+  m.general_calls = (int)mem11[0], m.lds_cap = mem11[1], m.unordered = mem11[2] != 0, m.fx_backoff = mem11[3], m.fx_skip_calls = mem11[4];
+  m.fx_spill_full = mem11[5] != 0, m.fx_fallbacks = mem11[6], m.fx_last_flags = mem11[7], m.fx_last_why = mem11[8];
+  m.fx_dirty = mem11[9] != 0, m.fx_ctrl_ready = mem11[10] != 0;
+  ExPath p;
+  p.fx = *path_bits & 1u, p.wide = *path_bits & 2u, p.run_sort = *path_bits & 4u, p.bin_order = *path_bits & 8u;
+  int rc = 0;
+  if (op == 0) {
+    p = ex_first_path(m, a != 0, b != 0);
+  } else if (op == 1) {
+    uint32_t why[24];
+    for (int i = 0; i < 24; ++i) why[i] = (uint32_t)((b >> i) & 1u);
+    rc = ex_next_path(p, a, why, m) ? 1 : 0;
+  } else if (op == 2) {
+    ex_learn_unordered(m, p, a, b);
+  } else {
+    ex_reset_backoff(m);
+  }
+  const uint32_t out[11] = {(uint32_t)m.general_calls, m.lds_cap, m.unordered, m.fx_backoff, m.fx_skip_calls, m.fx_spill_full,
+                            m.fx_fallbacks, m.fx_last_flags, m.fx_last_why, m.fx_dirty, m.fx_ctrl_ready};
+  std::memcpy(mem11, out, sizeof(out));
+  *path_bits = ex_path_bits(p);
+  return rc;
+}
+// ... and its sizes: out5 = total slots, slot bin capacity, default-path tiles, node grid, layer-2 grid
+void wc_host_ex_sizes(uint64_t n, int max_layer, int cluster_min, uint64_t floor, uint32_t last_splits, uint64_t out5[5]) {
+  out5[0] = ex_total_slots(n, max_layer, cluster_min, floor);
+  out5[1] = ex_slot_bin_cap(out5[0]);
+  out5[2] = ex_fx_tiles(n);
+  out5[3] = ex_fx_node_grid(n);
+  out5[4] = ex_fx_layer2_grid((unsigned)out5[3], last_splits);
+}
 
 // utils_test.cc:5-21 inputs -> out52 = Exp(v) | Log(Exp(v)) | Jl | Jl_inv | Jr | Jr_inv | Hat (layout of wc_selftest_so3)
 void wc_host_so3(const double v3[3], double out52[52]) {

@@ -267,10 +267,13 @@ class Context:
 
     def extract_path_info(self):
         """-> dict(fast=the last sweep was completed by the fast path, fallbacks=sweeps handed to the exact path so far, flags,
-        long_lists=the last fast sweep had long record lists: the next one merges them first (k_fx_merge))"""
+        long_lists=the last fast sweep had long record lists: the next one merges them first (k_fx_merge),
+        runs=pipelines the last sweep enqueued (1: no repeat), path=bits of the pipeline that completed it (1 default path, 2 wide
+        keys, 4 run-binned point sort, 8 time-bin surfel order), lds_cap=runs per bucket the run-binned sort takes in LDS)"""
         w = (C.c_uint32 * 64)()
         self._ck(self.lib.wc_debug_status(self.h, w))
-        return dict(fast=bool(w[61]), fallbacks=int(w[60]), flags=int(w[62]), why=int(w[63]), long_lists=bool(w[59]))
+        return dict(fast=bool(w[61]), fallbacks=int(w[60]), flags=int(w[62]), why=int(w[63]), long_lists=bool(w[59]),
+                    runs=int(w[56]), path=int(w[57]), lds_cap=int(w[58]))
 
     def extract_profile(self, enable=True):
         """True / 1: HIP events after every kernel group of the stage (each event costs ~5 us of stream time); 2: only the first
