@@ -48,10 +48,12 @@ def dot2_residual(A, y, b):
     return p + s
 
 
-def damped_system(H, g, radius):
-    """(A, gs, scale) of the damped, Jacobi-scaled system one LM step solves"""
+def damped_system(H, g, radius, scale=None):
+    """(A, gs, scale) of the damped, Jacobi-scaled system one LM step solves; scale: that of the solve's FIRST linearisation, which
+    Ceres keeps for every later one (None: H is the first)"""
     H = np.asarray(H, np.float64)
-    scale = 1.0 / (1.0 + np.sqrt(np.diag(H)))
+    if scale is None:
+        scale = 1.0 / (1.0 + np.sqrt(np.diag(H)))
     A = H * scale[:, None] * scale[None, :]
     gs = np.asarray(g, np.float64) * scale
     D = np.clip(np.diag(A), 1e-6, 1e32)
