@@ -111,6 +111,14 @@ typedef struct wc_map_surfel {
   double normal[3]; /* unit eigenvector of ev[0]; its component of largest magnitude (lowest axis on a tie) > 0 */
 } wc_map_surfel;
 
+/* One voxel of the map's exact state (wildcat_hip.h: wc_map_export_state, wc_map_absorb; not a reference type).  40 bytes, 8-aligned;
+ * the first 16 bytes are laid out as wc_map_surfel's.  The nine moment words of a WC_MAP_MOMENTS map travel in an array of their own. */
+typedef struct wc_map_voxel {
+  int32_t key[3];  /* the voxel index                                                                                       */
+  uint32_t count;  /* its point count                                                                                       */
+  int64_t sum[3];  /* the table's integer sums per axis: sum of round((p - r) * 2^32), r = the voxel's reference point      */
+} wc_map_voxel;
+
 /* Answer of wc_map_nearest_plane for one query (not a reference type).  80 bytes, 8-aligned. */
 typedef struct wc_map_plane_hit {
   wc_map_hit hit;   /* what wc_map_nearest writes for the query; hit.flags bit 1 is added: "the plane below is valid"          */

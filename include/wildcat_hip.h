@@ -74,6 +74,8 @@ int wc_ctx_set_params(wc_ctx *ctx, const wc_params *params);
  *                      whatever the value
  *   map_cast_groups (0) wc_map_raycast: workgroups of its kernel (0: chosen from the point count); every output byte is the same
  *                      whatever the value
+ *   map_absorb_groups (0) wc_map_absorb: workgroups of its kernel (0: chosen from the record count); the map is the same whatever the
+ *                      value
  *   lm_radius0         initial trust-region radius of wc_window_solve: 10^value (default -1 = the library's 1e4); tests use it to
  *                      look at the first step at other damping levels
  * Tests use it to run both forms of a choice on the same data.  Unknown names return WC_ERR_ARG. */
@@ -484,6 +486,37 @@ int wc_map_raycast(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double or
  * wc_map_export_surfels writes one wc_map_surfel per occupied voxel, in the order and number of wc_map_export, under its capacity and
  * error rules (WC_ERR_CAPACITY with *h_n = the needed count; d_out 8-aligned).  A map without moments: WC_ERR_ARG. */
 int wc_map_export_surfels(wc_ctx *ctx, wc_map *m, wc_map_surfel *d_out, uint64_t cap, uint64_t *h_n);
+/* the exact state: export, absorb, merge --------------------------------------------------------------------------------------- */
+/* wc_map_export and wc_map_export_surfels round the table's sums; the state is the sums themselves.  A voxel k of a map of voxel size v
+ * holds count, sum[a] = the sum over its points of q_a = round((p_a - r_a) * 2^32) with r_a = rint((k_a + 0.5) * v * 1024) / 1024 (a
+ * function of k_a and v alone), and in a WC_MAP_MOMENTS map nine more words, in this order: U_x, U_y, U_z (sums of u = (q + 2^15) >> 16),
+ * M_xx, M_xy, M_xz, M_yy, M_yz, M_zz (sums of u_a u_b).  All of them are integers, so a state that is exported and absorbed again gives
+ * the map back bit for bit, and the states of two maps of one voxel size add up to the map of the points of both.
+ *
+ * wc_map_export_state writes one wc_map_voxel per occupied voxel into d_vox (DEVICE, 8-aligned), in the order and number of
+ * wc_map_export, under its capacity and error rules: WC_ERR_CAPACITY with *h_n = the needed count when cap < n; the size is read back,
+ * the kernels are enqueued on the ctx stream and the call returns.  d_mom (DEVICE, 8-aligned, may be NULL) receives n x 9 int64 moment
+ * words in the order above; NULL: they are not written; non-NULL with a map created without WC_MAP_MOMENTS: WC_ERR_ARG.  A misaligned
+ * pointer is WC_ERR_ARG.  The map is not modified. */
+int wc_map_export_state(wc_ctx *ctx, wc_map *m, wc_map_voxel *d_vox, int64_t *d_mom, uint64_t cap, uint64_t *h_n);
+/* Every one of the n records (DEVICE, 8-aligned) adds its count, its three sums and - in a WC_MAP_MOMENTS map - its nine moment words
+ * (d_mom: n x 9 int64, DEVICE, 8-aligned) to the voxel of its key; the voxel is created where it is new.  The records need not be sorted
+ * and the keys need not be distinct: duplicates add up.
+ *   rejected   a record with |key[a]| >= 2^20 on any axis, count == 0 or count > 2^30 is counted and not applied
+ *   the sums   are taken as they are, neither checked against the count nor against the voxel's extent: a state no insert could have
+ *              produced gives a map no insert could have produced (centroids outside their voxel, negative variances)
+ *   moments    a WC_MAP_MOMENTS map with d_mom == NULL is WC_ERR_ARG; a plain map ignores d_mom, so a moments state loads into a plain map
+ *   n == 0     WC_OK, nothing is launched and no pointer is looked at; n > 2^31 is WC_ERR_ARG
+ * h_n_rejected follows wc_map_insert's convention: NULL returns without waiting, non-NULL waits and receives this call's rejected
+ * records.  The map's cumulative count of rejected POINTS (wc_map_info[2]) is not touched.  The voxel count grows by the new voxels and the
+ * point count by the accepted records' counts.  The table grows as before an insert, the n records counting as n possible new voxels. */
+int wc_map_absorb(wc_ctx *ctx, wc_map *m, const wc_map_voxel *d_vox, const int64_t *d_mom, uint64_t n, uint64_t *h_n_rejected);
+/* dst becomes, bit for bit, the map of the points of both maps; src is not modified.  Table to table on the device: no export, no sort,
+ * no host copy.  WC_ERR_ARG when dst == src, when either map belongs to another context, when the two voxel sizes are not bitwise equal
+ * doubles, or when dst has moments and src has none (a moments src merges into a plain dst, the moments are dropped).  Waits once, to
+ * read src's exact voxel count for dst's growth bound; the merge itself is enqueued on the ctx stream. */
+int wc_map_merge(wc_ctx *ctx, wc_map *dst, wc_map *src);
+
 /* Plane query.  The voxel is chosen as wc_map_nearest chooses it (candidates, distance, ties, max_dist, argument checks), and the first
  * 40 bytes of a wc_map_plane_hit are that call's wc_map_hit, except that bit 1 of flags is set iff a voxel was found, its
  * count >= min_points and its plane bit is set.  Then normal and sigma2 are the voxel's wc_map_surfel.normal and .ev[0], byte for byte, and

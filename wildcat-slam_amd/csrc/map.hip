@@ -36,6 +36,9 @@
 //   k_map_raycast  ray casting: the carve's ray and walk, read-only: one lane per ray, its M + 1 positions eight at a time - keys, hashes and
 //                   tested-flags of a batch, its first-slot key loads issued together, then the chains in ascending order up to the first
 //                   voxel with enough points - and one 48-byte wc_map_ray_hit per ray; no atomics but its four counters': wc_map_raycast
+//   k_map_state    state export: one lane per sorted voxel: the slot's integer sums themselves -> wc_map_voxel (+ nine moment words)
+//   k_map_absorb   state records added back by key (map_slot, then four / thirteen no-return atomic adds): wc_map_absorb
+//   k_map_merge    the same for every occupied slot of another map's table: wc_map_merge
 // Shared pieces: map_voxel_of (the voxel-index rule, host and device), map_find_from (the read-only probe chain), block_count (a
 // workgroup's counters), map_points_ok (a wc_points argument), map_replace_table (new table, rehash, free the old one), map_ray_of /
 // map_ray_begin / map_ray_step (a ray's setup and the step rule of its voxel walk: the carve and the ray cast)
@@ -773,6 +776,108 @@ __global__ void __launch_bounds__(256) k_map_count(const unsigned long long *key
   block_count<256>({nv, np}, {n_vox, n_pts});
 }
 
+// ---- the exact state (wc_map_export_state, wc_map_absorb, wc_map_merge) -------------------------------------------------------------
+constexpr int kStateThreads = 256;
+constexpr unsigned kStateMaxCount = 1u << 30;  // a record's count: 1 .. 2^30 (the plain map's limit per voxel)
+// the four (thirteen) integer sums of one voxel added to slot h: no-return 64-bit atomics (the slot may hold the key already, and two
+// records of a call may carry the same key); integers, so no order matters
+template <bool MOM>
+__device__ __forceinline__ void map_add_sums(long long *pay, long long *mom, unsigned long long h, unsigned long long sx, unsigned long long sy,
+                                             unsigned long long sz, unsigned long long cnt, const long long *src_mom) {
+  unsigned long long *p = (unsigned long long *)pay + 4 * h;
+  atomicAdd(p + 0, sx);
+  atomicAdd(p + 1, sy);
+  atomicAdd(p + 2, sz);
+  atomicAdd(p + 3, cnt);
+  if constexpr (MOM) {
+    unsigned long long *pm = (unsigned long long *)mom + kMapMom * h;
+    unsigned long long w[kMapMom];
+#pragma unroll
+    for (int j = 0; j < kMapMom; ++j) w[j] = (unsigned long long)src_mom[j];  // (the nine loads leave before the first atomic)
+#pragma unroll
+    for (int j = 0; j < kMapMom; ++j) atomicAdd(pm + j, w[j]);
+  }
+}
+
+// state export, step 3: one lane per sorted voxel: the slot's payload as two 16-byte loads, the 40-byte wc_map_voxel as five 8-byte
+// stores (key[0] is the low half of the first word: the host is little-endian, as the device), the nine moment words when asked for
+__global__ void __launch_bounds__(kStateThreads) k_map_state(const unsigned long long *skeys, const uint32_t *sslots, uint64_t n, const long long *pay,
+                                                             const long long *mom, wc_map_voxel *vox, long long *out_mom) {
+  const uint64_t i = (uint64_t)blockIdx.x * kStateThreads + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long key = skeys[i];
+  const uint64_t slot = sslots[i];
+  const longlong2 *p = (const longlong2 *)(pay + 4 * slot);
+  const longlong2 p0 = p[0], p1 = p[1];
+  const unsigned kx = (unsigned)map_unpack(key, 0), ky = (unsigned)map_unpack(key, 1), kz = (unsigned)map_unpack(key, 2);
+  unsigned long long *o = (unsigned long long *)(vox + i);
+  o[0] = (unsigned long long)kx | ((unsigned long long)ky << 32);
+  o[1] = (unsigned long long)kz | ((unsigned long long)(unsigned)p1.y << 32);
+  o[2] = (unsigned long long)p0.x;
+  o[3] = (unsigned long long)p0.y;
+  o[4] = (unsigned long long)p1.x;
+  if (out_mom) {
+#pragma unroll
+    for (int w = 0; w < kMapMom; ++w) out_mom[kMapMom * i + w] = mom[kMapMom * slot + w];
+  }
+}
+
+// absorb: grid-strided, one lane per record (five 8-byte loads); a record with a key out of range or a count outside 1 .. 2^30 is counted
+// and not applied; map_slot finds or creates the voxel (its CAS settles lanes that create the same key), then the sums are added.  No
+// LDS pre-aggregation: an exported state has distinct keys.  MOM: the map holds moments and in_mom is not NULL
+template <bool MOM>
+__global__ void __launch_bounds__(kStateThreads) k_map_absorb(const wc_map_voxel *vox, const long long *in_mom, uint64_t n, unsigned long long *keys,
+                                                              long long *pay, long long *mom, unsigned long long mask, unsigned long long *ctr) {
+  unsigned fresh = 0;
+  unsigned long long n_pts = 0, n_rej = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * kStateThreads;
+  for (uint64_t i = (uint64_t)blockIdx.x * kStateThreads + threadIdx.x; i < n; i += stride) {
+    const unsigned long long *r = (const unsigned long long *)(vox + i);
+    const unsigned long long w0 = r[0], w1 = r[1], sx = r[2], sy = r[3], sz = r[4];
+    const int kx = (int)(unsigned)w0, ky = (int)(unsigned)(w0 >> 32), kz = (int)(unsigned)w1;
+    const unsigned cnt = (unsigned)(w1 >> 32);
+    const bool ok = kx > -kMapKeyOff && kx < kMapKeyOff && ky > -kMapKeyOff && ky < kMapKeyOff && kz > -kMapKeyOff && kz < kMapKeyOff &&
+                    cnt >= 1u && cnt <= kStateMaxCount;
+    if (!ok) {
+      ++n_rej;
+      continue;
+    }
+    const unsigned long long h = map_slot(keys, mask, map_pack(kx, ky, kz), fresh);
+    if (h == kMapEmpty) {  // (cannot happen: the growth policy left room for every record)
+      atomicAdd(ctr + kCtrLost, 1ull);
+      continue;
+    }
+    map_add_sums<MOM>(pay, mom, h, sx, sy, sz, (unsigned long long)cnt, MOM ? in_mom + kMapMom * i : nullptr);
+    n_pts += cnt;
+  }
+  block_count<kStateThreads>({(unsigned long long)fresh, n_pts, n_rej}, {ctr + kCtrOcc, ctr + kCtrPts, ctr + kCtrRejCall});
+}
+
+// merge: one lane per slot of the source table, as k_map_rehash - but the destination may hold the key, so the sums are added, and the
+// destination's voxel and point counters grow by what is new.  MOM: the destination holds moments (then the source does)
+template <bool MOM>
+__global__ void __launch_bounds__(kStateThreads) k_map_merge(const unsigned long long *skeys, const long long *spay, const long long *smom, uint64_t scap,
+                                                             unsigned long long *keys, long long *pay, long long *mom, unsigned long long mask,
+                                                             unsigned long long *ctr) {
+  const uint64_t i = (uint64_t)blockIdx.x * kStateThreads + threadIdx.x;
+  unsigned fresh = 0;
+  unsigned long long n_pts = 0;
+  const unsigned long long key = i < scap ? skeys[i] : kMapEmpty;
+  if (key != kMapEmpty) {
+    const longlong2 *p = (const longlong2 *)(spay + 4 * i);
+    const longlong2 p0 = p[0], p1 = p[1];
+    const unsigned long long h = map_slot(keys, mask, key, fresh);
+    if (h != kMapEmpty) {
+      map_add_sums<MOM>(pay, mom, h, (unsigned long long)p0.x, (unsigned long long)p0.y, (unsigned long long)p1.x, (unsigned long long)p1.y,
+                        MOM ? smom + kMapMom * i : nullptr);
+      n_pts = (unsigned long long)p1.y;
+    } else {  // (cannot happen: the growth policy left room for every voxel of the source)
+      atomicAdd(ctr + kCtrLost, 1ull);
+    }
+  }
+  block_count<kStateThreads>({(unsigned long long)fresh, n_pts}, {ctr + kCtrOcc, ctr + kCtrPts});
+}
+
 // ---- carving (wc_map_carve) -------------------------------------------------------------------------------------------------------
 // what is the same for every ray of a call; the squares and the origin's voxel are formed once, on the host
 struct map_ray_args {
@@ -1120,19 +1225,46 @@ extern "C" int wc_map_destroy(wc_ctx *ctx, wc_map *m) {
   return WC_OK;
 }
 
+namespace {
+// what precedes every call that may create up to n voxels (insert: n points; absorb: n records; merge: the source's voxels) - growth
+// (policy at the top of the file): at most half full at every probe of the call
+int map_make_room(wc_ctx *ctx, wc_map *m, uint64_t n, const char *fn) {
+  const uint64_t need = 2 * (map_bound(m) + n);
+  if (need > m->cap) {
+    const uint64_t cap = pow2_at_least(need);
+    if (cap > ((uint64_t)1 << 32)) return wc_fail(ctx, WC_ERR_CAPACITY, "%s: the table would exceed 2^32 slots", fn);
+    WC_TRY(map_replace_table(ctx, m, cap, map_sel_all{}));
+    ++m->growths;
+  }
+  return WC_OK;
+}
+// ... and what follows its kernel: the n possible new voxels enter the bound; with h_n_rejected the call waits and reports its own
+// rejected count, without it the counters travel back behind the kernel and tighten the next call's bound when they have arrived
+int map_added(wc_ctx *ctx, wc_map *m, uint64_t n, uint64_t *h_n_rejected) {
+  m->pts_since += n;
+  if (h_n_rejected) {
+    WC_TRY(map_sync_counters(ctx, m));
+    *h_n_rejected = m->h_ctr[kCtrRejCall];
+    return WC_OK;
+  }
+  if (m->ctr_pending) {
+    m->pts_after_copy += n;
+  } else {
+    WC_HIP(ctx, hipMemcpyAsync(m->h_ctr, m->ctr, kCtrWords * 8, hipMemcpyDeviceToHost, ctx->stream));
+    WC_HIP(ctx, hipEventRecord(m->ev_ctr, ctx->stream));
+    m->ctr_pending = true;
+    m->pts_after_copy = 0;
+  }
+  return WC_OK;
+}
+}  // namespace
+
 extern "C" int wc_map_insert(wc_ctx *ctx, wc_map *m, const wc_points *pts, uint64_t *h_n_rejected) {
   wc_dev_guard dg_(ctx);
   if (!map_ok(ctx, m) || !map_points_ok(pts)) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
   if (h_n_rejected) *h_n_rejected = 0;
   if (pts->n == 0) return WC_OK;
-  // growth (policy at the top of the file): at most half full at every probe of this call
-  const uint64_t need = 2 * (map_bound(m) + pts->n);
-  if (need > m->cap) {
-    const uint64_t cap = pow2_at_least(need);
-    if (cap > ((uint64_t)1 << 32)) return wc_fail(ctx, WC_ERR_CAPACITY, "%s: the table would exceed 2^32 slots", __func__);
-    WC_TRY(map_replace_table(ctx, m, cap, map_sel_all{}));
-    ++m->growths;
-  }
+  WC_TRY(map_make_room(ctx, m, pts->n, __func__));
   WC_HIP(ctx, hipMemsetAsync(m->ctr + kCtrRejCall, 0, 8, ctx->stream));
   if (!m->mom)
     map_launch_insert<false, kMapPts>(ctx, m, *pts);
@@ -1141,22 +1273,7 @@ extern "C" int wc_map_insert(wc_ctx *ctx, wc_map *m, const wc_points *pts, uint6
   else
     map_launch_insert<true, kMapMomPts>(ctx, m, *pts);
   WC_HIP(ctx, hipGetLastError());
-  m->pts_since += pts->n;
-  if (h_n_rejected) {
-    WC_TRY(map_sync_counters(ctx, m));
-    *h_n_rejected = m->h_ctr[kCtrRejCall];
-    return WC_OK;
-  }
-  // (no wait: the counters travel back behind the kernel and tighten the next call's bound when they have arrived)
-  if (m->ctr_pending) {
-    m->pts_after_copy += pts->n;
-  } else {
-    WC_HIP(ctx, hipMemcpyAsync(m->h_ctr, m->ctr, kCtrWords * 8, hipMemcpyDeviceToHost, ctx->stream));
-    WC_HIP(ctx, hipEventRecord(m->ev_ctr, ctx->stream));
-    m->ctr_pending = true;
-    m->pts_after_copy = 0;
-  }
-  return WC_OK;
+  return map_added(ctx, m, pts->n, h_n_rejected);
 }
 
 extern "C" int wc_map_size(wc_ctx *ctx, wc_map *m, uint64_t *h_voxels, uint64_t *h_points) {
@@ -1242,6 +1359,66 @@ extern "C" int wc_map_export_surfels(wc_ctx *ctx, wc_map *m, wc_map_surfel *d_ou
   k_map_surfels<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(kout, vout, n, m->pay, m->mom, m->voxel, d_out);
   WC_HIP(ctx, hipGetLastError());
   return WC_OK;
+}
+
+// ---- the exact state (include/wildcat_hip.h: wc_map_export_state, wc_map_absorb, wc_map_merge) -----------------------------------
+extern "C" int wc_map_export_state(wc_ctx *ctx, wc_map *m, wc_map_voxel *d_vox, int64_t *d_mom, uint64_t cap, uint64_t *h_n) {
+  wc_dev_guard dg_(ctx);
+  if (!map_ok(ctx, m) || !h_n || (uintptr_t)d_vox % 8 || (uintptr_t)d_mom % 8 || (d_mom && !m->mom))
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or misaligned argument, a map of another context, or d_mom with a map created without WC_MAP_MOMENTS",
+                   __func__);
+  WC_TRY(map_export_size(ctx, m, __func__, cap, h_n));
+  const uint64_t n = *h_n;
+  if (n == 0) return WC_OK;
+  if (!d_vox) return wc_fail(ctx, WC_ERR_ARG, "%s: null output", __func__);
+  unsigned long long *kout = nullptr;
+  uint32_t *vout = nullptr;
+  WC_TRY(map_sorted_slots(ctx, m, n, &kout, &vout));
+  k_map_state<<<(unsigned)((n + kStateThreads - 1) / kStateThreads), kStateThreads, 0, ctx->stream>>>(kout, vout, n, m->pay, m->mom, d_vox,
+                                                                                                     (long long *)d_mom);
+  WC_HIP(ctx, hipGetLastError());
+  return WC_OK;
+}
+
+extern "C" int wc_map_absorb(wc_ctx *ctx, wc_map *m, const wc_map_voxel *d_vox, const int64_t *d_mom, uint64_t n, uint64_t *h_n_rejected) {
+  wc_dev_guard dg_(ctx);
+  if (!map_ok(ctx, m)) return wc_fail(ctx, WC_ERR_ARG, "%s: null argument or a map of another context", __func__);
+  if (h_n_rejected) *h_n_rejected = 0;
+  if (n == 0) return WC_OK;
+  if (!d_vox || (uintptr_t)d_vox % 8 || (uintptr_t)d_mom % 8 || (m->mom && !d_mom) || n > ((uint64_t)1 << 31))
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or misaligned records, n > 2^31, or a WC_MAP_MOMENTS map without d_mom", __func__);
+  WC_TRY(map_make_room(ctx, m, n, __func__));
+  WC_HIP(ctx, hipMemsetAsync(m->ctr + kCtrRejCall, 0, 8, ctx->stream));
+  const uint64_t blocks = (n + kStateThreads - 1) / kStateThreads;
+  uint64_t grid = std::min<uint64_t>(blocks, (uint64_t)8 * m->cus);
+  if (ctx->dev.map_absorb_groups > 0) grid = std::min<uint64_t>(blocks, (uint64_t)ctx->dev.map_absorb_groups);  // (development option)
+  if (m->mom)
+    k_map_absorb<true><<<(unsigned)grid, kStateThreads, 0, ctx->stream>>>(d_vox, (const long long *)d_mom, n, m->keys, m->pay, m->mom, m->cap - 1,
+                                                                          m->ctr);
+  else
+    k_map_absorb<false><<<(unsigned)grid, kStateThreads, 0, ctx->stream>>>(d_vox, nullptr, n, m->keys, m->pay, nullptr, m->cap - 1, m->ctr);
+  WC_HIP(ctx, hipGetLastError());
+  return map_added(ctx, m, n, h_n_rejected);
+}
+
+extern "C" int wc_map_merge(wc_ctx *ctx, wc_map *dst, wc_map *src) {
+  wc_dev_guard dg_(ctx);
+  if (!map_ok(ctx, dst) || !map_ok(ctx, src) || dst == src || std::memcmp(&dst->voxel, &src->voxel, sizeof(double)) != 0 || (dst->mom && !src->mom))
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null argument, dst == src, a map of another context, two voxel sizes, or moments in dst and none in src",
+                   __func__);
+  WC_TRY(map_sync_counters(ctx, src));  // (the wait: the source's exact voxel count bounds what the destination may gain)
+  const uint64_t n = src->h_ctr[kCtrOcc];
+  if (n == 0) return WC_OK;
+  WC_TRY(map_make_room(ctx, dst, n, __func__));
+  const unsigned grid = (unsigned)((src->cap + kStateThreads - 1) / kStateThreads);
+  if (dst->mom)
+    k_map_merge<true><<<grid, kStateThreads, 0, ctx->stream>>>(src->keys, src->pay, src->mom, src->cap, dst->keys, dst->pay, dst->mom, dst->cap - 1,
+                                                               dst->ctr);
+  else
+    k_map_merge<false><<<grid, kStateThreads, 0, ctx->stream>>>(src->keys, src->pay, nullptr, src->cap, dst->keys, dst->pay, nullptr, dst->cap - 1,
+                                                                dst->ctr);
+  WC_HIP(ctx, hipGetLastError());
+  return map_added(ctx, dst, n, nullptr);
 }
 
 extern "C" int wc_map_clear(wc_ctx *ctx, wc_map *m) {

@@ -14,6 +14,7 @@
 #include "../csrc/dmath.h"
 #include "cubic_bspline.h"
 #include "histogram.h"
+#include "map_file.h"
 
 using namespace wc;
 
@@ -598,6 +599,62 @@ bool LidarOdometry::CastMap(const float *xyz, size_t n, const double origin[3], 
   if (wc_map_raycast(ctx_, map_, &desc, origin, &params, (wc_map_ray_hit *)d_hits.p, &r) != WC_OK) return false;  // (as in AlignToMap)
   if (n) d_hits.ToHost(hits, n * sizeof(wc_map_ray_hit));
   if (result) *result = r;
+  return true;
+}
+// ---- the map's exact state as a file (host/map_file.h) ---------------------------------------------------------------------------
+static_assert(sizeof(wc_map_voxel) == sizeof(wc_map_file::Voxel) && offsetof(wc_map_voxel, count) == offsetof(wc_map_file::Voxel, count) &&
+                  offsetof(wc_map_voxel, sum) == offsetof(wc_map_file::Voxel, sum),
+              "the file's record is the library's wc_map_voxel");
+bool LidarOdometry::SaveMap(const std::string &path) {
+  if (!map_) return false;
+  uint64_t n = map_voxels();
+  std::vector<wc_map_file::Voxel> vox(n);
+  std::vector<int64_t> mom(map_moments_ ? 9 * n : 0);
+  if (n) {
+    const DevBuf d_vox(ctx_, n * sizeof(wc_map_voxel)), d_mom(ctx_, mom.size() * sizeof(int64_t));
+    WC_CALL(wc_map_export_state(ctx_, map_, (wc_map_voxel *)d_vox.p, (int64_t *)d_mom.p, n, &n));
+    d_vox.ToHost(vox.data(), n * sizeof(wc_map_voxel));
+    if (d_mom.p) d_mom.ToHost(mom.data(), mom.size() * sizeof(int64_t));
+  }
+  std::vector<uint8_t> file(wc_map_file::EncodedBytes(n, map_moments_));
+  wc_map_file::Encode(map_voxel_, map_moments_ ? wc_map_file::kFlagMoments : 0u, vox.data(), mom.data(), n, file.data());
+  if (wc_map_file::Decode(file.data(), file.size(), nullptr) != wc_map_file::kOk) return false;  // (a voxel beyond 2^30 points)
+  std::FILE *f = std::fopen(path.c_str(), "wb");
+  if (!f) return false;
+  const bool written = std::fwrite(file.data(), 1, file.size(), f) == file.size();
+  const bool closed = std::fclose(f) == 0;
+  if (!(written && closed)) std::remove(path.c_str());
+  return written && closed;
+}
+bool LidarOdometry::LoadMap(const std::string &path, bool merge) {
+  if (!map_) return false;
+  std::FILE *f = std::fopen(path.c_str(), "rb");
+  if (!f) return false;
+  std::vector<uint8_t> file;
+  uint8_t chunk[65536];
+  for (size_t got; (got = std::fread(chunk, 1, sizeof(chunk), f)) > 0;) file.insert(file.end(), chunk, chunk + got);
+  const bool read_ok = std::ferror(f) == 0;
+  std::fclose(f);
+  wc_map_file::Header h;
+  if (!read_ok || wc_map_file::Decode(file.data(), file.size(), &h) != wc_map_file::kOk) return false;
+  const bool file_moments = (h.flags & wc_map_file::kFlagMoments) != 0;
+  if (std::memcmp(&h.voxel, &map_voxel_, sizeof(double)) != 0 || (map_moments_ && !file_moments)) return false;
+  std::vector<wc_map_file::Voxel> vox(h.n);
+  std::vector<int64_t> mom(map_moments_ ? 9 * h.n : 0);
+  wc_map_file::Unpack(file.data(), h, vox.data(), map_moments_ ? mom.data() : nullptr);
+  if (!merge) {  // as SetMapVoxel re-creates it, with room for the file's voxels: no growth and no wc_map_clear
+    WC_CALL(wc_map_destroy(ctx_, map_));
+    map_ = nullptr;
+    WC_CALL(wc_map_create_ex(ctx_, map_voxel_, h.n, map_moments_ ? WC_MAP_MOMENTS : 0u, &map_));
+  }
+  if (h.n) {
+    const DevBuf d_vox(ctx_, h.n * sizeof(wc_map_voxel)), d_mom(ctx_, mom.size() * sizeof(int64_t));
+    CheckCall(ctx_, "wc_h2d", wc_h2d(ctx_, d_vox.p, vox.data(), h.n * sizeof(wc_map_voxel)));
+    if (d_mom.p) CheckCall(ctx_, "wc_h2d", wc_h2d(ctx_, d_mom.p, mom.data(), mom.size() * sizeof(int64_t)));
+    uint64_t rejected = 0;  // (asked for: the call waits, so the host vectors and device buffers outlive the kernel)
+    WC_CALL(wc_map_absorb(ctx_, map_, (const wc_map_voxel *)d_vox.p, (const int64_t *)d_mom.p, h.n, &rejected));
+    WC_CHECK(rejected == 0);  // (Decode refuses every record the absorb rejects)
+  }
   return true;
 }
 bool LidarOdometry::SetMapKeepRadius(double radius) {

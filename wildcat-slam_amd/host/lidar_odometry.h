@@ -116,6 +116,14 @@ class LidarOdometry {
   // arguments the library refuses.  Nothing in AddLidarScan calls it
   bool CastMap(const float *xyz, size_t n, const double origin[3], const wc_map_raycast_params &params, wc_map_ray_hit *hits,
                wc_map_raycast_result *result);
+  // the map's exact state (wc_map_export_state) as the canonical file of host/map_file.h; false - no file is left behind -
+  // without a map or when the file cannot be written.  Nothing in AddLidarScan calls SaveMap or LoadMap
+  bool SaveMap(const std::string &path);
+  // a file SaveMap wrote, absorbed (wc_map_absorb) into the map: re-created empty first, with room for the file's voxels (merge = false),
+  // or as it is (merge = true: counts and sums add up).  false - nothing touched - without a map, when the file is refused
+  // (wc_map_file::Decode), when its voxel size is not bitwise config().map_voxel_size, or when map_surfels is on and the file has no
+  // moments (a file with moments loads into a map without: they are dropped)
+  bool LoadMap(const std::string &path, bool merge = false);
   // wall time [ms] of the last completed sweep's map step (the undistortion when fill_outputs does not already form it, the insert's
   // enqueue - its kernel runs behind on the stream - and, with map_keep_radius, the crop, which waits).  Not part of last_stage_ms()
   double last_map_ms() const { return last_map_ms_; }

@@ -9,6 +9,7 @@
 #include "histogram.h"
 #include "imu_resampler.h"
 #include "lidar_odometry.h"
+#include "map_file.h"
 
 extern "C" {
 
@@ -235,6 +236,27 @@ int wc_odom_map_carve(void *h, const float *xyz, uint64_t n, const double origin
 int wc_odom_map_raycast(void *h, const float *xyz, uint64_t n, const double origin[3], const wc_map_raycast_params *params, wc_map_ray_hit *hits,
                         wc_map_raycast_result *result) {
   return params && ((LidarOdometry *)h)->CastMap(xyz, n, origin, *params, hits, result) ? 1 : 0;
+}
+// LidarOdometry::SaveMap / LoadMap (the canonical state file of host/map_file.h); 1 = done, 0 = refused (nothing touched)
+int wc_odom_map_save(void *h, const char *path) { return path && ((LidarOdometry *)h)->SaveMap(path) ? 1 : 0; }
+int wc_odom_map_load(void *h, const char *path, int merge) { return path && ((LidarOdometry *)h)->LoadMap(path, merge != 0) ? 1 : 0; }
+// host/map_file.h without a GPU.  encode: the file of n records (vox: n x 40 bytes as wc_map_voxel; mom: n x 9 int64, read with flags
+// bit 0) -> its size in bytes; written when cap is at least that.  decode: wc_map_file::Decode's code (0 = accepted; then *voxel, *flags
+// and *n describe the file, and vox / mom - either may be NULL - receive its records when cap >= n)
+uint64_t wc_host_map_file_encode(double voxel, uint32_t flags, const void *vox, const int64_t *mom, uint64_t n, uint8_t *out, uint64_t cap) {
+  const uint64_t bytes = wc_map_file::EncodedBytes(n, (flags & wc_map_file::kFlagMoments) != 0);
+  if (out && cap >= bytes) wc_map_file::Encode(voxel, flags, (const wc_map_file::Voxel *)vox, mom, n, out);
+  return bytes;
+}
+int wc_host_map_file_decode(const uint8_t *buf, uint64_t len, double *voxel, uint32_t *flags, uint64_t *n, void *vox, int64_t *mom, uint64_t cap) {
+  wc_map_file::Header h;
+  const int rc = wc_map_file::Decode(buf, len, &h);
+  if (rc != wc_map_file::kOk) return rc;
+  if (voxel) *voxel = h.voxel;
+  if (flags) *flags = h.flags;
+  if (n) *n = h.n;
+  if (vox && cap >= h.n) wc_map_file::Unpack(buf, h, (wc_map_file::Voxel *)vox, mom);
+  return rc;
 }
 // LioConfig::map_keep_radius: 0 = unbounded map; returns 0, or WC_ERR_ARG for a negative or NaN radius
 int wc_odom_set_map_keep_radius(void *h, double radius) { return ((LidarOdometry *)h)->SetMapKeepRadius(radius) ? 0 : WC_ERR_ARG; }

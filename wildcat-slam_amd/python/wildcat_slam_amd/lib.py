@@ -788,6 +788,61 @@ class PointMap:
         finally:
             d_out.free()
 
+    def state_device(self, d_vox, d_mom, cap):
+        """MAP_VOXEL records into d_vox and (n, 9) int64 moment words into d_mom (either may be None) (wc_map_export_state)
+        -> (return code, n): WC_ERR_CAPACITY leaves the needed count in n"""
+        n = C.c_uint64(0)
+        rc = self.lib.wc_map_export_state(self.ctx.h, self.h, C.c_void_p(d_vox.ptr if d_vox else 0), C.c_void_p(d_mom.ptr if d_mom else 0),
+                                          C.c_uint64(int(cap)), C.byref(n))
+        return rc, int(n.value)
+
+    def state(self):
+        """-> (MAP_VOXEL array, (n, 9) int64 moment words or None on a plain map): the table's integer sums themselves, one record per
+        occupied voxel in export()'s order"""
+        rc, n = self.state_device(None, None, 0)
+        if n == 0:
+            self.ctx._ck(rc)
+            return np.zeros(0, R.MAP_VOXEL), (np.zeros((0, 9), np.int64) if self.moments else None)
+        d_vox = self.ctx.alloc(R.MAP_VOXEL.itemsize * n)
+        d_mom = self.ctx.alloc(72 * n) if self.moments else None
+        try:
+            rc, m = self.state_device(d_vox, d_mom, n)
+            self.ctx._ck(rc)
+            return d_vox.download(R.MAP_VOXEL, m), (d_mom.download(np.int64, 9 * m).reshape(-1, 9) if d_mom else None)
+        finally:
+            for b in (d_vox, d_mom):
+                if b:
+                    b.free()
+
+    def absorb_device(self, d_vox, d_mom, n, want_count=True):
+        """n MAP_VOXEL records (and their moment words, or None) already in HBM added to the map by key (wc_map_absorb) -> records
+        rejected, or None without waiting when want_count is False"""
+        rej = C.c_uint64(0)
+        self.ctx._ck(self.lib.wc_map_absorb(self.ctx.h, self.h, C.c_void_p(d_vox.ptr if d_vox else 0), C.c_void_p(d_mom.ptr if d_mom else 0),
+                                            C.c_uint64(int(n)), C.byref(rej) if want_count else None))
+        return int(rej.value) if want_count else None
+
+    def absorb(self, vox, mom=None):
+        """a state (MAP_VOXEL array; mom: (n, 9) int64, needed by a map with moments), uploaded for the call -> records rejected.  The
+        records need not be sorted, duplicate keys add up"""
+        vox = np.ascontiguousarray(vox, R.MAP_VOXEL)
+        n = len(vox)
+        if mom is not None:
+            mom = np.ascontiguousarray(mom, np.int64).reshape(-1, 9)
+            assert len(mom) == n, "one row of nine moment words per record"
+        d_vox = self.ctx.to_device(vox) if n else None
+        d_mom = self.ctx.to_device(mom) if (mom is not None and n) else None
+        try:
+            return self.absorb_device(d_vox, d_mom, n)
+        finally:
+            for b in (d_vox, d_mom):
+                if b:
+                    b.free()
+
+    def merge(self, other):
+        """this map becomes the map of its own points and other's (wc_map_merge: table to table on the device); other is not modified"""
+        self.ctx._ck(self.lib.wc_map_merge(self.ctx.h, self.h, other.h))
+
     def nearest_plane_device(self, desc, max_dist, min_points, d_hits, want_count=True):
         """queries already in HBM (a wc_points descriptor) -> MAP_PLANE_HIT records in d_hits (wc_map_nearest_plane); returns the number
         of voxels found, or None without waiting when want_count is False"""
@@ -990,6 +1045,16 @@ class Odometry:
         if not self.lib.wc_odom_map_align(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), R.ptr(T), C.byref(opts), C.byref(summ)):
             return None
         return T.reshape(3, 4), _summary_dict(summ)
+
+    def map_save(self, path):
+        """the map's exact state as the canonical file of host/map_file.h (LidarOdometry::SaveMap) -> True, or False without a map or
+        when the file cannot be written"""
+        return bool(self.lib.wc_odom_map_save(self.h, os.fsencode(path)))
+
+    def map_load(self, path, merge=False):
+        """a file map_save wrote, absorbed into the map - re-created empty first unless merge (LidarOdometry::LoadMap) -> True, or False
+        (the map untouched) without a map, for a file the decoder refuses, another voxel size, or a file without moments with map_surfels on"""
+        return bool(self.lib.wc_odom_map_load(self.h, os.fsencode(path), C.c_int(1 if merge else 0)))
 
     def set_map_keep_radius(self, radius):
         """LioConfig::map_keep_radius: after every sweep the map keeps the cube of this half-side around the sensor; 0 = unbounded"""

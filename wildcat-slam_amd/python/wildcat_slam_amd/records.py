@@ -34,6 +34,9 @@ MAP_SURFEL = np.dtype(
     [("key", "i4", 3), ("count", "u4"), ("xyz", "f4", 3), ("flags", "u4"), ("cov", "f8", 6), ("ev", "f8", 3), ("normal", "f8", 3)]
 )  # wc_map_surfel
 assert MAP_SURFEL.itemsize == 128 and [MAP_SURFEL.fields[f][1] for f in ("count", "xyz", "flags", "cov", "ev", "normal")] == [12, 16, 28, 32, 80, 104]
+# wc_map_voxel: one voxel of the map's exact state (the first 16 bytes as MAP_SURFEL's); the nine moment words travel as an (n, 9) int64 array
+MAP_VOXEL = np.dtype([("key", "i4", 3), ("count", "u4"), ("sum", "i8", 3)])
+assert MAP_VOXEL.itemsize == 40 and [MAP_VOXEL.fields[f][1] for f in ("key", "count", "sum")] == [0, 12, 16]
 # wc_map_plane_hit: the fields of MAP_HIT (flags: bit 1 = the plane is valid), then the plane
 MAP_PLANE_HIT = np.dtype(MAP_HIT.descr + [("normal", "f8", 3), ("sigma2", "f8"), ("dist", "f8")])
 assert MAP_PLANE_HIT.itemsize == 80 and [MAP_PLANE_HIT.fields[f][1] for f in ("flags", "d2", "normal", "sigma2", "dist")] == [28, 32, 40, 64, 72]
