@@ -17,7 +17,7 @@ extract(points, params) -> dict, one row per surfel in the oracle's output order
   its root: a NaN is never this reference's answer), orient (normal . (centre - view) before orienting), members (point indices);
   stats: root_voxels, nodes_tested / nodes_plane per layer, clusters_total / clusters_rejected, surfels, min_gate_margin (as oracle/extract.cc),
   node_* and cluster_* arrays (n, centre, margin = distance of the nearer gate from its threshold, like, ev0, band = the width
-  16 sqrt(n) (|c|^2 + 1) 2^-53 + 1e-14 inside which the default path hands the sweep to the exact arithmetic), min_gap_dist (the
+  16 sqrt(n) (|c|^2 + 1) 2^-53 + 1e-14 + 3 B_cov(f = 1) inside which the default path hands the sweep to the exact arithmetic), min_gap_dist (the
   smallest | (t_i - t_{i-1}) - cluster_gap | over consecutive stamps of every tested node)."""
 from fractions import Fraction
 
@@ -105,10 +105,13 @@ def _pca(d, t, f_small, starts, counts, root_c):
     return dict(n=counts.copy(), center=c, cov=S, ev=ev, V=V, like=like, t=tm, f=f)
 
 
-def _band(n, c):
-    """the width of fx_pca's "near a gate" band (csrc/extract_fast.inc), as DESIGN.md states it"""
+def _band(n, c, vs=0.8):
+    """the width of fx_pca's "near a gate" band (csrc/extract_fast.inc), as DESIGN.md 4.3 states it: 16 x the reference's rounding noise, and
+    the default path's own error on lambda_0 - 3 B_cov of bounds() below, with f = 1 (a constant of the sweep)"""
     c = np.asarray(c, np.float64)
-    return 16.0 * np.sqrt(np.asarray(n, np.float64)) * ((c * c).sum(axis=1) + 1.0) * 2.0**-53 + 1e-14
+    vs = float(np.float32(vs))
+    grid = 3.0 * (2.0**-45 + 2 * 2.0**-33 * vs + 16 * 2.0**-53 * (vs / 2) ** 2)
+    return 16.0 * np.sqrt(np.asarray(n, np.float64)) * ((c * c).sum(axis=1) + 1.0) * 2.0**-53 + 1e-14 + grid
 
 
 def extract(points, params):
@@ -199,7 +202,7 @@ def extract(points, params):
     for name, rows in (("node", node_rows), ("cluster", cluster_rows)):
         for key in ("n", "center", "margin", "like", "ev0", "layer"):
             stats[name + "_" + key] = cat(rows, key) if key != "center" else (np.concatenate([r[key] for r in rows]) if rows else np.zeros((0, 3)))
-        stats[name + "_band"] = _band(stats[name + "_n"], stats[name + "_center"])
+        stats[name + "_band"] = _band(stats[name + "_n"], stats[name + "_center"], vs)
     margins = np.concatenate([stats["node_margin"], stats["cluster_margin"]])
     stats["min_gate_margin"] = float(margins.min()) if len(margins) else 1e300
     stats["min_gap_dist"] = min_gap_dist

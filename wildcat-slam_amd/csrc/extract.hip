@@ -1894,6 +1894,10 @@ int run_pipeline_fast(wc_ctx *ctx) {
   A.inv_span = 1.0 / (t_hi - t_lo);
   A.inv_vs = 1.0 / (double)P.voxel_size;
   A.qs = 4294967296.0, A.inv_q = 1.0 / 4294967296.0, A.inv_qq = std::ldexp(1.0, -44);
+  {  // the constant part of fx_pca's band: 1e-14 + 3 B_cov, B_cov with f = 1 (extract_fast.inc)
+    const double vs = (double)P.voxel_size;
+    A.band0 = 1e-14 + 3.0 * (std::ldexp(1.0, -45) + 2.0 * std::ldexp(1.0, -33) * vs + 16.0 * std::ldexp(1.0, -53) * (0.5 * vs) * (0.5 * vs));
+  }
   // capacities: a root block (640 B) per 8 points, a layer-2 node block per 16; the hash holds 4 x the root blocks; one
   // 128-byte record per LDS hash slot of every tile + a spill pool
   uint32_t mr = 1024;

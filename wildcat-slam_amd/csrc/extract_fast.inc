@@ -15,7 +15,7 @@
 //     open between bins) - again order independent;
 //   * takes every decision the reference takes (n > 20, n >= 20, lambda_0 < 0.01f, likeness > 0.1, cc:33,54,106-111,129,172)
 //     on these sums, and raises kFlagFxFallback whenever a PCA gate is closer to its threshold than the reference's own
-//     rounding noise could move it: finish() then repeats the sweep on the exact path.  Counts and ids are therefore the
+//     rounding noise or this path's own grids could move it: finish() then repeats the sweep on the exact path.  Counts and ids are therefore the
 //     reference's; centre / covariance / normal / sigma agree with the exact values to the grids' rounding (covariance entries 2^-45 m^2,
 //     bounds and measurements per field: DESIGN.md 4.3, tests/test_extract_precision_gpu.py); a surfel's timestamp is the correctly rounded mean
 //     (the reference's running sum rounds at ~1e-5 s with epoch-sized stamps), so the OUTPUT ORDER - ascending timestamp,
@@ -64,6 +64,7 @@ struct FxArgs {
   double inv_span;   // 1 / (t_hi - t_lo): time keys of the surfel order are 32-bit fractions of the sweep
   double inv_vs;     // 1 / (double)voxel_size: estimate of the voxel index, confirmed by the true division near integers
   double qs, inv_q, inv_qq;  // 2^32, 2^-32, 2^-44
+  double band0;      // the part of fx_pca's "near" band that does not depend on the cluster: 1e-14 + 3 B_cov, this path's own grids (see fx_pca)
   uint32_t *rkey;          // root hash: key + 1 (0 = empty); the slot is the index of the root's block
   uint32_t *rlist;         // [kFxSub * mr_per] slots of the roots created in this sweep, per sub-counter
   uint32_t tr_mask;
@@ -935,9 +936,13 @@ __device__ __forceinline__ void fx_pca(const FxArgs &A, const FxPart &m, const d
   const double isum = fx_rcp(sum);
   r.like = 2 * (r.ev[1] - r.ev[0]) * isum;
   // The reference forms sum(p p^T)/n - c c^T in fp64 on world coordinates (cc:40-47, :89-97): rounding noise of the order
-  // sqrt(n) |c|^2 eps in every covariance entry (SURVEY Q6).  A gate inside that band (x16) is not decided here.
+  // sqrt(n) |c|^2 eps in every covariance entry (SURVEY Q6).  A gate inside that band (x16) is not decided here - nor one inside
+  // THIS path's own error: its covariance entries are off by up to B_cov = 2^-45 (the product grid) + 2 2^-33 vs f (coordinates below
+  // 2^-8 m are finer than the 2^-32 m grid; f: the share of such points) + 16 2^-53 (vs/2)^2, lambda_0 by up to 3 B_cov (DESIGN 4.3).
+  // A.band0 = 1e-14 + 3 B_cov with f = 1, a constant of the sweep.  (Without it a root with its lower half in 0 < x < 2^-9 m, lambda_0
+  // 5e-12 above the threshold - 42 of the narrower bands - came out a plane: tests/test_extract_gates_gpu.py, lam0-root-slab.)
   const double R2 = r.c[0] * r.c[0] + r.c[1] * r.c[1] + r.c[2] * r.c[2] + 1.0;
-  const double dl = 16.0 * (n * fx_rsqrt(n)) * R2 * 1.1102230246251565e-16 + 1e-14;
+  const double dl = 16.0 * (n * fx_rsqrt(n)) * R2 * 1.1102230246251565e-16 + A.band0;
   const double dlike = 6.0 * dl * fabs(isum) + 1e-13;
   // (Round 5 also sent a smallest eigenvalue inside that band of ZERO to the exact path - the reference's sigma = sqrt(lambda_0) is then NaN
   // or a rounding-sized number by the luck of its own sums - and took it out again: such clusters are not rare, every stretch of ONE scan
@@ -964,7 +969,7 @@ __device__ __forceinline__ bool fx_surely_not_plane(const FxArgs &A, const FxPar
   const double tr = (c00 + c11) + c22;
   const double px = cc[0] + mx, py = cc[1] + my, pz = cc[2] + mz;
   const double R2 = px * px + py * py + pz * pz + 1.0;
-  const double dl = 16.0 * (n * fx_rsqrt(n)) * R2 * 1.1102230246251565e-16 + 1e-14;  // (fx_pca's band)
+  const double dl = 16.0 * (n * fx_rsqrt(n)) * R2 * 1.1102230246251565e-16 + A.band0;  // (fx_pca's band)
   return m.n != 0u && tr > 0.0 && 4.0 * det > 1.001 * (A.P.thr + dl) * tr * tr;
 }
 

@@ -266,7 +266,10 @@ class Context:
         self.set_params(self.params)
 
     def extract_path_info(self):
-        """-> dict(fast=the last sweep was completed by the fast path, fallbacks=sweeps handed to the exact path so far, flags,
+        """-> dict(fast=the last sweep was completed by the fast path, fallbacks=sweeps handed to the exact path so far, flags=status bits of
+        the last default-path sweep (64: it fell back), why=bit i: call site i of fx_fallback() fired in the LAST SWEEP THAT FELL BACK (it keeps its
+        value through later sweeps that do not; csrc/extract_fast.inc: 13 a child's PCA near a gate, 14 the root's, 15 a temporal cluster's,
+        FxWhy::gap - 7 in k_fx_nodes, 17 in k_fx_walk - a stamp gap within 8 ticks of cluster_gap, the rest capacities),
         long_lists=the last fast sweep had long record lists: the next one merges them first (k_fx_merge),
         runs=pipelines the last sweep enqueued (1: no repeat), path=bits of the pipeline that completed it (1 default path, 2 wide
         keys, 4 run-binned point sort, 8 time-bin surfel order), lds_cap=runs per bucket the run-binned sort takes in LDS)"""
