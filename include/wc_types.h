@@ -184,7 +184,7 @@ typedef struct wc_map_carve_result { /* 40 bytes */
   uint64_t rays_used;      /* rays that were walked                                             */
   uint64_t rays_skipped;   /* every other point of the call                                     */
   uint64_t steps;          /* sum of the used rays' walk lengths M                              */
-  uint64_t voxels_removed; /* occupied voxels selected (not removed yet: wildcat_hip.h)          */
+  uint64_t voxels_removed; /* occupied voxels selected (wc_map_carve_remove: and removed)       */
   uint64_t points_removed; /* ... and the points they hold                                      */
 } wc_map_carve_result;
 

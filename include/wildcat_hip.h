@@ -76,6 +76,8 @@ int wc_ctx_set_params(wc_ctx *ctx, const wc_params *params);
  *                      whatever the value
  *   map_absorb_groups (0) wc_map_absorb: workgroups of its kernel (0: chosen from the record count); the map is the same whatever the
  *                      value
+ *   map_remove_groups (0) wc_map_remove_keys: workgroups of its kernel (0: chosen from the key count); the map and the three counts are
+ *                      the same whatever the value
  *   lm_radius0         initial trust-region radius of wc_window_solve: 10^value (default -1 = the library's 1e4); tests use it to
  *                      look at the first step at other damping levels
  * Tests use it to run both forms of a choice on the same data.  Unknown names return WC_ERR_ARG. */
@@ -403,9 +405,9 @@ int wc_map_crop(wc_ctx *ctx, wc_map *m, const double lo[3], const double hi[3], 
 /* Carving: free space by visibility.  A lidar return also says that the space between the sensor and the return is empty: every point p
  * of `pts` (DEVICE pointers, the wc_points rules of wc_map_insert: either stride, pts->time ignored; every k-th ray: a larger xyz_stride)
  * is the end of a ray from `origin` - ONE sensor position for the whole call, in the map's frame - and an occupied voxel that enough
- * rays of the call passed through, and in which none of them ended, is SELECTED.  This version of the call counts what it selects and
- * leaves the map as it is: voxels_removed and points_removed say what a removal would take (DESIGN 8.4 says why the removal is not in
- * yet).  Every expression is fp64 without fused multiply-add, so a restatement (tests/map_carve_ref.py) reproduces the counts exactly:
+ * rays of the call passed through, and in which none of them ended, is SELECTED.  This call counts what it selects and
+ * leaves the map as it is: voxels_removed and points_removed say what a removal would take (wc_map_carve_remove, below, takes
+ * it).  Every expression is fp64 without fused multiply-add, so a restatement (tests/map_carve_ref.py) reproduces the counts exactly:
  *   ray           o = origin, P = (double)p, d = P - o, len2 = (d_x d_x + d_y d_y) + d_z d_z; k0 = floor(o / v), ke = floor(P / v) per
  *                 axis (VoxelLoc, true division); M = sum over the axes of |ke_a - k0_a|
  *   end mark      a point with finite coordinates and |ke_a| < 2^20 marks its end voxel ke, whether or not its ray is used
@@ -429,6 +431,28 @@ int wc_map_crop(wc_ctx *ctx, wc_map *m, const double lo[3], const double hi[3], 
  * this and do not remove it). */
 int wc_map_carve(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double origin[3], const wc_map_carve_params *params,
                  wc_map_carve_result *h_out);
+
+/* Removal in place.  A removed voxel's slot keeps a TOMBSTONE - a key word no voxel can have - instead of its key; the table
+ * keeps its size, and the next replacement of the table (a growth, a crop's, or a purge: a fresh table of the same size, made when live
+ * voxels + tombstones + the voxels a call may add would fill more than half of it) drops the tombstones.  After a removal the map is,
+ * through every call that reads it (wc_map_size, _export, _export_surfels, _export_state, _nearest, _nearest_plane, _linearize, _carve,
+ * _raycast, _merge as either side, _crop), bit for bit the map of the inserted points whose voxel was not removed.  A voxel that is
+ * removed and inserted again starts from zero sums.  wc_map_size reports the live voxels and their points; wc_map_info keeps its four
+ * words and their meaning (a purge is not a growth; the cumulative rejected count is untouched).
+ *
+ * wc_map_carve_remove: the definition, argument rules and errors are wc_map_carve's, word for word (reserved != 0 included); *h_out is
+ * what wc_map_carve would have returned on the same map, and the voxels it selects are then gone.  The call waits.  pts->n = 0 or an
+ * empty map: WC_OK, nothing removed. */
+int wc_map_carve_remove(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double origin[3], const wc_map_carve_params *params,
+                        wc_map_carve_result *h_out);
+/* Removes the voxels with the n indices d_keys (DEVICE, n x 3 int32 (kx, ky, kz), 4-aligned, in any order).
+ * h_out[3] = {voxels removed, points removed, keys that removed nothing}; the last counts the keys that are absent, the keys with
+ * |k_a| >= 2^20 on any axis, and the second and later copies of a key in the list - integer functions of the key set, independent of
+ * order, grid size (development option map_remove_groups) and schedule.  The call waits.  n = 0: WC_OK, nothing is launched and d_keys is
+ * not looked at.  WC_ERR_ARG: n > 2^31, a NULL or misaligned d_keys, a NULL h_out, a map of another context. */
+int wc_map_remove_keys(wc_ctx *ctx, wc_map *m, const int32_t *d_keys, uint64_t n, uint64_t h_out[3]);
+/* h_out[2] = {tombstones in the table now, purges so far}; host state, no wait */
+int wc_map_tombstones(wc_ctx *ctx, wc_map *m, uint64_t h_out[2]);
 
 /* Ray casting: what does the map put along a ray?  Every point p of `pts` (DEVICE pointers, the wc_points rules of wc_map_insert: either
  * stride, pts->time ignored) is the END of a ray from `origin` - ONE position for the whole call, in the map's frame; "in a direction up to

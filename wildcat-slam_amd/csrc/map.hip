@@ -3,7 +3,8 @@
 // far - the accumulated map the reference's RViz builds from /scan_in_imu_frame (lidar_odometry.cc:584-595).
 //
 // Table (one per wc_map): open addressing, linear probing, a power-of-two number of slots.
-//   keys[cap]     u64 packed voxel key (21 bits per axis, offset 2^20: ascending packed key = ascending (kx, ky, kz)); ~0 = empty
+//   keys[cap]     u64 packed voxel key (21 bits per axis, offset 2^20: ascending packed key = ascending (kx, ky, kz)); ~0 = empty,
+//                 ~0 - 1 = a tombstone: a removed voxel, a foreign key to every probe and skipped by every pass over the slots
 //   pay[cap][4]   i64 moments of the voxel's points: sum of q = round((p - r) * 2^32) per axis, count
 // r is the voxel centre rounded to 1/1024 m, a function of the key alone, so every point's q is a deterministic function of the point:
 // integer addition is associative, and the map is bit-identical however the same points are split across calls, ordered or
@@ -32,7 +33,10 @@
 //   k_map_carve    carving: one lane per ray from the call's origin to a point: the end voxel's word gets its mark, then the counted voxel
 //                   walk, eight steps ahead of the probes: keys, hashes and shell tests of a batch, its first-slot key loads issued
 //                   together, then the chains (read-only) and one no-return atomic add per occupied voxel seen through;
-//                   k_map_count<map_sel_carve> then counts the voxels the words select: wc_map_carve (which reports and does not remove yet)
+//                   k_map_count<map_sel_carve> then counts the voxels the words select: wc_map_carve (which reports and does not remove)
+//   k_map_erase<SEL>  k_map_count's pass that also turns the selected slots' keys into tombstones and takes them off the map's counters:
+//                   wc_map_carve_remove
+//   k_map_remove_keys  one lane per voxel index: probe, then a CAS of the key word to the tombstone: wc_map_remove_keys
 //   k_map_raycast  ray casting: the carve's ray and walk, read-only: one lane per ray, its M + 1 positions eight at a time - keys, hashes and
 //                   tested-flags of a batch, its first-slot key loads issued together, then the chains in ascending order up to the first
 //                   voxel with enough points - and one 48-byte wc_map_ray_hit per ray; no atomics but its four counters': wc_map_raycast
@@ -45,6 +49,8 @@
 // Growth policy: before an insert of n points the host takes an upper bound B of the occupied slots (the exact count of the last
 // completed insert's read-back plus every point inserted after it); when 2 (B + n) > cap the table is rehashed into the smallest power
 // of two >= 2 (B + n) slots.  The table is therefore at most half full at every probe, and an insert never runs out of room.
+// Tombstones hold slots: map_room.h takes the decision with them counted, and a table they alone have filled is replaced by a fresh
+// one of the same size (a purge).  A replacement of any kind drops them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -55,6 +61,7 @@
 
 #include "ctx.h"
 #include "dmath.h"
+#include "map_room.h"
 
 struct wc_map {
   wc_ctx *ctx = nullptr;
@@ -72,6 +79,8 @@ struct wc_map {
   uint64_t pts_since = 0;            // ... plus the points of every insert after it bound the occupied slots
   uint64_t pts_after_copy = 0;       // points of the inserts enqueued behind the pending copy
   uint64_t growths = 0;
+  uint64_t tombs = 0;                // tombstones in the table: exact, the removal calls wait and know what they removed
+  uint64_t purges = 0;               // replacements into a table of the same size, made to drop tombstones
   int cus = 256;
   wc_buf b_pairs[4], b_tmp, b_cnt;   // export scratch: keys in / out, slot indices in / out; rocPRIM temporary; compaction counter
   wc_buf b_lin;                      // wc_map_linearize: the tiles' partial sums and every level of their reduction (first use)
@@ -91,11 +100,13 @@ constexpr int kMapPts = 2;                         // consecutive points per lan
 constexpr int kMapMom = 9;                         // moment words per slot of a WC_MAP_MOMENTS map
 constexpr int kMapMomPts = 1;                      // points per lane of the moments insert (the alternative form: DESIGN, "Map surfels")
 constexpr unsigned long long kMapEmpty = ~0ull;
+constexpr unsigned long long kMapTomb = ~0ull - 1;  // a removed voxel: no packed key (63 bits), not empty; a slot is occupied iff key < kMapTomb
 constexpr double kMapUnit = 4294967296.0;          // fixed-point unit: 2^-32 m
 constexpr double kMapKeyLim = 1048576.0;           // |k| < 2^20
 constexpr int kMapKeyOff = 1 << 20;
 constexpr int kCtrOcc = 0, kCtrPts = 16, kCtrRej = 32, kCtrRejCall = 48, kCtrLost = 56;  // u64 word of each counter
-constexpr int kCtrFound = 64, kCtrKeepVox = 80, kCtrKeepPts = 96, kCtrWords = 112;      // query hits; a crop's kept voxels, points
+constexpr int kCtrFound = 64, kCtrKeepVox = 80, kCtrKeepPts = 96;                        // query hits; a crop's kept voxels, points
+constexpr int kCtrRmVox = 112, kCtrRmPts = 128, kCtrRmNone = 144, kCtrWords = 160;       // wc_map_remove_keys: voxels, points, keys that removed nothing
 constexpr int kNearThreads = 256;
 constexpr int kCompactChunk = 2048;                // slots per workgroup of k_map_compact
 constexpr int kCarveThreads = 256;
@@ -367,7 +378,7 @@ __global__ void __launch_bounds__(256) k_map_rehash(const unsigned long long *ok
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ocap) return;
   const unsigned long long key = okeys[i];
-  if (key == kMapEmpty) return;
+  if (key >= kMapTomb) return;  // (empty or a tombstone: tombstones never move, so every replacement purges them)
   if (!sel(key, i)) return;
   unsigned fresh = 0;
   const unsigned long long h = map_slot(keys, mask, key, fresh);
@@ -396,7 +407,7 @@ __global__ void __launch_bounds__(256) k_map_compact(const unsigned long long *k
     const uint64_t s = s0 + j;
     if (s >= cap) break;
     const unsigned long long key = keys[s];
-    if (key == kMapEmpty) continue;
+    if (key >= kMapTomb) continue;
     const unsigned at = atomicAdd(&n_local, 1u);
     sk[at] = key;
     ss[at] = (uint32_t)s;
@@ -769,11 +780,61 @@ __global__ void __launch_bounds__(256) k_map_count(const unsigned long long *key
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < cap; i += stride) {
     const unsigned long long key = keys[i];
     const bool selected = sel(key, i);
-    if (key == kMapEmpty || !selected) continue;
+    if (key >= kMapTomb || !selected) continue;
     ++nv;
     np += (unsigned long long)pay[4 * i + 3];
   }
   block_count<256>({nv, np}, {n_vox, n_pts});
+}
+
+// ---- removal in place (wc_map_carve_remove, wc_map_remove_keys: DESIGN 8.8) ----------------------------------------------------------
+// k_map_count's pass with a store: the key word of every occupied slot that `sel` selects becomes a tombstone (a plain 8-byte store: no
+// other lane of the launch reads a key, the selector looks at the carve's words), the voxel and its points are counted onto n_vox / n_pts
+// and taken off the map's counters (the negated workgroup sums, added).  Payload and moment words stay as they are: no probe reaches
+// them and a rehash does not carry them
+template <class SEL>
+__global__ void __launch_bounds__(256) k_map_erase(unsigned long long *keys, const long long *pay, uint64_t cap, SEL sel, unsigned long long *n_vox,
+                                                   unsigned long long *n_pts, unsigned long long *ctr) {
+  unsigned long long nv = 0, np = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < cap; i += stride) {
+    const unsigned long long key = keys[i];
+    const bool selected = sel(key, i);
+    if (key >= kMapTomb || !selected) continue;
+    keys[i] = kMapTomb;
+    ++nv;
+    np += (unsigned long long)pay[4 * i + 3];
+  }
+  block_count<256>({nv, np, 0ull - nv, 0ull - np}, {n_vox, n_pts, ctr + kCtrOcc, ctr + kCtrPts});
+}
+
+constexpr int kRemoveThreads = 256;
+// one lane per voxel index (kx, ky, kz), grid-strided: the range test, the read-only probe chain, then a CAS of the key word to the
+// tombstone - of the lanes that hold the same key exactly one sees it, the others (and an absent or out-of-range key) count as having
+// removed nothing; the count load comes behind a won CAS.  A lane that probes past a slot another lane is removing reads the key or the
+// tombstone: a foreign key either way
+__global__ void __launch_bounds__(kRemoveThreads) k_map_remove_keys(const int32_t *in, uint64_t n, unsigned long long *keys, const long long *pay,
+                                                                    unsigned long long mask, unsigned long long *ctr) {
+  unsigned long long nv = 0, np = 0, nn = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * kRemoveThreads;
+  for (uint64_t i = (uint64_t)blockIdx.x * kRemoveThreads + threadIdx.x; i < n; i += stride) {
+    const int kx = in[3 * i], ky = in[3 * i + 1], kz = in[3 * i + 2];
+    const bool ok = kx > -kMapKeyOff && kx < kMapKeyOff && ky > -kMapKeyOff && ky < kMapKeyOff && kz > -kMapKeyOff && kz < kMapKeyOff;
+    if (!ok) {
+      ++nn;
+      continue;
+    }
+    const unsigned long long key = map_pack(kx, ky, kz);
+    unsigned long long h = map_hash(key) & mask;
+    if (!map_find_from(keys, mask, key, h, keys[h]) || atomicCAS(&keys[h], key, kMapTomb) != key) {
+      ++nn;
+      continue;
+    }
+    ++nv;
+    np += (unsigned long long)pay[4 * h + 3];
+  }
+  block_count<kRemoveThreads>({nv, np, nn, 0ull - nv, 0ull - np},
+                              {ctr + kCtrRmVox, ctr + kCtrRmPts, ctr + kCtrRmNone, ctr + kCtrOcc, ctr + kCtrPts});
 }
 
 // ---- the exact state (wc_map_export_state, wc_map_absorb, wc_map_merge) -------------------------------------------------------------
@@ -863,7 +924,7 @@ __global__ void __launch_bounds__(kStateThreads) k_map_merge(const unsigned long
   unsigned fresh = 0;
   unsigned long long n_pts = 0;
   const unsigned long long key = i < scap ? skeys[i] : kMapEmpty;
-  if (key != kMapEmpty) {
+  if (key < kMapTomb) {
     const longlong2 *p = (const longlong2 *)(spay + 4 * i);
     const longlong2 p0 = p[0], p1 = p[1];
     const unsigned long long h = map_slot(keys, mask, key, fresh);
@@ -1089,11 +1150,6 @@ void map_free(wc_ctx *ctx, void *p) {
   (void)hipStreamSynchronize(ctx->stream);
   (void)hipFree(p);
 }
-uint64_t pow2_at_least(uint64_t x) {
-  uint64_t c = 1;
-  while (c < x) c <<= 1;
-  return c;
-}
 // a table of `cap` slots made empty (empty keys, zero payload; mom: NULL for a plain map), enqueued on the ctx stream
 int map_clear_table(wc_ctx *ctx, uint64_t cap, unsigned long long *keys, long long *pay, long long *mom) {
   WC_HIP(ctx, hipMemsetAsync(keys, 0xFF, cap * 8, ctx->stream));
@@ -1227,14 +1283,16 @@ extern "C" int wc_map_destroy(wc_ctx *ctx, wc_map *m) {
 
 namespace {
 // what precedes every call that may create up to n voxels (insert: n points; absorb: n records; merge: the source's voxels) - growth
-// (policy at the top of the file): at most half full at every probe of the call
+// (policy at the top of the file): at most half full at every probe of the call, tombstones counted as full slots.  The decision is
+// map_room.h's; a replacement of either kind drops the tombstones (k_map_rehash does not move them)
 int map_make_room(wc_ctx *ctx, wc_map *m, uint64_t n, const char *fn) {
-  const uint64_t need = 2 * (map_bound(m) + n);
-  if (need > m->cap) {
-    const uint64_t cap = pow2_at_least(need);
-    if (cap > ((uint64_t)1 << 32)) return wc_fail(ctx, WC_ERR_CAPACITY, "%s: the table would exceed 2^32 slots", fn);
+  uint64_t cap = 0;
+  const int what = map_room(m->cap, map_bound(m), m->tombs, n, &cap);
+  if (what == kMapRoomFull) return wc_fail(ctx, WC_ERR_CAPACITY, "%s: the table would exceed 2^32 slots", fn);
+  if (what != kMapRoomKeep) {
     WC_TRY(map_replace_table(ctx, m, cap, map_sel_all{}));
-    ++m->growths;
+    ++(what == kMapRoomGrow ? m->growths : m->purges);
+    m->tombs = 0;
   }
   return WC_OK;
 }
@@ -1428,6 +1486,7 @@ extern "C" int wc_map_clear(wc_ctx *ctx, wc_map *m) {
   WC_HIP(ctx, hipMemsetAsync(m->ctr, 0, kCtrWords * 8, ctx->stream));
   WC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (a pending counter copy lands before the host's bookkeeping is reset)
   m->occ_known = m->pts_since = m->pts_after_copy = 0;
+  m->tombs = 0;  // (the empty mark has overwritten them)
   m->ctr_pending = false;
   std::memset(m->h_ctr, 0, kCtrWords * 8);
   return WC_OK;
@@ -1662,6 +1721,7 @@ extern "C" int wc_map_crop(wc_ctx *ctx, wc_map *m, const double lo[3], const dou
   const uint64_t cap = pow2_at_least(2 * std::max<uint64_t>(kept, 1));
   if (kept != occ || cap != m->cap) {  // (otherwise the table already is what the crop would build)
     WC_TRY(map_replace_table(ctx, m, cap, box));
+    m->tombs = 0;  // (a replacement: the rehash leaves the tombstones behind)
     // the occupied-voxel and point counters become those of the kept voxels; rejected and growth counters stay
     WC_HIP(ctx, hipMemcpyAsync(m->ctr + kCtrOcc, m->ctr + kCtrKeepVox, 8, hipMemcpyDeviceToDevice, ctx->stream));
     WC_HIP(ctx, hipMemcpyAsync(m->ctr + kCtrPts, m->ctr + kCtrKeepPts, 8, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1674,18 +1734,21 @@ extern "C" int wc_map_crop(wc_ctx *ctx, wc_map *m, const double lo[3], const dou
 }
 
 // ---- carving free space along a sweep's rays (include/wildcat_hip.h: wc_map_carve) -------------------------------------------------
-extern "C" int wc_map_carve(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double origin[3], const wc_map_carve_params *params,
-                            wc_map_carve_result *h_out) {
+namespace {
+// wc_map_carve (remove = false: the map is left as it is) and wc_map_carve_remove: one definition, one ray kernel; the slot pass counts
+// (k_map_count) or counts and erases (k_map_erase)
+int map_carve(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double origin[3], const wc_map_carve_params *params, wc_map_carve_result *h_out,
+              bool remove, const char *fn) {
   wc_dev_guard dg_(ctx);
   const wc_map_carve_params *p = params;
   if (!map_ok(ctx, m) || !map_points_ok(pts) || !origin || !p || !h_out || pts->n >= ((uint64_t)1 << 31))
-    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (n < 2^31), or a map of another context", __func__);
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (n < 2^31), or a map of another context", fn);
   if (!(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2])) || !(p->min_range >= 0.0) ||
       !(p->max_range >= p->min_range) || p->shell > 8 || p->min_rays < 1 || p->max_steps < 1 || p->max_steps > 65536 || p->reserved != 0)
     return wc_fail(ctx, WC_ERR_ARG,
                    "%s: origin not finite, or params out of range (0 <= min_range <= max_range, shell <= 8, min_rays >= 1, 1 <= max_steps <= 65536, "
                    "reserved = 0)",
-                   __func__);
+                   fn);
   std::memset(h_out, 0, sizeof(*h_out));
   if (pts->n == 0) return WC_OK;  // (no ray, no end mark: nothing is removed and nothing is launched)
   map_ray_args A;
@@ -1706,15 +1769,60 @@ extern "C" int wc_map_carve(wc_ctx *ctx, wc_map *m, const wc_points *pts, const 
   if (ctx->dev.map_carve_groups > 0) grid = std::min<uint64_t>(blocks, (uint64_t)ctx->dev.map_carve_groups);  // (development option)
   k_map_carve<kCarveBatch><<<(unsigned)grid, kCarveThreads, 0, ctx->stream>>>(*pts, A, m->keys, m->cap - 1, words, cctr);
   WC_HIP(ctx, hipGetLastError());
-  // what the words select (this version reports it and leaves the map as it is: DESIGN 8.4)
+  // what the words select: counted, or counted and erased in the same pass
   const unsigned cgrid = (unsigned)std::min<uint64_t>((m->cap + 255) / 256, (uint64_t)8 * m->cus);
-  k_map_count<<<cgrid, 256, 0, ctx->stream>>>(m->keys, m->pay, m->cap, map_sel_carve{words, p->min_rays}, cctr + kCarveSelVox,
-                                              cctr + kCarveSelPts);
+  if (remove)
+    k_map_erase<<<cgrid, 256, 0, ctx->stream>>>(m->keys, m->pay, m->cap, map_sel_carve{words, p->min_rays}, cctr + kCarveSelVox,
+                                                cctr + kCarveSelPts, m->ctr);
+  else
+    k_map_count<<<cgrid, 256, 0, ctx->stream>>>(m->keys, m->pay, m->cap, map_sel_carve{words, p->min_rays}, cctr + kCarveSelVox,
+                                                cctr + kCarveSelPts);
   WC_HIP(ctx, hipGetLastError());
   WC_HIP(ctx, hipMemcpyAsync(m->h_carve, cctr, kCarveCtrWords * 8, hipMemcpyDeviceToHost, ctx->stream));
-  WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (remove)
+    WC_TRY(map_sync_counters(ctx, m));  // (the wait; the map's counters are exact again and a pending copy has landed)
+  else
+    WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   h_out->rays_used = m->h_carve[kCarveUsed], h_out->rays_skipped = m->h_carve[kCarveSkip], h_out->steps = m->h_carve[kCarveSteps];
   h_out->voxels_removed = m->h_carve[kCarveSelVox], h_out->points_removed = m->h_carve[kCarveSelPts];
+  if (remove) m->tombs += m->h_carve[kCarveSelVox];
+  return WC_OK;
+}
+}  // namespace
+
+extern "C" int wc_map_carve(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double origin[3], const wc_map_carve_params *params,
+                            wc_map_carve_result *h_out) {
+  return map_carve(ctx, m, pts, origin, params, h_out, false, __func__);
+}
+
+// ---- removal in place (include/wildcat_hip.h: wc_map_carve_remove, wc_map_remove_keys, wc_map_tombstones) ---------------
+extern "C" int wc_map_carve_remove(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double origin[3], const wc_map_carve_params *params,
+                                   wc_map_carve_result *h_out) {
+  return map_carve(ctx, m, pts, origin, params, h_out, true, __func__);
+}
+
+extern "C" int wc_map_remove_keys(wc_ctx *ctx, wc_map *m, const int32_t *d_keys, uint64_t n, uint64_t h_out[3]) {
+  wc_dev_guard dg_(ctx);
+  if (!map_ok(ctx, m) || !h_out) return wc_fail(ctx, WC_ERR_ARG, "%s: null argument or a map of another context", __func__);
+  h_out[0] = h_out[1] = h_out[2] = 0;
+  if (n == 0) return WC_OK;
+  if (!d_keys || (uintptr_t)d_keys % 4 || n > ((uint64_t)1 << 31))
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or misaligned keys, or n > 2^31", __func__);
+  WC_HIP(ctx, hipMemsetAsync(m->ctr + kCtrRmVox, 0, (kCtrRmNone - kCtrRmVox + 1) * 8, ctx->stream));
+  const uint64_t blocks = (n + kRemoveThreads - 1) / kRemoveThreads;
+  uint64_t grid = std::min<uint64_t>(blocks, (uint64_t)8 * m->cus);
+  if (ctx->dev.map_remove_groups > 0) grid = std::min<uint64_t>(blocks, (uint64_t)ctx->dev.map_remove_groups);  // (development option)
+  k_map_remove_keys<<<(unsigned)grid, kRemoveThreads, 0, ctx->stream>>>(d_keys, n, m->keys, m->pay, m->cap - 1, m->ctr);
+  WC_HIP(ctx, hipGetLastError());
+  WC_TRY(map_sync_counters(ctx, m));  // (the wait: the call's three counters travel with the map's)
+  h_out[0] = m->h_ctr[kCtrRmVox], h_out[1] = m->h_ctr[kCtrRmPts], h_out[2] = m->h_ctr[kCtrRmNone];
+  m->tombs += h_out[0];
+  return WC_OK;
+}
+
+extern "C" int wc_map_tombstones(wc_ctx *ctx, wc_map *m, uint64_t h_out[2]) {
+  if (!map_ok(ctx, m) || !h_out) return wc_fail(ctx, WC_ERR_ARG, "%s: null argument or a map of another context", __func__);
+  h_out[0] = m->tombs, h_out[1] = m->purges;
   return WC_OK;
 }
 

@@ -590,6 +590,27 @@ bool LidarOdometry::CarveMap(const float *xyz, size_t n, const double origin[3],
   if (result) *result = r;
   return true;
 }
+bool LidarOdometry::CarveMapRemove(const float *xyz, size_t n, const double origin[3], const wc_map_carve_params &params,
+                                   wc_map_carve_result *result) {
+  if (!map_ || !origin || (n && !xyz)) return false;
+  const DevBuf d_xyz(ctx_, n * 3 * sizeof(float));
+  const wc_points desc = UploadXyz(d_xyz, xyz, n);
+  wc_map_carve_result r;
+  if (wc_map_carve_remove(ctx_, map_, &desc, origin, &params, &r) != WC_OK) return false;  // (as in AlignToMap)
+  if (result) *result = r;
+  return true;
+}
+bool LidarOdometry::RemoveMapVoxels(const int32_t *keys, size_t n, uint64_t out[3]) {
+  if (!map_ || !out || (n && !keys)) return false;
+  const DevBuf d_keys(ctx_, n * 3 * sizeof(int32_t));
+  if (n) CheckCall(ctx_, "wc_h2d", wc_h2d(ctx_, d_keys.p, keys, n * 3 * sizeof(int32_t)));
+  return wc_map_remove_keys(ctx_, map_, (const int32_t *)d_keys.p, n, out) == WC_OK;
+}
+bool LidarOdometry::SetMapCarve(double range, uint32_t shell, uint32_t min_rays) {
+  if (!(range >= 0.0) || shell > 8 || min_rays < 1) return false;
+  config_.map_carve_range = range, config_.map_carve_shell = shell, config_.map_carve_min_rays = min_rays;
+  return true;
+}
 bool LidarOdometry::CastMap(const float *xyz, size_t n, const double origin[3], const wc_map_raycast_params &params, wc_map_ray_hit *hits,
                             wc_map_raycast_result *result) {
   if (!map_ || !origin || (n && (!xyz || !hits))) return false;
@@ -906,6 +927,11 @@ void LidarOdometry::AddLidarScan(const pcl::PointCloud<hilti_ros::Point>::Ptr &m
     if (!d_world) d_world = UndistortFinal(d_raw_sweep, n_sweep);
     const wc_points desc{d_world, (const char *)d_world + WC_HILTI_POINT_TIME_OFFSET, WC_HILTI_POINT_BYTES, WC_HILTI_POINT_BYTES, n_sweep};
     WC_CALL(wc_map_insert(ctx_, map_, &desc, nullptr));
+    if (config_.map_carve_range > 0.0) {  // the sweep's own rays from the sensor's position (the tf of FillOutputs) take what they contradict
+      const wc_map_carve_params cp{0.0, config_.map_carve_range, config_.map_carve_shell, config_.map_carve_min_rays, 4096, 0};
+      wc_map_carve_result cr;
+      WC_CALL(wc_map_carve_remove(ctx_, map_, &desc, samples_.back().pos, &cp, &cr));
+    }
     if (config_.map_keep_radius > 0.0) {  // the cube around this sweep's world -> imu_link origin (the tf of FillOutputs)
       const double *c = samples_.back().pos, r = config_.map_keep_radius;
       const double lo[3] = {c[0] - r, c[1] - r, c[2] - r}, hi[3] = {c[0] + r, c[1] + r, c[2] + r};

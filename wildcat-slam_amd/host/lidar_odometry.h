@@ -111,6 +111,14 @@ class LidarOdometry {
   // wc_map_carve for the rays origin -> each of n host points (xyz: n x 3 floats, the map's frame): *result (may be null) as the library
   // leaves it - what the rays select; the map is not modified.  false without a map or with arguments the library refuses
   bool CarveMap(const float *xyz, size_t n, const double origin[3], const wc_map_carve_params &params, wc_map_carve_result *result);
+  // CarveMap that also removes what it selects, in place (wc_map_carve_remove): *result is what CarveMap would have returned
+  bool CarveMapRemove(const float *xyz, size_t n, const double origin[3], const wc_map_carve_params &params, wc_map_carve_result *result);
+  // wc_map_remove_keys for n host voxel indices (keys: n x 3 int32): out[3] = voxels removed, points removed, keys that removed nothing.
+  // false - nothing touched - without a map, with out null, or with n > 0 and keys null
+  bool RemoveMapVoxels(const int32_t *keys, size_t n, uint64_t out[3]);
+  // config().map_carve_range / _shell / _min_rays (the per-sweep carve; range 0 = off); false - nothing changed - for a negative or NaN
+  // range, shell > 8 or min_rays < 1
+  bool SetMapCarve(double range, uint32_t shell, uint32_t min_rays);
   // wc_map_raycast for the rays origin -> each of n host points (xyz: n x 3 floats, the map's frame): hits receives n records - per ray the
   // first occupied voxel its walk tests -, *result (may be null) the call's counters; the map is not modified.  false without a map or with
   // arguments the library refuses.  Nothing in AddLidarScan calls it
@@ -125,7 +133,8 @@ class LidarOdometry {
   // moments (a file with moments loads into a map without: they are dropped)
   bool LoadMap(const std::string &path, bool merge = false);
   // wall time [ms] of the last completed sweep's map step (the undistortion when fill_outputs does not already form it, the insert's
-  // enqueue - its kernel runs behind on the stream - and, with map_keep_radius, the crop, which waits).  Not part of last_stage_ms()
+  // enqueue - its kernel runs behind on the stream -, with map_carve_range the carve, which waits, and, with map_keep_radius, the crop,
+  // which waits too).  Not part of last_stage_ms()
   double last_map_ms() const { return last_map_ms_; }
   LioConfig &config() { return config_; }
   void ApplyConfig();  // push config() changes (quirks, extraction arithmetic, iteration cap, extrinsics) into the device context

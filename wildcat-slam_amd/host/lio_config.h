@@ -1,6 +1,7 @@
 // lio_config.h — the reference's hard-coded configuration (src/odometry/lio_config.h:8-46), values unchanged.
 #pragma once
 #include <cmath>
+#include <cstdint>
 
 struct LioConfig {
   // IMU noise model (lio_config.h:10-14)
@@ -51,4 +52,12 @@ struct LioConfig {
   // the map also accumulates every voxel's second moments (wc_map_create_ex, WC_MAP_MOMENTS): ExportMapSurfels and QueryMapPlanes answer
   // with the plane through a voxel's points.  false (default) = the plain map: nothing more allocated or launched.  Needs map_voxel_size > 0
   bool map_surfels = false;
+  // not in the reference: per-sweep carving of the map (wc_map_carve_remove).  After a sweep's insert, the occupied voxels that at least
+  // map_carve_min_rays of the rays sensor -> point (the points the insert took; the sensor: the sweep's world -> imu_link origin, the tf of
+  // last_outputs()) no longer than map_carve_range [m] pass through, farther than map_carve_shell voxels from the ray's end, and in which no
+  // point of the sweep lies, are removed in place - before the keep-radius crop.  0 (default) = off: nothing allocated or launched.
+  // Needs map_voxel_size > 0.  Set through LidarOdometry::SetMapCarve
+  double map_carve_range = 0.0;
+  uint32_t map_carve_shell = 1;
+  uint32_t map_carve_min_rays = 2;
 };

@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "../csrc/extract_plan.h"
+#include "../csrc/map_room.h"
 #include "cubic_bspline.h"
 #include "histogram.h"
 #include "imu_resampler.h"
@@ -231,6 +232,25 @@ int wc_odom_map_linearize(void *h, const float *xyz, uint64_t n, const double T[
 // LidarOdometry::CarveMap for n host points (n x 3 floats); 1 = done, 0 = no map or refused arguments
 int wc_odom_map_carve(void *h, const float *xyz, uint64_t n, const double origin[3], const wc_map_carve_params *params, wc_map_carve_result *result) {
   return params && ((LidarOdometry *)h)->CarveMap(xyz, n, origin, *params, result) ? 1 : 0;
+}
+// LidarOdometry::CarveMapRemove, RemoveMapVoxels (keys: n x 3 int32 on the host) and SetMapCarve; 1 = done, 0 = no map or refused arguments
+int wc_odom_map_carve_remove(void *h, const float *xyz, uint64_t n, const double origin[3], const wc_map_carve_params *params,
+                             wc_map_carve_result *result) {
+  return params && ((LidarOdometry *)h)->CarveMapRemove(xyz, n, origin, *params, result) ? 1 : 0;
+}
+int wc_odom_map_remove_keys(void *h, const int32_t *keys, uint64_t n, uint64_t out3[3]) {
+  return ((LidarOdometry *)h)->RemoveMapVoxels(keys, n, out3) ? 1 : 0;
+}
+// LioConfig::map_carve_range / _shell / _min_rays; returns 0, or WC_ERR_ARG for a negative or NaN range, shell > 8 or min_rays < 1
+int wc_odom_set_map_carve(void *h, double range, uint32_t shell, uint32_t min_rays) {
+  return ((LidarOdometry *)h)->SetMapCarve(range, shell, min_rays) ? 0 : WC_ERR_ARG;
+}
+// csrc/map_room.h without a GPU: 0 = keep, 1 = grow, 2 = purge (*new_cap: the table's slots afterwards), negative: beyond 2^32 slots
+int wc_host_map_room(uint64_t cap, uint64_t live_bound, uint64_t tombs, uint64_t n, uint64_t *new_cap) {
+  uint64_t c = cap;
+  const int rc = map_room(cap, live_bound, tombs, n, &c);
+  if (new_cap) *new_cap = c;
+  return rc;
 }
 // LidarOdometry::CastMap for n host points (n x 3 floats) into n host records; 1 = done, 0 = no map or refused arguments
 int wc_odom_map_raycast(void *h, const float *xyz, uint64_t n, const double origin[3], const wc_map_raycast_params *params, wc_map_ray_hit *hits,

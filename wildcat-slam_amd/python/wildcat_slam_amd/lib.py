@@ -707,9 +707,45 @@ class PointMap:
     def carve(self, points, origin, max_range, min_range=0.0, shell=1, min_rays=1, max_steps=4096):
         """POINT records or an (n, 3) float32 array (uploaded for the call): the voxels that at least min_rays of the rays origin -> point
         pass through, farther than `shell` voxels from the ray's end, and in which no point of the call lies, are selected and counted
-        (wc_map_carve; this version does not remove them) -> dict(rays_used, rays_skipped, steps, voxels_removed, points_removed)"""
+        (wc_map_carve; it does not remove them: carve_remove() does) -> dict(rays_used, rays_skipped, steps, voxels_removed, points_removed)"""
         with self._uploaded(points) as (desc, _):
             return self.carve_device(desc, origin, map_carve_params(max_range, min_range, shell, min_rays, max_steps))
+
+    def carve_remove_device(self, desc, origin, params):
+        """carve_device() that also removes what it selects, in place (wc_map_carve_remove) -> what carve_device() would have returned"""
+        o = (C.c_double * 3)(*[float(x) for x in origin])
+        res = R.MapCarveResult()
+        self.ctx._ck(self.lib.wc_map_carve_remove(self.ctx.h, self.h, C.byref(desc), o, C.byref(params), C.byref(res)))
+        return _carve_dict(res)
+
+    def carve_remove(self, points, origin, max_range, min_range=0.0, shell=1, min_rays=1, max_steps=4096):
+        """carve() that also removes the voxels it selects: their slots keep a tombstone until the table is next replaced
+        (wc_map_carve_remove) -> the dict carve() would have returned on the same map"""
+        with self._uploaded(points) as (desc, _):
+            return self.carve_remove_device(desc, origin, map_carve_params(max_range, min_range, shell, min_rays, max_steps))
+
+    def remove_device(self, d_keys, n):
+        """n voxel indices ((n, 3) int32) already in HBM (wc_map_remove_keys) -> dict(voxels_removed, points_removed, keys_unused)"""
+        out = (C.c_uint64 * 3)()
+        self.ctx._ck(self.lib.wc_map_remove_keys(self.ctx.h, self.h, C.c_void_p(d_keys.ptr if d_keys else 0), C.c_uint64(int(n)), out))
+        return dict(zip(("voxels_removed", "points_removed", "keys_unused"), [int(x) for x in out]))
+
+    def remove(self, keys):
+        """the voxels with these indices ((n, 3) int32, any order, uploaded for the call) removed in place -> dict(voxels_removed,
+        points_removed, keys_unused: keys that are absent, out of the key range, or second and later copies of a key)"""
+        keys = np.ascontiguousarray(keys, np.int32).reshape(-1, 3)
+        d = self.ctx.to_device(keys) if len(keys) else None
+        try:
+            return self.remove_device(d, len(keys))
+        finally:
+            if d:
+                d.free()
+
+    def tombstones(self):
+        """-> (tombstones in the table now, purges so far) (wc_map_tombstones; host state, no wait)"""
+        out = (C.c_uint64 * 2)()
+        self.ctx._ck(self.lib.wc_map_tombstones(self.ctx.h, self.h, out))
+        return int(out[0]), int(out[1])
 
     def raycast_device(self, desc, origin, params, d_hits, want_result=True):
         """points already in HBM (a wc_points descriptor) as the ends of rays from origin -> MAP_RAY_HIT records in d_hits
@@ -1074,6 +1110,32 @@ class Odometry:
         if not self.lib.wc_odom_map_carve(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), o, C.byref(params), C.byref(res)):
             return None
         return _carve_dict(res)
+
+    def map_carve_remove(self, xyz, origin, max_range, min_range=0.0, shell=1, min_rays=1, max_steps=4096):
+        """map_carve() that also removes what it selects from the facade's map (LidarOdometry::CarveMapRemove) -> the dict map_carve()
+        would have returned, or None without a map or with arguments the library refuses"""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        o = (C.c_double * 3)(*[float(x) for x in origin])
+        params, res = map_carve_params(max_range, min_range, shell, min_rays, max_steps), R.MapCarveResult()
+        if not self.lib.wc_odom_map_carve_remove(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), o, C.byref(params), C.byref(res)):
+            return None
+        return _carve_dict(res)
+
+    def map_remove(self, keys):
+        """wc_map_remove_keys of the facade's map for the voxel indices keys ((n, 3) int32) (LidarOdometry::RemoveMapVoxels)
+        -> dict(voxels_removed, points_removed, keys_unused), or None without a map"""
+        keys = np.ascontiguousarray(keys, np.int32).reshape(-1, 3)
+        out = (C.c_uint64 * 3)()
+        if not self.lib.wc_odom_map_remove_keys(self.h, R.ptr(keys) if len(keys) else None, C.c_uint64(len(keys)), out):
+            return None
+        return dict(zip(("voxels_removed", "points_removed", "keys_unused"), [int(x) for x in out]))
+
+    def set_map_carve(self, max_range, shell=1, min_rays=2):
+        """LioConfig::map_carve_range / _shell / _min_rays: after every sweep's insert the sweep's own rays remove the voxels they
+        contradict (wc_map_carve_remove from the sensor's position); max_range 0 = off"""
+        rc = self.lib.wc_odom_set_map_carve(self.h, C.c_double(max_range), C.c_uint32(int(shell)), C.c_uint32(int(min_rays)))
+        if rc != 0:
+            raise WildcatError(rc, "wc_odom_set_map_carve(%r, %r, %r)" % (max_range, shell, min_rays))
 
     def map_raycast(self, xyz, origin, max_range, min_range=0.0, first_step=0, end_shell=0, min_points=1, max_steps=4096):
         """wc_map_raycast of the facade's map with the rows of xyz ((n, 3) float32) as the ends of rays from origin (LidarOdometry::CastMap)
