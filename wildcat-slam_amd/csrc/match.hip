@@ -102,6 +102,7 @@ constexpr uint32_t kNone = 0xFFFFFFFFu;
 struct MatchParams {
   double cs, as;        // centre / angular scale
   double time_min, ang_max, dist_max;
+  double cos_min;             // the angle gate on the cosine (match_cos_gate below): a dot product in [-1, cos_min) is rejected
   double cos_acc, plane_acc;  // the EARLY walk (match_tree.inc): accept a candidate when cos >= cos_acc and the plane distance <= plane_acc - ...
   int k, same_set;
 };
@@ -308,6 +309,63 @@ struct MatchPeerGuard {
   }
 };
 
+// The angle gate on the cosine.  The reference rejects a candidate when std::acos(d) > ang_max, d the dot product of the two normals
+// (cc:29, surfel.h:105-107).  The device's acos is not the host's: next to ang_max the two decided differently (found by
+// tests/test_match_gates_gpu.py at ang_max = 60, 90 and 100 deg, on cosines one to three doubles from the threshold; from 30 deg on a
+// step of the cosine is a step of the angle or less).  So the host finds c*, the smallest double whose std::acos is <= ang_max, by
+// bisection over the doubles of [-1, 1], and the kernel rejects d in [-1, c*): the reference's decision for every d, given that
+// std::acos decides monotonically - checked over 2 000 doubles on either side of c*, the call fails otherwise.  A dot product outside
+// [-1, 1], or NaN, has a NaN angle, which the reference lets pass: so does !(d < c* && d >= -1).  ang_max < 0 rejects all of [-1, 1]
+// (c* just above 1); ang_max >= pi, or NaN, rejects nothing (c* = -1).  Kept per thread for the last ang_max: the search for c* is
+// ~4 000 calls of acos, a tenth of a short search.
+static int64_t dbl_ord(double x) {  // the doubles in order: an integer that grows with x
+  int64_t i;
+  memcpy(&i, &x, 8);
+  return i >= 0 ? i : -(i & INT64_MAX);
+}
+static double dbl_unord(int64_t k) {
+  const int64_t i = k >= 0 ? k : ((-k) | INT64_MIN);
+  double x;
+  memcpy(&x, &i, 8);
+  return x;
+}
+static bool match_cos_gate(double ang, double *c_out) {
+  struct Last {
+    uint64_t bits;
+    double c;
+    bool ok, have;
+  };
+  static thread_local Last last{0, 0.0, false, false};
+  uint64_t bits;
+  memcpy(&bits, &ang, 8);
+  if (!last.have || last.bits != bits) {
+    double c;
+    bool ok = true;
+    if (!(std::acos(-1.0) > ang)) {
+      c = -1.0;
+    } else if (ang < 0.0) {
+      c = std::nextafter(1.0, 2.0);
+    } else {
+      int64_t lo = dbl_ord(-1.0), hi = dbl_ord(1.0);  // acos(lo) > ang >= acos(hi)
+      while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (std::acos(dbl_unord(mid)) <= ang)
+          hi = mid;
+        else
+          lo = mid;
+      }
+      c = dbl_unord(hi);
+      for (int64_t j = 1; j <= 2000 && ok; ++j) {
+        if (hi - j >= dbl_ord(-1.0)) ok = ok && std::acos(dbl_unord(hi - j)) > ang;
+        if (hi + j <= dbl_ord(1.0)) ok = ok && std::acos(dbl_unord(hi + j)) <= ang;
+      }
+    }
+    last = Last{bits, c, ok, true};
+  }
+  *c_out = last.c;
+  return last.ok;
+}
+
 // scratch lives in ctx->b_misc[1..7] slots to avoid another state struct.  want_shard: the call is a collective of the ctx's
 // communicator (wc_match_sharded) - every rank makes it with the same replicated arguments
 static int match_impl(wc_ctx *ctx, const wc_surfel *d_q_surf, const wc_pose *d_q_pose, uint64_t nq_, const wc_surfel *d_t_surf,
@@ -363,8 +421,16 @@ static int match_impl(wc_ctx *ctx, const wc_surfel *d_q_surf, const wc_pose *d_q
   M.cs = P.center_scale, M.as = P.angular_scale;
   M.time_min = P.time_diff_min, M.ang_max = P.angular_scale, M.dist_max = P.surfel_dist_max;
   M.k = P.knn_k, M.same_set = same_set ? 1 : 0;
-  // (margins of the early acceptance: 1e-9 in the angle and relative 1e-9 in the distance, against ~1e-15 between the walk's operands and the gates')
-  M.cos_acc = M.ang_max > 1e-8 ? std::cos(std::min(M.ang_max, 3.141592653589793) - 1e-9) + 1e-12 : 2.0;
+  if (!match_cos_gate(M.ang_max, &M.cos_min))
+    return wc_fail(ctx, WC_ERR_NUMERIC, "wc_match: acos does not decide monotonically next to angular_scale = %.17g", M.ang_max);
+  // Margins of the early acceptance (match_tree.inc).  The walk forms the cosine as dn as as and the plane distance as fabs(dp) as cs
+  // from the FEATURES, the gates form them from the world centres and normals.  Cosine: three more roundings of values <= 1 / as^2 in
+  // magnitude - a few 1e-16 -, against 1e-9 rad in the angle (sin(ang_max) 1e-9 in the cosine), never below the gate's own c*, plus
+  // 1e-12.  Plane distance: the features' centres are the world centres divided by cs, off by half an ulp of a number <= qmax each
+  // unless cs is a power of two, and so is their difference; weighted with the normal and summed that is <= 3 x 2.3e-16 qmax cs in
+  // metres, and the roundings of the sum itself are relative 1e-15 - against 1e-9 qmax cs (applied in the walk, which knows qmax), a
+  // relative 1e-9 and 1e-12.  tests/match_gates.py puts rejected candidates inside each of these margins (its "band" cases).
+  M.cos_acc = M.ang_max > 1e-8 ? std::max(std::cos(std::min(M.ang_max, 3.141592653589793) - 1e-9), M.cos_min) + 1e-12 : 2.0;
   M.plane_acc = M.dist_max * (1.0 - 1e-9) - 1e-12;
   // 3. exact k-NN + gates.  Same-set queries are processed in the order of the tree's leaves (the sorted target permutation), so
   // that the groups of a wavefront walk the same nodes; queries of another set in their own order.  (Rounds 4 - 5 sorted those by the

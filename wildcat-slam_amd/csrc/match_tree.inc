@@ -898,7 +898,8 @@ __global__ void __launch_bounds__(NT, 6) k_knn_tree_group(const wc_surfel *q_sur
       const double *w = tworld + (size_t)c * 7;
       bool p = !(fabs(w[6] - tq) < M.time_min);
       const V3 nc = mk3(w[3], w[4], w[5]);
-      p = p && !(acos(dot(nq_w, nc)) > M.ang_max);
+      const double dc = dot(nq_w, nc);
+      p = p && !(dc < M.cos_min && dc >= -1.0);  // acos(dc) > ang_max as the HOST's acos decides it (match.hip: match_cos_gate); NaN passes
       p = p && !(fabs(dot(nq_w, cq - mk3(w[0], w[1], w[2]))) > M.dist_max);
       pass[sl] = p;
     }
