@@ -540,6 +540,33 @@ int wc_map_absorb(wc_ctx *ctx, wc_map *m, const wc_map_voxel *d_vox, const int64
  * doubles, or when dst has moments and src has none (a moments src merges into a plain dst, the moments are dropped).  Waits once, to
  * read src's exact voxel count for dst's growth bound; the merge itself is enqueued on the ctx stream. */
 int wc_map_merge(wc_ctx *ctx, wc_map *dst, wc_map *src);
+/* A coarser level, exactly.  *out becomes a NEW map of voxel size V = (double)factor * v (one fp64 product; v = src's voxel size) that
+ * holds the voxels of src gathered factor^3 to one; src is not modified.  With r(k, v) = rint((k + 0.5) * v * 1024) / 1024, the reference
+ * point of wc_map_export_state:
+ *   key     K_a = floor(k_a / factor) per axis, toward minus infinity for negative k_a; |K| < 2^20 follows from |k| < 2^20
+ *   shift   D_a = (r(k_a, v) - r(K_a, V)) * 2^32: both reference points lie on the 2^-10 m grid below 2^23 m, so the difference and the
+ *           product are exact in fp64 and D_a is an integer multiple of 2^22;  E_a = D_a >> 16, exact
+ *   words   of a fine voxel (count n, sums S, moment words U, M), re-based in 64-bit two's-complement arithmetic:
+ *             S'_a = S_a + n D_a,   U'_a = U_a + n E_a,   M'_ab = M_ab + (E_a U_b + E_b U_a) + n E_a E_b     (U: the fine voxel's)
+ *           because a point's q' = q + D and u' = (q + D + 2^15) >> 16 = u + E.  The re-based words are added to voxel K of the new map,
+ *           which is created where it is new.  Integer sums: no order matters
+ *   flags   0: a plain map (a WC_MAP_MOMENTS src drops its moments); WC_MAP_MOMENTS: needs a WC_MAP_MOMENTS src, else WC_ERR_ARG; any
+ *           other bit: WC_ERR_ARG
+ *   limits  factor >= 1 (factor 1: an exact copy, D = 0); V <= 4.0; a NULL argument or a map of another context: WC_ERR_ARG.  A src that
+ *           holds more points in total (wc_map_size) than ONE voxel of the result may - 2^28 with WC_MAP_MOMENTS in flags, 2^30 without -
+ *           is WC_ERR_CAPACITY: the simple sufficient condition under which no coarse voxel overflows.  *out is untouched by every error
+ *   table   removed voxels (tombstones) are skipped; the new table has the slots wc_map_merge gives an empty destination: the smallest
+ *           power of two >= twice src's exact live voxel count, whose read-back is the call's one wait; the kernel is enqueued on the
+ *           ctx stream.  The result's voxel and point counts are those of its content; an empty src gives an empty map
+ * Through every call that reads a map the result is, bit for bit, the map wc_map_absorb builds from the re-based records; and bit for
+ * bit the map of src's points inserted at V whenever every point p has floor((double)p / V) == floor(floor((double)p / v) / factor) on
+ * every axis.  That condition always holds in exact arithmetic, and in fp64 for every p when v is a power of two (the divisions are then
+ * exact).  For another v it can fail only for a point whose quotient rounds onto an integer: a point on a voxel face to within rounding
+ * (measured with points placed on the faces on purpose, tests/test_map_coarsen_ref.py: v = 0.1, factor 3: 333 of 3000; v = 0.1, factor 2
+ * and v = 0.2, factor 5: none; uniformly random float points: none of 17 000 at any tested v).  Such a point is counted in the neighbouring coarse voxel, and its
+ * offset from that voxel's reference point is still exact.  The result is an ordinary map: it grows, merges (with a map of voxel size
+ * bitwise V) and is destroyed like any other. */
+int wc_map_coarsen(wc_ctx *ctx, wc_map *src, uint32_t factor, uint32_t flags, wc_map **out);
 
 /* Plane query.  The voxel is chosen as wc_map_nearest chooses it (candidates, distance, ties, max_dist, argument checks), and the first
  * 40 bytes of a wc_map_plane_hit are that call's wc_map_hit, except that bit 1 of flags is set iff a voxel was found, its
@@ -592,6 +619,17 @@ int wc_map_linearize(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double 
  * Python binding's default is 1e-9.  WC_ERR_ARG: max_iterations < 1, tol_rot / tol_trans / min_pivot not > 0, min_used < 6, and
  * whatever wc_map_linearize refuses. */
 int wc_map_align(wc_ctx *ctx, wc_map *m, const wc_points *pts, double T_io[12], const wc_map_align_opts *opts, wc_map_align_summary *h_out);
+/* Coarse to fine.  levels[0] runs first - the caller passes the coarsest map first -, and level l is exactly one
+ *   wc_map_align(ctx, levels[l], pts, T_io, &opts[l], &h_out[l])
+ * from the pose level l - 1 left (opts and h_out: n_levels records each).  A level that ends with termination 1 or 2 leaves T_io as
+ * wc_map_align defines, and the next level runs.  The levels need not be related to one another (wc_map_coarsen makes related ones: a
+ * plane is searched in the 27 voxels around a point, so a level of voxel size V catches offsets of the order of V).
+ * 1 <= n_levels <= 8.  The arguments of ALL levels are checked before any work, and WC_ERR_ARG then leaves T_io and h_out untouched: a
+ * NULL argument, a non-finite entry of T_io, and per level everything wc_map_align and wc_map_linearize refuse (a map of another
+ * context or one created without WC_MAP_MOMENTS, the options' ranges, reserved != 0).  Returns WC_OK otherwise, unless a level's call
+ * itself fails (a pose that sends a finite point to a non-finite one: that level's error, the levels before it have run). */
+int wc_map_align_pyramid(wc_ctx *ctx, wc_map *const *levels, uint32_t n_levels, const wc_points *pts, double T_io[12],
+                         const wc_map_align_opts *opts, wc_map_align_summary *h_out);
 
 #ifdef __cplusplus
 }

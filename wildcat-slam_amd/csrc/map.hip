@@ -43,6 +43,8 @@
 //   k_map_state    state export: one lane per sorted voxel: the slot's integer sums themselves -> wc_map_voxel (+ nine moment words)
 //   k_map_absorb   state records added back by key (map_slot, then four / thirteen no-return atomic adds): wc_map_absorb
 //   k_map_merge    the same for every occupied slot of another map's table: wc_map_merge
+//   k_map_coarsen  the merge's pass with the key divided and the sums re-based to the coarse voxel's reference point in registers: the
+//                   new map of wc_map_coarsen, factor^3 voxels to one
 // Shared pieces: map_voxel_of (the voxel-index rule, host and device), map_find_from (the read-only probe chain), block_count (a
 // workgroup's counters), map_points_ok (a wc_points argument), map_replace_table (new table, rehash, free the old one), map_ray_of /
 // map_ray_begin / map_ray_step (a ray's setup and the step rule of its voxel walk: the carve and the ray cast)
@@ -842,21 +844,29 @@ constexpr int kStateThreads = 256;
 constexpr unsigned kStateMaxCount = 1u << 30;  // a record's count: 1 .. 2^30 (the plain map's limit per voxel)
 // the four (thirteen) integer sums of one voxel added to slot h: no-return 64-bit atomics (the slot may hold the key already, and two
 // records of a call may carry the same key); integers, so no order matters
-template <bool MOM>
-__device__ __forceinline__ void map_add_sums(long long *pay, long long *mom, unsigned long long h, unsigned long long sx, unsigned long long sy,
-                                             unsigned long long sz, unsigned long long cnt, const long long *src_mom) {
+// (the two halves take register values: k_map_coarsen adds words it has re-based, map_add_sums words it loads)
+__device__ __forceinline__ void map_add_pay(long long *pay, unsigned long long h, unsigned long long sx, unsigned long long sy, unsigned long long sz,
+                                            unsigned long long cnt) {
   unsigned long long *p = (unsigned long long *)pay + 4 * h;
   atomicAdd(p + 0, sx);
   atomicAdd(p + 1, sy);
   atomicAdd(p + 2, sz);
   atomicAdd(p + 3, cnt);
+}
+__device__ __forceinline__ void map_add_mom(long long *mom, unsigned long long h, const unsigned long long (&w)[kMapMom]) {
+  unsigned long long *pm = (unsigned long long *)mom + kMapMom * h;
+#pragma unroll
+  for (int j = 0; j < kMapMom; ++j) atomicAdd(pm + j, w[j]);
+}
+template <bool MOM>
+__device__ __forceinline__ void map_add_sums(long long *pay, long long *mom, unsigned long long h, unsigned long long sx, unsigned long long sy,
+                                             unsigned long long sz, unsigned long long cnt, const long long *src_mom) {
+  map_add_pay(pay, h, sx, sy, sz, cnt);
   if constexpr (MOM) {
-    unsigned long long *pm = (unsigned long long *)mom + kMapMom * h;
     unsigned long long w[kMapMom];
 #pragma unroll
     for (int j = 0; j < kMapMom; ++j) w[j] = (unsigned long long)src_mom[j];  // (the nine loads leave before the first atomic)
-#pragma unroll
-    for (int j = 0; j < kMapMom; ++j) atomicAdd(pm + j, w[j]);
+    map_add_mom(mom, h, w);
   }
 }
 
@@ -933,6 +943,63 @@ __global__ void __launch_bounds__(kStateThreads) k_map_merge(const unsigned long
                         MOM ? smom + kMapMom * i : nullptr);
       n_pts = (unsigned long long)p1.y;
     } else {  // (cannot happen: the growth policy left room for every voxel of the source)
+      atomicAdd(ctr + kCtrLost, 1ull);
+    }
+  }
+  block_count<kStateThreads>({(unsigned long long)fresh, n_pts}, {ctr + kCtrOcc, ctr + kCtrPts});
+}
+
+// coarsen (include/wildcat_hip.h: wc_map_coarsen): one lane per slot of the source table, as k_map_merge - but the key becomes
+// K = floor(k / f) per axis and the sums are re-based from r(k, v) to r(K, V) in registers before they are added: the payload (two 16-byte
+// loads) and the nine moment words are loaded before the first atomic, then one map_slot probe and four (thirteen) no-return atomic adds.
+// Up to f^3 lanes add into one voxel; they sit at hashed slots of the source, so a workgroup has nothing to gather first.  D_a =
+// (r(k_a, v) - r(K_a, V)) 2^32 is exact in fp64 (both on the 2^-10 m grid, below 2^23 m) and a multiple of 2^22, E_a = D_a >> 16.  All
+// integer arithmetic is unsigned 64-bit, which wraps as the table's two's-complement adds do.  MOM: the destination holds moments (then the
+// source does)
+template <bool MOM>
+__global__ void __launch_bounds__(kStateThreads) k_map_coarsen(const unsigned long long *skeys, const long long *spay, const long long *smom, uint64_t scap,
+                                                               double v, double V, int f, unsigned long long *keys, long long *pay, long long *mom,
+                                                               unsigned long long mask, unsigned long long *ctr) {
+  const uint64_t i = (uint64_t)blockIdx.x * kStateThreads + threadIdx.x;
+  unsigned fresh = 0;
+  unsigned long long n_pts = 0;
+  const unsigned long long key = i < scap ? skeys[i] : kMapEmpty;
+  if (key < kMapTomb) {
+    const longlong2 *p = (const longlong2 *)(spay + 4 * i);
+    const longlong2 p0 = p[0], p1 = p[1];
+    unsigned long long w[kMapMom];
+    if constexpr (MOM) {
+#pragma unroll
+      for (int j = 0; j < kMapMom; ++j) w[j] = (unsigned long long)smom[kMapMom * i + j];
+    }
+    int K[3];
+    unsigned long long D[3], E[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const int k = map_unpack(key, a);
+      K[a] = k / f - (k % f < 0 ? 1 : 0);  // floor(k / f): toward minus infinity
+      const long long d = (long long)((map_ref(k, v) - map_ref(K[a], V)) * kMapUnit);
+      D[a] = (unsigned long long)d;
+      E[a] = (unsigned long long)(d >> 16);
+    }
+    const unsigned long long n = (unsigned long long)p1.y;
+    const unsigned long long sx = (unsigned long long)p0.x + n * D[0], sy = (unsigned long long)p0.y + n * D[1],
+                             sz = (unsigned long long)p1.x + n * D[2];
+    if constexpr (MOM) {
+      // M'_ab = M_ab + E_a U_b + E_b U_a + n E_a E_b with the source's U, then U'_a = U_a + n E_a
+      const unsigned long long U[3] = {w[0], w[1], w[2]};
+      constexpr int A[6] = {0, 0, 0, 1, 1, 2}, B[6] = {0, 1, 2, 1, 2, 2};
+#pragma unroll
+      for (int e = 0; e < 6; ++e) w[3 + e] += E[A[e]] * U[B[e]] + E[B[e]] * U[A[e]] + n * E[A[e]] * E[B[e]];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) w[a] = U[a] + n * E[a];
+    }
+    const unsigned long long h = map_slot(keys, mask, map_pack(K[0], K[1], K[2]), fresh);
+    if (h != kMapEmpty) {
+      map_add_pay(pay, h, sx, sy, sz, n);
+      if constexpr (MOM) map_add_mom(mom, h, w);
+      n_pts = n;
+    } else {  // (cannot happen: the table has room for every voxel of the source)
       atomicAdd(ctr + kCtrLost, 1ull);
     }
   }
@@ -1479,6 +1546,42 @@ extern "C" int wc_map_merge(wc_ctx *ctx, wc_map *dst, wc_map *src) {
   return map_added(ctx, dst, n, nullptr);
 }
 
+// ---- a coarser level (include/wildcat_hip.h: wc_map_coarsen) ----------------------------------------------------------
+extern "C" int wc_map_coarsen(wc_ctx *ctx, wc_map *src, uint32_t factor, uint32_t flags, wc_map **out) {
+  wc_dev_guard dg_(ctx);
+  const bool mom = (flags & WC_MAP_MOMENTS) != 0;
+  if (!map_ok(ctx, src) || !out || factor < 1 || !((double)factor * src->voxel <= 4.0) || (flags & ~(uint32_t)WC_MAP_MOMENTS) || (mom && !src->mom))
+    return wc_fail(ctx, WC_ERR_ARG,
+                   "%s: null argument, a map of another context, factor < 1, factor * voxel > 4.0, unknown flags, or WC_MAP_MOMENTS with a source "
+                   "created without it",
+                   __func__);
+  const double V = (double)factor * src->voxel;  // one fp64 product
+  WC_TRY(map_sync_counters(ctx, src));           // (the wait: the source's exact voxel count bounds the result's, its point count is checked)
+  const uint64_t n = src->h_ctr[kCtrOcc], limit = (uint64_t)1 << (mom ? 28 : 30);
+  if (src->h_ctr[kCtrPts] > limit)
+    return wc_fail(ctx, WC_ERR_CAPACITY, "%s: the source holds %llu points, one voxel of the result at most %llu", __func__,
+                   (unsigned long long)src->h_ctr[kCtrPts], (unsigned long long)limit);
+  wc_map *m = nullptr;
+  WC_TRY(wc_map_create_ex(ctx, V, n, flags, &m));  // pow2_at_least(2 n) slots: what wc_map_merge grows an empty destination to
+  if (n) {
+    const unsigned grid = (unsigned)((src->cap + kStateThreads - 1) / kStateThreads);
+    if (mom)
+      k_map_coarsen<true><<<grid, kStateThreads, 0, ctx->stream>>>(src->keys, src->pay, src->mom, src->cap, src->voxel, V, (int)factor, m->keys,
+                                                                   m->pay, m->mom, m->cap - 1, m->ctr);
+    else
+      k_map_coarsen<false><<<grid, kStateThreads, 0, ctx->stream>>>(src->keys, src->pay, nullptr, src->cap, src->voxel, V, (int)factor, m->keys,
+                                                                    m->pay, nullptr, m->cap - 1, m->ctr);
+    int rc = hipGetLastError() == hipSuccess ? WC_OK : wc_fail(ctx, WC_ERR_HIP, "%s: launch", __func__);
+    if (rc == WC_OK) rc = map_added(ctx, m, n, nullptr);
+    if (rc != WC_OK) {
+      wc_map_destroy(ctx, m);
+      return rc;
+    }
+  }
+  *out = m;
+  return WC_OK;
+}
+
 extern "C" int wc_map_clear(wc_ctx *ctx, wc_map *m) {
   wc_dev_guard dg_(ctx);
   if (!map_ok(ctx, m)) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
@@ -1655,12 +1758,14 @@ bool gn_step(const wc_map_normal_eq &ne, double min_pivot, double xi[6]) {
   }
   return true;
 }
+bool align_opts_ok(const wc_map_align_opts *o) {
+  return o && o->max_iterations >= 1 && o->tol_rot > 0.0 && o->tol_trans > 0.0 && o->min_used >= 6 && o->min_pivot > 0.0;
+}
 }  // namespace
 
 extern "C" int wc_map_align(wc_ctx *ctx, wc_map *m, const wc_points *pts, double T_io[12], const wc_map_align_opts *o,
                             wc_map_align_summary *h_out) {
-  if (!ctx || !T_io || !h_out || !o || o->max_iterations < 1 || !(o->tol_rot > 0.0) || !(o->tol_trans > 0.0) || o->min_used < 6 ||
-      !(o->min_pivot > 0.0))
+  if (!ctx || !T_io || !h_out || !align_opts_ok(o))
     return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (max_iterations >= 1, tol_rot, tol_trans, min_pivot > 0, min_used >= 6)",
                    __func__);
   std::memset(h_out, 0, sizeof(*h_out));
@@ -1698,6 +1803,23 @@ extern "C" int wc_map_align(wc_ctx *ctx, wc_map *m, const wc_points *pts, double
   if (!fresh) WC_TRY(wc_map_linearize(ctx, m, pts, T_io, &o->reg, &ne, nullptr));
   h_out->final_cost = ne.cost;
   h_out->n_used = ne.n_used, h_out->n_found = ne.n_found;
+  return WC_OK;
+}
+
+// coarse to fine: one wc_map_align per level, each from the pose the level before it left.  Everything wc_map_align and wc_map_linearize
+// refuse from their arguments alone is checked for every level before the first one runs
+extern "C" int wc_map_align_pyramid(wc_ctx *ctx, wc_map *const *levels, uint32_t n_levels, const wc_points *pts, double T_io[12],
+                                    const wc_map_align_opts *opts, wc_map_align_summary *h_out) {
+  bool ok = ctx && levels && n_levels >= 1 && n_levels <= 8 && map_points_ok(pts) && T_io && opts && h_out;
+  for (int j = 0; ok && j < 12; ++j) ok = std::isfinite(T_io[j]);
+  for (uint32_t l = 0; ok && l < n_levels; ++l)
+    ok = map_ok(ctx, levels[l]) && levels[l]->mom && align_opts_ok(&opts[l]) && reg_params_ok(&opts[l].reg);
+  if (!ok)
+    return wc_fail(ctx, WC_ERR_ARG,
+                   "%s: null or out-of-range argument (1 <= n_levels <= 8; per level what wc_map_align refuses: a map of another context or one "
+                   "created without WC_MAP_MOMENTS, its options), or a T_io that is not finite",
+                   __func__);
+  for (uint32_t l = 0; l < n_levels; ++l) WC_TRY(wc_map_align(ctx, levels[l], pts, T_io, &opts[l], &h_out[l]));
   return WC_OK;
 }
 

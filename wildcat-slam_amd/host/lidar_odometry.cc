@@ -524,6 +524,42 @@ bool LidarOdometry::AlignToMap(const float *xyz, size_t n, double T_io[12], cons
   if (summary) *summary = s;
   return true;
 }
+bool LidarOdometry::RelocalizeToMap(const float *xyz, size_t n, double T_io[12], uint32_t factor, uint32_t n_levels, const wc_map_align_opts &finest,
+                                    wc_map_align_summary *summaries) {
+  constexpr uint32_t kMaxLevels = 8;  // wc_map_align_pyramid's
+  if (!map_ || !map_moments_ || !T_io || (n && !xyz) || factor < 1 || n_levels < 1 || n_levels > kMaxLevels) return false;
+  double V = map_voxel_, scale[kMaxLevels] = {1.0};
+  for (uint32_t l = 1; l < n_levels; ++l) {
+    V = (double)factor * V;  // (as wc_map_coarsen forms it)
+    scale[l] = scale[l - 1] * (double)factor;
+    if (!(V <= 4.0)) return false;
+  }
+  // levels[0] = the coarsest ... levels[n_levels - 1] = the map itself; built finest first, each from the one before it
+  wc_map *levels[kMaxLevels] = {};
+  wc_map_align_opts opts[kMaxLevels];
+  wc_map_align_summary s[kMaxLevels];
+  levels[n_levels - 1] = map_;
+  bool ok = true;
+  for (uint32_t l = 1; ok && l < n_levels; ++l)
+    ok = wc_map_coarsen(ctx_, levels[n_levels - l], factor, WC_MAP_MOMENTS, &levels[n_levels - 1 - l]) == WC_OK;
+  for (uint32_t l = 0; l < n_levels; ++l) {
+    opts[n_levels - 1 - l] = finest;
+    opts[n_levels - 1 - l].reg.max_dist = finest.reg.max_dist * scale[l];
+  }
+  double T[12];
+  std::memcpy(T, T_io, sizeof(T));
+  if (ok) {
+    const DevBuf d_xyz(ctx_, n * 3 * sizeof(float));
+    const wc_points desc = UploadXyz(d_xyz, xyz, n);
+    ok = wc_map_align_pyramid(ctx_, levels, n_levels, &desc, T, opts, s) == WC_OK;  // (as in AlignToMap)
+  }
+  for (uint32_t l = 0; l + 1 < n_levels; ++l)
+    if (levels[l]) WC_CALL(wc_map_destroy(ctx_, levels[l]));
+  if (!ok) return false;
+  std::memcpy(T_io, T, sizeof(T));
+  if (summaries) std::memcpy(summaries, s, n_levels * sizeof(s[0]));
+  return true;
+}
 bool LidarOdometry::LinearizeAgainstMap(const float *xyz, size_t n, const double T[12], const wc_map_reg_params &params, wc_map_normal_eq *out,
                                         wc_map_reg_row *rows) {
   if (!map_ || !map_moments_ || !T || !out || (n && !xyz)) return false;

@@ -104,6 +104,14 @@ class LidarOdometry {
   // pose out, *summary (may be null) as wc_map_align leaves it.  false - nothing touched - without a map, with map_surfels off, or when
   // the library refuses the arguments.  Nothing in AddLidarScan calls it
   bool AlignToMap(const float *xyz, size_t n, double T_io[12], const wc_map_align_opts &opts, wc_map_align_summary *summary);
+  // AlignToMap from a rough pose, coarse to fine: levels 1 .. n_levels - 1 are built from the map by chained wc_map_coarsen(factor) - level
+  // l has voxel size (double)factor * that of level l - 1 -, wc_map_align_pyramid runs them coarsest first and the map itself last, each with
+  // `finest` except reg.max_dist, which is multiplied by (double)factor^l; then the built levels are destroyed.  summaries (may be null):
+  // n_levels records, coarsest first.  Nothing is cached: the levels are rebuilt per call (a relocalisation is rare; DESIGN 8.9 has the
+  // cost).  false - nothing touched - where AlignToMap returns false, for factor < 1, n_levels outside 1 .. 8, and when a level's voxel
+  // size would exceed 4.0.  Nothing in AddLidarScan calls it
+  bool RelocalizeToMap(const float *xyz, size_t n, double T_io[12], uint32_t factor, uint32_t n_levels, const wc_map_align_opts &finest,
+                       wc_map_align_summary *summaries);
   // one linearisation at T (wc_map_linearize): *out, and rows[n] when rows is not null; false as AlignToMap
   bool LinearizeAgainstMap(const float *xyz, size_t n, const double T[12], const wc_map_reg_params &params, wc_map_normal_eq *out,
                            wc_map_reg_row *rows);

@@ -225,6 +225,11 @@ uint64_t wc_odom_map_query_planes(void *h, const float *xyz, uint64_t n, double 
 int wc_odom_map_align(void *h, const float *xyz, uint64_t n, double T_io[12], const wc_map_align_opts *opts, wc_map_align_summary *summary) {
   return opts && ((LidarOdometry *)h)->AlignToMap(xyz, n, T_io, *opts, summary) ? 1 : 0;
 }
+// LidarOdometry::RelocalizeToMap; summaries: n_levels records, coarsest first (may be null); 1 = done, 0 = as wc_odom_map_align, or levels refused
+int wc_odom_map_relocalize(void *h, const float *xyz, uint64_t n, double T_io[12], uint32_t factor, uint32_t n_levels,
+                           const wc_map_align_opts *finest, wc_map_align_summary *summaries) {
+  return finest && ((LidarOdometry *)h)->RelocalizeToMap(xyz, n, T_io, factor, n_levels, *finest, summaries) ? 1 : 0;
+}
 int wc_odom_map_linearize(void *h, const float *xyz, uint64_t n, const double T[12], const wc_map_reg_params *params, wc_map_normal_eq *out,
                           wc_map_reg_row *rows) {
   return params && ((LidarOdometry *)h)->LinearizeAgainstMap(xyz, n, T, *params, out, rows) ? 1 : 0;

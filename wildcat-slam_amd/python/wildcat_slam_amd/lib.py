@@ -634,6 +634,36 @@ def _summary_dict(s):
                 n_found=int(s.n_found), last_step=np.array(list(s.last_step)))
 
 
+def map_pyramid_opts(levels, params=None, **kw):
+    """one wc_map_align_opts per map of `levels`: `params` (a wc_map_reg_params; default map_reg_params' own) with max_dist = the
+    level's voxel size, and map_align_opts' keywords -> list in the order of `levels`"""
+    p = params if params is not None else map_reg_params(1.0)
+    return [map_align_opts(map_reg_params(m.voxel, p.min_points, p.sigma0, p.cauchy_a), **kw) for m in levels]
+
+
+def map_align_pyramid_device(levels, desc, T, opts_list):
+    """wc_map_align_pyramid on points already in HBM: levels[0] runs first (the coarsest first), level l with opts_list[l] from the pose
+    level l - 1 left -> (T (3, 4), [summary dict per level])"""
+    n = len(levels)
+    assert n >= 1 and len(opts_list) == n, "one wc_map_align_opts per level"
+    ctx = levels[0].ctx
+    T = _pose12(T)
+    handles = (C.c_void_p * n)(*[m.h.value for m in levels])
+    opts, summ = (R.MapAlignOpts * n)(*opts_list), (R.MapAlignSummary * n)()
+    ctx._ck(ctx.lib.wc_map_align_pyramid(ctx.h, handles, C.c_uint32(n), C.byref(desc), R.ptr(T), opts, summ))
+    return T.reshape(3, 4), [_summary_dict(s) for s in summ]
+
+
+def map_align_pyramid(levels, points, T, opts_list=None, params=None, **kw):
+    """coarse-to-fine registration of POINT records or an (n, 3) float32 array against the maps of `levels`, coarsest first (pass
+    PointMap.pyramid()'s list reversed), from the pose T -> (T (3, 4), [summary dict per level]); opts_list: one wc_map_align_opts per
+    level, or map_pyramid_opts(levels, params, **kw)"""
+    if opts_list is None:
+        opts_list = map_pyramid_opts(levels, params, **kw)
+    with levels[0]._uploaded(points) as (desc, _):
+        return map_align_pyramid_device(levels, desc, T, opts_list)
+
+
 class PointMap:
     """wc_map: the device-resident voxel-downsampled map (DownSamplingVoxel, surfel_extraction.cc:228-261, over every insert)"""
 
@@ -882,6 +912,28 @@ class PointMap:
         """this map becomes the map of its own points and other's (wc_map_merge: table to table on the device); other is not modified"""
         self.ctx._ck(self.lib.wc_map_merge(self.ctx.h, self.h, other.h))
 
+    def coarsen(self, factor, moments=None):
+        """-> a new PointMap of voxel size float(factor) * voxel that holds this map's voxels gathered factor^3 to one, exactly
+        (wc_map_coarsen); moments: None follows this map, False drops them, True needs a map with moments.  This map is not modified"""
+        mom = self.moments if moments is None else bool(moments)
+        h = C.c_void_p(0)
+        self.ctx._ck(self.lib.wc_map_coarsen(self.ctx.h, self.h, C.c_uint32(int(factor)), C.c_uint32(R.MAP_MOMENTS if mom else 0), C.byref(h)))
+        m = object.__new__(PointMap)
+        m.ctx, m.lib, m.voxel, m.moments, m.h = self.ctx, self.lib, float(int(factor)) * self.voxel, mom, h
+        return m
+
+    def pyramid(self, factor, n_levels):
+        """-> [this map, coarsen(factor) of it, coarsen(factor) of that, ...]: n_levels maps, finest first; the caller closes levels 1 ..."""
+        levels = [self]
+        try:
+            for _ in range(1, int(n_levels)):
+                levels.append(levels[-1].coarsen(factor))
+        except WildcatError:
+            for m in levels[1:]:
+                m.close()
+            raise
+        return levels
+
     def nearest_plane_device(self, desc, max_dist, min_points, d_hits, want_count=True):
         """queries already in HBM (a wc_points descriptor) -> MAP_PLANE_HIT records in d_hits (wc_map_nearest_plane); returns the number
         of voxels found, or None without waiting when want_count is False"""
@@ -1084,6 +1136,19 @@ class Odometry:
         if not self.lib.wc_odom_map_align(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), R.ptr(T), C.byref(opts), C.byref(summ)):
             return None
         return T.reshape(3, 4), _summary_dict(summ)
+
+    def map_relocalize(self, xyz, T, factor, n_levels, opts):
+        """coarse-to-fine wc_map_align of xyz ((n, 3) float32) from the rough pose T (LidarOdometry::RelocalizeToMap): n_levels - 1
+        coarser levels built from the map by chained wc_map_coarsen(factor), run coarsest first with `opts` (the finest level's) and
+        max_dist multiplied by factor^l -> (T (3, 4), [summary dict per level, coarsest first]), or None where map_align returns None
+        or a level's voxel size would exceed 4.0"""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n_levels = int(n_levels)
+        T, summ = _pose12(T), (R.MapAlignSummary * max(n_levels, 1))()
+        if not 1 <= n_levels <= 8 or not self.lib.wc_odom_map_relocalize(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), R.ptr(T), C.c_uint32(int(factor)),
+                                                                          C.c_uint32(n_levels), C.byref(opts), summ):
+            return None
+        return T.reshape(3, 4), [_summary_dict(s) for s in summ]
 
     def map_save(self, path):
         """the map's exact state as the canonical file of host/map_file.h (LidarOdometry::SaveMap) -> True, or False without a map or
