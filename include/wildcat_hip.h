@@ -130,7 +130,16 @@ int wc_selftest_factor32(wc_ctx *ctx, int variant, int reps, const double *h_A, 
  *   d_out/d_ids  caller-allocated, capacity `cap` records; d_ids may be NULL
  *   h_n_out      number of surfels, sorted by ascending timestamp (surfel_extraction.cc:334), ties by id
  *   t_lo, t_hi   optional hint: all point timestamps lie in [t_lo, t_hi] (pass t_lo > t_hi to let the
- *                library read the first/last timestamp back from the device) */
+ *                library read the first/last timestamp back from the device)
+ * NON-FINITE POINTS.  A point with a NaN or infinite x, y or z contributes to nothing: it is in no node's count, sums, time bins
+ * or clusters, it raises no status flag whatever its stamp is (the hint binds the stamps of the finite points only; without a hint
+ * the first and the last record's stamps are read, whatever their coordinates), it does not decide the key origin (that is the
+ * first FINITE point's root voxel, or voxel 0 of a sweep without one) and by itself it does not move a sweep off the default path.
+ * The surfels of a cloud are the surfels of the same cloud with those points removed; a cloud without a finite point gives 0
+ * surfels and WC_OK.  (The reference drops them too, without saying so: VoxelLoc's cast puts them in voxels of their own kind,
+ * whose covariance is not finite and passes no gate.)  This holds for every form of the call - _enqueue / _finish, _batch_*,
+ * wc_extract_surfels_sharded - in both arithmetics.  FINITE coordinates beyond the key range (2^20 root voxels around the first
+ * finite point) and finite points with a stamp outside the hint remain WC_ERR_ARG. */
 int wc_extract_surfels(wc_ctx *ctx, const wc_points *pts, double t_lo, double t_hi, wc_surfel *d_out,
                        wc_surfel_id *d_ids, uint64_t cap, uint64_t *h_n_out);
 /* asynchronous split of the same call for pipelined / benchmarked use: enqueue does no host synchronisation,
@@ -158,7 +167,9 @@ int wc_extract_stage_ms(wc_ctx *ctx, float *h_ms5);
  * completed it (1 default path, 2 wide keys, 4 run-binned point sort, 8 time-bin surfel order), LDS capacity of the run-binned
  * sort; words 59..63: long lists, fall-backs so far, completed by the default path, its last flags and reasons) */
 int wc_debug_status(wc_ctx *ctx, uint32_t *h_out64);
-/* root-voxel index of every point: VoxelLoc (src/odometry/surfel_extraction.h:55-64); d_keys_xyz = 3 int32 per point */
+/* root-voxel index of every point: VoxelLoc (src/odometry/surfel_extraction.h:55-64); d_keys_xyz = 3 int32 per point.  An axis
+ * whose coordinate is NaN or infinite, or whose quotient does not fit an int32, gives INT32_MIN (what the reference's cast gives on
+ * x86-64; the other axes of the point are unaffected). */
 int wc_voxel_keys(wc_ctx *ctx, const wc_points *pts, int32_t *d_keys_xyz);
 
 /* one cloud over several GPUs (BASELINE config 5) --------------------------------------------------- */
@@ -183,7 +194,9 @@ int wc_route_partition(wc_ctx *ctx, const wc_points *pts, int world, wc_route_po
 /* the whole sharded call on one rank: partition the local time-contiguous slice, ONE all-to-all of 24-byte records through
  * the ctx's communicator, wc_extract_surfels on the points of the voxels this rank owns.  t_lo <= t_hi: the time range of
  * the WHOLE cloud.  Output: this rank's surfels (disjoint from the other ranks' by voxel), time sorted.
- * h_n_points_owned (may be NULL): points this rank received. */
+ * h_n_points_owned (may be NULL): points this rank received.  A point with a non-finite coordinate is routed like any other (an
+ * index of INT32_MIN on that axis, see wc_voxel_keys: ONE owner, counted in its h_n_points_owned) and dropped by the owner's
+ * extraction, as wc_extract_surfels drops it. */
 int wc_extract_surfels_sharded(wc_ctx *ctx, const wc_points *pts, double t_lo, double t_hi, wc_surfel *d_out, wc_surfel_id *d_ids,
                                uint64_t cap, uint64_t *h_n_out, uint64_t *h_n_points_owned);
 /* k time-sorted surfel lists, concatenated in d_in (h_counts[k] lengths) -> one list in the extraction's canonical order

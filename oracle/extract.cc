@@ -204,9 +204,15 @@ inline void load_point(const wc_points *pts, uint64_t i, Pt &q) {
   std::memcpy(&q.t, (const char *)pts->time + i * pts->time_stride, sizeof(double));
 }
 
-inline Key key_of(V3 p, double vs) {
-  return {(int32_t)std::floor(p.x / vs), (int32_t)std::floor(p.y / vs), (int32_t)std::floor(p.z / vs)};
+// VoxelLoc casts floor(p / vs) to int32.  For a quotient that is not finite or does not fit, that cast is undefined in C++;
+// on x86-64 it gives INT32_MIN, and that is the rule here, spelled out (both compares are false for NaN).  Such a point
+// shares its voxel only with points of its kind: the voxel's covariance is not finite and no gate passes - the
+// reference drops these points without saying so.
+inline int32_t key_axis(double p, double vs) {
+  const double f = std::floor(p / vs);
+  return (f >= -2147483648.0 && f <= 2147483647.0) ? (int32_t)f : INT32_MIN;
 }
+inline Key key_of(V3 p, double vs) { return {key_axis(p.x, vs), key_axis(p.y, vs), key_axis(p.z, vs)}; }
 }  // namespace
 
 extern "C" int wco_voxel_keys(const wc_points *pts, const wc_params *P, int32_t *keys_xyz) {

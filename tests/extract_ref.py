@@ -121,6 +121,12 @@ def extract(points, params):
     min_like = LD(np.float64(params.min_plane_likeness))
     minp, cmin, gap, max_layer = int(params.min_points), int(params.cluster_min_points), np.float64(params.cluster_gap), int(params.max_layer)
     view = np.array([params.view_point[i] for i in range(3)], np.float64)
+    fin = np.isfinite(np.stack([points["x"], points["y"], points["z"]], 1)).all(axis=1)
+    if not fin.all():  # a point with a non-finite coordinate contributes to nothing (the reference bins it with its own kind: no gate passes)
+        res = extract(points[fin], params)
+        idx = np.flatnonzero(fin)
+        res["members"] = [idx[m_] for m_ in res["members"]]
+        return res
     N = len(points)
     p = np.stack([points["x"], points["y"], points["z"]], 1).astype(np.float64)
     t = np.ascontiguousarray(points["time"], np.float64)

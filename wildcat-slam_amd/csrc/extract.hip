@@ -83,8 +83,41 @@ __device__ __forceinline__ void load_xyz(const wc_points &pts, uint64_t i, doubl
 __device__ __forceinline__ double load_t(const wc_points &pts, uint64_t i) {
   return *(const double *)((const char *)pts.time + i * pts.time_stride);
 }
-// VoxelLoc (surfel_extraction.h:59-64): floor(pos / resolution) cast to int32, true fp64 division
-__device__ __forceinline__ int vox(double p, double vs) { return (int)floor(p / vs); }
+// VoxelLoc (surfel_extraction.h:59-64): floor(pos / resolution) cast to int32, true fp64 division.  A quotient that is
+// not finite or does not fit an int32 gives INT32_MIN (what the reference's cast gives on x86-64; a bare conversion on
+// gfx950 turns NaN into 0 and saturates the rest).  Both compares are false for NaN.
+__device__ __forceinline__ int vox(double p, double vs) {
+  const double f = floor(p / vs);
+  return (f >= -2147483648.0 && f <= 2147483647.0) ? (int)f : INT32_MIN;
+}
+// THE RULE FOR NON-FINITE POINTS (wildcat_hip.h): a point with a NaN or infinite x, y or z contributes to
+// nothing - no key, no count, no sum, no flag.  (Coordinates are floats widened: the sum of three finite magnitudes is
+// finite; NaN fails the compare.)
+__device__ __forceinline__ bool finite3(double x, double y, double z) { return fabs(x) + fabs(y) + fabs(z) < (double)INFINITY; }
+// The key origin: the FIRST FINITE point of the sweep (point 0 of any clean sweep: one uniform branch), or 0 when there
+// is none.  Not simply 0 behind a non-finite point 0: the keys reach +-512 root voxels around the origin, and a sweep
+// 450 m from the frame's origin whose first return is a NaN would leave the 32-bit keys and the default path for it.
+// The wavefront looks for it together, its active lanes one point each per round.
+__device__ __forceinline__ void ex_origin(const wc_points &pts, double &x0, double &y0, double &z0) {
+  x0 = y0 = z0 = 0.0;
+  if (pts.n == 0) return;
+  load_xyz(pts, 0, x0, y0, z0);
+  if (finite3(x0, y0, z0)) return;
+  const unsigned long long act = __ballot(1);
+  const uint32_t rank = (uint32_t)__popcll(act & ((1ull << (__lane_id() & 63)) - 1ull)), cnt = (uint32_t)__popcll(act);
+  for (uint64_t b = 1; b < pts.n; b += cnt) {
+    const uint64_t i = b + rank;
+    double x = (double)INFINITY, y = 0.0, z = 0.0;
+    if (i < pts.n) load_xyz(pts, i, x, y, z);
+    const unsigned long long m = __ballot(finite3(x, y, z));
+    if (m) {
+      const int first = __ffsll((long long)m) - 1;
+      load_xyz(pts, b + (uint64_t)__popcll(act & ((1ull << first) - 1ull)), x0, y0, z0);
+      return;
+    }
+  }
+  x0 = y0 = z0 = 0.0;
+}
 
 template <typename K>
 struct KeyTraits;
@@ -113,12 +146,17 @@ __device__ __forceinline__ void raise_flag(uint32_t *status, uint32_t flag) {
 template <typename K>
 __global__ void __launch_bounds__(256) k_keygen(wc_points pts, double vs, K *keys, uint32_t *vals, uint32_t *status) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= pts.n) return;
   constexpr int B = KeyTraits<K>::bits;
   constexpr int half = 1 << (B - 1);
   double x0, y0, z0, x, y, z;
-  load_xyz(pts, 0, x0, y0, z0);
+  ex_origin(pts, x0, y0, z0);
+  if (i >= pts.n) return;
   load_xyz(pts, i, x, y, z);
+  vals[i] = (uint32_t)i;
+  if (!finite3(x, y, z)) {  // one key above every voxel's (the sort takes that bit along): a segment k_heads never makes a root of
+    keys[i] = (K)1 << (3 * B);
+    return;
+  }
   int rx = vox(x, vs) - vox(x0, vs) + half;
   int ry = vox(y, vs) - vox(y0, vs) + half;
   int rz = vox(z, vs) - vox(z0, vs) + half;
@@ -129,7 +167,6 @@ __global__ void __launch_bounds__(256) k_keygen(wc_points pts, double vs, K *key
     rz = min(max(rz, 0), 2 * half - 1);
   }
   keys[i] = (K)rx | ((K)ry << B) | ((K)rz << (2 * B));
-  vals[i] = (uint32_t)i;
 }
 
 __global__ void __launch_bounds__(256) k_voxel_keys(wc_points pts, double vs, int32_t *out) {
@@ -286,7 +323,8 @@ __global__ void __launch_bounds__(256) k_heads(const K *__restrict__ keys, uint6
   const uint64_t pos = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (pos >= n) return;
   const K k = keys[pos];
-  const bool live = (pos == 0 || keys[pos - 1] != k) && (pos + (uint64_t)min_points < n) && keys[pos + min_points] == k;
+  const bool live = (pos == 0 || keys[pos - 1] != k) && (pos + (uint64_t)min_points < n) && keys[pos + min_points] == k &&
+                    k != ((K)1 << (3 * KeyTraits<K>::bits));  // (the segment of the non-finite points: k_keygen)
   if (live) head_slots[pos / (uint64_t)(min_points + 1)] = HeadRec{(uint32_t)pos, 0u, 0u, 0u};
 }
 
@@ -401,7 +439,7 @@ __global__ void __launch_bounds__(64) k_roots(RootsArgs A) {
   const bool act = lane < 2 * lgrp;
 
   double x0, y0, z0;
-  load_xyz(A.pts, 0, x0, y0, z0);
+  ex_origin(A.pts, x0, y0, z0);
   const int k0x = vox(x0, P.vs), k0y = vox(y0, P.vs), k0z = vox(z0, P.vs);
 
   // ---- one root: stream its points (PHASE 2: also test and emit) ----
@@ -816,7 +854,7 @@ __global__ void __launch_bounds__(64) k_roots_banks(RootsArgs A, const K *__rest
   const unsigned long long lvl_mask = (PHASE == 1) ? ((1ull << kMom) - 1ull) : 0ull;
 
   double x0, y0, z0;
-  load_xyz(A.pts, 0, x0, y0, z0);
+  ex_origin(A.pts, x0, y0, z0);
   const int k0x = vox(x0, P.vs), k0y = vox(y0, P.vs), k0z = vox(z0, P.vs);
 
   auto do_root = [&](const HeadRec hrec, uint32_t tslot, uint32_t ncand, unsigned long long split1) __attribute__((always_inline)) {
@@ -1176,7 +1214,7 @@ __global__ void __launch_bounds__(64) k_roots_emit(RootsArgs A, const K *__restr
   constexpr int half = 1 << (B - 1);
   const int g = lane / G, l = lane - g * G;
   double x0, y0, z0;
-  load_xyz(A.pts, 0, x0, y0, z0);
+  ex_origin(A.pts, x0, y0, z0);
   const int k0x = vox(x0, P.vs), k0y = vox(y0, P.vs), k0z = vox(z0, P.vs);
   const float q0 = P.vs_f / 4;  // quarter_length_ of the root (cc:207)
 
@@ -1553,6 +1591,7 @@ __global__ void __launch_bounds__(256) k_init(InitArgs I) {
 // counts = run counts [kBuckets] | point counts [kBuckets].  1024 threads per 4096-point tile: one tile per CU is all a
 // 1 M-point sweep offers, so the latency hiding has to come from wavefronts of the same workgroup.
 constexpr int kRunThreads = 512;
+constexpr uint32_t kNoKey = 0xFFFFFFFFu;  // k_pt_runs: the point is not finite (voxel keys have 30 bits)
 __global__ void __launch_bounds__(kRunThreads) k_pt_runs(wc_points pts, double vs, uint64_t n, uint32_t *counts, uint64_t *bins,
                                                         uint32_t bin_cap, uint32_t *status) {
   __shared__ uint32_t s_key[kTile];
@@ -1563,7 +1602,8 @@ __global__ void __launch_bounds__(kRunThreads) k_pt_runs(wc_points pts, double v
   const uint64_t t0 = (uint64_t)blockIdx.x * kTile;
   const uint32_t cnt = (uint32_t)min((uint64_t)kTile, n - t0);
   double x0, y0, z0;
-  load_xyz(pts, 0, x0, y0, z0);
+  ex_origin(pts, x0, y0, z0);
+  const int k0x = vox(x0, vs), k0y = vox(y0, vs), k0z = vox(z0, vs);
   uint32_t key[kTile / kRunThreads];
 #pragma unroll
   for (int j = 0; j < kTile / kRunThreads; ++j) {  // all loads of the tile in flight before anything waits on them
@@ -1572,12 +1612,16 @@ __global__ void __launch_bounds__(kRunThreads) k_pt_runs(wc_points pts, double v
     if (i < cnt) {
       double x, y, z;
       load_xyz(pts, t0 + i, x, y, z);
-      int rx = vox(x, vs) - vox(x0, vs) + 512, ry = vox(y, vs) - vox(y0, vs) + 512, rz = vox(z, vs) - vox(z0, vs) + 512;
-      if ((unsigned)rx >= 1024u || (unsigned)ry >= 1024u || (unsigned)rz >= 1024u) {
-        raise_flag(status, kFlagKeyRange);
-        rx = min(max(rx, 0), 1023), ry = min(max(ry, 0), 1023), rz = min(max(rz, 0), 1023);
+      // a non-finite point: a key no voxel has, so it ends its neighbours' runs, and a run of them is never binned (below)
+      key[j] = kNoKey;
+      if (finite3(x, y, z)) {
+        int rx = vox(x, vs) - k0x + 512, ry = vox(y, vs) - k0y + 512, rz = vox(z, vs) - k0z + 512;
+        if ((unsigned)rx >= 1024u || (unsigned)ry >= 1024u || (unsigned)rz >= 1024u) {
+          raise_flag(status, kFlagKeyRange);
+          rx = min(max(rx, 0), 1023), ry = min(max(ry, 0), 1023), rz = min(max(rz, 0), 1023);
+        }
+        key[j] = (uint32_t)rx | ((uint32_t)ry << 10) | ((uint32_t)rz << 20);
       }
-      key[j] = (uint32_t)rx | ((uint32_t)ry << 10) | ((uint32_t)rz << 20);
     }
   }
   for (int b = t; b < kBuckets; b += kRunThreads) {
@@ -1601,7 +1645,7 @@ __global__ void __launch_bounds__(kRunThreads) k_pt_runs(wc_points pts, double v
   for (int j = 0; j < kTile / kRunThreads; ++j) {
     const uint32_t i = (uint32_t)j * kRunThreads + t;
     rank[j] = 0xFFFFFFFFu;
-    if (i < cnt && ((s_bits[i >> 6] >> (i & 63)) & 1ull)) {
+    if (i < cnt && key[j] != kNoKey && ((s_bits[i >> 6] >> (i & 63)) & 1ull)) {
       const uint32_t d = key_digit(key[j]);
       len[j] = run_length(s_bits, i, cnt);
       rank[j] = atomicAdd(&s_runs[d], 1u);
@@ -2167,7 +2211,7 @@ int run_pipeline(wc_ctx *ctx, const ExPath &path) {
   } else {
     k_keygen<K><<<g256, 256, 0, st>>>(pts, E.vs, (K *)ctx->b_keys[0].p, (uint32_t *)ctx->b_vals[0].p, status);
     WC_TRY(sort_pairs<K>(ctx, (K *)ctx->b_keys[0].p, (K *)ctx->b_keys[1].p, (uint32_t *)ctx->b_vals[0].p,
-                         (uint32_t *)ctx->b_vals[1].p, n, 3 * KeyTraits<K>::bits));
+                         (uint32_t *)ctx->b_vals[1].p, n, 3 * KeyTraits<K>::bits + 1));  // (+ 1: the key of the non-finite points)
   }
   RootsArgs A;
   A.pts = pts;

@@ -113,6 +113,8 @@ __device__ __forceinline__ uint32_t fx_hash32(uint32_t k) {
 
 // VoxelLoc (surfel_extraction.h:59-64) = floor(fl(p / vs)): p * (1 / vs) decides except within 1e-9 of an integer, where the
 // true fp64 division is repeated (the rounded quotient may sit on the other side of the integer)
+// (FINITE p only: the conversions are bare.  Pass A calls it for finite points alone, and a non-finite origin is replaced before its
+// index is used; a finite quotient beyond int32 saturates here where vox() gives INT32_MIN - kFlagKeyRange either way)
 __device__ __forceinline__ int fx_vox(double p, double vs, double inv_vs) {
   const double q = p * inv_vs;
   const double r = rint(q);
@@ -358,10 +360,10 @@ __device__ __forceinline__ void fx_acc_body(const FxArgs &A, const uint32_t bid)
     raw = fx_acc_load(A, bid);
   }
   double x0, y0, z0;
-  load_xyz(A.pts, 0, x0, y0, z0);
+  load_xyz(A.pts, 0, x0, y0, z0);  // (the key origin, if it is finite: looked at behind pass A's voxel indices, where ex_origin() replaces a non-finite one)
   // (fx_vox = floor(p / vs) by construction - the product with 1 / vs decides unless it lies within 1e-9 of an integer - without the
   // three divisions of vox(), ~35 instructions of every wavefront for a value all wavefronts share)
-  const int k0x = fx_vox(x0, P.vs, A.inv_vs), k0y = fx_vox(y0, P.vs, A.inv_vs), k0z = fx_vox(z0, P.vs, A.inv_vs);
+  int k0x = fx_vox(x0, P.vs, A.inv_vs), k0y = fx_vox(y0, P.vs, A.inv_vs), k0z = fx_vox(z0, P.vs, A.inv_vs);
   const float q0 = P.vs_f / 4;
 
   // the tile's points: coalesced loads (lane = point, four rounds: fx_acc_load) into LDS, then every lane takes FOUR CONSECUTIVE
@@ -436,6 +438,12 @@ __device__ __forceinline__ void fx_acc_body(const FxArgs &A, const uint32_t bid)
   // chains one after the other - 6.2 k of the workgroup's 26 k clocks; the flags are raised once, behind the loop)
   bool bad_key = false, bad_time = false;
   int kxs[kFxPts], kys[kFxPts], kzs[kFxPts];
+  // the point is finite; one that is not is skipped like a point behind the sweep's end: no key, no flag.  Looked at only in the rare
+  // block below: a non-finite coordinate fails the face test there (q - floor(q) is NaN for NaN and for +-inf), so a wavefront whose
+  // points all pass it has none, and the common path pays nothing for the rule
+  bool fin[kFxPts];
+#pragma unroll
+  for (int j = 0; j < kFxPts; ++j) fin[j] = true;
   {  // voxel indices: floor(p (1 / vs)); the rare coordinate within 1e-9 of a voxel face is divided properly, in ONE block
     // behind the loop (fx_vox)
     bool near = false;
@@ -450,9 +458,24 @@ __device__ __forceinline__ void fx_acc_body(const FxArgs &A, const uint32_t bid)
       kxs[j] = (int)fx, kys[j] = (int)fy, kzs[j] = (int)fz;
     }
     if (__ballot(near)) {
+      bool redo = false;  // a FINITE point near a face (a non-finite point needs no index)
 #pragma unroll
-      for (int j = 0; j < kFxPts; ++j) kxs[j] = fx_vox(px[j], P.vs, A.inv_vs), kys[j] = fx_vox(py[j], P.vs, A.inv_vs), kzs[j] = fx_vox(pz[j], P.vs, A.inv_vs);
+      for (int j = 0; j < kFxPts; ++j) {
+        const double qx = px[j] * A.inv_vs, qy = py[j] * A.inv_vs, qz = pz[j] * A.inv_vs;
+        const double dx = qx - floor(qx), dy = qy - floor(qy), dz = qz - floor(qz);
+        fin[j] = finite3(px[j], py[j], pz[j]);
+        redo = redo || (fin[j] && (!(dx > 1e-6 && dx < 1.0 - 1e-6) || !(dy > 1e-6 && dy < 1.0 - 1e-6) || !(dz > 1e-6 && dz < 1.0 - 1e-6)));
+      }
+      if (__ballot(redo)) {
+#pragma unroll
+        for (int j = 0; j < kFxPts; ++j)
+          if (fin[j]) kxs[j] = fx_vox(px[j], P.vs, A.inv_vs), kys[j] = fx_vox(py[j], P.vs, A.inv_vs), kzs[j] = fx_vox(pz[j], P.vs, A.inv_vs);
+      }
     }
+  }
+  if (!finite3(x0, y0, z0)) {  // (wave-uniform; here, behind the tile's loads, not in front of them)
+    ex_origin(A.pts, x0, y0, z0);
+    k0x = fx_vox(x0, P.vs, A.inv_vs), k0y = fx_vox(y0, P.vs, A.inv_vs), k0z = fx_vox(z0, P.vs, A.inv_vs);
   }
   // LEVEL 2: which layer-1 nodes of each point's root were queued, and where their blocks start - the four roots of a lane
   // looked up TOGETHER (hash probe, then the root's header: two round trips for the lane; one root after the other - a sweep in
@@ -464,7 +487,7 @@ __device__ __forceinline__ void fx_acc_body(const FxArgs &A, const uint32_t bid)
 #pragma unroll
     for (int j = 0; j < kFxPts; ++j) {
       const int rx = kxs[j] - k0x + 512, ry = kys[j] - k0y + 512, rz = kzs[j] - k0z + 512;
-      ok4[j] = base + j < n && (unsigned)rx < 1024u && (unsigned)ry < 1024u && (unsigned)rz < 1024u;
+      ok4[j] = base + j < n && fin[j] && (unsigned)rx < 1024u && (unsigned)ry < 1024u && (unsigned)rz < 1024u;
       key1[j] = ((uint32_t)rx | ((uint32_t)ry << 10) | ((uint32_t)rz << 20)) + 1u;
       slot4[j] = fx_hash32(key1[j]) & A.tr_mask;
     }
@@ -495,7 +518,7 @@ __device__ __forceinline__ void fx_acc_body(const FxArgs &A, const uint32_t bid)
   }
 #pragma unroll
   for (int j = 0; j < kFxPts; ++j) {
-    const bool have = base + j < n;
+    const bool have = base + j < n && fin[j];
     const double x = px[j], y = py[j], z = pz[j], t = pt[j];
     const int kx = kxs[j], ky = kys[j], kz = kzs[j];
     const int rx = kx - k0x + 512, ry = ky - k0y + 512, rz = kz - k0z + 512;
@@ -1553,7 +1576,7 @@ __global__ void __launch_bounds__(64) k_fx_nodes(FxArgs A) {
     }
   }
   double x0, y0, z0;
-  load_xyz(A.pts, 0, x0, y0, z0);
+  ex_origin(A.pts, x0, y0, z0);
   const int k0x = vox(x0, P.vs), k0y = vox(y0, P.vs), k0z = vox(z0, P.vs);
   const float q0 = P.vs_f / 4;
   const uint32_t wsub = blockIdx.x & (kFxSub - 1);

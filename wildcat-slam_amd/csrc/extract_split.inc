@@ -130,7 +130,7 @@ __device__ __forceinline__ void fx_test_body(const FxArgs &A, const uint32_t bid
 #pragma unroll
   for (int j = 0; j < kFxSub; ++j) total += min(*fx_cnt(A, bank, j), per);
   double x0, y0, z0;
-  load_xyz(A.pts, 0, x0, y0, z0);
+  ex_origin(A.pts, x0, y0, z0);
   const int k0x = vox(x0, P.vs), k0y = vox(y0, P.vs), k0z = vox(z0, P.vs);
   const float q0 = P.vs_f / 4;
   const uint32_t wsub = bid & (kFxSub - 1);

@@ -39,7 +39,12 @@ __host__ __device__ inline uint32_t route_hash(int32_t kx, int32_t ky, int32_t k
   return (uint32_t)h;
 }
 
-__device__ __forceinline__ int route_vox(double p, double vs) { return (int)floor(p / vs); }  // true fp64 division (h:59-64)
+// true fp64 division (h:59-64).  A quotient that is not finite or does not fit an int32 gives INT32_MIN (as vox() in extract.hip): a
+// non-finite point still has ONE defined owner, whose extraction drops it - any owner will do, the point contributes to nothing.
+__device__ __forceinline__ int route_vox(double p, double vs) {
+  const double f = floor(p / vs);
+  return (f >= -2147483648.0 && f <= 2147483647.0) ? (int)f : INT32_MIN;
+}
 
 __device__ __forceinline__ void route_load(const wc_points &pts, uint64_t i, float &x, float &y, float &z, double &t) {
   const float *f = (const float *)((const char *)pts.xyz + i * pts.xyz_stride);
