@@ -146,12 +146,20 @@ class ThreadComm:
     def shared(world):
         import threading
 
-        return {"world": world, "bar": threading.Barrier(world), "slot": [None] * world, "calls": [0] * world}
+        kinds = {k: [0] * world for k in ("allreduce", "alltoallv", "allgatherv")}
+        return {"world": world, "bar": threading.Barrier(world), "slot": [None] * world, "calls": [0] * world, "kinds": kinds}
+
+    @staticmethod
+    def counts(shared, kind=None):
+        """-> per rank, the collectives it has completed so far (kind None), or the collectives of one kind - "allreduce", "alltoallv",
+        "allgatherv" - it has ENTERED: counted when the callback is called, so a call that must not reach a collective leaves it as it was"""
+        return list(shared["calls"] if kind is None else shared["kinds"][kind])
 
     def __init__(self, shared, rank, ctx):
         self.s, self.rank, self.world, self.ctx = shared, rank, shared["world"], ctx
 
-    def _publish(self, obj):
+    def _publish(self, obj, kind):
+        self.s["kinds"][kind][self.rank] += 1
         self.s["slot"][self.rank] = obj
         self.s["bar"].wait()
         got = list(self.s["slot"])
@@ -162,7 +170,7 @@ class ThreadComm:
     def allreduce(self, ptr, count):
         mine = self.ctx.download_raw(ptr, count * 8).view(np.float64).copy()
         total = np.zeros_like(mine)
-        for part in self._publish(mine):  # fixed rank order: bitwise the same sum on every rank
+        for part in self._publish(mine, "allreduce"):  # fixed rank order: bitwise the same sum on every rank
             total = total + part
         self.ctx.upload_raw(ptr, total)
 
@@ -171,7 +179,7 @@ class ThreadComm:
         mine = self.ctx.download_raw(send_ptr, total) if total else np.zeros(0, np.uint8)
         offs = np.concatenate([[0], np.cumsum(send_bytes)]).astype(np.int64)
         parts = [mine[offs[r] : offs[r + 1]].copy() for r in range(self.world)]
-        got = self._publish(parts)
+        got = self._publish(parts, "alltoallv")
         recv = [got[src][self.rank] for src in range(self.world)]
         assert [len(p) for p in recv] == [int(b) for b in recv_bytes], "alltoallv: receive counts disagree"
         buf = np.concatenate(recv) if recv else np.zeros(0, np.uint8)
@@ -180,7 +188,7 @@ class ThreadComm:
 
     def allgatherv(self, send_ptr, send_bytes, recv_ptr, recv_bytes):
         mine = self.ctx.download_raw(send_ptr, int(send_bytes)) if send_bytes else np.zeros(0, np.uint8)
-        got = self._publish(mine.copy())
+        got = self._publish(mine.copy(), "allgatherv")
         assert [len(p) for p in got] == [int(b) for b in recv_bytes], "allgatherv: receive counts disagree"
         buf = np.concatenate(got)
         if len(buf):

@@ -349,11 +349,16 @@ class Context:
     def comm_rccl_destroy(self):
         self._ck(self.lib.wc_comm_rccl_destroy(self.h))
 
-    def route_partition(self, d_points, n, world):
-        """-> (DeviceBuffer of wc_route_point[n], counts[world])"""
+    def route_partition(self, d_points, n, world, desc=None, fill=None):
+        """-> (DeviceBuffer of wc_route_point[n], counts[world]).  desc: a wc_points descriptor of the caller's (any strides) instead of
+        the 48-byte records of d_points; fill: a byte value the output holds before the call, so that a record the call leaves
+        unwritten shows (tests)"""
         d_send = self.alloc(24 * max(n, 1))
+        if fill is not None:
+            d_send.upload(np.full(24 * max(n, 1), fill, np.uint8))
         counts = (C.c_uint64 * world)()
-        desc = self.points_desc(d_points, n)
+        if desc is None:
+            desc = self.points_desc(d_points, n)
         self._ck(self.lib.wc_route_partition(self.h, C.byref(desc), C.c_int(world), C.c_void_p(d_send.ptr), counts))
         return d_send, np.array(list(counts), np.uint64)
 
@@ -374,29 +379,43 @@ class Context:
                                                      C.c_void_p(d_ids.ptr), C.c_uint64(cap), C.byref(m), C.byref(owned)))
         return d_out, d_ids, int(m.value), int(owned.value)
 
-    def merge_surfels(self, lists, id_lists):
-        """host convenience: k sorted SURFEL arrays (+ ids) -> merged (surfels, ids)"""
+    def merge_surfels(self, lists, id_lists=None, want_ids=True, fill=None):
+        """host convenience: k sorted SURFEL arrays (+ ids) -> merged (surfels, ids).  id_lists None: no ids go in (only the stamps
+        compare) and none come out; want_ids False: the ids steer the merge and only the surfels are written -> (surfels, None) in both
+        cases.  fill: a byte value the outputs hold before the call, so that a record the call leaves unwritten shows (tests)"""
         counts = (C.c_uint64 * len(lists))(*[len(a) for a in lists])
         n = sum(len(a) for a in lists)
-        d_in, d_ids = self.to_device(np.concatenate(lists)), self.to_device(np.concatenate(id_lists))
-        d_out, d_oid = self.alloc(144 * max(n, 1)), self.alloc(16 * max(n, 1))
-        self._ck(self.lib.wc_merge_surfels(self.h, C.c_void_p(d_in.ptr), C.c_void_p(d_ids.ptr), counts, C.c_int(len(lists)), C.c_void_p(d_out.ptr),
-                                           C.c_void_p(d_oid.ptr)))
-        return d_out.download(R.SURFEL, n), d_oid.download(R.SURFEL_ID, n)
+        want_ids = want_ids and id_lists is not None
+        d_in = self.to_device(np.concatenate(lists))
+        d_ids = self.to_device(np.concatenate(id_lists)) if id_lists is not None else None
+        d_out, d_oid = self.alloc(144 * max(n, 1)), (self.alloc(16 * max(n, 1)) if want_ids else None)
+        if fill is not None:
+            for b in (d_out, d_oid):
+                if b:
+                    b.upload(np.full(b.nbytes, fill, np.uint8))
+        self._ck(self.lib.wc_merge_surfels(self.h, C.c_void_p(d_in.ptr), C.c_void_p(d_ids.ptr if d_ids else 0), counts, C.c_int(len(lists)),
+                                           C.c_void_p(d_out.ptr), C.c_void_p(d_oid.ptr if d_oid else 0)))
+        return d_out.download(R.SURFEL, n), (d_oid.download(R.SURFEL_ID, n) if want_ids else None)
 
-    def gather_surfels_device(self, d_local, d_local_ids, n_local, d_out, d_out_ids, cap):
-        """wc_gather_surfels into caller buffers (device) -> number of surfels of the merged, replicated list"""
+    def gather_surfels_device(self, d_local, d_local_ids, n_local, d_out, d_out_ids, cap, want_rc=False):
+        """wc_gather_surfels into caller buffers (device) -> number of surfels of the merged, replicated list.  d_local_ids / d_out_ids
+        None: NULL (no ids gathered / none written).  want_rc: -> (return code, *h_n_out) instead of raising - WC_ERR_CAPACITY leaves the
+        needed count in *h_n_out"""
         m = C.c_uint64(0)
-        self._ck(self.lib.wc_gather_surfels(self.h, C.c_void_p(d_local.ptr), C.c_void_p(d_local_ids.ptr), C.c_uint64(n_local), C.c_void_p(d_out.ptr),
-                                            C.c_void_p(d_out_ids.ptr if d_out_ids else 0), C.c_uint64(cap), C.byref(m)))
+        rc = self.lib.wc_gather_surfels(self.h, C.c_void_p(d_local.ptr if d_local else 0), C.c_void_p(d_local_ids.ptr if d_local_ids else 0),
+                                        C.c_uint64(n_local), C.c_void_p(d_out.ptr if d_out else 0), C.c_void_p(d_out_ids.ptr if d_out_ids else 0),
+                                        C.c_uint64(cap), C.byref(m))
+        if want_rc:
+            return rc, int(m.value)
+        self._ck(rc)
         return int(m.value)
 
-    def gather_surfels(self, d_local, d_local_ids, n_local, cap):
-        d_out, d_oid = self.alloc(144 * max(cap, 1)), self.alloc(16 * max(cap, 1))
-        m = C.c_uint64(0)
-        self._ck(self.lib.wc_gather_surfels(self.h, C.c_void_p(d_local.ptr), C.c_void_p(d_local_ids.ptr), C.c_uint64(n_local), C.c_void_p(d_out.ptr),
-                                            C.c_void_p(d_oid.ptr), C.c_uint64(cap), C.byref(m)))
-        return d_out.download(R.SURFEL, int(m.value)), d_oid.download(R.SURFEL_ID, int(m.value))
+    def gather_surfels(self, d_local, d_local_ids, n_local, cap, want_ids=True):
+        """-> (surfels, ids) of the merged, replicated list; d_local_ids None or want_ids False: see merge_surfels"""
+        want_ids = want_ids and d_local_ids is not None
+        d_out, d_oid = self.alloc(144 * max(cap, 1)), (self.alloc(16 * max(cap, 1)) if want_ids else None)
+        m = self.gather_surfels_device(d_local, d_local_ids, n_local, d_out, d_oid, cap)
+        return d_out.download(R.SURFEL, m), (d_oid.download(R.SURFEL_ID, m) if want_ids else None)
 
     # ---- sweep preparation (row f-1) -------------------------------------------------------------------------------------
     def prefilter_device(self, d_in, n, ext_quat, ext_t, min_range, max_range, blind_min, blind_max, d_out, cap, prev_time=None, d_kept_times=None):
