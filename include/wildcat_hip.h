@@ -305,6 +305,10 @@ int wc_match_pair(wc_ctx *ctx, const wc_surfel *d_sld_surf, const wc_pose *d_sld
  * The packed per-correspondence records are built once here; the calls below reuse them.
  * 2 <= ns <= 340 (dense normal equations of 12 ns unknowns; the reference's default 6.5 s window has 82 sample states),
  * otherwise WC_ERR_ARG.
+ * Refusals that restate the reference's CHECKs: WC_ERR_ORDER for a correspondence whose first stamp is not below its second (cc:256, :301;
+ * reported ahead of RANGE), WC_ERR_RANGE for a bracketed surfel stamp outside [times[0], times[ns-1]) (cc:259-265, :304-305; the fixed
+ * surfel of d_pairs_fix is not bracketed) and for an IMU triple whose second or third stamp lies outside the sample states of its factor,
+ * [times[sp1], times[sp1+2]] - [times[sp1], times[sp1+1]] in the last interval - (ImuFactor::ComputeStateCorr, cost_functor.h:367, :390).
  * Ordering: every host argument (h_imu, h_sample_times, h_grav) has been consumed when the call returns, and argument errors the
  * device finds (a surfel stamp outside the sample-state range, a correspondence that is not (older, newer)) are reported by it;
  * the call's LAST device work - the records and one copy of host-built lists - may still be in flight on the ctx stream.  The

@@ -174,17 +174,38 @@ class Window:
             lib().wco_window_destroy(self._h)
             self._h = None
 
-    def add_binary(self, surf, pose, pairs):
+    def add_binary(self, surf, pose, pairs, check=True):
         rc = lib().wco_window_add_binary(self._h, R.ptr(surf), R.ptr(pose), R.ptr(pairs), C.c_uint64(len(pairs)))
-        assert rc == 0, rc
+        return self._rc(rc, check)
 
-    def add_unary(self, fix_surf, fix_pose, sld_surf, sld_pose, pairs):
+    def add_unary(self, fix_surf, fix_pose, sld_surf, sld_pose, pairs, check=True):
         rc = lib().wco_window_add_unary(self._h, R.ptr(fix_surf), R.ptr(fix_pose), R.ptr(sld_surf), R.ptr(sld_pose), R.ptr(pairs), C.c_uint64(len(pairs)))
-        assert rc == 0, rc
+        return self._rc(rc, check)
 
-    def add_imu(self, imu):
+    def add_imu(self, imu, check=True):
         rc = lib().wco_window_add_imu(self._h, R.ptr(imu), C.c_uint64(len(imu)))
+        return self._rc(rc, check)
+
+    @staticmethod
+    def _rc(rc, check):
+        """check=False: the return code (2: a range CHECK of the reference, 3: an order CHECK) instead of an assertion; the factors
+        added before the offender stay in the window"""
+        assert rc == 0 or not check, rc
+        return rc
+
+    def lidar_factor(self, k):
+        """(kind, sp1l, sp2l, f1, f2) of surfel factor k in insertion order (binary, then unary; unary: sp1l = -1, f1 = 0)"""
+        info, f = (C.c_int32 * 3)(), (C.c_double * 2)()
+        rc = lib().wco_window_lidar_factor(self._h, C.c_uint64(k), info, f)
         assert rc == 0, rc
+        return info[0], info[1], info[2], f[0], f[1]
+
+    def imu_factor(self, k):
+        """(mode, sp1, (t1, t2, t3)) of IMU factor k in insertion order"""
+        info, t = (C.c_int32 * 2)(), (C.c_double * 3)()
+        rc = lib().wco_window_imu_factor(self._h, C.c_uint64(k), info, t)
+        assert rc == 0, rc
+        return info[0], info[1], (t[0], t[1], t[2])
 
     def counts(self):
         c = (C.c_uint64 * 6)()

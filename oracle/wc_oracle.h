@@ -82,10 +82,16 @@ int wco_window_add_binary(wco_window *w, const wc_surfel *surf, const wc_pose *p
 /* BuildFixWinLidarResiduals (cc:299-317): pair.first indexes fix_*, pair.second indexes sld_* */
 int wco_window_add_unary(wco_window *w, const wc_surfel *fix_surf, const wc_pose *fix_pose, const wc_surfel *sld_surf,
                          const wc_pose *sld_pose, const wc_pair *pairs, uint64_t n);
-/* BuildImuResiduals (cc:319-363) */
+/* BuildImuResiduals (cc:319-363); 2: a triple that starts on times[ns-1], or whose later stamps leave the sample states of its factor
+ * (the CHECKs of ImuFactor::ComputeStateCorr, cost_functor.h:367, :390) */
 int wco_window_add_imu(wco_window *w, const wc_imu_state *imu, uint64_t n_imu);
 uint64_t wco_window_num_residuals(const wco_window *w);
 void wco_window_counts(const wco_window *w, uint64_t counts[6]); /* bin mode0,1,2, unary, imu mode0, mode1 */
+/* what the construction decided for factor k, in insertion order (tests/window_cases.py): info = {kind (0,1,2 binary mode, 3 unary),
+ * sp1l (-1 unary), sp2l}, f = the two interpolation fractions as the evaluation forms them; info = {mode, sp1}, t = the triple's
+ * stamps.  Non-zero: no such factor. */
+int wco_window_lidar_factor(const wco_window *w, uint64_t k, int32_t info[3], double f[2]);
+int wco_window_imu_factor(const wco_window *w, uint64_t k, int32_t info[2], double t[3]);
 /* problem.Evaluate(apply_loss_function = true) (cc:62-65): cost = 1/2 sum rho; residuals loss-corrected */
 int wco_window_evaluate(const wco_window *w, const double *x, double *cost, double *residuals_or_null);
 /* one linearisation: dense H = J^T J (row-major 12ns x 12ns), g = J^T r, loss-corrected, no Jacobi scaling,

@@ -439,6 +439,10 @@ extern "C" int wco_window_add_imu(wco_window *w, const wc_imu_state *imu, uint64
     if (i3.t > w->times.back()) break;      // cc:327-329
     int it = upper_bound_idx(w->times, i1.t);
     if (it == 0 || it == ns) return 2;
+    {  // CHECKs of ComputeStateCorr (cost_functor.h:367, :390): every stamp of the triple inside the factor's sample states
+      const double lo = w->times[it - 1], hi = w->times[it == ns - 1 ? it : it + 1];
+      if (!(imu[i + 1].t >= lo && imu[i + 1].t <= hi && i3.t >= lo && i3.t <= hi)) return 2;
+    }
     ImuFactorRec f;
     f.i1 = imu[i], f.i2 = imu[i + 1], f.i3 = imu[i + 2];
     f.sp1 = it - 1, f.sp2 = it;
@@ -456,6 +460,23 @@ extern "C" int wco_window_add_imu(wco_window *w, const wc_imu_state *imu, uint64
 extern "C" uint64_t wco_window_num_residuals(const wco_window *w) { return w->lidar.size() + 12 * w->imu.size(); }
 extern "C" void wco_window_counts(const wco_window *w, uint64_t counts[6]) {
   for (int i = 0; i < 6; ++i) counts[i] = w->counts[i];
+}
+
+extern "C" int wco_window_lidar_factor(const wco_window *w, uint64_t k, int32_t info[3], double f[2]) {
+  if (k >= w->lidar.size()) return 1;
+  const LidarFactor &l = w->lidar[k];
+  const std::vector<double> &ts = w->times;
+  info[0] = l.kind, info[1] = l.sp1l, info[2] = l.sp2l;
+  f[0] = l.kind == 3 ? 0.0 : (l.s1.t - ts[l.sp1l]) / (ts[l.sp1r] - ts[l.sp1l]);  // as eval_lidar forms them
+  f[1] = (l.s2.t - ts[l.sp2l]) / (ts[l.sp2r] - ts[l.sp2l]);
+  return 0;
+}
+extern "C" int wco_window_imu_factor(const wco_window *w, uint64_t k, int32_t info[2], double t[3]) {
+  if (k >= w->imu.size()) return 1;
+  const ImuFactorRec &r = w->imu[k];
+  info[0] = r.mode, info[1] = r.sp1;
+  t[0] = r.i1.t, t[1] = r.i2.t, t[2] = r.i3.t;
+  return 0;
 }
 
 extern "C" int wco_window_evaluate(const wco_window *w, const double *x, double *cost, double *residuals) {

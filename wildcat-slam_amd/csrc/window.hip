@@ -1087,7 +1087,9 @@ __global__ void __launch_bounds__(144 * kGG, 8) k_gather(GatherArgs a) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const uint32_t sp = d[k][q].y & 0xFFu, sq_ = (d[k][q].y >> 8) & 0xFFu, sT = d[k][q].y >> 24;
-        val[k][q] = a.partial[d[k][q].x + tri_index(sp * 6u + (uint32_t)u, sq_ * 6u + (uint32_t)v, sT)];  // (p < q: row < column)
+        // (a slot without a source reads partial[0]: its descriptor is src[0], which a window without any factor does not have)
+        const bool have = live[k] && job[k].begin + q < job[k].end;
+        val[k][q] = a.partial[have ? d[k][q].x + tri_index(sp * 6u + (uint32_t)u, sq_ * 6u + (uint32_t)v, sT) : 0u];  // (p < q: row < column)
       }
 #pragma unroll
     for (int k = 0; k < kFarSets; ++k) {
@@ -2650,6 +2652,12 @@ static int window_build_impl(wc_ctx *ctx, const wc_surfel *d_sld_surf, const wc_
       if (h_imu[i + 2].t > W->times.back()) break;
       const int it = (int)(std::upper_bound(W->times.begin(), W->times.end(), h_imu[i].t) - W->times.begin());
       if (it == 0 || it == ns) return wc_fail(ctx, WC_ERR_RANGE, "IMU state outside the sample-state range");
+      {  // CHECKs of ComputeStateCorr (cost_functor.h:367, :390): every stamp of the triple inside the factor's two or three sample states
+        const double lo = W->times[it - 1], hi = W->times[it == ns - 1 ? it : it + 1], t2 = h_imu[i + 1].t, t3 = h_imu[i + 2].t;
+        if (!(t2 >= lo && t2 <= hi && t3 >= lo && t3 <= hi))
+          return wc_fail(ctx, WC_ERR_RANGE, "IMU triple %llu (stamps %.9f, %.9f, %.9f) reaches outside its sample states [%.9f, %.9f]",
+                         (unsigned long long)i, h_imu[i].t, t2, t3, lo, hi);
+      }
       ImuRec r;
       r.i1 = h_imu[i], r.i2 = h_imu[i + 1], r.i3 = h_imu[i + 2];
       r.sp1 = it - 1;
