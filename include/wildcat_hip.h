@@ -68,8 +68,8 @@ int wc_ctx_set_params(wc_ctx *ctx, const wc_params *params);
  *                      the bias elimination's backward error stays below 1e-9 - tests/test_lm_step_gpu.py; 0 = never)
  *   map_mom_pts (1)    wc_map_insert into a WC_MAP_MOMENTS map: points per lane - 1: tiles of 256 points, 54 KB of LDS; 2: the plain
  *                      insert's tiles of 512 points, 108 KB of LDS, one workgroup per CU (same sums either way)
- *   map_lin_groups (0) wc_map_linearize: workgroups of its first kernel (0: chosen from the point count); H, g and cost are byte-equal
- *                      whatever the value
+ *   map_lin_groups (0) wc_map_linearize and wc_map_linearize_batch: workgroups of the first kernel (0: chosen from the point count and
+ *                      K); H, g and cost are byte-equal whatever the value
  *   map_carve_groups (0) wc_map_carve: workgroups of its ray kernel (0: chosen from the point count); the five counts are the same
  *                      whatever the value
  *   map_cast_groups (0) wc_map_raycast: workgroups of its kernel (0: chosen from the point count); every output byte is the same
@@ -647,6 +647,51 @@ int wc_map_align(wc_ctx *ctx, wc_map *m, const wc_points *pts, double T_io[12], 
  * itself fails (a pose that sends a finite point to a non-finite one: that level's error, the levels before it have run). */
 int wc_map_align_pyramid(wc_ctx *ctx, wc_map *const *levels, uint32_t n_levels, const wc_points *pts, double T_io[12],
                          const wc_map_align_opts *opts, wc_map_align_summary *h_out);
+
+/* many pose hypotheses in one pass ------------------------------------------------------------------------------------- */
+/* wc_map_linearize for K poses of ONE point set: T is K x 12 doubles on the HOST, h_out K records, h_status K codes.
+ * Contract: where h_status[h] == WC_OK, h_out[h] is byte-equal to what wc_map_linearize(ctx, m, pts, T + 12 h, params, &out, NULL)
+ * writes - for every K, every grid size (development option map_lin_groups: the workgroups of the first kernel, as for the single
+ * call) and both point layouts.  Per hypothesis the summation order is wc_map_linearize's, unchanged: tiles of 256 points, chunks of 32
+ * rows in ascending order, the eight chunk sums in ascending order, reduce levels of fan 32 in ascending order.  One launch works on all
+ * (hypothesis, tile) pairs, one launch per level reduces that level of all hypotheses, ONE copy of K x 256 bytes travels back and the
+ * call waits once.  There is no d_rows.
+ * A pose that sends a finite point to a non-finite one: h_status[h] = WC_ERR_ARG and h_out[h] all zero; the other hypotheses are
+ * unaffected and the call returns WC_OK.
+ * WC_ERR_ARG for the whole call, h_out and h_status untouched: a NULL argument; a non-finite entry anywhere in T; whatever
+ * wc_map_linearize refuses of its map, points descriptor and params; K > 1024.
+ * WC_ERR_CAPACITY, outputs untouched: K * ceil(n / 256) > 2^20 (hypothesis, tile) pairs - a design cap, about 270 MB of partial sums
+ * (it is checked before anything of the points is read).
+ * K == 0: WC_OK, nothing is touched or launched.  pts->n == 0: WC_OK, every h_out[h] zero and every status WC_OK. */
+int wc_map_linearize_batch(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double *T, uint32_t K, const wc_map_reg_params *params,
+                           wc_map_normal_eq *h_out, int32_t *h_status);
+/* wc_map_align for K starts in lockstep: T_io is K x 12 doubles on the host, in and out.  Round r linearises, in one
+ * wc_map_linearize_batch launch chain, every hypothesis that still iterates together with the closing linearisation (final_cost at the
+ * final T) of those that ended in round r - 1; the poses of that set are compacted on the host.  A call makes at most
+ * max_iterations + 1 rounds, however large K is.  The host arithmetic per hypothesis is wc_map_align's own (one copy of it).
+ * Contract: T_io + 12 h, h_out[h] and h_status[h] are, byte for byte, what wc_map_align leaves and returns for that start - a start
+ * whose linearisation fails part-way (WC_ERR_ARG: T_io and the summary as they stood) included.  The call returns WC_OK then.
+ * Refused as a whole, everything untouched: what wc_map_linearize_batch and wc_map_align refuse of their arguments. */
+int wc_map_align_batch(wc_ctx *ctx, wc_map *m, const wc_points *pts, double *T_io, uint32_t K, const wc_map_align_opts *opts,
+                       wc_map_align_summary *h_out, int32_t *h_status);
+/* wc_map_align_pyramid for K starts: level l is one wc_map_align_batch over the hypotheses from the poses level l - 1 left, levels[0]
+ * (the coarsest) first.  h_out is level-major: n_levels x K records, record l * K + h.  A hypothesis whose status becomes an error is
+ * skipped on the later levels: its T stays, its later summaries are zero.  All levels' arguments are checked before any work
+ * (wc_map_align_pyramid's refusals and wc_map_align_batch's; everything untouched).  For every hypothesis that ends with status WC_OK,
+ * T_io and the summaries equal those of a single wc_map_align_pyramid call from that start, byte for byte. */
+int wc_map_align_pyramid_batch(wc_ctx *ctx, wc_map *const *levels, uint32_t n_levels, const wc_points *pts, double *T_io, uint32_t K,
+                               const wc_map_align_opts *opts, wc_map_align_summary *h_out, int32_t *h_status);
+/* The winner of a batch; host only, no context, no GPU.  Hypothesis h is eligible iff status[h] == WC_OK, termination != 2,
+ * n_used >= min_used and final_cost is finite.  Ranking: larger n_used first, then smaller final_cost, then the smaller index;
+ * *best = -1 when none is eligible (K == 0 included).  The inlier count comes first on purpose: a wrong heading can end with a LOWER
+ * cost than the right one, on few points that sit on floor and ceiling.  WC_ERR_ARG: a NULL argument (s and status may
+ * be NULL when K == 0). */
+int wc_map_align_best(const wc_map_align_summary *s, const int32_t *status, uint32_t K, uint64_t min_used, int32_t *best);
+/* K yaw hypotheses around a pose; host only, no context, no GPU.  T_k = (Rz(2 pi k / K) R0 | t0), T0 = (R0 | t0) row-major 3 x 4: the
+ * scan turned about the sensor's position, around the world z axis.  T_0 is T0 bitwise and every translation is t0 bitwise.  Sine and
+ * cosine are rounded once from extended precision; an entry is c r - s r' or s r + c r' (two rounded products and one sum).  K == 0:
+ * nothing is written.  WC_ERR_ARG: a NULL argument (T_out may be NULL when K == 0). */
+int wc_pose_yaw_grid(const double T0[12], uint32_t K, double *T_out);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,8 @@
 //   k_map_nearest<true>  plane query: the same search, then map_plane_of for the winning voxel only -> wc_map_plane_hit
 //   k_map_linearize / k_map_lin_reduce  registration: the plane query behind a pose, reduced to the point-to-plane normal equations in a
 //                   fixed order (tiles of 256 points, then levels of 32 partials, one launch each): wc_map_linearize, wc_map_align
+//   k_map_linearize_batch / k_map_lin_reduce_batch  the same for K poses of one point set in one launch chain, (hypothesis, tile) pairs
+//                   as work items, the tile body shared with k_map_linearize: wc_map_linearize_batch, wc_map_align_batch
 //   k_map_carve    carving: one lane per ray from the call's origin to a point: the end voxel's word gets its mark, then the counted voxel
 //                   walk, eight steps ahead of the probes: keys, hashes and shell tests of a batch, its first-slot key loads issued
 //                   together, then the chains (read-only) and one no-return atomic add per occupied voxel seen through;
@@ -58,6 +60,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 #include <rocprim/rocprim.hpp>
 
@@ -87,6 +90,10 @@ struct wc_map {
   wc_buf b_pairs[4], b_tmp, b_cnt;   // export scratch: keys in / out, slot indices in / out; rocPRIM temporary; compaction counter
   wc_buf b_lin;                      // wc_map_linearize: the tiles' partial sums and every level of their reduction (first use)
   unsigned long long *h_lin = nullptr;  // ... and the pinned landing place of the result (first use)
+  wc_buf b_pose;                     // wc_map_linearize_batch: the poses, K x 12 doubles (b_lin holds its partials too)
+  unsigned long long *h_linb = nullptr;  // ... the pinned landing place of its K final partials, grown on demand ...
+  double *h_pose = nullptr;          // ... and the pinned block the poses are uploaded from: both hold h_linb_cap hypotheses
+  uint64_t h_linb_cap = 0;
   wc_buf b_carve;                    // wc_map_carve: its five counter lines, then one u32 word per slot (first use, grown with the table)
   unsigned long long *h_carve = nullptr;  // ... and the pinned landing place of the counters (first use)
   wc_buf b_cast;                     // wc_map_raycast: its four counter lines (first use); nothing another call reads or writes
@@ -663,102 +670,130 @@ struct map_reg {
   unsigned min_points;
 };
 
+// one tile: the body k_map_linearize and k_map_linearize_batch share.  T: the pose (workgroup uniform); out: the tile's 256-byte partial;
+// rows: NULL or the call's wc_map_reg_row array; s_row, s_chunk, s_cnt: the workgroup's LDS (kLinFields * kLinPitch and kLinSums * 8
+// doubles, 3 words).  Every lane of the workgroup calls it
+__device__ __forceinline__ void map_lin_tile(const wc_points &pts, const double (&T)[12], const map_reg &R, double v, const unsigned long long *keys,
+                                             const long long *pay, const long long *mom, unsigned long long mask, wc_map_reg_row *rows,
+                                             uint64_t tile, unsigned long long *out, double *s_row, double *s_chunk, unsigned *s_cnt) {
+  const int t = threadIdx.x;
+  if (t < 3) s_cnt[t] = 0;
+  __syncthreads();  // (also: the previous tile's sums have been read)
+  const uint64_t i = tile * kLinThreads + t;
+  double row[kLinFields] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  bool used = false, hit = false, bad = false;
+  if (i < pts.n) {
+    const float *f = (const float *)((const char *)pts.xyz + i * pts.xyz_stride);
+    const float px = f[0], py = f[1], pz = f[2];
+    const double x0 = (double)px, y0 = (double)py, z0 = (double)pz;
+    const float qx = (float)(((T[0] * x0 + T[1] * y0) + T[2] * z0) + T[3]);
+    const float qy = (float)(((T[4] * x0 + T[5] * y0) + T[6] * z0) + T[7]);
+    const float qz = (float)(((T[8] * x0 + T[9] * y0) + T[10] * z0) + T[11]);
+    bad = isfinite(px) && isfinite(py) && isfinite(pz) && !(isfinite(qx) && isfinite(qy) && isfinite(qz));
+    const double x = (double)qx, y = (double)qy, z = (double)qz;
+    const map_found w = map_search<true>(x, y, z, v, keys, pay, mask);
+    hit = w.bc != 0 && w.best <= R.max_d2;
+    double pn[3], sigma2, dist;
+    used = map_hit_plane(w, hit, x, y, z, mom, R.min_points, pn, sigma2, dist);
+    if (used) {
+      row[0] = y * pn[2] - z * pn[1], row[1] = z * pn[0] - x * pn[2], row[2] = x * pn[1] - y * pn[0];
+      row[3] = pn[0], row[4] = pn[1], row[5] = pn[2];
+      row[6] = dist;
+      const double w2 = 1.0 / (R.s02 + sigma2), s = (w2 * dist) * dist;
+      if (R.a2 > 0.0) {
+        const double u = s / R.a2;
+        row[7] = w2 / (1.0 + u), row[8] = R.a2 * log1p(u);
+      } else {
+        row[7] = w2, row[8] = s;
+      }
+    }
+    if (rows) {  // (the record is 8-aligned: eight 8-byte stores)
+      double *o = (double *)(rows + i);
+#pragma unroll
+      for (int fld = 0; fld < 8; ++fld) o[fld] = row[fld];
+    }
+  }
+  // the counts: per wavefront, then integer adds in LDS (order independent)
+  const unsigned n_u = (unsigned)__popcll(__ballot(used)), n_h = (unsigned)__popcll(__ballot(hit)), n_b = (unsigned)__popcll(__ballot(bad));
+  if ((t & 63) == 0) {
+    if (n_u) atomicAdd(&s_cnt[0], n_u);
+    if (n_h) atomicAdd(&s_cnt[1], n_h);
+    if (n_b) atomicAdd(&s_cnt[2], n_b);
+  }
+  const int at = t + t / kLinFan;
+#pragma unroll
+  for (int fld = 0; fld < kLinFields; ++fld) s_row[fld * kLinPitch + at] = row[fld];
+  __syncthreads();
+  if (t < kLinSums * 8) {
+    const int e = t >> 3, c = t & 7;
+    // e -> the three factors of a term (k X) Y: H(a, b): X = J_a, Y = J_b; g_a: X = J_a, Y = d; sum rho: the term itself
+    int a = 0, b = e;
+    while (b >= 6 - a && a < 6) b -= 6 - a, ++a;
+    const int fx = e < 21 ? a : e - 21, fy = e < 21 ? a + b : 6;
+    const double *rk = s_row + 7 * kLinPitch + c * (kLinFan + 1), *rx = s_row + fx * kLinPitch + c * (kLinFan + 1),
+                 *ry = s_row + fy * kLinPitch + c * (kLinFan + 1), *rr = s_row + 8 * kLinPitch + c * (kLinFan + 1);
+    double acc = 0.0;
+    if (e < 27) {
+      acc = (rk[0] * rx[0]) * ry[0];
+      for (int j = 1; j < kLinFan; ++j) acc += (rk[j] * rx[j]) * ry[j];
+    } else {
+      acc = rr[0];
+      for (int j = 1; j < kLinFan; ++j) acc += rr[j];
+    }
+    s_chunk[e * 8 + c] = acc;
+  }
+  __syncthreads();
+  if (t < kLinWords) {
+    unsigned long long word = 0;
+    if (t < kLinSums) {
+      double acc = s_chunk[t * 8];
+#pragma unroll
+      for (int c = 1; c < 8; ++c) acc += s_chunk[t * 8 + c];
+      word = (unsigned long long)__double_as_longlong(acc);
+    } else if (t < kLinSums + 3) {
+      word = s_cnt[t - kLinSums];
+    }
+    out[t] = word;
+  }
+}
+
 __global__ void __launch_bounds__(kLinThreads) k_map_linearize(wc_points pts, map_pose P, map_reg R, double v, const unsigned long long *keys,
                                                                const long long *pay, const long long *mom, unsigned long long mask,
                                                                wc_map_reg_row *rows, unsigned long long *part) {
   __shared__ double s_row[kLinFields * kLinPitch];
   __shared__ double s_chunk[kLinSums * 8];
   __shared__ unsigned s_cnt[3];
-  const int t = threadIdx.x;
   const uint64_t tiles = (pts.n + kLinThreads - 1) / kLinThreads;
-  for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    if (t < 3) s_cnt[t] = 0;
-    __syncthreads();  // (also: the previous tile's sums have been read)
-    const uint64_t i = tile * kLinThreads + t;
-    double row[kLinFields] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    bool used = false, hit = false, bad = false;
-    if (i < pts.n) {
-      const float *f = (const float *)((const char *)pts.xyz + i * pts.xyz_stride);
-      const float px = f[0], py = f[1], pz = f[2];
-      const double x0 = (double)px, y0 = (double)py, z0 = (double)pz;
-      const float qx = (float)(((P.T[0] * x0 + P.T[1] * y0) + P.T[2] * z0) + P.T[3]);
-      const float qy = (float)(((P.T[4] * x0 + P.T[5] * y0) + P.T[6] * z0) + P.T[7]);
-      const float qz = (float)(((P.T[8] * x0 + P.T[9] * y0) + P.T[10] * z0) + P.T[11]);
-      bad = isfinite(px) && isfinite(py) && isfinite(pz) && !(isfinite(qx) && isfinite(qy) && isfinite(qz));
-      const double x = (double)qx, y = (double)qy, z = (double)qz;
-      const map_found w = map_search<true>(x, y, z, v, keys, pay, mask);
-      hit = w.bc != 0 && w.best <= R.max_d2;
-      double pn[3], sigma2, dist;
-      used = map_hit_plane(w, hit, x, y, z, mom, R.min_points, pn, sigma2, dist);
-      if (used) {
-        row[0] = y * pn[2] - z * pn[1], row[1] = z * pn[0] - x * pn[2], row[2] = x * pn[1] - y * pn[0];
-        row[3] = pn[0], row[4] = pn[1], row[5] = pn[2];
-        row[6] = dist;
-        const double w2 = 1.0 / (R.s02 + sigma2), s = (w2 * dist) * dist;
-        if (R.a2 > 0.0) {
-          const double u = s / R.a2;
-          row[7] = w2 / (1.0 + u), row[8] = R.a2 * log1p(u);
-        } else {
-          row[7] = w2, row[8] = s;
-        }
-      }
-      if (rows) {  // (the record is 8-aligned: eight 8-byte stores)
-        double *o = (double *)(rows + i);
+  for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x)
+    map_lin_tile(pts, P.T, R, v, keys, pay, mom, mask, rows, tile, part + tile * kLinWords, s_row, s_chunk, s_cnt);
+}
+
+// K poses in one launch (wc_map_linearize_batch: DESIGN 8.10).  A work item is a (hypothesis, tile) pair, item = h * tiles + tile:
+// neighbouring workgroups share a hypothesis and work on neighbouring tiles of it.  poses: K x 12 doubles, read through loads whose
+// address is the same for the whole workgroup.  part: hypothesis-major, hyp_words words each - the single call's level layout
+__global__ void __launch_bounds__(kLinThreads) k_map_linearize_batch(wc_points pts, const double *__restrict__ poses, unsigned K, map_reg R, double v,
+                                                                     const unsigned long long *keys, const long long *pay, const long long *mom,
+                                                                     unsigned long long mask, unsigned long long *__restrict__ part,
+                                                                     unsigned long long hyp_words) {
+  __shared__ double s_row[kLinFields * kLinPitch];
+  __shared__ double s_chunk[kLinSums * 8];
+  __shared__ unsigned s_cnt[3];
+  const unsigned tiles = (unsigned)((pts.n + kLinThreads - 1) / kLinThreads);  // (K * tiles <= 2^20: the host's capacity check)
+  const unsigned items = K * tiles;
+  for (unsigned item = blockIdx.x; item < items; item += gridDim.x) {
+    const unsigned h = item / tiles, tile = item - h * tiles;
+    const double *Tp = poses + (size_t)h * 12;
+    double T[12];
 #pragma unroll
-        for (int fld = 0; fld < 8; ++fld) o[fld] = row[fld];
-      }
-    }
-    // the counts: per wavefront, then integer adds in LDS (order independent)
-    const unsigned n_u = (unsigned)__popcll(__ballot(used)), n_h = (unsigned)__popcll(__ballot(hit)), n_b = (unsigned)__popcll(__ballot(bad));
-    if ((t & 63) == 0) {
-      if (n_u) atomicAdd(&s_cnt[0], n_u);
-      if (n_h) atomicAdd(&s_cnt[1], n_h);
-      if (n_b) atomicAdd(&s_cnt[2], n_b);
-    }
-    const int at = t + t / kLinFan;
-#pragma unroll
-    for (int fld = 0; fld < kLinFields; ++fld) s_row[fld * kLinPitch + at] = row[fld];
-    __syncthreads();
-    if (t < kLinSums * 8) {
-      const int e = t >> 3, c = t & 7;
-      // e -> the three factors of a term (k X) Y: H(a, b): X = J_a, Y = J_b; g_a: X = J_a, Y = d; sum rho: the term itself
-      int a = 0, b = e;
-      while (b >= 6 - a && a < 6) b -= 6 - a, ++a;
-      const int fx = e < 21 ? a : e - 21, fy = e < 21 ? a + b : 6;
-      const double *rk = s_row + 7 * kLinPitch + c * (kLinFan + 1), *rx = s_row + fx * kLinPitch + c * (kLinFan + 1),
-                   *ry = s_row + fy * kLinPitch + c * (kLinFan + 1), *rr = s_row + 8 * kLinPitch + c * (kLinFan + 1);
-      double acc = 0.0;
-      if (e < 27) {
-        acc = (rk[0] * rx[0]) * ry[0];
-        for (int j = 1; j < kLinFan; ++j) acc += (rk[j] * rx[j]) * ry[j];
-      } else {
-        acc = rr[0];
-        for (int j = 1; j < kLinFan; ++j) acc += rr[j];
-      }
-      s_chunk[e * 8 + c] = acc;
-    }
-    __syncthreads();
-    if (t < kLinWords) {
-      unsigned long long word = 0;
-      if (t < kLinSums) {
-        double acc = s_chunk[t * 8];
-#pragma unroll
-        for (int c = 1; c < 8; ++c) acc += s_chunk[t * 8 + c];
-        word = (unsigned long long)__double_as_longlong(acc);
-      } else if (t < kLinSums + 3) {
-        word = s_cnt[t - kLinSums];
-      }
-      part[tile * kLinWords + t] = word;
-    }
+    for (int j = 0; j < 12; ++j) T[j] = Tp[j];
+    map_lin_tile(pts, T, R, v, keys, pay, mom, mask, nullptr, tile, part + h * hyp_words + (size_t)tile * kLinWords, s_row, s_chunk, s_cnt);
   }
 }
 
-// one level of the second stage: out[j] = in[32 j] + in[32 j + 1] + ... in ascending order (the doubles; the counts are integers)
-__global__ void __launch_bounds__(256) k_map_lin_reduce(const unsigned long long *in, uint64_t m, unsigned long long *out) {
-  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  const uint64_t j = g / kLinWords, first = j * kLinFan;
-  const int e = (int)(g % kLinWords);
-  if (first >= m) return;
+// word e of partial j of the next level: in[32 j] + in[32 j + 1] + ... in ascending order (the doubles; the counts are integers); m: the
+// partials of `in`, 32 j < m
+__device__ __forceinline__ void map_lin_reduce_word(const unsigned long long *in, uint64_t m, uint64_t j, int e, unsigned long long *out) {
+  const uint64_t first = j * kLinFan;
   const uint64_t cnt = m - first < (uint64_t)kLinFan ? m - first : (uint64_t)kLinFan;
   const unsigned long long *p = in + first * kLinWords + e;
   unsigned long long word = p[0];
@@ -770,6 +805,25 @@ __global__ void __launch_bounds__(256) k_map_lin_reduce(const unsigned long long
     for (uint64_t r = 1; r < cnt; ++r) word += p[r * kLinWords];
   }
   out[j * kLinWords + e] = word;
+}
+
+// one level of the second stage, one lane per word of the next level
+__global__ void __launch_bounds__(256) k_map_lin_reduce(const unsigned long long *in, uint64_t m, unsigned long long *out) {
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint64_t j = g / kLinWords;
+  if (j * kLinFan >= m) return;
+  map_lin_reduce_word(in, m, j, (int)(g % kLinWords), out);
+}
+
+// the same level of all K hypotheses: hypothesis h reads its m partials at in + h * in_stride and writes its ceil(m / 32) at
+// out + h * out_stride (words)
+__global__ void __launch_bounds__(256) k_map_lin_reduce_batch(const unsigned long long *in, uint64_t in_stride, uint64_t m, unsigned long long *out,
+                                                              uint64_t out_stride, unsigned K) {
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint64_t per = (m + kLinFan - 1) / kLinFan * kLinWords;  // words of one hypothesis's next level
+  const uint64_t h = g / per, r = g - h * per;
+  if (h >= K) return;
+  map_lin_reduce_word(in + h * in_stride, m, r / kLinWords, (int)(r % kLinWords), out + h * out_stride);
 }
 
 // the occupied slots that `sel` selects and their points, reduced per workgroup: a crop's kept voxels, a carve's seen-through ones.  The
@@ -1336,12 +1390,15 @@ extern "C" int wc_map_destroy(wc_ctx *ctx, wc_map *m) {
   wc_buf_release(ctx, m->b_tmp);
   wc_buf_release(ctx, m->b_cnt);
   wc_buf_release(ctx, m->b_lin);
+  wc_buf_release(ctx, m->b_pose);
   wc_buf_release(ctx, m->b_carve);
   wc_buf_release(ctx, m->b_cast);
   (void)hipStreamSynchronize(ctx->stream);  // (the pinned counters may still be the target of an enqueued copy)
   if (m->ev_ctr) (void)hipEventDestroy(m->ev_ctr);
   if (m->h_ctr) (void)hipHostFree(m->h_ctr);
   if (m->h_lin) (void)hipHostFree(m->h_lin);
+  if (m->h_linb) (void)hipHostFree(m->h_linb);
+  if (m->h_pose) (void)hipHostFree(m->h_pose);
   if (m->h_carve) (void)hipHostFree(m->h_carve);
   if (m->h_cast) (void)hipHostFree(m->h_cast);
   delete m;
@@ -1653,6 +1710,23 @@ uint64_t lin_words(uint64_t tiles) {
   } while (m > 1);
   return total * kLinWords;
 }
+map_reg reg_of(const wc_map_reg_params *params) {
+  map_reg R;
+  R.max_d2 = params->max_dist * params->max_dist;
+  R.s02 = params->sigma0 * params->sigma0;
+  R.a2 = params->cauchy_a * params->cauchy_a;
+  R.min_points = params->min_points;
+  return R;
+}
+// a final partial (28 doubles, then n_used, n_found, n_bad) as the record
+void normal_eq_of(const unsigned long long *part, wc_map_normal_eq *out) {
+  double sums[kLinSums];
+  std::memcpy(sums, part, sizeof(sums));
+  for (int e = 0; e < 21; ++e) out->H[e] = sums[e];
+  for (int e = 0; e < 6; ++e) out->g[e] = sums[21 + e];
+  out->cost = 0.5 * sums[27];
+  out->n_used = part[kLinSums], out->n_found = part[kLinSums + 1];
+}
 }  // namespace
 
 extern "C" int wc_map_linearize(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double T[12], const wc_map_reg_params *params,
@@ -1670,11 +1744,7 @@ extern "C" int wc_map_linearize(wc_ctx *ctx, wc_map *m, const wc_points *pts, co
   const uint64_t tiles = (pts->n + kLinThreads - 1) / kLinThreads;
   WC_TRY(wc_ensure(ctx, m->b_lin, lin_words(tiles) * 8));
   if (!m->h_lin) WC_HIP(ctx, hipHostMalloc((void **)&m->h_lin, kLinWords * 8));
-  map_reg R;
-  R.max_d2 = params->max_dist * params->max_dist;
-  R.s02 = params->sigma0 * params->sigma0;
-  R.a2 = params->cauchy_a * params->cauchy_a;
-  R.min_points = params->min_points;
+  const map_reg R = reg_of(params);
   unsigned long long *lvl = (unsigned long long *)m->b_lin.p;
   uint64_t grid = std::min<uint64_t>(tiles, (uint64_t)8 * m->cus);
   if (ctx->dev.map_lin_groups > 0) grid = std::min<uint64_t>(tiles, (uint64_t)ctx->dev.map_lin_groups);  // (development option)
@@ -1692,13 +1762,83 @@ extern "C" int wc_map_linearize(wc_ctx *ctx, wc_map *m, const wc_points *pts, co
   WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (m->h_lin[kLinSums + 2])
     return wc_fail(ctx, WC_ERR_ARG, "%s: T sends %llu finite points to a non-finite one", __func__, m->h_lin[kLinSums + 2]);
-  double sums[kLinSums];
-  std::memcpy(sums, m->h_lin, sizeof(sums));
-  for (int e = 0; e < 21; ++e) h_out->H[e] = sums[e];
-  for (int e = 0; e < 6; ++e) h_out->g[e] = sums[21 + e];
-  h_out->cost = 0.5 * sums[27];
-  h_out->n_used = m->h_lin[kLinSums], h_out->n_found = m->h_lin[kLinSums + 1];
+  normal_eq_of(m->h_lin, h_out);
   return WC_OK;
+}
+
+namespace {
+constexpr uint32_t kLinBatchMax = 1024;         // hypotheses of one call
+constexpr uint64_t kLinBatchItems = 1ull << 20;  // (hypothesis, tile) pairs of one call: a design cap, about 270 MB of partials
+// wc_map_linearize_batch behind its argument checks, K >= 1: every hypothesis's record and status (WC_OK, or WC_ERR_ARG and a zero
+// record where the pose sends a finite point to a non-finite one).  One launch of k_map_linearize_batch, one of k_map_lin_reduce_batch
+// per level, one copy of K x 256 bytes, one wait
+int lin_batch_core(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double *T, uint32_t K, const wc_map_reg_params *params,
+                   wc_map_normal_eq *h_out, int32_t *h_status) {
+  std::memset(h_out, 0, (size_t)K * sizeof(*h_out));
+  for (uint32_t h = 0; h < K; ++h) h_status[h] = WC_OK;
+  if (pts->n == 0) return WC_OK;
+  const uint64_t tiles = (pts->n + kLinThreads - 1) / kLinThreads, hyp_words = lin_words(tiles);
+  // the partials hypothesis-major, then the K final partials side by side (the last level writes there, not into its own slot)
+  WC_TRY(wc_ensure(ctx, m->b_lin, ((uint64_t)K * hyp_words + (uint64_t)K * kLinWords) * 8));
+  WC_TRY(wc_ensure(ctx, m->b_pose, (size_t)K * 12 * sizeof(double)));
+  if (m->h_linb_cap < K) {
+    if (m->h_linb) (void)hipHostFree(m->h_linb);
+    if (m->h_pose) (void)hipHostFree(m->h_pose);
+    m->h_linb = nullptr, m->h_pose = nullptr, m->h_linb_cap = 0;
+    WC_HIP(ctx, hipHostMalloc((void **)&m->h_linb, (size_t)K * kLinWords * 8));
+    WC_HIP(ctx, hipHostMalloc((void **)&m->h_pose, (size_t)K * 12 * sizeof(double)));
+    m->h_linb_cap = K;
+  }
+  std::memcpy(m->h_pose, T, (size_t)K * 12 * sizeof(double));
+  WC_HIP(ctx, hipMemcpyAsync(m->b_pose.p, m->h_pose, (size_t)K * 12 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  unsigned long long *base = (unsigned long long *)m->b_lin.p, *fin = base + (uint64_t)K * hyp_words;
+  const uint64_t items = (uint64_t)K * tiles;
+  uint64_t grid = std::min<uint64_t>(items, (uint64_t)8 * m->cus);
+  if (ctx->dev.map_lin_groups > 0) grid = std::min<uint64_t>(items, (uint64_t)ctx->dev.map_lin_groups);  // (development option)
+  k_map_linearize_batch<<<(unsigned)grid, kLinThreads, 0, ctx->stream>>>(*pts, (const double *)m->b_pose.p, K, reg_of(params), m->voxel, m->keys,
+                                                                         m->pay, m->mom, m->cap - 1, base, hyp_words);
+  WC_HIP(ctx, hipGetLastError());
+  uint64_t cnt = tiles, off = 0;  // the level's partials and where they start within a hypothesis
+  do {
+    const uint64_t nxt = (cnt + kLinFan - 1) / kLinFan, off_out = off + cnt * kLinWords;
+    unsigned long long *out = nxt > 1 ? base + off_out : fin;
+    const uint64_t out_stride = nxt > 1 ? hyp_words : (uint64_t)kLinWords, lanes = (uint64_t)K * nxt * kLinWords;
+    k_map_lin_reduce_batch<<<(unsigned)((lanes + 255) / 256), 256, 0, ctx->stream>>>(base + off, hyp_words, cnt, out, out_stride, K);
+    WC_HIP(ctx, hipGetLastError());
+    off = off_out, cnt = nxt;
+  } while (cnt > 1);
+  WC_HIP(ctx, hipMemcpyAsync(m->h_linb, fin, (size_t)K * kLinWords * 8, hipMemcpyDeviceToHost, ctx->stream));
+  WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (uint32_t h = 0; h < K; ++h) {
+    const unsigned long long *part = m->h_linb + (size_t)h * kLinWords;
+    if (part[kLinSums + 2])
+      h_status[h] = WC_ERR_ARG;
+    else
+      normal_eq_of(part, &h_out[h]);
+  }
+  return WC_OK;
+}
+// what wc_map_linearize_batch refuses of its arguments other than the records it writes; WC_OK: the call may run
+int lin_batch_check(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double *T, uint32_t K, const wc_map_reg_params *params, const char *fn) {
+  if (!map_ok(ctx, m) || !m->mom || !map_points_ok(pts) || (K && !T) || !reg_params_ok(params) || K > kLinBatchMax)
+    return wc_fail(ctx, WC_ERR_ARG,
+                   "%s: null or out-of-range argument (K <= 1024), a map of another context or one created without WC_MAP_MOMENTS", fn);
+  for (uint64_t j = 0; j < (uint64_t)K * 12; ++j)
+    if (!std::isfinite(T[j]))
+      return wc_fail(ctx, WC_ERR_ARG, "%s: entry %u of hypothesis %u's T is not finite", fn, (unsigned)(j % 12), (unsigned)(j / 12));
+  if ((uint64_t)K * ((pts->n + kLinThreads - 1) / kLinThreads) > kLinBatchItems)
+    return wc_fail(ctx, WC_ERR_CAPACITY, "%s: K * ceil(n / 256) exceeds 2^20", fn);
+  return WC_OK;
+}
+}  // namespace
+
+extern "C" int wc_map_linearize_batch(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double *T, uint32_t K, const wc_map_reg_params *params,
+                                      wc_map_normal_eq *h_out, int32_t *h_status) {
+  wc_dev_guard dg_(ctx);
+  if (K && (!h_out || !h_status)) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
+  WC_TRY(lin_batch_check(ctx, m, pts, T, K, params, __func__));
+  if (K == 0) return WC_OK;
+  return lin_batch_core(ctx, m, pts, T, K, params, h_out, h_status);
 }
 
 namespace {
@@ -1761,6 +1901,44 @@ bool gn_step(const wc_map_normal_eq &ne, double min_pivot, double xi[6]) {
 bool align_opts_ok(const wc_map_align_opts *o) {
   return o && o->max_iterations >= 1 && o->tol_rot > 0.0 && o->tol_trans > 0.0 && o->min_used >= 6 && o->min_pivot > 0.0;
 }
+// wc_map_align's loop in pieces, so that the single call and the lockstep rounds of wc_map_align_batch run one copy of it
+enum { kAlignGo = 0, kAlignEndFresh = 1, kAlignEndStale = 2 };  // iterate again; ended, ne is the linearisation at T_io; ended, it is not
+void align_begin(wc_map_align_summary *s) {
+  std::memset(s, 0, sizeof(*s));
+  s->termination = 1;
+}
+// iteration `it` behind its linearisation ne at T_io
+int align_iter(const wc_map_normal_eq &ne, uint32_t it, double T_io[12], const wc_map_align_opts *o, wc_map_align_summary *s) {
+  if (it == 0) s->initial_cost = ne.cost;
+  double xi[6];
+  if (ne.n_used < o->min_used || !gn_step(ne, o->min_pivot, xi)) {
+    s->termination = 2;
+    return kAlignEndFresh;
+  }
+  double T[12];
+  std::memcpy(T, T_io, sizeof(T));
+  pose_update(T, xi);
+  bool finite = true;
+  for (int j = 0; j < 12; ++j) finite = finite && std::isfinite(T[j]);
+  if (!finite) {
+    s->termination = 2;
+    return kAlignEndFresh;
+  }
+  std::memcpy(T_io, T, sizeof(T));
+  std::memcpy(s->last_step, xi, sizeof(xi));
+  s->iterations = (int32_t)(it + 1);
+  const double rot = std::sqrt((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2]), tr = std::sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5]);
+  if (rot <= o->tol_rot && tr <= o->tol_trans) {
+    s->termination = 0;
+    return kAlignEndStale;
+  }
+  return it + 1 < o->max_iterations ? kAlignGo : kAlignEndStale;
+}
+// ne: the linearisation at the final T_io
+void align_end(const wc_map_normal_eq &ne, wc_map_align_summary *s) {
+  s->final_cost = ne.cost;
+  s->n_used = ne.n_used, s->n_found = ne.n_found;
+}
 }  // namespace
 
 extern "C" int wc_map_align(wc_ctx *ctx, wc_map *m, const wc_points *pts, double T_io[12], const wc_map_align_opts *o,
@@ -1768,42 +1946,77 @@ extern "C" int wc_map_align(wc_ctx *ctx, wc_map *m, const wc_points *pts, double
   if (!ctx || !T_io || !h_out || !align_opts_ok(o))
     return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (max_iterations >= 1, tol_rot, tol_trans, min_pivot > 0, min_used >= 6)",
                    __func__);
-  std::memset(h_out, 0, sizeof(*h_out));
-  h_out->termination = 1;
+  align_begin(h_out);
   wc_map_normal_eq ne;
-  bool fresh = false;  // ne is the linearisation at T_io
-  for (uint32_t it = 0; it < o->max_iterations; ++it) {
+  int st = kAlignGo;
+  for (uint32_t it = 0; st == kAlignGo; ++it) {
     WC_TRY(wc_map_linearize(ctx, m, pts, T_io, &o->reg, &ne, nullptr));
-    fresh = true;
-    if (it == 0) h_out->initial_cost = ne.cost;
-    double xi[6];
-    if (ne.n_used < o->min_used || !gn_step(ne, o->min_pivot, xi)) {
-      h_out->termination = 2;
-      break;
+    st = align_iter(ne, it, T_io, o, h_out);
+  }
+  if (st == kAlignEndStale) WC_TRY(wc_map_linearize(ctx, m, pts, T_io, &o->reg, &ne, nullptr));
+  align_end(ne, h_out);
+  return WC_OK;
+}
+
+namespace {
+// wc_map_align_batch behind its argument checks.  resume: the hypotheses whose h_status is not WC_OK on entry are skipped - T and status
+// stay, the summary is zero (wc_map_align_pyramid_batch's later levels); otherwise every status starts as WC_OK.
+// Round r: ONE lin_batch_core over the compacted poses of the hypotheses that iterate (r < max_iterations) and of those that ended in
+// round r - 1 and wait for the linearisation at their final T: at most max_iterations + 1 rounds
+int align_batch_core(wc_ctx *ctx, wc_map *m, const wc_points *pts, double *T_io, uint32_t K, const wc_map_align_opts *o, wc_map_align_summary *h_out,
+                     int32_t *h_status, bool resume) {
+  constexpr int kDone = 3;
+  std::vector<int> state(K, kAlignGo);
+  for (uint32_t h = 0; h < K; ++h) {
+    if (resume && h_status[h] != WC_OK) {
+      std::memset(&h_out[h], 0, sizeof(h_out[h]));
+      state[h] = kDone;
+      continue;
     }
-    double T[12];
-    std::memcpy(T, T_io, sizeof(T));
-    pose_update(T, xi);
-    bool finite = true;
-    for (int j = 0; j < 12; ++j) finite = finite && std::isfinite(T[j]);
-    if (!finite) {
-      h_out->termination = 2;
-      break;
-    }
-    std::memcpy(T_io, T, sizeof(T));
-    fresh = false;
-    std::memcpy(h_out->last_step, xi, sizeof(xi));
-    h_out->iterations = (int32_t)(it + 1);
-    const double rot = std::sqrt((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2]), tr = std::sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5]);
-    if (rot <= o->tol_rot && tr <= o->tol_trans) {
-      h_out->termination = 0;
-      break;
+    h_status[h] = WC_OK;
+    align_begin(&h_out[h]);
+  }
+  std::vector<uint32_t> idx;
+  std::vector<double> Tc;
+  std::vector<wc_map_normal_eq> ne;
+  std::vector<int32_t> st;
+  for (uint32_t it = 0;; ++it) {
+    idx.clear(), Tc.clear();
+    for (uint32_t h = 0; h < K; ++h)
+      if (state[h] != kDone) {
+        idx.push_back(h);
+        Tc.insert(Tc.end(), T_io + 12 * (size_t)h, T_io + 12 * (size_t)h + 12);
+      }
+    if (idx.empty()) break;
+    ne.resize(idx.size()), st.resize(idx.size());
+    WC_TRY(lin_batch_core(ctx, m, pts, Tc.data(), (uint32_t)idx.size(), &o->reg, ne.data(), st.data()));
+    for (size_t a = 0; a < idx.size(); ++a) {
+      const uint32_t h = idx[a];
+      if (st[a] != WC_OK) {  // (the single call returns here: T_io and the summary as they stand)
+        h_status[h] = st[a], state[h] = kDone;
+        continue;
+      }
+      // (a hypothesis that ended in the round before: this is the linearisation at its final T)
+      state[h] = state[h] == kAlignGo ? align_iter(ne[a], it, T_io + 12 * (size_t)h, o, &h_out[h]) : kAlignEndFresh;
+      if (state[h] == kAlignEndFresh) {
+        align_end(ne[a], &h_out[h]);
+        state[h] = kDone;
+      }
     }
   }
-  if (!fresh) WC_TRY(wc_map_linearize(ctx, m, pts, T_io, &o->reg, &ne, nullptr));
-  h_out->final_cost = ne.cost;
-  h_out->n_used = ne.n_used, h_out->n_found = ne.n_found;
   return WC_OK;
+}
+}  // namespace
+
+extern "C" int wc_map_align_batch(wc_ctx *ctx, wc_map *m, const wc_points *pts, double *T_io, uint32_t K, const wc_map_align_opts *o,
+                                  wc_map_align_summary *h_out, int32_t *h_status) {
+  wc_dev_guard dg_(ctx);
+  if (!ctx || (K && (!T_io || !h_out || !h_status)) || !align_opts_ok(o))
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (max_iterations >= 1, tol_rot, tol_trans, min_pivot > 0, min_used >= 6)",
+                   __func__);
+  WC_TRY(lin_batch_check(ctx, m, pts, T_io, K, &o->reg, __func__));
+  if (K == 0) return WC_OK;
+  return align_batch_core(ctx, m, pts, T_io, K, o, h_out, h_status, false);
 }
 
 // coarse to fine: one wc_map_align per level, each from the pose the level before it left.  Everything wc_map_align and wc_map_linearize
@@ -1820,6 +2033,48 @@ extern "C" int wc_map_align_pyramid(wc_ctx *ctx, wc_map *const *levels, uint32_t
                    "created without WC_MAP_MOMENTS, its options), or a T_io that is not finite",
                    __func__);
   for (uint32_t l = 0; l < n_levels; ++l) WC_TRY(wc_map_align(ctx, levels[l], pts, T_io, &opts[l], &h_out[l]));
+  return WC_OK;
+}
+
+// K hypotheses coarse to fine: level l is one align_batch_core over the hypotheses whose status is still WC_OK
+extern "C" int wc_map_align_pyramid_batch(wc_ctx *ctx, wc_map *const *levels, uint32_t n_levels, const wc_points *pts, double *T_io, uint32_t K,
+                                          const wc_map_align_opts *opts, wc_map_align_summary *h_out, int32_t *h_status) {
+  wc_dev_guard dg_(ctx);
+  bool ok = ctx && levels && n_levels >= 1 && n_levels <= 8 && opts && !(K && (!T_io || !h_out || !h_status));
+  for (uint32_t l = 0; ok && l < n_levels; ++l) ok = align_opts_ok(&opts[l]);
+  if (!ok)
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (1 <= n_levels <= 8; per level what wc_map_align_batch refuses)", __func__);
+  for (uint32_t l = 0; l < n_levels; ++l) WC_TRY(lin_batch_check(ctx, levels[l], pts, T_io, K, &opts[l].reg, __func__));
+  for (uint32_t l = 0; l < n_levels && K; ++l)
+    WC_TRY(align_batch_core(ctx, levels[l], pts, T_io, K, &opts[l], h_out + (size_t)l * K, h_status, l > 0));
+  return WC_OK;
+}
+
+// ---- the winner of a batch and yaw hypotheses: host only, no context (include/wildcat_hip.h) ------------------------------------------
+extern "C" int wc_map_align_best(const wc_map_align_summary *s, const int32_t *status, uint32_t K, uint64_t min_used, int32_t *best) {
+  if (!best || (K && (!s || !status))) return WC_ERR_ARG;
+  *best = -1;
+  for (uint32_t h = 0; h < K; ++h) {
+    if (status[h] != WC_OK || s[h].termination == 2 || s[h].n_used < min_used || !std::isfinite(s[h].final_cost)) continue;
+    if (*best < 0 || s[h].n_used > s[*best].n_used || (s[h].n_used == s[*best].n_used && s[h].final_cost < s[*best].final_cost)) *best = (int32_t)h;
+  }
+  return WC_OK;
+}
+
+extern "C" int wc_pose_yaw_grid(const double T0[12], uint32_t K, double *T_out) {
+  if (!T0 || (K && !T_out)) return WC_ERR_ARG;
+  for (uint32_t k = 0; k < K; ++k) {
+    double *T = T_out + 12 * (size_t)k;
+    std::memcpy(T, T0, 12 * sizeof(double));
+    if (k == 0) continue;
+    // the angle, its sine and cosine in long double, each rounded to double once: exact to half an ulp of a double
+    const long double ang = (2.0L * 3.14159265358979323846264338327950288L * (long double)k) / (long double)K;
+    const double c = (double)cosl(ang), sn = (double)sinl(ang);
+    for (int j = 0; j < 3; ++j) {
+      T[j] = c * T0[j] - sn * T0[4 + j];
+      T[4 + j] = sn * T0[j] + c * T0[4 + j];
+    }
+  }
   return WC_OK;
 }
 

@@ -524,28 +524,44 @@ bool LidarOdometry::AlignToMap(const float *xyz, size_t n, double T_io[12], cons
   if (summary) *summary = s;
   return true;
 }
-bool LidarOdometry::RelocalizeToMap(const float *xyz, size_t n, double T_io[12], uint32_t factor, uint32_t n_levels, const wc_map_align_opts &finest,
-                                    wc_map_align_summary *summaries) {
-  constexpr uint32_t kMaxLevels = 8;  // wc_map_align_pyramid's
-  if (!map_ || !map_moments_ || !T_io || (n && !xyz) || factor < 1 || n_levels < 1 || n_levels > kMaxLevels) return false;
-  double V = map_voxel_, scale[kMaxLevels] = {1.0};
+namespace {
+constexpr uint32_t kMaxLevels = 8;  // wc_map_align_pyramid's
+// the levels of a relocalisation: levels[0] = the coarsest ... levels[n_levels - 1] = the map itself, built finest first, each from the one
+// before it by wc_map_coarsen(factor); opts[l]: `finest` with reg.max_dist multiplied by (double)factor per level above the map.  false:
+// a level's voxel size would exceed 4.0 (nothing built), or a level could not be built (FreeLevels drops those that were)
+bool BuildLevels(wc_ctx *ctx, wc_map *map, double voxel, uint32_t factor, uint32_t n_levels, const wc_map_align_opts &finest,
+                 wc_map *(&levels)[kMaxLevels], wc_map_align_opts (&opts)[kMaxLevels]) {
+  double V = voxel, scale[kMaxLevels] = {1.0};
   for (uint32_t l = 1; l < n_levels; ++l) {
     V = (double)factor * V;  // (as wc_map_coarsen forms it)
     scale[l] = scale[l - 1] * (double)factor;
     if (!(V <= 4.0)) return false;
   }
-  // levels[0] = the coarsest ... levels[n_levels - 1] = the map itself; built finest first, each from the one before it
-  wc_map *levels[kMaxLevels] = {};
-  wc_map_align_opts opts[kMaxLevels];
-  wc_map_align_summary s[kMaxLevels];
-  levels[n_levels - 1] = map_;
+  levels[n_levels - 1] = map;
   bool ok = true;
   for (uint32_t l = 1; ok && l < n_levels; ++l)
-    ok = wc_map_coarsen(ctx_, levels[n_levels - l], factor, WC_MAP_MOMENTS, &levels[n_levels - 1 - l]) == WC_OK;
+    ok = wc_map_coarsen(ctx, levels[n_levels - l], factor, WC_MAP_MOMENTS, &levels[n_levels - 1 - l]) == WC_OK;
   for (uint32_t l = 0; l < n_levels; ++l) {
     opts[n_levels - 1 - l] = finest;
     opts[n_levels - 1 - l].reg.max_dist = finest.reg.max_dist * scale[l];
   }
+  return ok;
+}
+void FreeLevels(wc_ctx *ctx, wc_map *(&levels)[kMaxLevels], uint32_t n_levels) {
+  for (uint32_t l = 0; l + 1 < n_levels; ++l)
+    if (levels[l]) {
+      const int rc = wc_map_destroy(ctx, levels[l]);
+      if (rc != WC_OK) FatalCall(ctx, "wc_map_destroy", rc);
+    }
+}
+}  // namespace
+bool LidarOdometry::RelocalizeToMap(const float *xyz, size_t n, double T_io[12], uint32_t factor, uint32_t n_levels, const wc_map_align_opts &finest,
+                                    wc_map_align_summary *summaries) {
+  if (!map_ || !map_moments_ || !T_io || (n && !xyz) || factor < 1 || n_levels < 1 || n_levels > kMaxLevels) return false;
+  wc_map *levels[kMaxLevels] = {};
+  wc_map_align_opts opts[kMaxLevels];
+  wc_map_align_summary s[kMaxLevels];
+  bool ok = BuildLevels(ctx_, map_, map_voxel_, factor, n_levels, finest, levels, opts);
   double T[12];
   std::memcpy(T, T_io, sizeof(T));
   if (ok) {
@@ -553,11 +569,34 @@ bool LidarOdometry::RelocalizeToMap(const float *xyz, size_t n, double T_io[12],
     const wc_points desc = UploadXyz(d_xyz, xyz, n);
     ok = wc_map_align_pyramid(ctx_, levels, n_levels, &desc, T, opts, s) == WC_OK;  // (as in AlignToMap)
   }
-  for (uint32_t l = 0; l + 1 < n_levels; ++l)
-    if (levels[l]) WC_CALL(wc_map_destroy(ctx_, levels[l]));
+  FreeLevels(ctx_, levels, n_levels);
   if (!ok) return false;
   std::memcpy(T_io, T, sizeof(T));
   if (summaries) std::memcpy(summaries, s, n_levels * sizeof(s[0]));
+  return true;
+}
+bool LidarOdometry::RelocalizeSearch(const float *xyz, size_t n, double T_io[12], uint32_t n_yaw, uint32_t factor, uint32_t n_levels,
+                                     const wc_map_align_opts &finest, wc_map_align_summary *summaries, int32_t *best) {
+  if (!map_ || !map_moments_ || !T_io || (n && !xyz) || factor < 1 || n_levels < 1 || n_levels > kMaxLevels || n_yaw < 1 || n_yaw > 1024)
+    return false;
+  wc_map *levels[kMaxLevels] = {};
+  wc_map_align_opts opts[kMaxLevels];
+  std::vector<double> T((size_t)n_yaw * 12);
+  std::vector<wc_map_align_summary> s((size_t)n_levels * n_yaw);
+  std::vector<int32_t> status(n_yaw);
+  bool ok = BuildLevels(ctx_, map_, map_voxel_, factor, n_levels, finest, levels, opts) && wc_pose_yaw_grid(T_io, n_yaw, T.data()) == WC_OK;
+  if (ok) {
+    const DevBuf d_xyz(ctx_, n * 3 * sizeof(float));
+    const wc_points desc = UploadXyz(d_xyz, xyz, n);
+    ok = wc_map_align_pyramid_batch(ctx_, levels, n_levels, &desc, T.data(), n_yaw, opts, s.data(), status.data()) == WC_OK;  // (as in AlignToMap)
+  }
+  FreeLevels(ctx_, levels, n_levels);
+  int32_t win = -1;
+  ok = ok && wc_map_align_best(s.data() + (size_t)(n_levels - 1) * n_yaw, status.data(), n_yaw, finest.min_used, &win) == WC_OK && win >= 0;
+  if (!ok) return false;
+  std::memcpy(T_io, T.data() + (size_t)win * 12, 12 * sizeof(double));
+  if (summaries) std::memcpy(summaries, s.data(), s.size() * sizeof(s[0]));
+  if (best) *best = win;
   return true;
 }
 bool LidarOdometry::LinearizeAgainstMap(const float *xyz, size_t n, const double T[12], const wc_map_reg_params &params, wc_map_normal_eq *out,

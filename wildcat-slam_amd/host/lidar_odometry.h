@@ -112,6 +112,14 @@ class LidarOdometry {
   // size would exceed 4.0.  Nothing in AddLidarScan calls it
   bool RelocalizeToMap(const float *xyz, size_t n, double T_io[12], uint32_t factor, uint32_t n_levels, const wc_map_align_opts &finest,
                        wc_map_align_summary *summaries);
+  // RelocalizeToMap when the heading is unknown: n_yaw starts T_k = (Rz(2 pi k / n_yaw) R | t) of T_io (wc_pose_yaw_grid), all of them through
+  // the levels RelocalizeToMap builds in ONE wc_map_align_pyramid_batch, the winner chosen by wc_map_align_best on the finest level with
+  // finest.min_used; T_io becomes the winner's pose and the built levels are destroyed.  summaries (may be null): n_levels x n_yaw records,
+  // level-major, coarsest first; best (may be null): the winner's index.  false - nothing touched - where RelocalizeToMap returns false, for
+  // n_yaw outside 1 .. 1024, and when no hypothesis is eligible.  n_yaw = 1 gives RelocalizeToMap's pose byte for byte.  Nothing in
+  // AddLidarScan calls it
+  bool RelocalizeSearch(const float *xyz, size_t n, double T_io[12], uint32_t n_yaw, uint32_t factor, uint32_t n_levels,
+                        const wc_map_align_opts &finest, wc_map_align_summary *summaries, int32_t *best);
   // one linearisation at T (wc_map_linearize): *out, and rows[n] when rows is not null; false as AlignToMap
   bool LinearizeAgainstMap(const float *xyz, size_t n, const double T[12], const wc_map_reg_params &params, wc_map_normal_eq *out,
                            wc_map_reg_row *rows);

@@ -230,6 +230,12 @@ int wc_odom_map_relocalize(void *h, const float *xyz, uint64_t n, double T_io[12
                            const wc_map_align_opts *finest, wc_map_align_summary *summaries) {
   return finest && ((LidarOdometry *)h)->RelocalizeToMap(xyz, n, T_io, factor, n_levels, *finest, summaries) ? 1 : 0;
 }
+// LidarOdometry::RelocalizeSearch; summaries: n_levels x n_yaw records, level-major (may be null); best: the winner's index (may be null);
+// 1 = done, 0 = as wc_odom_map_relocalize, n_yaw outside 1 .. 1024, or no eligible hypothesis
+int wc_odom_map_relocalize_search(void *h, const float *xyz, uint64_t n, double T_io[12], uint32_t n_yaw, uint32_t factor, uint32_t n_levels,
+                                  const wc_map_align_opts *finest, wc_map_align_summary *summaries, int32_t *best) {
+  return finest && ((LidarOdometry *)h)->RelocalizeSearch(xyz, n, T_io, n_yaw, factor, n_levels, *finest, summaries, best) ? 1 : 0;
+}
 int wc_odom_map_linearize(void *h, const float *xyz, uint64_t n, const double T[12], const wc_map_reg_params *params, wc_map_normal_eq *out,
                           wc_map_reg_row *rows) {
   return params && ((LidarOdometry *)h)->LinearizeAgainstMap(xyz, n, T, *params, out, rows) ? 1 : 0;

@@ -683,6 +683,64 @@ def map_align_pyramid(levels, points, T, opts_list=None, params=None, **kw):
         return map_align_pyramid_device(levels, desc, T, opts_list)
 
 
+def _poses12(Ts):
+    """K poses, each 3 x 4 (or 4 x 4) row-major -> (K, 12) float64, a fresh contiguous array"""
+    Ts = np.asarray(Ts, np.float64)
+    K = len(Ts)
+    Ts = Ts.reshape(K, -1)[:, :12] if K else np.zeros((0, 12))
+    assert Ts.shape == (K, 12), "Ts: K poses, each 3 x 4 (or 4 x 4) row-major"
+    return np.ascontiguousarray(Ts).copy()
+
+
+def map_align_pyramid_batch_device(levels, desc, Ts, opts_list):
+    """wc_map_align_pyramid_batch on points already in HBM: K starts Ts through the maps of `levels` (coarsest first), level l with
+    opts_list[l] -> (Ts (K, 3, 4), [[summary dict per hypothesis] per level], status (K,) int32: 0, or the error code of a hypothesis
+    that was dropped on the way - its later summaries are zero)"""
+    n = len(levels)
+    assert n >= 1 and len(opts_list) == n, "one wc_map_align_opts per level"
+    ctx = levels[0].ctx
+    Ts = _poses12(Ts)
+    K = len(Ts)
+    handles = (C.c_void_p * n)(*[m.h.value for m in levels])
+    opts, summ, status = (R.MapAlignOpts * n)(*opts_list), (R.MapAlignSummary * max(n * K, 1))(), np.zeros(K, np.int32)
+    ctx._ck(ctx.lib.wc_map_align_pyramid_batch(ctx.h, handles, C.c_uint32(n), C.byref(desc), R.ptr(Ts), C.c_uint32(K), opts, summ, R.ptr(status)))
+    return Ts.reshape(K, 3, 4), [[_summary_dict(summ[l * K + h]) for h in range(K)] for l in range(n)], status
+
+
+def map_align_pyramid_batch(levels, points, Ts, opts_list=None, params=None, **kw):
+    """map_align_pyramid for K starts in one pass: POINT records or an (n, 3) float32 array against the maps of `levels`, coarsest first
+    -> as map_align_pyramid_batch_device; opts_list: one wc_map_align_opts per level, or map_pyramid_opts(levels, params, **kw)"""
+    if opts_list is None:
+        opts_list = map_pyramid_opts(levels, params, **kw)
+    with levels[0]._uploaded(points) as (desc, _):
+        return map_align_pyramid_batch_device(levels, desc, Ts, opts_list)
+
+
+def map_align_best(summaries, status, min_used):
+    """wc_map_align_best (needs no GPU): the winner among K summaries (dicts with termination, n_used, final_cost) with their statuses
+    -> its index, or -1 when no hypothesis is eligible.  Most inliers first, then the lower cost, then the lower index"""
+    K = len(summaries)
+    summ, best = (R.MapAlignSummary * max(K, 1))(), C.c_int32(0)
+    for h, d in enumerate(summaries):
+        summ[h].termination, summ[h].n_used, summ[h].final_cost = int(d["termination"]), int(d["n_used"]), float(d["final_cost"])
+    status = np.ascontiguousarray(status, np.int32).reshape(-1)
+    assert len(status) == K
+    rc = load().wc_map_align_best(summ, R.ptr(status) if K else None, C.c_uint32(K), C.c_uint64(int(min_used)), C.byref(best))
+    if rc != WC_OK:
+        raise WildcatError(rc, "wc_map_align_best refused its arguments")
+    return int(best.value)
+
+
+def pose_yaw_grid(T, K):
+    """wc_pose_yaw_grid (needs no GPU): K starts (Rz(2 pi k / K) R | t) of the pose T = (R | t) -> (K, 3, 4); entry 0 is T itself"""
+    T, K = _pose12(T), int(K)
+    out = np.zeros((K, 12))
+    rc = load().wc_pose_yaw_grid(R.ptr(T), C.c_uint32(K), R.ptr(out) if K else None)
+    if rc != WC_OK:
+        raise WildcatError(rc, "wc_pose_yaw_grid refused its arguments")
+    return out.reshape(K, 3, 4)
+
+
 class PointMap:
     """wc_map: the device-resident voxel-downsampled map (DownSamplingVoxel, surfel_extraction.cc:228-261, over every insert)"""
 
@@ -1003,6 +1061,43 @@ class PointMap:
         with self._uploaded(points) as (desc, _):
             return self.align_device(desc, T, opts)
 
+    def linearize_batch_device(self, desc, Ts, params):
+        """wc_map_linearize_batch on points already in HBM: K poses Ts -> (MAP_NORMAL_EQ array (K,), status (K,) int32); record h is
+        byte-equal to linearize_device's for pose h where status[h] is 0, and zero where it is not"""
+        Ts = _poses12(Ts)
+        K = len(Ts)
+        out, status = np.zeros(K, R.MAP_NORMAL_EQ), np.zeros(K, np.int32)
+        self.ctx._ck(self.lib.wc_map_linearize_batch(self.ctx.h, self.h, C.byref(desc), R.ptr(Ts) if K else None, C.c_uint32(K), C.byref(params),
+                                                     R.ptr(out) if K else None, R.ptr(status) if K else None))
+        return out, status
+
+    def linearize_batch(self, points, Ts, params=None, **kw):
+        """POINT records or an (n, 3) float32 array (uploaded for the call) and K poses -> as linearize_batch_device; params: a
+        wc_map_reg_params, or its fields as keywords (max_dist defaults to the voxel size)"""
+        if params is None:
+            kw.setdefault("max_dist", self.voxel)
+            params = map_reg_params(**kw)
+        with self._uploaded(points) as (desc, _):
+            return self.linearize_batch_device(desc, Ts, params)
+
+    def align_batch_device(self, desc, Ts, opts):
+        """wc_map_align_batch on points already in HBM: K starts in lockstep -> (Ts (K, 3, 4), [summary dict per hypothesis], status (K,)
+        int32), each hypothesis as align_device leaves it"""
+        Ts = _poses12(Ts)
+        K = len(Ts)
+        summ, status = (R.MapAlignSummary * max(K, 1))(), np.zeros(K, np.int32)
+        self.ctx._ck(self.lib.wc_map_align_batch(self.ctx.h, self.h, C.byref(desc), R.ptr(Ts) if K else None, C.c_uint32(K), C.byref(opts), summ,
+                                                 R.ptr(status) if K else None))
+        return Ts.reshape(K, 3, 4), [_summary_dict(summ[h]) for h in range(K)], status
+
+    def align_batch(self, points, Ts, opts=None, params=None, **kw):
+        """align for K starts in one pass (at most max_iterations + 1 rounds of one linearize_batch each) -> as align_batch_device; opts
+        and params as align's"""
+        if opts is None:
+            opts = map_align_opts(params if params is not None else map_reg_params(self.voxel), **kw)
+        with self._uploaded(points) as (desc, _):
+            return self.align_batch_device(desc, Ts, opts)
+
     def clear(self):
         self.ctx._ck(self.lib.wc_map_clear(self.ctx.h, self.h))
 
@@ -1168,6 +1263,21 @@ class Odometry:
                                                                           C.c_uint32(n_levels), C.byref(opts), summ):
             return None
         return T.reshape(3, 4), [_summary_dict(s) for s in summ]
+
+    def map_relocalize_search(self, xyz, T, n_yaw, factor, n_levels, opts):
+        """map_relocalize when the heading is unknown (LidarOdometry::RelocalizeSearch): n_yaw starts pose_yaw_grid(T, n_yaw) through the
+        levels in one batched pass, the winner by map_align_best on the finest level with opts.min_used -> (T (3, 4) of the winner,
+        [[summary dict per hypothesis] per level, coarsest first], the winner's index), or None where map_relocalize returns None, for
+        n_yaw outside 1 .. 1024, or when no hypothesis is eligible"""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n_levels, K = int(n_levels), int(n_yaw)
+        if not 1 <= n_levels <= 8 or not 1 <= K <= 1024:
+            return None
+        T, summ, best = _pose12(T), (R.MapAlignSummary * (n_levels * K))(), C.c_int32(-1)
+        if not self.lib.wc_odom_map_relocalize_search(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), R.ptr(T), C.c_uint32(K), C.c_uint32(int(factor)),
+                                                      C.c_uint32(n_levels), C.byref(opts), summ, C.byref(best)):
+            return None
+        return T.reshape(3, 4), [[_summary_dict(summ[l * K + h]) for h in range(K)] for l in range(n_levels)], int(best.value)
 
     def map_save(self, path):
         """the map's exact state as the canonical file of host/map_file.h (LidarOdometry::SaveMap) -> True, or False without a map or
