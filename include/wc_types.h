@@ -170,6 +170,19 @@ typedef struct wc_map_align_summary { /* 88 bytes */
   double last_step[6];  /* the last update applied (omega, upsilon); 0 if none                       */
 } wc_map_align_summary;
 
+/* wc_map_score_batch (wildcat_hip.h: "occupancy score of pose hypotheses"; not reference types) */
+typedef struct wc_map_score { /* 16 bytes: one hypothesis */
+  uint32_t n_hit;    /* points whose own voxel is live in the map with count >= min_points              */
+  uint32_t n_in;     /* points moved to a voxel inside the key range, |k| < 2^20 on every axis          */
+  uint32_t n_bad;    /* finite points the pose sent to a non-finite one                                 */
+  uint32_t reserved; /* written as 0                                                                    */
+} wc_map_score;
+
+typedef struct wc_map_score_params { /* 8 bytes */
+  uint32_t min_points; /* >= 1: a voxel counts when it holds at least this many points */
+  uint32_t reserved;   /* 0, anything else WC_ERR_ARG                                   */
+} wc_map_score_params;
+
 /* wc_map_carve (wildcat_hip.h): which rays of a call are used and what they select. */
 typedef struct wc_map_carve_params { /* 32 bytes */
   double min_range;   /* [m] 0 <= min_range <= max_range: a ray is used iff min_range^2 <= |p - origin|^2 <= max_range^2   */

@@ -70,6 +70,8 @@ int wc_ctx_set_params(wc_ctx *ctx, const wc_params *params);
  *                      insert's tiles of 512 points, 108 KB of LDS, one workgroup per CU (same sums either way)
  *   map_lin_groups (0) wc_map_linearize and wc_map_linearize_batch: workgroups of the first kernel (0: chosen from the point count and
  *                      K); H, g and cost are byte-equal whatever the value
+ *   map_score_groups (0) wc_map_score_batch: workgroups of its kernel (0: chosen from the point count and K); every record is the same
+ *                      whatever the value
  *   map_carve_groups (0) wc_map_carve: workgroups of its ray kernel (0: chosen from the point count); the five counts are the same
  *                      whatever the value
  *   map_cast_groups (0) wc_map_raycast: workgroups of its kernel (0: chosen from the point count); every output byte is the same
@@ -692,6 +694,39 @@ int wc_map_align_best(const wc_map_align_summary *s, const int32_t *status, uint
  * cosine are rounded once from extended precision; an entry is c r - s r' or s r + c r' (two rounded products and one sum).  K == 0:
  * nothing is written.  WC_ERR_ARG: a NULL argument (T_out may be NULL when K == 0). */
 int wc_pose_yaw_grid(const double T0[12], uint32_t K, double *T_out);
+
+/* occupancy score of pose hypotheses ------------------------------------------------------------------------------------ */
+/* For K poses of ONE point set, how many points land in an occupied voxel of the map: T is K x 12 doubles on the HOST, h_out K records on
+ * the host.  Hypothesis h has the pose T + 12 h.  One point, with x, y, z its floats cast to double and no fused multiply-add anywhere:
+ *   P_a = ((T[4a] x + T[4a+1] y) + T[4a+2] z) + T[4a+3],  q_a = (float)P_a          (wc_map_linearize's lines: one device function)
+ *   a point with a non-finite coordinate counts nowhere; a finite point whose q is not finite counts in n_bad; otherwise
+ *   k_a = floor((double)q_a / v), true fp64 division (wc_map_insert's rule: one function); the point counts in n_in iff |k_a| < 2^20
+ *   on every axis, and in n_hit iff, further, voxel k is live in the table - neither empty nor removed - and holds at least
+ *   params->min_points points.
+ * The point's own voxel only: one probe chain per (point, pose), no neighbourhood, no plane; plain and WC_MAP_MOMENTS maps alike.
+ * The counts are integers: every record is the same for every grid size (development option map_score_groups), schedule and run, and a
+ * restatement reproduces it byte for byte.  reserved is written as 0.  One copy of K x 16 bytes travels back and the call waits once; the
+ * map and the scratch of its other calls are only read.
+ * WC_ERR_ARG, h_out untouched: a NULL argument; a non-finite entry of T; min_points = 0 or reserved != 0 in params; a points descriptor
+ * wc_map_insert refuses; a map of another context; n >= 2^31; K > 2^20.
+ * WC_ERR_CAPACITY, h_out untouched: K * n > 2^34 (point, pose) pairs, checked before anything is read.  Both caps are design choices, not
+ * measurements.
+ * K == 0: WC_OK, nothing is touched or launched (T and h_out may be NULL).  pts->n == 0: every record zero.  An empty map: n_hit = 0, n_in
+ * and n_bad as defined. */
+int wc_map_score_batch(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double *T, uint32_t K, const wc_map_score_params *params,
+                       wc_map_score *h_out);
+/* Pose hypotheses on a lattice of headings and positions; host only, no context, no GPU.  K = n_yaw * n[0] * n[1] * n[2] poses, pose
+ * ((k n[0] + i0) n[1] + i1) n[2] + i2 = (R_k | t): R_k the rotation of wc_pose_yaw_grid(T0, n_yaw)'s entry k, bitwise, and
+ *   t_a = t0_a + ((double)(2 i_a - (n[a] - 1)) * 0.5) * step[a]       (the integer and the half are exact: one rounded product, one rounded sum)
+ * - the lattice is centred on t0 in WORLD axes.  n[a] = 1 gives t0_a itself, except that -0.0 becomes +0.0.
+ * WC_ERR_ARG, T_out untouched: a NULL argument; n_yaw or an n[a] of 0; K > 2^20; a step that is negative or not finite; a non-finite entry
+ * of T0. */
+int wc_pose_grid(const double T0[12], uint32_t n_yaw, const uint32_t n[3], const double step[3], double *T_out);
+/* The M best of K scores; host only, no context, no GPU.  Hypothesis h is eligible iff n_bad == 0 and n_hit >= min_hit.  Order: larger
+ * n_hit first, then the smaller index.  idx_out (M entries) receives the first min(M, eligible) indices in that order and -1 in the rest;
+ * *n_out receives that count.  There is no non-maximum suppression: the neighbours of a peak may fill the list.
+ * WC_ERR_ARG: a NULL n_out; a NULL scores with K > 0; a NULL idx_out with M > 0. */
+int wc_map_score_top(const wc_map_score *scores, uint32_t K, uint32_t M, uint32_t min_hit, int32_t *idx_out, uint32_t *n_out);
 
 #ifdef __cplusplus
 }

@@ -73,6 +73,7 @@ const DevOpt kDevOpts[] = {
     {"lm_side_stream", "WC_LM_SIDE_STREAM", &wc_dev_opts::lm_side_stream, false},
     {"map_mom_pts", "WC_MAP_MOM_PTS", &wc_dev_opts::map_mom_pts, false},
     {"map_lin_groups", "WC_MAP_LIN_GROUPS", &wc_dev_opts::map_lin_groups, false},
+    {"map_score_groups", "WC_MAP_SCORE_GROUPS", &wc_dev_opts::map_score_groups, false},
     {"map_carve_groups", "WC_MAP_CARVE_GROUPS", &wc_dev_opts::map_carve_groups, false},
     {"map_cast_groups", "WC_MAP_CAST_GROUPS", &wc_dev_opts::map_cast_groups, false},
     {"map_absorb_groups", "WC_MAP_ABSORB_GROUPS", &wc_dev_opts::map_absorb_groups, false},

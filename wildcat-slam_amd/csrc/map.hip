@@ -32,6 +32,9 @@
 //                   fixed order (tiles of 256 points, then levels of 32 partials, one launch each): wc_map_linearize, wc_map_align
 //   k_map_linearize_batch / k_map_lin_reduce_batch  the same for K poses of one point set in one launch chain, (hypothesis, tile) pairs
 //                   as work items, the tile body shared with k_map_linearize: wc_map_linearize_batch, wc_map_align_batch
+//   k_map_score_batch  occupancy score of K poses of one point set: a tile of 256 points in registers walks a block of hypotheses, one
+//                   read-only probe chain per (point, pose), eight hypotheses' first-slot key loads in flight; counts by ballot, LDS and one
+//                   32-bit atomic add per workgroup, hypothesis and count: wc_map_score_batch
 //   k_map_carve    carving: one lane per ray from the call's origin to a point: the end voxel's word gets its mark, then the counted voxel
 //                   walk, eight steps ahead of the probes: keys, hashes and shell tests of a batch, its first-slot key loads issued
 //                   together, then the chains (read-only) and one no-return atomic add per occupied voxel seen through;
@@ -49,7 +52,8 @@
 //                   new map of wc_map_coarsen, factor^3 voxels to one
 // Shared pieces: map_voxel_of (the voxel-index rule, host and device), map_find_from (the read-only probe chain), block_count (a
 // workgroup's counters), map_points_ok (a wc_points argument), map_replace_table (new table, rehash, free the old one), map_ray_of /
-// map_ray_begin / map_ray_step (a ray's setup and the step rule of its voxel walk: the carve and the ray cast)
+// map_ray_begin / map_ray_step (a ray's setup and the step rule of its voxel walk: the carve and the ray cast), map_move (a point through
+// a pose: the registration and the score)
 // Growth policy: before an insert of n points the host takes an upper bound B of the occupied slots (the exact count of the last
 // completed insert's read-back plus every point inserted after it); when 2 (B + n) > cap the table is rehashed into the smallest power
 // of two >= 2 (B + n) slots.  The table is therefore at most half full at every probe, and an insert never runs out of room.
@@ -98,6 +102,9 @@ struct wc_map {
   unsigned long long *h_carve = nullptr;  // ... and the pinned landing place of the counters (first use)
   wc_buf b_cast;                     // wc_map_raycast: its four counter lines (first use); nothing another call reads or writes
   unsigned long long *h_cast = nullptr;  // ... and their pinned landing place (first use)
+  wc_buf b_score;                    // wc_map_score_batch: K x 16 bytes of counts, then the K x 12 doubles of the poses; its own scratch
+  unsigned char *h_score = nullptr;  // ... and the pinned block of the same layout, grown on demand: it holds h_score_cap hypotheses
+  uint64_t h_score_cap = 0;
 };
 
 namespace {
@@ -670,6 +677,15 @@ struct map_reg {
   unsigned min_points;
 };
 
+// a point through a pose: q_a = (float)(((T[4a] x + T[4a+1] y) + T[4a+2] z) + T[4a+3]) with x, y, z the floats cast to double - the
+// registration's and the score's one copy (include/wildcat_hip.h states the association; -ffp-contract=off: no fused multiply-add)
+__device__ __forceinline__ void map_move(const double (&T)[12], float px, float py, float pz, float &qx, float &qy, float &qz) {
+  const double x0 = (double)px, y0 = (double)py, z0 = (double)pz;
+  qx = (float)(((T[0] * x0 + T[1] * y0) + T[2] * z0) + T[3]);
+  qy = (float)(((T[4] * x0 + T[5] * y0) + T[6] * z0) + T[7]);
+  qz = (float)(((T[8] * x0 + T[9] * y0) + T[10] * z0) + T[11]);
+}
+
 // one tile: the body k_map_linearize and k_map_linearize_batch share.  T: the pose (workgroup uniform); out: the tile's 256-byte partial;
 // rows: NULL or the call's wc_map_reg_row array; s_row, s_chunk, s_cnt: the workgroup's LDS (kLinFields * kLinPitch and kLinSums * 8
 // doubles, 3 words).  Every lane of the workgroup calls it
@@ -685,10 +701,8 @@ __device__ __forceinline__ void map_lin_tile(const wc_points &pts, const double 
   if (i < pts.n) {
     const float *f = (const float *)((const char *)pts.xyz + i * pts.xyz_stride);
     const float px = f[0], py = f[1], pz = f[2];
-    const double x0 = (double)px, y0 = (double)py, z0 = (double)pz;
-    const float qx = (float)(((T[0] * x0 + T[1] * y0) + T[2] * z0) + T[3]);
-    const float qy = (float)(((T[4] * x0 + T[5] * y0) + T[6] * z0) + T[7]);
-    const float qz = (float)(((T[8] * x0 + T[9] * y0) + T[10] * z0) + T[11]);
+    float qx, qy, qz;
+    map_move(T, px, py, pz, qx, qy, qz);
     bad = isfinite(px) && isfinite(py) && isfinite(pz) && !(isfinite(qx) && isfinite(qy) && isfinite(qz));
     const double x = (double)qx, y = (double)qy, z = (double)qz;
     const map_found w = map_search<true>(x, y, z, v, keys, pay, mask);
@@ -787,6 +801,88 @@ __global__ void __launch_bounds__(kLinThreads) k_map_linearize_batch(wc_points p
 #pragma unroll
     for (int j = 0; j < 12; ++j) T[j] = Tp[j];
     map_lin_tile(pts, T, R, v, keys, pay, mom, mask, nullptr, tile, part + h * hyp_words + (size_t)tile * kLinWords, s_row, s_chunk, s_cnt);
+  }
+}
+
+// ---- occupancy score of pose hypotheses (wc_map_score_batch: DESIGN 8.11) -----------------------------------------------------------
+// A workgroup keeps ONE tile of 256 points in registers, one point per lane, and walks a block of kScoreBlock hypotheses with it.  A work
+// item is a (hypothesis block, tile) pair, item = block * tiles + tile: neighbouring workgroups share the poses and read neighbouring
+// tiles.  The pose of a hypothesis is read at an address the whole workgroup shares (scalar loads).  BATCH hypotheses go together: their
+// moved points, keys, hashes and first-slot key loads first, then the chains and the count loads.  The three counts of a hypothesis: ballot
+// and popcount per wavefront, integer adds in LDS across the four wavefronts, then one 32-bit atomic add per workgroup, hypothesis and
+// non-zero count into out (K x 4 words, zeroed ahead of the launch).  Integer adds commute: the records do not depend on the grid, the
+// schedule or the run, and the launch boundary is the hand-off.
+constexpr int kScoreThreads = 256;
+constexpr int kScoreBlock = 32;  // hypotheses one work item walks with its tile
+constexpr int kScoreBatch = 8;   // hypotheses whose first-slot key loads are in flight together (as kCarveBatch, kCastBatch)
+template <int BATCH>
+__global__ void __launch_bounds__(kScoreThreads) k_map_score_batch(wc_points pts, const double *__restrict__ poses, unsigned K, double v,
+                                                                   const unsigned long long *__restrict__ keys, const long long *__restrict__ pay,
+                                                                   unsigned long long mask, unsigned min_points, unsigned *out) {
+  static_assert(kScoreBlock % BATCH == 0, "a block is a whole number of batches");
+  __shared__ unsigned s_cnt[kScoreBlock * 3];
+  const int t = threadIdx.x;
+  const unsigned long long tiles = (pts.n + kScoreThreads - 1) / kScoreThreads;
+  const unsigned long long items = (unsigned long long)((K + kScoreBlock - 1) / kScoreBlock) * tiles;  // (<= 2^15 * 2^23)
+  if (t < kScoreBlock * 3) s_cnt[t] = 0;
+  for (unsigned long long item = blockIdx.x; item < items; item += gridDim.x) {
+    const unsigned long long blk = item / tiles, tile = item - blk * tiles;
+    const unsigned h_first = (unsigned)blk * kScoreBlock;
+    const unsigned h_count = K - h_first < (unsigned)kScoreBlock ? K - h_first : (unsigned)kScoreBlock;
+    __syncthreads();  // (the zeros of s_cnt are in place: the first ones, or those the previous item's readers left)
+    const unsigned long long i = tile * kScoreThreads + t;
+    float px = 0.0f, py = 0.0f, pz = 0.0f;
+    bool valid = false;
+    if (i < pts.n) {
+      const float *f = (const float *)((const char *)pts.xyz + i * pts.xyz_stride);
+      px = f[0], py = f[1], pz = f[2];
+      valid = isfinite(px) && isfinite(py) && isfinite(pz);
+    }
+    for (unsigned b = 0; b < h_count; b += BATCH) {
+      unsigned long long key[BATCH], slot[BATCH], first[BATCH];
+      bool in[BATCH], bad[BATCH];
+#pragma unroll
+      for (int j = 0; j < BATCH; ++j) {
+        in[j] = bad[j] = false;
+        key[j] = slot[j] = 0, first[j] = kMapEmpty;
+        if (b + j < h_count) {  // (workgroup uniform)
+          const double *Tp = poses + (size_t)(h_first + b + j) * 12;
+          double T[12];
+#pragma unroll
+          for (int e = 0; e < 12; ++e) T[e] = Tp[e];
+          float qx, qy, qz;
+          map_move(T, px, py, pz, qx, qy, qz);
+          const bool fin = isfinite(qx) && isfinite(qy) && isfinite(qz);
+          int kx, ky, kz;
+          const bool ok = map_voxel_of((double)qx, (double)qy, (double)qz, v, kx, ky, kz);  // (false for a non-finite q: the compares fail)
+          bad[j] = valid && !fin;
+          in[j] = valid && fin && ok;
+          key[j] = map_pack(kx, ky, kz);
+          slot[j] = map_hash(key[j]) & mask;  // (always inside the table: the load below needs no further bound)
+          if (in[j]) first[j] = keys[slot[j]];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < BATCH; ++j) {
+        if (b + j < h_count) {
+          bool hit = false;
+          if (in[j] && map_find_from(keys, mask, key[j], slot[j], first[j])) hit = (unsigned long long)pay[4 * slot[j] + 3] >= min_points;
+          const unsigned n_h = (unsigned)__popcll(__ballot(hit)), n_i = (unsigned)__popcll(__ballot(in[j])),
+                         n_b = (unsigned)__popcll(__ballot(bad[j]));
+          if ((t & 63) == 0) {
+            if (n_h) atomicAdd(&s_cnt[(b + j) * 3 + 0], n_h);
+            if (n_i) atomicAdd(&s_cnt[(b + j) * 3 + 1], n_i);
+            if (n_b) atomicAdd(&s_cnt[(b + j) * 3 + 2], n_b);
+          }
+        }
+      }
+    }
+    __syncthreads();
+    if (t < kScoreBlock * 3) {
+      const unsigned c = s_cnt[t], hl = (unsigned)t / 3;
+      s_cnt[t] = 0;
+      if (c && hl < h_count) atomicAdd(out + (size_t)(h_first + hl) * 4 + ((unsigned)t - 3 * hl), c);
+    }
   }
 }
 
@@ -1393,6 +1489,7 @@ extern "C" int wc_map_destroy(wc_ctx *ctx, wc_map *m) {
   wc_buf_release(ctx, m->b_pose);
   wc_buf_release(ctx, m->b_carve);
   wc_buf_release(ctx, m->b_cast);
+  wc_buf_release(ctx, m->b_score);
   (void)hipStreamSynchronize(ctx->stream);  // (the pinned counters may still be the target of an enqueued copy)
   if (m->ev_ctr) (void)hipEventDestroy(m->ev_ctr);
   if (m->h_ctr) (void)hipHostFree(m->h_ctr);
@@ -1401,6 +1498,7 @@ extern "C" int wc_map_destroy(wc_ctx *ctx, wc_map *m) {
   if (m->h_pose) (void)hipHostFree(m->h_pose);
   if (m->h_carve) (void)hipHostFree(m->h_carve);
   if (m->h_cast) (void)hipHostFree(m->h_cast);
+  if (m->h_score) (void)hipHostFree(m->h_score);
   delete m;
   return WC_OK;
 }
@@ -2075,6 +2173,91 @@ extern "C" int wc_pose_yaw_grid(const double T0[12], uint32_t K, double *T_out) 
       T[4 + j] = sn * T0[j] + c * T0[4 + j];
     }
   }
+  return WC_OK;
+}
+
+// ---- occupancy score of pose hypotheses (include/wildcat_hip.h: wc_map_score_batch, wc_pose_grid, wc_map_score_top) ------
+namespace {
+constexpr uint32_t kScoreMaxK = 1u << 20;        // hypotheses of one call, and poses of one wc_pose_grid
+constexpr uint64_t kScoreMaxPairs = 1ull << 34;  // (point, pose) pairs of one call: both are design caps
+}  // namespace
+
+extern "C" int wc_map_score_batch(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double *T, uint32_t K, const wc_map_score_params *params,
+                                  wc_map_score *h_out) {
+  wc_dev_guard dg_(ctx);
+  if (!map_ok(ctx, m) || !map_points_ok(pts) || !params || params->min_points == 0 || params->reserved != 0 || (K && (!T || !h_out)) ||
+      pts->n >= ((uint64_t)1 << 31) || K > kScoreMaxK)
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (n < 2^31, K <= 2^20, min_points >= 1, reserved = 0), or a map of another context",
+                   __func__);
+  for (uint64_t j = 0; j < (uint64_t)K * 12; ++j)
+    if (!std::isfinite(T[j]))
+      return wc_fail(ctx, WC_ERR_ARG, "%s: entry %u of hypothesis %u's T is not finite", __func__, (unsigned)(j % 12), (unsigned)(j / 12));
+  if ((uint64_t)K * pts->n > kScoreMaxPairs) return wc_fail(ctx, WC_ERR_CAPACITY, "%s: K * n exceeds 2^34", __func__);
+  if (K == 0) return WC_OK;
+  if (pts->n == 0) {
+    std::memset(h_out, 0, (size_t)K * sizeof(*h_out));
+    return WC_OK;
+  }
+  const size_t cnt_bytes = (size_t)K * sizeof(wc_map_score), pose_bytes = (size_t)K * 12 * sizeof(double);
+  WC_TRY(wc_ensure(ctx, m->b_score, cnt_bytes + pose_bytes));
+  if (m->h_score_cap < K) {
+    if (m->h_score) (void)hipHostFree(m->h_score);
+    m->h_score = nullptr, m->h_score_cap = 0;
+    WC_HIP(ctx, hipHostMalloc((void **)&m->h_score, cnt_bytes + pose_bytes));
+    m->h_score_cap = K;
+  }
+  unsigned *d_cnt = (unsigned *)m->b_score.p;
+  double *d_pose = (double *)((unsigned char *)m->b_score.p + cnt_bytes);
+  std::memcpy(m->h_score + cnt_bytes, T, pose_bytes);
+  WC_HIP(ctx, hipMemcpyAsync(d_pose, m->h_score + cnt_bytes, pose_bytes, hipMemcpyHostToDevice, ctx->stream));
+  WC_HIP(ctx, hipMemsetAsync(d_cnt, 0, cnt_bytes, ctx->stream));
+  const uint64_t tiles = (pts->n + kScoreThreads - 1) / kScoreThreads, items = (uint64_t)((K + kScoreBlock - 1) / kScoreBlock) * tiles;
+  uint64_t grid = std::min<uint64_t>(items, (uint64_t)8 * m->cus);
+  if (ctx->dev.map_score_groups > 0) grid = std::min<uint64_t>(items, (uint64_t)ctx->dev.map_score_groups);  // (development option)
+  k_map_score_batch<kScoreBatch><<<(unsigned)grid, kScoreThreads, 0, ctx->stream>>>(*pts, d_pose, K, m->voxel, m->keys, m->pay, m->cap - 1,
+                                                                                   params->min_points, d_cnt);
+  WC_HIP(ctx, hipGetLastError());
+  WC_HIP(ctx, hipMemcpyAsync(m->h_score, d_cnt, cnt_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::memcpy(h_out, m->h_score, cnt_bytes);
+  return WC_OK;
+}
+
+extern "C" int wc_pose_grid(const double T0[12], uint32_t n_yaw, const uint32_t n[3], const double step[3], double *T_out) {
+  if (!T0 || !n || !step || !T_out) return WC_ERR_ARG;
+  uint64_t K = n_yaw;
+  for (int a = 0; a < 3; ++a) {
+    if (K == 0 || K > kScoreMaxK || n[a] == 0 || !(step[a] >= 0.0) || !std::isfinite(step[a])) return WC_ERR_ARG;
+    K *= n[a];  // (at most 2^20 * 2^32)
+  }
+  if (K > kScoreMaxK) return WC_ERR_ARG;
+  for (int j = 0; j < 12; ++j)
+    if (!std::isfinite(T0[j])) return WC_ERR_ARG;
+  std::vector<double> rot((size_t)n_yaw * 12);
+  if (wc_pose_yaw_grid(T0, n_yaw, rot.data()) != WC_OK) return WC_ERR_ARG;
+  double *T = T_out;
+  for (uint32_t k = 0; k < n_yaw; ++k)
+    for (uint32_t i0 = 0; i0 < n[0]; ++i0)
+      for (uint32_t i1 = 0; i1 < n[1]; ++i1)
+        for (uint32_t i2 = 0; i2 < n[2]; ++i2, T += 12) {
+          const uint32_t i[3] = {i0, i1, i2};
+          std::memcpy(T, rot.data() + (size_t)k * 12, 12 * sizeof(double));
+          for (int a = 0; a < 3; ++a)  // (2 i - (n - 1) is an exact integer, its half exact: one rounded product, one rounded sum)
+            T[4 * a + 3] = T0[4 * a + 3] + ((double)(2 * (int64_t)i[a] - ((int64_t)n[a] - 1)) * 0.5) * step[a];
+        }
+  return WC_OK;
+}
+
+extern "C" int wc_map_score_top(const wc_map_score *scores, uint32_t K, uint32_t M, uint32_t min_hit, int32_t *idx_out, uint32_t *n_out) {
+  if (!n_out || (K && !scores) || (M && !idx_out)) return WC_ERR_ARG;
+  std::vector<uint32_t> ok;
+  for (uint32_t h = 0; h < K; ++h)
+    if (scores[h].n_bad == 0 && scores[h].n_hit >= min_hit) ok.push_back(h);
+  const size_t take = std::min<size_t>(M, ok.size());
+  std::partial_sort(ok.begin(), ok.begin() + take, ok.end(),
+                    [&](uint32_t a, uint32_t b) { return scores[a].n_hit != scores[b].n_hit ? scores[a].n_hit > scores[b].n_hit : a < b; });
+  for (uint32_t j = 0; j < M; ++j) idx_out[j] = j < take ? (int32_t)ok[j] : -1;
+  *n_out = (uint32_t)take;
   return WC_OK;
 }
 

@@ -599,6 +599,49 @@ bool LidarOdometry::RelocalizeSearch(const float *xyz, size_t n, double T_io[12]
   if (best) *best = win;
   return true;
 }
+bool LidarOdometry::RelocalizeGlobal(const float *xyz, size_t n, double T_io[12], uint32_t n_yaw, const uint32_t n_xyz[3], const double step[3],
+                                     uint32_t top_m, uint32_t factor, uint32_t n_levels, const wc_map_align_opts &finest,
+                                     wc_map_align_summary *summaries, int32_t *best) {
+  if (!map_ || !map_moments_ || !T_io || (n && !xyz) || factor < 1 || n_levels < 1 || n_levels > kMaxLevels || top_m < 1 || top_m > 1024 ||
+      !n_xyz || !step)
+    return false;
+  uint64_t K = n_yaw;  // (wc_pose_grid refuses what is out of range; here only the size of its output is needed)
+  for (int a = 0; a < 3; ++a) K = K > ((uint64_t)1 << 20) ? K : K * n_xyz[a];
+  if (K == 0 || K > ((uint64_t)1 << 20)) return false;
+  std::vector<double> grid((size_t)K * 12);
+  wc_map *levels[kMaxLevels] = {};
+  wc_map_align_opts opts[kMaxLevels];
+  std::vector<wc_map_score> scores((size_t)K);
+  std::vector<int32_t> idx(top_m), status(top_m);
+  std::vector<double> T((size_t)top_m * 12);
+  std::vector<wc_map_align_summary> s;
+  uint32_t cnt = 0;
+  bool ok = BuildLevels(ctx_, map_, map_voxel_, factor, n_levels, finest, levels, opts) &&
+            wc_pose_grid(T_io, n_yaw, n_xyz, step, grid.data()) == WC_OK;
+  if (ok) {
+    const DevBuf d_xyz(ctx_, n * 3 * sizeof(float));
+    const wc_points desc = UploadXyz(d_xyz, xyz, n);
+    const wc_map_score_params sp = {1u, 0u};
+    ok = wc_map_score_batch(ctx_, levels[0], &desc, grid.data(), (uint32_t)K, &sp, scores.data()) == WC_OK &&  // (as in AlignToMap)
+         wc_map_score_top(scores.data(), (uint32_t)K, top_m, finest.min_used, idx.data(), &cnt) == WC_OK && cnt >= 1;
+    if (ok) {
+      for (uint32_t r = 0; r < cnt; ++r) std::memcpy(T.data() + (size_t)r * 12, grid.data() + (size_t)idx[r] * 12, 12 * sizeof(double));
+      s.resize((size_t)n_levels * cnt);
+      ok = wc_map_align_pyramid_batch(ctx_, levels, n_levels, &desc, T.data(), cnt, opts, s.data(), status.data()) == WC_OK;
+    }
+  }
+  FreeLevels(ctx_, levels, n_levels);
+  int32_t win = -1;
+  ok = ok && wc_map_align_best(s.data() + (size_t)(n_levels - 1) * cnt, status.data(), cnt, finest.min_used, &win) == WC_OK && win >= 0;
+  if (!ok) return false;
+  std::memcpy(T_io, T.data() + (size_t)win * 12, 12 * sizeof(double));
+  if (summaries) {  // (level-major with top_m records per level; the candidates that did not exist: zero)
+    std::memset(summaries, 0, (size_t)n_levels * top_m * sizeof(summaries[0]));
+    for (uint32_t l = 0; l < n_levels; ++l) std::memcpy(summaries + (size_t)l * top_m, s.data() + (size_t)l * cnt, cnt * sizeof(s[0]));
+  }
+  if (best) *best = win;
+  return true;
+}
 bool LidarOdometry::LinearizeAgainstMap(const float *xyz, size_t n, const double T[12], const wc_map_reg_params &params, wc_map_normal_eq *out,
                                         wc_map_reg_row *rows) {
   if (!map_ || !map_moments_ || !T || !out || (n && !xyz)) return false;

@@ -120,6 +120,16 @@ class LidarOdometry {
   // AddLidarScan calls it
   bool RelocalizeSearch(const float *xyz, size_t n, double T_io[12], uint32_t n_yaw, uint32_t factor, uint32_t n_levels,
                         const wc_map_align_opts &finest, wc_map_align_summary *summaries, int32_t *best);
+  // RelocalizeToMap when neither heading nor position is known: the levels RelocalizeToMap builds; the n_yaw x n_xyz[0] x n_xyz[1] x n_xyz[2]
+  // poses wc_pose_grid makes around T_io (spacing step, world axes); wc_map_score_batch of all of them on the COARSEST level with
+  // min_points = 1; the top_m best by wc_map_score_top (min_hit = finest.min_used) through ONE wc_map_align_pyramid_batch in rank order; the
+  // winner by wc_map_align_best on the finest level with finest.min_used; T_io becomes its pose and the built levels are destroyed.
+  // summaries (may be null): n_levels x top_m records, level-major, coarsest first, in rank order (zero where fewer candidates were
+  // eligible); best (may be null): the winner's rank.  false - nothing touched - where RelocalizeToMap returns false, for top_m outside
+  // 1 .. 1024, for a grid wc_pose_grid or wc_map_score_batch refuses, and when no candidate or no aligned hypothesis is eligible.  A
+  // 1 x (1, 1, 1) grid with top_m = 1 and an eligible start gives RelocalizeToMap's pose byte for byte.  Nothing in AddLidarScan calls it
+  bool RelocalizeGlobal(const float *xyz, size_t n, double T_io[12], uint32_t n_yaw, const uint32_t n_xyz[3], const double step[3], uint32_t top_m,
+                        uint32_t factor, uint32_t n_levels, const wc_map_align_opts &finest, wc_map_align_summary *summaries, int32_t *best);
   // one linearisation at T (wc_map_linearize): *out, and rows[n] when rows is not null; false as AlignToMap
   bool LinearizeAgainstMap(const float *xyz, size_t n, const double T[12], const wc_map_reg_params &params, wc_map_normal_eq *out,
                            wc_map_reg_row *rows);

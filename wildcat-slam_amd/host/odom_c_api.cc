@@ -236,6 +236,13 @@ int wc_odom_map_relocalize_search(void *h, const float *xyz, uint64_t n, double 
                                   const wc_map_align_opts *finest, wc_map_align_summary *summaries, int32_t *best) {
   return finest && ((LidarOdometry *)h)->RelocalizeSearch(xyz, n, T_io, n_yaw, factor, n_levels, *finest, summaries, best) ? 1 : 0;
 }
+// LidarOdometry::RelocalizeGlobal; summaries: n_levels x top_m records, level-major, rank order (may be null); best: the winner's rank (may be
+// null); 1 = done, 0 = as wc_odom_map_relocalize, top_m outside 1 .. 1024, a refused grid, or no eligible candidate or hypothesis
+int wc_odom_map_relocalize_global(void *h, const float *xyz, uint64_t n, double T_io[12], uint32_t n_yaw, const uint32_t n_xyz[3],
+                                  const double step[3], uint32_t top_m, uint32_t factor, uint32_t n_levels, const wc_map_align_opts *finest,
+                                  wc_map_align_summary *summaries, int32_t *best) {
+  return finest && ((LidarOdometry *)h)->RelocalizeGlobal(xyz, n, T_io, n_yaw, n_xyz, step, top_m, factor, n_levels, *finest, summaries, best) ? 1 : 0;
+}
 int wc_odom_map_linearize(void *h, const float *xyz, uint64_t n, const double T[12], const wc_map_reg_params *params, wc_map_normal_eq *out,
                           wc_map_reg_row *rows) {
   return params && ((LidarOdometry *)h)->LinearizeAgainstMap(xyz, n, T, *params, out, rows) ? 1 : 0;

@@ -741,6 +741,35 @@ def pose_yaw_grid(T, K):
     return out.reshape(K, 3, 4)
 
 
+def pose_grid(T, n_yaw, n_xyz, step):
+    """wc_pose_grid (needs no GPU): n_yaw headings x n_xyz[0] x n_xyz[1] x n_xyz[2] positions spaced by step around the pose T, centred
+    on its translation in world axes -> (K, 3, 4), pose ((k n0 + i0) n1 + i1) n2 + i2; the rotations are pose_yaw_grid's"""
+    T = _pose12(T)
+    n = np.ascontiguousarray(n_xyz, np.uint32).reshape(-1)
+    step = np.ascontiguousarray(step, np.float64).reshape(-1)
+    assert n.size == 3 and step.size == 3, "n_xyz and step: three entries each"
+    K = int(n_yaw) * int(n[0]) * int(n[1]) * int(n[2])
+    if not 1 <= K <= 2**20:
+        raise WildcatError(11, "wc_pose_grid: between 1 and 2^20 poses")
+    out = np.zeros((K, 12))
+    rc = load().wc_pose_grid(R.ptr(T), C.c_uint32(int(n_yaw)), R.ptr(n), R.ptr(step), R.ptr(out))
+    if rc != WC_OK:
+        raise WildcatError(rc, "wc_pose_grid refused its arguments")
+    return out.reshape(K, 3, 4)
+
+
+def map_score_top(scores, M, min_hit=0):
+    """wc_map_score_top (needs no GPU): the indices of the M best MAP_SCORE records - n_bad == 0 and n_hit >= min_hit; larger n_hit
+    first, then the smaller index -> int32 array of the min(M, eligible) indices"""
+    scores = np.ascontiguousarray(scores, R.MAP_SCORE).reshape(-1)
+    K, M = len(scores), int(M)
+    idx, cnt = np.full(max(M, 1), -1, np.int32), C.c_uint32(0)
+    rc = load().wc_map_score_top(R.ptr(scores) if K else None, C.c_uint32(K), C.c_uint32(M), C.c_uint32(int(min_hit)), R.ptr(idx), C.byref(cnt))
+    if rc != WC_OK:
+        raise WildcatError(rc, "wc_map_score_top refused its arguments")
+    return idx[: cnt.value].copy()
+
+
 class PointMap:
     """wc_map: the device-resident voxel-downsampled map (DownSamplingVoxel, surfel_extraction.cc:228-261, over every insert)"""
 
@@ -1080,6 +1109,21 @@ class PointMap:
         with self._uploaded(points) as (desc, _):
             return self.linearize_batch_device(desc, Ts, params)
 
+    def score_batch_device(self, desc, Ts, min_points=1):
+        """wc_map_score_batch on points already in HBM: K poses Ts -> MAP_SCORE array (K,): per pose the points that land in a voxel
+        holding at least min_points points (n_hit), inside the key range (n_in), and sent to a non-finite point (n_bad)"""
+        Ts = _poses12(Ts)
+        K = len(Ts)
+        out, params = np.zeros(K, R.MAP_SCORE), R.MapScoreParams(int(min_points), 0)
+        self.ctx._ck(self.lib.wc_map_score_batch(self.ctx.h, self.h, C.byref(desc), R.ptr(Ts) if K else None, C.c_uint32(K), C.byref(params),
+                                                 R.ptr(out) if K else None))
+        return out
+
+    def score_batch(self, points, Ts, min_points=1):
+        """POINT records or an (n, 3) float32 array (uploaded for the call) and K poses -> as score_batch_device"""
+        with self._uploaded(points) as (desc, _):
+            return self.score_batch_device(desc, Ts, min_points)
+
     def align_batch_device(self, desc, Ts, opts):
         """wc_map_align_batch on points already in HBM: K starts in lockstep -> (Ts (K, 3, 4), [summary dict per hypothesis], status (K,)
         int32), each hypothesis as align_device leaves it"""
@@ -1278,6 +1322,25 @@ class Odometry:
                                                       C.c_uint32(n_levels), C.byref(opts), summ, C.byref(best)):
             return None
         return T.reshape(3, 4), [[_summary_dict(summ[l * K + h]) for h in range(K)] for l in range(n_levels)], int(best.value)
+
+    def map_relocalize_global(self, xyz, T, n_yaw, n_xyz, step, top_m, factor, n_levels, opts):
+        """map_relocalize when neither heading nor position is known (LidarOdometry::RelocalizeGlobal): the poses pose_grid(T, n_yaw, n_xyz,
+        step) scored on the coarsest level (PointMap.score_batch, min_points 1), the top_m best (map_score_top, min_hit = opts.min_used)
+        through the levels in one batched pass in rank order, the winner by map_align_best on the finest level -> (T (3, 4) of the winner,
+        [[summary dict per candidate, rank order] per level, coarsest first], the winner's rank), or None where map_relocalize returns None,
+        for top_m outside 1 .. 1024, for a refused grid, or when no candidate or no aligned hypothesis is eligible"""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n_levels, M = int(n_levels), int(top_m)
+        n = np.ascontiguousarray(n_xyz, np.uint32).reshape(-1)
+        step = np.ascontiguousarray(step, np.float64).reshape(-1)
+        if not 1 <= n_levels <= 8 or not 1 <= M <= 1024 or n.size != 3 or step.size != 3:
+            return None
+        T, summ, best = _pose12(T), (R.MapAlignSummary * (n_levels * M))(), C.c_int32(-1)
+        if not self.lib.wc_odom_map_relocalize_global(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), R.ptr(T), C.c_uint32(int(n_yaw)), R.ptr(n),
+                                                      R.ptr(step), C.c_uint32(M), C.c_uint32(int(factor)), C.c_uint32(n_levels), C.byref(opts),
+                                                      summ, C.byref(best)):
+            return None
+        return T.reshape(3, 4), [[_summary_dict(summ[l * M + h]) for h in range(M)] for l in range(n_levels)], int(best.value)
 
     def map_save(self, path):
         """the map's exact state as the canonical file of host/map_file.h (LidarOdometry::SaveMap) -> True, or False without a map or

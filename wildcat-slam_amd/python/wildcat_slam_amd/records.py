@@ -46,6 +46,10 @@ MAP_REG_ROW = np.dtype([("J", "f8", 6), ("d", "f8"), ("k", "f8")])  # wc_map_reg
 MAP_NORMAL_EQ = np.dtype([("H", "f8", 21), ("g", "f8", 6), ("cost", "f8"), ("n_used", "u8"), ("n_found", "u8")])  # wc_map_normal_eq
 assert MAP_REG_ROW.itemsize == 64 and MAP_NORMAL_EQ.itemsize == 240 and MAP_NORMAL_EQ.fields["cost"][1] == 216
 
+# wc_map_score: one pose hypothesis's counts (wc_map_score_batch)
+MAP_SCORE = np.dtype([("n_hit", "u4"), ("n_in", "u4"), ("n_bad", "u4"), ("reserved", "u4")])
+assert MAP_SCORE.itemsize == 16
+
 # wc_map_ray_hit: the first 32 bytes as MAP_HIT's (flags: bit 0 = the ray was not cast), then the entering parameter and the walk's counts
 MAP_RAY_HIT = np.dtype([("xyz", "f4", 3), ("count", "u4"), ("key", "i4", 3), ("flags", "u4"), ("t", "f8"), ("step", "u4"), ("tested", "u4")])
 assert MAP_RAY_HIT.itemsize == 48 and [MAP_RAY_HIT.fields[f][1] for f in ("count", "key", "flags", "t", "step", "tested")] == [12, 16, 28, 32, 40, 44]
@@ -152,6 +156,12 @@ class MapRegParams(C.Structure):
     """wc_map_reg_params"""
 
     _fields_ = [("max_dist", C.c_double), ("min_points", C.c_uint32), ("reserved", C.c_uint32), ("sigma0", C.c_double), ("cauchy_a", C.c_double)]
+
+
+class MapScoreParams(C.Structure):
+    """wc_map_score_params"""
+
+    _fields_ = [("min_points", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class MapAlignOpts(C.Structure):
