@@ -68,8 +68,8 @@ int wc_ctx_set_params(wc_ctx *ctx, const wc_params *params);
  *                      the bias elimination's backward error stays below 1e-9 - tests/test_lm_step_gpu.py; 0 = never)
  *   map_mom_pts (1)    wc_map_insert into a WC_MAP_MOMENTS map: points per lane - 1: tiles of 256 points, 54 KB of LDS; 2: the plain
  *                      insert's tiles of 512 points, 108 KB of LDS, one workgroup per CU (same sums either way)
- *   map_lin_groups (0) wc_map_linearize and wc_map_linearize_batch: workgroups of the first kernel (0: chosen from the point count and
- *                      K); H, g and cost are byte-equal whatever the value
+ *   map_lin_groups (0) wc_map_linearize, wc_map_linearize_batch and the align calls on them: workgroups of their one first kernel (0:
+ *                      chosen from the point count and K); H, g and cost are byte-equal whatever the value
  *   map_score_groups (0) wc_map_score_batch: workgroups of its kernel (0: chosen from the point count and K); every record is the same
  *                      whatever the value
  *   map_carve_groups (0) wc_map_carve: workgroups of its ray kernel (0: chosen from the point count); the five counts are the same

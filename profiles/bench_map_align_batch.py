@@ -1,4 +1,4 @@
-"""Timings of the batched registration (csrc/map.hip: k_map_linearize_batch, k_map_lin_reduce_batch) beside the single calls
+"""Timings of the batched registration (csrc/map.hip: k_map_linearize<false>, k_map_lin_reduce) beside the single calls
 it replaces.  Writes profiles/map_align_batch_bench.json (--out) after every step, so that a run that does not complete leaves what it
 measured:
   the map      DESIGN 8.9's room (60 000 points, v = 0.2) and its three coarser levels

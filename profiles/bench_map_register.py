@@ -1,4 +1,4 @@
-"""Timings of the registration against the voxel map (csrc/map.hip: k_map_linearize, k_map_lin_reduce; include/wildcat_hip.h
+"""Timings of the registration against the voxel map (csrc/map.hip: k_map_linearize<true>, k_map_lin_reduce; include/wildcat_hip.h
 "registration against the map") beside the plane query it grew out of, in one process, on the 11-sweep map of bench_map_surfels.py
 (1 M-point sweeps of the room of synth.g1_room, v = 0.05 and 0.2).  Prints ONE JSON object and writes it to
 profiles/map_register_bench.json:

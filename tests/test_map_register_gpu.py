@@ -1,4 +1,4 @@
-"""Registration against the voxel map on the device (wc_map_linearize, wc_map_align, csrc/map.hip: k_map_linearize, k_map_lin_reduce)
+"""Registration against the voxel map on the device (wc_map_linearize, wc_map_align, csrc/map.hip: k_map_linearize<true>, k_map_lin_reduce)
 against the restatement of map_register_ref.py on the map's own export: the rows byte for byte, the sums within the bound their
 additions allow, determinism over runs, grids, layouts and outputs, one Gauss-Newton step by its backward error, the recovery of a known
 pose, the refused arguments and the facade."""

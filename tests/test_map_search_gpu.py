@@ -1,7 +1,8 @@
 """Many pose hypotheses in one pass on the device (include/wildcat_hip.h: wc_map_linearize_batch, wc_map_align_batch,
-wc_map_align_pyramid_batch, wc_map_align_best, wc_pose_yaw_grid; csrc/map.hip: k_map_linearize_batch, k_map_lin_reduce_batch; DESIGN
-8.10): every batched call byte for byte against its single calls, the hypothesis that fails alone, the refusals, the yaw search on the
-scene of map_search_ref.py against the float64 restatement, and the facade."""
+wc_map_align_pyramid_batch, wc_map_align_best, wc_pose_yaw_grid; csrc/map.hip: k_map_linearize<ONE>, k_map_lin_reduce; DESIGN
+8.10): every batched call byte for byte against its single calls, the hypothesis that fails alone, the refusals, what the single and
+the batched pyramid leave apart on a failing level, the yaw search on the scene of map_search_ref.py against the float64 restatement,
+and the facade."""
 import ctypes as C
 
 import numpy as np
@@ -70,6 +71,35 @@ def test_linearize_batch_equals_the_single_calls(gpu, world, n):
         assert ne.tobytes() == single[:3].tobytes() and not status.any()
     finally:
         gpu.set_dev_option("map_lin_groups", 0)
+        for b in bufs:
+            b.free()
+
+
+@pytest.mark.parametrize("n", [257, 1])
+def test_linearize_with_rows_equals_the_batch_of_one(gpu, world, n):
+    """wc_map_linearize with d_rows and wc_map_linearize_batch at K = 1 on the same pose: one record, for map_lin_groups 0 and 1 and both
+    point layouts; the single call's rows after a batch of one and one of 33 (the scratch they share grows and shrinks) are the rows of
+    the call made before them"""
+    m, scan, T = world["levels"][1], world["scan"][:n], world["poses"][1]
+    prm = L.map_reg_params(m.voxel, cauchy_a=0.4)
+    bufs = [gpu.to_device(scan), gpu.to_device(point_records(scan))]
+    d_rows = gpu.alloc(64 * n)
+    try:
+        for groups in (0, 1):
+            gpu.set_dev_option("map_lin_groups", groups)
+            for desc in (R.Points(bufs[0].ptr, 0, 12, 0, n), R.Points(bufs[1].ptr, 0, 48, 0, n)):
+                ne = m.linearize_device(desc, T, prm, d_rows)
+                rows = gpu.download_raw(d_rows.ptr, 64 * n).tobytes()
+                assert n == 1 or (rows != bytes(64 * n) and ne["n_used"] > n // 8)
+                one, status = m.linearize_batch_device(desc, T[None], prm)
+                assert status.tolist() == [0] and one[0].tobytes() == ne.tobytes(), (groups, desc.xyz_stride)
+                m.linearize_batch_device(desc, world["poses"][:33], prm)
+                d_rows.upload(np.full(64 * n, 0x5A, np.uint8))
+                again = m.linearize_device(desc, T, prm, d_rows)
+                assert again.tobytes() == ne.tobytes() and gpu.download_raw(d_rows.ptr, 64 * n).tobytes() == rows, (groups, desc.xyz_stride)
+    finally:
+        gpu.set_dev_option("map_lin_groups", 0)
+        d_rows.free()
         for b in bufs:
             b.free()
 
@@ -239,6 +269,32 @@ def test_align_pyramid_batch_equals_the_single_pyramids(gpu, world, search, n_le
     if n_levels == 4:
         assert Ts8.tobytes() == Ts[:8].tobytes() and not status8.any()
         assert [[summary_bytes(s) for s in row] for row in summ8] == [[summary_bytes(s) for s in row[:8]] for row in summ]
+
+
+def test_a_failing_level_ends_the_single_pyramid_and_only_the_hypothesis_of_the_batched_one(gpu, world):
+    """a start whose first linearisation fails, two levels: wc_map_align_pyramid returns the error, T_io stays and the second level's
+    summary is not touched; wc_map_align_pyramid_batch with K = 1 returns WC_OK with the error as the status and a ZERO second summary;
+    the context then computes what it computed before"""
+    lib, levels = gpu.lib, world["levels"][1::-1]  # coarsest first
+    scan = world["scan"][:2000]
+    d = gpu.to_device(scan)
+    desc = R.Points(d.ptr, 0, 12, 0, len(scan))
+    prm = L.map_reg_params(levels[1].voxel)
+    before = levels[1].linearize_device(desc, world["T"], prm).tobytes()
+    handles = (C.c_void_p * 2)(*[m.h.value for m in levels])
+    opts = (R.MapAlignOpts * 2)(*L.map_pyramid_opts(levels, **world["kw"]))
+    start = np.ascontiguousarray(far_pose(1e39).reshape(-1))
+    size = C.sizeof(R.MapAlignSummary)
+    Tio, summ = start.copy(), (R.MapAlignSummary * 2)()
+    C.memset(summ, 0x5A, 2 * size)
+    assert lib.wc_map_align_pyramid(gpu.h, handles, C.c_uint32(2), C.byref(desc), R.ptr(Tio), opts, summ) == WC_ERR_ARG
+    assert Tio.tobytes() == start.tobytes() and bytes(summ[1]) == bytes([0x5A]) * size
+    Tio, status = start.copy(), np.full(1, -1, np.int32)
+    C.memset(summ, 0x5A, 2 * size)
+    assert lib.wc_map_align_pyramid_batch(gpu.h, handles, C.c_uint32(2), C.byref(desc), R.ptr(Tio), C.c_uint32(1), opts, summ, R.ptr(status)) == 0
+    assert status.tolist() == [WC_ERR_ARG] and Tio.tobytes() == start.tobytes() and bytes(summ[1]) == bytes(size)
+    assert levels[1].linearize_device(desc, world["T"], prm).tobytes() == before
+    d.free()
 
 
 def test_yaw_search_finds_the_pose_the_pyramid_alone_loses(gpu, world, search):

@@ -46,7 +46,7 @@ struct wc_dev_opts {
   int lm_side_stream = 1;    // two-collective form: the large collective on a side stream (1: with the in-library RCCL binding; 0: never; 2: always - tests)
   int lm_one_collective = 0; // sharded windows: rounds 3 - 5's ONE all-reduce per linearisation (IMU triples sharded too) instead of the two-collective form
   int map_mom_pts = 1;       // insert into a WC_MAP_MOMENTS map: points per lane (1: tile 256, 54 KB of LDS; 2: the plain tile, 108 KB)
-  int map_lin_groups = 0;    // wc_map_linearize: workgroups of k_map_linearize (0: by size) - the sums do not depend on it (tests)
+  int map_lin_groups = 0;    // lin_core (one pose or K): workgroups of k_map_linearize<ONE> (0: by size) - the sums do not depend on it (tests)
   int map_score_groups = 0;  // wc_map_score_batch: workgroups of k_map_score_batch (0: by size) - the records do not depend on it (tests)
   int map_cast_groups = 0;   // wc_map_raycast: workgroups of k_map_raycast (0: by size) - the output bytes do not depend on it (tests)
   int map_carve_groups = 0;  // wc_map_carve: workgroups of k_map_carve (0: by size) - the result does not depend on it (tests)

@@ -28,10 +28,10 @@
 //                   a carve's seen-through ones
 //   k_map_surfels   surfel export: one lane per sorted voxel: map_plane_of (exact 128-bit covariance numerator, fx_eig3) -> wc_map_surfel
 //   k_map_nearest<true>  plane query: the same search, then map_plane_of for the winning voxel only -> wc_map_plane_hit
-//   k_map_linearize / k_map_lin_reduce  registration: the plane query behind a pose, reduced to the point-to-plane normal equations in a
-//                   fixed order (tiles of 256 points, then levels of 32 partials, one launch each): wc_map_linearize, wc_map_align
-//   k_map_linearize_batch / k_map_lin_reduce_batch  the same for K poses of one point set in one launch chain, (hypothesis, tile) pairs
-//                   as work items, the tile body shared with k_map_linearize: wc_map_linearize_batch, wc_map_align_batch
+//   k_map_linearize<ONE> / k_map_lin_reduce  registration: the plane query behind a pose, reduced to the point-to-plane normal equations
+//                   in a fixed order (tiles of 256 points, then levels of 32 partials, one launch each), for K poses of one point set
+//                   in one launch chain with (hypothesis, tile) pairs as work items; <true>: one pose, in the kernel arguments.  One
+//                   host core (lin_core) under wc_map_linearize, wc_map_align, their pyramid and their _batch forms
 //   k_map_score_batch  occupancy score of K poses of one point set: a tile of 256 points in registers walks a block of hypotheses, one
 //                   read-only probe chain per (point, pose), eight hypotheses' first-slot key loads in flight; counts by ballot, LDS and one
 //                   32-bit atomic add per workgroup, hypothesis and count: wc_map_score_batch
@@ -92,12 +92,11 @@ struct wc_map {
   uint64_t purges = 0;               // replacements into a table of the same size, made to drop tombstones
   int cus = 256;
   wc_buf b_pairs[4], b_tmp, b_cnt;   // export scratch: keys in / out, slot indices in / out; rocPRIM temporary; compaction counter
-  wc_buf b_lin;                      // wc_map_linearize: the tiles' partial sums and every level of their reduction (first use)
-  unsigned long long *h_lin = nullptr;  // ... and the pinned landing place of the result (first use)
-  wc_buf b_pose;                     // wc_map_linearize_batch: the poses, K x 12 doubles (b_lin holds its partials too)
-  unsigned long long *h_linb = nullptr;  // ... the pinned landing place of its K final partials, grown on demand ...
-  double *h_pose = nullptr;          // ... and the pinned block the poses are uploaded from: both hold h_linb_cap hypotheses
-  uint64_t h_linb_cap = 0;
+  wc_buf b_lin;                      // lin_core: K hypotheses' tile partials and every level of their reduction, then the K final partials
+  unsigned long long *h_lin = nullptr;  // ... and the pinned landing place of those K final partials: it holds h_lin_cap, grown on demand
+  uint64_t h_lin_cap = 0;
+  wc_buf b_pose;                     // lin_core with K > 1: the poses, K x 12 doubles (one pose travels in the kernel arguments) ...
+  double *h_pose = nullptr;          // ... and the pinned block they are uploaded from: h_lin_cap hypotheses once that exceeds 1
   wc_buf b_carve;                    // wc_map_carve: its five counter lines, then one u32 word per slot (first use, grown with the table)
   unsigned long long *h_carve = nullptr;  // ... and the pinned landing place of the counters (first use)
   wc_buf b_cast;                     // wc_map_raycast: its four counter lines (first use); nothing another call reads or writes
@@ -662,7 +661,7 @@ __global__ void __launch_bounds__(kNearThreads) k_map_nearest(wc_points q, doubl
 //   256-byte partial per tile: 28 doubles, then the integer counts n_used, n_found, n_bad (finite points the pose sent to a non-finite
 //   one) and a zero word, written with plain vector stores.
 //   k_map_lin_reduce: partial j of level l + 1 = partials 32 j .. 32 j + 31 of level l added in ascending order, one launch per level
-//   until one partial is left (the launch boundary is the hand-off: no ticket, no fence, no atomics on doubles).
+//   (of every hypothesis) until one partial is left (the launch boundary is the hand-off: no ticket, no fence, no atomics on doubles).
 constexpr int kLinThreads = 256;
 constexpr int kLinSums = 28;    // H's upper triangle (21), g (6), sum rho (1)
 constexpr int kLinWords = 32;   // 8-byte words of a partial
@@ -686,7 +685,7 @@ __device__ __forceinline__ void map_move(const double (&T)[12], float px, float 
   qz = (float)(((T[8] * x0 + T[9] * y0) + T[10] * z0) + T[11]);
 }
 
-// one tile: the body k_map_linearize and k_map_linearize_batch share.  T: the pose (workgroup uniform); out: the tile's 256-byte partial;
+// one tile of k_map_linearize.  T: the pose (workgroup uniform); out: the tile's 256-byte partial;
 // rows: NULL or the call's wc_map_reg_row array; s_row, s_chunk, s_cnt: the workgroup's LDS (kLinFields * kLinPitch and kLinSums * 8
 // doubles, 3 words).  Every lane of the workgroup calls it
 __device__ __forceinline__ void map_lin_tile(const wc_points &pts, const double (&T)[12], const map_reg &R, double v, const unsigned long long *keys,
@@ -771,36 +770,27 @@ __device__ __forceinline__ void map_lin_tile(const wc_points &pts, const double 
   }
 }
 
-__global__ void __launch_bounds__(kLinThreads) k_map_linearize(wc_points pts, map_pose P, map_reg R, double v, const unsigned long long *keys,
-                                                               const long long *pay, const long long *mom, unsigned long long mask,
-                                                               wc_map_reg_row *rows, unsigned long long *part) {
+// The registration's first kernel in its two forms, one body.  ONE: one pose, carried in the kernel arguments (P; poses and K
+// are not read), the work items are the tiles and rows may be non-null.  Otherwise K poses in a device array (poses: K x 12 doubles, read
+// through loads whose address is the same for the whole workgroup; P and rows are not read), and a work item is a (hypothesis, tile)
+// pair, item = h * tiles + tile: neighbouring workgroups share a hypothesis and work on neighbouring tiles of it.  Items are counted in
+// 64 bits in both forms: no cap on n comes from here.  part: hypothesis-major, hyp_words words each
+template <bool ONE>
+__global__ void __launch_bounds__(kLinThreads) k_map_linearize(wc_points pts, map_pose P, const double *__restrict__ poses, unsigned K, map_reg R,
+                                                               double v, const unsigned long long *keys, const long long *pay,
+                                                               const long long *mom, unsigned long long mask, wc_map_reg_row *rows,
+                                                               unsigned long long *part, unsigned long long hyp_words) {
   __shared__ double s_row[kLinFields * kLinPitch];
   __shared__ double s_chunk[kLinSums * 8];
   __shared__ unsigned s_cnt[3];
-  const uint64_t tiles = (pts.n + kLinThreads - 1) / kLinThreads;
-  for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x)
-    map_lin_tile(pts, P.T, R, v, keys, pay, mom, mask, rows, tile, part + tile * kLinWords, s_row, s_chunk, s_cnt);
-}
-
-// K poses in one launch (wc_map_linearize_batch: DESIGN 8.10).  A work item is a (hypothesis, tile) pair, item = h * tiles + tile:
-// neighbouring workgroups share a hypothesis and work on neighbouring tiles of it.  poses: K x 12 doubles, read through loads whose
-// address is the same for the whole workgroup.  part: hypothesis-major, hyp_words words each - the single call's level layout
-__global__ void __launch_bounds__(kLinThreads) k_map_linearize_batch(wc_points pts, const double *__restrict__ poses, unsigned K, map_reg R, double v,
-                                                                     const unsigned long long *keys, const long long *pay, const long long *mom,
-                                                                     unsigned long long mask, unsigned long long *__restrict__ part,
-                                                                     unsigned long long hyp_words) {
-  __shared__ double s_row[kLinFields * kLinPitch];
-  __shared__ double s_chunk[kLinSums * 8];
-  __shared__ unsigned s_cnt[3];
-  const unsigned tiles = (unsigned)((pts.n + kLinThreads - 1) / kLinThreads);  // (K * tiles <= 2^20: the host's capacity check)
-  const unsigned items = K * tiles;
-  for (unsigned item = blockIdx.x; item < items; item += gridDim.x) {
-    const unsigned h = item / tiles, tile = item - h * tiles;
-    const double *Tp = poses + (size_t)h * 12;
+  const uint64_t tiles = (pts.n + kLinThreads - 1) / kLinThreads, items = ONE ? tiles : (uint64_t)K * tiles;
+  for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
+    const uint64_t h = ONE ? 0 : item / tiles, tile = item - h * tiles;
+    const double *Tp = ONE ? P.T : poses + h * 12;
     double T[12];
 #pragma unroll
     for (int j = 0; j < 12; ++j) T[j] = Tp[j];
-    map_lin_tile(pts, T, R, v, keys, pay, mom, mask, nullptr, tile, part + h * hyp_words + (size_t)tile * kLinWords, s_row, s_chunk, s_cnt);
+    map_lin_tile(pts, T, R, v, keys, pay, mom, mask, ONE ? rows : nullptr, tile, part + h * hyp_words + tile * kLinWords, s_row, s_chunk, s_cnt);
   }
 }
 
@@ -903,22 +893,14 @@ __device__ __forceinline__ void map_lin_reduce_word(const unsigned long long *in
   out[j * kLinWords + e] = word;
 }
 
-// one level of the second stage, one lane per word of the next level
-__global__ void __launch_bounds__(256) k_map_lin_reduce(const unsigned long long *in, uint64_t m, unsigned long long *out) {
-  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  const uint64_t j = g / kLinWords;
-  if (j * kLinFan >= m) return;
-  map_lin_reduce_word(in, m, j, (int)(g % kLinWords), out);
-}
-
-// the same level of all K hypotheses: hypothesis h reads its m partials at in + h * in_stride and writes its ceil(m / 32) at
-// out + h * out_stride (words)
-__global__ void __launch_bounds__(256) k_map_lin_reduce_batch(const unsigned long long *in, uint64_t in_stride, uint64_t m, unsigned long long *out,
-                                                              uint64_t out_stride, unsigned K) {
+// one level of the second stage for all K hypotheses, one lane per word of the next level: hypothesis h reads its m partials at
+// in + h * in_stride and writes its ceil(m / 32) at out + h * out_stride (words)
+__global__ void __launch_bounds__(256) k_map_lin_reduce(const unsigned long long *in, uint64_t in_stride, uint64_t m, unsigned long long *out,
+                                                        uint64_t out_stride, unsigned K) {
   const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   const uint64_t per = (m + kLinFan - 1) / kLinFan * kLinWords;  // words of one hypothesis's next level
-  const uint64_t h = g / per, r = g - h * per;
-  if (h >= K) return;
+  if (g >= K * per) return;
+  const uint64_t h = K == 1 ? 0 : g / per, r = g - h * per;  // (one pose: no division by a run-time value, as before the K-pose form)
   map_lin_reduce_word(in + h * in_stride, m, r / kLinWords, (int)(r % kLinWords), out + h * out_stride);
 }
 
@@ -1494,7 +1476,6 @@ extern "C" int wc_map_destroy(wc_ctx *ctx, wc_map *m) {
   if (m->ev_ctr) (void)hipEventDestroy(m->ev_ctr);
   if (m->h_ctr) (void)hipHostFree(m->h_ctr);
   if (m->h_lin) (void)hipHostFree(m->h_lin);
-  if (m->h_linb) (void)hipHostFree(m->h_linb);
   if (m->h_pose) (void)hipHostFree(m->h_pose);
   if (m->h_carve) (void)hipHostFree(m->h_carve);
   if (m->h_cast) (void)hipHostFree(m->h_cast);
@@ -1825,90 +1806,70 @@ void normal_eq_of(const unsigned long long *part, wc_map_normal_eq *out) {
   out->cost = 0.5 * sums[27];
   out->n_used = part[kLinSums], out->n_found = part[kLinSums + 1];
 }
-}  // namespace
-
-extern "C" int wc_map_linearize(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double T[12], const wc_map_reg_params *params,
-                                wc_map_normal_eq *h_out, wc_map_reg_row *d_rows) {
-  wc_dev_guard dg_(ctx);
-  if (!map_ok(ctx, m) || !m->mom || !map_points_ok(pts) || !T || !h_out || !reg_params_ok(params) || (uintptr_t)d_rows % 8)
-    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument, a map of another context or one created without WC_MAP_MOMENTS", __func__);
-  map_pose P;
-  for (int j = 0; j < 12; ++j) {
-    if (!std::isfinite(T[j])) return wc_fail(ctx, WC_ERR_ARG, "%s: T[%d] is not finite", __func__, j);
-    P.T[j] = T[j];
-  }
-  std::memset(h_out, 0, sizeof(*h_out));
-  if (pts->n == 0) return WC_OK;
-  const uint64_t tiles = (pts->n + kLinThreads - 1) / kLinThreads;
-  WC_TRY(wc_ensure(ctx, m->b_lin, lin_words(tiles) * 8));
-  if (!m->h_lin) WC_HIP(ctx, hipHostMalloc((void **)&m->h_lin, kLinWords * 8));
-  const map_reg R = reg_of(params);
-  unsigned long long *lvl = (unsigned long long *)m->b_lin.p;
-  uint64_t grid = std::min<uint64_t>(tiles, (uint64_t)8 * m->cus);
-  if (ctx->dev.map_lin_groups > 0) grid = std::min<uint64_t>(tiles, (uint64_t)ctx->dev.map_lin_groups);  // (development option)
-  k_map_linearize<<<(unsigned)grid, kLinThreads, 0, ctx->stream>>>(*pts, P, R, m->voxel, m->keys, m->pay, m->mom, m->cap - 1, d_rows, lvl);
-  WC_HIP(ctx, hipGetLastError());
-  uint64_t cnt = tiles;
-  do {
-    const uint64_t nxt = (cnt + kLinFan - 1) / kLinFan;
-    unsigned long long *out = lvl + cnt * kLinWords;
-    k_map_lin_reduce<<<(unsigned)((nxt * kLinWords + 255) / 256), 256, 0, ctx->stream>>>(lvl, cnt, out);
-    WC_HIP(ctx, hipGetLastError());
-    lvl = out, cnt = nxt;
-  } while (cnt > 1);
-  WC_HIP(ctx, hipMemcpyAsync(m->h_lin, lvl, kLinWords * 8, hipMemcpyDeviceToHost, ctx->stream));
-  WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (m->h_lin[kLinSums + 2])
-    return wc_fail(ctx, WC_ERR_ARG, "%s: T sends %llu finite points to a non-finite one", __func__, m->h_lin[kLinSums + 2]);
-  normal_eq_of(m->h_lin, h_out);
+// what every registration call asks of its map, points and params: a map of this context with moments, readable points, valid params
+bool reg_args_ok(const wc_ctx *ctx, const wc_map *m, const wc_points *pts, const wc_map_reg_params *params) {
+  return map_ok(ctx, m) && m->mom && map_points_ok(pts) && reg_params_ok(params);
+}
+// K poses (K x 12 doubles) without a non-finite entry: the registration's and the score's check
+int poses_finite(wc_ctx *ctx, const double *T, uint32_t K, const char *fn) {
+  for (uint64_t j = 0; j < (uint64_t)K * 12; ++j)
+    if (!std::isfinite(T[j]))
+      return wc_fail(ctx, WC_ERR_ARG, "%s: entry %u of hypothesis %u's T is not finite", fn, (unsigned)(j % 12), (unsigned)(j / 12));
   return WC_OK;
 }
-
-namespace {
 constexpr uint32_t kLinBatchMax = 1024;         // hypotheses of one call
-constexpr uint64_t kLinBatchItems = 1ull << 20;  // (hypothesis, tile) pairs of one call: a design cap, about 270 MB of partials
-// wc_map_linearize_batch behind its argument checks, K >= 1: every hypothesis's record and status (WC_OK, or WC_ERR_ARG and a zero
-// record where the pose sends a finite point to a non-finite one).  One launch of k_map_linearize_batch, one of k_map_lin_reduce_batch
-// per level, one copy of K x 256 bytes, one wait
-int lin_batch_core(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double *T, uint32_t K, const wc_map_reg_params *params,
-                   wc_map_normal_eq *h_out, int32_t *h_status) {
+constexpr uint64_t kLinBatchItems = 1ull << 20;  // (hypothesis, tile) pairs of one batched call: a design cap, about 270 MB of partials
+// The linearisation at K >= 1 poses behind the entry points' argument checks: every hypothesis's record and status (WC_OK, or WC_ERR_ARG
+// and a zero record where the pose sends a finite point to a non-finite one).  One launch of k_map_linearize, one of k_map_lin_reduce per
+// level, one copy of K x 256 bytes, one wait.  K = 1: the pose travels in the kernel arguments (no copy to the device) and rows may be
+// non-null; K > 1: the poses are uploaded from their pinned block first
+int lin_core(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double *T, uint32_t K, const wc_map_reg_params *params, wc_map_reg_row *rows,
+             wc_map_normal_eq *h_out, int32_t *h_status) {
   std::memset(h_out, 0, (size_t)K * sizeof(*h_out));
   for (uint32_t h = 0; h < K; ++h) h_status[h] = WC_OK;
   if (pts->n == 0) return WC_OK;
   const uint64_t tiles = (pts->n + kLinThreads - 1) / kLinThreads, hyp_words = lin_words(tiles);
   // the partials hypothesis-major, then the K final partials side by side (the last level writes there, not into its own slot)
   WC_TRY(wc_ensure(ctx, m->b_lin, ((uint64_t)K * hyp_words + (uint64_t)K * kLinWords) * 8));
-  WC_TRY(wc_ensure(ctx, m->b_pose, (size_t)K * 12 * sizeof(double)));
-  if (m->h_linb_cap < K) {
-    if (m->h_linb) (void)hipHostFree(m->h_linb);
+  if (m->h_lin_cap < K) {
+    if (m->h_lin) (void)hipHostFree(m->h_lin);
     if (m->h_pose) (void)hipHostFree(m->h_pose);
-    m->h_linb = nullptr, m->h_pose = nullptr, m->h_linb_cap = 0;
-    WC_HIP(ctx, hipHostMalloc((void **)&m->h_linb, (size_t)K * kLinWords * 8));
-    WC_HIP(ctx, hipHostMalloc((void **)&m->h_pose, (size_t)K * 12 * sizeof(double)));
-    m->h_linb_cap = K;
+    m->h_lin = nullptr, m->h_pose = nullptr, m->h_lin_cap = 0;
+    WC_HIP(ctx, hipHostMalloc((void **)&m->h_lin, (size_t)K * kLinWords * 8));
+    if (K > 1) WC_HIP(ctx, hipHostMalloc((void **)&m->h_pose, (size_t)K * 12 * sizeof(double)));
+    m->h_lin_cap = K;
   }
-  std::memcpy(m->h_pose, T, (size_t)K * 12 * sizeof(double));
-  WC_HIP(ctx, hipMemcpyAsync(m->b_pose.p, m->h_pose, (size_t)K * 12 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   unsigned long long *base = (unsigned long long *)m->b_lin.p, *fin = base + (uint64_t)K * hyp_words;
+  const map_reg R = reg_of(params);
   const uint64_t items = (uint64_t)K * tiles;
   uint64_t grid = std::min<uint64_t>(items, (uint64_t)8 * m->cus);
   if (ctx->dev.map_lin_groups > 0) grid = std::min<uint64_t>(items, (uint64_t)ctx->dev.map_lin_groups);  // (development option)
-  k_map_linearize_batch<<<(unsigned)grid, kLinThreads, 0, ctx->stream>>>(*pts, (const double *)m->b_pose.p, K, reg_of(params), m->voxel, m->keys,
-                                                                         m->pay, m->mom, m->cap - 1, base, hyp_words);
+  if (K == 1) {
+    map_pose P;
+    std::memcpy(P.T, T, sizeof(P.T));
+    k_map_linearize<true><<<(unsigned)grid, kLinThreads, 0, ctx->stream>>>(*pts, P, nullptr, 1u, R, m->voxel, m->keys, m->pay, m->mom, m->cap - 1,
+                                                                          rows, base, hyp_words);
+  } else {
+    WC_TRY(wc_ensure(ctx, m->b_pose, (size_t)K * 12 * sizeof(double)));
+    std::memcpy(m->h_pose, T, (size_t)K * 12 * sizeof(double));
+    WC_HIP(ctx, hipMemcpyAsync(m->b_pose.p, m->h_pose, (size_t)K * 12 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    k_map_linearize<false><<<(unsigned)grid, kLinThreads, 0, ctx->stream>>>(*pts, map_pose{}, (const double *)m->b_pose.p, K, R, m->voxel, m->keys,
+                                                                           m->pay, m->mom, m->cap - 1, nullptr, base, hyp_words);
+  }
   WC_HIP(ctx, hipGetLastError());
   uint64_t cnt = tiles, off = 0;  // the level's partials and where they start within a hypothesis
   do {
     const uint64_t nxt = (cnt + kLinFan - 1) / kLinFan, off_out = off + cnt * kLinWords;
     unsigned long long *out = nxt > 1 ? base + off_out : fin;
     const uint64_t out_stride = nxt > 1 ? hyp_words : (uint64_t)kLinWords, lanes = (uint64_t)K * nxt * kLinWords;
-    k_map_lin_reduce_batch<<<(unsigned)((lanes + 255) / 256), 256, 0, ctx->stream>>>(base + off, hyp_words, cnt, out, out_stride, K);
+    k_map_lin_reduce<<<(unsigned)((lanes + 255) / 256), 256, 0, ctx->stream>>>(base + off, hyp_words, cnt, out, out_stride, K);
     WC_HIP(ctx, hipGetLastError());
     off = off_out, cnt = nxt;
   } while (cnt > 1);
-  WC_HIP(ctx, hipMemcpyAsync(m->h_linb, fin, (size_t)K * kLinWords * 8, hipMemcpyDeviceToHost, ctx->stream));
+  WC_HIP(ctx, hipMemcpyAsync(m->h_lin, fin, (size_t)K * kLinWords * 8, hipMemcpyDeviceToHost, ctx->stream));
   WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (uint32_t h = 0; h < K; ++h) {
-    const unsigned long long *part = m->h_linb + (size_t)h * kLinWords;
+    const unsigned long long *part = m->h_lin + (size_t)h * kLinWords;
     if (part[kLinSums + 2])
       h_status[h] = WC_ERR_ARG;
     else
@@ -1916,19 +1877,32 @@ int lin_batch_core(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double *T
   }
   return WC_OK;
 }
+// the single calls' error for a status lin_core left at K = 1 (the count is still in its landing place)
+int lin_one_failed(wc_ctx *ctx, const wc_map *m, const char *fn) {
+  return wc_fail(ctx, WC_ERR_ARG, "%s: T sends %llu finite points to a non-finite one", fn, m->h_lin[kLinSums + 2]);
+}
 // what wc_map_linearize_batch refuses of its arguments other than the records it writes; WC_OK: the call may run
 int lin_batch_check(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double *T, uint32_t K, const wc_map_reg_params *params, const char *fn) {
-  if (!map_ok(ctx, m) || !m->mom || !map_points_ok(pts) || (K && !T) || !reg_params_ok(params) || K > kLinBatchMax)
+  if (!reg_args_ok(ctx, m, pts, params) || (K && !T) || K > kLinBatchMax)
     return wc_fail(ctx, WC_ERR_ARG,
                    "%s: null or out-of-range argument (K <= 1024), a map of another context or one created without WC_MAP_MOMENTS", fn);
-  for (uint64_t j = 0; j < (uint64_t)K * 12; ++j)
-    if (!std::isfinite(T[j]))
-      return wc_fail(ctx, WC_ERR_ARG, "%s: entry %u of hypothesis %u's T is not finite", fn, (unsigned)(j % 12), (unsigned)(j / 12));
+  WC_TRY(poses_finite(ctx, T, K, fn));
   if ((uint64_t)K * ((pts->n + kLinThreads - 1) / kLinThreads) > kLinBatchItems)
     return wc_fail(ctx, WC_ERR_CAPACITY, "%s: K * ceil(n / 256) exceeds 2^20", fn);
   return WC_OK;
 }
 }  // namespace
+
+extern "C" int wc_map_linearize(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double T[12], const wc_map_reg_params *params,
+                                wc_map_normal_eq *h_out, wc_map_reg_row *d_rows) {
+  wc_dev_guard dg_(ctx);
+  if (!reg_args_ok(ctx, m, pts, params) || !T || !h_out || (uintptr_t)d_rows % 8)
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument, a map of another context or one created without WC_MAP_MOMENTS", __func__);
+  WC_TRY(poses_finite(ctx, T, 1, __func__));
+  int32_t status;
+  WC_TRY(lin_core(ctx, m, pts, T, 1, params, d_rows, h_out, &status));
+  return status == WC_OK ? WC_OK : lin_one_failed(ctx, m, __func__);
+}
 
 extern "C" int wc_map_linearize_batch(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double *T, uint32_t K, const wc_map_reg_params *params,
                                       wc_map_normal_eq *h_out, int32_t *h_status) {
@@ -1936,7 +1910,7 @@ extern "C" int wc_map_linearize_batch(wc_ctx *ctx, wc_map *m, const wc_points *p
   if (K && (!h_out || !h_status)) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
   WC_TRY(lin_batch_check(ctx, m, pts, T, K, params, __func__));
   if (K == 0) return WC_OK;
-  return lin_batch_core(ctx, m, pts, T, K, params, h_out, h_status);
+  return lin_core(ctx, m, pts, T, K, params, nullptr, h_out, h_status);
 }
 
 namespace {
@@ -1999,7 +1973,7 @@ bool gn_step(const wc_map_normal_eq &ne, double min_pivot, double xi[6]) {
 bool align_opts_ok(const wc_map_align_opts *o) {
   return o && o->max_iterations >= 1 && o->tol_rot > 0.0 && o->tol_trans > 0.0 && o->min_used >= 6 && o->min_pivot > 0.0;
 }
-// wc_map_align's loop in pieces, so that the single call and the lockstep rounds of wc_map_align_batch run one copy of it
+// the Gauss-Newton loop of one start in pieces: the lockstep rounds of align_batch_core call them per hypothesis
 enum { kAlignGo = 0, kAlignEndFresh = 1, kAlignEndStale = 2 };  // iterate again; ended, ne is the linearisation at T_io; ended, it is not
 void align_begin(wc_map_align_summary *s) {
   std::memset(s, 0, sizeof(*s));
@@ -2039,28 +2013,12 @@ void align_end(const wc_map_normal_eq &ne, wc_map_align_summary *s) {
 }
 }  // namespace
 
-extern "C" int wc_map_align(wc_ctx *ctx, wc_map *m, const wc_points *pts, double T_io[12], const wc_map_align_opts *o,
-                            wc_map_align_summary *h_out) {
-  if (!ctx || !T_io || !h_out || !align_opts_ok(o))
-    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (max_iterations >= 1, tol_rot, tol_trans, min_pivot > 0, min_used >= 6)",
-                   __func__);
-  align_begin(h_out);
-  wc_map_normal_eq ne;
-  int st = kAlignGo;
-  for (uint32_t it = 0; st == kAlignGo; ++it) {
-    WC_TRY(wc_map_linearize(ctx, m, pts, T_io, &o->reg, &ne, nullptr));
-    st = align_iter(ne, it, T_io, o, h_out);
-  }
-  if (st == kAlignEndStale) WC_TRY(wc_map_linearize(ctx, m, pts, T_io, &o->reg, &ne, nullptr));
-  align_end(ne, h_out);
-  return WC_OK;
-}
-
 namespace {
-// wc_map_align_batch behind its argument checks.  resume: the hypotheses whose h_status is not WC_OK on entry are skipped - T and status
-// stay, the summary is zero (wc_map_align_pyramid_batch's later levels); otherwise every status starts as WC_OK.
-// Round r: ONE lin_batch_core over the compacted poses of the hypotheses that iterate (r < max_iterations) and of those that ended in
-// round r - 1 and wait for the linearisation at their final T: at most max_iterations + 1 rounds
+// The alignment of K >= 1 starts behind the entry points' argument checks.  resume: the hypotheses whose h_status is not WC_OK on entry
+// are skipped - T and status stay, the summary is zero (wc_map_align_pyramid_batch's later levels); otherwise every status starts as
+// WC_OK.  Round r: ONE lin_core over the compacted poses of the hypotheses that iterate (r < max_iterations) and of those that ended in
+// round r - 1 and wait for the linearisation at their final T: at most max_iterations + 1 rounds.  A hypothesis whose linearisation
+// fails ends there: its status is the error, its T and summary stay as they stand
 int align_batch_core(wc_ctx *ctx, wc_map *m, const wc_points *pts, double *T_io, uint32_t K, const wc_map_align_opts *o, wc_map_align_summary *h_out,
                      int32_t *h_status, bool resume) {
   constexpr int kDone = 3;
@@ -2076,8 +2034,9 @@ int align_batch_core(wc_ctx *ctx, wc_map *m, const wc_points *pts, double *T_io,
   }
   std::vector<uint32_t> idx;
   std::vector<double> Tc;
-  std::vector<wc_map_normal_eq> ne;
-  std::vector<int32_t> st;
+  std::vector<wc_map_normal_eq> ne(K);  // (sized once: a round fills a prefix)
+  std::vector<int32_t> st(K);
+  idx.reserve(K), Tc.reserve((size_t)K * 12);
   for (uint32_t it = 0;; ++it) {
     idx.clear(), Tc.clear();
     for (uint32_t h = 0; h < K; ++h)
@@ -2086,11 +2045,10 @@ int align_batch_core(wc_ctx *ctx, wc_map *m, const wc_points *pts, double *T_io,
         Tc.insert(Tc.end(), T_io + 12 * (size_t)h, T_io + 12 * (size_t)h + 12);
       }
     if (idx.empty()) break;
-    ne.resize(idx.size()), st.resize(idx.size());
-    WC_TRY(lin_batch_core(ctx, m, pts, Tc.data(), (uint32_t)idx.size(), &o->reg, ne.data(), st.data()));
+    WC_TRY(lin_core(ctx, m, pts, Tc.data(), (uint32_t)idx.size(), &o->reg, nullptr, ne.data(), st.data()));
     for (size_t a = 0; a < idx.size(); ++a) {
       const uint32_t h = idx[a];
-      if (st[a] != WC_OK) {  // (the single call returns here: T_io and the summary as they stand)
+      if (st[a] != WC_OK) {
         h_status[h] = st[a], state[h] = kDone;
         continue;
       }
@@ -2104,33 +2062,52 @@ int align_batch_core(wc_ctx *ctx, wc_map *m, const wc_points *pts, double *T_io,
   }
   return WC_OK;
 }
+// one start through align_batch_core, its status as the call's error: wc_map_align and a level of wc_map_align_pyramid behind their checks
+int align_one(wc_ctx *ctx, wc_map *m, const wc_points *pts, double T_io[12], const wc_map_align_opts *o, wc_map_align_summary *h_out,
+              const char *fn) {
+  int32_t status;
+  WC_TRY(align_batch_core(ctx, m, pts, T_io, 1, o, h_out, &status, false));
+  return status == WC_OK ? WC_OK : lin_one_failed(ctx, m, fn);
+}
+constexpr const char *kAlignOptsMsg =
+    "%s: null or out-of-range argument (max_iterations >= 1, tol_rot, tol_trans, min_pivot > 0, min_used >= 6)";
 }  // namespace
+
+extern "C" int wc_map_align(wc_ctx *ctx, wc_map *m, const wc_points *pts, double T_io[12], const wc_map_align_opts *o,
+                            wc_map_align_summary *h_out) {
+  wc_dev_guard dg_(ctx);
+  if (!ctx || !T_io || !h_out || !align_opts_ok(o)) return wc_fail(ctx, WC_ERR_ARG, kAlignOptsMsg, __func__);
+  align_begin(h_out);  // (a refusal below leaves the summary begun, as it always has)
+  if (!reg_args_ok(ctx, m, pts, &o->reg))
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument, a map of another context or one created without WC_MAP_MOMENTS", __func__);
+  WC_TRY(poses_finite(ctx, T_io, 1, __func__));
+  return align_one(ctx, m, pts, T_io, o, h_out, __func__);
+}
 
 extern "C" int wc_map_align_batch(wc_ctx *ctx, wc_map *m, const wc_points *pts, double *T_io, uint32_t K, const wc_map_align_opts *o,
                                   wc_map_align_summary *h_out, int32_t *h_status) {
   wc_dev_guard dg_(ctx);
-  if (!ctx || (K && (!T_io || !h_out || !h_status)) || !align_opts_ok(o))
-    return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (max_iterations >= 1, tol_rot, tol_trans, min_pivot > 0, min_used >= 6)",
-                   __func__);
+  if (!ctx || (K && (!T_io || !h_out || !h_status)) || !align_opts_ok(o)) return wc_fail(ctx, WC_ERR_ARG, kAlignOptsMsg, __func__);
   WC_TRY(lin_batch_check(ctx, m, pts, T_io, K, &o->reg, __func__));
   if (K == 0) return WC_OK;
   return align_batch_core(ctx, m, pts, T_io, K, o, h_out, h_status, false);
 }
 
-// coarse to fine: one wc_map_align per level, each from the pose the level before it left.  Everything wc_map_align and wc_map_linearize
-// refuse from their arguments alone is checked for every level before the first one runs
+// coarse to fine: one start per level, each from the pose the level before it left; the first level whose linearisation fails is the
+// call's error, and the later levels' summaries stay untouched.  Everything wc_map_align refuses from its arguments alone is checked for
+// every level before the first one runs
 extern "C" int wc_map_align_pyramid(wc_ctx *ctx, wc_map *const *levels, uint32_t n_levels, const wc_points *pts, double T_io[12],
                                     const wc_map_align_opts *opts, wc_map_align_summary *h_out) {
-  bool ok = ctx && levels && n_levels >= 1 && n_levels <= 8 && map_points_ok(pts) && T_io && opts && h_out;
+  wc_dev_guard dg_(ctx);
+  bool ok = ctx && levels && n_levels >= 1 && n_levels <= 8 && T_io && opts && h_out;
   for (int j = 0; ok && j < 12; ++j) ok = std::isfinite(T_io[j]);
-  for (uint32_t l = 0; ok && l < n_levels; ++l)
-    ok = map_ok(ctx, levels[l]) && levels[l]->mom && align_opts_ok(&opts[l]) && reg_params_ok(&opts[l].reg);
+  for (uint32_t l = 0; ok && l < n_levels; ++l) ok = reg_args_ok(ctx, levels[l], pts, &opts[l].reg) && align_opts_ok(&opts[l]);
   if (!ok)
     return wc_fail(ctx, WC_ERR_ARG,
                    "%s: null or out-of-range argument (1 <= n_levels <= 8; per level what wc_map_align refuses: a map of another context or one "
                    "created without WC_MAP_MOMENTS, its options), or a T_io that is not finite",
                    __func__);
-  for (uint32_t l = 0; l < n_levels; ++l) WC_TRY(wc_map_align(ctx, levels[l], pts, T_io, &opts[l], &h_out[l]));
+  for (uint32_t l = 0; l < n_levels; ++l) WC_TRY(align_one(ctx, levels[l], pts, T_io, &opts[l], &h_out[l], __func__));
   return WC_OK;
 }
 
@@ -2189,9 +2166,7 @@ extern "C" int wc_map_score_batch(wc_ctx *ctx, wc_map *m, const wc_points *pts, 
       pts->n >= ((uint64_t)1 << 31) || K > kScoreMaxK)
     return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument (n < 2^31, K <= 2^20, min_points >= 1, reserved = 0), or a map of another context",
                    __func__);
-  for (uint64_t j = 0; j < (uint64_t)K * 12; ++j)
-    if (!std::isfinite(T[j]))
-      return wc_fail(ctx, WC_ERR_ARG, "%s: entry %u of hypothesis %u's T is not finite", __func__, (unsigned)(j % 12), (unsigned)(j / 12));
+  WC_TRY(poses_finite(ctx, T, K, __func__));
   if ((uint64_t)K * pts->n > kScoreMaxPairs) return wc_fail(ctx, WC_ERR_CAPACITY, "%s: K * n exceeds 2^34", __func__);
   if (K == 0) return WC_OK;
   if (pts->n == 0) {

@@ -554,46 +554,56 @@ void FreeLevels(wc_ctx *ctx, wc_map *(&levels)[kMaxLevels], uint32_t n_levels) {
       if (rc != WC_OK) FatalCall(ctx, "wc_map_destroy", rc);
     }
 }
+// What the three relocalisations share: the levels built (BuildLevels), the points uploaded once, the candidate starts in T through ONE
+// wc_map_align_pyramid_batch, the built levels destroyed.  seed(coarsest level, points) runs ahead of the alignment and may still fill T;
+// false from it ends the call.  T: K x 12 doubles, the starts in and the aligned poses out; s: n_levels x K summaries, level-major;
+// status: K codes.  false: BuildLevels' cases, the seed's, or arguments the library refuses (no abort: as in AlignToMap)
+template <class Seed>
+bool AlignCandidates(wc_ctx *ctx, wc_map *map, double voxel, const float *xyz, size_t n, uint32_t factor, uint32_t n_levels,
+                     const wc_map_align_opts &finest, Seed seed, std::vector<double> &T, std::vector<wc_map_align_summary> &s,
+                     std::vector<int32_t> &status) {
+  wc_map *levels[kMaxLevels] = {};
+  wc_map_align_opts opts[kMaxLevels];
+  bool ok = BuildLevels(ctx, map, voxel, factor, n_levels, finest, levels, opts);
+  if (ok) {
+    const DevBuf d_xyz(ctx, n * 3 * sizeof(float));
+    const wc_points desc = UploadXyz(d_xyz, xyz, n);
+    ok = seed(levels[0], desc);
+    if (ok) {
+      const uint32_t K = (uint32_t)(T.size() / 12);
+      s.resize((size_t)n_levels * K), status.resize(K);
+      ok = wc_map_align_pyramid_batch(ctx, levels, n_levels, &desc, T.data(), K, opts, s.data(), status.data()) == WC_OK;
+    }
+  }
+  FreeLevels(ctx, levels, n_levels);
+  return ok;
+}
+const auto kNoSeed = [](wc_map *, const wc_points &) { return true; };
 }  // namespace
 bool LidarOdometry::RelocalizeToMap(const float *xyz, size_t n, double T_io[12], uint32_t factor, uint32_t n_levels, const wc_map_align_opts &finest,
                                     wc_map_align_summary *summaries) {
   if (!map_ || !map_moments_ || !T_io || (n && !xyz) || factor < 1 || n_levels < 1 || n_levels > kMaxLevels) return false;
-  wc_map *levels[kMaxLevels] = {};
-  wc_map_align_opts opts[kMaxLevels];
-  wc_map_align_summary s[kMaxLevels];
-  bool ok = BuildLevels(ctx_, map_, map_voxel_, factor, n_levels, finest, levels, opts);
-  double T[12];
-  std::memcpy(T, T_io, sizeof(T));
-  if (ok) {
-    const DevBuf d_xyz(ctx_, n * 3 * sizeof(float));
-    const wc_points desc = UploadXyz(d_xyz, xyz, n);
-    ok = wc_map_align_pyramid(ctx_, levels, n_levels, &desc, T, opts, s) == WC_OK;  // (as in AlignToMap)
-  }
-  FreeLevels(ctx_, levels, n_levels);
-  if (!ok) return false;
-  std::memcpy(T_io, T, sizeof(T));
-  if (summaries) std::memcpy(summaries, s, n_levels * sizeof(s[0]));
+  std::vector<double> T(T_io, T_io + 12);
+  std::vector<wc_map_align_summary> s;
+  std::vector<int32_t> status;
+  // (one hypothesis: by the batched form's contract what wc_map_align_pyramid leaves; its error is the hypothesis's status)
+  if (!AlignCandidates(ctx_, map_, map_voxel_, xyz, n, factor, n_levels, finest, kNoSeed, T, s, status) || status[0] != WC_OK) return false;
+  std::memcpy(T_io, T.data(), 12 * sizeof(double));
+  if (summaries) std::memcpy(summaries, s.data(), s.size() * sizeof(s[0]));
   return true;
 }
 bool LidarOdometry::RelocalizeSearch(const float *xyz, size_t n, double T_io[12], uint32_t n_yaw, uint32_t factor, uint32_t n_levels,
                                      const wc_map_align_opts &finest, wc_map_align_summary *summaries, int32_t *best) {
   if (!map_ || !map_moments_ || !T_io || (n && !xyz) || factor < 1 || n_levels < 1 || n_levels > kMaxLevels || n_yaw < 1 || n_yaw > 1024)
     return false;
-  wc_map *levels[kMaxLevels] = {};
-  wc_map_align_opts opts[kMaxLevels];
   std::vector<double> T((size_t)n_yaw * 12);
-  std::vector<wc_map_align_summary> s((size_t)n_levels * n_yaw);
-  std::vector<int32_t> status(n_yaw);
-  bool ok = BuildLevels(ctx_, map_, map_voxel_, factor, n_levels, finest, levels, opts) && wc_pose_yaw_grid(T_io, n_yaw, T.data()) == WC_OK;
-  if (ok) {
-    const DevBuf d_xyz(ctx_, n * 3 * sizeof(float));
-    const wc_points desc = UploadXyz(d_xyz, xyz, n);
-    ok = wc_map_align_pyramid_batch(ctx_, levels, n_levels, &desc, T.data(), n_yaw, opts, s.data(), status.data()) == WC_OK;  // (as in AlignToMap)
-  }
-  FreeLevels(ctx_, levels, n_levels);
+  std::vector<wc_map_align_summary> s;
+  std::vector<int32_t> status;
   int32_t win = -1;
-  ok = ok && wc_map_align_best(s.data() + (size_t)(n_levels - 1) * n_yaw, status.data(), n_yaw, finest.min_used, &win) == WC_OK && win >= 0;
-  if (!ok) return false;
+  if (wc_pose_yaw_grid(T_io, n_yaw, T.data()) != WC_OK ||
+      !AlignCandidates(ctx_, map_, map_voxel_, xyz, n, factor, n_levels, finest, kNoSeed, T, s, status) ||
+      wc_map_align_best(s.data() + (size_t)(n_levels - 1) * n_yaw, status.data(), n_yaw, finest.min_used, &win) != WC_OK || win < 0)
+    return false;
   std::memcpy(T_io, T.data() + (size_t)win * 12, 12 * sizeof(double));
   if (summaries) std::memcpy(summaries, s.data(), s.size() * sizeof(s[0]));
   if (best) *best = win;
@@ -608,32 +618,27 @@ bool LidarOdometry::RelocalizeGlobal(const float *xyz, size_t n, double T_io[12]
   uint64_t K = n_yaw;  // (wc_pose_grid refuses what is out of range; here only the size of its output is needed)
   for (int a = 0; a < 3; ++a) K = K > ((uint64_t)1 << 20) ? K : K * n_xyz[a];
   if (K == 0 || K > ((uint64_t)1 << 20)) return false;
-  std::vector<double> grid((size_t)K * 12);
-  wc_map *levels[kMaxLevels] = {};
-  wc_map_align_opts opts[kMaxLevels];
-  std::vector<wc_map_score> scores((size_t)K);
-  std::vector<int32_t> idx(top_m), status(top_m);
-  std::vector<double> T((size_t)top_m * 12);
+  std::vector<double> grid((size_t)K * 12), T;
   std::vector<wc_map_align_summary> s;
+  std::vector<int32_t> status;
   uint32_t cnt = 0;
-  bool ok = BuildLevels(ctx_, map_, map_voxel_, factor, n_levels, finest, levels, opts) &&
-            wc_pose_grid(T_io, n_yaw, n_xyz, step, grid.data()) == WC_OK;
-  if (ok) {
-    const DevBuf d_xyz(ctx_, n * 3 * sizeof(float));
-    const wc_points desc = UploadXyz(d_xyz, xyz, n);
+  // the starts: the top_m best of the grid by their occupancy score on the coarsest level, in rank order
+  const auto seed = [&](wc_map *coarsest, const wc_points &desc) {
+    std::vector<wc_map_score> scores((size_t)K);
+    std::vector<int32_t> idx(top_m);
     const wc_map_score_params sp = {1u, 0u};
-    ok = wc_map_score_batch(ctx_, levels[0], &desc, grid.data(), (uint32_t)K, &sp, scores.data()) == WC_OK &&  // (as in AlignToMap)
-         wc_map_score_top(scores.data(), (uint32_t)K, top_m, finest.min_used, idx.data(), &cnt) == WC_OK && cnt >= 1;
-    if (ok) {
-      for (uint32_t r = 0; r < cnt; ++r) std::memcpy(T.data() + (size_t)r * 12, grid.data() + (size_t)idx[r] * 12, 12 * sizeof(double));
-      s.resize((size_t)n_levels * cnt);
-      ok = wc_map_align_pyramid_batch(ctx_, levels, n_levels, &desc, T.data(), cnt, opts, s.data(), status.data()) == WC_OK;
-    }
-  }
-  FreeLevels(ctx_, levels, n_levels);
+    if (wc_map_score_batch(ctx_, coarsest, &desc, grid.data(), (uint32_t)K, &sp, scores.data()) != WC_OK ||
+        wc_map_score_top(scores.data(), (uint32_t)K, top_m, finest.min_used, idx.data(), &cnt) != WC_OK || cnt < 1)
+      return false;
+    T.resize((size_t)cnt * 12);
+    for (uint32_t r = 0; r < cnt; ++r) std::memcpy(T.data() + (size_t)r * 12, grid.data() + (size_t)idx[r] * 12, 12 * sizeof(double));
+    return true;
+  };
   int32_t win = -1;
-  ok = ok && wc_map_align_best(s.data() + (size_t)(n_levels - 1) * cnt, status.data(), cnt, finest.min_used, &win) == WC_OK && win >= 0;
-  if (!ok) return false;
+  if (wc_pose_grid(T_io, n_yaw, n_xyz, step, grid.data()) != WC_OK ||
+      !AlignCandidates(ctx_, map_, map_voxel_, xyz, n, factor, n_levels, finest, seed, T, s, status) ||
+      wc_map_align_best(s.data() + (size_t)(n_levels - 1) * cnt, status.data(), cnt, finest.min_used, &win) != WC_OK || win < 0)
+    return false;
   std::memcpy(T_io, T.data() + (size_t)win * 12, 12 * sizeof(double));
   if (summaries) {  // (level-major with top_m records per level; the candidates that did not exist: zero)
     std::memset(summaries, 0, (size_t)n_levels * top_m * sizeof(summaries[0]));

@@ -105,7 +105,8 @@ class LidarOdometry {
   // the library refuses the arguments.  Nothing in AddLidarScan calls it
   bool AlignToMap(const float *xyz, size_t n, double T_io[12], const wc_map_align_opts &opts, wc_map_align_summary *summary);
   // AlignToMap from a rough pose, coarse to fine: levels 1 .. n_levels - 1 are built from the map by chained wc_map_coarsen(factor) - level
-  // l has voxel size (double)factor * that of level l - 1 -, wc_map_align_pyramid runs them coarsest first and the map itself last, each with
+  // l has voxel size (double)factor * that of level l - 1 -, the pyramid (wc_map_align_pyramid_batch with this one start: byte for byte
+  // wc_map_align_pyramid, whose error is the start's status) runs them coarsest first and the map itself last, each with
   // `finest` except reg.max_dist, which is multiplied by (double)factor^l; then the built levels are destroyed.  summaries (may be null):
   // n_levels records, coarsest first.  Nothing is cached: the levels are rebuilt per call (a relocalisation is rare; DESIGN 8.9 has the
   // cost).  false - nothing touched - where AlignToMap returns false, for factor < 1, n_levels outside 1 .. 8, and when a level's voxel
