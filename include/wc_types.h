@@ -170,6 +170,51 @@ typedef struct wc_map_align_summary { /* 88 bytes */
   double last_step[6];  /* the last update applied (omega, upsilon); 0 if none                       */
 } wc_map_align_summary;
 
+/* wc_map_linearize_ct / wc_map_align_ct (wildcat_hip.h: "registration of a stamped sweep in continuous time"; not reference types) */
+typedef struct wc_map_ct_normal_eq { /* 640 bytes */
+  double H00[21];     /* upper triangle, row-major: sum (kaa J_i) J_j, kaa = (k a) a; the begin pose's block           */
+  double H01[21];     /* sum (kab J_i) J_j, kab = (k a) s: the block between the poses (symmetric as well)              */
+  double H11[21];     /* sum (kbb J_i) J_j, kbb = (k s) s; the end pose's block                                        */
+  double g0[6];       /* sum (ka J_i) d, ka = k a                                                                      */
+  double g1[6];       /* sum (kb J_i) d, kb = k s                                                                      */
+  double cost;        /* 0.5 * sum rho                                                                                 */
+  uint64_t n_used;    /* points in span with a valid plane                                                             */
+  uint64_t n_found;   /* points in span whose search found a voxel                                                     */
+  uint64_t n_outside; /* points whose stamp is not in [t_begin, t_end] (a NaN stamp included)                          */
+  uint64_t reserved;  /* written as 0                                                                                  */
+} wc_map_ct_normal_eq;
+
+typedef struct wc_map_ct_row { /* 72 bytes: one point's share, optional output; all zero for an unused point */
+  double J[6]; /* wc_map_reg_row's J at the moved point                         */
+  double d;    /* the plane hit's dist                                          */
+  double k;    /* w2 * rho'                                                     */
+  double s;    /* (t - t_begin) / span: the end pose's share, 1.0 - s the begin's */
+} wc_map_ct_row;
+
+typedef struct wc_map_ct_align_opts { /* 96 bytes */
+  wc_map_reg_params reg;
+  uint32_t max_iterations; /* >= 1                                                                             */
+  uint32_t min_used;       /* >= 12: fewer used points end the loop with termination 2                         */
+  double tol_rot;          /* > 0 [rad]: converged when both |omega| <= tol_rot and ...                        */
+  double tol_trans;        /* > 0 [m]:   ... both |upsilon| <= tol_trans                                       */
+  double min_pivot;        /* > 0: wc_map_align_opts' min_pivot, for the 12 x 12 matrix                        */
+  double prior[4];         /* >= 0, finite: information weights holding the begin rotation [rad^-2], the begin
+                              translation [m^-2], the end rotation and the end translation to their input
+                              values (first order: wildcat_hip.h); 0: none                                     */
+} wc_map_ct_align_opts;
+
+typedef struct wc_map_ct_align_summary { /* 152 bytes */
+  double initial_cost;  /* cost at the poses passed in (the points' share alone)                     */
+  double final_cost;    /* cost at the poses returned (the points' share alone)                      */
+  int32_t iterations;   /* pose updates applied                                                      */
+  int32_t termination;  /* as wc_map_align_summary: 0 = convergence, 1 = max_iterations, 2 = failure */
+  uint64_t n_used;      /* at the poses returned                                                     */
+  uint64_t n_found;
+  uint64_t n_outside;
+  double last_step[12]; /* the last update applied (omega, upsilon of begin, then of end); 0 if none */
+  double prior_cost;    /* 0.5 * sum w_i acc_i^2 at the poses returned, acc = the sum of the steps   */
+} wc_map_ct_align_summary;
+
 /* wc_map_score_batch (wildcat_hip.h: "occupancy score of pose hypotheses"; not reference types) */
 typedef struct wc_map_score { /* 16 bytes: one hypothesis */
   uint32_t n_hit;    /* points whose own voxel is live in the map with count >= min_points              */

@@ -695,6 +695,72 @@ int wc_map_align_best(const wc_map_align_summary *s, const int32_t *status, uint
  * nothing is written.  WC_ERR_ARG: a NULL argument (T_out may be NULL when K == 0). */
 int wc_pose_yaw_grid(const double T0[12], uint32_t K, double *T_out);
 
+/* registration of a stamped sweep in continuous time: two poses ------------------------------------------------------------ */
+/* wc_map_linearize_ct is wc_map_linearize for a RAW sweep: every point carries a stamp (pts->time, doubles, DEVICE), and the unknowns are
+ * the pose at t_begin and the pose at t_end (wc_pose: pos, quat = (w, x, y, z); body -> map), 12 degrees of freedom.  A point's pose is
+ * interpolated between the two by its stamp on the device.  On the host, once: span = t_end - t_begin, and quat_end is negated where
+ * (((w0 w1 + x0 x1) + y0 y1) + z0 z1) < 0; the quaternions need not be unit.  One point, with p = its floats cast to double, t its stamp, no
+ * fused multiply-add anywhere, q0 / p0 the begin pose's quat / pos and q1 / p1 the end's:
+ *   s = (t - t_begin) / span,  a = 1.0 - s;  the point is IN SPAN iff t_begin <= t <= t_end (a NaN stamp is not)
+ *   q_c = a * q0_c + s * q1_c  (c = w, x, y, z),   c_c = a * p0_c + s * p1_c  (c = x, y, z)
+ *   nn = ((qw qw + qx qx) + qy qy) + qz qz,  f = 2.0 / nn
+ *   u = v x p,  r = v x u,  v = (qx, qy, qz):  u_x = qy p_z - qz p_y, u_y = qz p_x - qx p_z, u_z = qx p_y - qy p_x, r likewise from v and u
+ *   P_c = (p_c + f * (qw * u_c + r_c)) + c_c,   the moved point is (float)P_c
+ * - the normalised linear blend of the two quaternions without a square root or a trigonometric function: every field is a chain of
+ * IEEE multiplications, additions and one division, so a restatement reproduces it bit for bit (wc_pose_interp_move is the host's).  It is
+ * NOT wc_undistort_sweep's slerp: it follows the same great arc at a slightly different speed.  With Theta the rotation angle between the
+ * two poses, the blend's rotation at s leads the slerp's by
+ *   delta(s) = 2 atan2(s sin(Theta / 2), (1 - s) + s cos(Theta / 2)) - s Theta
+ * about the common axis: zero at s = 0, 1/2, 1, extremal near s = 0.21 and 0.79, about 0.004 Theta^3 there (DESIGN 8.12 has the value
+ * at Theta = 0.2 rad).
+ * A point out of span is unused, counts in n_outside, and is not searched.  A point in span: its moved float point is searched exactly
+ * as wc_map_linearize searches its q (the same device functions, max_dist, min_points, flags), and J = (Q x n, n), d, w2, s2 = (w2 d) d, k
+ * and rho are wc_map_linearize's, the Cauchy form included.  The unknown is xi = (xi_begin, xi_end), each (omega, upsilon), applied as
+ * T_u <- Exp(xi_u) T_u, and the linearisation is  d(dist) ~ a J . xi_begin + s J . xi_end  (CT-ICP's): exact at T_begin = T_end and first
+ * order in the inter-pose motion otherwise - for a point p with |p_end - p_begin| = D and Theta as above, an entry of the true gradient
+ * with respect to omega_begin differs from a J_i by at most a (s D + (Theta / 2 + Theta^2 / 8) |p|), with respect to omega_end by at most
+ * s (a D + (Theta / 2 + Theta^2 / 8) |p|) (the neglected translation term is a s omega x (p_end - p_begin), the rotation term is of the
+ * order of the inter-pose angle), and the upsilon entries are exact.  Weights kaa = (k a) a, kab = (k a) s, kbb = (k s) s, ka = k a, kb = k s:
+ *   H00_ij = sum (kaa J_i) J_j,  H01_ij = sum (kab J_i) J_j,  H11_ij = sum (kbb J_i) J_j  (i <= j; all three symmetric)
+ *   g0_i = sum (ka J_i) d,  g1_i = sum (kb J_i) d,  cost = 0.5 * sum rho:   76 sums
+ *   n_used, n_found (in-span points whose search found a voxel), n_outside
+ * Order of the sums: wc_map_linearize's, unchanged - tiles of 256 points, chunks of 32 rows in ascending order, the eight chunk sums in
+ * ascending order, reduce levels of fan 32 - so A(n) carries over, and the 640 bytes are byte-equal from run to run, for every grid size
+ * (map_lin_groups), for both point layouts, with and without the optional outputs.  One 640-byte record travels back; the call waits once.
+ * d_rows (DEVICE, 8-aligned, may be NULL): one wc_map_ct_row per point (J, d, k, s), all zero for an unused point.
+ * d_xyz_out (DEVICE, 4-aligned, may be NULL): n x 3 floats, the moved point of every point in span and three quiet NaNs (0x7fc00000) for a
+ * point out of span - the registered sweep, ready for wc_map_insert (which rejects the NaN rows).
+ * WC_ERR_ARG: what wc_map_linearize refuses of its map, points and params; a NULL pts->time (with n > 0) or a time_stride that is 0 or not
+ * a multiple of 8; a NULL pose or h_out; a non-finite pose entry; a quaternion whose squared norm is 0 or not finite; t_end <= t_begin or
+ * a non-finite stamp bound or span; poses that send a finite point in span to a non-finite one (h_out is then zero).  pts->n == 0: WC_OK,
+ * h_out all zero.  The map is not modified. */
+int wc_map_linearize_ct(wc_ctx *ctx, wc_map *m, const wc_points *pts, const wc_pose *pose_begin, const wc_pose *pose_end, double t_begin,
+                        double t_end, const wc_map_reg_params *params, wc_map_ct_normal_eq *h_out, wc_map_ct_row *d_rows, float *d_xyz_out);
+/* Gauss-Newton on wc_map_linearize_ct: the two poses in, the aligned poses out.  Each iteration: linearise; termination 2 if
+ * n_used < min_used; the 12 x 12 system of wc_map_ct_step - H = (H00 H01; H01 H11), g = (g0, g1), plus the prior - solved by
+ * wc_map_align's rules (unit-diagonal scaling, Cholesky in fp64 on the host, min_pivot; one solver of a size parameter serves both); then
+ *   quat_u <- quat(Rod(omega_u)) * quat_u, divided by its norm;   pos_u <- Rod(omega_u) pos_u + upsilon_u       (u = begin, end)
+ * with quat(Rod(w)) = (cos(th / 2), (sin(th / 2) / th) w), th = |w| ((1, w / 2) at th = 0).  Termination 0 when |omega| <= tol_rot and
+ * |upsilon| <= tol_trans for both poses; 1 after max_iterations updates; a closing linearisation gives final_cost and the counts.
+ * The prior is first order: with acc the running sum of the applied steps, H_ii += w_i and g_i += w_i acc_i (w = prior[0] on the begin
+ * rotation's three entries, prior[1] on the begin translation's, prior[2], prior[3] on the end's).  It is a regulariser for sweeps whose
+ * geometry leaves a direction of one pose free - it pulls the SUM of the steps to zero -, not a prior on the manifold: the sum of rotation
+ * vectors is the rotation's logarithm only to first order.  prior_cost = 0.5 sum w_i acc_i^2.
+ * WC_ERR_ARG: max_iterations < 1, tol_rot / tol_trans / min_pivot not > 0, min_used < 12, a prior weight that is negative or not finite,
+ * and whatever wc_map_linearize_ct refuses (the poses then stay as they were passed in, or as the last accepted step left them). */
+int wc_map_align_ct(wc_ctx *ctx, wc_map *m, const wc_points *pts, wc_pose *pose_begin_io, wc_pose *pose_end_io, double t_begin, double t_end,
+                    const wc_map_ct_align_opts *opts, wc_map_ct_align_summary *h_out);
+/* The host restatement of the device's interpolation and move, same associations; host only, no context, no GPU.  xyz: n x 3 floats,
+ * times: n doubles, xyz_out: n x 3 floats - the moved point, or three quiet NaNs (0x7fc00000) for a stamp out of span.  WC_ERR_ARG: a NULL
+ * argument (the arrays may be NULL when n == 0), a non-finite pose entry, a zero quaternion, t_end <= t_begin or a non-finite bound. */
+int wc_pose_interp_move(const wc_pose *pose_begin, const wc_pose *pose_end, double t_begin, double t_end, const float *xyz,
+                        const double *times, uint64_t n, float *xyz_out);
+/* The host's 12 x 12 step; host only, no context, no GPU.  A = (H00 H01; H01 H11) + diag(w), b = (g0, g1) + w * acc; xi12 solves
+ * A xi = -b by wc_map_align's Cholesky of the matrix scaled to unit diagonal.  prior: 4 weights (wc_map_ct_align_opts), acc: 12 doubles.
+ * WC_OK: xi12 written.  WC_ERR_NUMERIC: a pivot is not finite or below min_pivot, or the step is not finite (xi12 untouched).
+ * WC_ERR_ARG: a NULL argument, min_pivot not > 0, a prior weight that is negative or not finite. */
+int wc_map_ct_step(const wc_map_ct_normal_eq *ne, const double prior[4], const double acc[12], double min_pivot, double xi12[12]);
+
 /* occupancy score of pose hypotheses ------------------------------------------------------------------------------------ */
 /* For K poses of ONE point set, how many points land in an occupied voxel of the map: T is K x 12 doubles on the HOST, h_out K records on
  * the host.  Hypothesis h has the pose T + 12 h.  One point, with x, y, z its floats cast to double and no fused multiply-add anywhere:

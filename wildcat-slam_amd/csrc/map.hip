@@ -32,6 +32,9 @@
 //                   in a fixed order (tiles of 256 points, then levels of 32 partials, one launch each), for K poses of one point set
 //                   in one launch chain with (hypothesis, tile) pairs as work items; <true>: one pose, in the kernel arguments.  One
 //                   host core (lin_core) under wc_map_linearize, wc_map_align, their pyramid and their _batch forms
+//   k_map_linearize_ct  registration of a stamped sweep between two poses: every point through the pose interpolated at its stamp
+//                   (map_move_ct), the same search, 76 sums in the same order, k_map_lin_reduce<80, 76>: wc_map_linearize_ct,
+//                   wc_map_align_ct
 //   k_map_score_batch  occupancy score of K poses of one point set: a tile of 256 points in registers walks a block of hypotheses, one
 //                   read-only probe chain per (point, pose), eight hypotheses' first-slot key loads in flight; counts by ballot, LDS and one
 //                   32-bit atomic add per workgroup, hypothesis and count: wc_map_score_batch
@@ -104,6 +107,8 @@ struct wc_map {
   wc_buf b_score;                    // wc_map_score_batch: K x 16 bytes of counts, then the K x 12 doubles of the poses; its own scratch
   unsigned char *h_score = nullptr;  // ... and the pinned block of the same layout, grown on demand: it holds h_score_cap hypotheses
   uint64_t h_score_cap = 0;
+  wc_buf b_ct;                       // wc_map_linearize_ct: the tile partials (80 words each) and every level of their reduction; its own scratch
+  unsigned long long *h_ct = nullptr;  // ... and the pinned landing place of the final partial, 640 bytes (first use)
 };
 
 namespace {
@@ -877,31 +882,178 @@ __global__ void __launch_bounds__(kScoreThreads) k_map_score_batch(wc_points pts
 }
 
 // word e of partial j of the next level: in[32 j] + in[32 j + 1] + ... in ascending order (the doubles; the counts are integers); m: the
-// partials of `in`, 32 j < m
+// partials of `in`, 32 j < m.  WORDS: the 8-byte words of a partial, the first SUMS of them doubles (32 and 28: the rigid registration's;
+// 80 and 76: the continuous-time one's)
+template <int WORDS, int SUMS>
 __device__ __forceinline__ void map_lin_reduce_word(const unsigned long long *in, uint64_t m, uint64_t j, int e, unsigned long long *out) {
   const uint64_t first = j * kLinFan;
   const uint64_t cnt = m - first < (uint64_t)kLinFan ? m - first : (uint64_t)kLinFan;
-  const unsigned long long *p = in + first * kLinWords + e;
+  const unsigned long long *p = in + first * WORDS + e;
   unsigned long long word = p[0];
-  if (e < kLinSums) {
+  if (e < SUMS) {
     double acc = __longlong_as_double((long long)word);
-    for (uint64_t r = 1; r < cnt; ++r) acc += __longlong_as_double((long long)p[r * kLinWords]);
+    for (uint64_t r = 1; r < cnt; ++r) acc += __longlong_as_double((long long)p[r * WORDS]);
     word = (unsigned long long)__double_as_longlong(acc);
   } else {
-    for (uint64_t r = 1; r < cnt; ++r) word += p[r * kLinWords];
+    for (uint64_t r = 1; r < cnt; ++r) word += p[r * WORDS];
   }
-  out[j * kLinWords + e] = word;
+  out[j * WORDS + e] = word;
 }
 
 // one level of the second stage for all K hypotheses, one lane per word of the next level: hypothesis h reads its m partials at
 // in + h * in_stride and writes its ceil(m / 32) at out + h * out_stride (words)
+template <int WORDS, int SUMS>
 __global__ void __launch_bounds__(256) k_map_lin_reduce(const unsigned long long *in, uint64_t in_stride, uint64_t m, unsigned long long *out,
                                                         uint64_t out_stride, unsigned K) {
   const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  const uint64_t per = (m + kLinFan - 1) / kLinFan * kLinWords;  // words of one hypothesis's next level
+  const uint64_t per = (m + kLinFan - 1) / kLinFan * WORDS;  // words of one hypothesis's next level
   if (g >= K * per) return;
   const uint64_t h = K == 1 ? 0 : g / per, r = g - h * per;  // (one pose: no division by a run-time value, as before the K-pose form)
-  map_lin_reduce_word(in + h * in_stride, m, r / kLinWords, (int)(r % kLinWords), out + h * out_stride);
+  map_lin_reduce_word<WORDS, SUMS>(in + h * in_stride, m, r / WORDS, (int)(r % WORDS), out + h * out_stride);
+}
+
+// ---- registration of a stamped sweep in continuous time (wc_map_linearize_ct: DESIGN 8.12) -------------------------------------------
+// k_map_linearize<true> with the point's own pose: interpolated between a begin and an end pose by the point's stamp (map_move_ct: the
+// normalised linear blend, include/wildcat_hip.h states the associations), and a row that carries the two poses' shares a = 1 - s and s.
+// 76 sums - H00, H01, H11 (21 each), g0, g1 (6 each), sum rho - in k_map_linearize's order: lane (e, c) adds the terms of rows
+// 32 c .. 32 c + 31 in ascending order, 76 x 8 pairs over 256 lanes in three rounds, then lane e adds the eight chunk sums in ascending
+// order.  One 640-byte partial per tile: 76 doubles, then n_used, n_found, n_outside, n_bad, written with plain vector stores; the
+// levels are k_map_lin_reduce<80, 76>.
+constexpr int kCtSums = 76;
+constexpr int kCtWords = 80;
+constexpr int kCtFields = 13;  // J[6], d, rho, kaa, kab, kbb, ka, kb
+struct map_ct_pose {
+  double p0[3], q0[4], p1[3], q1[4];  // pos and quat (w, x, y, z) of the begin and of the end pose; q1 on q0's side (the host negates it)
+  double t_begin, t_end, span;
+};
+// the stamp test and the share of the end pose: false (and s = 0) for a stamp outside [t_begin, t_end] or NaN
+__host__ __device__ inline bool map_ct_share(const map_ct_pose &C, double t, double &s) {
+  const bool in = t >= C.t_begin && t <= C.t_end;
+  s = in ? (t - C.t_begin) / C.span : 0.0;
+  return in;
+}
+// a point through the pose interpolated at s - the device's and wc_pose_interp_move's one copy (-ffp-contract=off: no fused multiply-add)
+__host__ __device__ inline void map_move_ct(const map_ct_pose &C, double s, float fx, float fy, float fz, float &ox, float &oy, float &oz) {
+  const double a = 1.0 - s, px = (double)fx, py = (double)fy, pz = (double)fz;
+  const double qw = a * C.q0[0] + s * C.q1[0], qx = a * C.q0[1] + s * C.q1[1], qy = a * C.q0[2] + s * C.q1[2], qz = a * C.q0[3] + s * C.q1[3];
+  const double cx = a * C.p0[0] + s * C.p1[0], cy = a * C.p0[1] + s * C.p1[1], cz = a * C.p0[2] + s * C.p1[2];
+  const double nn = ((qw * qw + qx * qx) + qy * qy) + qz * qz, f = 2.0 / nn;
+  const double ux = qy * pz - qz * py, uy = qz * px - qx * pz, uz = qx * py - qy * px;
+  const double rx = qy * uz - qz * uy, ry = qz * ux - qx * uz, rz = qx * uy - qy * ux;
+  ox = (float)((px + f * (qw * ux + rx)) + cx);
+  oy = (float)((py + f * (qw * uy + ry)) + cy);
+  oz = (float)((pz + f * (qw * uz + rz)) + cz);
+}
+
+__global__ void __launch_bounds__(kLinThreads) k_map_linearize_ct(wc_points pts, map_ct_pose C, map_reg R, double v, const unsigned long long *keys,
+                                                                  const long long *pay, const long long *mom, unsigned long long mask,
+                                                                  wc_map_ct_row *rows, float *xyz_out, unsigned long long *part) {
+  __shared__ double s_row[kCtFields * kLinPitch];
+  __shared__ double s_chunk[kCtSums * 8];
+  __shared__ unsigned s_cnt[4];
+  const int t = threadIdx.x;
+  const uint64_t tiles = (pts.n + kLinThreads - 1) / kLinThreads;
+  for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    // lanes 0 .. 3 own the count words: they zero them here and are the only lanes that read them, at the tile's end (below) - the same
+    // lane reads, then zeroes, in program order, so no barrier is needed between one tile's read and the next tile's zero
+    if (t < 4) s_cnt[t] = 0;
+    __syncthreads();  // (also: the previous tile's rows and chunk sums have been read - their next writes lie behind this barrier)
+    const uint64_t i = tile * kLinThreads + t;
+    double row[kCtFields] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    bool used = false, hit = false, bad = false, outside = false;
+    if (i < pts.n) {
+      const float *f = (const float *)((const char *)pts.xyz + i * pts.xyz_stride);
+      const float px = f[0], py = f[1], pz = f[2];
+      const double stamp = *(const double *)((const char *)pts.time + i * pts.time_stride);
+      double s;
+      const bool in = map_ct_share(C, stamp, s);
+      outside = !in;
+      float qx = __uint_as_float(0x7fc00000u), qy = qx, qz = qx;
+      double k = 0.0;
+      if (in) {
+        map_move_ct(C, s, px, py, pz, qx, qy, qz);
+        bad = isfinite(px) && isfinite(py) && isfinite(pz) && !(isfinite(qx) && isfinite(qy) && isfinite(qz));
+        const double x = (double)qx, y = (double)qy, z = (double)qz;
+        const map_found w = map_search<true>(x, y, z, v, keys, pay, mask);
+        hit = w.bc != 0 && w.best <= R.max_d2;
+        double pn[3], sigma2, dist;
+        used = map_hit_plane(w, hit, x, y, z, mom, R.min_points, pn, sigma2, dist);
+        if (used) {
+          row[0] = y * pn[2] - z * pn[1], row[1] = z * pn[0] - x * pn[2], row[2] = x * pn[1] - y * pn[0];
+          row[3] = pn[0], row[4] = pn[1], row[5] = pn[2];
+          row[6] = dist;
+          const double w2 = 1.0 / (R.s02 + sigma2), s2 = (w2 * dist) * dist;
+          if (R.a2 > 0.0) {
+            const double u = s2 / R.a2;
+            k = w2 / (1.0 + u), row[7] = R.a2 * log1p(u);
+          } else {
+            k = w2, row[7] = s2;
+          }
+          const double a = 1.0 - s, ka = k * a, kb = k * s;
+          row[8] = ka * a, row[9] = ka * s, row[10] = kb * s, row[11] = ka, row[12] = kb;
+        }
+      }
+      if (rows) {  // (the record is 8-aligned: nine 8-byte stores)
+        double *o = (double *)(rows + i);
+#pragma unroll
+        for (int fld = 0; fld < 7; ++fld) o[fld] = row[fld];
+        o[7] = k, o[8] = used ? s : 0.0;
+      }
+      if (xyz_out) xyz_out[3 * i] = qx, xyz_out[3 * i + 1] = qy, xyz_out[3 * i + 2] = qz;
+    }
+    // the counts: per wavefront, then integer adds in LDS (order independent)
+    const unsigned n_u = (unsigned)__popcll(__ballot(used)), n_h = (unsigned)__popcll(__ballot(hit)), n_o = (unsigned)__popcll(__ballot(outside)),
+                   n_b = (unsigned)__popcll(__ballot(bad));
+    if ((t & 63) == 0) {
+      if (n_u) atomicAdd(&s_cnt[0], n_u);
+      if (n_h) atomicAdd(&s_cnt[1], n_h);
+      if (n_o) atomicAdd(&s_cnt[2], n_o);
+      if (n_b) atomicAdd(&s_cnt[3], n_b);
+    }
+    const int at = t + t / kLinFan;
+#pragma unroll
+    for (int fld = 0; fld < kCtFields; ++fld) s_row[fld * kLinPitch + at] = row[fld];
+    __syncthreads();
+#pragma unroll
+    for (int round = 0; round < (kCtSums * 8 + kLinThreads - 1) / kLinThreads; ++round) {
+      const int pair = round * kLinThreads + t;
+      if (pair < kCtSums * 8) {
+        const int e = pair >> 3, c = pair & 7;
+        // e -> the three factors of a term (W X) Y: a block of H: W = kaa, kab or kbb, X = J_a, Y = J_b; g0, g1: W = ka or kb, X = J_a, Y = d
+        int fw, fx, fy = 6;
+        if (e < 63) {  // entry idx of block blk -> (a, a + b) of the upper triangle
+          const int blk = e / 21, idx = e - 21 * blk;
+          int a = 0, b = idx;
+          while (b >= 6 - a) b -= 6 - a, ++a;
+          fw = 8 + blk, fx = a, fy = a + b;
+        } else if (e < 69) {
+          fw = 11, fx = e - 63;
+        } else {
+          fw = 12, fx = e < 75 ? e - 69 : 0;  // (e = 75: sum rho, no factors)
+        }
+        const int at_c = c * (kLinFan + 1);
+        double acc;
+        if (e < 75) {
+          const double *rw = s_row + fw * kLinPitch + at_c, *rx = s_row + fx * kLinPitch + at_c, *ry = s_row + fy * kLinPitch + at_c;
+          acc = (rw[0] * rx[0]) * ry[0];
+          for (int j = 1; j < kLinFan; ++j) acc += (rw[j] * rx[j]) * ry[j];
+        } else {
+          const double *rr = s_row + 7 * kLinPitch + at_c;
+          acc = rr[0];
+          for (int j = 1; j < kLinFan; ++j) acc += rr[j];
+        }
+        s_chunk[e * 8 + c] = acc;
+      }
+    }
+    __syncthreads();
+    if (t < kCtSums) {
+      double acc = s_chunk[t * 8];
+#pragma unroll
+      for (int c = 1; c < 8; ++c) acc += s_chunk[t * 8 + c];
+      part[tile * kCtWords + t] = (unsigned long long)__double_as_longlong(acc);
+    }
+    if (t < kCtWords - kCtSums) part[tile * kCtWords + kCtSums + t] = s_cnt[t];  // (the lanes that zero them for the next tile)
+  }
 }
 
 // the occupied slots that `sel` selects and their points, reduced per workgroup: a crop's kept voxels, a carve's seen-through ones.  The
@@ -1472,6 +1624,7 @@ extern "C" int wc_map_destroy(wc_ctx *ctx, wc_map *m) {
   wc_buf_release(ctx, m->b_carve);
   wc_buf_release(ctx, m->b_cast);
   wc_buf_release(ctx, m->b_score);
+  wc_buf_release(ctx, m->b_ct);
   (void)hipStreamSynchronize(ctx->stream);  // (the pinned counters may still be the target of an enqueued copy)
   if (m->ev_ctr) (void)hipEventDestroy(m->ev_ctr);
   if (m->h_ctr) (void)hipHostFree(m->h_ctr);
@@ -1480,6 +1633,7 @@ extern "C" int wc_map_destroy(wc_ctx *ctx, wc_map *m) {
   if (m->h_carve) (void)hipHostFree(m->h_carve);
   if (m->h_cast) (void)hipHostFree(m->h_cast);
   if (m->h_score) (void)hipHostFree(m->h_score);
+  if (m->h_ct) (void)hipHostFree(m->h_ct);
   delete m;
   return WC_OK;
 }
@@ -1862,7 +2016,7 @@ int lin_core(wc_ctx *ctx, wc_map *m, const wc_points *pts, const double *T, uint
     const uint64_t nxt = (cnt + kLinFan - 1) / kLinFan, off_out = off + cnt * kLinWords;
     unsigned long long *out = nxt > 1 ? base + off_out : fin;
     const uint64_t out_stride = nxt > 1 ? hyp_words : (uint64_t)kLinWords, lanes = (uint64_t)K * nxt * kLinWords;
-    k_map_lin_reduce<<<(unsigned)((lanes + 255) / 256), 256, 0, ctx->stream>>>(base + off, hyp_words, cnt, out, out_stride, K);
+    k_map_lin_reduce<kLinWords, kLinSums><<<(unsigned)((lanes + 255) / 256), 256, 0, ctx->stream>>>(base + off, hyp_words, cnt, out, out_stride, K);
     WC_HIP(ctx, hipGetLastError());
     off = off_out, cnt = nxt;
   } while (cnt > 1);
@@ -1914,9 +2068,9 @@ extern "C" int wc_map_linearize_batch(wc_ctx *ctx, wc_map *m, const wc_points *p
 }
 
 namespace {
-// R <- Rod(omega) R, t <- Rod(omega) t + upsilon, Rod(w) = I + A K + B K^2, K = [w]x, A = sin(th) / th, B = (sin(th/2) / (th/2))^2 / 2
-void pose_update(double T[12], const double xi[6]) {
-  const double wx = xi[0], wy = xi[1], wz = xi[2];
+// Rod(w) = I + A K + B K^2, K = [w]x, A = sin(th) / th, B = (sin(th/2) / (th/2))^2 / 2: the rigid and the continuous-time update's one copy
+void rod_matrix(const double w[3], double E[3][3]) {
+  const double wx = w[0], wy = w[1], wz = w[2];
   const double th = std::sqrt((wx * wx + wy * wy) + wz * wz);
   double A = 1.0, B = 0.5;
   if (th > 0.0) {
@@ -1924,27 +2078,30 @@ void pose_update(double T[12], const double xi[6]) {
     A = std::sin(th) / th, B = 0.5 * (h * h);
   }
   const double K[3][3] = {{0.0, -wz, wy}, {wz, 0.0, -wx}, {-wy, wx, 0.0}};
-  double E[3][3];
   for (int r = 0; r < 3; ++r)
     for (int c = 0; c < 3; ++c) {
       const double k2 = (K[r][0] * K[0][c] + K[r][1] * K[1][c]) + K[r][2] * K[2][c];
       E[r][c] = ((r == c ? 1.0 : 0.0) + A * K[r][c]) + B * k2;
     }
+}
+// R <- Rod(omega) R, t <- Rod(omega) t + upsilon
+void pose_update(double T[12], const double xi[6]) {
+  double E[3][3];
+  rod_matrix(xi, E);
   double N[12];
   for (int r = 0; r < 3; ++r)
     for (int c = 0; c < 4; ++c) N[4 * r + c] = ((E[r][0] * T[c] + E[r][1] * T[4 + c]) + E[r][2] * T[8 + c]) + (c == 3 ? xi[3 + r] : 0.0);
   std::memcpy(T, N, sizeof(N));
 }
-// H xi = -g by a Cholesky factorisation of H scaled to unit diagonal; false: a pivot (the number under the square root) is not finite
-// or below min_pivot
-bool gn_step(const wc_map_normal_eq &ne, double min_pivot, double xi[6]) {
-  double A[6][6], D[6], L[6][6] = {}, y[6];
-  for (int a = 0, e = 0; a < 6; ++a)
-    for (int b = a; b < 6; ++b, ++e) A[a][b] = A[b][a] = ne.H[e];
-  for (int a = 0; a < 6; ++a) D[a] = 1.0 / std::sqrt(A[a][a]);
-  for (int i = 0; i < 6; ++i)
+// A xi = -g for the symmetric n x n matrix A (row-major, n <= 12: 6 the rigid registration's, 12 the continuous-time one's) by a Cholesky
+// factorisation of A scaled to unit diagonal; false: a pivot (the number under the square root) is not finite or below min_pivot
+constexpr int kGnMax = 12;
+bool gn_solve(int n, const double *A, const double *g, double min_pivot, double *xi) {
+  double D[kGnMax], L[kGnMax][kGnMax] = {}, y[kGnMax];
+  for (int a = 0; a < n; ++a) D[a] = 1.0 / std::sqrt(A[a * n + a]);
+  for (int i = 0; i < n; ++i)
     for (int j = 0; j <= i; ++j) {
-      double s = (D[i] * A[i][j]) * D[j];
+      double s = (D[i] * A[i * n + j]) * D[j];
       if (i == j) s = 1.0;
       for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
       if (i == j) {
@@ -1954,21 +2111,31 @@ bool gn_step(const wc_map_normal_eq &ne, double min_pivot, double xi[6]) {
         L[i][j] = s / L[j][j];
       }
     }
-  for (int i = 0; i < 6; ++i) {
-    double s = -(D[i] * ne.g[i]);
+  for (int i = 0; i < n; ++i) {
+    double s = -(D[i] * g[i]);
     for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
     y[i] = s / L[i][i];
   }
-  for (int i = 5; i >= 0; --i) {
+  for (int i = n - 1; i >= 0; --i) {
     double s = y[i];
-    for (int k = i + 1; k < 6; ++k) s -= L[k][i] * xi[k];
+    for (int k = i + 1; k < n; ++k) s -= L[k][i] * xi[k];
     xi[i] = s / L[i][i];
   }
-  for (int i = 0; i < 6; ++i) {
+  for (int i = 0; i < n; ++i) {
     xi[i] *= D[i];
     if (!std::isfinite(xi[i])) return false;
   }
   return true;
+}
+// the 21 entries of an upper triangle, row-major, into the 6 x 6 block of the n x n matrix A at (r0, c0) - and mirrored, into (c0, r0)
+void put_block(const double H[21], int n, double *A, int r0, int c0) {
+  for (int a = 0, e = 0; a < 6; ++a)
+    for (int b = a; b < 6; ++b, ++e) A[(r0 + a) * n + (c0 + b)] = A[(r0 + b) * n + (c0 + a)] = A[(c0 + b) * n + (r0 + a)] = A[(c0 + a) * n + (r0 + b)] = H[e];
+}
+bool gn_step(const wc_map_normal_eq &ne, double min_pivot, double xi[6]) {
+  double A[36];
+  put_block(ne.H, 6, A, 0, 0);
+  return gn_solve(6, A, ne.g, min_pivot, xi);
 }
 bool align_opts_ok(const wc_map_align_opts *o) {
   return o && o->max_iterations >= 1 && o->tol_rot > 0.0 && o->tol_trans > 0.0 && o->min_used >= 6 && o->min_pivot > 0.0;
@@ -2122,6 +2289,207 @@ extern "C" int wc_map_align_pyramid_batch(wc_ctx *ctx, wc_map *const *levels, ui
   for (uint32_t l = 0; l < n_levels; ++l) WC_TRY(lin_batch_check(ctx, levels[l], pts, T_io, K, &opts[l].reg, __func__));
   for (uint32_t l = 0; l < n_levels && K; ++l)
     WC_TRY(align_batch_core(ctx, levels[l], pts, T_io, K, &opts[l], h_out + (size_t)l * K, h_status, l > 0));
+  return WC_OK;
+}
+
+// ---- registration of a stamped sweep in continuous time (include/wildcat_hip.h: wc_map_linearize_ct, wc_map_align_ct) -----------------
+namespace {
+// the two poses and the stamp bounds as the kernel and wc_pose_interp_move take them: span formed once, the end quaternion on the begin
+// one's side.  false: a non-finite entry, a quaternion whose squared norm is 0 or not finite, t_end <= t_begin, a non-finite bound or span
+bool ct_pose_of(const wc_pose *b, const wc_pose *e, double t_begin, double t_end, map_ct_pose *C) {
+  if (!b || !e || !std::isfinite(t_begin) || !std::isfinite(t_end) || !(t_end > t_begin)) return false;
+  for (int j = 0; j < 3; ++j) C->p0[j] = b->pos[j], C->p1[j] = e->pos[j];
+  for (int j = 0; j < 4; ++j) C->q0[j] = b->quat[j], C->q1[j] = e->quat[j];
+  for (int j = 0; j < 3; ++j)
+    if (!std::isfinite(C->p0[j]) || !std::isfinite(C->p1[j])) return false;
+  for (const double *q : {C->q0, C->q1}) {
+    const double nn = ((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3];
+    if (!std::isfinite(nn) || !(nn > 0.0)) return false;  // (a non-finite entry makes nn non-finite)
+  }
+  const double dot = ((C->q0[0] * C->q1[0] + C->q0[1] * C->q1[1]) + C->q0[2] * C->q1[2]) + C->q0[3] * C->q1[3];
+  if (dot < 0.0)
+    for (int j = 0; j < 4; ++j) C->q1[j] = -C->q1[j];
+  C->t_begin = t_begin, C->t_end = t_end, C->span = t_end - t_begin;
+  return std::isfinite(C->span) && C->span > 0.0;
+}
+constexpr uint32_t kCtNaN = 0x7fc00000u;  // the quiet NaN of a point out of span in d_xyz_out
+// the sizes of the reduction's levels, as lin_words, in partials of kCtWords words
+uint64_t ct_words(uint64_t tiles) { return lin_words(tiles) / kLinWords * kCtWords; }
+// a final partial (76 doubles, then n_used, n_found, n_outside, n_bad) as the record
+void ct_normal_eq_of(const unsigned long long *part, wc_map_ct_normal_eq *out) {
+  double sums[kCtSums];
+  std::memcpy(sums, part, sizeof(sums));
+  for (int e = 0; e < 21; ++e) out->H00[e] = sums[e], out->H01[e] = sums[21 + e], out->H11[e] = sums[42 + e];
+  for (int e = 0; e < 6; ++e) out->g0[e] = sums[63 + e], out->g1[e] = sums[69 + e];
+  out->cost = 0.5 * sums[75];
+  out->n_used = part[kCtSums], out->n_found = part[kCtSums + 1], out->n_outside = part[kCtSums + 2], out->reserved = 0;
+}
+bool ct_args_ok(const wc_ctx *ctx, const wc_map *m, const wc_points *pts, const wc_map_reg_params *params) {
+  return reg_args_ok(ctx, m, pts, params) &&
+         (pts->n == 0 || (pts->time && pts->time_stride >= 8 && pts->time_stride % 8 == 0 && (uintptr_t)pts->time % 8 == 0));
+}
+constexpr const char *kCtArgsMsg =
+    "%s: null or out-of-range argument (stamps: 8-aligned doubles; poses: finite, non-zero quaternions; t_begin < t_end, finite), a map of "
+    "another context or one created without WC_MAP_MOMENTS";
+// The linearisation behind the entry points' checks: one launch of k_map_linearize_ct, one of k_map_lin_reduce<80, 76> per level, one copy
+// of 640 bytes, one wait.  *h_out: the record, or zero and WC_ERR_ARG where the poses send a finite point to a non-finite one
+int ct_lin_core(wc_ctx *ctx, wc_map *m, const wc_points *pts, const map_ct_pose &C, const wc_map_reg_params *params, wc_map_ct_normal_eq *h_out,
+                wc_map_ct_row *d_rows, float *d_xyz_out, const char *fn) {
+  std::memset(h_out, 0, sizeof(*h_out));
+  if (pts->n == 0) return WC_OK;
+  const uint64_t tiles = (pts->n + kLinThreads - 1) / kLinThreads, words = ct_words(tiles);
+  WC_TRY(wc_ensure(ctx, m->b_ct, (words + kCtWords) * 8));
+  if (!m->h_ct) WC_HIP(ctx, hipHostMalloc((void **)&m->h_ct, (size_t)kCtWords * 8));
+  unsigned long long *base = (unsigned long long *)m->b_ct.p, *fin = base + words;
+  uint64_t grid = std::min<uint64_t>(tiles, (uint64_t)8 * m->cus);
+  if (ctx->dev.map_lin_groups > 0) grid = std::min<uint64_t>(tiles, (uint64_t)ctx->dev.map_lin_groups);  // (development option)
+  k_map_linearize_ct<<<(unsigned)grid, kLinThreads, 0, ctx->stream>>>(*pts, C, reg_of(params), m->voxel, m->keys, m->pay, m->mom, m->cap - 1,
+                                                                      d_rows, d_xyz_out, base);
+  WC_HIP(ctx, hipGetLastError());
+  uint64_t cnt = tiles, off = 0;  // the level's partials and where they start
+  do {
+    const uint64_t nxt = (cnt + kLinFan - 1) / kLinFan, off_out = off + cnt * kCtWords;
+    unsigned long long *out = nxt > 1 ? base + off_out : fin;
+    const uint64_t lanes = nxt * kCtWords;
+    k_map_lin_reduce<kCtWords, kCtSums><<<(unsigned)((lanes + 255) / 256), 256, 0, ctx->stream>>>(base + off, 0, cnt, out, 0, 1u);
+    WC_HIP(ctx, hipGetLastError());
+    off = off_out, cnt = nxt;
+  } while (cnt > 1);
+  WC_HIP(ctx, hipMemcpyAsync(m->h_ct, fin, (size_t)kCtWords * 8, hipMemcpyDeviceToHost, ctx->stream));
+  WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (m->h_ct[kCtSums + 3])
+    return wc_fail(ctx, WC_ERR_ARG, "%s: the poses send %llu finite points to a non-finite one", fn, m->h_ct[kCtSums + 3]);
+  ct_normal_eq_of(m->h_ct, h_out);
+  return WC_OK;
+}
+bool ct_prior_ok(const double prior[4]) {
+  for (int j = 0; j < 4; ++j)
+    if (!(prior[j] >= 0.0) || !std::isfinite(prior[j])) return false;
+  return true;
+}
+// the 12 x 12 step: A = (H00 H01; H01 H11) + diag(w), b = (g0, g1) + w acc
+bool ct_step(const wc_map_ct_normal_eq &ne, const double prior[4], const double acc[12], double min_pivot, double xi[12]) {
+  double A[144], b[12];
+  put_block(ne.H00, 12, A, 0, 0);
+  put_block(ne.H11, 12, A, 6, 6);
+  put_block(ne.H01, 12, A, 0, 6);
+  for (int i = 0; i < 12; ++i) {
+    const double w = prior[i / 3];
+    A[i * 12 + i] += w;
+    b[i] = (i < 6 ? ne.g0[i] : ne.g1[i - 6]) + w * acc[i];
+  }
+  return gn_solve(12, A, b, min_pivot, xi);
+}
+// quat <- quat(Rod(omega)) * quat divided by its norm, pos <- Rod(omega) pos + upsilon
+void ct_pose_update(wc_pose *P, const double xi[6]) {
+  const double wx = xi[0], wy = xi[1], wz = xi[2];
+  const double th = std::sqrt((wx * wx + wy * wy) + wz * wz);
+  const double h = th > 0.0 ? std::sin(0.5 * th) / th : 0.5;
+  const double dw = std::cos(0.5 * th), dx = h * wx, dy = h * wy, dz = h * wz;
+  const double *q = P->quat;
+  double r[4];
+  r[0] = ((dw * q[0] - dx * q[1]) - dy * q[2]) - dz * q[3];
+  r[1] = ((dw * q[1] + dx * q[0]) + dy * q[3]) - dz * q[2];
+  r[2] = ((dw * q[2] - dx * q[3]) + dy * q[0]) + dz * q[1];
+  r[3] = ((dw * q[3] + dx * q[2]) - dy * q[1]) + dz * q[0];
+  const double nrm = std::sqrt(((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]) + r[3] * r[3]);
+  for (int j = 0; j < 4; ++j) P->quat[j] = r[j] / nrm;
+  double E[3][3];
+  rod_matrix(xi, E);
+  double t[3];
+  for (int a = 0; a < 3; ++a) t[a] = ((E[a][0] * P->pos[0] + E[a][1] * P->pos[1]) + E[a][2] * P->pos[2]) + xi[3 + a];
+  std::memcpy(P->pos, t, sizeof(t));
+}
+bool ct_align_opts_ok(const wc_map_ct_align_opts *o) {
+  return o && o->max_iterations >= 1 && o->tol_rot > 0.0 && o->tol_trans > 0.0 && o->min_used >= 12 && o->min_pivot > 0.0 && ct_prior_ok(o->prior);
+}
+double norm3(const double *x) { return std::sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]); }
+}  // namespace
+
+extern "C" int wc_map_linearize_ct(wc_ctx *ctx, wc_map *m, const wc_points *pts, const wc_pose *pose_begin, const wc_pose *pose_end,
+                                   double t_begin, double t_end, const wc_map_reg_params *params, wc_map_ct_normal_eq *h_out,
+                                   wc_map_ct_row *d_rows, float *d_xyz_out) {
+  wc_dev_guard dg_(ctx);
+  map_ct_pose C;
+  if (!ct_args_ok(ctx, m, pts, params) || !h_out || (uintptr_t)d_rows % 8 || (uintptr_t)d_xyz_out % 4 ||
+      !ct_pose_of(pose_begin, pose_end, t_begin, t_end, &C))
+    return wc_fail(ctx, WC_ERR_ARG, kCtArgsMsg, __func__);
+  return ct_lin_core(ctx, m, pts, C, params, h_out, d_rows, d_xyz_out, __func__);
+}
+
+extern "C" int wc_map_align_ct(wc_ctx *ctx, wc_map *m, const wc_points *pts, wc_pose *pose_begin_io, wc_pose *pose_end_io, double t_begin,
+                               double t_end, const wc_map_ct_align_opts *o, wc_map_ct_align_summary *s) {
+  wc_dev_guard dg_(ctx);
+  if (!ctx || !s || !ct_align_opts_ok(o))
+    return wc_fail(ctx, WC_ERR_ARG,
+                   "%s: null or out-of-range argument (max_iterations >= 1, tol_rot, tol_trans, min_pivot > 0, min_used >= 12, prior >= 0)", __func__);
+  map_ct_pose C;
+  if (!ct_args_ok(ctx, m, pts, &o->reg) || !ct_pose_of(pose_begin_io, pose_end_io, t_begin, t_end, &C))
+    return wc_fail(ctx, WC_ERR_ARG, kCtArgsMsg, __func__);
+  std::memset(s, 0, sizeof(*s));
+  s->termination = 1;
+  double acc[12] = {};
+  wc_map_ct_normal_eq ne;
+  bool fresh = false;  // ne is the linearisation at the poses as they stand
+  for (uint32_t it = 0; it < o->max_iterations; ++it) {
+    if (!ct_pose_of(pose_begin_io, pose_end_io, t_begin, t_end, &C)) return wc_fail(ctx, WC_ERR_NUMERIC, "%s: an update left an unusable pose", __func__);
+    WC_TRY(ct_lin_core(ctx, m, pts, C, &o->reg, &ne, nullptr, nullptr, __func__));
+    fresh = true;
+    if (it == 0) s->initial_cost = ne.cost;
+    double xi[12];
+    if (ne.n_used < o->min_used || !ct_step(ne, o->prior, acc, o->min_pivot, xi)) {
+      s->termination = 2;
+      break;
+    }
+    wc_pose b = *pose_begin_io, e = *pose_end_io;
+    ct_pose_update(&b, xi), ct_pose_update(&e, xi + 6);
+    map_ct_pose C2;
+    if (!ct_pose_of(&b, &e, t_begin, t_end, &C2)) {  // (a non-finite update)
+      s->termination = 2;
+      break;
+    }
+    *pose_begin_io = b, *pose_end_io = e;
+    fresh = false;
+    for (int j = 0; j < 12; ++j) acc[j] += xi[j];
+    std::memcpy(s->last_step, xi, sizeof(xi));
+    s->iterations = (int32_t)(it + 1);
+    if (norm3(xi) <= o->tol_rot && norm3(xi + 3) <= o->tol_trans && norm3(xi + 6) <= o->tol_rot && norm3(xi + 9) <= o->tol_trans) {
+      s->termination = 0;
+      break;
+    }
+  }
+  if (!fresh) {
+    if (!ct_pose_of(pose_begin_io, pose_end_io, t_begin, t_end, &C)) return wc_fail(ctx, WC_ERR_NUMERIC, "%s: an update left an unusable pose", __func__);
+    WC_TRY(ct_lin_core(ctx, m, pts, C, &o->reg, &ne, nullptr, nullptr, __func__));
+  }
+  s->final_cost = ne.cost;
+  s->n_used = ne.n_used, s->n_found = ne.n_found, s->n_outside = ne.n_outside;
+  double pc = 0.0;
+  for (int j = 0; j < 12; ++j) pc += (o->prior[j / 3] * acc[j]) * acc[j];
+  s->prior_cost = 0.5 * pc;
+  return WC_OK;
+}
+
+extern "C" int wc_pose_interp_move(const wc_pose *pose_begin, const wc_pose *pose_end, double t_begin, double t_end, const float *xyz,
+                                   const double *times, uint64_t n, float *xyz_out) {
+  map_ct_pose C;
+  if ((n && (!xyz || !times || !xyz_out)) || !ct_pose_of(pose_begin, pose_end, t_begin, t_end, &C)) return WC_ERR_ARG;
+  for (uint64_t i = 0; i < n; ++i) {
+    double s;
+    if (map_ct_share(C, times[i], s)) {
+      map_move_ct(C, s, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], xyz_out[3 * i], xyz_out[3 * i + 1], xyz_out[3 * i + 2]);
+    } else {
+      for (int a = 0; a < 3; ++a) std::memcpy(&xyz_out[3 * i + a], &kCtNaN, 4);
+    }
+  }
+  return WC_OK;
+}
+
+extern "C" int wc_map_ct_step(const wc_map_ct_normal_eq *ne, const double prior[4], const double acc[12], double min_pivot, double xi12[12]) {
+  if (!ne || !prior || !acc || !xi12 || !(min_pivot > 0.0) || !ct_prior_ok(prior)) return WC_ERR_ARG;
+  double xi[12];
+  if (!ct_step(*ne, prior, acc, min_pivot, xi)) return WC_ERR_NUMERIC;
+  std::memcpy(xi12, xi, sizeof(xi));
   return WC_OK;
 }
 

@@ -524,6 +524,33 @@ bool LidarOdometry::AlignToMap(const float *xyz, size_t n, double T_io[12], cons
   if (summary) *summary = s;
   return true;
 }
+bool LidarOdometry::AlignSweepToMap(const void *points48, size_t n, wc_pose *pose_begin_io, wc_pose *pose_end_io, const wc_map_ct_align_opts &opts,
+                                    wc_map_ct_align_summary *summary, bool insert) {
+  if (!map_ || !map_moments_ || !pose_begin_io || !pose_end_io || !n || !points48) return false;
+  double t_begin = std::numeric_limits<double>::infinity(), t_end = -t_begin;
+  for (size_t i = 0; i < n; ++i) {
+    double t;
+    std::memcpy(&t, (const char *)points48 + i * WC_HILTI_POINT_BYTES + WC_HILTI_POINT_TIME_OFFSET, sizeof(t));
+    if (std::isfinite(t)) t_begin = std::min(t_begin, t), t_end = std::max(t_end, t);
+  }
+  if (!(t_begin < t_end)) return false;
+  const DevBuf d_pts(ctx_, n * WC_HILTI_POINT_BYTES), d_out(ctx_, insert ? n * 3 * sizeof(float) : 0);
+  CheckCall(ctx_, "wc_h2d", wc_h2d(ctx_, d_pts.p, points48, n * WC_HILTI_POINT_BYTES));
+  const wc_points desc{d_pts.p, (const char *)d_pts.p + WC_HILTI_POINT_TIME_OFFSET, WC_HILTI_POINT_BYTES, WC_HILTI_POINT_BYTES, n};
+  wc_pose b = *pose_begin_io, e = *pose_end_io;
+  wc_map_ct_align_summary s;
+  // (an argument the library refuses is the caller's: no abort, as in AlignToMap)
+  if (wc_map_align_ct(ctx_, map_, &desc, &b, &e, t_begin, t_end, &opts, &s) != WC_OK) return false;
+  if (insert) {  // the registered sweep at the final poses, straight from the linearisation's own moved points
+    wc_map_ct_normal_eq ne;
+    if (wc_map_linearize_ct(ctx_, map_, &desc, &b, &e, t_begin, t_end, &opts.reg, &ne, nullptr, (float *)d_out.p) != WC_OK) return false;
+    const wc_points moved{d_out.p, nullptr, 12, 0, n};
+    WC_CALL(wc_map_insert(ctx_, map_, &moved, nullptr));
+  }
+  *pose_begin_io = b, *pose_end_io = e;
+  if (summary) *summary = s;
+  return true;
+}
 namespace {
 constexpr uint32_t kMaxLevels = 8;  // wc_map_align_pyramid's
 // the levels of a relocalisation: levels[0] = the coarsest ... levels[n_levels - 1] = the map itself, built finest first, each from the one

@@ -104,6 +104,13 @@ class LidarOdometry {
   // pose out, *summary (may be null) as wc_map_align leaves it.  false - nothing touched - without a map, with map_surfels off, or when
   // the library refuses the arguments.  Nothing in AddLidarScan calls it
   bool AlignToMap(const float *xyz, size_t n, double T_io[12], const wc_map_align_opts &opts, wc_map_align_summary *summary);
+  // registration of a RAW sweep in continuous time (wc_map_align_ct): n 48-byte point records on the host, in the body frame, with stamps;
+  // pose_begin_io is the body -> map pose at the sweep's smallest finite stamp, pose_end_io at its largest (the two stamp bounds of the
+  // call); the aligned poses out, *summary (may be null) as wc_map_align_ct leaves it.  insert: the registered sweep - the moved points
+  // wc_map_linearize_ct writes at the final poses - is inserted into the map.  false - nothing touched - where AlignToMap returns false,
+  // for n = 0, and for a sweep whose finite stamps do not span an interval.  Nothing in AddLidarScan calls it
+  bool AlignSweepToMap(const void *points48, size_t n, wc_pose *pose_begin_io, wc_pose *pose_end_io, const wc_map_ct_align_opts &opts,
+                       wc_map_ct_align_summary *summary, bool insert);
   // AlignToMap from a rough pose, coarse to fine: levels 1 .. n_levels - 1 are built from the map by chained wc_map_coarsen(factor) - level
   // l has voxel size (double)factor * that of level l - 1 -, the pyramid (wc_map_align_pyramid_batch with this one start: byte for byte
   // wc_map_align_pyramid, whose error is the start's status) runs them coarsest first and the map itself last, each with

@@ -225,6 +225,11 @@ uint64_t wc_odom_map_query_planes(void *h, const float *xyz, uint64_t n, double 
 int wc_odom_map_align(void *h, const float *xyz, uint64_t n, double T_io[12], const wc_map_align_opts *opts, wc_map_align_summary *summary) {
   return opts && ((LidarOdometry *)h)->AlignToMap(xyz, n, T_io, *opts, summary) ? 1 : 0;
 }
+// LidarOdometry::AlignSweepToMap for n host records of 48 bytes; 1 = done, 0 = as wc_odom_map_align, an empty sweep or one without a stamp interval
+int wc_odom_map_align_sweep(void *h, const void *points48, uint64_t n, wc_pose *pose_begin_io, wc_pose *pose_end_io,
+                            const wc_map_ct_align_opts *opts, wc_map_ct_align_summary *summary, int insert) {
+  return opts && ((LidarOdometry *)h)->AlignSweepToMap(points48, n, pose_begin_io, pose_end_io, *opts, summary, insert != 0) ? 1 : 0;
+}
 // LidarOdometry::RelocalizeToMap; summaries: n_levels records, coarsest first (may be null); 1 = done, 0 = as wc_odom_map_align, or levels refused
 int wc_odom_map_relocalize(void *h, const float *xyz, uint64_t n, double T_io[12], uint32_t factor, uint32_t n_levels,
                            const wc_map_align_opts *finest, wc_map_align_summary *summaries) {

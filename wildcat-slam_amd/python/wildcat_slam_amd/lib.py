@@ -758,6 +758,59 @@ def pose_grid(T, n_yaw, n_xyz, step):
     return out.reshape(K, 3, 4)
 
 
+def map_ct_align_opts(params, max_iterations=20, tol_rot=1e-6, tol_trans=1e-6, min_used=12, min_pivot=1e-9, prior=(0.0, 0.0, 0.0, 0.0)):
+    """wc_map_ct_align_opts around a wc_map_reg_params; prior: the four information weights (begin rotation, begin translation, end
+    rotation, end translation)"""
+    return R.MapCtAlignOpts(params, int(max_iterations), int(min_used), float(tol_rot), float(tol_trans), float(min_pivot),
+                            (C.c_double * 4)(*[float(w) for w in prior]))
+
+
+def _pose_rec(pose):
+    """(pos (3,), quat (4,) = (w, x, y, z)) or seven numbers -> wc_pose"""
+    p = np.concatenate([np.asarray(x, np.float64).reshape(-1) for x in pose]) if len(pose) == 2 else np.asarray(pose, np.float64).reshape(-1)
+    assert p.size == 7, "a pose: pos (3) and quat (4) = (w, x, y, z)"
+    return R.Pose((C.c_double * 3)(*p[:3]), (C.c_double * 4)(*p[3:]))
+
+
+def _pose_pair(rec):
+    return np.array(list(rec.pos)), np.array(list(rec.quat))
+
+
+def _ct_summary_dict(s):
+    return dict(initial_cost=s.initial_cost, final_cost=s.final_cost, iterations=s.iterations, termination=s.termination, n_used=int(s.n_used),
+                n_found=int(s.n_found), n_outside=int(s.n_outside), last_step=np.array(list(s.last_step)), prior_cost=s.prior_cost)
+
+
+def pose_interp_move(pose_begin, pose_end, t_begin, t_end, xyz, times):
+    """wc_pose_interp_move (needs no GPU): the device's interpolation and move of wc_map_linearize_ct on the host -> (n, 3) float32, NaN
+    rows for the stamps outside [t_begin, t_end]"""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    times = np.ascontiguousarray(times, np.float64).reshape(-1)
+    assert len(times) == len(xyz)
+    out = np.zeros((len(xyz), 3), np.float32)
+    b, e = _pose_rec(pose_begin), _pose_rec(pose_end)
+    rc = load().wc_pose_interp_move(C.byref(b), C.byref(e), C.c_double(t_begin), C.c_double(t_end), R.ptr(xyz), R.ptr(times), C.c_uint64(len(xyz)),
+                                    R.ptr(out))
+    if rc != WC_OK:
+        raise WildcatError(rc, "wc_pose_interp_move refused its arguments")
+    return out
+
+
+def map_ct_step(ne, prior=(0.0, 0.0, 0.0, 0.0), acc=None, min_pivot=1e-9):
+    """wc_map_ct_step (needs no GPU): the 12 x 12 Gauss-Newton step of a MAP_CT_NORMAL_EQ record with the prior weights and the running
+    sum of steps acc -> xi (12,), or None when a pivot falls below min_pivot"""
+    ne = np.ascontiguousarray(ne, R.MAP_CT_NORMAL_EQ).reshape(1)
+    prior = np.ascontiguousarray(prior, np.float64).reshape(4)
+    acc = np.zeros(12) if acc is None else np.ascontiguousarray(acc, np.float64).reshape(12)
+    xi = np.zeros(12)
+    rc = load().wc_map_ct_step(R.ptr(ne), R.ptr(prior), R.ptr(acc), C.c_double(min_pivot), R.ptr(xi))
+    if rc == 13:  # WC_ERR_NUMERIC
+        return None
+    if rc != WC_OK:
+        raise WildcatError(rc, "wc_map_ct_step refused its arguments")
+    return xi
+
+
 def map_score_top(scores, M, min_hit=0):
     """wc_map_score_top (needs no GPU): the indices of the M best MAP_SCORE records - n_bad == 0 and n_hit >= min_hit; larger n_hit
     first, then the smaller index -> int32 array of the min(M, eligible) indices"""
@@ -1090,6 +1143,75 @@ class PointMap:
         with self._uploaded(points) as (desc, _):
             return self.align_device(desc, T, opts)
 
+    @contextlib.contextmanager
+    def _uploaded_stamped(self, points, times=None):
+        """POINT records (their own stamps), or an (n, 3) float32 array with `times` (n,) float64, in HBM for the length of a with block
+        -> the wc_points descriptor with its time pointer set; freed on the way out"""
+        points = np.ascontiguousarray(points)
+        if points.dtype == R.POINT:
+            assert times is None, "POINT records carry their stamps"
+            bufs = [self.ctx.to_device(points)] if len(points) else []
+            desc = R.Points(bufs[0].ptr, bufs[0].ptr + 24, 48, 48, len(points)) if bufs else R.Points(0, 0, 48, 48, 0)
+        else:
+            points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+            times = np.ascontiguousarray(times, np.float64).reshape(-1)
+            assert len(times) == len(points), "one stamp per point"
+            bufs = [self.ctx.to_device(points), self.ctx.to_device(times)] if len(points) else []
+            desc = R.Points(bufs[0].ptr, bufs[1].ptr, 12, 8, len(points)) if bufs else R.Points(0, 0, 12, 8, 0)
+        try:
+            yield desc
+        finally:
+            for b in bufs:
+                b.free()
+
+    def linearize_ct_device(self, desc, pose_begin, pose_end, t_begin, t_end, params, d_rows=None, d_xyz_out=None):
+        """stamped points already in HBM, the poses (pos, quat) at t_begin and t_end -> MAP_CT_NORMAL_EQ record (wc_map_linearize_ct);
+        d_rows: a DeviceBuffer for one MAP_CT_ROW per point, d_xyz_out: one for n x 3 floats (the moved points), or None"""
+        out = np.zeros(1, R.MAP_CT_NORMAL_EQ)
+        b, e = _pose_rec(pose_begin), _pose_rec(pose_end)
+        self.ctx._ck(self.lib.wc_map_linearize_ct(self.ctx.h, self.h, C.byref(desc), C.byref(b), C.byref(e), C.c_double(t_begin), C.c_double(t_end),
+                                                  C.byref(params), R.ptr(out), C.c_void_p(d_rows.ptr if d_rows else 0),
+                                                  C.c_void_p(d_xyz_out.ptr if d_xyz_out else 0)))
+        return out[0]
+
+    def linearize_ct(self, points, pose_begin, pose_end, t_begin, t_end, params=None, times=None, want_rows=False, want_xyz=False, **kw):
+        """a raw sweep - POINT records, or an (n, 3) float32 array with times - registered in continuous time between two poses ->
+        MAP_CT_NORMAL_EQ record, followed by the MAP_CT_ROW array with want_rows and the moved points (n, 3) float32 with want_xyz;
+        params: a wc_map_reg_params, or its fields as keywords (max_dist defaults to the voxel size)"""
+        if params is None:
+            kw.setdefault("max_dist", self.voxel)
+            params = map_reg_params(**kw)
+        with self._uploaded_stamped(points, times) as desc:
+            n = int(desc.n)
+            d_rows = self.ctx.alloc(72 * max(n, 1)) if want_rows else None
+            d_xyz = self.ctx.alloc(12 * max(n, 1)) if want_xyz else None
+            try:
+                out = [self.linearize_ct_device(desc, pose_begin, pose_end, t_begin, t_end, params, d_rows, d_xyz)]
+                if want_rows:
+                    out.append(d_rows.download(R.MAP_CT_ROW, n))
+                if want_xyz:
+                    out.append(d_xyz.download(np.float32, 3 * n).reshape(n, 3))
+            finally:
+                for b in (d_rows, d_xyz):
+                    if b:
+                        b.free()
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def align_ct_device(self, desc, pose_begin, pose_end, t_begin, t_end, opts):
+        """wc_map_align_ct on stamped points already in HBM -> ((pos, quat) of begin, (pos, quat) of end, summary dict)"""
+        b, e, summ = _pose_rec(pose_begin), _pose_rec(pose_end), R.MapCtAlignSummary()
+        self.ctx._ck(self.lib.wc_map_align_ct(self.ctx.h, self.h, C.byref(desc), C.byref(b), C.byref(e), C.c_double(t_begin), C.c_double(t_end),
+                                              C.byref(opts), C.byref(summ)))
+        return _pose_pair(b), _pose_pair(e), _ct_summary_dict(summ)
+
+    def align_ct(self, points, pose_begin, pose_end, t_begin, t_end, opts=None, params=None, times=None, **kw):
+        """Gauss-Newton registration of a raw sweep in continuous time, from the poses at t_begin and t_end -> as align_ct_device; opts: a
+        wc_map_ct_align_opts, or params (a wc_map_reg_params, default max_dist = the voxel size) and map_ct_align_opts' keywords"""
+        if opts is None:
+            opts = map_ct_align_opts(params if params is not None else map_reg_params(self.voxel), **kw)
+        with self._uploaded_stamped(points, times) as desc:
+            return self.align_ct_device(desc, pose_begin, pose_end, t_begin, t_end, opts)
+
     def linearize_batch_device(self, desc, Ts, params):
         """wc_map_linearize_batch on points already in HBM: K poses Ts -> (MAP_NORMAL_EQ array (K,), status (K,) int32); record h is
         byte-equal to linearize_device's for pose h where status[h] is 0, and zero where it is not"""
@@ -1294,6 +1416,18 @@ class Odometry:
         if not self.lib.wc_odom_map_align(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), R.ptr(T), C.byref(opts), C.byref(summ)):
             return None
         return T.reshape(3, 4), _summary_dict(summ)
+
+    def map_align_sweep(self, points, pose_begin, pose_end, opts, insert=False):
+        """wc_map_align_ct of a raw sweep of POINT records (body frame, with stamps) against the map, from the poses (pos, quat) at the
+        sweep's smallest and largest stamp (LidarOdometry::AlignSweepToMap); insert: the registered sweep is inserted into the map ->
+        ((pos, quat) of begin, (pos, quat) of end, summary dict), or None where map_align returns None or the sweep spans no interval"""
+        points = np.ascontiguousarray(points)
+        assert points.dtype == R.POINT, "POINT records"
+        b, e, summ = _pose_rec(pose_begin), _pose_rec(pose_end), R.MapCtAlignSummary()
+        if not self.lib.wc_odom_map_align_sweep(self.h, R.ptr(points), C.c_uint64(len(points)), C.byref(b), C.byref(e), C.byref(opts), C.byref(summ),
+                                                C.c_int(1 if insert else 0)):
+            return None
+        return _pose_pair(b), _pose_pair(e), _ct_summary_dict(summ)
 
     def map_relocalize(self, xyz, T, factor, n_levels, opts):
         """coarse-to-fine wc_map_align of xyz ((n, 3) float32) from the rough pose T (LidarOdometry::RelocalizeToMap): n_levels - 1

@@ -46,6 +46,12 @@ MAP_REG_ROW = np.dtype([("J", "f8", 6), ("d", "f8"), ("k", "f8")])  # wc_map_reg
 MAP_NORMAL_EQ = np.dtype([("H", "f8", 21), ("g", "f8", 6), ("cost", "f8"), ("n_used", "u8"), ("n_found", "u8")])  # wc_map_normal_eq
 assert MAP_REG_ROW.itemsize == 64 and MAP_NORMAL_EQ.itemsize == 240 and MAP_NORMAL_EQ.fields["cost"][1] == 216
 
+# wc_map_linearize_ct / wc_map_align_ct: one point's row (J, d, k and the end pose's share s), the 640-byte normal equations of two poses
+MAP_CT_ROW = np.dtype([("J", "f8", 6), ("d", "f8"), ("k", "f8"), ("s", "f8")])  # wc_map_ct_row
+MAP_CT_NORMAL_EQ = np.dtype([("H00", "f8", 21), ("H01", "f8", 21), ("H11", "f8", 21), ("g0", "f8", 6), ("g1", "f8", 6), ("cost", "f8"),
+                             ("n_used", "u8"), ("n_found", "u8"), ("n_outside", "u8"), ("reserved", "u8")])  # wc_map_ct_normal_eq
+assert MAP_CT_ROW.itemsize == 72 and MAP_CT_NORMAL_EQ.itemsize == 640 and MAP_CT_NORMAL_EQ.fields["cost"][1] == 600
+
 # wc_map_score: one pose hypothesis's counts (wc_map_score_batch)
 MAP_SCORE = np.dtype([("n_hit", "u4"), ("n_in", "u4"), ("n_bad", "u4"), ("reserved", "u4")])
 assert MAP_SCORE.itemsize == 16
@@ -189,6 +195,45 @@ class MapAlignSummary(C.Structure):
         ("n_found", C.c_uint64),
         ("last_step", C.c_double * 6),
     ]
+
+
+class Pose(C.Structure):
+    """wc_pose: pos, quat = (w, x, y, z)"""
+
+    _fields_ = [("pos", C.c_double * 3), ("quat", C.c_double * 4)]
+
+
+class MapCtAlignOpts(C.Structure):
+    """wc_map_ct_align_opts"""
+
+    _fields_ = [
+        ("reg", MapRegParams),
+        ("max_iterations", C.c_uint32),
+        ("min_used", C.c_uint32),
+        ("tol_rot", C.c_double),
+        ("tol_trans", C.c_double),
+        ("min_pivot", C.c_double),
+        ("prior", C.c_double * 4),
+    ]
+
+
+class MapCtAlignSummary(C.Structure):
+    """wc_map_ct_align_summary"""
+
+    _fields_ = [
+        ("initial_cost", C.c_double),
+        ("final_cost", C.c_double),
+        ("iterations", C.c_int32),
+        ("termination", C.c_int32),
+        ("n_used", C.c_uint64),
+        ("n_found", C.c_uint64),
+        ("n_outside", C.c_uint64),
+        ("last_step", C.c_double * 12),
+        ("prior_cost", C.c_double),
+    ]
+
+
+assert C.sizeof(Pose) == 56 and C.sizeof(MapCtAlignOpts) == 96 and C.sizeof(MapCtAlignSummary) == 152
 
 
 class MapCarveParams(C.Structure):
