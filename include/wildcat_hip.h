@@ -559,6 +559,58 @@ int wc_map_absorb(wc_ctx *ctx, wc_map *m, const wc_map_voxel *d_vox, const int64
  * doubles, or when dst has moments and src has none (a moments src merges into a plain dst, the moments are dropped).  Waits once, to
  * read src's exact voxel count for dst's growth bound; the merge itself is enqueued on the ctx stream. */
 int wc_map_merge(wc_ctx *ctx, wc_map *dst, wc_map *src);
+/* A map built in another frame, merged under a rigid pose.  T is wc_map_linearize's row-major 3 x 4 (R | t) in fp64: it
+ * takes src's frame to dst's.  Every live voxel of src - key k, count n, sums S and, where both maps hold moments, words U, M - is moved
+ * as ONE Gaussian and added to the voxel of dst its centroid moves into; table to table on the device, in integers.  With v the voxel
+ * size and r(k, v) = rint((k + 0.5) * v * 1024) / 1024, every fp64 operation below is a single IEEE operation in the stated association
+ * (no fused multiply-add), so the state of dst afterwards is a pure function of the two states and T: byte-equal for every run, grid
+ * size and slot order of src, and reproducible with integers plus IEEE fp64 (tests/map_moved_ref.py).
+ *   1 centroid   c_a  = r(k_a, v) + ((double)S_a / (double)n) * 2^-32
+ *                c'_a = ((T[4a] c_x + T[4a+1] c_y) + T[4a+2] c_z) + T[4a+3]
+ *   2 key        K_a  = floor(c'_a / v), the insert's rule on the fp64 centroid.  The voxel is REJECTED - counted, not applied - when a
+ *                c'_a is not finite or |K_a| >= 2^20 on an axis (and by the count cap under "limits")
+ *   3 sums       m_a  = llrint((c'_a - r(K_a, v)) * 2^32),  S'_a = n m_a in wrapping 64-bit arithmetic: the moved centroid is kept to
+ *                the 2^-32 m grid
+ *   4 moments    N_ab = n M_ab - U_a U_b in 128 bits, rounded once to fp64 on its magnitude (as the surfel export rounds it);
+ *                C_ab = fp64(N_ab) / (double)n, one division;  B_ij = (R_i0 C_0j + R_i1 C_1j) + R_i2 C_2j;
+ *                C'_ij = (B_i0 R_j0 + B_i1 R_j1) + B_i2 R_j2 for i <= j;  e_a = (m_a + 2^15) >> 16;  U'_a = n e_a;
+ *                M'_ab = llrint(C'_ab) + n e_a e_b.  The moved voxel's integer covariance numerator n M' - U' U' is thus exactly
+ *                n llrint((R C R^T)_ab), and adding the words into a voxel that already holds points obeys the parallel-axis rule by
+ *                construction.  Skipped when dst is a plain map (a moments src merges into a plain dst)
+ *   5 deposit    count, S' and (U', M') are added to voxel K of dst, which is created where it is new
+ * WC_ERR_ARG, with dst and a pre-filled h_out untouched: dst == src; a map of another context; voxel sizes that are not bitwise equal;
+ * moments in dst and none in src; T == NULL; a non-finite entry of T; |(R^T R - I)_ij| > 1e-9 for some entry, with (R^T R)_ij =
+ * (R_0i R_0j + R_1i R_1j) + R_2i R_2j - a design threshold against passing something that is no rotation, not a measurement.
+ * Tombstoned slots of src are skipped; src is never modified.  dst grows as wc_map_merge grows it, by src's live voxel count, whose
+ * read-back is the call's one wait before the launch.  h_out (may be NULL: the call then returns without waiting) receives {voxels
+ * applied, points applied, voxels rejected, points rejected} of this call; dst's voxel and point counts grow by what is new and what was
+ * applied.  An empty src is WC_OK with four zeros.
+ * Limits.
+ *   extent    all n points of a source voxel go to the ONE voxel their centroid moves into: nothing is split over the voxels the moved
+ *             voxel straddles, so a voxel's points can reach v sqrt(3) from its far corner and its Gaussian describes them, not a
+ *             sample of that voxel's own cube
+ *   overflow  c' lies in voxel K, so |c'_a - r(K_a, v)| <= v / 2 + 2^-11 m (+ rounding) <= 2.0005 m for v <= 4: |m| < 2^33.001 and
+ *             |e| < 2^17.001, the bound of a point's u ("map surfels" above).  The second moments do not stay inside that section's
+ *             product bound: the points of a cube of side v have a variance of up to 3 v^2 / 4 along its diagonal, which a rotation can
+ *             turn onto an axis, so M'_aa / n <= 3 v^2 / 4 + e_a^2 in units of 2^-32 m^2 - below 2^34.003 for v <= 2 (2^28 points per
+ *             voxel hold, as for an insert), below 2^36.003 for v <= 4.  The call therefore enforces a cap: with v > 2 a source voxel of
+ *             more than 2^26 points is rejected.  This holds for a source whose voxels hold points of their own cube (inserted,
+ *             merged, coarsened); a source that is itself the result of a move has wider voxels ("extent") and no such bound
+ *   counts    what the counts of a destination voxel reach is not checked against 2^28 / 2^30, as in wc_map_merge
+ *   exactness a coincident source voxel (C = 0) stays exactly so: M'_ab = n e_a e_b.  A voxel that is exactly planar stays exactly planar
+ *             only where R C R^T rounds to a singular matrix on the integer grid; in general its smallest eigenvalue becomes a rounding
+ *             residue of the order of 2^-32 / n m^2
+ *   identity  T = identity does NOT give wc_map_merge's bits: S' = n llrint(S / n) is not S in general, and the moments are re-based to
+ *             the rounded centroid.  Use wc_map_merge for maps of one frame */
+int wc_map_merge_moved(wc_ctx *ctx, wc_map *dst, wc_map *src, const double T[12], uint64_t h_out[4]);
+/* Steps 1 - 4 above over n exported records on the HOST: no context, no GPU, the same per-voxel function (csrc/map.hip: map_move_voxel).
+ * out_vox[i] receives the record (K, n, S') of vox[i] and out_mom[9 i ..] its nine words; a rejected record - by step 2, by the count
+ * cap, or one wc_map_absorb would reject (|key| >= 2^20, count 0 or > 2^30) - is written as all zeros (count 0, which wc_map_absorb
+ * skips) and counted in *n_rejected (may be NULL).  mom and out_mom are both NULL (step 4 is skipped) or both given.  wc_map_absorb of
+ * the output into dst gives, bit for bit, the map wc_map_merge_moved gives.  The output keys need not be distinct or sorted.
+ * WC_ERR_ARG, with every output untouched: voxel outside [0.01, 4.0]; T as above; n > 0 with vox or out_vox NULL; one of mom, out_mom NULL. */
+int wc_map_move_state(const wc_map_voxel *vox, const int64_t *mom, uint64_t n, double voxel, const double T[12], wc_map_voxel *out_vox,
+                      int64_t *out_mom, uint64_t *n_rejected);
 /* A coarser level, exactly.  *out becomes a NEW map of voxel size V = (double)factor * v (one fp64 product; v = src's voxel size) that
  * holds the voxels of src gathered factor^3 to one; src is not modified.  With r(k, v) = rint((k + 0.5) * v * 1024) / 1024, the reference
  * point of wc_map_export_state:

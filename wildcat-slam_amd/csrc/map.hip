@@ -126,7 +126,8 @@ constexpr double kMapKeyLim = 1048576.0;           // |k| < 2^20
 constexpr int kMapKeyOff = 1 << 20;
 constexpr int kCtrOcc = 0, kCtrPts = 16, kCtrRej = 32, kCtrRejCall = 48, kCtrLost = 56;  // u64 word of each counter
 constexpr int kCtrFound = 64, kCtrKeepVox = 80, kCtrKeepPts = 96;                        // query hits; a crop's kept voxels, points
-constexpr int kCtrRmVox = 112, kCtrRmPts = 128, kCtrRmNone = 144, kCtrWords = 160;       // wc_map_remove_keys: voxels, points, keys that removed nothing
+constexpr int kCtrRmVox = 112, kCtrRmPts = 128, kCtrRmNone = 144;                        // wc_map_remove_keys: voxels, points, keys that removed nothing
+constexpr int kCtrMvVox = 160, kCtrMvPts = 176, kCtrMvRejVox = 192, kCtrMvRejPts = 208, kCtrWords = 224;  // wc_map_merge_moved: this call's four counts
 constexpr int kNearThreads = 256;
 constexpr int kCompactChunk = 2048;                // slots per workgroup of k_map_compact
 constexpr int kCarveThreads = 256;
@@ -146,7 +147,7 @@ __device__ __forceinline__ unsigned long long map_hash(unsigned long long k) {  
   return k;
 }
 // reference point of a voxel on the 2^-10 m grid: the voxel centre, rounded; a function of (k, v) alone
-__device__ __forceinline__ double map_ref(int k, double v) { return rint(((double)k + 0.5) * v * 1024.0) * (1.0 / 1024.0); }
+__host__ __device__ __forceinline__ double map_ref(int k, double v) { return rint(((double)k + 0.5) * v * 1024.0) * (1.0 / 1024.0); }
 __device__ __forceinline__ int map_unpack(unsigned long long key, int axis) {
   return (int)((key >> (42 - 21 * axis)) & 0x1FFFFFull) - kMapKeyOff;
 }
@@ -463,10 +464,15 @@ __global__ void __launch_bounds__(256) k_map_centroids(const unsigned long long 
 // a non-negative 128-bit integer rounded ONCE (to nearest, ties to even) to fp64.  The device has no library conversion for __int128:
 // the top 64 bits of the normalised value, with every bit below them folded into bit 0 (eleven places under the rounding position, so it
 // only breaks ties), go through the hardware's correctly rounded u64 conversion; the scaling by a power of two is exact
-__device__ __forceinline__ double map_u128_to_double(unsigned __int128 m) {
+// (__host__ too: wc_map_move_state runs map_move_voxel without a GPU; the host has no __clzll, hi != 0 there)
+__host__ __device__ __forceinline__ double map_u128_to_double(unsigned __int128 m) {
   const unsigned long long hi = (unsigned long long)(m >> 64), lo = (unsigned long long)m;
   if (hi == 0) return (double)lo;
+#if defined(__HIP_DEVICE_COMPILE__)
   const int s = __clzll((long long)hi);
+#else
+  const int s = __builtin_clzll(hi);
+#endif
   const unsigned __int128 n = m << s;
   const unsigned long long top = (unsigned long long)(n >> 64) | ((unsigned long long)n != 0 ? 1ull : 0ull);
   return ldexp((double)top, 64 - s);
@@ -1290,6 +1296,107 @@ __global__ void __launch_bounds__(kStateThreads) k_map_coarsen(const unsigned lo
   block_count<kStateThreads>({(unsigned long long)fresh, n_pts}, {ctr + kCtrOcc, ctr + kCtrPts});
 }
 
+// ---- a state under a rigid pose (include/wildcat_hip.h: wc_map_merge_moved, wc_map_move_state) -------------------------
+constexpr unsigned long long kMovedBigCount = 1ull << 26;  // the most points a source voxel of a map with v > 2 m may hold (header: limits)
+// one voxel's Gaussian - count n, sums S, moment words w (MOM) - moved by T: the key it lands in and its words relative to that voxel's
+// reference point.  The kernel's and the host's one copy, every operation in the header's stated order (-ffp-contract=off: no fused
+// multiply-add on either side).  false: the voxel is rejected and `o` is not to be used
+struct map_moved_voxel {
+  int K[3];
+  unsigned long long S[3], w[kMapMom];
+};
+template <bool MOM>
+__host__ __device__ __forceinline__ bool map_move_voxel(int kx, int ky, int kz, unsigned long long n, long long sx, long long sy, long long sz,
+                                                        const unsigned long long (&w)[kMapMom], double v, const double (&T)[12],
+                                                        map_moved_voxel &o) {
+  const double dn = (double)n;
+  // 1. the centroid, and where it goes
+  const double cx = map_ref(kx, v) + ((double)sx / dn) * (1.0 / kMapUnit), cy = map_ref(ky, v) + ((double)sy / dn) * (1.0 / kMapUnit),
+               cz = map_ref(kz, v) + ((double)sz / dn) * (1.0 / kMapUnit);
+  const double px = ((T[0] * cx + T[1] * cy) + T[2] * cz) + T[3], py = ((T[4] * cx + T[5] * cy) + T[6] * cz) + T[7],
+               pz = ((T[8] * cx + T[9] * cy) + T[10] * cz) + T[11];
+  // 2. its voxel: the insert's rule; a non-finite coordinate or |K| >= 2^20 fails it
+  if (!map_voxel_of(px, py, pz, v, o.K[0], o.K[1], o.K[2])) return false;
+  if (v > 2.0 && n > kMovedBigCount) return false;
+  // 3. the first sums: n times the centroid on the 2^-32 m grid
+  const long long m[3] = {llrint((px - map_ref(o.K[0], v)) * kMapUnit), llrint((py - map_ref(o.K[1], v)) * kMapUnit),
+                          llrint((pz - map_ref(o.K[2], v)) * kMapUnit)};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) o.S[a] = n * (unsigned long long)m[a];
+  if constexpr (MOM) {
+    // 4. C = N / n with N_ab = n M_ab - U_a U_b in 128 bits, rounded once; C' = (R C) R^T; the words that give back n llrint(C')
+    constexpr int A[6] = {0, 0, 0, 1, 1, 2}, B[6] = {0, 1, 2, 1, 2, 2};
+    double c6[6];
+#pragma unroll
+    for (int e = 0; e < 6; ++e) {
+      const __int128 N = (__int128)(long long)n * (__int128)(long long)w[3 + e] - (__int128)(long long)w[A[e]] * (__int128)(long long)w[B[e]];
+      const bool neg = N < 0;
+      const double mag = map_u128_to_double(neg ? (unsigned __int128)(-N) : (unsigned __int128)N);
+      c6[e] = (neg ? -mag : mag) / dn;
+    }
+    const double Cm[3][3] = {{c6[0], c6[1], c6[2]}, {c6[1], c6[3], c6[4]}, {c6[2], c6[4], c6[5]}};
+    double Bm[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) Bm[i][j] = (T[4 * i] * Cm[0][j] + T[4 * i + 1] * Cm[1][j]) + T[4 * i + 2] * Cm[2][j];
+    }
+    unsigned long long E[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      E[a] = (unsigned long long)((m[a] + 32768) >> 16);
+      o.w[a] = n * E[a];
+    }
+#pragma unroll
+    for (int e = 0; e < 6; ++e) {
+      const int i = A[e], j = B[e];
+      const double c = (Bm[i][0] * T[4 * j] + Bm[i][1] * T[4 * j + 1]) + Bm[i][2] * T[4 * j + 2];
+      o.w[3 + e] = (unsigned long long)llrint(c) + n * E[i] * E[j];
+    }
+  }
+  return true;
+}
+
+// merge under a pose: one lane per slot of the source table, as k_map_coarsen - the payload (two 16-byte loads) and the nine moment words
+// are loaded before the first atomic, map_move_voxel runs in registers, then one map_slot probe and four (thirteen) no-return atomic
+// adds.  Lanes whose voxels land in one destination voxel sit at hashed slots of the source: nothing to gather first.  The pose and v
+// travel in the kernel arguments.  Applied and rejected voxels and points go to the call's four counters, fresh voxels and applied
+// points to the destination's own.  MOM: the destination holds moments (then the source does)
+template <bool MOM>
+__global__ void __launch_bounds__(kStateThreads) k_map_merge_moved(const unsigned long long *skeys, const long long *spay, const long long *smom,
+                                                                   uint64_t scap, double v, map_pose P, unsigned long long *keys, long long *pay,
+                                                                   long long *mom, unsigned long long mask, unsigned long long *ctr) {
+  const uint64_t i = (uint64_t)blockIdx.x * kStateThreads + threadIdx.x;
+  unsigned fresh = 0;
+  unsigned long long n_vox = 0, n_pts = 0, r_vox = 0, r_pts = 0;
+  const unsigned long long key = i < scap ? skeys[i] : kMapEmpty;
+  if (key < kMapTomb) {
+    const longlong2 *p = (const longlong2 *)(spay + 4 * i);
+    const longlong2 p0 = p[0], p1 = p[1];
+    unsigned long long w[kMapMom] = {};
+    if constexpr (MOM) {
+#pragma unroll
+      for (int j = 0; j < kMapMom; ++j) w[j] = (unsigned long long)smom[kMapMom * i + j];
+    }
+    const unsigned long long n = (unsigned long long)p1.y;
+    map_moved_voxel o;
+    if (map_move_voxel<MOM>(map_unpack(key, 0), map_unpack(key, 1), map_unpack(key, 2), n, p0.x, p0.y, p1.x, w, v, P.T, o)) {
+      const unsigned long long h = map_slot(keys, mask, map_pack(o.K[0], o.K[1], o.K[2]), fresh);
+      if (h != kMapEmpty) {
+        map_add_pay(pay, h, o.S[0], o.S[1], o.S[2], n);
+        if constexpr (MOM) map_add_mom(mom, h, o.w);
+        n_vox = 1, n_pts = n;
+      } else {  // (cannot happen: the growth policy left room for every voxel of the source)
+        atomicAdd(ctr + kCtrLost, 1ull);
+      }
+    } else {
+      r_vox = 1, r_pts = n;
+    }
+  }
+  block_count<kStateThreads>({(unsigned long long)fresh, n_pts, n_vox, n_pts, r_vox, r_pts},
+                             {ctr + kCtrOcc, ctr + kCtrPts, ctr + kCtrMvVox, ctr + kCtrMvPts, ctr + kCtrMvRejVox, ctr + kCtrMvRejPts});
+}
+
 // ---- carving (wc_map_carve) -------------------------------------------------------------------------------------------------------
 // what is the same for every ray of a call; the squares and the origin's voxel are formed once, on the host
 struct map_ray_args {
@@ -1836,7 +1943,90 @@ extern "C" int wc_map_merge(wc_ctx *ctx, wc_map *dst, wc_map *src) {
   return map_added(ctx, dst, n, nullptr);
 }
 
-// ---- a coarser level (include/wildcat_hip.h: wc_map_coarsen) ----------------------------------------------------------
+// ---- a state under a rigid pose (include/wildcat_hip.h: wc_map_merge_moved, wc_map_move_state) ---------------------
+namespace {
+// a pose the move accepts: twelve finite entries and |(R^T R - I)_ij| <= 1e-9, (R^T R)_ij = (R_0i R_0j + R_1i R_1j) + R_2i R_2j
+bool map_pose_rigid(const double *T) {
+  if (!T) return false;
+  for (int j = 0; j < 12; ++j)
+    if (!std::isfinite(T[j])) return false;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double g = (T[i] * T[j] + T[4 + i] * T[4 + j]) + T[8 + i] * T[8 + j];
+      if (!(std::fabs(g - (i == j ? 1.0 : 0.0)) <= 1e-9)) return false;
+    }
+  return true;
+}
+}  // namespace
+
+extern "C" int wc_map_merge_moved(wc_ctx *ctx, wc_map *dst, wc_map *src, const double T[12], uint64_t h_out[4]) {
+  wc_dev_guard dg_(ctx);
+  if (!map_ok(ctx, dst) || !map_ok(ctx, src) || dst == src || std::memcmp(&dst->voxel, &src->voxel, sizeof(double)) != 0 ||
+      (dst->mom && !src->mom) || !map_pose_rigid(T))
+    return wc_fail(ctx, WC_ERR_ARG,
+                   "%s: null argument, dst == src, a map of another context, two voxel sizes, moments in dst and none in src, or a T that is "
+                   "not finite or not rigid (|R^T R - I| <= 1e-9)",
+                   __func__);
+  WC_TRY(map_sync_counters(ctx, src));  // (the wait: the source's exact voxel count bounds what the destination may gain)
+  const uint64_t n = src->h_ctr[kCtrOcc];
+  if (n == 0) {
+    if (h_out) h_out[0] = h_out[1] = h_out[2] = h_out[3] = 0;
+    return WC_OK;
+  }
+  WC_TRY(map_make_room(ctx, dst, n, __func__));
+  WC_HIP(ctx, hipMemsetAsync(dst->ctr + kCtrMvVox, 0, (size_t)(kCtrWords - kCtrMvVox) * 8, ctx->stream));
+  map_pose P;
+  std::memcpy(P.T, T, sizeof(P.T));
+  const unsigned grid = (unsigned)((src->cap + kStateThreads - 1) / kStateThreads);
+  if (dst->mom)
+    k_map_merge_moved<true><<<grid, kStateThreads, 0, ctx->stream>>>(src->keys, src->pay, src->mom, src->cap, src->voxel, P, dst->keys, dst->pay,
+                                                                     dst->mom, dst->cap - 1, dst->ctr);
+  else
+    k_map_merge_moved<false><<<grid, kStateThreads, 0, ctx->stream>>>(src->keys, src->pay, nullptr, src->cap, src->voxel, P, dst->keys, dst->pay,
+                                                                      nullptr, dst->cap - 1, dst->ctr);
+  WC_HIP(ctx, hipGetLastError());
+  if (!h_out) return map_added(ctx, dst, n, nullptr);
+  dst->pts_since += n;  // (as map_added: the n possible new voxels stay in the bound if the read-back fails)
+  WC_TRY(map_sync_counters(ctx, dst));
+  h_out[0] = dst->h_ctr[kCtrMvVox], h_out[1] = dst->h_ctr[kCtrMvPts], h_out[2] = dst->h_ctr[kCtrMvRejVox], h_out[3] = dst->h_ctr[kCtrMvRejPts];
+  return WC_OK;
+}
+
+extern "C" int wc_map_move_state(const wc_map_voxel *vox, const int64_t *mom, uint64_t n, double voxel, const double T[12], wc_map_voxel *out_vox,
+                                 int64_t *out_mom, uint64_t *n_rejected) {
+  if (!(voxel >= 0.01 && voxel <= 4.0) || !map_pose_rigid(T) || (n && (!vox || !out_vox)) || (mom != nullptr) != (out_mom != nullptr))
+    return WC_ERR_ARG;
+  double P[12];
+  std::memcpy(P, T, sizeof(P));
+  uint64_t rej = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const wc_map_voxel &r = vox[i];
+    unsigned long long w[kMapMom] = {};
+    if (mom)
+      for (int j = 0; j < kMapMom; ++j) w[j] = (unsigned long long)mom[kMapMom * i + j];
+    bool ok = r.key[0] > -kMapKeyOff && r.key[0] < kMapKeyOff && r.key[1] > -kMapKeyOff && r.key[1] < kMapKeyOff && r.key[2] > -kMapKeyOff &&
+              r.key[2] < kMapKeyOff && r.count >= 1u && r.count <= kStateMaxCount;  // (what wc_map_absorb accepts)
+    map_moved_voxel o;
+    if (ok)
+      ok = mom ? map_move_voxel<true>(r.key[0], r.key[1], r.key[2], r.count, r.sum[0], r.sum[1], r.sum[2], w, voxel, P, o)
+               : map_move_voxel<false>(r.key[0], r.key[1], r.key[2], r.count, r.sum[0], r.sum[1], r.sum[2], w, voxel, P, o);
+    wc_map_voxel q;
+    std::memset(&q, 0, sizeof(q));
+    if (ok) {
+      q.count = r.count;
+      for (int a = 0; a < 3; ++a) q.key[a] = o.K[a], q.sum[a] = (int64_t)o.S[a];
+    } else {
+      ++rej;
+    }
+    out_vox[i] = q;
+    if (mom)
+      for (int j = 0; j < kMapMom; ++j) out_mom[kMapMom * i + j] = ok ? (int64_t)o.w[j] : 0;
+  }
+  if (n_rejected) *n_rejected = rej;
+  return WC_OK;
+}
+
+// ---- a coarser level(include/wildcat_hip.h: wc_map_coarsen) ----------------------------------------------------------
 extern "C" int wc_map_coarsen(wc_ctx *ctx, wc_map *src, uint32_t factor, uint32_t flags, wc_map **out) {
   wc_dev_guard dg_(ctx);
   const bool mom = (flags & WC_MAP_MOMENTS) != 0;

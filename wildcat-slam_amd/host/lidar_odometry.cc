@@ -10,6 +10,7 @@
 #include <chrono>
 #include <cstring>
 #include <limits>
+#include <memory>
 
 #include "../csrc/dmath.h"
 #include "cubic_bspline.h"
@@ -585,16 +586,16 @@ void FreeLevels(wc_ctx *ctx, wc_map *(&levels)[kMaxLevels], uint32_t n_levels) {
 // wc_map_align_pyramid_batch, the built levels destroyed.  seed(coarsest level, points) runs ahead of the alignment and may still fill T;
 // false from it ends the call.  T: K x 12 doubles, the starts in and the aligned poses out; s: n_levels x K summaries, level-major;
 // status: K codes.  false: BuildLevels' cases, the seed's, or arguments the library refuses (no abort: as in AlignToMap)
-template <class Seed>
-bool AlignCandidates(wc_ctx *ctx, wc_map *map, double voxel, const float *xyz, size_t n, uint32_t factor, uint32_t n_levels,
-                     const wc_map_align_opts &finest, Seed seed, std::vector<double> &T, std::vector<wc_map_align_summary> &s,
-                     std::vector<int32_t> &status) {
+// (upload(): the points' descriptor, called once the levels stand - the host cloud uploaded into a buffer of the call, or points that are
+// in device memory already, as MergeMapFile's exported centroids)
+template <class Upload, class Seed>
+bool AlignCandidatesOf(wc_ctx *ctx, wc_map *map, double voxel, Upload upload, uint32_t factor, uint32_t n_levels, const wc_map_align_opts &finest,
+                       Seed seed, std::vector<double> &T, std::vector<wc_map_align_summary> &s, std::vector<int32_t> &status) {
   wc_map *levels[kMaxLevels] = {};
   wc_map_align_opts opts[kMaxLevels];
   bool ok = BuildLevels(ctx, map, voxel, factor, n_levels, finest, levels, opts);
   if (ok) {
-    const DevBuf d_xyz(ctx, n * 3 * sizeof(float));
-    const wc_points desc = UploadXyz(d_xyz, xyz, n);
+    const wc_points desc = upload();
     ok = seed(levels[0], desc);
     if (ok) {
       const uint32_t K = (uint32_t)(T.size() / 12);
@@ -604,6 +605,17 @@ bool AlignCandidates(wc_ctx *ctx, wc_map *map, double voxel, const float *xyz, s
   }
   FreeLevels(ctx, levels, n_levels);
   return ok;
+}
+template <class Seed>
+bool AlignCandidates(wc_ctx *ctx, wc_map *map, double voxel, const float *xyz, size_t n, uint32_t factor, uint32_t n_levels,
+                     const wc_map_align_opts &finest, Seed seed, std::vector<double> &T, std::vector<wc_map_align_summary> &s,
+                     std::vector<int32_t> &status) {
+  std::unique_ptr<DevBuf> d_xyz;  // (allocated by upload(): behind BuildLevels, as before)
+  const auto upload = [&] {
+    d_xyz.reset(new DevBuf(ctx, n * 3 * sizeof(float)));
+    return UploadXyz(*d_xyz, xyz, n);
+  };
+  return AlignCandidatesOf(ctx, map, voxel, upload, factor, n_levels, finest, seed, T, s, status);
 }
 const auto kNoSeed = [](wc_map *, const wc_points &) { return true; };
 }  // namespace
@@ -797,8 +809,11 @@ bool LidarOdometry::SaveMap(const std::string &path) {
   if (!(written && closed)) std::remove(path.c_str());
   return written && closed;
 }
-bool LidarOdometry::LoadMap(const std::string &path, bool merge) {
-  if (!map_) return false;
+namespace {
+// what LoadMap and MergeMapFile begin with: the file read, decoded and held against the map's voxel size and flags; the records (and,
+// with `moments`, their moment words) unpacked.  false: the file cannot be read, Decode refuses it, its voxel size is not bitwise
+// `voxel`, or `moments` is asked of a file without
+bool ReadMapFile(const std::string &path, double voxel, bool moments, std::vector<wc_map_file::Voxel> &vox, std::vector<int64_t> &mom) {
   std::FILE *f = std::fopen(path.c_str(), "rb");
   if (!f) return false;
   std::vector<uint8_t> file;
@@ -809,23 +824,72 @@ bool LidarOdometry::LoadMap(const std::string &path, bool merge) {
   wc_map_file::Header h;
   if (!read_ok || wc_map_file::Decode(file.data(), file.size(), &h) != wc_map_file::kOk) return false;
   const bool file_moments = (h.flags & wc_map_file::kFlagMoments) != 0;
-  if (std::memcmp(&h.voxel, &map_voxel_, sizeof(double)) != 0 || (map_moments_ && !file_moments)) return false;
-  std::vector<wc_map_file::Voxel> vox(h.n);
-  std::vector<int64_t> mom(map_moments_ ? 9 * h.n : 0);
-  wc_map_file::Unpack(file.data(), h, vox.data(), map_moments_ ? mom.data() : nullptr);
+  if (std::memcmp(&h.voxel, &voxel, sizeof(double)) != 0 || (moments && !file_moments)) return false;
+  vox.resize(h.n);
+  mom.resize(moments ? 9 * h.n : 0);
+  wc_map_file::Unpack(file.data(), h, vox.data(), moments ? mom.data() : nullptr);
+  return true;
+}
+// ... and the records absorbed into `map`
+void AbsorbRecords(wc_ctx *ctx, wc_map *map, const std::vector<wc_map_file::Voxel> &vox, const std::vector<int64_t> &mom) {
+  const uint64_t n = vox.size();
+  if (!n) return;
+  const DevBuf d_vox(ctx, n * sizeof(wc_map_voxel)), d_mom(ctx, mom.size() * sizeof(int64_t));
+  CheckCall(ctx, "wc_h2d", wc_h2d(ctx, d_vox.p, vox.data(), n * sizeof(wc_map_voxel)));
+  if (d_mom.p) CheckCall(ctx, "wc_h2d", wc_h2d(ctx, d_mom.p, mom.data(), mom.size() * sizeof(int64_t)));
+  uint64_t rejected = 0;  // (asked for: the call waits, so the host vectors and device buffers outlive the kernel)
+  CheckCall(ctx, "wc_map_absorb", wc_map_absorb(ctx, map, (const wc_map_voxel *)d_vox.p, (const int64_t *)d_mom.p, n, &rejected));
+  WC_CHECK(rejected == 0);  // (Decode refuses every record the absorb rejects)
+}
+}  // namespace
+bool LidarOdometry::LoadMap(const std::string &path, bool merge) {
+  if (!map_) return false;
+  std::vector<wc_map_file::Voxel> vox;
+  std::vector<int64_t> mom;
+  if (!ReadMapFile(path, map_voxel_, map_moments_, vox, mom)) return false;
   if (!merge) {  // as SetMapVoxel re-creates it, with room for the file's voxels: no growth and no wc_map_clear
     WC_CALL(wc_map_destroy(ctx_, map_));
     map_ = nullptr;
-    WC_CALL(wc_map_create_ex(ctx_, map_voxel_, h.n, map_moments_ ? WC_MAP_MOMENTS : 0u, &map_));
+    WC_CALL(wc_map_create_ex(ctx_, map_voxel_, vox.size(), map_moments_ ? WC_MAP_MOMENTS : 0u, &map_));
   }
-  if (h.n) {
-    const DevBuf d_vox(ctx_, h.n * sizeof(wc_map_voxel)), d_mom(ctx_, mom.size() * sizeof(int64_t));
-    CheckCall(ctx_, "wc_h2d", wc_h2d(ctx_, d_vox.p, vox.data(), h.n * sizeof(wc_map_voxel)));
-    if (d_mom.p) CheckCall(ctx_, "wc_h2d", wc_h2d(ctx_, d_mom.p, mom.data(), mom.size() * sizeof(int64_t)));
-    uint64_t rejected = 0;  // (asked for: the call waits, so the host vectors and device buffers outlive the kernel)
-    WC_CALL(wc_map_absorb(ctx_, map_, (const wc_map_voxel *)d_vox.p, (const int64_t *)d_mom.p, h.n, &rejected));
-    WC_CHECK(rejected == 0);  // (Decode refuses every record the absorb rejects)
+  AbsorbRecords(ctx_, map_, vox, mom);
+  return true;
+}
+bool LidarOdometry::MergeMapFile(const std::string &path, double T_io[12], uint32_t factor, uint32_t n_levels, const wc_map_align_opts &opts,
+                                 wc_map_align_summary *summaries) {
+  if (!map_ || !map_moments_ || !T_io || factor < 1 || n_levels < 1 || n_levels > kMaxLevels) return false;
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<wc_map_file::Voxel> vox;
+  std::vector<int64_t> mom;
+  if (!ReadMapFile(path, map_voxel_, true, vox, mom)) return false;
+  wc_map *other = nullptr;  // the file's map, in the file's frame
+  WC_CALL(wc_map_create_ex(ctx_, map_voxel_, vox.size(), WC_MAP_MOMENTS, &other));
+  AbsorbRecords(ctx_, other, vox, mom);
+  std::vector<double> T(T_io, T_io + 12);
+  std::vector<wc_map_align_summary> s;
+  std::vector<int32_t> status;
+  bool ok;
+  {
+    // its centroids, exported on the device, are the points RelocalizeToMap's level chain aligns to the facade's map
+    uint64_t n = vox.size();
+    const DevBuf d_xyz(ctx_, n * 3 * sizeof(float)), d_count(ctx_, n * sizeof(uint32_t));
+    const auto exported = [&] {
+      CheckCall(ctx_, "wc_map_export", wc_map_export(ctx_, other, (float *)d_xyz.p, (uint32_t *)d_count.p, nullptr, n, &n));
+      return wc_points{d_xyz.p, nullptr, 12, 0, n};
+    };
+    ok = AlignCandidatesOf(ctx_, map_, map_voxel_, exported, factor, n_levels, opts, kNoSeed, T, s, status) && status[0] == WC_OK;
   }
+  if (ok) {
+    const wc_map_align_summary &last = s[n_levels - 1];
+    ok = last.termination != 2 && last.n_used >= opts.min_used;
+  }
+  // (a T the library refuses - no rotation, from a start that was none - is the caller's: no abort, as in AlignToMap)
+  if (ok) ok = wc_map_merge_moved(ctx_, map_, other, T.data(), nullptr) == WC_OK;
+  WC_CALL(wc_map_destroy(ctx_, other));
+  if (!ok) return false;
+  std::memcpy(T_io, T.data(), 12 * sizeof(double));
+  if (summaries) std::memcpy(summaries, s.data(), s.size() * sizeof(s[0]));
+  last_map_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return true;
 }
 bool LidarOdometry::SetMapKeepRadius(double radius) {

@@ -166,6 +166,15 @@ class LidarOdometry {
   // (wc_map_file::Decode), when its voxel size is not bitwise config().map_voxel_size, or when map_surfels is on and the file has no
   // moments (a file with moments loads into a map without: they are dropped)
   bool LoadMap(const std::string &path, bool merge = false);
+  // a file SaveMap wrote in ANOTHER frame, aligned to the map and merged into it under the pose found: the file is decoded
+  // into a temporary map of the facade's voxel size with moments; that map's centroids (wc_map_export, on the device) go through the level
+  // chain of RelocalizeToMap from T_io (the file's frame to the map's) with `opts` as its `finest`; when the finest level ends with
+  // termination 0 or 1 and n_used >= opts.min_used, wc_map_merge_moved adds the temporary map to the facade's under the found pose, T_io
+  // becomes that pose and summaries (may be null) receives n_levels records, coarsest first.  false - the map and T_io untouched - where
+  // LoadMap(path) or RelocalizeToMap would return false (map_surfels off included), when the alignment ends with termination 2 or too few
+  // points, and when the library refuses the pose.  The call's wall time goes to last_map_ms().  Nothing in AddLidarScan calls it
+  bool MergeMapFile(const std::string &path, double T_io[12], uint32_t factor, uint32_t n_levels, const wc_map_align_opts &opts,
+                    wc_map_align_summary *summaries);
   // wall time [ms] of the last completed sweep's map step (the undistortion when fill_outputs does not already form it, the insert's
   // enqueue - its kernel runs behind on the stream -, with map_carve_range the carve, which waits, and, with map_keep_radius, the crop,
   // which waits too).  Not part of last_stage_ms()

@@ -283,6 +283,12 @@ int wc_odom_map_raycast(void *h, const float *xyz, uint64_t n, const double orig
 // LidarOdometry::SaveMap / LoadMap (the canonical state file of host/map_file.h); 1 = done, 0 = refused (nothing touched)
 int wc_odom_map_save(void *h, const char *path) { return path && ((LidarOdometry *)h)->SaveMap(path) ? 1 : 0; }
 int wc_odom_map_load(void *h, const char *path, int merge) { return path && ((LidarOdometry *)h)->LoadMap(path, merge != 0) ? 1 : 0; }
+// LidarOdometry::MergeMapFile: a file of another frame aligned from T_io and merged under the pose found; summaries: n_levels records,
+// coarsest first (may be null); 1 = done, 0 = refused (the map and T_io untouched)
+int wc_odom_map_merge_file(void *h, const char *path, double T_io[12], uint32_t factor, uint32_t n_levels, const wc_map_align_opts *opts,
+                           wc_map_align_summary *summaries) {
+  return path && opts && ((LidarOdometry *)h)->MergeMapFile(path, T_io, factor, n_levels, *opts, summaries) ? 1 : 0;
+}
 // host/map_file.h without a GPU.  encode: the file of n records (vox: n x 40 bytes as wc_map_voxel; mom: n x 9 int64, read with flags
 // bit 0) -> its size in bytes; written when cap is at least that.  decode: wc_map_file::Decode's code (0 = accepted; then *voxel, *flags
 // and *n describe the file, and vox / mom - either may be NULL - receive its records when cap >= n)

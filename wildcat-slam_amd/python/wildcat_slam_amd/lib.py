@@ -811,6 +811,29 @@ def map_ct_step(ne, prior=(0.0, 0.0, 0.0, 0.0), acc=None, min_pivot=1e-9):
     return xi
 
 
+def map_move_state(vox, mom, voxel, T):
+    """wc_map_move_state (needs no GPU): the records of a state (MAP_VOXEL array; mom: (n, 9) int64 or None) of a map of voxel size
+    `voxel`, each moved by the rigid T (3 x 4) as wc_map_merge_moved moves it -> (vox, mom or None, records rejected); a rejected
+    record is all zeros"""
+    vox = np.ascontiguousarray(vox, R.MAP_VOXEL).reshape(-1)
+    n = len(vox)
+    if mom is not None:
+        mom = np.ascontiguousarray(mom, np.int64).reshape(-1, 9)
+        assert len(mom) == n, "one row of nine moment words per record"
+    out = np.zeros(n, R.MAP_VOXEL)
+    out_mom = None if mom is None else np.zeros((n, 9), np.int64)
+    if n == 0:  # (nothing to move; the call itself still checks voxel and T)
+        vox, mom = np.zeros(1, R.MAP_VOXEL), (None if mom is None else np.zeros((1, 9), np.int64))
+    o, om = (out, out_mom) if n else (np.zeros(1, R.MAP_VOXEL), None if mom is None else np.zeros((1, 9), np.int64))
+    T12 = None if T is None else _pose12(T)
+    rej = C.c_uint64(0)
+    rc = load().wc_map_move_state(R.ptr(vox), None if mom is None else R.ptr(mom), C.c_uint64(n), C.c_double(voxel),
+                                  None if T12 is None else R.ptr(T12), R.ptr(o), None if om is None else R.ptr(om), C.byref(rej))
+    if rc != WC_OK:
+        raise WildcatError(rc, "wc_map_move_state refused its arguments")
+    return out, out_mom, int(rej.value)
+
+
 def map_score_top(scores, M, min_hit=0):
     """wc_map_score_top (needs no GPU): the indices of the M best MAP_SCORE records - n_bad == 0 and n_hit >= min_hit; larger n_hit
     first, then the smaller index -> int32 array of the min(M, eligible) indices"""
@@ -1070,6 +1093,25 @@ class PointMap:
     def merge(self, other):
         """this map becomes the map of its own points and other's (wc_map_merge: table to table on the device); other is not modified"""
         self.ctx._ck(self.lib.wc_map_merge(self.ctx.h, self.h, other.h))
+
+    def merge_moved(self, other, T, want_counts=True):
+        """other, a map built in another frame, added to this map under the rigid T (3 x 4: other's frame to this one's), every voxel
+        moved as one Gaussian (wc_map_merge_moved: table to table on the device) -> [voxels applied, points applied, voxels rejected,
+        points rejected], or None without waiting when want_counts is False; other is not modified"""
+        out = (C.c_uint64 * 4)()
+        T12 = None if T is None else _pose12(T)
+        self.ctx._ck(self.lib.wc_map_merge_moved(self.ctx.h, self.h, other.h, None if T12 is None else R.ptr(T12), out if want_counts else None))
+        return [int(x) for x in out] if want_counts else None
+
+    def moved(self, T):
+        """-> a new PointMap of this map's voxel size and flags that holds this map moved by T: an empty map plus merge_moved"""
+        m = PointMap(self.ctx, self.voxel, moments=self.moments)
+        try:
+            m.merge_moved(self, T)
+        except WildcatError:
+            m.close()
+            raise
+        return m
 
     def coarsen(self, factor, moments=None):
         """-> a new PointMap of voxel size float(factor) * voxel that holds this map's voxels gathered factor^3 to one, exactly
@@ -1485,6 +1527,18 @@ class Odometry:
         """a file map_save wrote, absorbed into the map - re-created empty first unless merge (LidarOdometry::LoadMap) -> True, or False
         (the map untouched) without a map, for a file the decoder refuses, another voxel size, or a file without moments with map_surfels on"""
         return bool(self.lib.wc_odom_map_load(self.h, os.fsencode(path), C.c_int(1 if merge else 0)))
+
+    def map_merge_file(self, path, T, factor, n_levels, opts):
+        """a file map_save wrote in ANOTHER frame, aligned to the map from the rough pose T (the file's frame to the map's) through
+        map_relocalize's levels on the file's centroids, then merged under the pose found, every voxel moved as one Gaussian
+        (LidarOdometry::MergeMapFile, wc_map_merge_moved) -> (T (3, 4), [summary dict per level, coarsest first]), or None (the map
+        untouched) where map_load or map_relocalize refuses, or when the alignment ends with termination 2 or under opts.min_used"""
+        n_levels = int(n_levels)
+        T, summ = _pose12(T), (R.MapAlignSummary * max(n_levels, 1))()
+        if not 1 <= n_levels <= 8 or not self.lib.wc_odom_map_merge_file(self.h, os.fsencode(path), R.ptr(T), C.c_uint32(int(factor)),
+                                                                          C.c_uint32(n_levels), C.byref(opts), summ):
+            return None
+        return T.reshape(3, 4), [_summary_dict(s) for s in summ]
 
     def set_map_keep_radius(self, radius):
         """LioConfig::map_keep_radius: after every sweep the map keeps the cube of this half-side around the sensor; 0 = unbounded"""
