@@ -56,6 +56,10 @@ int wc_ctx_set_params(wc_ctx *ctx, const wc_params *params);
  *                      -DWC_DEV_KNOBS build only - the release kernels carry no profiling branch and ignore the option)
  *   fx_merge_min       list length from which the next sweep merges record lists first (default 3)
  *   fx_split           node stage of the default extraction: 0 fused kernel, 1 two kernels, -1 by size
+ *   fx_acc_form        form of the default extraction's first kernel: bit 0 - the per-point part runs per load round, under the loads;
+ *                      bit 1 - records are linked into their lists before their sums exist; 0 - neither (the earlier kernel's order
+ *                      WITHOUT its early first hash probe, which bit 1 replaced: slower than that kernel was); -1 - the library's
+ *                      own choice (both bits; bit 0 alone for sweeps above 2 M points that are not packed).  The layer-2 kernel has bit 1 only.  Every form writes the same bytes
  *   no_bucket_sort     exact path: radix sort instead of the run-binned sort
  *   ex_sync            wc_extract_surfels_finish waits for the stream instead of the sweep's completion ticket
  *   match_pair_serial  wc_match_pair runs its two searches one after the other on the ctx

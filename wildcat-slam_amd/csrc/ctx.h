@@ -39,6 +39,7 @@ struct wc_dev_opts {
   int debug_skip = 0;        // knock-out bits of the default extraction path (results are WRONG; timing runs only)
   int fx_merge_min = 3;      // list length from which the next sweep runs k_fx_merge
   int fx_split = -1;         // node stage of the default extraction: 0 fused, 1 two kernels, -1 by size
+  int fx_acc_form = -1;      // form of k_fx_acc: bit 0 pass A per load round, bit 1 link early; 0 neither (round 6's order without its early hash probe: slower than round 6); -1 the library's choice by size
   int no_bucket_sort = 0;    // exact path: radix sort instead of the run-binned sort
   int ex_sync = 0;           // extraction: finish waits for the stream instead of the completion ticket
   int match_pair_serial = 0; // wc_match_pair runs its searches one after the other on the ctx

@@ -65,6 +65,7 @@ const DevOpt kDevOpts[] = {
     {"debug_skip", "WC_DEBUG_SKIP", &wc_dev_opts::debug_skip, false},
     {"fx_merge_min", "WC_FX_MERGE_MIN", &wc_dev_opts::fx_merge_min, false},
     {"fx_split", "WC_FX_SPLIT", &wc_dev_opts::fx_split, false},
+    {"fx_acc_form", "WC_FX_ACC_FORM", &wc_dev_opts::fx_acc_form, false},
     {"no_bucket_sort", "WC_NO_BUCKET_SORT", &wc_dev_opts::no_bucket_sort, true},
     {"ex_sync", "WC_EX_SYNC", &wc_dev_opts::ex_sync, true},
     {"match_pair_serial", "WC_MATCH_PAIR_SERIAL", &wc_dev_opts::match_pair_serial, true},

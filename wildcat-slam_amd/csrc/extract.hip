@@ -2047,7 +2047,7 @@ int run_pipeline_fast(wc_ctx *ctx) {
     ctx->ex.deferred = true;
     return WC_OK;
   }
-  k_fx_acc<1><<<tiles, kFxThreads, 0, st>>>(A);
+  fx_launch_acc<1>(ctx, tiles, st, A);
   dbg_sync("k_fx_acc<1>");
   ex_mark(ctx, 2);
   if (M.fx_long_lists) k_fx_merge<1><<<std::min<unsigned>(ngrid * 2u, 8192u), 128, 0, st>>>(A);
@@ -2075,7 +2075,7 @@ int fx_tail(wc_ctx *ctx, bool layer2) {
   std::memcpy(&A, ctx->ex.roots_args, sizeof(A));
   ExMemory &M = ctx->ex_mem;
   if (layer2) {
-    k_fx_acc<2><<<ex_fx_tiles(A.pts.n), kFxThreads, 0, st>>>(A);
+    fx_launch_acc<2>(ctx, ex_fx_tiles(A.pts.n), st, A);
     if (M.fx_long_lists2) k_fx_merge<2><<<std::min(8192u, std::max(64u, M.last_splits)), 128, 0, st>>>(A);
     const unsigned g2 = ex_fx_layer2_grid(ex_fx_node_grid(A.pts.n), M.last_splits);
     if (ctx->ex.fx_split) {
@@ -2475,14 +2475,14 @@ extern "C" int wc_extract_surfels_batch_enqueue(wc_ctx *ctx, const wc_sweep_job 
   FxBatch B;
   B.args = (const FxArgs *)d, B.K = Kd, B.flags = dt + 3 * (K + 1);
   B.start = dt;
-  k_fx_acc_b<1><<<s_acc[Kd], kFxThreads, 0, st>>>(B);
+  fx_launch_acc_b<1>(ctx, s_acc[Kd], st, B);
   B.start = dt + (K + 1);
   if (any_merge) k_fx_merge_b<1><<<s_nodes[Kd], 128, 0, st>>>(B);
   k_fx_walk_b<1><<<s_nodes[Kd], 64, 0, st>>>(B);
   k_fx_test_b<1><<<s_nodes[Kd], 64, 0, st>>>(B);
   if (any_l2) {
     B.start = dt;
-    k_fx_acc_b<2><<<s_acc[Kd], kFxThreads, 0, st>>>(B);
+    fx_launch_acc_b<2>(ctx, s_acc[Kd], st, B);
     B.start = dt + 2 * (K + 1);
     if (any_merge) k_fx_merge_b<2><<<s_g2[Kd], 128, 0, st>>>(B);
     k_fx_walk_b<2><<<s_g2[Kd], 64, 0, st>>>(B);

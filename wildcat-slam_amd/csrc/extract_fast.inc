@@ -24,7 +24,11 @@
 //   k_fx_acc<1>    ONE pass over the points: 4 consecutive points per lane, per-lane integer partial sums while the cell
 //                  stays the same, LDS hash of the tile's cells (ds atomics); every cell of the tile becomes ONE 128-byte
 //                  record in HBM (plain stores) that is pushed onto the cell's list in its root's block with ONE atomic
-//                  exchange; roots get a dense index through an insert-only hash table
+//                  exchange; roots get a dense index through an insert-only hash table.  Its phases overlap: the per-point part
+//                  (fx_point) runs per load round while the later rounds are in flight, its results go through LDS to the lane that
+//                  owns four consecutive points; the direct records are linked (fx_link_claim, fx_link_head) as soon as the cell
+//                  codes are known and stored (fx_store) when their sums exist.  Development option fx_acc_form selects the forms
+//                  without either part (k_fx_acc_form<LEVEL, FORM>): every form writes the same bytes
 //   k_fx_nodes<1>  8 lanes per root voxel (lane = layer-1 octant), 8 roots per wavefront: every lane walks the record lists
 //                  of its node in time-bin order - node totals, temporal clusters -, then node tests and cluster PCAs
 //                  (cc:82-126, :12-65), emission into slots + time bins, layer-2 queue, list heads cleaned behind it
@@ -190,20 +194,21 @@ __device__ __forceinline__ void fx_add_cell(unsigned long long *cell, const FxPa
 // WAVE-UNIFORM call (lanes without a record pass active = false): the lanes of a wavefront mostly push cells of the same few
 // root voxels, and same-address atomics of one instruction are expensive - one lane per distinct root does the hash insert
 // and the header update for all of them.
-// The first probe of a root's hash insert, issued EARLY (k_fx_acc, right after the cell codes are known, for the root of every
-// lane's last point - the parent of the partial the lane closes at its end): the atomic's round trip runs beside the partial
-// sums and the cross-lane merge instead of in front of the list-head exchange.  Per lane: the key + 1 (0: none), the slot
-// probed, the value the compare-and-swap found there (held by the lane `lead` that issued it) .
-struct FxEarly {
-  uint32_t key1, s0, found;
+// A push has THREE steps, which k_fx_acc may issue apart (its form bit 1: link early, store late):
+//   fx_link_claim  the wavefront's distinct parents, a leader lane and the smallest bin of each; every leader issues the first probe
+//                  of its root's hash insert (LEVEL 1)
+//   fx_link_head   the leaders finish the claim (further probes are rare), append the roots they created to the dense root list and
+//                  raise the header's smallest bin; every lane exchanges its list head for ridx + 1 and gets `old`
+//   fx_store       the record's fourteen words, `old` among them
+// The link needs the cell code and the record index alone, not the sums: issued as soon as the codes are known, its atomics' round
+// trips run beside pass B and the cross-lane merge.  Nothing reads a list inside k_fx_acc, so a head may name a record that is
+// written later in the same kernel; k_fx_nodes starts behind the kernel boundary.
+struct FxClaim {  // per lane: the leader lane of the lane's parent, the parent's smallest bin, the home slot and what the leader's probe found there
   int lead;
+  uint32_t gmb, s0, found;
 };
 template <int LEVEL>
-__device__ __forceinline__ void fx_push(const FxArgs &A, bool active, unsigned long long code, const FxPart &a, uint32_t sub, uint32_t ridx,
-                                        const FxEarly &E) {
-  const int lane = threadIdx.x & 63;
-  unsigned long long *blk = nullptr;
-  uint32_t oct, bin, pkey;
+__device__ __forceinline__ void fx_code_fields(unsigned long long code, uint32_t &pkey, uint32_t &oct, uint32_t &bin) {
   if (LEVEL == 1) {
     pkey = (uint32_t)(code & 0x3FFFFFFFull) + 1u;
     oct = (uint32_t)(code >> 30) & 7u;
@@ -213,6 +218,12 @@ __device__ __forceinline__ void fx_push(const FxArgs &A, bool active, unsigned l
     oct = (uint32_t)(code >> 28) & 7u;
     bin = (uint32_t)(code >> 31) & 0xFFFFFu;
   }
+}
+template <int LEVEL>
+__device__ __forceinline__ FxClaim fx_link_claim(const FxArgs &A, bool active, unsigned long long code) {
+  const int lane = threadIdx.x & 63;
+  uint32_t oct, bin, pkey;
+  fx_code_fields<LEVEL>(code, pkey, oct, bin);
   // the distinct parents of the wavefront: leader lane and smallest bin of each (registers only)
   int lead = lane;
   uint32_t gmb = bin;
@@ -231,28 +242,37 @@ __device__ __forceinline__ void fx_push(const FxArgs &A, bool active, unsigned l
   // every leader claims / finds its parent's block AT THE SAME TIME (one round trip for the wavefront's parents, not one
   // per parent); the roots created here are appended to the dense root list with one counter atomic per wavefront, whose
   // answer is only awaited after the list heads have been exchanged
+  FxClaim c;
+  c.lead = lead, c.gmb = gmb, c.s0 = 0u, c.found = 0u;
+  if (LEVEL == 1) {
+    c.s0 = fx_hash32(pkey) & A.tr_mask;
+    if (active && lane == lead && !(WC_DBG(A.P, 64))) c.found = atomicCAS(&A.rkey[c.s0], 0u, pkey);
+  }
+  return c;
+}
+// returns whether the lane's record is to be written; old: the list's previous head (the record's word 13)
+template <int LEVEL>
+__device__ __forceinline__ bool fx_link_head(const FxArgs &A, bool active, unsigned long long code, uint32_t sub, uint32_t ridx, const FxClaim &c,
+                                             uint32_t &old) {
+  const int lane = threadIdx.x & 63;
+  unsigned long long *blk = nullptr;
+  uint32_t oct, bin, pkey;
+  fx_code_fields<LEVEL>(code, pkey, oct, bin);
+  const int lead = c.lead;
+  const uint32_t gmb = c.gmb;
   const bool leader = active && lane == lead;
   uint32_t slot = 0xFFFFFFFFu;
   bool created = false;
-  // (the early probe of this lane's key sits in the lane that made it)
-  const uint32_t e_found = (uint32_t)__shfl((int)E.found, E.lead);
-  const bool e_have = LEVEL == 1 && E.key1 != 0u && E.key1 == pkey;
   if (leader) {
     if (LEVEL == 1) {
       if (WC_DBG(A.P, 64)) {
-        slot = fx_hash32(pkey) & A.tr_mask;
+        slot = c.s0;
+      } else if (c.found == 0u || c.found == pkey) {
+        slot = c.s0;
+        created = c.found == 0u;
       } else {
-        uint32_t s = fx_hash32(pkey) & A.tr_mask;
-        int probe = 0;
-        if (e_have) {  // the first probe has been made already
-          if (e_found == 0u || e_found == pkey) {
-            slot = s;  // (a root the early probe created is appended to the root list by k_fx_acc itself, at its end)
-          } else {
-            s = (s + 1u) & A.tr_mask;
-            probe = 1;
-          }
-        }
-        for (; slot == 0xFFFFFFFFu && probe < 64; ++probe) {
+        uint32_t s = (c.s0 + 1u) & A.tr_mask;
+        for (int probe = 1; probe < 64; ++probe) {
           const uint32_t k = atomicCAS(&A.rkey[s], 0u, pkey);
           if (k == 0u || k == pkey) {
             slot = s;
@@ -277,7 +297,7 @@ __device__ __forceinline__ void fx_push(const FxArgs &A, bool active, unsigned l
     atomicMax((uint32_t *)b0 + 2, 0xFFFFFFFFu - gmb);  // smallest bin of the block
   }
   const uint32_t myslot = (uint32_t)__shfl((int)slot, lead);
-  uint32_t old = 0;
+  old = 0u;
   const bool ok = active && myslot != 0xFFFFFFFFu;
   if (ok) {
     blk = (LEVEL == 1 ? A.blk : A.blk2) + (size_t)myslot * kFxBlockW;
@@ -294,8 +314,14 @@ __device__ __forceinline__ void fx_push(const FxArgs &A, bool active, unsigned l
         fx_fallback(A.status, 3);
     }
   }
-  if (!ok) return;
+  return ok;
+}
+// (called by the lanes whose record is to be written only)
+template <int LEVEL>
+__device__ __forceinline__ void fx_store(const FxArgs &A, unsigned long long code, const FxPart &a, uint32_t ridx, uint32_t old) {
   if (WC_DBG(A.P, 16)) return;
+  uint32_t oct, bin, pkey;
+  fx_code_fields<LEVEL>(code, pkey, oct, bin);
   unsigned long long *rec = A.rec + ((size_t)(LEVEL - 1) * A.rec_cap + ridx) * kFxRecW;
   ulonglong2 *r2 = (ulonglong2 *)rec;
   r2[0] = make_ulonglong2((unsigned long long)a.n | ((unsigned long long)bin << 32), (unsigned long long)a.st);
@@ -306,6 +332,108 @@ __device__ __forceinline__ void fx_push(const FxArgs &A, bool active, unsigned l
   r2[5] = make_ulonglong2((unsigned long long)a.ss[5], a.tmin_inv);
   r2[6] = make_ulonglong2(a.tmax_p1, (unsigned long long)old);  // next record of this (node, slot) list, 0 = end
 }
+// the three steps in one place (WAVE-UNIFORM call): the tile's hash cells, the spill pool, and the direct records of a form that
+// links where it stores
+template <int LEVEL>
+__device__ __forceinline__ void fx_push(const FxArgs &A, bool active, unsigned long long code, const FxPart &a, uint32_t sub, uint32_t ridx) {
+  const FxClaim c = fx_link_claim<LEVEL>(A, active, code);
+  uint32_t old;
+  if (fx_link_head<LEVEL>(A, active, code, sub, ridx, c, old)) fx_store<LEVEL>(A, code, a, ridx, old);
+}
+
+// ---- pass A for ONE point: every form of k_fx_acc forms a point's cell code and integer coordinates with these routines ----------
+struct FxPt {
+  unsigned long long code;  // 0: the point is skipped
+  double tmag;              // fma(t - t_lo, 2^s, M): the tick in magic form
+  uint32_t qlx, qly, qlz;   // low words of fma(p - cc, 2^32, M): the high word is M's (|q| < 2^31)
+};
+// voxel index floor(p (1 / vs)); returns whether the point is finite.  The rare coordinate within 1e-6 of a voxel face is divided
+// properly (fx_vox) in a WAVE-UNIFORM block: the fractional part against an ABSOLUTE 1e-6 is wider than fx_vox's own relative band up
+// to |q| ~ 1000, and p (1 / vs) is within 5e-16 |q| of p / vs, i.e. inside the band for every coordinate a float can resolve to a
+// voxel - two compares on a value the floor needs anyway instead of rint + a relative bound.  A non-finite coordinate fails the face
+// test (q - floor(q) is NaN for NaN and for +-inf), so the finite-point rule is looked at in the rare block alone and the common path
+// pays nothing for it.
+__device__ __forceinline__ bool fx_pt_index(const FxArgs &A, double x, double y, double z, int &kx, int &ky, int &kz) {
+  const double qx = x * A.inv_vs, qy = y * A.inv_vs, qz = z * A.inv_vs;
+  const double fx = floor(qx), fy = floor(qy), fz = floor(qz);
+  const double dx = qx - fx, dy = qy - fy, dz = qz - fz;
+  const bool near = !(dx > 1e-6 && dx < 1.0 - 1e-6) || !(dy > 1e-6 && dy < 1.0 - 1e-6) || !(dz > 1e-6 && dz < 1.0 - 1e-6);
+  kx = (int)fx, ky = (int)fy, kz = (int)fz;
+  bool fin = true;
+  if (__ballot(near)) {
+    fin = finite3(x, y, z);  // (a non-finite point needs no index)
+    if (__ballot(fin && near)) {
+      if (fin) kx = fx_vox(x, A.P.vs, A.inv_vs), ky = fx_vox(y, A.P.vs, A.inv_vs), kz = fx_vox(z, A.P.vs, A.inv_vs);
+    }
+  }
+  return fin;
+}
+// key of the root voxel relative to the origin voxel k0 (10 bits per axis)
+__device__ __forceinline__ bool fx_pt_key(int kx, int ky, int kz, int k0x, int k0y, int k0z, uint32_t &key) {
+  const int rx = kx - k0x + 512, ry = ky - k0y + 512, rz = kz - k0z + 512;
+  key = (uint32_t)rx | ((uint32_t)ry << 10) | ((uint32_t)rz << 20);
+  return (unsigned)rx < 1024u && (unsigned)ry < 1024u && (unsigned)rz < 1024u;
+}
+// octant, tick, time bin, cell code and the magic-form coordinates.  have: the point exists and is finite.  LEVEL 2: split / base2 are
+// the queued layer-1 nodes of the point's root and where their blocks start.  No early exit: the range flags are raised by the caller,
+// once (with the checks as exits the compiler ran the four chains of a lane one after the other).
+// Integer moments from fp64 instructions (round 5).  With M = 1.5 x 2^52, fma(a, 2^32, M) holds rint(a 2^32) in the low mantissa
+// bits of a double whose exponent is fixed: its BIT PATTERN minus M's is that integer.  So a coordinate q (units of 2^-32 m, |q| <
+// 2^31), a tick (< 2^41) and - with M2 = 1.5 x 2^72 - a product q_i q_j rounded to the 2^20 grid (units of 2^-64 m^2: the 2^-44 m^2
+// of the records) are each ONE fma, and their exact sums are 64-bit integer additions of the bit patterns: n x bits(M) is taken off
+// the high words when a partial closes (fx_fix).
+template <int LEVEL>
+__device__ __forceinline__ FxPt fx_pt_code(const FxArgs &A, bool have, double x, double y, double z, double t, int kx, int ky, int kz, int k0x,
+                                           int k0y, int k0z, uint32_t split, uint32_t base2, bool &bad_key, bool &bad_time) {
+  const ExParams &P = A.P;
+  uint32_t key;
+  const bool key_ok = fx_pt_key(kx, ky, kz, k0x, k0y, k0z, key);
+  // octants exactly as CutOctoTree forms them (cc:147-165): strict >, child centre = centre +- quarter in float
+  // (0.5 + k) vs is exact in fp64 (the voxel size is a float - 24 significant bits - and 0.5 + k a handful), so is the fused form
+  // k vs + vs / 2: the same value, one instruction less per axis
+  const double cx = fma((double)kx, (double)P.vs_f, 0.5 * (double)P.vs_f), cy = fma((double)ky, (double)P.vs_f, 0.5 * (double)P.vs_f),
+               cz = fma((double)kz, (double)P.vs_f, 0.5 * (double)P.vs_f);
+  const int bx = x > cx, by = y > cy, bz = z > cz;
+  const uint32_t o1 = (uint32_t)(4 * bx + 2 * by + bz);
+  // time: tick = (t - t_lo) 2^s (exact for stamps on a 2^-s grid), bin = floor((t - t_lo) / w)
+  const double trel = t - A.t_lo;
+  const double tm = fma(trel, A.tick, kFxMagic);  // (tick = 2^s: the product is exact, the fma rounds it to an integer once)
+  const bool time_ok = tm >= kFxMagic && tm < kFxMagic + 2199023255552.0;  // tick in [0, 2^41)
+  bad_key = bad_key || (have && !key_ok);
+  bad_time = bad_time || (have && key_ok && !time_ok);
+  bool use = have && key_ok && time_ok;
+  const uint32_t bin = (uint32_t)(use ? trel * A.inv_w : 0.0);
+  unsigned long long c;
+  if (LEVEL == 1) {
+    c = (unsigned long long)key | ((unsigned long long)o1 << 30) | ((unsigned long long)bin << 33) | (1ull << 63);
+  } else {
+    const float q0 = P.vs_f / 4;
+    use = use && ((split >> o1) & 1u);
+    const uint32_t qn = base2 + (uint32_t)__popc(split & ((1u << o1) - 1u));
+    const double c1x = cx + (double)((float)(2 * bx - 1) * q0), c1y = cy + (double)((float)(2 * by - 1) * q0),
+                 c1z = cz + (double)((float)(2 * bz - 1) * q0);
+    const uint32_t o2 = (uint32_t)(4 * (x > c1x) + 2 * (y > c1y) + (z > c1z));
+    c = (unsigned long long)qn | ((unsigned long long)o2 << 28) | ((unsigned long long)bin << 31) | (1ull << 63);
+  }
+  // coordinates relative to the voxel centre ITSELF: (0.5 + k) vs is exact (above), a multiple of 2^-25 m for a voxel size in
+  // [0.5, 1); p is a float widened, so p - centre is exact as well and (p - centre) 2^32 an integer for |p| >= 2^-8 m (the fma rounds
+  // the rest)
+  FxPt o;
+  o.code = use ? c : 0ull;
+  o.tmag = tm;
+  const double mx = fma(x - cx, A.qs, kFxMagic), my = fma(y - cy, A.qs, kFxMagic), mz = fma(z - cz, A.qs, kFxMagic);
+  // (the mantissa is 2^51 + q: its low word is q mod 2^32, its high word M's for q >= 0 and M's - 1 for q < 0 - pass B rebuilds the
+  // double from the low word alone; points with code 0 are skipped there: whatever these hold)
+  o.qlx = (uint32_t)__double_as_longlong(mx), o.qly = (uint32_t)__double_as_longlong(my), o.qlz = (uint32_t)__double_as_longlong(mz);
+  return o;
+}
+// the whole of pass A for one point of the layer-0/1 pass.  in_range: the point's index is below the sweep's point count
+__device__ __forceinline__ FxPt fx_point(const FxArgs &A, bool in_range, double x, double y, double z, double t, int k0x, int k0y, int k0z,
+                                         bool &bad_key, bool &bad_time) {
+  int kx, ky, kz;
+  const bool fin = fx_pt_index(A, x, y, z, kx, ky, kz);
+  return fx_pt_code<1>(A, in_range && fin, x, y, z, t, kx, ky, kz, k0x, k0y, k0z, 0u, 0u, bad_key, bad_time);
+}
 
 // ---- the streaming pass ---------------------------------------------------------------------------------------------------
 // the raw values of a tile as its threads fetch them (lane = point, four rounds): held in registers between the request and the
@@ -314,6 +442,9 @@ struct FxRaw {
   float x[kFxPts], y[kFxPts], z[kFxPts];
   double t[kFxPts];
 };
+// FULL: the tile lies inside the sweep (a wave-uniform test of the caller's) - its loads are unconditional, so that whoever uses the
+// rounds one after the other waits for a COUNT of outstanding loads, not for all of them (a branch around a load drains the counter)
+template <bool FULL = false>
 __device__ __forceinline__ FxRaw fx_acc_load(const FxArgs &A, const uint32_t bid) {
   FxRaw r;
   const uint64_t tb = (uint64_t)bid * kFxTile, n = A.pts.n;
@@ -321,21 +452,30 @@ __device__ __forceinline__ FxRaw fx_acc_load(const FxArgs &A, const uint32_t bid
   for (int it = 0; it < kFxPts; ++it) {
     const uint64_t i = tb + (uint64_t)it * kFxThreads + threadIdx.x;
     r.x[it] = r.y[it] = r.z[it] = 0.f, r.t[it] = 0.0;
-    if (i < n) {
+    if (FULL || i < n) {
       // (Round 5 tried ONE 16-byte load for x, y, z, pad of a 48-byte record + the stamp at +24 - two requests per point instead of
       // four: k_fx_acc<1> 19.7 - 21.2 -> 21.5 - 23 us at C2, alternating builds on one box.  Element-wise loads stay.)
       const float *f = (const float *)((const char *)A.pts.xyz + i * A.pts.xyz_stride);
       r.x[it] = f[0], r.y[it] = f[1], r.z[it] = f[2];
       r.t[it] = load_t(A.pts, i);
     }
+    // (issue order = round order: the scheduler otherwise moves the stamps' loads behind the coordinates' and round 0 waits for round 3's)
+    if (FULL) __builtin_amdgcn_sched_barrier(0);
   }
   return r;
 }
 
-template <int LEVEL>
+// FORM (development option fx_acc_form; kFxAccForm is what the library runs): bit 0 - LEVEL 1, staged path: pass A per load round,
+// under the loads; bit 1 - the direct records are linked as soon as the codes are known and stored where the sums exist.  0 is the
+// order of rounds 2 - 6 - all loads, transposition, pass A, pass B, link + store - WITHOUT round 5's early first hash probe (FxEarly,
+// which bit 1 replaced): nothing of the link goes out before the sums exist, so form 0 is slower than the kernel of round 6.  Every form writes the same bytes.
+constexpr int kFxAccForm = 3;
+template <int LEVEL, int FORM>
 __device__ __forceinline__ void fx_acc_body(const FxArgs &A, const uint32_t bid) {  // bid: this workgroup's tile of ITS sweep
-  // LDS: first the staging area of the tile's points (20 KB), then - the points are in registers - the tile's cell hash
-  // (28 KB) in the same bytes: 28 KB per workgroup = five workgroups per CU, the whole grid of a 1 M-point sweep resident
+  constexpr bool kRounds = LEVEL == 1 && (FORM & 1) != 0, kLinkEarly = (FORM & 2) != 0;
+  // LDS: first the staging area of the tile's points (20 KB of raw values, or 28 KB of pass A's results where pass A runs per load
+  // round), then - the points are in registers - the tile's cell hash (28 KB) in the same bytes: 28 KB per workgroup = five
+  // workgroups per CU, the whole grid of a 1 M-point sweep resident
   __shared__ unsigned long long lds_raw[kFxLds * 14];
   unsigned long long *h_key = lds_raw;                                        // [kFxLds]
   unsigned long long(*h_rec)[13] = (unsigned long long(*)[13])(lds_raw + kFxLds);  // [kFxLds][13]
@@ -346,8 +486,69 @@ __device__ __forceinline__ void fx_acc_body(const FxArgs &A, const uint32_t bid)
   const uint64_t n = A.pts.n;
   const uint64_t base = ((uint64_t)bid * kFxThreads + tid) * kFxPts;
   static_assert(kFxPts == 4, "the LDS transposition reads four points per lane");
-  // the tile's loads go out FIRST (in front of point 0's and the divisions behind it)
-  const bool direct = A.fmt == 2u && ((uint64_t)bid + 1u) * kFxTile <= n;  // wave-uniform
+  const bool full = ((uint64_t)bid + 1u) * kFxTile <= n;  // wave-uniform
+  const bool direct = A.fmt == 2u && full;
+  // ---- pass A: cell code, time tick and integer coordinates of the lane's four points (code 0: the point is skipped): fx_point ----
+  unsigned long long code[kFxPts];
+  double tmag[kFxPts];
+  uint32_t qlx[kFxPts], qly[kFxPts], qlz[kFxPts];
+  bool bad_key = false, bad_time = false;
+  if (kRounds && !direct) {
+    // PASS A PER LOAD ROUND.  Pass A needs one point at a time, not the lane-owns-four-consecutive-points layout of pass B and the
+    // scan: the loads stay lane = point in four rounds, all issued at once, and the lane runs fx_point on round r's point as soon as
+    // round r has returned - the SIMDs work while the memory system serves the later rounds.  The RESULTS (28 bytes per point: code,
+    // tick, three low words; struct of arrays) are transposed through LDS instead of the raw values (20 bytes): exactly the bytes of
+    // the cell hash, which takes them over behind the same barriers as before.
+    static_assert(kFxTile * 28 == kFxLds * 14 * 8, "the staged results fill the hash area exactly");
+    unsigned long long *s_code = lds_raw;                    // [kFxTile]
+    double *s_tm = (double *)(lds_raw + kFxTile);          // [kFxTile]
+    uint32_t *s_qx = (uint32_t *)(lds_raw + 2 * kFxTile), *s_qy = s_qx + kFxTile, *s_qz = s_qy + kFxTile;
+    // the key origin's load goes out in front of the tile's: its voxel is needed before round 0
+    double x0, y0, z0;
+    load_xyz(A.pts, 0, x0, y0, z0);
+    // (one copy of the rounds per kind of tile: joined in front of the rounds, the full tile's registers would meet the partial
+    // tile's guarded ones and the compiler waits for the loads where it merges them)
+    auto rounds = [&](auto full_tag) -> bool {
+      constexpr bool kFull = decltype(full_tag)::value;
+      const FxRaw raw = fx_acc_load<kFull>(A, bid);
+      if (!finite3(x0, y0, z0)) ex_origin(A.pts, x0, y0, z0);  // (wave-uniform, rare)
+      const int k0x = fx_vox(x0, P.vs, A.inv_vs), k0y = fx_vox(y0, P.vs, A.inv_vs), k0z = fx_vox(z0, P.vs, A.inv_vs);
+      if (WC_DBG(P, 4)) {  // profiling experiment: loads only
+        double sacc = 0;
+#pragma unroll
+        for (int j = 0; j < kFxPts; ++j) sacc += (double)raw.x[j] + (double)raw.y[j] + (double)raw.z[j] + raw.t[j];
+        if (sacc == 1.2345) h_key[tid] = 1ull;
+        return false;
+      }
+      const uint64_t tb = (uint64_t)bid * kFxTile;
+#pragma unroll
+      for (int it = 0; it < kFxPts; ++it) {
+        const uint32_t i = (uint32_t)it * kFxThreads + (uint32_t)tid;
+        const FxPt p = fx_point(A, kFull || tb + i < n, (double)raw.x[it], (double)raw.y[it], (double)raw.z[it], raw.t[it], k0x, k0y, k0z, bad_key,
+                                bad_time);
+        s_code[i] = p.code, s_tm[i] = p.tmag;
+        s_qx[i] = p.qlx, s_qy[i] = p.qly, s_qz[i] = p.qlz;
+      }
+      return true;
+    };
+    if (!(full ? rounds(std::true_type{}) : rounds(std::false_type{}))) return;
+    __syncthreads();
+    {  // the lane's four consecutive points: 16-byte LDS reads
+      const ulonglong2 c01 = ((const ulonglong2 *)s_code)[2 * tid], c23 = ((const ulonglong2 *)s_code)[2 * tid + 1];
+      const double2 t01 = ((const double2 *)s_tm)[2 * tid], t23 = ((const double2 *)s_tm)[2 * tid + 1];
+      const uint4 vx = ((const uint4 *)s_qx)[tid], vy = ((const uint4 *)s_qy)[tid], vz = ((const uint4 *)s_qz)[tid];
+      code[0] = c01.x, code[1] = c01.y, code[2] = c23.x, code[3] = c23.y;
+      tmag[0] = t01.x, tmag[1] = t01.y, tmag[2] = t23.x, tmag[3] = t23.y;
+      qlx[0] = vx.x, qlx[1] = vx.y, qlx[2] = vx.z, qlx[3] = vx.w;
+      qly[0] = vy.x, qly[1] = vy.y, qly[2] = vy.z, qly[3] = vy.w;
+      qlz[0] = vz.x, qlz[1] = vz.y, qlz[2] = vz.z, qlz[3] = vz.w;
+    }
+    __syncthreads();  // every lane has its points: the staging bytes become the (empty) cell hash
+    for (int i = tid; i < kFxLds * 14; i += kFxThreads) lds_raw[i] = 0ull;
+    __syncthreads();
+  } else {
+  // the order of rounds 2 - 6 (LEVEL 2: its per-point hash look-ups are loads of their own and would drain the tile's in order; packed
+  // points: no staging at all).  The tile's loads go out FIRST (in front of point 0's and the divisions behind it)
   FxRaw raw;
   float4 da = make_float4(0.f, 0.f, 0.f, 0.f), db = da, dc = da;
   double2 dt01 = make_double2(0.0, 0.0), dt23 = dt01;
@@ -364,7 +565,6 @@ __device__ __forceinline__ void fx_acc_body(const FxArgs &A, const uint32_t bid)
   // (fx_vox = floor(p / vs) by construction - the product with 1 / vs decides unless it lies within 1e-9 of an integer - without the
   // three divisions of vox(), ~35 instructions of every wavefront for a value all wavefronts share)
   int k0x = fx_vox(x0, P.vs, A.inv_vs), k0y = fx_vox(y0, P.vs, A.inv_vs), k0z = fx_vox(z0, P.vs, A.inv_vs);
-  const float q0 = P.vs_f / 4;
 
   // the tile's points: coalesced loads (lane = point, four rounds: fx_acc_load) into LDS, then every lane takes FOUR CONSECUTIVE
   // points (a lane that reads its own 4 x 48 bytes straight from HBM runs at half the rate: 64 scattered 12-byte pieces per
@@ -410,69 +610,11 @@ __device__ __forceinline__ void fx_acc_body(const FxArgs &A, const uint32_t bid)
     if (sacc == 1.2345) h_key[tid] = 1ull;
     return;
   }
-  auto flush_lds = [&](unsigned long long code, const FxPart &a) -> bool {
-    uint32_t s = fx_hash32((uint32_t)code ^ (uint32_t)(code >> 29)) & (kFxLds - 1);
-    for (int probe = 0; probe < kFxLdsProbe; ++probe) {
-      const unsigned long long old = atomicCAS(&h_key[s], 0ull, code);
-      if (old == 0ull || old == code) {
-        fx_add_cell(&h_rec[s][0], a);
-        return true;
-      }
-      s = (s + 1) & (kFxLds - 1);
-    }
-    return false;  // the tile has more cells than its hash holds (within the probe limit): the caller spills the partial
-  };
-
-  // ---- pass A: cell code, time tick and integer coordinates of the lane's four points (code 0: the point is skipped) ----
-  // Integer moments from fp64 instructions (round 5).  With M = 1.5 x 2^52, fma(a, 2^32, M) holds rint(a 2^32) in the low mantissa
-  // bits of a double whose exponent is fixed: its BIT PATTERN minus M's is that integer.  So a coordinate q (units of 2^-32 m, |q| <
-  // 2^31), a tick (< 2^41) and - with M2 = 1.5 x 2^72 - a product q_i q_j rounded to the 2^20 grid (units of 2^-64 m^2: the 2^-44 m^2
-  // of the records) are each ONE fma, and their exact sums are 64-bit integer additions of the bit patterns: n x bits(M) is taken off
-  // the high words when a partial closes (fx_fix).  Was: v_rndne + v_cvt per value, a 32 x 32 -> 64-bit multiply-add (quarter rate),
-  // a 64-bit shift and an add per product - ~85 instruction slots per point in pass B, now ~25.  The products are rounded to
-  // nearest-even where the integer form rounded half up: deterministic per point either way, so the sums stay order independent.
-  unsigned long long code[kFxPts];
-  double tmag[kFxPts];                                // fma(t - t_lo, 2^s, M): the tick in magic form
-  uint32_t qlx[kFxPts], qly[kFxPts], qlz[kFxPts];    // low words of fma(p - cc, 2^32, M): the high word is M's (|q| < 2^31)
-  // (no branch inside the loop of the four points: with the range checks as early exits the compiler ran the four dependent
-  // chains one after the other - 6.2 k of the workgroup's 26 k clocks; the flags are raised once, behind the loop)
-  bool bad_key = false, bad_time = false;
+  // voxel indices first (the four chains of a lane side by side), then - LEVEL 2 - the look-ups, then the codes
   int kxs[kFxPts], kys[kFxPts], kzs[kFxPts];
-  // the point is finite; one that is not is skipped like a point behind the sweep's end: no key, no flag.  Looked at only in the rare
-  // block below: a non-finite coordinate fails the face test there (q - floor(q) is NaN for NaN and for +-inf), so a wavefront whose
-  // points all pass it has none, and the common path pays nothing for the rule
   bool fin[kFxPts];
 #pragma unroll
-  for (int j = 0; j < kFxPts; ++j) fin[j] = true;
-  {  // voxel indices: floor(p (1 / vs)); the rare coordinate within 1e-9 of a voxel face is divided properly, in ONE block
-    // behind the loop (fx_vox)
-    bool near = false;
-#pragma unroll
-    for (int j = 0; j < kFxPts; ++j) {
-      // (the fractional part against an ABSOLUTE 1e-6 - wider than fx_vox's own relative band up to |q| ~ 1000, and p (1 / vs) is
-      // within 5e-16 |q| of p / vs, i.e. inside the band for every coordinate a float can resolve to a voxel: two compares on a value the floor needs anyway instead of rint + a relative bound; NaN is "near")
-      const double qx = px[j] * A.inv_vs, qy = py[j] * A.inv_vs, qz = pz[j] * A.inv_vs;
-      const double fx = floor(qx), fy = floor(qy), fz = floor(qz);
-      const double dx = qx - fx, dy = qy - fy, dz = qz - fz;
-      near = near || !(dx > 1e-6 && dx < 1.0 - 1e-6) || !(dy > 1e-6 && dy < 1.0 - 1e-6) || !(dz > 1e-6 && dz < 1.0 - 1e-6);
-      kxs[j] = (int)fx, kys[j] = (int)fy, kzs[j] = (int)fz;
-    }
-    if (__ballot(near)) {
-      bool redo = false;  // a FINITE point near a face (a non-finite point needs no index)
-#pragma unroll
-      for (int j = 0; j < kFxPts; ++j) {
-        const double qx = px[j] * A.inv_vs, qy = py[j] * A.inv_vs, qz = pz[j] * A.inv_vs;
-        const double dx = qx - floor(qx), dy = qy - floor(qy), dz = qz - floor(qz);
-        fin[j] = finite3(px[j], py[j], pz[j]);
-        redo = redo || (fin[j] && (!(dx > 1e-6 && dx < 1.0 - 1e-6) || !(dy > 1e-6 && dy < 1.0 - 1e-6) || !(dz > 1e-6 && dz < 1.0 - 1e-6)));
-      }
-      if (__ballot(redo)) {
-#pragma unroll
-        for (int j = 0; j < kFxPts; ++j)
-          if (fin[j]) kxs[j] = fx_vox(px[j], P.vs, A.inv_vs), kys[j] = fx_vox(py[j], P.vs, A.inv_vs), kzs[j] = fx_vox(pz[j], P.vs, A.inv_vs);
-      }
-    }
-  }
+  for (int j = 0; j < kFxPts; ++j) fin[j] = fx_pt_index(A, px[j], py[j], pz[j], kxs[j], kys[j], kzs[j]);
   if (!finite3(x0, y0, z0)) {  // (wave-uniform; here, behind the tile's loads, not in front of them)
     ex_origin(A.pts, x0, y0, z0);
     k0x = fx_vox(x0, P.vs, A.inv_vs), k0y = fx_vox(y0, P.vs, A.inv_vs), k0z = fx_vox(z0, P.vs, A.inv_vs);
@@ -481,14 +623,17 @@ __device__ __forceinline__ void fx_acc_body(const FxArgs &A, const uint32_t bid)
   // looked up TOGETHER (hash probe, then the root's header: two round trips for the lane; one root after the other - a sweep in
   // firing order has four different ones - was up to eight, and most of this launch)
   uint32_t split4[kFxPts], base4[kFxPts];
+#pragma unroll
+  for (int j = 0; j < kFxPts; ++j) split4[j] = base4[j] = 0u;
   if (LEVEL == 2) {
     uint32_t key1[kFxPts], slot4[kFxPts], found4[kFxPts];
     bool ok4[kFxPts];
 #pragma unroll
     for (int j = 0; j < kFxPts; ++j) {
-      const int rx = kxs[j] - k0x + 512, ry = kys[j] - k0y + 512, rz = kzs[j] - k0z + 512;
-      ok4[j] = base + j < n && fin[j] && (unsigned)rx < 1024u && (unsigned)ry < 1024u && (unsigned)rz < 1024u;
-      key1[j] = ((uint32_t)rx | ((uint32_t)ry << 10) | ((uint32_t)rz << 20)) + 1u;
+      uint32_t key;
+      const bool key_ok = fx_pt_key(kxs[j], kys[j], kzs[j], k0x, k0y, k0z, key);
+      ok4[j] = base + j < n && fin[j] && key_ok;
+      key1[j] = key + 1u;
       slot4[j] = fx_hash32(key1[j]) & A.tr_mask;
     }
 #pragma unroll
@@ -518,78 +663,27 @@ __device__ __forceinline__ void fx_acc_body(const FxArgs &A, const uint32_t bid)
   }
 #pragma unroll
   for (int j = 0; j < kFxPts; ++j) {
-    const bool have = base + j < n && fin[j];
-    const double x = px[j], y = py[j], z = pz[j], t = pt[j];
-    const int kx = kxs[j], ky = kys[j], kz = kzs[j];
-    const int rx = kx - k0x + 512, ry = ky - k0y + 512, rz = kz - k0z + 512;
-    const bool key_ok = (unsigned)rx < 1024u && (unsigned)ry < 1024u && (unsigned)rz < 1024u;
-    const uint32_t key = (uint32_t)rx | ((uint32_t)ry << 10) | ((uint32_t)rz << 20);
-    // octants exactly as CutOctoTree forms them (cc:147-165): strict >, child centre = centre +- quarter in float
-    // (0.5 + k) vs is exact in fp64 (above), so is the fused form k vs + vs / 2: the same value, one instruction less per axis
-    const double cx = fma((double)kx, (double)P.vs_f, 0.5 * (double)P.vs_f), cy = fma((double)ky, (double)P.vs_f, 0.5 * (double)P.vs_f),
-                 cz = fma((double)kz, (double)P.vs_f, 0.5 * (double)P.vs_f);
-    const int bx = x > cx, by = y > cy, bz = z > cz;
-    const uint32_t o1 = (uint32_t)(4 * bx + 2 * by + bz);
-    // time: tick = (t - t_lo) 2^s (exact for stamps on a 2^-s grid), bin = floor((t - t_lo) / w)
-    const double trel = t - A.t_lo;
-    const double tm = fma(trel, A.tick, kFxMagic);  // (tick = 2^s: the product is exact, the fma rounds it to an integer once)
-    const bool time_ok = tm >= kFxMagic && tm < kFxMagic + 2199023255552.0;  // tick in [0, 2^41)
-    bad_key = bad_key || (have && !key_ok);
-    bad_time = bad_time || (have && key_ok && !time_ok);
-    bool use = have && key_ok && time_ok;
-    const uint32_t bin = (uint32_t)(use ? trel * A.inv_w : 0.0);
-    unsigned long long c;
-    if (LEVEL == 1) {
-      c = (unsigned long long)key | ((unsigned long long)o1 << 30) | ((unsigned long long)bin << 33) | (1ull << 63);
-    } else {
-      use = use && ((split4[j] >> o1) & 1u);
-      const uint32_t qn = base4[j] + (uint32_t)__popc(split4[j] & ((1u << o1) - 1u));
-      const double c1x = cx + (double)((float)(2 * bx - 1) * q0), c1y = cy + (double)((float)(2 * by - 1) * q0),
-                   c1z = cz + (double)((float)(2 * bz - 1) * q0);
-      const uint32_t o2 = (uint32_t)(4 * (x > c1x) + 2 * (y > c1y) + (z > c1z));
-      c = (unsigned long long)qn | ((unsigned long long)o2 << 28) | ((unsigned long long)bin << 31) | (1ull << 63);
-    }
-    // coordinates relative to the voxel centre ITSELF (round 5; rounds 2 - 4 rounded it to 1/1024 m first: three instructions per
-    // axis for nothing).  The voxel size is a float - 24 significant bits - and 0.5 + k a handful: their product (0.5 + k) vs is EXACT
-    // in fp64, a multiple of 2^-25 m for a voxel size in [0.5, 1); p is a float widened, so p - centre is exact as well and
-    // (p - centre) 2^32 an integer for |p| >= 2^-8 m (the fma rounds the rest)
-    const double ccx = cx, ccy = cy, ccz = cz;  // (exact: see the note on the reference point below)
-    code[j] = use ? c : 0ull;
-    tmag[j] = tm;
-    const double mx = fma(x - ccx, A.qs, kFxMagic), my = fma(y - ccy, A.qs, kFxMagic), mz = fma(z - ccz, A.qs, kFxMagic);
-    // (the mantissa is 2^51 + q: its low word is q mod 2^32, its high word M's for q >= 0 and M's - 1 for q < 0 - pass B rebuilds the
-    // double from the low word alone; points with code 0 are skipped there: whatever these hold)
-    qlx[j] = (uint32_t)__double_as_longlong(mx), qly[j] = (uint32_t)__double_as_longlong(my), qlz[j] = (uint32_t)__double_as_longlong(mz);
+    const FxPt p = fx_pt_code<LEVEL>(A, base + j < n && fin[j], px[j], py[j], pz[j], pt[j], kxs[j], kys[j], kzs[j], k0x, k0y, k0z, split4[j], base4[j],
+                                     bad_key, bad_time);
+    code[j] = p.code, tmag[j] = p.tmag;
+    qlx[j] = p.qlx, qly[j] = p.qly, qlz[j] = p.qlz;
+  }
   }
   if (bad_key) raise_flag(A.status, kFlagKeyRange);
   if (bad_time) raise_flag(A.status, kFlagTimeRange);
-  // early first probe of the root hash for the parent of every lane's last point (see FxEarly), if the wavefront has at most four
-  // distinct ones (a sweep with run structure: one or two)
-  FxEarly early, no_early;
-  no_early.key1 = 0u, no_early.s0 = 0u, no_early.found = 0u, no_early.lead = threadIdx.x & 63;
-  early = no_early;
-  if (LEVEL == 1) {
-    unsigned long long lc = 0ull;
-#pragma unroll
-    for (int j = 0; j < kFxPts; ++j) lc = code[j] ? code[j] : lc;
-    const uint32_t pk = lc ? (uint32_t)(lc & 0x3FFFFFFFull) + 1u : 0u;
-    unsigned long long todo = __ballot(pk != 0u);
-    int lead = threadIdx.x & 63, rounds = 0;
-    while (todo && rounds < 4) {
-      const int first = __ffsll((long long)todo) - 1;
-      const uint32_t k0 = (uint32_t)__shfl((int)pk, first);
-      const bool mine = pk != 0u && pk == k0;
-      if (mine) lead = first;
-      todo &= ~__ballot(mine);
-      ++rounds;
+  auto flush_lds = [&](unsigned long long code, const FxPart &a) -> bool {
+    uint32_t s = fx_hash32((uint32_t)code ^ (uint32_t)(code >> 29)) & (kFxLds - 1);
+    for (int probe = 0; probe < kFxLdsProbe; ++probe) {
+      const unsigned long long old = atomicCAS(&h_key[s], 0ull, code);
+      if (old == 0ull || old == code) {
+        fx_add_cell(&h_rec[s][0], a);
+        return true;
+      }
+      s = (s + 1) & (kFxLds - 1);
     }
-    if (!todo && !(WC_DBG(P, 64))) {
-      early.key1 = pk;
-      early.lead = lead;
-      early.s0 = fx_hash32(pk) & A.tr_mask;
-      if (pk != 0u && (int)(threadIdx.x & 63) == lead) early.found = atomicCAS(&A.rkey[early.s0], 0u, pk);
-    }
-  }
+    return false;  // the tile has more cells than its hash holds (within the probe limit): the caller spills the partial
+  };
+
   // A partial sum is closed where the cell changes inside the lane (before point j = 1..3) and at the end of the lane (its
   // open partial, merged with the neighbouring lanes' below).  Few closings in a wavefront - a sweep with run structure -
   // become records in HBM right away (slot = rank among the wavefront's closings of that class: no atomics, no LDS); many
@@ -597,21 +691,67 @@ __device__ __forceinline__ void fx_acc_body(const FxArgs &A, const uint32_t bid)
   const int lane = tid & 63, wave = tid >> 6;
   const unsigned long long lt_mask = (1ull << lane) - 1ull;
   bool bnd[kFxPts];
+  unsigned long long ccode[kFxPts];  // class j < 3: the cell the lane closes in front of point j + 1; class 3: the lane's last cell
   {
     unsigned long long open = 0ull;
 #pragma unroll
     for (int j = 0; j < kFxPts; ++j) {
       bnd[j] = code[j] != 0ull && open != 0ull && code[j] != open;
+      if (j) ccode[j - 1] = open;
       if (code[j] != 0ull) open = code[j];
     }
+    ccode[kFxPts - 1] = open;
+  }
+  // the run tails: the last lane of a run of equal last cells inside its row of 16 lanes (the segmented scan below sums the run into
+  // it).  From the codes alone: the lane to the right in the row (row_shl:1; the row's last lane sees 0)
+  bool tail;
+  {
+    const unsigned long long mycode = ccode[kFxPts - 1];
+    const uint32_t nlo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)mycode, 0x101, 0xF, 0xF, true);
+    const uint32_t nhi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(mycode >> 32), 0x101, 0xF, 0xF, true);
+    const unsigned long long nextc = (unsigned long long)nlo | ((unsigned long long)nhi << 32);
+    tail = mycode != 0ull && ((lane & 15) == 15 || nextc != mycode);
   }
   const uint32_t rec0 = bid * (uint32_t)kFxRecTile + (uint32_t)kFxLds + (uint32_t)wave * 4u * (uint32_t)kFxDirect;
+  auto direct_ridx = [&](int cls, unsigned long long mclass) -> uint32_t {  // slot = rank among the wavefront's closings of the class
+    return rec0 + (uint32_t)cls * (uint32_t)kFxDirect + (uint32_t)__popcll(mclass & lt_mask);
+  };
+  // THE route decision, in one place for the link and for the store: a class with at most kFxDirect closings in the wavefront
+  // writes its records straight to HBM (mclass: the wavefront's closings of the class, not empty)
+  auto direct_route = [](unsigned long long mclass) -> bool { return __popcll(mclass) <= kFxDirect; };
+  // LINK EARLY (form bit 1): every class that takes the direct route is linked here, where its codes and record indices are known -
+  // first the claims of all classes (one round trip for their hash probes), then the heads; the records follow from close_partial
+  uint32_t l_old[kFxPts];
+  bool l_ok[kFxPts];
+#pragma unroll
+  for (int cls = 0; cls < kFxPts; ++cls) l_old[cls] = 0u, l_ok[cls] = false;
+  if (kLinkEarly && !(WC_DBG(P, 2))) {
+    FxClaim claim[kFxPts];
+#pragma unroll
+    for (int cls = 0; cls < kFxPts; ++cls) {
+      const bool closing = cls < 3 ? bnd[cls + 1] : tail;
+      const unsigned long long mclass = __ballot(closing);
+      if (mclass && direct_route(mclass)) claim[cls] = fx_link_claim<LEVEL>(A, closing, ccode[cls] & 0x7FFFFFFFFFFFFFFFull);
+    }
+#pragma unroll
+    for (int cls = 0; cls < kFxPts; ++cls) {
+      const bool closing = cls < 3 ? bnd[cls + 1] : tail;
+      const unsigned long long mclass = __ballot(closing);
+      if (mclass && direct_route(mclass))
+        l_ok[cls] = fx_link_head<LEVEL>(A, closing, ccode[cls] & 0x7FFFFFFFFFFFFFFFull, sub, direct_ridx(cls, mclass), claim[cls], l_old[cls]);
+    }
+  }
   // WAVE-UNIFORM: `closing` marks the lanes that close a partial of class cls now
   auto close_partial = [&](int cls, bool closing, unsigned long long c, const FxPart &a) {
     const unsigned long long mclass = __ballot(closing);
     if (!mclass || (WC_DBG(P, 2))) return;
-    if (__popcll(mclass) <= kFxDirect) {
-      fx_push<LEVEL>(A, closing, c & 0x7FFFFFFFFFFFFFFFull, a, sub, rec0 + (uint32_t)cls * (uint32_t)kFxDirect + (uint32_t)__popcll(mclass & lt_mask), cls == 3 ? early : no_early);
+    if (direct_route(mclass)) {
+      const uint32_t ridx = direct_ridx(cls, mclass);
+      if (kLinkEarly) {
+        if (closing && l_ok[cls]) fx_store<LEVEL>(A, c & 0x7FFFFFFFFFFFFFFFull, a, ridx, l_old[cls]);
+      } else {
+        fx_push<LEVEL>(A, closing, c & 0x7FFFFFFFFFFFFFFFull, a, sub, ridx);
+      }
     } else {
       const bool failed = closing && !flush_lds(c, a);
       const unsigned long long mf = __ballot(failed);
@@ -623,7 +763,7 @@ __device__ __forceinline__ void fx_acc_body(const FxArgs &A, const uint32_t bid)
         const uint32_t k = b0 + (uint32_t)__popcll(mf & lt_mask);
         const bool room = k < A.spill_per;
         if (failed && !room) fx_fallback(A.status, 4);
-        fx_push<LEVEL>(A, failed && room, c & 0x7FFFFFFFFFFFFFFFull, a, sub, A.rec_tiles * (uint32_t)kFxRecTile + sp * A.spill_per + k, no_early);
+        fx_push<LEVEL>(A, failed && room, c & 0x7FFFFFFFFFFFFFFFull, a, sub, A.rec_tiles * (uint32_t)kFxRecTile + sp * A.spill_per + k);
       }
     }
   };
@@ -680,16 +820,6 @@ __device__ __forceinline__ void fx_acc_body(const FxArgs &A, const uint32_t bid)
     tlo_m = fmin(tlo_m, tmag[j]), thi_m = fmax(thi_m, tmag[j]);
   }
   fx_fix();  // the lane's open partial, as integers from here on
-  // roots created by the early probes: their places in the dense root list are requested now (one counter atomic per wavefront;
-  // its answer is used at the very end)
-  bool e_made = false;
-  unsigned long long e_cm = 0ull;
-  uint32_t e_base = 0;
-  if (LEVEL == 1) {
-    e_made = early.key1 != 0u && (int)(threadIdx.x & 63) == early.lead && early.found == 0u;
-    e_cm = __ballot(e_made);
-    if (e_cm && (int)(threadIdx.x & 63) == __ffsll((long long)e_cm) - 1) e_base = atomicAdd(fx_cnt(A, kFxStRoots, sub), (uint32_t)__popcll(e_cm));
-  }
   // The lanes' open partials: neighbouring lanes hold consecutive points and mostly the same cell (a scan line stays in one
   // 0.4 m octant for tens of points), so runs of equal cells are summed across the lanes first - an inclusive segmented scan
   // INSIDE each row of 16 lanes, four steps of DPP row shifts (v_mov_b32_dpp row_shr: a full-rate VALU move; the same scan
@@ -738,11 +868,6 @@ __device__ __forceinline__ void fx_acc_body(const FxArgs &A, const uint32_t bid)
     step(std::integral_constant<int, 2>{});
     step(std::integral_constant<int, 4>{});
     step(std::integral_constant<int, 8>{});
-    // the lane to the right in the row (row_shl:1; the row's last lane sees 0)
-    const uint32_t nlo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)mycode, 0x101, 0xF, 0xF, true);
-    const uint32_t nhi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(mycode >> 32), 0x101, 0xF, 0xF, true);
-    const unsigned long long nextc = (unsigned long long)nlo | ((unsigned long long)nhi << 32);
-    const bool tail = mycode != 0ull && (rl == 15 || nextc != mycode);
     close_partial(3, tail, mycode, acc);
   }
   __syncthreads();
@@ -762,18 +887,7 @@ __device__ __forceinline__ void fx_acc_body(const FxArgs &A, const uint32_t bid)
       a.tmin_inv = h_rec[i][11];
       a.tmax_p1 = h_rec[i][12];
     }
-    if (__ballot(c != 0ull)) fx_push<LEVEL>(A, c != 0ull, c & 0x7FFFFFFFFFFFFFFFull, a, sub, bid * (uint32_t)kFxRecTile + (uint32_t)i, no_early);
-  }
-  if (LEVEL == 1 && e_cm) {  // roots created by the early probes -> the dense root list
-    const int l = threadIdx.x & 63;
-    const uint32_t list_base = (uint32_t)__shfl((int)e_base, __ffsll((long long)e_cm) - 1);
-    if (e_made) {
-      const uint32_t local = list_base + (uint32_t)__popcll(e_cm & ((1ull << l) - 1ull));
-      if (local < A.mr_per)
-        A.rlist[sub * A.mr_per + local] = early.s0;
-      else
-        fx_fallback(A.status, 5);
-    }
+    if (__ballot(c != 0ull)) fx_push<LEVEL>(A, c != 0ull, c & 0x7FFFFFFFFFFFFFFFull, a, sub, bid * (uint32_t)kFxRecTile + (uint32_t)i);
   }
 }
 
@@ -787,7 +901,12 @@ __device__ __forceinline__ void fx_acc_body(const FxArgs &A, const uint32_t bid)
 // latency a prefetch could hide - with a quarter fewer wavefronts per CU the same instruction streams simply take longer.)
 template <int LEVEL>
 __global__ void __launch_bounds__(kFxThreads) k_fx_acc(FxArgs A) {
-  fx_acc_body<LEVEL>(A, blockIdx.x);
+  fx_acc_body<LEVEL, kFxAccForm>(A, blockIdx.x);
+}
+// the other forms (development option fx_acc_form: tests and A/B runs), under a name of their own
+template <int LEVEL, int FORM>
+__global__ void __launch_bounds__(kFxThreads) k_fx_acc_form(FxArgs A) {
+  fx_acc_body<LEVEL, FORM>(A, blockIdx.x);
 }
 
 // K sweeps in ONE launch (wc_extract_surfels_batch): workgroup -> (sweep k, tile) through the prefix table start[] (K + 1
@@ -819,7 +938,48 @@ __global__ void __launch_bounds__(kFxThreads) k_fx_acc_b(FxBatch B) {
   const int k = fx_batch_find(B, blockIdx.x, bid);
   if (LEVEL == 2 && !(B.flags[k] & 1u)) return;
   WC_FX_BATCH_ARGS(sA, B, k)
-  fx_acc_body<LEVEL>(sA, bid);
+  fx_acc_body<LEVEL, kFxAccForm>(sA, bid);
+}
+template <int LEVEL, int FORM>
+__global__ void __launch_bounds__(kFxThreads) k_fx_acc_form_b(FxBatch B) {
+  uint32_t bid;
+  const int k = fx_batch_find(B, blockIdx.x, bid);
+  if (LEVEL == 2 && !(B.flags[k] & 1u)) return;
+  WC_FX_BATCH_ARGS(sA, B, k)
+  fx_acc_body<LEVEL, FORM>(sA, bid);
+}
+// host side: the kernel of the form the context asks for, or - option -1 - the library's choice: kFxAccForm (the default kernels)
+// while one round of workgroups holds the sweep (up to 2 M points: the grid starts together and its phases would run one after the
+// other - what both bits are for), bit 0 alone for a LARGER sweep on the staged path: there successive rounds of workgroups overlap
+// already, and measured at 10 M points as records both bits together are slower than the kernel without either while bit 0 alone is
+// faster (DESIGN 3.1); packed points keep kFxAccForm at every size (bit 1 gains 3 % at 10 M).  n = 0: a batch (kFxAccForm).
+// Bit 0 does not apply to LEVEL 2: its forms are told apart by bit 1 alone, so that no instantiation exists twice under two names
+constexpr uint64_t kFxAccResident = 2000000ull;  // (the bound of FxArgs::static_map: run_pipeline_fast)
+inline int fx_acc_form_of(const wc_ctx *ctx, int level, uint64_t n, uint32_t fmt) {
+  static_assert(kFxAccForm == 3, "fx_launch_acc / fx_launch_acc_b: the cases they name are the NON-default forms");
+  int f = ctx->dev.fx_acc_form & 3;
+  if (ctx->dev.fx_acc_form < 0) f = (n > kFxAccResident && fmt != 2u) ? 1 : kFxAccForm;
+  return level == 2 ? ((f & 2) ? kFxAccForm : 0) : f;
+}
+template <int LEVEL>
+void fx_launch_acc(const wc_ctx *ctx, unsigned grid, hipStream_t st, const FxArgs &A) {
+  const int f = fx_acc_form_of(ctx, LEVEL, A.pts.n, A.fmt);
+  if (f == 0) return (void)k_fx_acc_form<LEVEL, 0><<<grid, kFxThreads, 0, st>>>(A);
+  if constexpr (LEVEL == 1) {
+    if (f == 1) return (void)k_fx_acc_form<1, 1><<<grid, kFxThreads, 0, st>>>(A);
+    if (f == 2) return (void)k_fx_acc_form<1, 2><<<grid, kFxThreads, 0, st>>>(A);
+  }
+  k_fx_acc<LEVEL><<<grid, kFxThreads, 0, st>>>(A);
+}
+template <int LEVEL>
+void fx_launch_acc_b(const wc_ctx *ctx, unsigned grid, hipStream_t st, const FxBatch &B) {
+  const int f = fx_acc_form_of(ctx, LEVEL, 0, 0u);
+  if (f == 0) return (void)k_fx_acc_form_b<LEVEL, 0><<<grid, kFxThreads, 0, st>>>(B);
+  if constexpr (LEVEL == 1) {
+    if (f == 1) return (void)k_fx_acc_form_b<1, 1><<<grid, kFxThreads, 0, st>>>(B);
+    if (f == 2) return (void)k_fx_acc_form_b<1, 2><<<grid, kFxThreads, 0, st>>>(B);
+  }
+  k_fx_acc_b<LEVEL><<<grid, kFxThreads, 0, st>>>(B);
 }
 
 // ---- long lists: one record per (node, time slot) --------------------------------------------------------------------------
