@@ -168,8 +168,7 @@ int wc_extract_surfels_batch_finish(wc_ctx *ctx, uint64_t *h_n_out, int K);
  * entries are 0), 0 = off. */
 int wc_extract_profile(wc_ctx *ctx, int enable);
 int wc_extract_stage_ms(wc_ctx *ctx, float *h_ms5);
-/* raw status words of the last extraction (profiling aid; words 16.. hold per-section cycle sums when the library
- * is built with -DWC_PROF_ROOTS; words 56..58: pipelines the last sweep enqueued (1 = no repeat), path bits of the run that
+/* raw status words of the last extraction (profiling aid; words 56..58: pipelines the last sweep enqueued (1 = no repeat), path bits of the run that
  * completed it (1 default path, 2 wide keys, 4 run-binned point sort, 8 time-bin surfel order), LDS capacity of the run-binned
  * sort; words 59..63: long lists, fall-backs so far, completed by the default path, its last flags and reasons) */
 int wc_debug_status(wc_ctx *ctx, uint32_t *h_out64);

@@ -1,14 +1,17 @@
 """A/B of the extraction on one box: python profiles/dev/ab_extract.py <tree> [steps] - wall ms per sweep (enqueue + finish) of the C2
-sweep as 48-byte records and packed, the firing-order sweep, the 10 M-point cloud in both layouts, with the library of <tree>"""
+sweep as 48-byte records and packed, the firing-order sweep, the 10 M-point cloud in both layouts, with the library of <tree>.
+python profiles/dev/ab_extract.py <tree> [steps] exact - the exact path (exact_sums = 1) on the C2 sweep and the firing-order sweep only"""
 import os, sys, time
 tree = os.path.abspath(sys.argv[1])
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 200
+exact = len(sys.argv) > 3 and sys.argv[3] == "exact"
 sys.path.insert(0, os.path.join(tree, "wildcat-slam_amd", "python"))
 import numpy as np
 from wildcat_slam_amd import lib, synth
 from wildcat_slam_amd import records as Rec
 
 ctx = lib.Context(0)
+ctx.set_exact_sums(exact)
 def run(pts, soa, steps):
     n = len(pts)
     cap = (3 * n) // 20 + 1
@@ -45,9 +48,12 @@ def run(pts, soa, steps):
 
 c2 = synth.g2_lattice(3906, m=32)[0]
 room = synth.g1_room(1_000_000, seed=synth.SEED + 3)
-c5 = synth.g2_lattice(39062, m=32)[0]
 out = []
-for name, pts, soa, st in (("c2", c2, False, steps), ("c2soa", c2, True, steps), ("room", room, False, steps // 2), ("roomsoa", room, True, steps // 2), ("c5", c5, False, steps // 4), ("c5soa", c5, True, steps // 4)):
+work = [("c2", c2, False, steps), ("room", room, False, steps // 2)]
+if not exact:
+    c5 = synth.g2_lattice(39062, m=32)[0]
+    work = [work[0], ("c2soa", c2, True, steps), work[1], ("roomsoa", room, True, steps // 2), ("c5", c5, False, steps // 4), ("c5soa", c5, True, steps // 4)]
+for name, pts, soa, st in work:
     ms, m, stg = run(pts, soa, st)
     out.append("%s %.4f %s" % (name, ms, list(stg.values())))
 print(os.path.basename(tree) or "new", " | ".join(out))

@@ -286,6 +286,58 @@ def test_unordered_small_sweep_stays_on_the_run_binned_path(fresh_gpu, oracle):
     assert res["path"]["lds_cap"] == 1024 and res["fast"]["path"]["lds_cap"] == 1024
 
 
+# (runs, lds_cap) of sweeps 1, 2, 3 below: RECORDED on these very sweeps from the library as it was before the three root kernels
+# of the exact path were rebuilt on shared routines (the convention of `fresh_gpu`); not derived from the new code.
+_STREAMING_FORMS = {
+    # layer 2 in use (oracle: 5 069 surfels, 48 of them at layer 2): both phase-2 kernels emit through the shared layer-2 finish
+    "layer2": (dict(min_points=5, cluster_min_points=5, cluster_gap=1.0), ((1, 256), (1, 256), (1, 256))),
+    # 26 k temporal clusters: roots with more candidates than one batch of PCAs holds, i.e. the later batches of the loop
+    "many_candidates": (dict(min_points=5, cluster_min_points=5), ((1, 256), (1, 256), (1, 256))),
+}
+
+
+@pytest.mark.parametrize("case", sorted(_STREAMING_FORMS))
+def test_exact_streaming_forms_give_the_same_bytes(fresh_gpu, oracle, case):
+    """exact_sums = 1 streams a root's points with one of three kernels: k_roots (run-binned sort, sweep with run structure - or the
+    first sweep of a context, whatever its structure), k_roots_banks<RUNS> (run-binned sort, the previous sweep reported fewer than four
+    points per run) and k_roots_banks<!RUNS> (radix sort).  "Same sums in the same order, hence the same bits": the same firing-order
+    cloud through all three must give the same surfel and id bytes, and the oracle's ids.  Parameters chosen so that the phase-2 kernels
+    emit layer-2 surfels (default-parameter rooms of this size emit none) resp. so that roots hold more candidates than one PCA batch."""
+    overrides, recorded = _STREAMING_FORMS[case]
+    gpu = fresh_gpu
+    params = oracle.default_params()
+    for k, v in overrides.items():
+        setattr(params, k, v)
+    pts = synth.g1_room(60_000, seed=5)
+    s_ref, id_ref, st = oracle.extract_surfels(pts, params)
+    # the oracle conditions the case stands for (a change of synth must not hollow the test out)
+    if case == "layer2":
+        assert np.any((id_ref["node"] & 3) == 2)
+    else:
+        assert st.clusters_total > 20_000
+    params.exact_sums = 1  # set once: every sweep below is the exact path's
+    gpu.set_params(params)
+    try:
+        got = []
+        for sweep in (1, 2, 3):
+            if sweep == 3:
+                gpu.set_dev_option("no_bucket_sort", 1)  # radix sort: k_roots_banks<.., false>
+            s, ids = gpu.extract_surfels(pts)
+            info = gpu.extract_path_info()
+            print(case, "sweep", sweep, "n", len(s), info)
+            got.append((s.tobytes(), ids.tobytes(), info))
+        for sweep, (sb, ib, info) in enumerate(got, 1):
+            assert not info["fast"]
+            assert ib == id_ref.tobytes(), (case, sweep)
+            assert sb == got[0][0] and ib == got[0][1], (case, sweep)
+            # sweeps 1 and 2 are completed on the run-binned sort (2: after sweep 1 reported one run per point), sweep 3 is not
+            assert info["path"] == (BIN_ORDER if sweep == 3 else RUN_SORT | BIN_ORDER), (case, sweep, info)
+            assert (info["runs"], info["lds_cap"]) == recorded[sweep - 1], (case, sweep, info)
+    finally:
+        gpu.set_dev_option("no_bucket_sort", 0)
+        gpu.set_params(oracle.default_params())
+
+
 @pytest.mark.parametrize("override", [
     dict(max_layer=1),                                  # no layer-2 pass at all
     dict(max_layer=0),                                  # root voxels only

@@ -21,6 +21,11 @@
 //                    split are queued
 //   5. k_roots<2>    layer 2 of the queued roots (launched only if the previous sweep needed it)
 //   6. k_slot_emit   time order (surfel_extraction.cc:334) + copy slot -> caller's buffer, count to the host mailbox
+// Sweeps without run structure stream with k_roots_banks<1 / 2> in steps 3 and 5 (another algorithm, the same sums).  What the three
+// root kernels have in common exists once, in front of them: hand_out_roots (dense root list, sparse head table, split jobs; one or
+// three roots per wavefront), key_origin + root_desc (RootDesc: voxel index, centre, quarter length, slot base, candidate cap),
+// point_octants, put_moment_terms, run_point_search, cand_meta_pack / _node / _ord + put_candidate, lane_job + plane_gate /
+// cluster_gate (one lane of a batch of PCAs), finish_layer2 (tests + emission of both phase-2 kernels), count_surfels.
 // Host side: what a sweep runs is an ExPath (extract_plan.h) - default or exact pipeline, 32- or 64-bit keys, run-binned or
 // radix point sort (k_keygen + rocPRIM + k_heads + k_roots_banks: sweeps without run structure or with overfull bins), time
 // bins or a radix sort of the slot keys.  wc_extract_surfels_enqueue takes ex_first_path(), finish() waits for the sweep's
@@ -270,7 +275,6 @@ struct RootsArgs {
   uint64_t *slot_bins;          // [kBuckets][slot_bin_cap] (time key << 32 | slot) of the surfels of each time bucket
   uint32_t slot_bin_cap;
   struct SplitJob *split_jobs;  // roots queued for the layer-2 pass; count in status[4]
-  uint32_t *prof;               // WC_PROF_ROOTS builds: 8 section timers per head slot
   double *node_tot;             // [head slot][9][11] node totals of the layer-0/1 pass
   uint32_t *root_ncand;         // [head slot] candidates written by the layer-0/1 pass
 };
@@ -328,19 +332,6 @@ __global__ void __launch_bounds__(256) k_heads(const K *__restrict__ keys, uint6
   if (live) head_slots[pos / (uint64_t)(min_points + 1)] = HeadRec{(uint32_t)pos, 0u, 0u, 0u};
 }
 
-#ifdef WC_PROF_ROOTS
-// per-root section timers (cycle counter), kept in registers and written once per root to a private row: no shared
-// counters (a hot atomic would sit in the same in-order memory queue as the loads being timed)
-#define WC_TICK(i)                                                  \
-  do {                                                              \
-    const unsigned long long now_ = __builtin_readcyclecounter();   \
-    prof_[i] += (uint32_t)(now_ - tick_);                           \
-    tick_ = now_;                                                   \
-  } while (0)
-#else
-#define WC_TICK(i)
-#endif
-
 struct SplitJob {  // a root whose layer-1 nodes need the layer-2 pass (k_roots<K, 2>)
   uint32_t slot, ncand;  // head table slot of the root
   unsigned long long split1;
@@ -392,13 +383,226 @@ struct RootLocator {
   }
 };
 
+// ---- what the three root kernels of the exact path (k_roots, k_roots_banks, k_roots_emit) share: every rule that has to agree
+//      bit for bit with the reference - root geometry, octants, moment terms, candidate slots, the two gates - exists once, here ----
+
+// the live roots of a sweep reach the wavefronts, NG at a time (1: the streaming kernels; 3: k_roots_emit, lane group g = lane / (64 / NG)
+// takes root g), from one of three lists:
+//   kRootList   RUNS mode: roots NG w .. NG w + NG - 1 of the dense work list (RootLocator).  (A device-side dequeue word serialised
+//               at ~90 dequeues/us and cost more than it balanced.)
+//   kHeadTable  the sparse head table of k_heads: every wavefront owns a contiguous range of slots and scans it with a ballot
+//   kSplitJobs  the njobs roots queued for the layer-2 pass, strided (NG = 1)
+// f(hrec, tslot, ncand, split1) gets, per lane, the root of the lane's group: its head record and head table slot (~0: the group has
+// no root this time) and, for a split job, its candidate count so far and the layer-1 octants that get split (cc:175-182).
+enum RootSource { kRootList, kHeadTable, kSplitJobs };
+template <RootSource SRC, int NG, typename F>
+__device__ __forceinline__ void hand_out_roots(const RootsArgs &A, int lane, uint32_t njobs, F &&f) {
+  static_assert(SRC != kSplitJobs || NG == 1, "split jobs go one to a wavefront");
+  const int g = (NG == 1) ? 0 : lane / (64 / NG);
+  if constexpr (SRC == kSplitJobs) {
+    for (uint32_t it = blockIdx.x; it < njobs; it += gridDim.x) {
+      const SplitJob job = A.split_jobs[it];
+      f(A.heads[job.slot], job.slot, job.ncand, job.split1);
+    }
+  } else if constexpr (SRC == kRootList) {
+    RootLocator loc;
+    loc.init(A, lane);
+    for (uint32_t w0 = blockIdx.x * NG; w0 < loc.total; w0 += gridDim.x * NG) {
+      uint32_t tslot = 0xFFFFFFFFu;
+      for (int k = 0; k < NG; ++k)
+        if (w0 + k < loc.total) {
+          const uint32_t sl = loc.slot_of(A, w0 + k);
+          if (g == k) tslot = sl;
+        }
+      f((NG == 1 || tslot != 0xFFFFFFFFu) ? A.heads[tslot] : HeadRec{0u, 0u, 0u, 0u}, tslot, 0u, 0ull);
+    }
+  } else {
+    const uint32_t per_wave = (A.nslots + gridDim.x - 1) / gridDim.x;
+    const uint32_t it_end = min((blockIdx.x + 1) * per_wave, A.nslots);
+    for (uint32_t it = blockIdx.x * per_wave; it < it_end; it += 64) {
+      const uint32_t my_pos = (it + lane < it_end) ? A.heads[it + lane].pos : 0xFFFFFFFFu;
+      unsigned long long live_mask = __ballot(my_pos != 0xFFFFFFFFu);
+      while (live_mask) {
+        uint32_t tslot = 0xFFFFFFFFu;
+        int src = 0;
+        for (int k = 0; k < NG; ++k) {
+          if (!live_mask) break;
+          const int bit = __ffsll((long long)live_mask) - 1;
+          live_mask &= live_mask - 1;
+          if (g == k) tslot = it + (uint32_t)bit, src = bit;
+        }
+        const uint32_t pos = (uint32_t)__shfl((int)my_pos, src);  // (a head record of this table is its position and nothing else)
+        f(HeadRec{tslot != 0xFFFFFFFFu ? pos : 0u, 0u, 0u, 0u}, tslot, 0u, 0ull);
+      }
+    }
+  }
+}
+
+// voxel index of the key origin (ex_origin): what the root keys are relative to
+struct KeyOrigin {
+  int x, y, z;
+};
+__device__ __forceinline__ KeyOrigin key_origin(const RootsArgs &A) {
+  double x0, y0, z0;
+  ex_origin(A.pts, x0, y0, z0);
+  return KeyOrigin{vox(x0, A.P.vs), vox(y0, A.P.vs), vox(z0, A.P.vs)};
+}
+
+// one root voxel: absolute voxel index, centre ((0.5 + k) * voxel_size, cc:208-210), quarter_length_ (cc:207), first candidate slot
+struct RootDesc {
+  int kx, ky, kz;
+  double cx, cy, cz;
+  float q0;
+  uint64_t slot_base;
+  // candidates of the root that have a slot, out of the ncand it counted
+  __device__ __forceinline__ uint32_t cand_cap(const RootsArgs &A, uint32_t ncand) const {
+    return (uint32_t)min((uint64_t)ncand, A.total_slots > slot_base ? A.total_slots - slot_base : 0);
+  }
+};
+// RUNS: the key is the bucket digit of the root's bin joined with the rest in its first run composite; otherwise keys[] is sorted
+template <typename K, bool RUNS>
+__device__ __forceinline__ RootDesc root_desc(const RootsArgs &A, const HeadRec &hrec, const K *keys, const KeyOrigin &org) {
+  constexpr int B = KeyTraits<K>::bits;
+  constexpr int half = 1 << (B - 1);
+  const ExParams &P = A.P;
+  const K rootkey = RUNS ? (K)key_join(hrec.gidx / A.run_cap, comp_rest(A.runs[hrec.gidx])) : keys[hrec.pos];
+  RootDesc R;
+  R.kx = (int)(rootkey & ((K(1) << B) - 1)) - half + org.x;
+  R.ky = (int)((rootkey >> B) & ((K(1) << B) - 1)) - half + org.y;
+  R.kz = (int)((rootkey >> (2 * B)) & ((K(1) << B) - 1)) - half + org.z;
+  R.cx = (0.5 + R.kx) * P.vs_f, R.cy = (0.5 + R.ky) * P.vs_f, R.cz = (0.5 + R.kz) * P.vs_f;
+  R.q0 = P.vs_f / 4;
+  R.slot_base = ((uint64_t)hrec.pos * (uint64_t)(P.max_layer + 1)) / (uint64_t)P.cluster_min;
+  return R;
+}
+
+// octants of a point: o1 in its root, o2 in that layer-1 child.  octant = 4*[x>cx] + 2*[y>cy] + [z>cz] (strict >, cc:147-158);
+// child centre = centre +- quarter, the offset formed in float (cc:163-165)
+__device__ __forceinline__ void point_octants(const RootDesc &R, double px, double py, double pz, int &o1, int &o2) {
+  const int bx = px > R.cx, by = py > R.cy, bz = pz > R.cz;
+  const double c1x = R.cx + (double)((float)(2 * bx - 1) * R.q0);
+  const double c1y = R.cy + (double)((float)(2 * by - 1) * R.q0);
+  const double c1z = R.cz + (double)((float)(2 * bz - 1) * R.q0);
+  o1 = 4 * bx + 2 * by + bz;
+  o2 = 4 * (px > c1x) + 2 * (py > c1y) + (pz > c1z);
+}
+
+// the 11 moment terms {1, t, x, y, z, xx, xy, xz, yy, yz, zz} of a point, `stride` doubles apart
+__device__ __forceinline__ void put_moment_terms(double *dst, int stride, double pt, double px, double py, double pz) {
+  dst[0] = 1.0, dst[stride] = pt, dst[2 * stride] = px, dst[3 * stride] = py, dst[4 * stride] = pz;
+  dst[5 * stride] = px * px, dst[6 * stride] = px * py, dst[7 * stride] = px * pz, dst[8 * stride] = py * py, dst[9 * stride] = py * pz,
+               dst[10 * stride] = pz * pz;
+}
+
+// RUNS mode, a root of many sorted runs: index of its pp-th point in time order, pp < hrec.total, by binary search in the root's
+// run offsets (off0 = run_off[hrec.gidx], the offset of its first run)
+__device__ __forceinline__ uint32_t run_point_search(const RootsArgs &A, const HeadRec &hrec, uint32_t off0, uint32_t pp) {
+  const uint32_t *ro = A.run_off + hrec.gidx;
+  uint32_t lo = 0, hi = hrec.nr;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (ro[mid] - off0 <= pp)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return comp_start(A.runs[(size_t)hrec.gidx + lo]) + (pp - (ro[lo] - off0));
+}
+
+// cand_meta word of a candidate cluster: node (root-local: 0 the root, 1..8 layer 1; layer-2 pass: 0..63) | (phase - 1) << 7 | ordinal
+// of the cluster in its node << 8
+__device__ __forceinline__ uint32_t cand_meta_pack(int nu, int phase, uint32_t ord) { return (uint32_t)nu | ((uint32_t)(phase - 1) << 7) | (ord << 8); }
+__device__ __forceinline__ int cand_meta_node(uint32_t meta) { return (int)(meta & 0x7F); }
+__device__ __forceinline__ uint32_t cand_meta_ord(uint32_t meta) { return meta >> 8; }
+
+// a closed temporal cluster of at least cluster_min points becomes candidate number ncand of its root (the caller counts): the lanes
+// of `lanes` hold its 11 sums, lane m the m-th (v).  A root that counts more candidates than it has slots raises kFlagSlotOverflow.
+__device__ __forceinline__ void put_candidate(const RootsArgs &A, const RootDesc &R, uint32_t ncand, bool lanes, int m, double v, int nu, int phase,
+                                              uint32_t ord, int lane) {
+  const uint64_t slot = R.slot_base + ncand;
+  if (slot < A.total_slots) {
+    if (lanes) {
+      A.cand[slot * kMom + m] = v;
+      if (m == 0) A.cand_meta[slot] = cand_meta_pack(nu, phase, ord);
+    }
+  } else if (lane == 0) {
+    raise_flag(A.status, kFlagSlotOverflow);
+  }
+}
+
+// One lane's job in a batch of 3x3 PCAs - node tests and candidate clusters side by side, so that a root costs one eigen-solve
+// latency instead of two.  node_lane: test node nu_node, tot = its 11 totals (InitOctoTree / CutOctoTree, cc:129-138, :170-183: only a
+// node of more than min_points points is tested); cand_lane: candidate c of the root (ClusterSurfels' second loop, cc:32-64).
+struct LaneJob {
+  bool have;      // there are moments, rr is their PCA
+  int nu;         // node
+  uint32_t ord;   // candidate: ordinal of the cluster in its node ...
+  uint64_t slot;  // ... and its slot
+  Pca rr;
+};
+__device__ __forceinline__ void lane_job(const RootsArgs &A, const RootDesc &R, bool node_lane, const double *tot, int nu_node, bool cand_lane,
+                                         uint32_t c, LaneJob &J) {
+  double mom[kMom];
+  J.have = false, J.nu = 0, J.ord = 0, J.slot = 0;
+  if (node_lane) {
+    J.nu = nu_node;
+    if (tot[0] > (double)A.P.min_points) {
+      J.have = true;
+      for (int i = 0; i < kMom; ++i) mom[i] = tot[i];
+    }
+  } else if (cand_lane) {
+    J.slot = R.slot_base + c;
+    const uint32_t meta = A.cand_meta[J.slot];
+    J.nu = cand_meta_node(meta);
+    J.ord = cand_meta_ord(meta);
+    J.have = true;
+    for (int i = 0; i < kMom; ++i) mom[i] = A.cand[J.slot * kMom + i];
+  }
+  if (J.have) pca_from_moments(mom, J.rr);
+}
+// The two gates.  They are NOT each other's negation: at equality a node is no plane, and a cluster of a plane node still passes.
+__device__ __forceinline__ bool plane_gate(const ExParams &P, const Pca &rr) { return (rr.ev[0] < P.thr) && (rr.like > P.min_like); }    // cc:106-111
+__device__ __forceinline__ bool cluster_gate(const ExParams &P, const Pca &rr) { return !(rr.ev[0] > P.thr || rr.like < P.min_like); }  // cc:54
+
+// the surfel count: with the time bins it is the total of the bin counts (k_slot_emit); a per-root atomic on one word serialises
+// at ~12 ns per root once every wavefront reaches this point at the same time (47 us for 3.9 k roots)
+__device__ __forceinline__ void count_surfels(const RootsArgs &A, uint32_t emitted, int lane) {
+  if (lane == 0 && emitted && !A.slot_counts) atomicAdd(&A.status[0], emitted);
+}
+
+// Layer 2 of one root, after its points were streamed: s_total = the totals of its 64 layer-2 nodes (LDS), of which those below the
+// split layer-1 octants (split1) exist.  The first batch of PCAs tests the 64 nodes, every later one takes 64 of the candidates
+// [cand_begin, ncand) the pass added; the clusters of plane nodes that pass their gate become surfels.  -> surfels emitted
+__device__ __forceinline__ uint32_t finish_layer2(const RootsArgs &A, const RootDesc &R, const double *s_total, unsigned long long split1,
+                                                  uint32_t cand_begin, uint32_t ncand, int lane) {
+  const uint32_t ncap = R.cand_cap(A, ncand);
+  unsigned long long plane_mask = 0;
+  uint32_t emitted = 0;
+  for (uint32_t batch = 0;; ++batch) {
+    const bool node_lane = (batch == 0) && ((split1 >> (lane >> 3)) & 1ull);
+    const uint32_t cbase = cand_begin + (batch == 0 ? 0u : (batch - 1) * 64u);
+    const uint32_t c = cbase + (uint32_t)lane;
+    const bool cand_lane = batch > 0 && c < ncap;
+    if (batch > 0 && cbase >= ncap) break;
+    LaneJob J;
+    lane_job(A, R, node_lane, s_total + lane * kMom, lane, cand_lane, c, J);
+    if (batch == 0) plane_mask = __ballot(node_lane && J.have && plane_gate(A.P, J.rr));
+    bool ok = false;
+    if (cand_lane && J.have && ((plane_mask >> J.nu) & 1ull) && cluster_gate(A.P, J.rr)) {
+      emit_surfel(A, J.rr, J.slot, 2, J.nu, J.ord, R.kx, R.ky, R.kz, R.q0);
+      ok = true;
+    }
+    emitted += (uint32_t)__popcll(__ballot(ok));
+  }
+  return emitted;
+}
+
 // One wavefront per root voxel.  PHASE 1 streams the root + its eight layer-1 nodes (9 table rows) and leaves node totals
 // and candidate clusters to k_roots_emit; roots with layer-1 nodes that were tested and are not planes (CutOctoTree
 // recursion, cc:175-182) are queued for PHASE 2, a second launch of the same streaming code over the 64 layer-2 nodes with
 // the tests and the emission fused in (rare on regular scenes, so the common case keeps a 7 KB LDS footprint).
 // Runs behind the run-binned point sort only (the radix-sort path streams with k_roots_banks): a root's points are its sorted
-// runs.  Work assignment: root number blockIdx.x of the dense work list (RootLocator).  (A device-side dequeue word
-// serialised at ~90 dequeues/us and cost more than it balanced.)
+// runs.  Work assignment: root number blockIdx.x of the dense work list, or the queued split jobs (hand_out_roots).
 template <typename K, int PHASE>
 __global__ void __launch_bounds__(64) k_roots(RootsArgs A) {
   constexpr int phase = PHASE;  // octree pass: 1 = root + layer 1 (streaming only, k_roots_emit finishes it), 2 = layer 2 (fused)
@@ -418,8 +622,6 @@ __global__ void __launch_bounds__(64) k_roots(RootsArgs A) {
 
   const int lane = threadIdx.x;
   const ExParams &P = A.P;
-  constexpr int B = KeyTraits<K>::bits;
-  constexpr int half = 1 << (B - 1);
   const uint32_t njobs = (PHASE == 2) ? A.status[4] : 0u;
   if (PHASE == 2 && blockIdx.x >= njobs) return;  // usually nothing is queued: leave before anything else is loaded
   // (no status check: after a bin overflow the run structures are incomplete but consistent - the roots of the overflowed
@@ -438,18 +640,10 @@ __global__ void __launch_bounds__(64) k_roots(RootsArgs A) {
   const int m = lane2 - Lq * kMom;
   const bool act = lane < 2 * lgrp;
 
-  double x0, y0, z0;
-  ex_origin(A.pts, x0, y0, z0);
-  const int k0x = vox(x0, P.vs), k0y = vox(y0, P.vs), k0z = vox(z0, P.vs);
+  const KeyOrigin org = key_origin(A);
 
   // ---- one root: stream its points (PHASE 2: also test and emit) ----
   auto do_root = [&](const HeadRec hrec, uint32_t tslot, uint32_t ncand, unsigned long long split1) {
-    uint32_t emitted = 0;
-    const uint64_t head = hrec.pos;
-#ifdef WC_PROF_ROOTS
-    unsigned long long tick_ = __builtin_readcyclecounter();
-    uint32_t prof_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
     // lane r < 64 keeps run r of this root (start index, root-local offset) in registers
     uint32_t r_start = 0, r_off = 0;
     uint64_t comp = 0;
@@ -458,8 +652,8 @@ __global__ void __launch_bounds__(64) k_roots(RootsArgs A) {
       r_off = A.run_off[(size_t)hrec.gidx + lane];
     }
     r_start = comp_start(comp);
-    r_off -= (uint32_t)__builtin_amdgcn_readfirstlane((int)r_off);
-    const K rootkey = (K)key_join(hrec.gidx / A.run_cap, (uint32_t)__builtin_amdgcn_readfirstlane((int)comp_rest(comp)));
+    const uint32_t off0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r_off);
+    r_off -= off0;
     // index of the root's p-th point (time order)
     // (called by all lanes: the register path broadcasts run descriptors with readlane)
     auto point_index = [&](uint32_t pp, bool ok_lane) -> uint32_t {
@@ -472,30 +666,11 @@ __global__ void __launch_bounds__(64) k_roots(RootsArgs A) {
         }
         return st + (pp - o);
       }
-      if (!ok_lane) return 0u;
-      const uint32_t *ro = A.run_off + hrec.gidx;  // many runs (unordered input): binary search in the offset table
-      const uint32_t o0 = ro[0];
-      uint32_t lo = 0, hi = hrec.nr;
-      while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (ro[mid] - o0 <= pp)
-          lo = mid;
-        else
-          hi = mid;
-      }
-      return comp_start(A.runs[(size_t)hrec.gidx + lo]) + (pp - (ro[lo] - o0));
+      return ok_lane ? run_point_search(A, hrec, off0, pp) : 0u;  // many runs (unordered input)
     };
-
-    // absolute root voxel index and centre ((0.5 + k) * voxel_size, cc:208-210)
-    const int kx = (int)(rootkey & ((K(1) << B) - 1)) - half + k0x;
-    const int ky = (int)((rootkey >> B) & ((K(1) << B) - 1)) - half + k0y;
-    const int kz = (int)((rootkey >> (2 * B)) & ((K(1) << B) - 1)) - half + k0z;
-    const double cx = (0.5 + kx) * P.vs_f, cy = (0.5 + ky) * P.vs_f, cz = (0.5 + kz) * P.vs_f;
-    const float q0 = P.vs_f / 4;  // quarter_length_ of the root (cc:207)
-    const uint64_t slot_base = (head * (uint64_t)(P.max_layer + 1)) / (uint64_t)P.cluster_min;
+    const RootDesc R = root_desc<K, true>(A, hrec, (const K *)nullptr, org);
 
     const uint32_t cand_begin = ncand;
-    {
     for (int i = lane; i < ntab * kMom; i += 64) {
       s_open[i] = 0.0;
       s_total[i] = 0.0;
@@ -519,8 +694,7 @@ __global__ void __launch_bounds__(64) k_roots(RootsArgs A) {
       load_xyz(A.pts, idx, px, py, pz);
       pt = load_t(A.pts, idx);
     }
-    WC_TICK(0);  // head -> first loads issued
-    int carry_o1 = -2;      // layer-1 octant / timestamp of the last point of the previous chunk
+    int carry_o1 = -2;     // layer-1 octant / timestamp of the last point of the previous chunk
     double carry_t = 0.0;
     while (true) {
       const int nvalid = __popcll(__ballot(valid));  // valid lanes are a prefix: keys are sorted
@@ -528,19 +702,11 @@ __global__ void __launch_bounds__(64) k_roots(RootsArgs A) {
       __syncthreads();
       int my_o1 = -1;
       if (valid) {
-        // octant = 4*[x>cx] + 2*[y>cy] + [z>cz] (strict >, cc:147-158); child centre = centre +- quarter (cc:163-165)
-        const int bx = px > cx, by = py > cy, bz = pz > cz;
-        const double c1x = cx + (double)((float)(2 * bx - 1) * q0);
-        const double c1y = cy + (double)((float)(2 * by - 1) * q0);
-        const double c1z = cz + (double)((float)(2 * bz - 1) * q0);
-        const int o1 = 4 * bx + 2 * by + bz;
-        const int o2 = 4 * (px > c1x) + 2 * (py > c1y) + (pz > c1z);
+        int o1, o2;
+        point_octants(R, px, py, pz, o1, o2);
         // the moment terms are formed here, lane-parallel: the sequential pass below is bound by LDS reads (15 wavefronts
         // per CU stream at once), and one 8-byte read per (point, moment) is half of what two factors would cost
-        double *pr = s_prod + lane;
-        pr[0] = 1.0, pr[kProdStride] = pt, pr[2 * kProdStride] = px, pr[3 * kProdStride] = py, pr[4 * kProdStride] = pz;
-        pr[5 * kProdStride] = px * px, pr[6 * kProdStride] = px * py, pr[7 * kProdStride] = px * pz, pr[8 * kProdStride] = py * py,
-                         pr[9 * kProdStride] = py * pz, pr[10 * kProdStride] = pz * pz;
+        put_moment_terms(s_prod + lane, kProdStride, pt, px, py, pz);
         s_code[lane] = (uint32_t)(o1 * 8 + o2);
         my_o1 = o1;
       }
@@ -573,9 +739,8 @@ __global__ void __launch_bounds__(64) k_roots(RootsArgs A) {
         }
       }
 
-      WC_TICK(1);  // staging (incl. waiting for the gather)
       // ---- stream the staged points in time order ----
-      int j = (WC_DBG(P, 1)) ? nvalid : 0;
+      int j = 0;
       while (j < nvalid) {
         const unsigned long long rem = ev >> j;
         const int je = rem ? j + (__ffsll((long long)rem) - 1) : nvalid;  // next event (or end of chunk)
@@ -633,15 +798,7 @@ __global__ void __launch_bounds__(64) k_roots(RootsArgs A) {
             const int cnt_l = __shfl(n_open, l * kMom);
             const bool mine = act && (Lq == l);
             if (cnt_l >= P.cluster_min) {  // clusters with fewer points are dropped (cc:33)
-              const uint64_t slot = slot_base + ncand;
-              if (slot < A.total_slots) {
-                if (mine && !is_tot) {
-                  A.cand[slot * kMom + m] = a_acc;
-                  if (m == 0) A.cand_meta[slot] = (uint32_t)nu | ((uint32_t)(phase - 1) << 7) | (s_ord[nu] << 8);
-                }
-              } else if (lane == 0) {
-                raise_flag(A.status, kFlagSlotOverflow);
-              }
+              put_candidate(A, R, ncand, mine && !is_tot, m, a_acc, nu, phase, s_ord[nu], lane);
               ++ncand;
             }
             if (mine) {
@@ -657,7 +814,6 @@ __global__ void __launch_bounds__(64) k_roots(RootsArgs A) {
           last = t;
         }
       }
-      WC_TICK(2);  // sequential pass
       if (nvalid < 64) break;
       valid = nvalid_next;
     }
@@ -674,109 +830,23 @@ __global__ void __launch_bounds__(64) k_roots(RootsArgs A) {
     // still-open clusters become candidates too (end of ClusterSurfels' first loop)
     for (int nu = 0; nu < ntab; ++nu) {
       if (s_cnt[nu] >= P.cluster_min) {
-        const uint64_t slot = slot_base + ncand;
-        if (slot < A.total_slots) {
-          if (lane < kMom) A.cand[slot * kMom + lane] = s_open[nu * kMom + lane];
-          if (lane == 0) A.cand_meta[slot] = (uint32_t)nu | ((uint32_t)(phase - 1) << 7) | (s_ord[nu] << 8);
-        } else if (lane == 0) {
-          raise_flag(A.status, kFlagSlotOverflow);
-        }
+        put_candidate(A, R, ncand, lane < kMom, lane, lane < kMom ? s_open[nu * kMom + lane] : 0.0, nu, phase, s_ord[nu], lane);
         ++ncand;
       }
-    }
     }
     if (PHASE == 1) {  // hand the node totals and the candidate count to k_roots_emit (tests + emission)
       for (int i = lane; i < ntab * kMom; i += 64) A.node_tot[(size_t)tslot * (9 * kMom) + i] = s_total[i];
       if (lane == 0) A.root_ncand[tslot] = ncand;
-      WC_TICK(3);
-#ifdef WC_PROF_ROOTS
-      if (lane == 0 && A.prof)
-        for (int i = 0; i < 8; ++i) A.prof[(head / 21) * 8 + i] += prof_[i];
-#endif
       __syncthreads();
       return;
     }
     __threadfence_block();
     __syncthreads();
-    WC_TICK(3);  // write-back + open-cluster flush + fence
-    if (WC_DBG(P, 2)) return;
-
-    // ---- ONE pass of 3x3 PCAs for the node tests (InitOctoTree / CutOctoTree gates, cc:129-138, :170-183) and for
-    //      the candidate clusters (ClusterSurfels' second loop, cc:32-64): lanes [0, ntab) take the nodes, the lanes
-    //      above them the first candidates, so a root costs one eigen-solve latency instead of two ----
-    const uint32_t ncap = (uint32_t)min((uint64_t)ncand, A.total_slots > slot_base ? A.total_slots - slot_base : 0);
-    unsigned long long plane_mask = 0;
-    for (uint32_t batch = 0;; ++batch) {
-      // lane job: node test (first batch only) or candidate
-      const bool node_lane = (batch == 0) && lane < ntab;
-      const int cand_lane0 = (batch == 0) ? ntab : 0;
-      const uint32_t cbase = cand_begin + (batch == 0 ? 0u : (uint32_t)(64 - ntab) + (batch - 1) * 64u);
-      const uint32_t c = cbase + (uint32_t)(lane - cand_lane0);
-      const bool cand_lane = lane >= cand_lane0 && c < ncap;
-      if (batch > 0 && cbase >= ncap) break;
-      double mom[kMom];
-      bool have = false;
-      int nu = 0;
-      uint32_t ord = 0;
-      uint64_t slot = 0;
-      if (node_lane) {
-        bool exists = true;
-        if (phase == 2) exists = (split1 >> (lane >> 3)) & 1ull;
-        nu = lane;
-        if (exists && s_total[lane * kMom] > (double)P.min_points) {
-          have = true;
-          for (int i = 0; i < kMom; ++i) mom[i] = s_total[lane * kMom + i];
-        }
-      } else if (cand_lane) {
-        slot = slot_base + c;
-        const uint32_t meta = A.cand_meta[slot];
-        nu = (int)(meta & 0x7F);
-        ord = meta >> 8;
-        have = true;
-        for (int i = 0; i < kMom; ++i) mom[i] = A.cand[slot * kMom + i];
-      }
-      WC_TICK(4);  // moments loaded
-      Pca rr;
-      if (have && !(WC_DBG(P, 4))) pca_from_moments(mom, rr);
-      WC_TICK(5);  // eigen-solves
-      if (WC_DBG(P, 4)) { rr.ev[0] = 1e-5; rr.ev[1] = rr.ev[2] = 1e-2; rr.like = 0.9; rr.tmean = mom[1] / mom[0]; for (int i = 0; i < 3; ++i) { rr.c[i] = mom[2 + i] / mom[0]; rr.nrm[i] = 0.577; } for (int i = 0; i < 9; ++i) rr.cov[i] = 0; }
-      if (batch == 0) {
-        const bool plane = node_lane && have && (rr.ev[0] < P.thr) && (rr.like > P.min_like);  // cc:106-111
-        plane_mask = __ballot(plane);
-      }
-      bool ok = false;
-      if (cand_lane && have && ((plane_mask >> nu) & 1ull) && !(rr.ev[0] > P.thr || rr.like < P.min_like)) {  // cc:54
-        const int layer = (phase == 2) ? 2 : (nu == 0 ? 0 : 1);
-        emit_surfel(A, rr, slot, layer, nu, ord, kx, ky, kz, q0);
-        ok = true;
-      }
-      emitted += (uint32_t)__popcll(__ballot(ok));
-      WC_TICK(6);  // gates + surfel stores
-    }
-    // the surfel count: with the time bins it is the total of the bin counts (k_slot_emit); a per-root atomic on one
-    // word serialises at ~12 ns per root once every wavefront reaches this point at the same time (47 us for 3.9 k roots)
-    if (lane == 0 && emitted && !A.slot_counts) atomicAdd(&A.status[0], emitted);
-#ifdef WC_PROF_ROOTS
-    if (lane == 0 && PHASE != 2 && A.prof)
-      for (int i = 0; i < 8; ++i) A.prof[(head / 21) * 8 + i] += prof_[i];
-#endif
+    count_surfels(A, finish_layer2(A, R, s_total, split1, cand_begin, ncand, lane), lane);
     __syncthreads();
   };
 
-  // ---- work items of this wavefront ----
-  if (PHASE == 2) {  // the queued split jobs, strided
-    for (uint32_t it = blockIdx.x; it < njobs; it += gridDim.x) {
-      const SplitJob job = A.split_jobs[it];
-      do_root(A.heads[job.slot], job.slot, job.ncand, job.split1);  // split1 = layer-1 octants that get split (cc:175-182)
-    }
-  } else {  // compacted root list: one root per wavefront
-    RootLocator loc;
-    loc.init(A, lane);
-    for (uint32_t w = blockIdx.x; w < loc.total; w += gridDim.x) {
-      const uint32_t tslot = loc.slot_of(A, w);
-      do_root(A.heads[tslot], tslot, 0u, 0ull);
-    }
-  }
+  hand_out_roots<PHASE == 2 ? kSplitJobs : kRootList, 1>(A, lane, njobs, do_root);
 }
 
 // ---- streaming for sweeps WITHOUT run structure (the radix-sort path) --------------------------------------------------
@@ -836,13 +906,10 @@ __device__ __forceinline__ unsigned long long readlane_u64(uint32_t lo, uint32_t
 template <typename K, int PHASE, bool RUNS>
 __global__ void __launch_bounds__(64) k_roots_banks(RootsArgs A, const K *__restrict__ keys) {
   constexpr int phase = PHASE;
-  constexpr int ntab = (phase == 1) ? 9 : 64;
   __shared__ double s_total[(PHASE == 2) ? 64 * kMom : 1];  // PHASE 2: totals of the 64 layer-2 nodes for the fused tests
-  __shared__ double s_prod[64 * kMom];                      // the 11 moment terms of every staged point
+  __shared__ double s_prod[64 * kMom];                      // the 11 moment terms of every staged point, POINT-major
   const int lane = threadIdx.x;
   const ExParams &P = A.P;
-  constexpr int B = KeyTraits<K>::bits;
-  constexpr int half = 1 << (B - 1);
   const uint32_t njobs = (PHASE == 2) ? A.status[4] : 0u;
   if (PHASE == 2 && blockIdx.x >= njobs) return;
 
@@ -853,37 +920,19 @@ __global__ void __launch_bounds__(64) k_roots_banks(RootsArgs A, const K *__rest
   const bool use_children = (PHASE == 2) || P.max_layer >= 1;
   const unsigned long long lvl_mask = (PHASE == 1) ? ((1ull << kMom) - 1ull) : 0ull;
 
-  double x0, y0, z0;
-  ex_origin(A.pts, x0, y0, z0);
-  const int k0x = vox(x0, P.vs), k0y = vox(y0, P.vs), k0z = vox(z0, P.vs);
+  const KeyOrigin org = key_origin(A);
 
   auto do_root = [&](const HeadRec hrec, uint32_t tslot, uint32_t ncand, unsigned long long split1) __attribute__((always_inline)) {
-    uint32_t emitted = 0;
     const uint64_t head = hrec.pos;
     // RUNS: the root's points are hrec.nr sorted runs starting at runs[hrec.gidx] (a sweep without run structure: one run
     // per point, so point p of the root is simply run p; otherwise a binary search in the run offsets)
-    const K rootkey = RUNS ? (K)key_join(hrec.gidx / A.run_cap, comp_rest(A.runs[hrec.gidx])) : keys[head];
     const bool unit_runs = RUNS && hrec.nr == hrec.total;
     const uint32_t off0 = (RUNS && !unit_runs) ? A.run_off[hrec.gidx] : 0u;
     auto run_point = [&](uint32_t pp) __attribute__((always_inline)) -> uint32_t {  // RUNS: index of the root's pp-th point, pp < total
-      if (unit_runs) return comp_start(A.runs[(size_t)hrec.gidx + pp]);
-      const uint32_t *ro = A.run_off + hrec.gidx;
-      uint32_t lo = 0, hi = hrec.nr;
-      while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (ro[mid] - off0 <= pp)
-          lo = mid;
-        else
-          hi = mid;
-      }
-      return comp_start(A.runs[(size_t)hrec.gidx + lo]) + (pp - (ro[lo] - off0));
+      return unit_runs ? comp_start(A.runs[(size_t)hrec.gidx + pp]) : run_point_search(A, hrec, off0, pp);
     };
-    const int kx = (int)(rootkey & ((K(1) << B) - 1)) - half + k0x;
-    const int ky = (int)((rootkey >> B) & ((K(1) << B) - 1)) - half + k0y;
-    const int kz = (int)((rootkey >> (2 * B)) & ((K(1) << B) - 1)) - half + k0z;
-    const double cx = (0.5 + kx) * P.vs_f, cy = (0.5 + ky) * P.vs_f, cz = (0.5 + kz) * P.vs_f;
-    const float q0 = P.vs_f / 4;  // quarter_length_ of the root (cc:207)
-    const uint64_t slot_base = (head * (uint64_t)(P.max_layer + 1)) / (uint64_t)P.cluster_min;
+    const RootDesc R = root_desc<K, RUNS>(A, hrec, keys, org);
+    const K rootkey = RUNS ? (K)0 : keys[head];  // (!RUNS: a root's points are keys / vals[head ...] while the key stays the same)
     const uint32_t cand_begin = ncand;
 
     // a temporal cluster of node nu ends (ClusterSurfels' first loop, cc:22-29): clusters with fewer than cluster_min points
@@ -891,17 +940,8 @@ __global__ void __launch_bounds__(64) k_roots_banks(RootsArgs A, const K *__rest
     // (The sums are passed by value: a reference bound to bank A in one call and bank B in another turns into a pointer
     // select after inlining and drags the sums into scratch memory.)
     auto end_cluster = [&](bool lanes, int nu, double ao, uint32_t ord, int cnt_lane) __attribute__((always_inline)) {
-      const int cnt = (int)readlane_d(ao, cnt_lane);
-      if (cnt >= P.cluster_min) {
-        const uint64_t slot = slot_base + ncand;
-        if (slot < A.total_slots) {
-          if (lanes) {
-            A.cand[slot * kMom + m] = ao;
-            if (m == 0) A.cand_meta[slot] = (uint32_t)nu | ((uint32_t)(phase - 1) << 7) | (ord << 8);
-          }
-        } else if (lane == 0) {
-          raise_flag(A.status, kFlagSlotOverflow);
-        }
+      if ((int)readlane_d(ao, cnt_lane) >= P.cluster_min) {
+        put_candidate(A, R, ncand, lanes, m, ao, nu, phase, ord, lane);
         ++ncand;
       }
     };
@@ -950,22 +990,11 @@ __global__ void __launch_bounds__(64) k_roots_banks(RootsArgs A, const K *__rest
         int node = 0;
         bool in = false;
         if (valid) {
-          // octant = 4*[x>cx] + 2*[y>cy] + [z>cz] (strict >, cc:147-158); child centre = centre +- quarter (cc:163-165)
-          const int bx = px > cx, by = py > cy, bz = pz > cz;
-          const int o1 = 4 * bx + 2 * by + bz;
-          if (so < 0) {
-            node = o1;
-            in = true;
-          } else {
-            const double c1x = cx + (double)((float)(2 * bx - 1) * q0);
-            const double c1y = cy + (double)((float)(2 * by - 1) * q0);
-            const double c1z = cz + (double)((float)(2 * bz - 1) * q0);
-            node = 4 * (px > c1x) + 2 * (py > c1y) + (pz > c1z);
-            in = (o1 == so);
-          }
-          double *pr = s_prod + lane * kMom;
-          pr[0] = 1.0, pr[1] = pt, pr[2] = px, pr[3] = py, pr[4] = pz;
-          pr[5] = px * px, pr[6] = px * py, pr[7] = px * pz, pr[8] = py * py, pr[9] = py * pz, pr[10] = pz * pz;
+          int o1, o2;
+          point_octants(R, px, py, pz, o1, o2);
+          node = (so < 0) ? o1 : o2;
+          in = (so < 0) || (o1 == so);
+          put_moment_terms(s_prod + lane * kMom, 1, pt, px, py, pz);
         }
         // cluster boundaries, lane-parallel: a new cluster starts at a point whose gap to the previous point OF THE SAME
         // NODE exceeds cluster_gap (cc:24).  Predecessor inside the chunk: highest lower lane with the same child.
@@ -1028,7 +1057,6 @@ __global__ void __launch_bounds__(64) k_roots_banks(RootsArgs A, const K *__rest
         //      v_readlane for the masks, one LDS read, four EXEC-masked adds ----
         const unsigned long long GE = G0 | G1;
         unsigned long long todo = (PHASE == 1) ? ((nvalid == 64) ? ~0ull : ((1ull << nvalid) - 1ull)) : IN;
-        if (WC_DBG(P, 1)) todo = 0;  // development option debug_skip = 1: profiling experiments only
         while (todo) {
           const unsigned long long evs = GE & todo;
           unsigned long long seg = evs ? (todo & ((evs & (0ull - evs)) - 1ull)) : todo;  // the points in front of the next cluster end
@@ -1125,79 +1153,11 @@ __global__ void __launch_bounds__(64) k_roots_banks(RootsArgs A, const K *__rest
     }
     __threadfence_block();
     __syncthreads();
-    // ---- node tests of the 64 layer-2 nodes + their candidate clusters, one batch of 3x3 PCAs (as in k_roots<K, 2>) ----
-    const uint32_t ncap = (uint32_t)min((uint64_t)ncand, A.total_slots > slot_base ? A.total_slots - slot_base : 0);
-    unsigned long long plane_mask = 0;
-    for (uint32_t batch = 0;; ++batch) {
-      const bool node_lane = (batch == 0) && lane < ntab;
-      const int cand_lane0 = (batch == 0) ? ntab : 0;
-      const uint32_t cbase = cand_begin + (batch == 0 ? 0u : (uint32_t)(64 - ntab) + (batch - 1) * 64u);
-      const uint32_t c = cbase + (uint32_t)(lane - cand_lane0);
-      const bool cand_lane = lane >= cand_lane0 && c < ncap;
-      if (batch > 0 && cbase >= ncap) break;
-      double mom[kMom];
-      bool have = false;
-      int nu = 0;
-      uint32_t ord = 0;
-      uint64_t slot = 0;
-      if (node_lane) {
-        const bool exists = (split1 >> (lane >> 3)) & 1ull;
-        nu = lane;
-        if (exists && s_total[lane * kMom] > (double)P.min_points) {
-          have = true;
-          for (int i = 0; i < kMom; ++i) mom[i] = s_total[lane * kMom + i];
-        }
-      } else if (cand_lane) {
-        slot = slot_base + c;
-        const uint32_t meta = A.cand_meta[slot];
-        nu = (int)(meta & 0x7F);
-        ord = meta >> 8;
-        have = true;
-        for (int i = 0; i < kMom; ++i) mom[i] = A.cand[slot * kMom + i];
-      }
-      Pca rr;
-      if (have) pca_from_moments(mom, rr);
-      if (batch == 0) {
-        const bool plane = node_lane && have && (rr.ev[0] < P.thr) && (rr.like > P.min_like);  // cc:106-111
-        plane_mask = __ballot(plane);
-      }
-      bool ok = false;
-      if (cand_lane && have && ((plane_mask >> nu) & 1ull) && !(rr.ev[0] > P.thr || rr.like < P.min_like)) {  // cc:54
-        emit_surfel(A, rr, slot, 2, nu, ord, kx, ky, kz, q0);
-        ok = true;
-      }
-      emitted += (uint32_t)__popcll(__ballot(ok));
-    }
-    if (lane == 0 && emitted && !A.slot_counts) atomicAdd(&A.status[0], emitted);
+    count_surfels(A, finish_layer2(A, R, s_total, split1, cand_begin, ncand, lane), lane);
     __syncthreads();
   };
 
-  // ---- work items of this wavefront ----
-  if (PHASE == 2) {  // the queued split jobs, strided
-    for (uint32_t it = blockIdx.x; it < njobs; it += gridDim.x) {
-      const SplitJob job = A.split_jobs[it];
-      do_root(A.heads[job.slot], job.slot, job.ncand, job.split1);
-    }
-  } else if (RUNS) {  // compacted root list: one root per wavefront
-    RootLocator loc;
-    loc.init(A, lane);
-    for (uint32_t w = blockIdx.x; w < loc.total; w += gridDim.x) {
-      const uint32_t tslot = loc.slot_of(A, w);
-      do_root(A.heads[tslot], tslot, 0u, 0ull);
-    }
-  } else {  // sparse head table: every wavefront owns a contiguous range of slots
-    const uint32_t per_wave = (A.nslots + gridDim.x - 1) / gridDim.x;
-    const uint32_t it_end = min((blockIdx.x + 1) * per_wave, A.nslots);
-    for (uint32_t it = blockIdx.x * per_wave; it < it_end; it += 64) {
-      const uint32_t my_pos = (it + lane < it_end) ? A.heads[it + lane].pos : 0xFFFFFFFFu;
-      unsigned long long live_mask = __ballot(my_pos != 0xFFFFFFFFu);
-      while (live_mask) {
-        const int hb = __ffsll((long long)live_mask) - 1;
-        live_mask &= live_mask - 1;
-        do_root(HeadRec{(uint32_t)__shfl((int)my_pos, hb), 0u, 0u, 0u}, it + (uint32_t)hb, 0u, 0ull);
-      }
-    }
-  }
+  hand_out_roots<PHASE == 2 ? kSplitJobs : (RUNS ? kRootList : kHeadTable), 1>(A, lane, njobs, do_root);
 }
 
 // Node tests + emission of the layer-0/1 pass, THREE roots per wavefront.  One root offers 9 node tests and a dozen or so
@@ -1207,119 +1167,50 @@ __global__ void __launch_bounds__(64) k_roots_banks(RootsArgs A, const K *__rest
 // second loop, cc:32-64); later batches (rare) take 21 more candidates per group.
 template <typename K, bool RUNS>
 __global__ void __launch_bounds__(64) k_roots_emit(RootsArgs A, const K *__restrict__ keys) {
-  constexpr int G = 21, NG = 3;
+  constexpr int NG = 3, G = 64 / NG;
   const int lane = threadIdx.x;
   const ExParams &P = A.P;
-  constexpr int B = KeyTraits<K>::bits;
-  constexpr int half = 1 << (B - 1);
   const int g = lane / G, l = lane - g * G;
-  double x0, y0, z0;
-  ex_origin(A.pts, x0, y0, z0);
-  const int k0x = vox(x0, P.vs), k0y = vox(y0, P.vs), k0z = vox(z0, P.vs);
-  const float q0 = P.vs_f / 4;  // quarter_length_ of the root (cc:207)
+  const KeyOrigin org = key_origin(A);
 
   // one pass over up to NG roots; tslot = head table slot of this lane's group's root (~0: none)
-  auto do_roots = [&](uint32_t tslot) {
-      bool active = g < NG && tslot != 0xFFFFFFFFu;
-      HeadRec hrec{0u, 0u, 0u, 0u};
-      if (active) hrec = A.heads[tslot];
-      const uint64_t head = hrec.pos;
-      const uint32_t gidx_or = hrec.gidx;
-      const uint32_t ncand = active ? A.root_ncand[tslot] : 0u;  // side tables are indexed by table slot: no wait for hrec
-      K rootkey;
-      if (RUNS) {
-        const uint32_t gidx = gidx_or;
-        rootkey = (K)key_join(gidx / A.run_cap, comp_rest(A.runs[gidx]));
-      } else {
-        rootkey = keys[head];
+  auto do_roots = [&](const HeadRec hrec, uint32_t tslot, uint32_t, unsigned long long) {
+    bool active = tslot != 0xFFFFFFFFu;
+    const uint32_t ncand = active ? A.root_ncand[tslot] : 0u;  // side tables are indexed by table slot: no wait for hrec
+    const RootDesc R = root_desc<K, RUNS>(A, hrec, keys, org);
+    const uint32_t ncap = R.cand_cap(A, ncand);
+    uint32_t plane_mask = 0, split1 = 0, emitted = 0;
+    for (uint32_t batch = 0;; ++batch) {
+      const bool node_lane = active && batch == 0 && l < 9;
+      const uint32_t c = (batch == 0) ? (uint32_t)(l - 9) : (uint32_t)(G - 9) + (batch - 1) * G + (uint32_t)l;
+      const bool cand_lane = active && (batch > 0 || l >= 9) && c < ncap;
+      if (!__ballot(node_lane || cand_lane)) break;
+      LaneJob J;
+      lane_job(A, R, node_lane, A.node_tot + (size_t)tslot * (9 * kMom) + l * kMom, l, cand_lane, c, J);
+      if (batch == 0) {
+        const bool plane = node_lane && J.have && plane_gate(P, J.rr);
+        const int sh = (g < NG) ? g * G : 0;
+        plane_mask = (uint32_t)(__ballot(plane) >> sh) & 0x1FFu;
+        const bool root_tested = (__ballot(node_lane && J.have) >> sh) & 1ull;
+        if (!root_tested) active = false;  // n <= min_points: nothing below this root exists (cc:129)
+        const uint32_t nonplane = (uint32_t)(__ballot(node_lane && J.have && !plane) >> sh) & 0x1FFu;
+        split1 = (P.max_layer >= 2 && active) ? (nonplane >> 1) : 0u;  // tested layer-1 nodes that are not planes (cc:175-182)
       }
-      const int kx = (int)(rootkey & ((K(1) << B) - 1)) - half + k0x;
-      const int ky = (int)((rootkey >> B) & ((K(1) << B) - 1)) - half + k0y;
-      const int kz = (int)((rootkey >> (2 * B)) & ((K(1) << B) - 1)) - half + k0z;
-      const uint64_t slot_base = (head * (uint64_t)(P.max_layer + 1)) / (uint64_t)P.cluster_min;
-      const uint32_t ncap = (uint32_t)min((uint64_t)ncand, A.total_slots > slot_base ? A.total_slots - slot_base : 0);
-      uint32_t plane_mask = 0, split1 = 0, emitted = 0;
-      for (uint32_t batch = 0;; ++batch) {
-        const bool node_lane = active && batch == 0 && l < 9;
-        const uint32_t c = (batch == 0) ? (uint32_t)(l - 9) : (uint32_t)(G - 9) + (batch - 1) * G + (uint32_t)l;
-        const bool cand_lane = active && (batch > 0 || l >= 9) && c < ncap;
-        if (!__ballot(node_lane || cand_lane)) break;
-        double mom[kMom];
-        bool have = false;
-        int nu = 0;
-        uint32_t ord = 0;
-        uint64_t slot = 0;
-        if (node_lane) {
-          const double *tot = A.node_tot + (size_t)tslot * (9 * kMom) + l * kMom;
-          nu = l;
-          if (tot[0] > (double)P.min_points) {
-            have = true;
-            for (int i = 0; i < kMom; ++i) mom[i] = tot[i];
-          }
-        } else if (cand_lane) {
-          slot = slot_base + c;
-          const uint32_t meta = A.cand_meta[slot];
-          nu = (int)(meta & 0x7F);
-          ord = meta >> 8;
-          have = true;
-          for (int i = 0; i < kMom; ++i) mom[i] = A.cand[slot * kMom + i];
-        }
-        Pca rr;
-        if (have) pca_from_moments(mom, rr);
-        if (batch == 0) {
-          const bool plane = node_lane && have && (rr.ev[0] < P.thr) && (rr.like > P.min_like);  // cc:106-111
-          const int sh = (g < NG) ? g * G : 0;
-          plane_mask = (uint32_t)(__ballot(plane) >> sh) & 0x1FFu;
-          const bool root_tested = (__ballot(node_lane && have) >> sh) & 1ull;
-          if (!root_tested) active = false;  // n <= min_points: nothing below this root exists (cc:129)
-          const uint32_t nonplane = (uint32_t)(__ballot(node_lane && have && !plane) >> sh) & 0x1FFu;
-          split1 = (P.max_layer >= 2 && active) ? (nonplane >> 1) : 0u;  // tested layer-1 nodes that are not planes (cc:175-182)
-        }
-        bool ok = false;
-        if (cand_lane && active && have && ((plane_mask >> nu) & 1u) && !(rr.ev[0] > P.thr || rr.like < P.min_like)) {  // cc:54
-          emit_surfel(A, rr, slot, nu == 0 ? 0 : 1, nu, ord, kx, ky, kz, q0);
-          ok = true;
-        }
-        emitted += (uint32_t)__popcll(__ballot(ok));
+      bool ok = false;
+      if (cand_lane && active && J.have && ((plane_mask >> J.nu) & 1u) && cluster_gate(P, J.rr)) {
+        emit_surfel(A, J.rr, J.slot, J.nu == 0 ? 0 : 1, J.nu, J.ord, R.kx, R.ky, R.kz, R.q0);
+        ok = true;
       }
-      if (active && l == 0 && split1 != 0) {  // layer-2 pass needed: queue the root for k_roots<K, 2>
-        const uint32_t q = atomicAdd(&A.status[4], 1u);
-        A.split_jobs[q] = SplitJob{tslot, ncand, (unsigned long long)split1};
-      }
-      // without the slot histogram (general path) the surfel count is accumulated here
-      if (lane == 0 && emitted && !A.slot_counts) atomicAdd(&A.status[0], emitted);
+      emitted += (uint32_t)__popcll(__ballot(ok));
+    }
+    if (active && l == 0 && split1 != 0) {  // layer-2 pass needed: queue the root for the phase-2 kernel
+      const uint32_t q = atomicAdd(&A.status[4], 1u);
+      A.split_jobs[q] = SplitJob{tslot, ncand, (unsigned long long)split1};
+    }
+    count_surfels(A, emitted, lane);
   };
 
-  if (RUNS) {  // compacted root list: roots 3 w .. 3 w + 2
-    RootLocator loc;
-    loc.init(A, lane);
-    for (uint32_t w0 = blockIdx.x * NG; w0 < loc.total; w0 += gridDim.x * NG) {
-      uint32_t tslot = 0xFFFFFFFFu;
-      for (int k = 0; k < NG; ++k)
-        if (w0 + k < loc.total) {
-          const uint32_t sl = loc.slot_of(A, w0 + k);
-          if (g == k) tslot = sl;
-        }
-      do_roots(tslot);
-    }
-  } else {  // sparse head table: every wavefront owns a contiguous range of slots
-    const uint32_t per_wave = (A.nslots + gridDim.x - 1) / gridDim.x;
-    const uint32_t it_end = min((blockIdx.x + 1) * per_wave, A.nslots);
-    for (uint32_t it = blockIdx.x * per_wave; it < it_end; it += 64) {
-      const uint32_t my_pos = (it + lane < it_end) ? A.heads[it + lane].pos : 0xFFFFFFFFu;
-      unsigned long long live_mask = __ballot(my_pos != 0xFFFFFFFFu);
-      while (live_mask) {
-        uint32_t tslot = 0xFFFFFFFFu;
-        for (int k = 0; k < NG; ++k) {
-          if (!live_mask) break;
-          const int bit = __ffsll((long long)live_mask) - 1;
-          live_mask &= live_mask - 1;
-          if (g == k) tslot = it + (uint32_t)bit;
-        }
-        do_roots(tslot);
-      }
-    }
-  }
+  hand_out_roots<RUNS ? kRootList : kHeadTable, NG>(A, lane, 0u, do_roots);
 }
 
 __global__ void __launch_bounds__(256) k_iota(uint32_t *v, uint64_t n) {
@@ -2240,12 +2131,6 @@ int run_pipeline(wc_ctx *ctx, const ExPath &path) {
   ex_mark(ctx, 2);
   WC_TRY(wc_ensure(ctx, ctx->b_misc[5], (size_t)A.nslots * sizeof(SplitJob)));
   A.split_jobs = (SplitJob *)ctx->b_misc[5].p;
-  A.prof = nullptr;
-#ifdef WC_PROF_ROOTS
-  WC_TRY(wc_ensure(ctx, ctx->b_misc[6], (size_t)A.nslots * 32));
-  WC_HIP(ctx, hipMemsetAsync(ctx->b_misc[6].p, 0, (size_t)A.nslots * 32, st));
-  A.prof = (uint32_t *)ctx->b_misc[6].p;
-#endif
   WC_TRY(wc_ensure(ctx, ctx->b_misc[7], (size_t)A.nslots * (9 * kMom * 8 + 4)));
   A.node_tot = (double *)ctx->b_misc[7].p;
   A.root_ncand = (uint32_t *)(A.node_tot + (size_t)A.nslots * 9 * kMom);
@@ -2533,7 +2418,7 @@ extern "C" int wc_extract_stage_ms(wc_ctx *ctx, float *h_ms5) {
 }
 
 extern "C" int wc_debug_status(wc_ctx *ctx, uint32_t *h_out64) {
-  wc_dev_guard dg_(ctx);  // profiling aid: status words [0..16) + section timers
+  wc_dev_guard dg_(ctx);  // profiling aid: status words [0..16) + what the host side remembers of the sweep
   if (!ctx || !h_out64) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
   // (the device copy has been cleared for the next call already: words 0..15 come from the host mailbox of the last call)
   for (int i = 0; i < 64; ++i) h_out64[i] = i < 16 ? ctx->h_status[i] : 0u;
@@ -2545,21 +2430,6 @@ extern "C" int wc_debug_status(wc_ctx *ctx, uint32_t *h_out64) {
   h_out64[61] = ctx->ex.path.fx ? 1u : 0u;  // the last sweep was completed by the fast (integer-moment) path
   h_out64[62] = ctx->ex_mem.fx_last_flags;
   h_out64[63] = ctx->ex_mem.fx_last_why;  // bit i: call site i of fx_fallback() fired in the last sweep that fell back
-#ifdef WC_PROF_ROOTS
-  // average the per-root section timers into words [16, 24), number of timed roots in word 24
-  const size_t nslots = ctx->ex.pts.n / (size_t)(ctx->P.min_points + 1) + 1;
-  std::vector<uint32_t> rows(nslots * 8);
-  WC_HIP(ctx, hipMemcpy(rows.data(), ctx->b_misc[6].p, nslots * 32, hipMemcpyDeviceToHost));
-  double sum[8] = {0};
-  uint32_t cnt = 0;
-  for (size_t r = 0; r < nslots; ++r)
-    if (rows[r * 8 + 1]) {
-      ++cnt;
-      for (int i = 0; i < 8; ++i) sum[i] += rows[r * 8 + i];
-    }
-  for (int i = 0; i < 8; ++i) h_out64[16 + i] = cnt ? (uint32_t)(sum[i] / cnt) : 0;
-  h_out64[24] = cnt;
-#endif
   return WC_OK;
 }
 
