@@ -275,7 +275,27 @@ typedef struct wc_map_raycast_result { /* 32 bytes */
   uint64_t tested;       /* sum of the rays' `tested`                         */
 } wc_map_raycast_result;
 
-/* Communicator of a multi-GPU job: one process (and one wc_ctx) per GPU.  The library calls these for its few collectives;
+/* wc_map_components / wc_map_remove_small / wc_map_label_keys (wildcat_hip.h): which voxels are nodes and which of them are adjacent. */
+#define WC_MAP_NO_COMPONENT 0xFFFFFFFFu /* label of an occupied voxel that is not a node */
+#define WC_MAP_CC_DROP_SPARSE 1u        /* wc_map_remove_small: the occupied voxels that are not nodes are removed too */
+typedef struct wc_map_cc_params { /* 16 bytes */
+  uint32_t connectivity; /* 6, 18 or 26: the sum of |a - b| over the axes is at most 1, 2 or 3; anything else WC_ERR_ARG */
+  uint32_t min_points;   /* >= 1: an occupied voxel is a node when it holds at least this many points                  */
+  uint32_t flags;        /* 0 or WC_MAP_CC_DROP_SPARSE; any other bit WC_ERR_ARG                                       */
+  uint32_t reserved;     /* 0, anything else WC_ERR_ARG                                                                */
+} wc_map_cc_params;
+
+/* One connected component (wildcat_hip.h: wc_map_components).  40 bytes, 8-aligned; integers only, so every field is independent of
+ * order and schedule. */
+typedef struct wc_map_component {
+  uint32_t first;  /* export index of the root: the component's voxel of smallest (kx, ky, kz) */
+  uint32_t voxels; /* nodes in the component                                                   */
+  uint64_t points; /* ... and the points they hold                                             */
+  int32_t kmin[3]; /* the key bounding box, per axis                                           */
+  int32_t kmax[3];
+} wc_map_component;
+
+/* Communicator of a multi-GPU job: one process (and one wc_ctx) per GPU. The library calls these for its few collectives;
  * wc_comm_rccl_init() installs an in-library RCCL implementation, tests / other runtimes install callbacks.
  * All buffers are DEVICE pointers on the ctx's GPU; a callback returns 0 on success and must have completed (or be
  * stream-ordered on the ctx's stream) when it returns.  Byte counts are per rank, data consecutive in rank order. */

@@ -31,7 +31,8 @@ enum {
   WC_ERR_HIP = 10,      /* HIP runtime error                                                        */
   WC_ERR_ARG = 11,      /* bad argument                                                             */
   WC_ERR_NOGPU = 12,    /* no gfx950 device visible                                                 */
-  WC_ERR_NUMERIC = 13   /* linear solve failed                                                      */
+  WC_ERR_NUMERIC = 13,  /* linear solve failed                                                      */
+  WC_ERR_INTERNAL = 14  /* a bounded loop of a kernel ran past its bound: a defect, reported instead of a hang */
 };
 
 typedef struct wc_ctx wc_ctx;
@@ -84,6 +85,8 @@ int wc_ctx_set_params(wc_ctx *ctx, const wc_params *params);
  *                      value
  *   map_remove_groups (0) wc_map_remove_keys: workgroups of its kernel (0: chosen from the key count); the map and the three counts are
  *                      the same whatever the value
+ *   map_cc_groups (0)  wc_map_components, wc_map_remove_small: workgroups of their per-voxel kernels (0: chosen from the voxel count);
+ *                      every output byte and the map are the same whatever the value
  *   lm_radius0         initial trust-region radius of wc_window_solve: 10^value (default -1 = the library's 1e4); tests use it to
  *                      look at the first step at other damping levels
  * Tests use it to run both forms of a choice on the same data.  Unknown names return WC_ERR_ARG. */
@@ -475,6 +478,49 @@ int wc_map_carve_remove(wc_ctx *ctx, wc_map *m, const wc_points *pts, const doub
 int wc_map_remove_keys(wc_ctx *ctx, wc_map *m, const int32_t *d_keys, uint64_t n, uint64_t h_out[3]);
 /* h_out[2] = {tombstones in the table now, purges so far}; host state, no wait */
 int wc_map_tombstones(wc_ctx *ctx, wc_map *m, uint64_t h_out[2]);
+
+/* Connected components of the occupied voxels, and removal of the small ones.  params: wc_map_cc_params (wc_types.h).
+ *   nodes       the occupied voxels (tombstones are not voxels) whose point count is >= min_points.  min_points >= 1
+ *   edges       two nodes a, b are adjacent iff a != b, max_axis |a - b| == 1 and sum_axis |a - b| <= c, with c = 1, 2, 3 for
+ *               connectivity 6, 18, 26; any other value of connectivity is WC_ERR_ARG.  A neighbour index outside the key range
+ *               (|k_a| >= 2^20) does not exist: the packed key's 21-bit fields never wrap into another axis or to the other end of the range
+ *   component   the classes of the transitive closure
+ *   root        the root of a component is its voxel of smallest (kx, ky, kz), which is the smallest packed key
+ *   numbering   components are numbered 0 .. C-1 in ascending order of their root
+ *   labels      voxels are listed in the order of wc_map_export (ascending key); label[i] is the component number of export entry i; an
+ *               occupied voxel that is not a node gets WC_MAP_NO_COMPONENT = 0xFFFFFFFF
+ *   record      wc_map_component, 40 bytes, 8-aligned: first = export index of the root; voxels; points; kmin[3], kmax[3] = the key
+ *               bounding box.  All fields are integers, so every field is order independent
+ * A component is a function of the set of occupied keys (and their counts, through min_points) alone: every output is independent of
+ * table layout, grid size (development option map_cc_groups) and schedule, and a restatement on the exported map (tests/map_components_ref.py)
+ * reproduces it byte for byte.
+ *
+ * wc_map_components: d_keys (DEVICE, n x 3 int32, 4-aligned, may be NULL) receives the voxel indices and d_label (DEVICE, n uint32) the
+ * labels of the n occupied voxels, cap = the entries either holds; d_comps (DEVICE, 8-aligned, may be NULL) receives the C records, cap_comps
+ * = the records it holds.  h_out[4] = {voxels n, nodes, components C, voxels of the largest component}.  WC_ERR_CAPACITY with h_out filled
+ * when cap < n (nothing is written to d_keys / d_label) or when d_comps != NULL and cap_comps < C (nothing is written to d_comps).  An empty
+ * map is WC_OK with zeros.  The map is read, never written, and so is every scratch whose content another call of the map relies on: the
+ * call has a uint32 word per slot and its per-voxel arrays of its own (taken on the first call, grow-only), and shares only the export's
+ * sort buffers, which every export fills afresh.  The call waits.  Plain and WC_MAP_MOMENTS maps alike.
+ * WC_ERR_ARG: a NULL ctx, map, params or h_out; a map of another context; connectivity not 6 / 18 / 26; min_points = 0; an unknown flag;
+ * reserved != 0; a misaligned pointer; cap > 0 with d_label NULL.  WC_ERR_INTERNAL (map untouched): a bounded loop of the labelling
+ * ran past its bound. */
+int wc_map_components(wc_ctx *ctx, wc_map *m, const wc_map_cc_params *params, int32_t *d_keys, uint32_t *d_label, uint64_t cap,
+                      wc_map_component *d_comps, uint64_t cap_comps, uint64_t h_out[4]);
+/* Removes, in place and through tombstones (above), every voxel of a component with voxels < min_voxels or points < min_comp_points.  A
+ * threshold of 0 switches its test off; both 0 removes nothing.  With flag WC_MAP_CC_DROP_SPARSE it also removes the occupied voxels that
+ * are not nodes; without it they stay.  h_out[4] = {components before, components removed, voxels removed, points removed}.  After it the
+ * map is, through every call that reads it, bit for bit the map of the points whose voxel stayed.  The call is idempotent: components are
+ * disjoint, so what stays keeps its components, and a second call removes nothing.  The call waits.  Argument errors as wc_map_components;
+ * every error leaves the map as it was. */
+int wc_map_remove_small(wc_ctx *ctx, wc_map *m, const wc_map_cc_params *params, uint32_t min_voxels, uint64_t min_comp_points, uint64_t h_out[4]);
+/* The same function of an exported map on the host, without a GPU or a context: keys (n x 3 int32) and count (n uint32) as wc_map_export
+ * returns them; label_out (n uint32), comps_out (may be NULL; cap_comps records) and h_out as wc_map_components fills them.
+ * WC_ERR_ARG: keys that are not strictly ascending in (kx, ky, kz) (unsorted or duplicate) or have |k_a| >= 2^20; n > 2^31; a NULL
+ * argument (keys, count, label_out with n > 0; params; h_out); params as above.  WC_ERR_CAPACITY with h_out (and label_out) filled when
+ * comps_out != NULL and cap_comps < C. */
+int wc_map_label_keys(const int32_t *keys, const uint32_t *count, uint64_t n, const wc_map_cc_params *params, uint32_t *label_out,
+                      wc_map_component *comps_out, uint64_t cap_comps, uint64_t h_out[4]);
 
 /* Ray casting: what does the map put along a ray?  Every point p of `pts` (DEVICE pointers, the wc_points rules of wc_map_insert: either
  * stride, pts->time ignored) is the END of a ray from `origin` - ONE position for the whole call, in the map's frame; "in a direction up to

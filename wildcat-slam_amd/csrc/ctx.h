@@ -52,6 +52,7 @@ struct wc_dev_opts {
   int map_cast_groups = 0;   // wc_map_raycast: workgroups of k_map_raycast (0: by size) - the output bytes do not depend on it (tests)
   int map_carve_groups = 0;  // wc_map_carve: workgroups of k_map_carve (0: by size) - the result does not depend on it (tests)
   int map_remove_groups = 0; // wc_map_remove_keys: workgroups of k_map_remove_keys (0: by size) - the map and the counts do not depend on it (tests)
+  int map_cc_groups = 0;     // wc_map_components, wc_map_remove_small: workgroups of their per-voxel kernels (0: by size) - no output byte depends on it (tests)
   int map_absorb_groups = 0; // wc_map_absorb: workgroups of k_map_absorb (0: by size) - the map does not depend on it (tests)
   int lm_dense_radius = 7;   // iterations whose trust-region radius exceeds 10^value take the dense step (0: never)
   int lm_radius0 = -1;       // initial trust-region radius of a solve: 10^value (-1: the library's 1e4)

@@ -79,6 +79,7 @@ const DevOpt kDevOpts[] = {
     {"map_cast_groups", "WC_MAP_CAST_GROUPS", &wc_dev_opts::map_cast_groups, false},
     {"map_absorb_groups", "WC_MAP_ABSORB_GROUPS", &wc_dev_opts::map_absorb_groups, false},
     {"map_remove_groups", "WC_MAP_REMOVE_GROUPS", &wc_dev_opts::map_remove_groups, false},
+    {"map_cc_groups", "WC_MAP_CC_GROUPS", &wc_dev_opts::map_cc_groups, false},
     {"lm_dense_radius", "WC_LM_DENSE_RADIUS", &wc_dev_opts::lm_dense_radius, false},
     {"lm_radius0", "WC_LM_RADIUS0", &wc_dev_opts::lm_radius0, false},
 };

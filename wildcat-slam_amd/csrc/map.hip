@@ -48,6 +48,10 @@
 //   k_map_raycast  ray casting: the carve's ray and walk, read-only: one lane per ray, its M + 1 positions eight at a time - keys, hashes and
 //                   tested-flags of a batch, its first-slot key loads issued together, then the chains in ascending order up to the first
 //                   voxel with enough points - and one 48-byte wc_map_ray_hit per ray; no atomics but its four counters': wc_map_raycast
+//   k_map_cc_index / _link / _flatten / _clear / _stats / _select / _erase  connected components of the occupied voxels: a per-slot index
+//                   word, lock-free union-find over the export order (every access to the parent array an agent-scope atomic, every
+//                   loop bounded), pointer jumping in a launch of its own, a rocPRIM scan of the root flags, integer atomics per component;
+//                   the last one writes tombstones: wc_map_components, wc_map_remove_small
 //   k_map_state    state export: one lane per sorted voxel: the slot's integer sums themselves -> wc_map_voxel (+ nine moment words)
 //   k_map_absorb   state records added back by key (map_slot, then four / thirteen no-return atomic adds): wc_map_absorb
 //   k_map_merge    the same for every occupied slot of another map's table: wc_map_merge
@@ -109,6 +113,11 @@ struct wc_map {
   uint64_t h_score_cap = 0;
   wc_buf b_ct;                       // wc_map_linearize_ct: the tile partials (80 words each) and every level of their reduction; its own scratch
   unsigned long long *h_ct = nullptr;  // ... and the pinned landing place of the final partial, 640 bytes (first use)
+  wc_buf b_cc_idx;                   // wc_map_components / wc_map_remove_small: one u32 word per slot, slot -> export index (first use, grown with the table)
+  wc_buf b_cc;                       // ... their counter lines, then four u32 arrays per export entry: parent, root, root flag, component number
+  wc_buf b_cc_comps;                 // ... the C records, then one u32 selection word per component
+  wc_buf b_cc_tmp;                   // ... rocPRIM's temporary of the scan; all four are this feature's own scratch
+  unsigned long long *h_cc = nullptr;  // ... and the pinned landing place of the counters (first use)
 };
 
 namespace {
@@ -1590,6 +1599,298 @@ __global__ void __launch_bounds__(kCastThreads) k_map_raycast(wc_points pts, map
   block_count<kCastThreads>({n_cast, n_skip, n_hit, n_tested}, {cctr + kCastCast, cctr + kCastSkip, cctr + kCastHits, cctr + kCastTested});
 }
 
+// ---- connected components (wc_map_components, wc_map_remove_small: DESIGN 8.14) -------------------------------------------------------
+constexpr int kCcThreads = 256;
+constexpr uint32_t kCcNone = 0xFFFFFFFFu;  // WC_MAP_NO_COMPONENT: in the per-slot index and the parent array, a voxel that is not a node
+constexpr int kCcNodes = 0, kCcComps = 16, kCcLargest = 32, kCcErr = 48, kCcRmComps = 64, kCcRmVox = 80, kCcRmPts = 96,
+              kCcCtrWords = 112;  // u64 word of each of the calls' counters
+// the 13 lexicographically negative offsets of the 27-neighbourhood: the 3 faces, then the 6 edges, then the 4 corners, so that
+// connectivity 6 / 18 / 26 is the first 3 / 9 / 13 of them.  The same table on the host (wc_map_label_keys)
+__host__ __device__ constexpr int cc_off(int j, int a) {
+  constexpr int t[13][3] = {{-1, 0, 0},  {0, -1, 0},  {0, 0, -1},  {-1, -1, 0}, {-1, 1, 0},  {-1, 0, -1}, {-1, 0, 1},
+                            {0, -1, -1}, {0, -1, 1},  {-1, -1, -1}, {-1, -1, 1}, {-1, 1, -1}, {-1, 1, 1}};
+  return t[j][a];
+}
+__host__ __device__ constexpr int cc_lower(uint32_t connectivity) { return connectivity == 6 ? 3 : (connectivity == 18 ? 9 : 13); }
+__host__ __device__ __forceinline__ bool cc_in_range(int k) { return k > -kMapKeyOff && k < kMapKeyOff; }
+
+// The parent array inside the link launch: EVERY access is an agent-scope atomic (a load that bypasses the CU's L1, a compare-and-swap or a
+// minimum at L2) - workgroups read here the words other workgroups write in the same launch, and a plain load could follow a stale L1 line
+// for ever
+__device__ __forceinline__ uint32_t cc_load(uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// Unites the trees of a and b.  Invariant of the array: parent[x] <= x, and only a root (parent[x] == x) is ever hooked, under a smaller
+// root - parents only ever decrease, so the root that remains of a component is its smallest index.  `a` is ANY member of the lane's own
+// component (the lane's entry at first) and comes back as the root the call ended on, where the lane's next call starts: in a settled
+// region the neighbour's parent IS that root, and the call is one load that does not touch the root's own word - the one word every lane
+// of a large component would otherwise load twice per neighbour.  No lane waits for another: `steps` counts every load and every
+// compare-and-swap of the call against `budget` (8 n + 64, derived below); false: the budget ran out
+__device__ __forceinline__ bool cc_unite(uint32_t *parent, uint32_t &a, uint32_t b, unsigned long long budget) {
+  unsigned long long steps = 0;
+  while (true) {
+    // the two walks to a root, b's first.  Termination: every iteration replaces x by parent[x] < x, so a walk from x takes at most x
+    // iterations whatever other lanes do meanwhile (they only lower parents); on the way x's link is shortened to its grandparent (a
+    // minimum: the word only decreases and keeps pointing at an ancestor).  b's walk ends early when it meets a: one component already
+#pragma unroll
+    for (int w = 1; w >= 0; --w) {
+      uint32_t x = w ? b : a;
+      uint32_t p = cc_load(parent + x);
+      ++steps;
+      while (p != x && !(w && p == a)) {
+        if (++steps > budget) return false;
+        const uint32_t g = cc_load(parent + p);
+        if (g != p) __hip_atomic_fetch_min(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        x = p, p = g;
+      }
+      if (w && p == a) return true;  // (a is an ancestor of b, or b itself)
+      if (w)
+        b = x;
+      else
+        a = x;
+    }
+    if (a == b) return true;
+    const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
+    uint32_t seen = hi;
+    if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+      a = lo;
+      return true;
+    }
+    // a failed compare-and-swap means another lane lowered parent[hi] (seen < hi): hi is no root any more.  The pair goes on from
+    // (seen, lo), strictly below (hi, lo): over the whole call a + b decreases with every walk step and every failure, so there are at
+    // most a + b <= 2 n of them, each with at most three loads and one compare-and-swap - the budget of 8 n + 64 is never reached
+    if (++steps > budget) return false;
+    a = seen, b = lo;
+  }
+}
+
+// the per-slot index and the parent array: export entry i of a node into idx[its slot] and parent[i]; kCcNone for an occupied voxel with
+// fewer than min_points points.  Only occupied slots' words are written, and only those are ever read (a probe ends on the key)
+__global__ void __launch_bounds__(kCcThreads) k_map_cc_index(const uint32_t *sslots, uint64_t n, const long long *pay, unsigned min_points, uint32_t *idx,
+                                                             uint32_t *parent, unsigned long long *cctr) {
+  unsigned long long nodes = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * kCcThreads;
+  for (uint64_t i = (uint64_t)blockIdx.x * kCcThreads + threadIdx.x; i < n; i += stride) {
+    const uint32_t slot = sslots[i];
+    const bool node = (unsigned long long)pay[4 * (uint64_t)slot + 3] >= min_points;
+    const uint32_t w = node ? (uint32_t)i : kCcNone;
+    idx[slot] = w;
+    parent[i] = w;
+    nodes += node;
+  }
+  block_count<kCcThreads>({nodes}, {cctr + kCcNodes});
+}
+
+// one lane per export entry, grid-strided: the NB lower neighbours of a node - their keys, hashes and range tests, their first-slot key
+// loads issued together (as k_map_nearest does per plane of nine), then the chains (read-only: the table is not written here), one word
+// of the index per neighbour found, and a cc_unite per neighbour that is a node.  Every register array is indexed by the unrolled loops'
+// constants.  A lane whose cc_unite runs out of budget counts itself in *err and leaves: the host reports WC_ERR_INTERNAL
+template <int NB>
+__global__ void __launch_bounds__(kCcThreads) k_map_cc_link(const unsigned long long *skeys, uint64_t n, const unsigned long long *keys,
+                                                            unsigned long long mask, const uint32_t *idx, uint32_t *parent,
+                                                            unsigned long long budget, unsigned long long *err) {
+  const uint64_t stride = (uint64_t)gridDim.x * kCcThreads;
+  for (uint64_t i = (uint64_t)blockIdx.x * kCcThreads + threadIdx.x; i < n; i += stride) {
+    if (cc_load(parent + i) == kCcNone) continue;  // (not a node: the word never changes)
+    const unsigned long long key = skeys[i];
+    const int kx = map_unpack(key, 0), ky = map_unpack(key, 1), kz = map_unpack(key, 2);
+    unsigned long long nk[NB], c[NB];
+    uint32_t h[NB];
+    uint32_t mine = (uint32_t)i;  // (a member of this lane's component: cc_unite moves it to the root it ends on)
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      const int x = kx + cc_off(j, 0), y = ky + cc_off(j, 1), z = kz + cc_off(j, 2);
+      const bool ok = cc_in_range(x) && cc_in_range(y) && cc_in_range(z);  // (a neighbour outside the key range does not exist: no field wraps)
+      nk[j] = map_pack(x, y, z);
+      h[j] = (uint32_t)(map_hash(nk[j]) & mask);
+      c[j] = ok ? keys[h[j]] : kMapEmpty;
+    }
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      if (c[j] == kMapEmpty) continue;  // (out of range, or an empty first slot: absent)
+      unsigned long long hh = h[j];
+      if (!map_find_from(keys, mask, nk[j], hh, c[j])) continue;
+      const uint32_t other = idx[hh];
+      if (other == kCcNone) continue;
+      if (!cc_unite(parent, mine, other, budget)) {
+        atomicAdd(err, 1ull);
+        return;
+      }
+    }
+  }
+}
+
+// a separate launch: the parent array is only read here (what the link launch wrote), so plain loads.  root[i] = the root of i's tree, its
+// component's smallest index; flag[i] = 1 for a root; kCcNone / 0 for a voxel that is not a node.  The walk strictly decreases: at most
+// i steps; the bound guards a broken array
+__global__ void __launch_bounds__(kCcThreads) k_map_cc_flatten(const uint32_t *parent, uint64_t n, uint32_t *root, uint32_t *flag,
+                                                               unsigned long long *cctr) {
+  unsigned long long roots = 0, bad = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * kCcThreads;
+  for (uint64_t i = (uint64_t)blockIdx.x * kCcThreads + threadIdx.x; i < n; i += stride) {
+    uint32_t x = (uint32_t)i, p = parent[i];
+    if (p == kCcNone) {
+      root[i] = kCcNone, flag[i] = 0;
+      continue;
+    }
+    uint64_t steps = 0;
+    while (p != x && p < x && steps <= n) x = p, p = parent[x], ++steps;
+    bad += p != x;
+    root[i] = x;
+    flag[i] = x == (uint32_t)i;
+    roots += x == (uint32_t)i;
+  }
+  block_count<kCcThreads>({roots, bad}, {cctr + kCcComps, cctr + kCcErr});
+}
+
+__global__ void __launch_bounds__(kCcThreads) k_map_cc_clear(wc_map_component *comps, uint64_t C) {
+  const uint64_t stride = (uint64_t)gridDim.x * kCcThreads;
+  for (uint64_t c = (uint64_t)blockIdx.x * kCcThreads + threadIdx.x; c < C; c += stride) {
+    wc_map_component r;
+    r.first = 0, r.voxels = 0, r.points = 0;
+    r.kmin[0] = r.kmin[1] = r.kmin[2] = INT32_MAX;
+    r.kmax[0] = r.kmax[1] = r.kmax[2] = INT32_MIN;
+    comps[c] = r;
+  }
+}
+
+// the sums and bounds a wavefront holds for ONE component, lane by lane, until cc_flush reduces them across the wavefront and lane 0
+// issues the eight integer atomics
+struct cc_acc {
+  unsigned vox = 0;
+  unsigned long long pts = 0;
+  int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+};
+__device__ __forceinline__ void cc_flush(cc_acc &acc, uint32_t comp, wc_map_component *comps, unsigned lane) {
+  const unsigned vox = wave_sum(acc.vox);
+  const unsigned long long pts = wave_sum(acc.pts);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+#pragma unroll
+    for (int o = 32; o; o >>= 1) acc.lo[a] = min(acc.lo[a], __shfl_down(acc.lo[a], o)), acc.hi[a] = max(acc.hi[a], __shfl_down(acc.hi[a], o));
+  }
+  if (lane == 0 && vox) {
+    wc_map_component *c = comps + comp;
+    atomicAdd(&c->voxels, vox);
+    atomicAdd((unsigned long long *)&c->points, pts);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) atomicMin(&c->kmin[a], acc.lo[a]), atomicMax(&c->kmax[a], acc.hi[a]);
+  }
+  acc = cc_acc{};
+}
+// labels and records: num[] is the exclusive scan of the root flags, so a component's number is num[its root].  Every wavefront takes a
+// CONTIGUOUS run of 64-entry tiles of the export order.  While the nodes of its tiles all lie in one component (the rule in key order:
+// a wall is thousands of consecutive entries) each lane adds its own entries up in registers, and the wavefront issues its eight
+// integer atomics once per run of tiles (Guideline 12: a large component's record is ONE line, and an atomic per tile on it was the
+// whole cost of the call); a tile with nodes of several components issues one set per distinct component.  Integers: no order matters.  Reads only
+// what earlier launches wrote
+__global__ void __launch_bounds__(kCcThreads) k_map_cc_stats(const unsigned long long *skeys, const uint32_t *sslots, uint64_t n, const long long *pay,
+                                                             const uint32_t *root, const uint32_t *num, uint32_t *label, int32_t *keys_out,
+                                                             wc_map_component *comps) {
+  const unsigned lane = threadIdx.x & 63u;
+  const uint64_t wave = ((uint64_t)blockIdx.x * kCcThreads + threadIdx.x) >> 6, waves = (uint64_t)gridDim.x * (kCcThreads / 64);
+  const uint64_t tiles = (n + 63) / 64, per = (tiles + waves - 1) / waves;
+  const uint64_t t_end = wave * per + per < tiles ? wave * per + per : tiles;
+  cc_acc acc;
+  uint32_t cur = kCcNone;  // (the component the accumulators belong to: the same in every lane)
+  // (the bounds are the wavefront's: every lane of a wavefront takes the same trips, so the cross-lane operations are whole)
+  for (uint64_t t = wave * per; t < t_end; ++t) {
+    const uint64_t i = t * 64 + lane;
+    uint32_t comp = kCcNone;
+    unsigned long long cnt = 0;
+    int k[3] = {0, 0, 0};
+    if (i < n) {
+      const unsigned long long key = skeys[i];
+      const uint32_t r = root[i];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) k[a] = map_unpack(key, a);
+      if (keys_out) keys_out[3 * i] = k[0], keys_out[3 * i + 1] = k[1], keys_out[3 * i + 2] = k[2];
+      if (r != kCcNone) {
+        comp = num[r];
+        cnt = (unsigned long long)pay[4 * (uint64_t)sslots[i] + 3];
+        if (r == (uint32_t)i) comps[comp].first = r;  // (the one writer of this word)
+      }
+      if (label) label[i] = comp;
+    }
+    const unsigned long long nodes = __ballot(comp != kCcNone);
+    if (!nodes) continue;
+    const uint32_t c0 = (uint32_t)__shfl((int)comp, __ffsll((long long)nodes) - 1);
+    const bool one = __all(comp == c0 || comp == kCcNone);
+    if (cur != kCcNone && !(one && c0 == cur)) {
+      cc_flush(acc, cur, comps, lane);
+      cur = kCcNone;
+    }
+    if (one) {
+      cur = c0;
+      if (comp != kCcNone) {
+        acc.vox += 1, acc.pts += cnt;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) acc.lo[a] = min(acc.lo[a], k[a]), acc.hi[a] = max(acc.hi[a], k[a]);
+      }
+    } else {
+      // several components in one tile (the rings a spinning lidar leaves on a floor interleave in key order): one reduction and one
+      // set of atomics per DISTINCT component of the tile, not per node - a loop of at most 64 wavefront-uniform trips
+      unsigned long long left = nodes;
+      while (left) {
+        const uint32_t c = (uint32_t)__shfl((int)comp, __ffsll((long long)left) - 1);
+        const bool mine = comp == c;
+        cc_acc part;
+        if (mine) {
+          part.vox = 1, part.pts = cnt;
+#pragma unroll
+          for (int a = 0; a < 3; ++a) part.lo[a] = part.hi[a] = k[a];
+        }
+        cc_flush(part, c, comps, lane);
+        left &= ~__ballot(mine);
+      }
+    }
+  }
+  if (cur != kCcNone) cc_flush(acc, cur, comps, lane);
+}
+
+// over the C records: the largest component's voxels; with sel != NULL (wc_map_remove_small) sel[c] = 1 for a component below a
+// threshold that is switched on, and their number
+__global__ void __launch_bounds__(kCcThreads) k_map_cc_select(const wc_map_component *comps, uint64_t C, uint32_t min_voxels,
+                                                              unsigned long long min_points, uint32_t *sel, unsigned long long *cctr) {
+  unsigned long long largest = 0, gone = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * kCcThreads;
+  for (uint64_t c = (uint64_t)blockIdx.x * kCcThreads + threadIdx.x; c < C; c += stride) {
+    const uint32_t v = comps[c].voxels;
+    const unsigned long long p = comps[c].points;
+    largest = largest > v ? largest : (unsigned long long)v;
+    if (sel) {
+      const bool s = (min_voxels && v < min_voxels) || (min_points && p < min_points);
+      sel[c] = s;
+      gone += s;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    const unsigned long long other = __shfl_down(largest, o);
+    largest = largest > other ? largest : other;
+  }
+  if ((threadIdx.x & 63) == 0 && largest) atomicMax(cctr + kCcLargest, largest);
+  block_count<kCcThreads>({gone}, {cctr + kCcRmComps});
+}
+
+// wc_map_remove_small's pass over the export entries: the slot of every voxel of a selected component (and, with drop_sparse, of every
+// voxel that is not a node) gets the tombstone by a plain 8-byte store - no lane of this launch reads a key -, and the counters move as
+// k_map_erase moves them
+__global__ void __launch_bounds__(kCcThreads) k_map_cc_erase(const uint32_t *sslots, uint64_t n, const uint32_t *root, const uint32_t *num,
+                                                             const uint32_t *sel, unsigned drop_sparse, unsigned long long *keys, const long long *pay,
+                                                             unsigned long long *cctr, unsigned long long *ctr) {
+  unsigned long long nv = 0, np = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * kCcThreads;
+  for (uint64_t i = (uint64_t)blockIdx.x * kCcThreads + threadIdx.x; i < n; i += stride) {
+    const uint32_t r = root[i];
+    const bool gone = r == kCcNone ? drop_sparse != 0 : sel[num[r]] != 0;
+    if (!gone) continue;
+    const uint64_t slot = sslots[i];
+    keys[slot] = kMapTomb;
+    ++nv;
+    np += (unsigned long long)pay[4 * slot + 3];
+  }
+  block_count<kCcThreads>({nv, np, 0ull - nv, 0ull - np}, {cctr + kCcRmVox, cctr + kCcRmPts, ctr + kCtrOcc, ctr + kCtrPts});
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 int map_alloc(wc_ctx *ctx, void **p, size_t bytes) {
   *p = nullptr;
@@ -1732,6 +2033,10 @@ extern "C" int wc_map_destroy(wc_ctx *ctx, wc_map *m) {
   wc_buf_release(ctx, m->b_cast);
   wc_buf_release(ctx, m->b_score);
   wc_buf_release(ctx, m->b_ct);
+  wc_buf_release(ctx, m->b_cc_idx);
+  wc_buf_release(ctx, m->b_cc);
+  wc_buf_release(ctx, m->b_cc_comps);
+  wc_buf_release(ctx, m->b_cc_tmp);
   (void)hipStreamSynchronize(ctx->stream);  // (the pinned counters may still be the target of an enqueued copy)
   if (m->ev_ctr) (void)hipEventDestroy(m->ev_ctr);
   if (m->h_ctr) (void)hipHostFree(m->h_ctr);
@@ -1741,6 +2046,7 @@ extern "C" int wc_map_destroy(wc_ctx *ctx, wc_map *m) {
   if (m->h_cast) (void)hipHostFree(m->h_cast);
   if (m->h_score) (void)hipHostFree(m->h_score);
   if (m->h_ct) (void)hipHostFree(m->h_ct);
+  if (m->h_cc) (void)hipHostFree(m->h_cc);
   delete m;
   return WC_OK;
 }
@@ -2958,4 +3264,218 @@ extern "C" int wc_map_raycast(wc_ctx *ctx, wc_map *m, const wc_points *pts, cons
     h_out->hits = m->h_cast[kCastHits], h_out->tested = m->h_cast[kCastTested];
   }
   return WC_OK;
+}
+
+// ---- connected components (include/wildcat_hip.h: wc_map_components, wc_map_remove_small, wc_map_label_keys) -------------
+namespace {
+bool cc_params_ok(const wc_map_cc_params *p) {
+  return p && (p->connectivity == 6 || p->connectivity == 18 || p->connectivity == 26) && p->min_points >= 1 &&
+         !(p->flags & ~(uint32_t)WC_MAP_CC_DROP_SPARSE) && p->reserved == 0;
+}
+constexpr const char *kCcParamsText = "connectivity 6, 18 or 26, min_points >= 1, flags: WC_MAP_CC_DROP_SPARSE, reserved = 0";
+
+// what one run of the labelling leaves in the map's scratch, until the next call that uses it
+struct cc_run {
+  uint64_t n = 0, nodes = 0, comps = 0, largest = 0;
+  unsigned long long *skeys = nullptr;  // the export's sorted pairs
+  uint32_t *sslots = nullptr;
+  unsigned long long *cctr = nullptr;
+  uint32_t *root = nullptr, *num = nullptr, *sel = nullptr;
+  wc_map_component *d_comps = nullptr;
+  unsigned grid = 1;
+};
+unsigned cc_grid(const wc_ctx *ctx, const wc_map *m, uint64_t items) {
+  const uint64_t blocks = std::max<uint64_t>((items + kCcThreads - 1) / kCcThreads, 1);
+  uint64_t grid = std::min<uint64_t>(blocks, (uint64_t)8 * m->cus);
+  if (ctx->dev.map_cc_groups > 0) grid = std::min<uint64_t>(blocks, (uint64_t)ctx->dev.map_cc_groups);  // (development option)
+  return (unsigned)grid;
+}
+// the labelling of the map as it stands: index, link, flatten, scan, then - the component count read back - records and the largest.
+// d_label / d_keys (either may be NULL) are written by the stats pass; want_sel: the selection words of wc_map_remove_small.  Waits twice
+int cc_core(wc_ctx *ctx, wc_map *m, const wc_map_cc_params *p, uint32_t *d_label, int32_t *d_keys, bool want_sel, uint32_t min_voxels,
+            uint64_t min_comp_points, cc_run *R, const char *fn) {
+  WC_TRY(map_sync_counters(ctx, m));
+  const uint64_t n = R->n = m->h_ctr[kCtrOcc];
+  if (n == 0) return WC_OK;
+  WC_TRY(map_sorted_slots(ctx, m, n, &R->skeys, &R->sslots));
+  WC_TRY(wc_ensure(ctx, m->b_cc_idx, (size_t)m->cap * 4));
+  WC_TRY(wc_ensure(ctx, m->b_cc, (size_t)kCcCtrWords * 8 + (size_t)n * 16));
+  if (!m->h_cc) WC_HIP(ctx, hipHostMalloc((void **)&m->h_cc, kCcCtrWords * 8));
+  unsigned long long *cctr = R->cctr = (unsigned long long *)m->b_cc.p;
+  uint32_t *idx = (uint32_t *)m->b_cc_idx.p, *parent = (uint32_t *)(cctr + kCcCtrWords), *root = parent + n, *flag = root + n, *num = flag + n;
+  R->root = root, R->num = num;
+  WC_HIP(ctx, hipMemsetAsync(cctr, 0, (size_t)kCcCtrWords * 8, ctx->stream));
+  const unsigned grid = R->grid = cc_grid(ctx, m, n);
+  k_map_cc_index<<<grid, kCcThreads, 0, ctx->stream>>>(R->sslots, n, m->pay, p->min_points, idx, parent, cctr);
+  WC_HIP(ctx, hipGetLastError());
+  const unsigned long long budget = 8ull * n + 64;
+  if (p->connectivity == 6)
+    k_map_cc_link<3><<<grid, kCcThreads, 0, ctx->stream>>>(R->skeys, n, m->keys, m->cap - 1, idx, parent, budget, cctr + kCcErr);
+  else if (p->connectivity == 18)
+    k_map_cc_link<9><<<grid, kCcThreads, 0, ctx->stream>>>(R->skeys, n, m->keys, m->cap - 1, idx, parent, budget, cctr + kCcErr);
+  else
+    k_map_cc_link<13><<<grid, kCcThreads, 0, ctx->stream>>>(R->skeys, n, m->keys, m->cap - 1, idx, parent, budget, cctr + kCcErr);
+  WC_HIP(ctx, hipGetLastError());
+  k_map_cc_flatten<<<grid, kCcThreads, 0, ctx->stream>>>(parent, n, root, flag, cctr);
+  WC_HIP(ctx, hipGetLastError());
+  size_t tmp = 0;
+  WC_HIP(ctx, rocprim::exclusive_scan(nullptr, tmp, flag, num, 0u, (size_t)n, rocprim::plus<uint32_t>(), ctx->stream));
+  WC_TRY(wc_ensure(ctx, m->b_cc_tmp, tmp));
+  tmp = m->b_cc_tmp.cap;
+  WC_HIP(ctx, rocprim::exclusive_scan(m->b_cc_tmp.p, tmp, flag, num, 0u, (size_t)n, rocprim::plus<uint32_t>(), ctx->stream));
+  WC_HIP(ctx, hipMemcpyAsync(m->h_cc, cctr, kCcCtrWords * 8, hipMemcpyDeviceToHost, ctx->stream));
+  WC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the first wait: the records' buffer is sized from the component count)
+  if (m->h_cc[kCcErr])
+    return wc_fail(ctx, WC_ERR_INTERNAL, "%s: %llu lanes of the labelling ran past their loop bound (the map is untouched)", fn, m->h_cc[kCcErr]);
+  R->nodes = m->h_cc[kCcNodes];
+  const uint64_t C = R->comps = m->h_cc[kCcComps];
+  WC_TRY(wc_ensure(ctx, m->b_cc_comps, (size_t)std::max<uint64_t>(C, 1) * (sizeof(wc_map_component) + 4)));
+  R->d_comps = (wc_map_component *)m->b_cc_comps.p;
+  R->sel = (uint32_t *)(R->d_comps + std::max<uint64_t>(C, 1));
+  if (C) {
+    k_map_cc_clear<<<cc_grid(ctx, m, C), kCcThreads, 0, ctx->stream>>>(R->d_comps, C);
+    WC_HIP(ctx, hipGetLastError());
+  }
+  if (C || d_label || d_keys) {
+    // (two wavefronts per CU, each on a contiguous run of tiles: the fewer wavefronts, the fewer atomics on a large component's record)
+    unsigned sgrid = (unsigned)std::min<uint64_t>(grid, (uint64_t)std::max(m->cus / 2, 1));
+    if (ctx->dev.map_cc_groups > 0) sgrid = grid;
+    k_map_cc_stats<<<sgrid, kCcThreads, 0, ctx->stream>>>(R->skeys, R->sslots, n, m->pay, root, num, d_label, d_keys, R->d_comps);
+    WC_HIP(ctx, hipGetLastError());
+  }
+  if (C) {
+    k_map_cc_select<<<cc_grid(ctx, m, C), kCcThreads, 0, ctx->stream>>>(R->d_comps, C, min_voxels, min_comp_points, want_sel ? R->sel : nullptr, cctr);
+    WC_HIP(ctx, hipGetLastError());
+    WC_HIP(ctx, hipMemcpyAsync(m->h_cc, cctr, kCcCtrWords * 8, hipMemcpyDeviceToHost, ctx->stream));
+    WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    R->largest = m->h_cc[kCcLargest];
+  }
+  return WC_OK;
+}
+}  // namespace
+
+extern "C" int wc_map_components(wc_ctx *ctx, wc_map *m, const wc_map_cc_params *params, int32_t *d_keys, uint32_t *d_label, uint64_t cap,
+                                 wc_map_component *d_comps, uint64_t cap_comps, uint64_t h_out[4]) {
+  wc_dev_guard dg_(ctx);
+  if (!map_ok(ctx, m) || !h_out || (uintptr_t)d_keys % 4 || (uintptr_t)d_label % 4 || (uintptr_t)d_comps % 8 || (cap && !d_label))
+    return wc_fail(ctx, WC_ERR_ARG, "%s: null or misaligned argument, cap > 0 without d_label, or a map of another context", __func__);
+  if (!cc_params_ok(params)) return wc_fail(ctx, WC_ERR_ARG, "%s: params out of range (%s)", __func__, kCcParamsText);
+  h_out[0] = h_out[1] = h_out[2] = h_out[3] = 0;
+  WC_TRY(map_sync_counters(ctx, m));
+  const uint64_t n = m->h_ctr[kCtrOcc];
+  if (n == 0) return WC_OK;
+  const bool fits = cap >= n;
+  cc_run R;
+  WC_TRY(cc_core(ctx, m, params, fits ? d_label : nullptr, fits ? d_keys : nullptr, false, 0, 0, &R, __func__));
+  h_out[0] = R.n, h_out[1] = R.nodes, h_out[2] = R.comps, h_out[3] = R.largest;
+  const bool comps_fit = !d_comps || cap_comps >= R.comps;
+  if (d_comps && comps_fit && R.comps)
+    WC_HIP(ctx, hipMemcpyAsync(d_comps, R.d_comps, (size_t)R.comps * sizeof(wc_map_component), hipMemcpyDeviceToDevice, ctx->stream));
+  WC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the call waits: labels, keys and records are there on return)
+  if (!fits) return wc_fail(ctx, WC_ERR_CAPACITY, "%s: %llu voxels, capacity %llu", __func__, (unsigned long long)n, (unsigned long long)cap);
+  if (!comps_fit)
+    return wc_fail(ctx, WC_ERR_CAPACITY, "%s: %llu components, capacity %llu", __func__, (unsigned long long)R.comps, (unsigned long long)cap_comps);
+  return WC_OK;
+}
+
+extern "C" int wc_map_remove_small(wc_ctx *ctx, wc_map *m, const wc_map_cc_params *params, uint32_t min_voxels, uint64_t min_comp_points,
+                                   uint64_t h_out[4]) {
+  wc_dev_guard dg_(ctx);
+  if (!map_ok(ctx, m) || !h_out) return wc_fail(ctx, WC_ERR_ARG, "%s: null argument or a map of another context", __func__);
+  if (!cc_params_ok(params)) return wc_fail(ctx, WC_ERR_ARG, "%s: params out of range (%s)", __func__, kCcParamsText);
+  h_out[0] = h_out[1] = h_out[2] = h_out[3] = 0;
+  cc_run R;
+  WC_TRY(cc_core(ctx, m, params, nullptr, nullptr, true, min_voxels, min_comp_points, &R, __func__));
+  h_out[0] = R.comps;
+  const unsigned drop = (params->flags & WC_MAP_CC_DROP_SPARSE) ? 1u : 0u;
+  const uint64_t sel_comps = R.comps ? m->h_cc[kCcRmComps] : 0;
+  if (R.n == 0 || (!sel_comps && !(drop && R.nodes < R.n))) return WC_OK;  // (nothing selected: nothing is launched, no tombstone is written)
+  k_map_cc_erase<<<R.grid, kCcThreads, 0, ctx->stream>>>(R.sslots, R.n, R.root, R.num, R.sel, drop, m->keys, m->pay, R.cctr, m->ctr);
+  WC_HIP(ctx, hipGetLastError());
+  WC_HIP(ctx, hipMemcpyAsync(m->h_cc, R.cctr, kCcCtrWords * 8, hipMemcpyDeviceToHost, ctx->stream));
+  WC_TRY(map_sync_counters(ctx, m));  // (the wait; the map's counters are exact again and a pending copy has landed)
+  h_out[1] = sel_comps, h_out[2] = m->h_cc[kCcRmVox], h_out[3] = m->h_cc[kCcRmPts];
+  m->tombs += h_out[2];
+  return WC_OK;
+}
+
+extern "C" int wc_map_label_keys(const int32_t *keys, const uint32_t *count, uint64_t n, const wc_map_cc_params *params, uint32_t *label_out,
+                                 wc_map_component *comps_out, uint64_t cap_comps, uint64_t h_out[4]) {
+  if (!h_out || !cc_params_ok(params) || n > ((uint64_t)1 << 31) || (n && (!keys || !count || !label_out))) return WC_ERR_ARG;
+  auto pack = [](int kx, int ky, int kz) {
+    return ((uint64_t)(kx + kMapKeyOff) << 42) | ((uint64_t)(ky + kMapKeyOff) << 21) | (uint64_t)(kz + kMapKeyOff);
+  };
+  std::vector<uint64_t> pk(n);
+  for (uint64_t i = 0; i < n; ++i) {
+    const int32_t *k = keys + 3 * i;
+    if (!cc_in_range(k[0]) || !cc_in_range(k[1]) || !cc_in_range(k[2])) return WC_ERR_ARG;
+    pk[i] = pack(k[0], k[1], k[2]);
+    if (i && pk[i] <= pk[i - 1]) return WC_ERR_ARG;  // (unsorted, or a key twice)
+  }
+  // union-find over the export order: the larger root under the smaller, so a component's root is its smallest index
+  std::vector<uint32_t> parent(n);
+  uint64_t nodes = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const bool node = count[i] >= params->min_points;
+    parent[i] = node ? (uint32_t)i : kCcNone;
+    nodes += node;
+  }
+  auto find = [&](uint32_t x) {
+    uint32_t r = x;
+    while (parent[r] != r) r = parent[r];
+    while (parent[x] != r) {
+      const uint32_t nx = parent[x];
+      parent[x] = r;
+      x = nx;
+    }
+    return r;
+  };
+  const int nb = cc_lower(params->connectivity);
+  for (uint64_t i = 0; i < n; ++i) {
+    if (parent[i] == kCcNone) continue;
+    const int32_t *k = keys + 3 * i;
+    for (int j = 0; j < nb; ++j) {
+      const int x = k[0] + cc_off(j, 0), y = k[1] + cc_off(j, 1), z = k[2] + cc_off(j, 2);
+      if (!cc_in_range(x) || !cc_in_range(y) || !cc_in_range(z)) continue;
+      const uint64_t q = pack(x, y, z);
+      const auto it = std::lower_bound(pk.begin(), pk.begin() + i, q);  // (a lower neighbour: a smaller key, an earlier entry)
+      if (it == pk.begin() + i || *it != q) continue;
+      const uint32_t o = (uint32_t)(it - pk.begin());
+      if (parent[o] == kCcNone) continue;
+      const uint32_t a = find((uint32_t)i), b = find(o);
+      if (a != b) parent[std::max(a, b)] = std::min(a, b);
+    }
+  }
+  std::vector<uint32_t> num(n, kCcNone);
+  uint64_t C = 0;
+  for (uint64_t i = 0; i < n; ++i)
+    if (parent[i] == (uint32_t)i) num[i] = (uint32_t)C++;
+  std::vector<uint32_t> vox(C, 0);
+  const bool comps_fit = !comps_out || cap_comps >= C;
+  const bool write = comps_out && comps_fit;
+  for (uint64_t c = 0; write && c < C; ++c) {
+    wc_map_component r;
+    std::memset(&r, 0, sizeof(r));
+    r.kmin[0] = r.kmin[1] = r.kmin[2] = INT32_MAX;
+    r.kmax[0] = r.kmax[1] = r.kmax[2] = INT32_MIN;
+    comps_out[c] = r;
+  }
+  uint64_t largest = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (parent[i] == kCcNone) {
+      label_out[i] = kCcNone;
+      continue;
+    }
+    const uint32_t r = find((uint32_t)i), c = num[r];
+    label_out[i] = c;
+    largest = std::max<uint64_t>(largest, ++vox[c]);
+    if (!write) continue;
+    wc_map_component &o = comps_out[c];
+    if (r == (uint32_t)i) o.first = r;
+    o.voxels += 1;
+    o.points += count[i];
+    for (int a = 0; a < 3; ++a) o.kmin[a] = std::min(o.kmin[a], keys[3 * i + a]), o.kmax[a] = std::max(o.kmax[a], keys[3 * i + a]);
+  }
+  h_out[0] = n, h_out[1] = nodes, h_out[2] = C, h_out[3] = largest;
+  return comps_fit ? WC_OK : WC_ERR_CAPACITY;
 }

@@ -768,6 +768,30 @@ bool LidarOdometry::RemoveMapVoxels(const int32_t *keys, size_t n, uint64_t out[
   if (n) CheckCall(ctx_, "wc_h2d", wc_h2d(ctx_, d_keys.p, keys, n * 3 * sizeof(int32_t)));
   return wc_map_remove_keys(ctx_, map_, (const int32_t *)d_keys.p, n, out) == WC_OK;
 }
+bool LidarOdometry::MapComponents(const wc_map_cc_params &params, int32_t *keys, uint32_t *labels, size_t cap, wc_map_component *comps,
+                                  size_t cap_comps, uint64_t out[4]) {
+  if (!map_ || !out) return false;
+  // (device room for what the caller can take: a call with too little of either fills out[] and writes nothing there)
+  const DevBuf d_keys(ctx_, keys ? cap * 3 * sizeof(int32_t) : 0), d_labels(ctx_, labels ? cap * sizeof(uint32_t) : 0),
+      d_comps(ctx_, comps ? std::max<size_t>(cap_comps, 1) * sizeof(wc_map_component) : 0);
+  uint64_t o[4] = {0, 0, 0, 0};
+  const int rc = wc_map_components(ctx_, map_, &params, (int32_t *)d_keys.p, (uint32_t *)d_labels.p, labels ? cap : 0, (wc_map_component *)d_comps.p,
+                                   comps ? cap_comps : 0, o);
+  if (rc != WC_OK && rc != WC_ERR_CAPACITY) return false;  // (as in AlignToMap)
+  std::memcpy(out, o, sizeof(o));
+  if (rc != WC_OK) return false;
+  if (o[0] && keys) d_keys.ToHost(keys, o[0] * 3 * sizeof(int32_t));
+  if (o[0] && labels) d_labels.ToHost(labels, o[0] * sizeof(uint32_t));
+  if (o[2] && comps) d_comps.ToHost(comps, o[2] * sizeof(wc_map_component));
+  return true;
+}
+bool LidarOdometry::RemoveSmallMapComponents(const wc_map_cc_params &params, uint32_t min_voxels, uint64_t min_comp_points, uint64_t out[4]) {
+  if (!map_ || !out) return false;
+  uint64_t o[4] = {0, 0, 0, 0};
+  if (wc_map_remove_small(ctx_, map_, &params, min_voxels, min_comp_points, o) != WC_OK) return false;  // (as in AlignToMap)
+  std::memcpy(out, o, sizeof(o));
+  return true;
+}
 bool LidarOdometry::SetMapCarve(double range, uint32_t shell, uint32_t min_rays) {
   if (!(range >= 0.0) || shell > 8 || min_rays < 1) return false;
   config_.map_carve_range = range, config_.map_carve_shell = shell, config_.map_carve_min_rays = min_rays;

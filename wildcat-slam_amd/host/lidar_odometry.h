@@ -150,6 +150,17 @@ class LidarOdometry {
   // wc_map_remove_keys for n host voxel indices (keys: n x 3 int32): out[3] = voxels removed, points removed, keys that removed nothing.
   // false - nothing touched - without a map, with out null, or with n > 0 and keys null
   bool RemoveMapVoxels(const int32_t *keys, size_t n, uint64_t out[3]);
+  // wc_map_components of the map into host arrays: labels (cap entries; null: a query for the sizes) and keys (cap x 3; may be null) in
+  // ExportMap's order, comps (cap_comps records; may be null), out[4] = voxels, nodes, components, voxels of the largest.  false without a
+  // map, with out null, with params the library refuses (out untouched), or when cap or cap_comps is too small (out filled, nothing
+  // else written).  The map is not modified.  Nothing in AddLidarScan calls it
+  bool MapComponents(const wc_map_cc_params &params, int32_t *keys, uint32_t *labels, size_t cap, wc_map_component *comps, size_t cap_comps,
+                     uint64_t out[4]);
+  // wc_map_remove_small: out[4] = components before, components removed, voxels removed, points removed; false - nothing touched - without
+  // a map, with out null or with params the library refuses.  Nothing in AddLidarScan calls it, and there is no per-sweep option: a
+  // surface first seen at the edge of range is a small component for a sweep or two, and removing it every sweep would restart its sums
+  // from zero each time - when to call it is the caller's policy
+  bool RemoveSmallMapComponents(const wc_map_cc_params &params, uint32_t min_voxels, uint64_t min_comp_points, uint64_t out[4]);
   // config().map_carve_range / _shell / _min_rays (the per-sweep carve; range 0 = off); false - nothing changed - for a negative or NaN
   // range, shell > 8 or min_rays < 1
   bool SetMapCarve(double range, uint32_t shell, uint32_t min_rays);

@@ -264,6 +264,15 @@ int wc_odom_map_carve_remove(void *h, const float *xyz, uint64_t n, const double
 int wc_odom_map_remove_keys(void *h, const int32_t *keys, uint64_t n, uint64_t out3[3]) {
   return ((LidarOdometry *)h)->RemoveMapVoxels(keys, n, out3) ? 1 : 0;
 }
+// LidarOdometry::MapComponents (host arrays; keys, comps and - for a size query - labels may be null) and RemoveSmallMapComponents;
+// 1 = done, 0 = no map, refused arguments, or (wc_odom_map_components, out4 filled) too little room
+int wc_odom_map_components(void *h, const wc_map_cc_params *params, int32_t *keys, uint32_t *labels, uint64_t cap, wc_map_component *comps,
+                           uint64_t cap_comps, uint64_t out4[4]) {
+  return params && ((LidarOdometry *)h)->MapComponents(*params, keys, labels, cap, comps, cap_comps, out4) ? 1 : 0;
+}
+int wc_odom_map_remove_small(void *h, const wc_map_cc_params *params, uint32_t min_voxels, uint64_t min_comp_points, uint64_t out4[4]) {
+  return params && ((LidarOdometry *)h)->RemoveSmallMapComponents(*params, min_voxels, min_comp_points, out4) ? 1 : 0;
+}
 // LioConfig::map_carve_range / _shell / _min_rays; returns 0, or WC_ERR_ARG for a negative or NaN range, shell > 8 or min_rays < 1
 int wc_odom_set_map_carve(void *h, double range, uint32_t shell, uint32_t min_rays) {
   return ((LidarOdometry *)h)->SetMapCarve(range, shell, min_rays) ? 0 : WC_ERR_ARG;

@@ -846,6 +846,36 @@ def map_score_top(scores, M, min_hit=0):
     return idx[: cnt.value].copy()
 
 
+def map_cc_params(connectivity=26, min_points=1, drop_sparse=False, reserved=0):
+    """a wc_map_cc_params record (PointMap.components, .remove_small, map_label_keys)"""
+    return R.MapCcParams(int(connectivity), int(min_points), R.MAP_CC_DROP_SPARSE if drop_sparse else 0, int(reserved))
+
+
+_CC_OUT = ("voxels", "nodes", "components", "largest")
+
+
+def map_label_keys(keys, counts, connectivity=26, min_points=1, cap_comps=None, params=None):
+    """wc_map_label_keys (needs no GPU): the connected components of an exported map - keys (n, 3) int32 strictly ascending, counts (n,)
+    uint32, as PointMap.export() returns them -> (labels (n,) uint32, MAP_COMPONENT array, dict(voxels, nodes, components, largest)).
+    cap_comps (tests): the records' capacity; when it is too small a WildcatError with code WC_ERR_CAPACITY carries the dict as .out"""
+    keys = np.ascontiguousarray(keys, np.int32).reshape(-1, 3)
+    counts = np.ascontiguousarray(counts, np.uint32).reshape(-1)
+    assert len(counts) == len(keys), "one count per key"
+    n = len(keys)
+    p = params if params is not None else map_cc_params(connectivity, min_points)
+    labels = np.zeros(max(n, 1), np.uint32)
+    comps = np.zeros(max(n if cap_comps is None else int(cap_comps), 1), R.MAP_COMPONENT)
+    out = (C.c_uint64 * 4)()
+    rc = load().wc_map_label_keys(R.ptr(keys) if n else None, R.ptr(counts) if n else None, C.c_uint64(n), C.byref(p), R.ptr(labels), R.ptr(comps),
+                                  C.c_uint64(n if cap_comps is None else int(cap_comps)), out)
+    res = dict(zip(_CC_OUT, [int(x) for x in out]))
+    if rc != WC_OK:
+        e = WildcatError(rc, "wc_map_label_keys: " + ("capacity" if rc == WC_ERR_CAPACITY else "refused its arguments"))
+        e.out = res if rc == WC_ERR_CAPACITY else None
+        raise e
+    return labels[:n].copy(), comps[: res["components"]].copy(), res
+
+
 class PointMap:
     """wc_map: the device-resident voxel-downsampled map (DownSamplingVoxel, surfel_extraction.cc:228-261, over every insert)"""
 
@@ -958,6 +988,45 @@ class PointMap:
         out = (C.c_uint64 * 2)()
         self.ctx._ck(self.lib.wc_map_tombstones(self.ctx.h, self.h, out))
         return int(out[0]), int(out[1])
+
+    def components_device(self, params, d_keys, d_label, cap, d_comps, cap_comps):
+        """labels (and voxel indices, component records: either may be None) into HBM (wc_map_components) -> (return code,
+        dict(voxels, nodes, components, largest)): WC_ERR_CAPACITY leaves the needed counts in the dict"""
+        out = (C.c_uint64 * 4)()
+        rc = self.lib.wc_map_components(self.ctx.h, self.h, C.byref(params), C.c_void_p(d_keys.ptr if d_keys else 0),
+                                        C.c_void_p(d_label.ptr if d_label else 0), C.c_uint64(int(cap)), C.c_void_p(d_comps.ptr if d_comps else 0),
+                                        C.c_uint64(int(cap_comps)), out)
+        return rc, dict(zip(_CC_OUT, [int(x) for x in out]))
+
+    def components(self, connectivity=26, min_points=1):
+        """the connected components of the occupied voxels with at least min_points points under 6 / 18 / 26 connectivity -> (keys (n, 3)
+        int32 in export()'s order, labels (n,) uint32 - MAP_NO_COMPONENT for a voxel below min_points -, MAP_COMPONENT array in ascending
+        order of the components' smallest key, dict(voxels, nodes, components, largest))"""
+        p = map_cc_params(connectivity, min_points)
+        rc, res = self.components_device(p, None, None, 0, None, 0)
+        n, nc = res["voxels"], res["components"]
+        if n == 0:
+            self.ctx._ck(rc)
+            return np.zeros((0, 3), np.int32), np.zeros(0, np.uint32), np.zeros(0, R.MAP_COMPONENT), res
+        if rc not in (WC_OK, WC_ERR_CAPACITY):
+            self.ctx._ck(rc)
+        bk, bl, bc = self.ctx.alloc(12 * n), self.ctx.alloc(4 * n), self.ctx.alloc(R.MAP_COMPONENT.itemsize * max(nc, 1))
+        try:
+            rc, res = self.components_device(p, bk, bl, n, bc, nc)
+            self.ctx._ck(rc)
+            return (bk.download(np.int32, 3 * n).reshape(-1, 3), bl.download(np.uint32, n), bc.download(R.MAP_COMPONENT, res["components"]), res)
+        finally:
+            for b in (bk, bl, bc):
+                b.free()
+
+    def remove_small(self, min_voxels, min_comp_points=0, connectivity=26, min_points=1, drop_sparse=False):
+        """removes in place every component with fewer than min_voxels voxels or fewer than min_comp_points points (0: that test is off);
+        drop_sparse: the voxels below min_points too (wc_map_remove_small) -> dict(components, components_removed, voxels_removed,
+        points_removed)"""
+        p = map_cc_params(connectivity, min_points, drop_sparse)
+        out = (C.c_uint64 * 4)()
+        self.ctx._ck(self.lib.wc_map_remove_small(self.ctx.h, self.h, C.byref(p), C.c_uint32(int(min_voxels)), C.c_uint64(int(min_comp_points)), out))
+        return dict(zip(("components", "components_removed", "voxels_removed", "points_removed"), [int(x) for x in out]))
 
     def raycast_device(self, desc, origin, params, d_hits, want_result=True):
         """points already in HBM (a wc_points descriptor) as the ends of rays from origin -> MAP_RAY_HIT records in d_hits
@@ -1574,6 +1643,28 @@ class Odometry:
         if not self.lib.wc_odom_map_remove_keys(self.h, R.ptr(keys) if len(keys) else None, C.c_uint64(len(keys)), out):
             return None
         return dict(zip(("voxels_removed", "points_removed", "keys_unused"), [int(x) for x in out]))
+
+    def map_components(self, connectivity=26, min_points=1):
+        """wc_map_components of the facade's map (LidarOdometry::MapComponents) -> (keys, labels, MAP_COMPONENT array, dict(voxels, nodes,
+        components, largest)) as PointMap.components(), or None without a map or with arguments the library refuses"""
+        p, out = map_cc_params(connectivity, min_points), (C.c_uint64 * 4)()
+        f = self.lib.wc_odom_map_components
+        if not f(self.h, C.byref(p), None, None, C.c_uint64(0), None, C.c_uint64(0), out):  # (the sizes; 1 only for an empty map)
+            if not out[0]:
+                return None
+        n, nc = int(out[0]), int(out[2])
+        keys, labels, comps = np.zeros((max(n, 1), 3), np.int32), np.zeros(max(n, 1), np.uint32), np.zeros(max(nc, 1), R.MAP_COMPONENT)
+        if n and not f(self.h, C.byref(p), R.ptr(keys), R.ptr(labels), C.c_uint64(n), R.ptr(comps), C.c_uint64(nc), out):
+            return None
+        return keys[:n], labels[:n], comps[:nc], dict(zip(_CC_OUT, [int(x) for x in out]))
+
+    def map_remove_small(self, min_voxels, min_comp_points=0, connectivity=26, min_points=1, drop_sparse=False):
+        """wc_map_remove_small of the facade's map (LidarOdometry::RemoveSmallMapComponents) -> dict(components, components_removed,
+        voxels_removed, points_removed), or None without a map or with arguments the library refuses"""
+        p, out = map_cc_params(connectivity, min_points, drop_sparse), (C.c_uint64 * 4)()
+        if not self.lib.wc_odom_map_remove_small(self.h, C.byref(p), C.c_uint32(int(min_voxels)), C.c_uint64(int(min_comp_points)), out):
+            return None
+        return dict(zip(("components", "components_removed", "voxels_removed", "points_removed"), [int(x) for x in out]))
 
     def set_map_carve(self, max_range, shell=1, min_rays=2):
         """LioConfig::map_carve_range / _shell / _min_rays: after every sweep's insert the sweep's own rays remove the voxels they

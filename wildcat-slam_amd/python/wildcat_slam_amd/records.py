@@ -60,6 +60,12 @@ assert MAP_SCORE.itemsize == 16
 MAP_RAY_HIT = np.dtype([("xyz", "f4", 3), ("count", "u4"), ("key", "i4", 3), ("flags", "u4"), ("t", "f8"), ("step", "u4"), ("tested", "u4")])
 assert MAP_RAY_HIT.itemsize == 48 and [MAP_RAY_HIT.fields[f][1] for f in ("count", "key", "flags", "t", "step", "tested")] == [12, 16, 28, 32, 40, 44]
 
+# wc_map_component: one connected component of the occupied voxels (wc_map_components, wc_map_label_keys)
+MAP_COMPONENT = np.dtype([("first", "u4"), ("voxels", "u4"), ("points", "u8"), ("kmin", "i4", 3), ("kmax", "i4", 3)])
+assert MAP_COMPONENT.itemsize == 40 and [MAP_COMPONENT.fields[f][1] for f in ("voxels", "points", "kmin", "kmax")] == [4, 8, 16, 28]
+MAP_NO_COMPONENT = 0xFFFFFFFF  # WC_MAP_NO_COMPONENT
+MAP_CC_DROP_SPARSE = 1  # WC_MAP_CC_DROP_SPARSE
+
 assert SURFEL.itemsize == 144 and POSE.itemsize == 56 and IMU_STATE.itemsize == 112 and PAIR.itemsize == 8
 assert SURFEL_ID.itemsize == 16 and POINT.itemsize == 48
 
@@ -168,6 +174,12 @@ class MapScoreParams(C.Structure):
     """wc_map_score_params"""
 
     _fields_ = [("min_points", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MapCcParams(C.Structure):
+    """wc_map_cc_params"""
+
+    _fields_ = [("connectivity", C.c_uint32), ("min_points", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class MapAlignOpts(C.Structure):
