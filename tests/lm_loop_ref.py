@@ -138,6 +138,17 @@ def longest_rejected_run_before_acceptance(trace):
     return best
 
 
+SWITCH = 1e7  # 10^lm_dense_radius: above it the default form takes the dense step
+
+
+def expected_retries(prob, trace, form, upto=None):
+    """dense re-tries: the rejected iterations that came from the elimination - the default form, four sample states or more, a
+    radius at or below the switch"""
+    if form != "default" or prob["ns"] < 4:
+        return 0
+    return sum(r.kind == REJECTED and r.radius <= SWITCH for r in trace[:upto])
+
+
 def last_rejection(trace):
     """1-based iteration of the last rejected (or invalid) step, 0 if none"""
     return max([i + 1 for i, r in enumerate(trace) if r.kind in (REJECTED, INVALID)] or [0])

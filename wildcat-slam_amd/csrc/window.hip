@@ -41,6 +41,7 @@
 
 #include "ctx.h"
 #include "dmath.h"
+#include "lm_loop.h"
 #include "so3_fused.h"
 
 using namespace wc;
@@ -79,6 +80,30 @@ struct FarJob {  // a block pair more than two sample blocks apart with at most 
 struct WinParams {
   double sigma0_sq, cauchy_b, inv_cauchy_b, w_gyr, w_acc, w_bg, w_ba, dt, grav[3];
   int quirks, ns, fix_first;
+};
+
+// The solver's mailbox: kMailWords doubles on the device (W->mail); the kernels that post (gather_post, k_post_reduce, k_post_cost,
+// k_sum_blocks) mirror its first kMailMirror words into the pinned one (ctx->h_mail), whose words behind them are the host's alone.
+enum MailWord : int {
+  kMailCost = 0,         // cost and ...
+  kMailGmax = 1,         // ... max |g| of the linearisation a step starts from (or of a stand-alone linearisation / evaluation)
+  kMailModelChange = 2,  // lm_step: the step's model cost change, ...
+  kMailStepNorm = 3,     // ... |step| ...
+  kMailXNorm = 4,        // ... and |x|
+  kMailCandCost = 5,     // cost and ...
+  kMailCandGmax = 6,     // ... max |g| at the candidate
+  kMailFail = 32,        // (an int) the factorisations' fail flag
+  kMailMirror = 40,      // words [0, kMailMirror) travel to the pinned mailbox
+  kMailLate = 40,        // pinned only, + parity of W->lin_count: the two-collective form's late max |g| (k_expand_corners)
+  kMailTicket = 48,      // pinned: the ticket wait_mail reads; device: the four check sums of wc_window_build_sharded
+  kMailSurfelCost = 52,  // two-collective form: the surfel factors' cost + a spare word (the 16-byte collective), ...
+  kMailImuCost = 54,     // ... the replicated IMU factors' cost ...
+  kMailEvalCost = 55,    // ... and where an evaluation's k_post_cost puts the sum it has no linearisation buffer for
+  kMailGatherDone = 60,  // k_gather: g / cost workgroups finished (uint32, zero at rest) ...
+  kMailGatherMax = 61,   // ... and the bits of their maximum of |g| (zero at rest)
+  kMailStepDone = 62,    // k_schur_bias_y_step: workgroups finished (uint32, zero at rest)
+  kMailWords = 64,
+  kMailStage = 64,       // pinned only: the candidate lm_step stages (the window's unknowns)
 };
 
 }  // namespace
@@ -1014,14 +1039,14 @@ __device__ __forceinline__ double gather_pair_sum(const Src *src, const double *
 // k_post_reduce inside k_gather: called by every thread of the ns + 1 workgroups that wrote g / the cost; local_max (thread 0) =
 // max |g| over the entries this workgroup wrote (0 for the cost workgroup).  The host's mailbox leaves while the block-pair
 // workgroups of the launch are still summing.  No fence and no second look at g: a workgroup publishes its maximum with an atomic
-// maximum on the bits of the (non-negative) double - mail[61], zero at rest - and the cost workgroup stores the cost atomically,
+// maximum on the bits of the (non-negative) double - mail[kMailGatherMax], zero at rest - and the cost workgroup stores the cost atomically,
 // both at agent scope and acknowledged (vmcnt) before the workgroup is counted; the workgroup that counts last reads the two words
 // back atomically.  (Rounds 3 - 4: a __threadfence() in every workgroup, another in the last one, which then read all of g again -
 // two L2 write-backs of ~3.5 us each and a round of loads at the end of every linearisation.)
 __device__ __forceinline__ void gather_post(const GatherArgs &a, double local_max) {
   __shared__ uint32_t s_last;
   const int tid = threadIdx.x;
-  unsigned long long *gm = (unsigned long long *)(a.mail + 61);
+  unsigned long long *gm = (unsigned long long *)(a.mail + kMailGatherMax);
   if (tid == 0) {
     if (local_max > 0.0)  // (a NaN entry is skipped, as fmax did)
       (void)__hip_atomic_fetch_max(gm, (unsigned long long)__double_as_longlong(local_max), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1032,7 +1057,7 @@ __device__ __forceinline__ void gather_post(const GatherArgs &a, double local_ma
   if (!s_last || tid >= 64) return;
   const double mx = __longlong_as_double((long long)__hip_atomic_load(gm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
   const double cost = __hip_atomic_load(&a.cost[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (a.host_mail && tid < 40) a.host_mail[tid] = (tid == a.mail_slot) ? cost : (tid == a.mail_slot + 1 ? mx : a.mail[tid]);
+  if (a.host_mail && tid < kMailMirror) a.host_mail[tid] = (tid == a.mail_slot) ? cost : (tid == a.mail_slot + 1 ? mx : a.mail[tid]);
   if (tid == 0) {
     a.mail[a.mail_slot] = cost;
     a.mail[a.mail_slot + 1] = mx;
@@ -1041,7 +1066,7 @@ __device__ __forceinline__ void gather_post(const GatherArgs &a, double local_ma
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the wavefront's 40 stores to the pinned mailbox
     if (tid == 0) {
       __threadfence_system();
-      __hip_atomic_store((unsigned long long *)(a.host_mail + 48), a.ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store((unsigned long long *)(a.host_mail + kMailTicket), a.ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
   if (tid == 0) {
@@ -1443,19 +1468,19 @@ __global__ void __launch_bounds__(64) k_expand_corners(const double *red, uint32
   if (I != J) H[(size_t)gj * n + gi] = v;  // (a diagonal block's thread (u, w) owns entry (u, w) alone: (w, u) is thread (w, u)'s)
 }
 
-// the linearisation's cost = the IMU factors' (every rank's own sum: mail[54]) + the surfel factors' (summed over the ranks: mail[52]),
+// the linearisation's cost = the IMU factors' (every rank's own sum: mail[kMailImuCost]) + the surfel factors' (summed over the ranks: mail[kMailSurfelCost]),
 // sent to the host as soon as the 16-byte collective is through
 __global__ void __launch_bounds__(64) k_post_cost(double *mail, int slot, double *cost_out, double *host_mail, unsigned long long ticket) {
   const int tid = threadIdx.x;
-  const double c = mail[54] + mail[52];
+  const double c = mail[kMailImuCost] + mail[kMailSurfelCost];
   if (tid == 0) mail[slot] = c, cost_out[0] = c;
   if (host_mail) {
-    if (tid < 40) host_mail[tid] = tid == slot ? c : mail[tid];
+    if (tid < kMailMirror) host_mail[tid] = tid == slot ? c : mail[tid];
     if (ticket) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       if (tid == 0) {
         __threadfence_system();
-        __hip_atomic_store((unsigned long long *)(host_mail + 48), ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store((unsigned long long *)(host_mail + kMailTicket), ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
   }
@@ -1516,7 +1541,7 @@ __global__ void __launch_bounds__(256) k_eval_imu(WinParams wp, const ImuRec *re
   if (threadIdx.x == 0) block_cost[blockIdx.x] = s[0];
 }
 
-// (host_mail != null: the whole 40-double mailbox is stored to pinned host memory right here - the copy node that would
+// (host_mail != null: the mailbox's kMailMirror words are stored to pinned host memory right here - the copy node that would
 // follow is a 4 us blit kernel on the critical path of every LM iteration)
 __global__ void __launch_bounds__(1024) k_sum_blocks(const double *v, uint32_t n, double *mail, int slot, double *host_mail) {
   __shared__ double s[1024];
@@ -1532,7 +1557,7 @@ __global__ void __launch_bounds__(1024) k_sum_blocks(const double *v, uint32_t n
   if (tid == 0) mail[slot] = s[0];
   if (host_mail) {
     __syncthreads();
-    if (tid < 40) host_mail[tid] = (tid == slot) ? s[0] : mail[tid];
+    if (tid < kMailMirror) host_mail[tid] = (tid == slot) ? s[0] : mail[tid];
   }
 }
 
@@ -2218,8 +2243,8 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // z_j -= L[block k rows][j] . y_k for the chunk's j left of block k; L and Linv of a step do not depend on y and are
 // loaded before the step's first barrier.
 // candidate point and the scalars the trust-region logic needs:
-//   xc = x - y * scale ; mail[2] = model_cost_change = (y.gs + sum D y^2) / 2 ; mail[3] = |step| ; mail[4] = |x|
-//   mail[0] = cost, mail[1] = max |g| of the linearisation this step starts from (what k_post_reduce writes after a
+//   xc = x - y * scale ; mail[kMailModelChange] = (y.gs + sum D y^2) / 2 ; mail[kMailStepNorm] = |step| ; mail[kMailXNorm] = |x|
+//   mail[kMailCost] = cost, mail[kMailGmax] = max |g| of the linearisation this step starts from (what k_post_reduce writes after a
 //   stand-alone linearisation; inside the LM loop that launch is saved)
 // Runs at the end of the LAST back-substitution launch (the workgroup that has just finished y; a launch of its own was 5 - 6 us
 // of every LM iteration).
@@ -2255,11 +2280,11 @@ __device__ __forceinline__ void lm_step(const double *x, const double *y, const 
     __syncthreads();
   }
   if (tid == 0) {
-    mail[2] = 0.5 * s0[0];
-    mail[3] = sqrt(s1[0]);
-    mail[4] = sqrt(s2[0]);
-    mail[0] = lin_cost[0];
-    mail[1] = s3[0];
+    mail[kMailModelChange] = 0.5 * s0[0];
+    mail[kMailStepNorm] = sqrt(s1[0]);
+    mail[kMailXNorm] = sqrt(s2[0]);
+    mail[kMailCost] = lin_cost[0];
+    mail[kMailGmax] = s3[0];
   }
 }
 
@@ -2890,8 +2915,8 @@ static int window_build_impl(wc_ctx *ctx, const wc_surfel *d_sld_surf, const wc_
   WC_TRY(wc_ensure(ctx, W->A, np_al * np_al * 8));
   WC_TRY(wc_ensure(ctx, W->Lmat, np_al * np_al * 8));
   WC_TRY(wc_ensure(ctx, W->y, np_al * 8));
-  WC_TRY(wc_ensure(ctx, W->mail, 64 * 8));
-  WC_HIP(ctx, hipMemsetAsync((double *)W->mail.p + 60, 0, 24, ctx->stream));  // k_gather's count of finished g / cost workgroups, their maximum of |g|; [62]: k_schur_bias_y_step's count
+  WC_TRY(wc_ensure(ctx, W->mail, kMailWords * 8));
+  WC_HIP(ctx, hipMemsetAsync((double *)W->mail.p + kMailGatherDone, 0, (kMailStepDone + 1 - kMailGatherDone) * 8, ctx->stream));  // k_gather's count of finished g / cost workgroups, their maximum of |g|; k_schur_bias_y_step's count
   const size_t ncb = (W->nb + 255) / 256 + (W->nu + 255) / 256 + (W->ni + 255) / 256 + 8;
   WC_TRY(wc_ensure(ctx, W->cost_part, ncb * 8));
   if (!W->fam_done[1]) WC_HIP(ctx, hipEventCreateWithFlags(&W->fam_done[1], hipEventDisableTiming));
@@ -2975,7 +3000,7 @@ extern "C" int wc_window_build_sharded(wc_ctx *ctx, const wc_surfel *d_sld_surf,
   }
   W->two_coll = two;
   const double mine[4] = {(double)W->nb, (double)W->nu, (double)W->ni, 1.0};
-  double *chk = (double *)W->mail.p + 48;
+  double *chk = (double *)W->mail.p + kMailTicket;
   WC_HIP(ctx, hipMemcpyAsync(chk, mine, sizeof(mine), hipMemcpyHostToDevice, ctx->stream));
   WC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (`mine` is a stack array)
   WC_TRY(do_allreduce(ctx, W, chk, 4));
@@ -3001,7 +3026,7 @@ inline double *lin_H(wc_window_state *W, bool other = false) { return (double *)
 inline double *lin_g(wc_window_state *W, bool other = false) { return lin_H(W, other) + (size_t)W->n * W->n; }
 inline double *lin_cost(wc_window_state *W, bool other = false) { return lin_g(W, other) + W->np; }
 
-// ticket != 0: stored to host_mail[48] behind the mailbox (system-scope fence in between) - the host waits for it by reading
+// ticket != 0: stored to host_mail[kMailTicket] behind the mailbox (system-scope fence in between) - the host waits for it by reading
 // pinned memory instead of waiting for the stream (wait_mail)
 __global__ void __launch_bounds__(1024) k_post_reduce(const double *g, const double *cost, int n, double *mail, int slot, double *host_mail = nullptr,
                                                      unsigned long long ticket = 0) {
@@ -3019,10 +3044,10 @@ __global__ void __launch_bounds__(1024) k_post_reduce(const double *g, const dou
     mail[slot] = cost[0];
     mail[slot + 1] = s[0];
     if (host_mail) {  // the whole mailbox to pinned host memory (as k_sum_blocks does on the evaluation path)
-      for (int i = 0; i < 40; ++i) host_mail[i] = (i == slot) ? cost[0] : (i == slot + 1 ? s[0] : mail[i]);
+      for (int i = 0; i < kMailMirror; ++i) host_mail[i] = (i == slot) ? cost[0] : (i == slot + 1 ? s[0] : mail[i]);
       if (ticket) {
         __threadfence_system();
-        __hip_atomic_store((unsigned long long *)(host_mail + 48), ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store((unsigned long long *)(host_mail + kMailTicket), ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
   }
@@ -3120,7 +3145,7 @@ int enqueue_linearize(wc_ctx *ctx, wc_window_state *W, const double *d_x, int ma
   ga.cost_base = W->npart_doubles;
   // max |g| + the mailbox by the last of k_gather's g / cost workgroups (one GPU; behind an all-reduce k_post_reduce stays a launch)
   ga.post = packed ? 0 : 1;
-  ga.mail_slot = mail_slot, ga.done = (uint32_t *)((double *)W->mail.p + 60), ga.mail = (double *)W->mail.p, ga.host_mail = host_mail, ga.ticket = ticket;
+  ga.mail_slot = mail_slot, ga.done = (uint32_t *)((double *)W->mail.p + kMailGatherDone), ga.mail = (double *)W->mail.p, ga.host_mail = host_mail, ga.ticket = ticket;
   const uint32_t gather_grid = W->nheavy + (W->nnear + kGG * kLightSets - 1) / (kGG * kLightSets) + (W->nfar + kFarGroups * kFarSets - 1) / (kFarGroups * kFarSets) + W->ns + 1;
   ga.only = 0;
   if (two) {
@@ -3128,15 +3153,15 @@ int enqueue_linearize(wc_ctx *ctx, wc_window_state *W, const double *d_x, int ma
     // sums straight into H / g + their cost.  The 16-byte sum of the costs goes first and k_post_cost sends the linearisation's cost to the
     // host: the trust-region decision does not wait for the 0.6 - 2.3 MB of pose corners, which only k_schur_form needs.
     double *mail = (double *)W->mail.p;
-    ga.only = 1, ga.packed = 1, ga.H = red, ga.g = red + (size_t)36 * W->npairs, ga.cost = mail + 52, ga.post = 0;
+    ga.only = 1, ga.packed = 1, ga.H = red, ga.g = red + (size_t)36 * W->npairs, ga.cost = mail + kMailSurfelCost, ga.post = 0;
     k_gather<<<gather_grid, 144 * kGG, 0, st>>>(ga);
-    ga.only = 2, ga.packed = 0, ga.H = lin_H(W, other), ga.g = lin_g(W, other), ga.cost = mail + 54;
+    ga.only = 2, ga.packed = 0, ga.H = lin_H(W, other), ga.g = lin_g(W, other), ga.cost = mail + kMailImuCost;
     k_gather<<<gather_grid, 144 * kGG, 0, st>>>(ga);
     WC_HIP(ctx, hipGetLastError());
-    WC_TRY(do_allreduce(ctx, W, mail + 52, 2));  // collective 1: {cost of the surfel factors, spare}
+    WC_TRY(do_allreduce(ctx, W, mail + kMailSurfelCost, 2));  // collective 1: {cost of the surfel factors, spare}
     k_post_cost<<<1, 64, 0, st>>>(mail, mail_slot, lin_cost(W, other), host_mail, ticket);
     double *late = nullptr;
-    if (host_mail) late = host_mail + 40 + (W->lin_count & 1u);
+    if (host_mail) late = host_mail + kMailLate + (W->lin_count & 1u);
     ++W->lin_count;
     // collective 2 (pose corners + the pose half of g) and the expansion: on the side stream when the communicator enqueues (the in-library
     // RCCL binding) - the ctx stream goes on with the bias elimination, which reads nothing of it, and waits in front of k_schur_form
@@ -3186,7 +3211,7 @@ int enqueue_linearize(wc_ctx *ctx, wc_window_state *W, const double *d_x, int ma
 // stream wait after 50 ms (a faulted kernel never stores its ticket: the stream wait then reports the error).
 int wait_mail(wc_ctx *ctx, unsigned long long ticket) {
   if (ticket) {
-    const volatile unsigned long long *w = (const volatile unsigned long long *)(ctx->h_mail + 48);
+    const volatile unsigned long long *w = (const volatile unsigned long long *)(ctx->h_mail + kMailTicket);
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t spin = 0;; ++spin) {
       if (__atomic_load_n((const unsigned long long *)w, __ATOMIC_ACQUIRE) == ticket) return WC_OK;
@@ -3213,11 +3238,11 @@ int enqueue_evaluate(wc_ctx *ctx, wc_window_state *W, const double *d_x, double 
                                   d_res ? d_res + W->nb + W->nu : nullptr, cp + gb + gu);
   if (two_collectives(ctx, W)) {  // (the IMU factors are on every rank: their cost is added behind the sum of the surfel factors')
     double *mail = (double *)W->mail.p;
-    k_sum_blocks<<<1, 1024, 0, st>>>(cp, gb + gu, mail, 52, nullptr);
-    k_sum_blocks<<<1, 1024, 0, st>>>(cp + gb + gu, gi, mail, 54, nullptr);
+    k_sum_blocks<<<1, 1024, 0, st>>>(cp, gb + gu, mail, kMailSurfelCost, nullptr);
+    k_sum_blocks<<<1, 1024, 0, st>>>(cp + gb + gu, gi, mail, kMailImuCost, nullptr);
     WC_HIP(ctx, hipGetLastError());
-    WC_TRY(do_allreduce(ctx, W, mail + 52, 2));
-    k_post_cost<<<1, 64, 0, st>>>(mail, mail_slot, mail + 55, nullptr, 0ull);
+    WC_TRY(do_allreduce(ctx, W, mail + kMailSurfelCost, 2));
+    k_post_cost<<<1, 64, 0, st>>>(mail, mail_slot, mail + kMailEvalCost, nullptr, 0ull);
     WC_HIP(ctx, hipGetLastError());
     return WC_OK;
   }
@@ -3231,6 +3256,153 @@ int read_mail(wc_ctx *ctx, wc_window_state *W, int count) {
   WC_HIP(ctx, hipMemcpyAsync(ctx->h_mail, W->mail.p, (size_t)count * 8, hipMemcpyDeviceToHost, ctx->stream));
   WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return WC_OK;
+}
+
+// ---- one attempt of an LM iteration (wc_window_solve): a damped step - LevenbergMarquardtStrategy::ComputeStep on the device, by
+// the bias elimination or by the dense factor of all unknowns -, then the candidate's linearisation and the wait for its mail ------
+
+// the bias elimination's geometry (window_schur.inc) at ns sample states
+struct SchurGeom {
+  int ns, npz, M, ldr, nch, np2, nblk2, nlev = 0;
+  explicit SchurGeom(int ns_)
+      : ns(ns_), npz(6 * ns_), M((ns_ + 1) / 2), ldr(((npz + 1 + 63) / 64) * 64), nch((ldr + 255) / 256), np2(((npz + 1 + kNB - 1) / kNB) * kNB), nblk2(np2 / kNB) {
+    for (int s = 1; s < M; s *= 2) ++nlev;
+  }
+};
+
+// what the attempts of one solve share
+struct SolveRun {
+  SchurGeom G;
+  bool speculate;       // the solve uses the elimination: level 0 of the next one is formed behind every candidate's linearisation
+  bool mailed;          // the candidate's linearisation posts to the pinned mailbox itself, with a ticket (else the mailbox is copied)
+  double *h_mail_dev;   // device address of the pinned mailbox (its staging area: + kMailStage)
+  const void *pcr_ready_for = nullptr;  // the H whose undamped level-0 blocks sit in pcr_D / A / R [0]
+  int late_slot = 0;    // (two-collective form) where the last candidate's max |g| lands
+};
+
+inline int *mail_fail(wc_window_state *W) { return (int *)((double *)W->mail.p + kMailFail); }
+inline StepArgs step_args(wc_window_state *W, const SolveRun &R, int on) {
+  return StepArgs{(const double *)W->x.p, (const double *)W->scale.p, lin_g(W), (const double *)W->diag.p, lin_cost(W), (double *)W->xc.p,
+                  (double *)W->mail.p, R.h_mail_dev + kMailStage, on};
+}
+
+void enqueue_pcr_init(wc_ctx *ctx, wc_window_state *W, const SchurGeom &G, bool other) {
+  const PcrSrc src{lin_H(W, other), lin_g(W, other), (const double *)W->scale.p, W->n, G.ns, 0.0, (double *)W->diag.p};
+  k_pcr_init<<<dim3(G.M, G.nch), 256, 0, ctx->stream>>>(src, (double *)W->pcr_D[0].p, (double *)W->pcr_A[0].p, (double *)W->pcr_R[0].p, G.ldr, mail_fail(W));
+}
+
+// bias unknowns first, by parallel cyclic reduction (window_schur.inc); the dense panel steps run on the pose half
+int enqueue_schur_step(wc_ctx *ctx, wc_window_state *W, SolveRun &R, double radius) {
+  hipStream_t st = ctx->stream;
+  const SchurGeom &G = R.G;
+  const int n = W->n, ns = G.ns, npz = G.npz, M = G.M, ldr = G.ldr, nch = G.nch, np2 = G.np2, ld2 = np2, nblk2 = G.nblk2, nlev = G.nlev;
+  double *H = lin_H(W), *g = lin_g(W), *scale = (double *)W->scale.p, *diag = (double *)W->diag.p, *A = (double *)W->A.p, *Lmat = (double *)W->Lmat.p;
+  int *fail = mail_fail(W);
+  double *Dp[2] = {(double *)W->pcr_D[0].p, (double *)W->pcr_D[1].p}, *Ap[2] = {(double *)W->pcr_A[0].p, (double *)W->pcr_A[1].p};
+  double *Rp[2] = {(double *)W->pcr_R[0].p, (double *)W->pcr_R[1].p}, *yred = (double *)W->yred.p;
+  int cur = 0;
+  // level 0 from H, UNDAMPED (radius 0) - unless it is there already: enqueued behind the linearisation this H came from,
+  // before the host knew that its step would be accepted (enqueue_candidate)
+  if (R.pcr_ready_for != (const void *)H) enqueue_pcr_init(ctx, W, G, /*other=*/false);
+  R.pcr_ready_for = nullptr;  // (the levels overwrite level 0)
+  const PcrDamp damp{radius, ns, diag}, nodamp{0.0, ns, diag};
+  for (int s = 1, lev = 0; lev < nlev; s *= 2, ++lev) {  // (ns >= 4: at least one level)
+    const bool last = lev == nlev - 1, first = lev == 0;
+    // (the levels of small stride work on banded right-hand sides: fewer column chunks per row - k_pcr_level; rounds 3 - 5 ran
+    // every level over all columns)
+    const int band_chunks = (kSB * (4 * s + 1) + 255) / 256;
+    const int limited = band_chunks < nch ? band_chunks : 0;
+    const dim3 grid(M * (limited ? limited : nch));
+    if (last && first)
+      k_pcr_level<true, true><<<grid, 256, 0, st>>>(s, M, Dp[cur], Ap[cur], Rp[cur], Dp[cur ^ 1], Ap[cur ^ 1], Rp[cur ^ 1], ldr, fail, damp, npz, limited);
+    else if (last)
+      k_pcr_level<true, false><<<grid, 256, 0, st>>>(s, M, Dp[cur], Ap[cur], Rp[cur], Dp[cur ^ 1], Ap[cur ^ 1], Rp[cur ^ 1], ldr, fail, nodamp, npz, limited);
+    else if (first)
+      k_pcr_level<false, true><<<grid, 256, 0, st>>>(s, M, Dp[cur], Ap[cur], Rp[cur], Dp[cur ^ 1], Ap[cur ^ 1], Rp[cur ^ 1], ldr, fail, damp, npz, limited);
+    else
+      k_pcr_level<false, false><<<grid, 256, 0, st>>>(s, M, Dp[cur], Ap[cur], Rp[cur], Dp[cur ^ 1], Ap[cur ^ 1], Rp[cur ^ 1], ldr, fail, nodamp, npz, limited);
+    cur ^= 1;
+  }
+  double *X = Rp[cur];  // the last level wrote X = T^-1 [C | bB] where the others write R'
+  WC_TRY(join_side(ctx, W));  // (the pose blocks and the pose half of g: summed over the ranks on the side stream)
+  k_schur_form<<<((np2 + 255) / 256) * (1 + ns + (np2 - npz)), 256, 0, st>>>(H, g, scale, X, n, ns, ldr, np2, ld2, radius, A, diag, Lmat, (double *)W->Linv.p, fail, (np2 + 255) / 256);
+  // the back substitution: identity rows appended to the factorisation (chol_extra_tile), k_back_mul, one fused tail (rounds 2 - 5:
+  // chunk solves + products and two tail launches)
+  for (int k = 0; k + 1 < nblk2; ++k) {
+    const int tiles = ((nblk2 - k - 1) * kNB + 63) / 64;
+    const int n_tri = 1 + tiles * (tiles + 1) / 2;
+    const int n_extra = (((k + 1) * kNB + 63) / 64) * tiles;
+    k_chol_step<<<n_tri + n_extra, 256, 0, st>>>(A, ld2, k, nblk2, Lmat, (double *)W->Linv.p, fail, npz, n_tri, tiles);
+  }
+  k_back_mul<<<(npz + 7) / 8, 256, 0, st>>>(A, Lmat, ld2, nblk2, npz, (const double *)W->Linv.p, yred);
+  k_schur_bias_y_step<<<(npz + 3) / 4, 256, 0, st>>>(X, yred, ns, ldr, (double *)W->y.p, step_args(W, R, 0), n, (uint32_t *)((double *)W->mail.p + kMailStepDone), yred + npz + kNB);
+  return WC_OK;
+}
+
+// round 2's dense factor of all unknowns
+int enqueue_dense_step(wc_ctx *ctx, wc_window_state *W, const SolveRun &R, double radius) {
+  hipStream_t st = ctx->stream;
+  const int n = W->n, np = W->np, ld = W->ld, nblk = np / kNB;
+  double *A = (double *)W->A.p, *y = (double *)W->y.p, *Lmat = (double *)W->Lmat.p;
+  int *fail = mail_fail(W);
+  dim3 grid((np + 255) / 256, np);
+  grid.y += 1;  // (+ the workgroup of the first diagonal block)
+  WC_TRY(join_side(ctx, W));
+  k_damp_first<<<grid, 256, 0, st>>>(lin_H(W), lin_g(W), (double *)W->scale.p, n, np, ld, radius, A, (double *)W->diag.p, Lmat, (double *)W->Linv.p, fail);
+  for (int k = 0; k + 1 < nblk; ++k) {
+    const int tiles = ((nblk - k - 1) * kNB + 63) / 64;
+    k_chol_step<<<1 + tiles * (tiles + 1) / 2, 256, 0, st>>>(A, ld, k, nblk, Lmat, (double *)W->Linv.p, fail, n, 1 + tiles * (tiles + 1) / 2, tiles);
+  }
+  // back substitution, chunk by chunk from the last block row
+  const double *zsrc = Lmat + (size_t)n * ld;
+  for (int hi = (n + kNB - 1) / kNB; hi > 0;) {
+    const int lo = std::max(0, hi - kBackChunk);
+    k_chol_back_chunk<<<1, 1024, 0, st>>>(Lmat, ld, n, (const double *)W->Linv.p, zsrc, y, lo, hi, step_args(W, R, lo == 0 ? 1 : 0));
+    if (lo > 0) k_chol_back_gemv<<<lo, 1024, 0, st>>>(Lmat, ld, n, zsrc, y, lo, hi);
+    zsrc = y;
+    hi = lo;
+  }
+  return WC_OK;
+}
+
+// Round 3: the candidate's cost comes from a LINEARISATION at the candidate (into the other {H, g, cost} buffer) instead of a
+// cost-only pass over the same records (round 2): an accepted step - the rule - then needs no second pass (one pass over the factors
+// per iteration instead of two, -0.05 ms of 0.6 at C4), a rejected one has formed an H nobody uses (+0.1 ms).  Its cost and
+// max |g| arrive with the iteration's mailbox, so nothing is pending between iterations: ONE host round trip per iteration.
+int enqueue_candidate(wc_ctx *ctx, wc_window_state *W, SolveRun &R) {
+  const unsigned long long ticket = R.mailed ? ++ctx->mail_ticket : 0;
+  R.late_slot = (int)(W->lin_count & 1u);
+  WC_TRY(enqueue_linearize(ctx, W, (const double *)W->xc.p, kMailCandCost, /*other=*/true, R.mailed ? R.h_mail_dev : nullptr, ticket));
+  WC_HIP(ctx, hipGetLastError());
+  if (!R.mailed) WC_HIP(ctx, hipMemcpyAsync(ctx->h_mail, W->mail.p, kMailMirror * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (R.speculate) {
+    // the next iteration's level 0 from the CANDIDATE's H, while the host waits for this iteration's mailbox and decides
+    // (the blocks do not depend on the radius).  An accepted step - the rule - finds them there; a rejected one forms its own.
+    // (Behind the mailbox's copy: k_pcr_init clears the factorisation's fail flag, which that copy carries.  Rounds 3 - 4 formed
+    // level 0 at the start of every iteration.)
+    enqueue_pcr_init(ctx, W, R.G, /*other=*/true);
+    R.pcr_ready_for = (const void *)lin_H(W, true);
+  }
+  return wait_mail(ctx, ticket);
+}
+
+int enqueue_attempt(wc_ctx *ctx, wc_window_state *W, SolveRun &R, bool elimination, double radius) {
+  WC_TRY(elimination ? enqueue_schur_step(ctx, W, R, radius) : enqueue_dense_step(ctx, W, R, radius));
+  return enqueue_candidate(ctx, W, R);
+}
+
+// one attempt's mail out of the pinned mailbox (behind wait_mail)
+LmMail lm_mail(const wc_ctx *ctx, const LmLoop &L) {
+  const double *h = ctx->h_mail;
+  LmMail m{0, h[kMailModelChange], h[kMailStepNorm], h[kMailCandCost], h[kMailCandGmax], L.late_pending ? h[kMailLate + L.late_at] : 0.0};
+  std::memcpy(&m.fail, &h[kMailFail], 4);
+  return m;
+}
+
+double host_norm(const std::vector<double> &v) {
+  double s = 0.0;
+  for (size_t i = 0; i < v.size(); ++i) s += v[i] * v[i];
+  return std::sqrt(s);
 }
 
 }  // namespace
@@ -3254,9 +3426,9 @@ extern "C" int wc_window_evaluate(wc_ctx *ctx, const double *h_x, double *h_cost
   if (!ctx || !ctx->win || !ctx->win->built || !h_x || !h_cost) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
   wc_window_state *W = ctx->win;
   WC_HIP(ctx, hipMemcpyAsync(W->x.p, h_x, (size_t)W->n * 8, hipMemcpyHostToDevice, ctx->stream));
-  WC_TRY(enqueue_evaluate(ctx, W, (const double *)W->x.p, d_residuals, 0));
-  WC_TRY(read_mail(ctx, W, 1));
-  *h_cost = ctx->h_mail[0];
+  WC_TRY(enqueue_evaluate(ctx, W, (const double *)W->x.p, d_residuals, kMailCost));
+  WC_TRY(read_mail(ctx, W, kMailCost + 1));
+  *h_cost = ctx->h_mail[kMailCost];
   return WC_OK;
 }
 
@@ -3265,12 +3437,12 @@ extern "C" int wc_window_linearize(wc_ctx *ctx, const double *h_x, double *d_H, 
   if (!ctx || !ctx->win || !ctx->win->built || !h_x) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
   wc_window_state *W = ctx->win;
   WC_HIP(ctx, hipMemcpyAsync(W->x.p, h_x, (size_t)W->n * 8, hipMemcpyHostToDevice, ctx->stream));
-  WC_TRY(enqueue_linearize(ctx, W, (const double *)W->x.p, 0));
+  WC_TRY(enqueue_linearize(ctx, W, (const double *)W->x.p, kMailCost));
   WC_TRY(join_side(ctx, W));
   if (d_H) WC_HIP(ctx, hipMemcpyAsync(d_H, lin_H(W), (size_t)W->n * W->n * 8, hipMemcpyDeviceToDevice, ctx->stream));
   if (d_g) WC_HIP(ctx, hipMemcpyAsync(d_g, lin_g(W), (size_t)W->n * 8, hipMemcpyDeviceToDevice, ctx->stream));
-  WC_TRY(read_mail(ctx, W, 2));
-  if (h_cost) *h_cost = ctx->h_mail[0];
+  WC_TRY(read_mail(ctx, W, kMailGmax + 1));
+  if (h_cost) *h_cost = ctx->h_mail[kMailCost];
   return WC_OK;
 }
 
@@ -3283,21 +3455,24 @@ extern "C" int wc_window_linearize_timed(wc_ctx *ctx, const double *h_x, int rep
     return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
   wc_window_state *W = ctx->win;
   WC_HIP(ctx, hipMemcpyAsync(W->x.p, h_x, (size_t)W->n * 8, hipMemcpyHostToDevice, ctx->stream));
-  WC_TRY(enqueue_linearize(ctx, W, (const double *)W->x.p, 0));
+  WC_TRY(enqueue_linearize(ctx, W, (const double *)W->x.p, kMailCost));
   WC_TRY(wc_timer_start(ctx));
-  for (int r = 0; r < reps; ++r) WC_TRY(enqueue_linearize(ctx, W, (const double *)W->x.p, 0));
+  for (int r = 0; r < reps; ++r) WC_TRY(enqueue_linearize(ctx, W, (const double *)W->x.p, kMailCost));
   WC_TRY(join_side(ctx, W));
   float ms = 0.f;
   WC_TRY(wc_timer_stop_ms(ctx, &ms));
-  WC_TRY(read_mail(ctx, W, 2));
+  WC_TRY(read_mail(ctx, W, kMailGmax + 1));
   *h_ms_per_linearisation = ms / (float)reps;
   return WC_OK;
 }
 
 // Multi-GPU: correspondences are sharded over ranks, the unknowns stay replicated.  The caller installs a callback that
 // sums a device buffer of doubles over all ranks (RCCL all-reduce over xGMI via torch.distributed or rccl directly);
-// it is invoked once per linearisation on the packed buffer {H, g, cost} and once per candidate-cost evaluation on one
-// double.  Every rank then runs the identical, deterministic LM logic on identical numbers.
+// what it is invoked on depends on the window's form (two_collectives).  A window the caller shards itself: once per linearisation
+// on the packed buffer {upper block triangle of H, g, cost, spare}, once per cost evaluation on one double.  A window of
+// wc_window_build_sharded (IMU factors replicated): twice per linearisation - two doubles {cost of the surfel factors, spare}, then
+// the pose corners and the pose half of g - and once per cost evaluation on those two doubles.  Every rank then runs the
+// identical, deterministic LM logic (lm_loop.h) on identical numbers.
 extern "C" int wc_window_set_allreduce(wc_ctx *ctx, int (*fn)(void *user, double *d_buf, uint64_t count), void *user) {
   wc_dev_guard dg_(ctx);
   if (!ctx) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
@@ -3310,286 +3485,74 @@ extern "C" int wc_window_set_allreduce(wc_ctx *ctx, int (*fn)(void *user, double
   return WC_OK;
 }
 
-// ceres::Solve with the reference's options (lidar_odometry.cc:551-561): Ceres-default trust-region LM restated
-// (upstream semantics, see oracle/window.cc for the per-rule citations).
+// ceres::Solve with the reference's options (lidar_odometry.cc:551-561): Ceres-default trust-region LM.  Every decision of the loop
+// is lm_loop.h's; this function enqueues what it decides and moves the buffers an accepted step swaps.
 extern "C" int wc_window_solve(wc_ctx *ctx, double *h_x_inout, wc_solve_summary *summary, double *h_first_step) {
   wc_dev_guard dg_(ctx);
   if (!ctx || !ctx->win || !ctx->win->built || !h_x_inout || !summary) return wc_fail(ctx, WC_ERR_ARG, "%s: null or out-of-range argument", __func__);
   wc_window_state *W = ctx->win;
   hipStream_t st = ctx->stream;
-  const int n = W->n, np = W->np, ld = W->ld, nblk = np / kNB;
+  const int n = W->n;
   std::memset(summary, 0, sizeof(*summary));
-  double *x = (double *)W->x.p, *xc = (double *)W->xc.p, *H = lin_H(W), *g = lin_g(W);
-  double *scale = (double *)W->scale.p, *diag = (double *)W->diag.p, *A = (double *)W->A.p, *y = (double *)W->y.p;
-  double *Lmat = (double *)W->Lmat.p;
-  double *mail = (double *)W->mail.p;
-  int *fail = (int *)((double *)W->mail.p + 32);
   std::vector<double> best(h_x_inout, h_x_inout + n), cur(best);
-  const bool lm_dense = ctx->dev.lm_dense != 0;
-  const bool use_schur = !lm_dense && W->ns >= 4;  // (two super-blocks at least: the reduction has a level)
-  if (use_schur) {
-    const int ns_al = std::max(W->ns, 96), M_al = (ns_al + 1) / 2, ldr_al = ((6 * ns_al + 1 + 63) / 64) * 64;  // (as in wc_window_build: no re-allocation while a window grows)
+  // the two-collective form of a sharded window: the cost of a linearisation reaches the host behind the 16-byte collective (ticket), its
+  // max |g| behind the large one - in a late slot of the pinned mailbox the loop reads with the NEXT ticket (lm_loop.h: late_gradient)
+  const bool multi = multi_gpu(ctx, W), two = two_collectives(ctx, W);
+  const LmConfig cfg{ctx->P.max_iterations, ctx->dev.lm_radius0, ctx->dev.lm_dense_radius, ctx->dev.lm_dense != 0, W->ns, two};
+  // the candidate's linearisation posts its cost (and, but for the two-collective form, its max |g|) to the pinned mailbox itself, with a
+  // ticket: one GPU, or the two-collective form's k_post_cost.  Behind the one all-reduce of the other sharded forms, the mailbox is copied
+  SolveRun run{SchurGeom(W->ns), lm_uses_elimination(cfg), /*mailed=*/!multi || two, nullptr};
+  if (run.speculate) {
+    const SchurGeom al(std::max(W->ns, 96));  // (as in wc_window_build: no re-allocation while a window grows)
     for (int b = 0; b < 2; ++b) {
-      WC_TRY(wc_ensure(ctx, W->pcr_D[b], (size_t)M_al * 144 * 8));
-      WC_TRY(wc_ensure(ctx, W->pcr_A[b], (size_t)M_al * 144 * 8));
-      WC_TRY(wc_ensure(ctx, W->pcr_R[b], (size_t)M_al * kSB * ldr_al * 8));
+      WC_TRY(wc_ensure(ctx, W->pcr_D[b], (size_t)al.M * 144 * 8));
+      WC_TRY(wc_ensure(ctx, W->pcr_A[b], (size_t)al.M * 144 * 8));
+      WC_TRY(wc_ensure(ctx, W->pcr_R[b], (size_t)al.M * kSB * al.ldr * 8));
     }
-    WC_TRY(wc_ensure(ctx, W->yred, (size_t)(12 * ns_al + 2 * kNB + 128) * 8));  // (y of the pose half; behind it the fused tail's partial sums: four per workgroup)
+    WC_TRY(wc_ensure(ctx, W->yred, (size_t)(12 * al.ns + 2 * kNB + 128) * 8));  // (y of the pose half; behind it the fused tail's partial sums: four per workgroup)
   }
-
-  double *h_mail_dev = nullptr, *h_stage_dev = nullptr;  // device addresses of the pinned mailbox and of its staging area
   {
     void *dp = nullptr;
     if (hipHostGetDevicePointer(&dp, ctx->h_mail, 0) != hipSuccess || !dp) return wc_fail(ctx, WC_ERR_HIP, "pinned mailbox is not device-mapped");
-    h_mail_dev = (double *)dp;
-    h_stage_dev = h_mail_dev + 64;
+    run.h_mail_dev = (double *)dp;
   }
-  // the two-collective form of a sharded window: the cost of a linearisation reaches the host behind the 16-byte collective (ticket), its
-  // max |g| behind the large one - in a late slot of the pinned mailbox the loop reads with the NEXT ticket (two_late)
-  const bool multi = multi_gpu(ctx, W), two = two_collectives(ctx, W);
-  // the candidate's linearisation posts its cost (and, but for the two-collective form, its max |g|) to the pinned mailbox itself, with a
-  // ticket: one GPU, or the two-collective form's k_post_cost.  Behind the one all-reduce of the other sharded forms, the mailbox is copied
-  const bool mailed = !multi || two;
-  WC_HIP(ctx, hipMemcpyAsync(x, cur.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+  WC_HIP(ctx, hipMemcpyAsync(W->x.p, cur.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
   if (!multi) {
     // the first linearisation's cost / max |g| through the pinned mailbox and its ticket, like every later one (the stream
     // wait of rounds 1 - 3 added the end-of-kernel signal and the runtime's wake-up, ~20 us per solve; k_scale_init runs behind it)
     const unsigned long long ticket = ++ctx->mail_ticket;
-    WC_TRY(enqueue_linearize(ctx, W, x, 0, /*other=*/false, h_mail_dev, ticket));
-    k_scale_init<<<(n + 255) / 256, 256, 0, st>>>(H, n, scale);
+    WC_TRY(enqueue_linearize(ctx, W, (const double *)W->x.p, kMailCost, /*other=*/false, run.h_mail_dev, ticket));
+    k_scale_init<<<(n + 255) / 256, 256, 0, st>>>(lin_H(W), n, (double *)W->scale.p);
     WC_HIP(ctx, hipGetLastError());
     WC_TRY(wait_mail(ctx, ticket));
   } else {
-    WC_TRY(enqueue_linearize(ctx, W, x, 0));
+    WC_TRY(enqueue_linearize(ctx, W, (const double *)W->x.p, kMailCost));
     WC_TRY(join_side(ctx, W));
-    k_scale_init<<<(n + 255) / 256, 256, 0, st>>>(H, n, scale);
-    WC_TRY(read_mail(ctx, W, 2));
+    k_scale_init<<<(n + 255) / 256, 256, 0, st>>>(lin_H(W), n, (double *)W->scale.p);
+    WC_TRY(read_mail(ctx, W, kMailGmax + 1));
   }
-  summary->n_linearizations = 1;
-  double cost = ctx->h_mail[0], gmax = ctx->h_mail[1];
-  summary->initial_cost = cost;
-  double min_cost = cost, radius = ctx->dev.lm_radius0 == -1 ? 1e4 : std::pow(10.0, (double)ctx->dev.lm_radius0), decrease = 2.0, x_norm = 0.0;
-  for (int i = 0; i < n; ++i) x_norm += cur[i] * cur[i];
-  x_norm = std::sqrt(x_norm);
-  int iter = 0, consecutive_invalid = 0;
-  bool first_recorded = false;
-  bool two_late = false;  // (two-collective form) max |g| of the accepted point has not been looked at yet: it sits in h_mail[40 + two_at]
-  int two_slot = 0, two_at = 0;
-  // Round 3: the candidate's cost comes from a LINEARISATION at the candidate (into the other {H, g, cost} buffer) instead of a
-  // cost-only pass over the same records (round 2): an accepted step - the rule - then needs no second pass (one pass over the factors
-  // per iteration instead of two, -0.05 ms of 0.6 at C4), a rejected one has formed an H nobody uses (+0.1 ms).  Its cost and
-  // max |g| arrive with the iteration's mailbox, so nothing is pending between iterations: ONE host round trip per iteration.
-  const void *pcr_ready_for = nullptr;  // the H whose undamped level-0 blocks sit in pcr_D / A / R [0]
-  summary->termination = 1;
-  if (gmax <= 1e-10) {
-    summary->termination = 0;
-  } else {
-    while (true) {
-      if (iter >= ctx->P.max_iterations) {
-        summary->termination = 1;
-        break;
-      }
-      if ((!two_late && gmax <= 1e-10) || radius <= 1e-32) {
-        summary->termination = 0;
-        break;
-      }
-      ++iter;
-      // One attempt of the iteration: the damped step (bias elimination + dense factor of the pose half, or - schur = false - round 2's
-      // dense factor of all unknowns), the candidate, its linearisation, the mailbox.
-      auto attempt = [&](bool schur) -> int {
-        // LevenbergMarquardtStrategy::ComputeStep on the device
-        if (schur) {
-          // bias unknowns first, by parallel cyclic reduction (window_schur.inc); the dense panel steps run on the pose half
-          const int ns = W->ns, npz = 6 * ns, M = (ns + 1) / 2;
-          const int ldr = ((npz + 1 + 63) / 64) * 64, nch = (ldr + 255) / 256;
-          const int np2 = ((npz + 1 + kNB - 1) / kNB) * kNB, ld2 = np2, nblk2 = np2 / kNB;
-          double *Dp[2] = {(double *)W->pcr_D[0].p, (double *)W->pcr_D[1].p}, *Ap[2] = {(double *)W->pcr_A[0].p, (double *)W->pcr_A[1].p};
-          double *Rp[2] = {(double *)W->pcr_R[0].p, (double *)W->pcr_R[1].p}, *yred = (double *)W->yred.p;
-          int cur = 0, nlev = 0;
-          for (int s = 1; s < M; s *= 2) ++nlev;
-          double *X = nullptr;
-          // level 0 from H, UNDAMPED (radius 0) - unless it is there already: enqueued behind the linearisation this H came from,
-          // before the host knew that its step would be accepted (see behind the candidate's linearisation below)
-          if (pcr_ready_for != (const void *)H) {
-            const PcrSrc src{H, g, scale, n, ns, 0.0, diag};
-            k_pcr_init<<<dim3(M, nch), 256, 0, st>>>(src, Dp[0], Ap[0], Rp[0], ldr, fail);
-          }
-          pcr_ready_for = nullptr;  // (the levels overwrite level 0)
-          const PcrDamp damp{radius, ns, diag}, nodamp{0.0, ns, diag};
-          for (int s = 1, lev = 0; lev < nlev; s *= 2, ++lev) {  // (ns >= 4: at least one level)
-            const bool last = lev == nlev - 1, first = lev == 0;
-            // (the levels of small stride work on banded right-hand sides: fewer column chunks per row - k_pcr_level; rounds 3 - 5 ran
-            // every level over all columns)
-            const int band_chunks = (kSB * (4 * s + 1) + 255) / 256;
-            const int limited = band_chunks < nch ? band_chunks : 0;
-            const dim3 grid(M * (limited ? limited : nch));
-            if (last && first)
-              k_pcr_level<true, true><<<grid, 256, 0, st>>>(s, M, Dp[cur], Ap[cur], Rp[cur], Dp[cur ^ 1], Ap[cur ^ 1], Rp[cur ^ 1], ldr, fail, damp, npz, limited);
-            else if (last)
-              k_pcr_level<true, false><<<grid, 256, 0, st>>>(s, M, Dp[cur], Ap[cur], Rp[cur], Dp[cur ^ 1], Ap[cur ^ 1], Rp[cur ^ 1], ldr, fail, nodamp, npz, limited);
-            else if (first)
-              k_pcr_level<false, true><<<grid, 256, 0, st>>>(s, M, Dp[cur], Ap[cur], Rp[cur], Dp[cur ^ 1], Ap[cur ^ 1], Rp[cur ^ 1], ldr, fail, damp, npz, limited);
-            else
-              k_pcr_level<false, false><<<grid, 256, 0, st>>>(s, M, Dp[cur], Ap[cur], Rp[cur], Dp[cur ^ 1], Ap[cur ^ 1], Rp[cur ^ 1], ldr, fail, nodamp, npz, limited);
-            cur ^= 1;
-          }
-          X = Rp[cur];  // the last level wrote X = T^-1 [C | bB] where the others write R'
-          WC_TRY(join_side(ctx, W));  // (the pose blocks and the pose half of g: summed over the ranks on the side stream)
-          k_schur_form<<<((np2 + 255) / 256) * (1 + ns + (np2 - npz)), 256, 0, st>>>(H, g, scale, X, n, ns, ldr, np2, ld2, radius, A, diag, Lmat, (double *)W->Linv.p, fail, (np2 + 255) / 256);
-          // the back substitution: identity rows appended to the factorisation (chol_extra_tile), k_back_mul, one fused tail (rounds 2 - 5:
-          // chunk solves + products and two tail launches)
-          for (int k = 0; k + 1 < nblk2; ++k) {
-            const int tiles = ((nblk2 - k - 1) * kNB + 63) / 64;
-            const int n_tri = 1 + tiles * (tiles + 1) / 2;
-            const int n_extra = (((k + 1) * kNB + 63) / 64) * tiles;
-            k_chol_step<<<n_tri + n_extra, 256, 0, st>>>(A, ld2, k, nblk2, Lmat, (double *)W->Linv.p, fail, npz, n_tri, tiles);
-          }
-          const StepArgs sa{x, scale, g, diag, lin_cost(W), xc, mail, h_stage_dev, 0};
-          k_back_mul<<<(npz + 7) / 8, 256, 0, st>>>(A, Lmat, ld2, nblk2, npz, (const double *)W->Linv.p, yred);
-          k_schur_bias_y_step<<<(npz + 3) / 4, 256, 0, st>>>(X, yred, ns, ldr, y, sa, n, (uint32_t *)(mail + 62), yred + npz + kNB);
-        } else {
-          {
-            dim3 grid((np + 255) / 256, np);
-            grid.y += 1;  // (+ the workgroup of the first diagonal block)
-            WC_TRY(join_side(ctx, W));
-            k_damp_first<<<grid, 256, 0, st>>>(H, g, scale, n, np, ld, radius, A, diag, Lmat, (double *)W->Linv.p, fail);
-          }
-          for (int k = 0; k + 1 < nblk; ++k) {
-            const int tiles = ((nblk - k - 1) * kNB + 63) / 64;
-            k_chol_step<<<1 + tiles * (tiles + 1) / 2, 256, 0, st>>>(A, ld, k, nblk, Lmat, (double *)W->Linv.p, fail, n, 1 + tiles * (tiles + 1) / 2, tiles);
-          }
-          {  // back substitution, chunk by chunk from the last block row
-            const double *zsrc = Lmat + (size_t)n * ld;
-            for (int hi = (n + kNB - 1) / kNB; hi > 0;) {
-              const int lo = std::max(0, hi - kBackChunk);
-              const StepArgs sa{x, scale, g, diag, lin_cost(W), xc, mail, h_stage_dev, lo == 0 ? 1 : 0};
-              k_chol_back_chunk<<<1, 1024, 0, st>>>(Lmat, ld, n, (const double *)W->Linv.p, zsrc, y, lo, hi, sa);
-              if (lo > 0) k_chol_back_gemv<<<lo, 1024, 0, st>>>(Lmat, ld, n, zsrc, y, lo, hi);
-              zsrc = y;
-              hi = lo;
-            }
-          }
-        }
-        const unsigned long long ticket = mailed ? ++ctx->mail_ticket : 0;
-        if (two) two_slot = (int)(W->lin_count & 1u);  // (where this linearisation's max |g| will land)
-        // mail[5] = cost, [6] = max |g| at the candidate
-        WC_TRY(enqueue_linearize(ctx, W, xc, 5, /*other=*/true, mailed ? h_mail_dev : nullptr, ticket));
-        WC_HIP(ctx, hipGetLastError());
-        if (!mailed) WC_HIP(ctx, hipMemcpyAsync(ctx->h_mail, mail, 40 * 8, hipMemcpyDeviceToHost, st));
-        if (use_schur) {
-          // the next iteration's level 0 from the CANDIDATE's H, while the host waits for this iteration's mailbox and decides
-          // (the blocks do not depend on the radius).  An accepted step - the rule - finds them there; a rejected one forms its own.
-          // (Behind the mailbox's copy: k_pcr_init clears the factorisation's fail flag, which that copy carries.  Rounds 3 - 4 formed
-          // level 0 at the start of every iteration.)
-          const int ns = W->ns, npz = 6 * ns, M = (ns + 1) / 2, ldr = ((npz + 1 + 63) / 64) * 64, nch = (ldr + 255) / 256;
-          const PcrSrc src{lin_H(W, true), lin_g(W, true), scale, n, ns, 0.0, diag};
-          k_pcr_init<<<dim3(M, nch), 256, 0, st>>>(src, (double *)W->pcr_D[0].p, (double *)W->pcr_A[0].p, (double *)W->pcr_R[0].p, ldr, fail);
-          pcr_ready_for = (const void *)lin_H(W, true);
-        }
-        WC_TRY(wait_mail(ctx, ticket));
-        return WC_OK;
-      };
-      // As the radius grows the damping leaves the bias block T, whose own conditioning (random-walk factors tying neighbouring biases,
-      // weak absolute information) then shows: cond(T) grows with the radius, and the cyclic reduction's explicit 12 x 12 inverses lose
-      // digits a direct factorisation keeps - its normwise backward error in the bias rows is about cond(T) eps.  Measured on the step
-      // itself (tests/test_lm_step_gpu.py): at most 2e-10 up to a radius of 1e7, 1.4e-9 at 1e8, 1.2e-8 at 1e9 (the dense step: 1e-15).
-      // First seen in profiles/stress_facade.py on sparse streams (a sweep of 38 iterations for the oracle's 35, states 2.5e-4 apart).
-      // Iterations above 1e7 take round 2's dense step (development option lm_dense_radius: the exponent, 0 = never).
-      const bool schur_now = use_schur && !(ctx->dev.lm_dense_radius > 0 && radius > std::pow(10.0, (double)ctx->dev.lm_dense_radius));
-      WC_TRY(attempt(schur_now));
-      if (two_late) {  // max |g| at the point this iteration started from has arrived with the iteration's ticket (its kernels ran behind that expand)
-        gmax = ctx->h_mail[40 + two_at];
-        two_late = false;
-        if (gmax <= 1e-10) {  // GradientToleranceReached there: the reference stops before this iteration
-          --iter;
-          summary->termination = 0;
-          break;
-        }
-      }
-      summary->n_cost_evaluations++;
-      int hfail;
-      std::memcpy(&hfail, &ctx->h_mail[32], 4);
-      double model_change = ctx->h_mail[2], step_norm = ctx->h_mail[3], cand_cost = ctx->h_mail[5];
-      // A step the trust region is about to REJECT (or an invalid one) that came from the bias elimination is formed again by the dense
-      // factorisation of all unknowns before the decision is taken (round 5).  The elimination computes S = P - C^T T^-1 C through a
-      // parallel cyclic reduction without pivoting; on ill-conditioned windows (a free gauge held by the IMU factors alone, a large
-      // radius, dozens of iterations) its step can be worse than a direct factorisation's - profiles/stress_window.py found solves that
-      // rejected steps the oracle (and round 2's dense path) accepted and then needed 38 iterations for the oracle's 27, or hit the
-      // iteration limit.  Accepted steps - the rule: all of them in the bench's windows, the odometry step and the facade's stream - cost
-      // nothing extra; a genuine rejection costs one dense step.
-      if (schur_now) {
-        const bool invalid = hfail || !(model_change > 0) || !std::isfinite(step_norm);
-        const double dc = cost - cand_cost;
-        const bool rejected = !invalid && step_norm > 1e-8 * (x_norm + 1e-8) && std::fabs(dc) > 1e-6 * cost && !(dc / model_change > 1e-3);
-        if (invalid || rejected) {
-          WC_TRY(attempt(false));
-          summary->n_cost_evaluations++;
-          summary->first_step[1] += 1.0;  // (dense re-tries of this solve)
-          std::memcpy(&hfail, &ctx->h_mail[32], 4);
-          model_change = ctx->h_mail[2], step_norm = ctx->h_mail[3], cand_cost = ctx->h_mail[5];
-        }
-      }
-      if (hfail || !(model_change > 0) || !std::isfinite(step_norm)) {  // HandleInvalidStep
-        if (++consecutive_invalid >= 5) {
-          summary->termination = 2;
-          break;
-        }
-        radius *= 0.5;
-        summary->unsuccessful_steps++;
-        continue;
-      }
-      consecutive_invalid = 0;
-      if (!first_recorded) {
-        first_recorded = true;
-        summary->first_step[0] = step_norm;
-        if (h_first_step)
-          for (int i = 0; i < n; ++i) h_first_step[i] = ctx->h_mail[64 + i] - cur[i];  // (the candidate lm_step staged)
-      }
-      if (step_norm <= 1e-8 * (x_norm + 1e-8)) {  // ParameterToleranceReached
-        summary->termination = 0;
-        break;
-      }
-      const double cost_change = cost - cand_cost;
-      if (std::fabs(cost_change) <= 1e-6 * cost) {  // FunctionToleranceReached
-        summary->termination = 0;
-        break;
-      }
-      const double rho = cost_change / model_change;
-      if (rho > 1e-3) {  // HandleSuccessfulStep
-        std::swap(W->x, W->xc);
-        x = (double *)W->x.p, xc = (double *)W->xc.p;
-        // the accepted point = the candidate lm_step staged in pinned memory (|x| and the best point are host state)
-        std::memcpy(cur.data(), ctx->h_mail + 64, (size_t)n * 8);
-        x_norm = 0.0;
-        for (int i = 0; i < n; ++i) x_norm += cur[i] * cur[i];
-        x_norm = std::sqrt(x_norm);
-        // the candidate's linearisation IS the new point's
-        W->lin_sel ^= 1;
-        H = lin_H(W), g = lin_g(W);
-        cost = cand_cost, gmax = ctx->h_mail[6];
-        if (two) gmax = 1.0, two_late = true, two_at = two_slot;  // (not there yet: looked at behind the next iteration's ticket)
-        if (cost < min_cost) {
-          min_cost = cost;
-          best = cur;
-        }
-        summary->n_linearizations++;
-        radius = radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3));
-        radius = std::min(1e16, radius);
-        decrease = 2.0;
-        summary->successful_steps++;
-      } else {  // HandleUnsuccessfulStep
-        radius = radius / decrease;
-        decrease *= 2;
-        summary->unsuccessful_steps++;
-      }
+  LmLoop L = lm_begin(cfg, ctx->h_mail[kMailCost], ctx->h_mail[kMailGmax], host_norm(cur));
+  for (LmAction act; (act = lm_next(L)) != kLmStop;) {
+    WC_TRY(enqueue_attempt(ctx, W, run, act == kLmElimination, L.radius));
+    LmVerdict v = lm_judge(L, lm_mail(ctx, L));
+    if (v == kLmRetryDense) {
+      WC_TRY(enqueue_attempt(ctx, W, run, false, L.radius));
+      v = lm_judge(L, lm_mail(ctx, L));
     }
+    if (L.first_step_now && h_first_step)
+      for (int i = 0; i < n; ++i) h_first_step[i] = ctx->h_mail[kMailStage + i] - cur[i];  // (the candidate lm_step staged)
+    if (v != kLmAccepted) continue;
+    std::swap(W->x, W->xc);
+    // the accepted point = the candidate lm_step staged in pinned memory (|x| and the best point are host state)
+    std::memcpy(cur.data(), ctx->h_mail + kMailStage, (size_t)n * 8);
+    W->lin_sel ^= 1;  // the candidate's linearisation IS the new point's
+    if (lm_accepted(L, host_norm(cur), run.late_slot)) best = cur;
   }
   if (W->side_pending) {  // (the last linearisation's expansion may still run on the side stream: nothing of this solve outlives the call)
     WC_TRY(join_side(ctx, W));
     WC_HIP(ctx, hipStreamSynchronize(st));
   }
-  summary->iterations = iter;
-  summary->final_cost = min_cost;
+  *summary = lm_summary(L);
   std::memcpy(h_x_inout, best.data(), (size_t)n * 8);
   return WC_OK;
 }

@@ -547,11 +547,11 @@ __global__ void __launch_bounds__(256) k_schur_bias_y_step(const double *__restr
   if (lane == 0) sp[0][w] = mc, sp[1][w] = sn, sp[2][w] = xn, sp[3][w] = gm;
   __syncthreads();
   if (tid == 0) {
-    S.mail[2] = 0.5 * ((sp[0][0] + sp[0][1]) + (sp[0][2] + sp[0][3]));
-    S.mail[3] = sqrt((sp[1][0] + sp[1][1]) + (sp[1][2] + sp[1][3]));
-    S.mail[4] = sqrt((sp[2][0] + sp[2][1]) + (sp[2][2] + sp[2][3]));
-    S.mail[0] = S.lin_cost[0];
-    S.mail[1] = fmax(fmax(sp[3][0], sp[3][1]), fmax(sp[3][2], sp[3][3]));
+    S.mail[kMailModelChange] = 0.5 * ((sp[0][0] + sp[0][1]) + (sp[0][2] + sp[0][3]));
+    S.mail[kMailStepNorm] = sqrt((sp[1][0] + sp[1][1]) + (sp[1][2] + sp[1][3]));
+    S.mail[kMailXNorm] = sqrt((sp[2][0] + sp[2][1]) + (sp[2][2] + sp[2][3]));
+    S.mail[kMailCost] = S.lin_cost[0];
+    S.mail[kMailGmax] = fmax(fmax(sp[3][0], sp[3][1]), fmax(sp[3][2], sp[3][3]));
     __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }

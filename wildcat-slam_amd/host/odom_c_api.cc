@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "../csrc/extract_plan.h"
+#include "../csrc/lm_loop.h"
 #include "../csrc/map_room.h"
 #include "cubic_bspline.h"
 #include "histogram.h"
@@ -378,6 +379,41 @@ void wc_host_ex_sizes(uint64_t n, int max_layer, int cluster_min, uint64_t floor
   out5[2] = ex_fx_tiles(n);
   out5[3] = ex_fx_node_grid(n);
   out5[4] = ex_fx_layer2_grid((unsigned)out5[3], last_splits);
+}
+
+// csrc/lm_loop.h - the decisions of the window solver's LM loop - driven step by step over a caller-owned state block
+// (tests/test_lm_loop_cpu.py).  op -1: -> the block's size in bytes.  op 0, lm_begin: in = max_iterations, lm_radius0,
+// lm_dense_radius, lm_dense, ns, late_gradient, cost, max |g|, |x|.  op 1, lm_next -> LmAction.  op 2, lm_judge: in = fail,
+// model_change, step_norm, cand_cost, cand_gmax, late_gmax -> LmVerdict.  op 3, lm_accepted: in = |x|, late slot -> 1: best so far.
+// out22 (may be NULL), after the op: cost, gmax, min_cost, radius, decrease, x_norm, iter, consecutive_invalid, first_recorded,
+// first_step_now, late_pending, late_at, then lm_summary: initial_cost, final_cost, iterations, successful_steps,
+// unsuccessful_steps, termination, n_linearizations, n_cost_evaluations, first_step[0], first_step[1].  -2: bad op or block
+int wc_host_lm_loop(int op, void *state, uint64_t state_bytes, const double *in, double *out22) {
+  if (op == -1) return (int)sizeof(LmLoop);
+  if (!state || state_bytes < sizeof(LmLoop) || (op != 1 && !in)) return -2;
+  LmLoop L;
+  std::memcpy(&L, state, sizeof(L));
+  int rc = 0;
+  if (op == 0)
+    L = lm_begin(LmConfig{(int)in[0], (int)in[1], (int)in[2], in[3] != 0, (int)in[4], in[5] != 0}, in[6], in[7], in[8]);
+  else if (op == 1)
+    rc = (int)lm_next(L);
+  else if (op == 2)
+    rc = (int)lm_judge(L, LmMail{(int)in[0], in[1], in[2], in[3], in[4], in[5]});
+  else if (op == 3)
+    rc = lm_accepted(L, in[0], (int)in[1]) ? 1 : 0;
+  else
+    return -2;
+  std::memcpy(state, &L, sizeof(L));
+  if (out22) {
+    const wc_solve_summary s = lm_summary(L);
+    const double o[22] = {L.cost, L.gmax, L.min_cost, L.radius, L.decrease, L.x_norm, (double)L.iter, (double)L.consecutive_invalid,
+                          (double)L.first_recorded, (double)L.first_step_now, (double)L.late_pending, (double)L.late_at,
+                          s.initial_cost, s.final_cost, (double)s.iterations, (double)s.successful_steps, (double)s.unsuccessful_steps,
+                          (double)s.termination, (double)s.n_linearizations, (double)s.n_cost_evaluations, s.first_step[0], s.first_step[1]};
+    std::memcpy(out22, o, sizeof(o));
+  }
+  return rc;
 }
 
 // utils_test.cc:5-21 inputs -> out52 = Exp(v) | Log(Exp(v)) | Jl | Jl_inv | Jr | Jr_inv | Hat (layout of wc_selftest_so3)
