@@ -96,6 +96,16 @@ typedef struct wc_map_hit {
   double d2;      /* squared distance query -> centroid                                                      */
 } wc_map_hit;
 
+/* wc_map_knn (wildcat_hip.h: "k nearest voxels within a radius"; not a reference type) */
+#define WC_MAP_KNN_NOT_OWN 1u /* skip the candidate whose voxel index equals the query's own kq */
+typedef struct wc_map_knn_params { /* 24 bytes */
+  double max_dist;     /* > 0, may be +inf; NaN or <= 0: WC_ERR_ARG                                       */
+  uint32_t k;          /* 1 .. 16: records per query                                                      */
+  uint32_t reach;      /* 1 or 2: candidates are the voxels kq + {-reach .. reach}^3 (27 or 125)          */
+  uint32_t min_points; /* >= 1: a candidate needs count >= min_points                                     */
+  uint32_t flags;      /* WC_MAP_KNN_NOT_OWN or 0; any other bit: WC_ERR_ARG                              */
+} wc_map_knn_params;
+
 /* wc_map_create_ex flags */
 #define WC_MAP_MOMENTS 1u /* every voxel also accumulates the second moments of its points: surfel export and plane queries */
 

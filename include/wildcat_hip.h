@@ -418,6 +418,30 @@ int wc_map_clear(wc_ctx *ctx, wc_map *m);
  * h_n_found (may be NULL) receives the number of accepted hits; asking for it waits for the stream, passing NULL returns without
  * waiting.  queries->n == 0 is WC_OK; NULL d_hits with n > 0 or a map of another context is WC_ERR_ARG.  The map is not modified. */
 int wc_map_nearest(wc_ctx *ctx, wc_map *m, const wc_points *queries, double max_dist, wc_map_hit *d_hits, uint64_t *h_n_found);
+/* k nearest voxels within a radius.  For every query point q (the wc_points rules of wc_map_nearest) d_hits receives params->k
+ * wc_map_hit records, d_hits[i * k + j], j = 0 .. k - 1, and d_within[i] (may be NULL) one count; a pure function of the exported map
+ * and the query:
+ *   voxel of the query  kq and the query that cannot be searched: exactly wc_map_nearest's
+ *   candidates          the occupied voxels with index kq + {-reach .. reach}^3 (27 for reach 1, 125 for reach 2) whose every index
+ *                       lies inside the key range (others are skipped), with count >= min_points and, with WC_MAP_KNN_NOT_OWN, an
+ *                       index other than kq
+ *   distance            wc_map_nearest's d2: to the float centroid wc_map_export returns, (dx*dx + dy*dy) + dz*dz in fp64, no fused
+ *                       multiply-add
+ *   acceptance          a candidate is accepted iff d2 <= max_dist * max_dist (the product formed once on the host in fp64)
+ *   answer              the accepted candidates in ascending d2, ties in ascending (kx, ky, kz): the first min(k, within) of them are the
+ *                       query's first records, ordinary wc_map_hit records; its remaining records are the miss record (zeros, d2 = +inf)
+ *   d_within[i]         the number of accepted candidates, NOT capped by k: the neighbour count of a radius filter
+ *   unsearchable query  all k records are the miss record with flags = 1, and d_within[i] = 0
+ * so a restatement on the exported map reproduces every record bit for bit.  Consequence: a centroid within max_dist <= reach * v of q
+ * lies in one of the candidate voxels, so for max_dist <= reach * v the answer is the k globally nearest centroids within max_dist, with
+ * wc_map_nearest's one exception (a centroid that the rounding to float carried across a face of its own voxel).  With k = 1, reach = 1,
+ * min_points = 1 and flags = 0 the records are byte for byte wc_map_nearest's.
+ * h_out (may be NULL) receives {queries with within > 0, records written = sum of min(k, within), sum of within}; asking for it waits
+ * for the stream, passing NULL returns without waiting.  queries->n == 0 is WC_OK.  WC_ERR_ARG, with every output untouched: NULL params,
+ * NULL d_hits with n > 0, k outside 1 .. 16, reach other than 1 or 2, min_points == 0, an unknown flag, max_dist NaN or <= 0, a map of
+ * another context.  The map is not modified; plain and WC_MAP_MOMENTS maps behave alike; a removed voxel is never a candidate. */
+int wc_map_knn(wc_ctx *ctx, wc_map *m, const wc_points *queries, const wc_map_knn_params *params, wc_map_hit *d_hits, uint32_t *d_within,
+               uint64_t h_out[3]);
 /* Crop and compact.  A voxel k is kept iff floor(lo[a] / v) <= k[a] <= floor(hi[a] / v) on all three axes (the voxels that intersect
  * the box); +-inf bounds are allowed and clamped to the key range, NaN or lo[a] > hi[a] is WC_ERR_ARG.  The kept voxels keep their
  * integer sums and counts: the result is, bit for bit, the map of exactly those inserted points whose voxel is kept.  They are

@@ -24,6 +24,10 @@
 //   k_map_centroids export: centroid = r + sum / (count * 2^32) in fp64, rounded once to float; count; key (optional)
 //   k_map_nearest   query: one lane per query; the first-slot key loads of the 27 voxels around the query's own are issued nine at a
 //                   time before any is examined, payload loads and divisions only for the occupied ones; read-only probes, no CAS
+//   k_map_knn<KMAX, REACH>  k nearest within a radius: one lane per query; the 27 or 125 voxels around it in ascending key order, the
+//                   first-slot key loads of nine (an x plane) or five (a z row) in flight together, read-only chains; a sorted list of
+//                   KMAX (d2, slot) entries in registers, every index a compile-time constant; k records per query, the count of
+//                   accepted voxels uncapped: wc_map_knn
 //   k_map_count<SEL>  the selected voxels and their points, counted per workgroup: a crop's kept ones (then k_map_rehash<map_sel_box>),
 //                   a carve's seen-through ones
 //   k_map_surfels   surfel export: one lane per sorted voxel: map_plane_of (exact 128-bit covariance numerator, fx_eig3) -> wc_map_surfel
@@ -136,7 +140,8 @@ constexpr int kMapKeyOff = 1 << 20;
 constexpr int kCtrOcc = 0, kCtrPts = 16, kCtrRej = 32, kCtrRejCall = 48, kCtrLost = 56;  // u64 word of each counter
 constexpr int kCtrFound = 64, kCtrKeepVox = 80, kCtrKeepPts = 96;                        // query hits; a crop's kept voxels, points
 constexpr int kCtrRmVox = 112, kCtrRmPts = 128, kCtrRmNone = 144;                        // wc_map_remove_keys: voxels, points, keys that removed nothing
-constexpr int kCtrMvVox = 160, kCtrMvPts = 176, kCtrMvRejVox = 192, kCtrMvRejPts = 208, kCtrWords = 224;  // wc_map_merge_moved: this call's four counts
+constexpr int kCtrMvVox = 160, kCtrMvPts = 176, kCtrMvRejVox = 192, kCtrMvRejPts = 208, kCtrMvEnd = 224;  // wc_map_merge_moved: this call's four counts
+constexpr int kCtrKnnSome = 224, kCtrKnnRec = 240, kCtrKnnWithin = 256, kCtrWords = 272;  // wc_map_knn: queries with a neighbour, records, sum of within
 constexpr int kNearThreads = 256;
 constexpr int kCompactChunk = 2048;                // slots per workgroup of k_map_compact
 constexpr int kCarveThreads = 256;
@@ -670,6 +675,123 @@ __global__ void __launch_bounds__(kNearThreads) k_map_nearest(wc_points q, doubl
     ((double *)o)[4] = hit ? w.best : __builtin_inf();
   }
   block_count<kNearThreads>({n_found}, {found});
+}
+
+// k nearest within a radius (wc_map_knn): the candidates are the occupied voxels of kq + {-REACH .. REACH}^3 that hold min_points points
+// (and, with not_own, are not kq itself), the distance is map_search's d2, a candidate is accepted iff d2 <= max_d2, and the answer is
+// the accepted ones in ascending (d2, key).  One lane per query, grid-strided.  The neighbours are visited in ascending key order (x
+// outermost), a batch at a time - an x plane of nine (REACH 1) or a z row of five (REACH 2) - whose first-slot key loads are issued
+// before any is looked at, as map_search does; the batches are a rolled loop, so the code is one batch long.  The list is KMAX entries
+// of (d2, slot) in registers, kept sorted by a fully unrolled compare-and-shift (every index a compile-time constant: no scratch) that
+// moves a candidate in front of an entry only on a strictly smaller d2: ties keep the visiting order, the key order, with no key
+// compare.  An entry's centroid, count and index are formed again from its slot at write-out, by the expressions the search used.
+constexpr int kKnnThreads = 256;
+template <int KMAX>
+struct map_knn_list {
+  double d[KMAX];
+  unsigned s[KMAX];
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j) d[j] = __builtin_inf(), s[j] = 0u;
+  }
+  // entry j becomes the candidate, its predecessor or itself; descending j reads only entries not yet rewritten
+  __device__ __forceinline__ void insert(double d2, unsigned slot) {
+#pragma unroll
+    for (int j = KMAX - 1; j >= 0; --j) {
+      const bool here = d2 < d[j];
+      bool up = false;
+      if constexpr (KMAX > 1)
+        if (j > 0) up = d2 < d[j > 0 ? j - 1 : 0];
+      const double pd = up ? d[j > 0 ? j - 1 : 0] : d2;
+      const unsigned ps = up ? s[j > 0 ? j - 1 : 0] : slot;
+      d[j] = here ? pd : d[j];
+      s[j] = here ? ps : s[j];
+    }
+  }
+};
+
+template <int KMAX, int REACH>
+__global__ void __launch_bounds__(kKnnThreads) k_map_knn(wc_points q, double v, double max_d2, unsigned k, unsigned min_points, unsigned not_own,
+                                                         const unsigned long long *keys, const long long *pay, unsigned long long mask,
+                                                         wc_map_hit *hits, uint32_t *within, unsigned long long *n_some,
+                                                         unsigned long long *n_rec, unsigned long long *n_within) {
+  constexpr int W = 2 * REACH + 1;
+  constexpr int B = REACH == 1 ? 9 : 5;  // neighbours of a batch
+  constexpr int NB = W * W * W / B;      // 3 planes, 25 rows
+  unsigned long long c_some = 0, c_rec = 0, c_within = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * kKnnThreads;
+  for (uint64_t i = (uint64_t)blockIdx.x * kKnnThreads + threadIdx.x; i < q.n; i += stride) {
+    const float *f = (const float *)((const char *)q.xyz + i * q.xyz_stride);
+    const double x = (double)f[0], y = (double)f[1], z = (double)f[2];
+    int kx, ky, kz;
+    const bool ok = map_voxel_of(x, y, z, v, kx, ky, kz);
+    map_knn_list<KMAX> L;
+    L.clear();
+    unsigned nw = 0;
+    if (ok) {
+#pragma unroll 1
+      for (int b = 0; b < NB; ++b) {
+        const int bx = REACH == 1 ? b - 1 : b / W - REACH, by = REACH == 1 ? 0 : b % W - REACH;  // (REACH 1: y and z come from j)
+        unsigned long long key[B], h[B], cur[B];
+#pragma unroll
+        for (int j = 0; j < B; ++j) {
+          const int ox = bx, oy = REACH == 1 ? j / 3 - 1 : by, oz = REACH == 1 ? j % 3 - 1 : j - REACH;
+          const int nx = kx + ox, ny = ky + oy, nz = kz + oz;
+          // (a neighbour beyond the key range, or the query's own voxel under not_own: the empty mark, as in map_search)
+          const bool in = nx > -kMapKeyOff && nx < kMapKeyOff && ny > -kMapKeyOff && ny < kMapKeyOff && nz > -kMapKeyOff && nz < kMapKeyOff &&
+                          !(not_own && (ox | oy | oz) == 0);
+          key[j] = in ? map_pack(nx, ny, nz) : kMapEmpty;
+          h[j] = in ? map_hash(key[j]) & mask : 0;
+          cur[j] = keys[h[j]];
+        }
+#pragma unroll
+        for (int j = 0; j < B; ++j) {
+          if (key[j] == kMapEmpty) continue;
+          unsigned long long hj = h[j];
+          if (!map_find_from(keys, mask, key[j], hj, cur[j])) continue;
+          const longlong2 *p = (const longlong2 *)(pay + 4 * hj);
+          const longlong2 p0 = p[0], p1 = p[1];
+          if ((unsigned long long)p1.y < min_points) continue;
+          const double cnt = (double)p1.y;
+          const int nx = kx + bx, ny = ky + (REACH == 1 ? j / 3 - 1 : by), nz = kz + (REACH == 1 ? j % 3 - 1 : j - REACH);
+          const float cx = map_centroid(nx, v, p0.x, cnt), cy = map_centroid(ny, v, p0.y, cnt), cz = map_centroid(nz, v, p1.x, cnt);
+          const double ex = x - (double)cx, ey = y - (double)cy, ez = z - (double)cz;
+          const double d2 = (ex * ex + ey * ey) + ez * ez;
+          if (!(d2 <= max_d2)) continue;
+          ++nw;
+          if (d2 < L.d[KMAX - 1]) L.insert(d2, (unsigned)hj);
+        }
+      }
+    }
+    const unsigned n_out = nw < k ? nw : k;
+    c_some += nw ? 1u : 0u, c_rec += n_out, c_within += nw;
+    if (within) within[i] = nw;
+    // the k 40-byte records as five 8-byte stores each (the records are 8-aligned)
+    uint2 *o = (uint2 *)(hits + i * k);
+    const unsigned flags = ok ? 0u : 1u;
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j) {
+      if ((unsigned)j >= k) continue;  // (k <= KMAX)
+      if ((unsigned)j < n_out) {
+        const unsigned long long hj = L.s[j], key = keys[hj];
+        const longlong2 *p = (const longlong2 *)(pay + 4 * hj);
+        const longlong2 p0 = p[0], p1 = p[1];
+        const double cnt = (double)p1.y;
+        const int nx = map_unpack(key, 0), ny = map_unpack(key, 1), nz = map_unpack(key, 2);
+        const float cx = map_centroid(nx, v, p0.x, cnt), cy = map_centroid(ny, v, p0.y, cnt), cz = map_centroid(nz, v, p1.x, cnt);
+        o[5 * j + 0] = make_uint2(__float_as_uint(cx), __float_as_uint(cy));
+        o[5 * j + 1] = make_uint2(__float_as_uint(cz), (unsigned)p1.y);
+        o[5 * j + 2] = make_uint2((unsigned)nx, (unsigned)ny);
+        o[5 * j + 3] = make_uint2((unsigned)nz, flags);
+        ((double *)o)[5 * j + 4] = L.d[j];
+      } else {
+        o[5 * j + 0] = make_uint2(0u, 0u), o[5 * j + 1] = make_uint2(0u, 0u), o[5 * j + 2] = make_uint2(0u, 0u);
+        o[5 * j + 3] = make_uint2(0u, flags);
+        ((double *)o)[5 * j + 4] = __builtin_inf();
+      }
+    }
+  }
+  block_count<kKnnThreads>({c_some, c_rec, c_within}, {n_some, n_rec, n_within});
 }
 
 // ---- registration (wc_map_linearize) ----------------------------------------------------------------------------------------------
@@ -2280,7 +2402,7 @@ extern "C" int wc_map_merge_moved(wc_ctx *ctx, wc_map *dst, wc_map *src, const d
     return WC_OK;
   }
   WC_TRY(map_make_room(ctx, dst, n, __func__));
-  WC_HIP(ctx, hipMemsetAsync(dst->ctr + kCtrMvVox, 0, (size_t)(kCtrWords - kCtrMvVox) * 8, ctx->stream));
+  WC_HIP(ctx, hipMemsetAsync(dst->ctr + kCtrMvVox, 0, (size_t)(kCtrMvEnd - kCtrMvVox) * 8, ctx->stream));
   map_pose P;
   std::memcpy(P.T, T, sizeof(P.T));
   const unsigned grid = (unsigned)((src->cap + kStateThreads - 1) / kStateThreads);
@@ -2422,6 +2544,57 @@ extern "C" int wc_map_nearest_plane(wc_ctx *ctx, wc_map *m, const wc_points *que
     return wc_fail(ctx, WC_ERR_ARG, "%s: a map created without WC_MAP_MOMENTS, or min_points < 3", __func__);
   }
   return map_nearest(ctx, m, queries, max_dist, min_points, d_hits, h_n_found, __func__);
+}
+
+namespace {
+template <int KMAX, int REACH>
+void knn_launch(wc_ctx *ctx, wc_map *m, const wc_points &q, double max_d2, const wc_map_knn_params &p, wc_map_hit *d_hits, uint32_t *d_within,
+                unsigned grid) {
+  k_map_knn<KMAX, REACH><<<grid, kKnnThreads, 0, ctx->stream>>>(q, m->voxel, max_d2, p.k, p.min_points, p.flags & WC_MAP_KNN_NOT_OWN, m->keys,
+                                                                m->pay, m->cap - 1, d_hits, d_within, m->ctr + kCtrKnnSome,
+                                                                m->ctr + kCtrKnnRec, m->ctr + kCtrKnnWithin);
+}
+template <int REACH>
+void knn_launch_k(wc_ctx *ctx, wc_map *m, const wc_points &q, double max_d2, const wc_map_knn_params &p, wc_map_hit *d_hits, uint32_t *d_within,
+                  unsigned grid) {
+  // the smallest instantiation that holds k entries
+  if (p.k <= 1) knn_launch<1, REACH>(ctx, m, q, max_d2, p, d_hits, d_within, grid);
+  else if (p.k <= 4) knn_launch<4, REACH>(ctx, m, q, max_d2, p, d_hits, d_within, grid);
+  else if (p.k <= 8) knn_launch<8, REACH>(ctx, m, q, max_d2, p, d_hits, d_within, grid);
+  else knn_launch<16, REACH>(ctx, m, q, max_d2, p, d_hits, d_within, grid);
+}
+}  // namespace
+
+extern "C" int wc_map_knn(wc_ctx *ctx, wc_map *m, const wc_points *queries, const wc_map_knn_params *params, wc_map_hit *d_hits,
+                          uint32_t *d_within, uint64_t h_out[3]) {
+  wc_dev_guard dg_(ctx);
+  const wc_points *q = queries;
+  const wc_map_knn_params *p = params;
+  if (!map_ok(ctx, m) || !map_points_ok(q) || !p || !(p->max_dist > 0.0) || p->k < 1 || p->k > 16 || (p->reach != 1 && p->reach != 2) ||
+      p->min_points < 1 || (p->flags & ~(uint32_t)WC_MAP_KNN_NOT_OWN) || (q->n && (!d_hits || (uintptr_t)d_hits % 8)) ||
+      (uintptr_t)d_within % 4)
+    return wc_fail(ctx, WC_ERR_ARG,
+                   "%s: null or out-of-range argument (max_dist > 0, k in 1 .. 16, reach 1 or 2, min_points >= 1, known flags, a map of "
+                   "this context)",
+                   __func__);
+  if (h_out) h_out[0] = h_out[1] = h_out[2] = 0;
+  if (q->n == 0) return WC_OK;
+  const double max_d2 = p->max_dist * p->max_dist;  // (formed once, here: the kernel accepts d2 <= max_d2)
+  if (h_out) WC_HIP(ctx, hipMemsetAsync(m->ctr + kCtrKnnSome, 0, (size_t)(kCtrWords - kCtrKnnSome) * 8, ctx->stream));
+  const uint64_t blocks = (q->n + kKnnThreads - 1) / kKnnThreads;
+  const unsigned grid = (unsigned)std::min<uint64_t>(blocks, (uint64_t)8 * m->cus);
+  if (p->reach == 1)
+    knn_launch_k<1>(ctx, m, *q, max_d2, *p, d_hits, d_within, grid);
+  else
+    knn_launch_k<2>(ctx, m, *q, max_d2, *p, d_hits, d_within, grid);
+  WC_HIP(ctx, hipGetLastError());
+  if (h_out) {
+    WC_HIP(ctx, hipMemcpyAsync(m->h_ctr + kCtrKnnSome, m->ctr + kCtrKnnSome, (size_t)(kCtrWords - kCtrKnnSome) * 8, hipMemcpyDeviceToHost,
+                               ctx->stream));
+    WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    h_out[0] = m->h_ctr[kCtrKnnSome], h_out[1] = m->h_ctr[kCtrKnnRec], h_out[2] = m->h_ctr[kCtrKnnWithin];
+  }
+  return WC_OK;
 }
 
 // ---- registration against the map (include/wildcat_hip.h: wc_map_linearize, wc_map_align) ------------------------------------------

@@ -738,6 +738,23 @@ size_t LidarOdometry::QueryMap(const float *xyz, size_t n, double max_dist, wc_m
   d_hits.ToHost(hits, n * sizeof(wc_map_hit));
   return found;
 }
+size_t LidarOdometry::QueryMapKnn(const float *xyz, size_t n, const wc_map_knn_params &p, wc_map_hit *hits, uint32_t *within) {
+  if (!n || !xyz || !hits) return 0;
+  if (!(p.max_dist > 0.0) || p.k < 1 || p.k > 16 || (p.reach != 1 && p.reach != 2) || p.min_points < 1 || (p.flags & ~(uint32_t)WC_MAP_KNN_NOT_OWN))
+    return 0;
+  if (!map_) {
+    FillMisses(hits, n * p.k);
+    if (within) std::memset(within, 0, n * sizeof(uint32_t));
+    return 0;
+  }
+  const DevBuf d_xyz(ctx_, n * 3 * sizeof(float)), d_hits(ctx_, n * p.k * sizeof(wc_map_hit)), d_within(ctx_, n * sizeof(uint32_t));
+  const wc_points desc = UploadXyz(d_xyz, xyz, n);
+  uint64_t out[3] = {0, 0, 0};
+  WC_CALL(wc_map_knn(ctx_, map_, &desc, &p, (wc_map_hit *)d_hits.p, (uint32_t *)d_within.p, out));
+  d_hits.ToHost(hits, n * p.k * sizeof(wc_map_hit));
+  if (within) d_within.ToHost(within, n * sizeof(uint32_t));
+  return out[0];
+}
 size_t LidarOdometry::CropMap(const double lo[3], const double hi[3]) {
   uint64_t removed = 0;
   if (map_) WC_CALL(wc_map_crop(ctx_, map_, lo, hi, &removed));

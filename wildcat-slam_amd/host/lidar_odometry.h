@@ -90,6 +90,10 @@ class LidarOdometry {
   // nearest map voxel of n host points (xyz: n x 3 floats) within max_dist (> 0, may be +inf): hits[n] as wc_map_nearest defines them;
   // returns the number found.  Without a map: 0, every hit a miss
   size_t QueryMap(const float *xyz, size_t n, double max_dist, wc_map_hit *hits);
+  // wc_map_knn for n host points (xyz: n x 3 floats): hits[n * p.k], within[n] (may be null); returns the number of queries with a
+  // neighbour (as QueryMap).  Without a map: 0, every record a miss and every count 0.  Parameters the library would refuse (k outside
+  // 1 .. 16 among them, so the size of hits is unknown): 0, nothing written
+  size_t QueryMapKnn(const float *xyz, size_t n, const wc_map_knn_params &p, wc_map_hit *hits, uint32_t *within);
   // drops the voxels that do not intersect the box [lo, hi] and compacts the table (wc_map_crop); returns the voxels removed
   size_t CropMap(const double lo[3], const double hi[3]);
   // config().map_surfels = on, the map re-created empty (as SetMapVoxel does)

@@ -211,6 +211,10 @@ double wc_odom_map_ms(void *h) { return ((const LidarOdometry *)h)->last_map_ms(
 uint64_t wc_odom_map_query(void *h, const float *xyz, uint64_t n, double max_dist, wc_map_hit *hits) {
   return ((LidarOdometry *)h)->QueryMap(xyz, n, max_dist, hits);
 }
+// wc_map_knn for n host points (n x 3 floats) -> hits[n * params->k] (wc_map_hit), within[n] (may be NULL); returns the queries with a neighbour
+uint64_t wc_odom_map_query_knn(void *h, const float *xyz, uint64_t n, const wc_map_knn_params *params, wc_map_hit *hits, uint32_t *within) {
+  return params ? ((LidarOdometry *)h)->QueryMapKnn(xyz, n, *params, hits, within) : 0;
+}
 // keeps the voxels that intersect the box [lo, hi]; returns the voxels removed
 uint64_t wc_odom_map_crop(void *h, const double lo[3], const double hi[3]) { return ((LidarOdometry *)h)->CropMap(lo, hi); }
 // LioConfig::map_surfels: the map re-created empty, with (1) or without (0) second moments

@@ -932,6 +932,31 @@ class PointMap:
             self.nearest_device(desc, max_dist, d_hits)
             return d_hits.download(R.MAP_HIT, desc.n)
 
+    def knn_device(self, desc, params, d_hits, d_within=None, want_counts=True):
+        """queries already in HBM (a wc_points descriptor) -> params.k MAP_HIT records per query in d_hits and, if given, one uint32 per
+        query in d_within (wc_map_knn, params: R.MapKnnParams); returns (queries with a neighbour, records written, sum of within), or
+        None without waiting when want_counts is False"""
+        out = (C.c_uint64 * 3)()
+        self.ctx._ck(self.lib.wc_map_knn(self.ctx.h, self.h, C.byref(desc), C.byref(params), C.c_void_p(d_hits.ptr if d_hits else 0),
+                                         C.c_void_p(d_within.ptr if d_within else 0), out if want_counts else None))
+        return tuple(int(x) for x in out) if want_counts else None
+
+    def knn(self, queries, k, max_dist=np.inf, reach=1, min_points=1, not_own=False):
+        """POINT records or an (n, 3) float32 array (uploaded for the call) -> (hits (n, k) MAP_HIT, within (n,) uint32): per query the
+        centroids of the voxels around it - 27 with reach 1, 125 with reach 2 - that hold min_points points and lie within max_dist,
+        nearest first, ties by voxel index; the records past the last one found are misses (count = 0).  within is the number of such
+        voxels, not capped by k.  not_own leaves the query's own voxel out"""
+        params = R.MapKnnParams(float(max_dist), int(k), int(reach), int(min_points), R.MAP_KNN_NOT_OWN if not_own else 0)
+        with self._uploaded(queries) as (desc, _):
+            d_hits = self.ctx.alloc(R.MAP_HIT.itemsize * max(desc.n * max(int(k), 1), 1))
+            d_within = self.ctx.alloc(4 * max(desc.n, 1))
+            try:
+                self.knn_device(desc, params, d_hits, d_within, want_counts=False)
+                return d_hits.download(R.MAP_HIT, desc.n * int(k)).reshape(desc.n, int(k)), d_within.download(np.uint32, desc.n)
+            finally:
+                d_hits.free()
+                d_within.free()
+
     def crop(self, lo, hi):
         """keeps the voxels that intersect the box [lo, hi] (+-inf allowed) and compacts the table (wc_map_crop) -> voxels removed"""
         lo, hi = (C.c_double * 3)(*[float(x) for x in lo]), (C.c_double * 3)(*[float(x) for x in hi])
@@ -1476,6 +1501,19 @@ class Odometry:
         self.lib.wc_odom_map_query.restype = C.c_uint64
         self.lib.wc_odom_map_query(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), C.c_double(max_dist), R.ptr(hits))
         return hits
+
+    def map_query_knn(self, xyz, k, max_dist=np.inf, reach=1, min_points=1, not_own=False):
+        """PointMap.knn of every row of xyz ((n, 3) float32) against the facade's map -> (hits (n, k) MAP_HIT, within (n,) uint32)
+        (LidarOdometry::QueryMapKnn); without a map every record is a miss"""
+        k = int(k)
+        if not (max_dist > 0 and 1 <= k <= 16 and reach in (1, 2) and min_points >= 1):
+            raise WildcatError(11, "map_query_knn: max_dist must be > 0, k in 1 .. 16, reach 1 or 2, min_points >= 1")
+        params = R.MapKnnParams(float(max_dist), k, int(reach), int(min_points), R.MAP_KNN_NOT_OWN if not_own else 0)
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        hits, within = np.zeros((len(xyz), k), R.MAP_HIT), np.zeros(len(xyz), np.uint32)
+        self.lib.wc_odom_map_query_knn.restype = C.c_uint64
+        self.lib.wc_odom_map_query_knn(self.h, R.ptr(xyz), C.c_uint64(len(xyz)), C.byref(params), R.ptr(hits), R.ptr(within))
+        return hits, within
 
     def map_crop(self, lo, hi):
         """keeps the map's voxels that intersect the box [lo, hi] -> voxels removed (LidarOdometry::CropMap)"""

@@ -297,6 +297,16 @@ class MapRaycastResult(C.Structure):
     ]
 
 
+MAP_KNN_NOT_OWN = 1  # WC_MAP_KNN_NOT_OWN
+
+
+class MapKnnParams(C.Structure):
+    """wc_map_knn_params"""
+
+    _fields_ = [("max_dist", C.c_double), ("k", C.c_uint32), ("reach", C.c_uint32), ("min_points", C.c_uint32), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(MapKnnParams) == 24
 assert C.sizeof(MapCarveParams) == 32 and C.sizeof(MapCarveResult) == 40
 assert C.sizeof(MapRaycastParams) == 32 and C.sizeof(MapRaycastResult) == 32
 assert C.sizeof(MapRegParams) == 32 and C.sizeof(MapAlignOpts) == 64 and C.sizeof(MapAlignSummary) == 88
