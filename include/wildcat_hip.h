@@ -42,11 +42,27 @@ const char *wc_version(void);
 int wc_device_count(void);
 void wc_params_default(wc_params *p); /* SURVEY.md §2.1 values: surfel_extraction.cc:327, knn_surfel_matcher.h:37-41,
                                          lio_config.h:10-14,32-45 */
+/* Host only, no context, no GPU: WC_OK when every field of p is a value the library can run with, else WC_ERR_ARG and, in *field
+ * (may be NULL), the name of the first field that is not (a static string; NULL when p passes).  The rules: voxel_size, surfel_sigma0,
+ * cauchy_a and imu_dt finite and > 0; planer_threshold, cluster_gap and the four IMU weights finite and >= 0; min_plane_likeness and
+ * view_point finite; center_scale and angular_scale finite and not 0 (a negative scale is a scale); surfel_dist_max and time_diff_min
+ * anything but NaN (an infinite gate is a gate that is always open or always shut); max_layer 0..2, min_points >= 0,
+ * cluster_min_points >= 1, knn_k 1..16, max_iterations >= 0.  Every one of these is divided by, or scales what goes into a kernel:
+ * a value outside them would put NaN or infinity into the kd-tree's features, the loss or the IMU Jacobians. */
+int wc_params_check(const wc_params *p, const char **field);
+/* params NULL: wc_params_default.  Parameters that fail wc_params_check: WC_ERR_ARG, no context. */
 int wc_ctx_create(const wc_params *params, int device, wc_ctx **out);
 void wc_ctx_destroy(wc_ctx *ctx);
 const char *wc_last_error(const wc_ctx *ctx);
 int wc_ctx_set_stream(wc_ctx *ctx, void *hip_stream); /* NULL = the ctx's own stream */
+/* Replaces the context's parameters.  Parameters that fail wc_params_check are refused before anything is launched: WC_ERR_ARG,
+ * wc_last_error names the field and its rule, and the context keeps the parameters it had.
+ * When a parameter is read: extraction and matcher parameters by the call that extracts or matches; the factor parameters
+ * (surfel_sigma0, cauchy_a, w_gyr, w_acc, w_bg, w_ba, imu_dt, reference_quirks) by wc_window_build, which copies them into the
+ * problem - a wc_ctx_set_params between the build and wc_window_linearize / _evaluate / _solve does not change the problem built;
+ * max_iterations by wc_window_solve, at the solve. */
 int wc_ctx_set_params(wc_ctx *ctx, const wc_params *params);
+int wc_ctx_get_params(const wc_ctx *ctx, wc_params *out); /* the parameters in force (a copy; host only) */
 /* Development options of ONE context - the only way to change what the release library executes besides wc_params.  The release
  * build reads no environment variable that alters a result or a code path (a stray WC_* variable cannot change what a node runs);
  * the variables it does read only PRINT: WC_ALLOC_DEBUG, WC_FX_DEBUG, WC_MATCH_DEBUG, WC_MATCH_TIMING, WC_WIN_DEBUG, WC_DEBUG_GATHER
@@ -321,7 +337,10 @@ int wc_match_pair(wc_ctx *ctx, const wc_surfel *d_sld_surf, const wc_pose *d_sld
  * device finds (a surfel stamp outside the sample-state range, a correspondence that is not (older, newer)) are reported by it;
  * the call's LAST device work - the records and one copy of host-built lists - may still be in flight on the ctx stream.  The
  * calls that use the problem (wc_window_solve / _linearize / _evaluate) are enqueued behind it on that stream; a caller that reads
- * the device arguments' buffers on ANOTHER stream orders itself with an event on the ctx stream, as after any asynchronous call. */
+ * the device arguments' buffers on ANOTHER stream orders itself with an event on the ctx stream, as after any asynchronous call.
+ * Parameters: the build copies the context's factor parameters (surfel_sigma0, cauchy_a, w_gyr, w_acc, w_bg, w_ba, imu_dt,
+ * reference_quirks) into the problem; every later linearisation, evaluation and solve of this problem uses that copy, whatever
+ * wc_ctx_set_params is given in between.  max_iterations alone is read by wc_window_solve when it is called. */
 int wc_window_build(wc_ctx *ctx, const wc_surfel *d_sld_surf, const wc_pose *d_sld_pose, const wc_pair *d_pairs_sld,
                     uint64_t n_pairs_sld, const wc_surfel *d_fix_surf, const wc_pose *d_fix_pose, const wc_pair *d_pairs_fix,
                     uint64_t n_pairs_fix, const wc_imu_state *h_imu, uint64_t n_imu, const double *h_sample_times, uint64_t ns,

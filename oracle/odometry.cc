@@ -97,6 +97,12 @@ struct wco_odom {
   double imu_rate = 200, sample_dt = 0.08, fixed_window_duration = 20.0, sliding_window_duration = 6.0, sweep_duration = 0.5;
   double gravity_norm = 9.81;
   int outer_iter_num_max = 1, inner_iter_num_max = 100;
+  // lio_config.h:10-14
+  double gyroscope_noise_density = 0.00015198973532354657, accelerometer_noise_density = 0.006308226052016165;
+  double gyroscope_random_walk = 0.00011673723527962174, accelerometer_random_walk = 2.664506559330434e-06;
+  double imu_factor_weight = 0.01;
+  double ext_rot[9] = {-5.32125e-08, -1, 0, -1, -5.32125e-08, -0, 0, 0, -1};  // lio_config.h:25-28
+  bool data_added = false;
   wc_params P;
 
   std::deque<ImuMsg> imu_buff;
@@ -242,14 +248,62 @@ void shrink_to_fit(wco_odom *o) {
 
 }  // namespace
 
+namespace {
+// what follows from the configuration values: the stages' parameters and the extrinsic quaternion.  The cost weights are
+// lio_config.h:42-45 word for word (the members there are initialised from the members above them)
+void derive(wco_odom *o) {
+  const int quirks = o->P.reference_quirks;
+  wco_params_default(&o->P);
+  o->P.reference_quirks = quirks;
+  const double imu_rate = o->imu_rate, imu_factor_weight = o->imu_factor_weight;
+  o->P.w_gyr = 1 / (o->gyroscope_noise_density * std::sqrt(imu_rate)) * imu_factor_weight;
+  o->P.w_acc = 1 / (o->accelerometer_noise_density * std::sqrt(imu_rate)) * imu_factor_weight;
+  o->P.w_bg = 1 / (o->gyroscope_random_walk / std::sqrt(imu_rate)) * imu_factor_weight;
+  o->P.w_ba = 1 / (o->accelerometer_random_walk / std::sqrt(imu_rate)) * imu_factor_weight;
+  o->P.imu_dt = 1 / imu_rate;  // (ImuFactor's dt: lidar_odometry.cc:331)
+  o->P.max_iterations = o->inner_iter_num_max;
+  stq(o->ext_q, quat_from_matrix_eigen(o->ext_rot));
+}
+}  // namespace
+
 extern "C" wco_odom *wco_odom_create(void) {
   wco_odom *o = new wco_odom;
+  std::memset(&o->P, 0, sizeof(o->P));  // (the struct's padding too: wco_odom_params hands out its bytes)
   wco_params_default(&o->P);
-  o->P.max_iterations = o->inner_iter_num_max;
-  const double rot[9] = {-5.32125e-08, -1, 0, -1, -5.32125e-08, -0, 0, 0, -1};  // lio_config.h:25-28
-  stq(o->ext_q, quat_from_matrix_eigen(rot));
+  derive(o);
   return o;
 }
+
+extern "C" void wco_odom_get_config(const wco_odom *o, wco_odom_config *c) {
+  c->gyroscope_noise_density = o->gyroscope_noise_density, c->accelerometer_noise_density = o->accelerometer_noise_density;
+  c->gyroscope_random_walk = o->gyroscope_random_walk, c->accelerometer_random_walk = o->accelerometer_random_walk;
+  c->imu_factor_weight = o->imu_factor_weight;
+  c->max_range = o->max_range, c->min_range = o->min_range;
+  for (int i = 0; i < 3; ++i) c->blind_min[i] = o->blind_min[i], c->blind_max[i] = o->blind_max[i], c->ext_translation[i] = o->ext_t[i];
+  for (int i = 0; i < 9; ++i) c->ext_rotation[i] = o->ext_rot[i];
+  c->imu_rate = o->imu_rate, c->sample_dt = o->sample_dt, c->fixed_window_duration = o->fixed_window_duration;
+  c->sliding_window_duration = o->sliding_window_duration, c->sweep_duration = o->sweep_duration;
+  c->gravity_norm = o->gravity_norm;
+  c->outer_iter_num_max = o->outer_iter_num_max, c->inner_iter_num_max = o->inner_iter_num_max;
+}
+
+extern "C" int wco_odom_set_config(wco_odom *o, const wco_odom_config *c) {
+  if (o->data_added) return 1;
+  o->gyroscope_noise_density = c->gyroscope_noise_density, o->accelerometer_noise_density = c->accelerometer_noise_density;
+  o->gyroscope_random_walk = c->gyroscope_random_walk, o->accelerometer_random_walk = c->accelerometer_random_walk;
+  o->imu_factor_weight = c->imu_factor_weight;
+  o->max_range = c->max_range, o->min_range = c->min_range;
+  for (int i = 0; i < 3; ++i) o->blind_min[i] = c->blind_min[i], o->blind_max[i] = c->blind_max[i], o->ext_t[i] = c->ext_translation[i];
+  for (int i = 0; i < 9; ++i) o->ext_rot[i] = c->ext_rotation[i];
+  o->imu_rate = c->imu_rate, o->sample_dt = c->sample_dt, o->fixed_window_duration = c->fixed_window_duration;
+  o->sliding_window_duration = c->sliding_window_duration, o->sweep_duration = c->sweep_duration;
+  o->gravity_norm = c->gravity_norm;
+  o->outer_iter_num_max = c->outer_iter_num_max, o->inner_iter_num_max = c->inner_iter_num_max;
+  derive(o);
+  return 0;
+}
+
+extern "C" void wco_odom_params(const wco_odom *o, wc_params *out) { std::memcpy(out, &o->P, sizeof(*out)); }
 extern "C" void wco_odom_destroy(wco_odom *o) { delete o; }
 extern "C" int wco_odom_error(const wco_odom *o) { return o->error; }
 
@@ -257,10 +311,12 @@ extern "C" void wco_odom_add_imu(wco_odom *o, double t, const double acc[3], con
   ImuMsg m;
   m.t = t;
   for (int d = 0; d < 3; ++d) m.acc[d] = acc[d], m.gyr[d] = gyr[d];
+  o->data_added = true;
   o->imu_buff.push_back(m);
 }
 
 extern "C" void wco_odom_add_scan(wco_odom *o, const void *points48, uint64_t n) {
+  o->data_added = true;
   if (o->error) return;
   // lidar -> imu frame, range / blind-box filter (cc:489-496)
   std::vector<Pt48> kept(n);

@@ -324,6 +324,25 @@ class Odometry:
     def set_quirks(self, on):
         lib().wco_odom_set_quirks(self._h, C.c_int(1 if on else 0))
 
+    def config(self):
+        c = R.OdomConfig()
+        lib().wco_odom_get_config(self._h, C.byref(c))
+        return c.to_dict()
+
+    def set_config(self, **fields):
+        """the named configuration values of lio_config.h:8-41 (wco_odom_set_config); only before any data"""
+        c = R.OdomConfig()
+        lib().wco_odom_get_config(self._h, C.byref(c))
+        c.update(**fields)
+        rc = lib().wco_odom_set_config(self._h, C.byref(c))
+        assert rc == 0, "the oracle's configuration cannot change once data has been added"
+
+    def params(self):
+        """the wc_params the oracle's stages are called with"""
+        p = R.Params()
+        lib().wco_odom_params(self._h, C.byref(p))
+        return p
+
     def export_state(self):
         """(samples (ns, 23): timestamp, cor[12], grav[3], quat[4], pos[3]; imu states as R.IMU_STATE records)"""
         cnt = (C.c_uint64 * 2)()

@@ -113,6 +113,22 @@ void wco_odom_destroy(wco_odom *o);
 int wco_odom_error(const wco_odom *o); /* non-zero: a CHECK of the reference would have aborted */
 void wco_odom_add_imu(wco_odom *o, double t, const double acc[3], const double gyr[3]);  /* AddImuData cc:607-611 */
 void wco_odom_add_scan(wco_odom *o, const void *points48, uint64_t n);                  /* AddLidarScan cc:487-605 */
+/* the configuration values of lio_config.h:8-41 (the layout of the facade's wc_odom_config, host/lio_config.h - restated, not included).
+ * wco_odom_set_config: before any data; P's IMU cost weights by lio_config.h:42-45, imu_dt = 1 / imu_rate, max_iterations = inner_iter_num_max;
+ * non-zero, nothing changed: data has been added already.  wco_odom_params: the wc_params the oracle's stages are called with. */
+typedef struct wco_odom_config {
+  double gyroscope_noise_density, accelerometer_noise_density, gyroscope_random_walk, accelerometer_random_walk, imu_factor_weight;
+  double max_range, min_range;
+  double blind_min[3], blind_max[3];
+  double ext_translation[3];
+  double ext_rotation[9];
+  double imu_rate, sample_dt, fixed_window_duration, sliding_window_duration, sweep_duration;
+  double gravity_norm;
+  int32_t outer_iter_num_max, inner_iter_num_max;
+} wco_odom_config;
+void wco_odom_get_config(const wco_odom *o, wco_odom_config *out);
+int wco_odom_set_config(wco_odom *o, const wco_odom_config *c);
+void wco_odom_params(const wco_odom *o, wc_params *out);
 void wco_odom_set_quirks(wco_odom *o, int on); /* 0: Q1/Q3 Jacobians accumulated, fixed window trimmed (not a reference mode) */
 void wco_odom_export_state(const wco_odom *o, double *samples23, uint64_t cap_s, wc_imu_state *imu, uint64_t cap_i,
                            uint64_t counts[2]);

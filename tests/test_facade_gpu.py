@@ -266,3 +266,68 @@ def test_facade_free_running_drift_report(gpu, oracle, exact_sums):
     assert len(per_sweep) >= 15
     odo.close()
     ref.close()
+
+
+@pytest.mark.parametrize("name", ["imu_model", "timing_preprocessing_extrinsics"])
+def test_facade_non_default_configuration_against_the_oracle(gpu, oracle, name):
+    """the per-sweep comparison of test_facade_each_sweep_against_the_oracle_resynchronised, its bars unchanged, with a non-default
+    LioConfig set on both sides (tests/config_cases.py): the IMU model - noise densities x 2, imu_factor_weight 0.03, a 100 Hz IMU - and
+    timing, preprocessing and extrinsics - sample_dt 0.1, sweep_duration 0.4, gravity_norm 9.80, ranges 1 to 30 m, a shifted blind box,
+    the lidar mounted elsewhere and turned by 2 degrees.  Three sweeps, the shortest stream that completes them (1.5 s and 1.3 s at
+    300 k points/s).  The configuration reaches the solver: the wc_params the facade's context holds are read back and are the
+    oracle's.  Each configuration is live - tests/test_config_cpu.py::test_each_facade_configuration_is_live: under the default
+    configuration the oracle's sample states are 0.2 to 0.9 away (imu_model; 2.4e-3 to 6.9e-3 with imu_rate alone taken), or it forms
+    7 and 13 sample states and two sweeps where the test configuration forms 5, 9 and 13 and three.  Measured on the MI355X, worst
+    sample-state difference per sweep (bar 1e-6): 6.2e-10, 5.9e-12, 5.1e-13 (imu_model; 100, 45 and 49 LM iterations) and 2.8e-9, 1.4e-8,
+    7.1e-10 (100, 23, 20); surfel and correspondence counts equal in every sweep."""
+    import config_cases as cc
+    from wildcat_slam_amd import lib
+
+    fields = cc.CONFIGS[name]["config"]
+    msgs, imu, _ = cc.stream(name)
+    odo, ref = lib.Odometry(0), oracle.Odometry()
+    before = odo.ctx_params()
+    assert bytes(before) == bytes(lib.default_params())
+    odo.set_config(**fields)
+    ref.set_config(**fields)
+    assert odo.config() == ref.config() and all(np.array_equal(np.asarray(odo.config()[k], np.float64).reshape(-1), np.asarray(v, np.float64).reshape(-1)) for k, v in fields.items())
+    held = odo.ctx_params()
+    assert bytes(held) == bytes(ref.params())
+    if name == "imu_model":
+        assert held.imu_dt == 0.01 and all(getattr(held, k) != getattr(before, k) for k in ("w_gyr", "w_acc", "w_bg", "w_ba"))
+        # a configuration whose derived parameters are refused changes nothing
+        with pytest.raises(lib.WildcatError) as err:
+            odo.set_config(gyroscope_noise_density=0.0)
+        assert err.value.code == lib.WC_ERR_ARG and "w_gyr" in str(err.value)
+        assert bytes(odo.ctx_params()) == bytes(held) and odo.config()["gyroscope_noise_density"] == fields["gyroscope_noise_density"]
+    else:
+        assert bytes(held) == bytes(before)  # (none of these fields is a library parameter: the facade itself uses them)
+    odo.set_keep_pair_stamps(True)
+    per_sweep = []
+
+    def on_sweep(k):
+        a, b = odo.samples(), ref.samples()
+        sa, sb = odo.stats(), ref.stats()
+        assert a.shape == b.shape and np.array_equal(a[:, 0], b[:, 0])  # same sample states, same timestamps
+        for key in ("sld_surfels", "fix_surfels", "lm_iters", "termination"):
+            assert sa[key] == sb[key], (k, key, sa[key], sb[key])
+        for key in ("binary", "unary"):
+            assert abs(sa[key] - sb[key]) <= 2, (k, key, sa[key], sb[key])
+        for which in (0, 1):
+            only_f, only_o = _pair_set_difference(odo.pair_stamps(which), ref.pair_stamps(which), 1e-5)
+            assert only_f + only_o <= 4, (k, which, only_f, only_o)
+        d = _state_diff(a, b)
+        per_sweep.append((k, float("%.2g" % d), int(sa["sld_surfels"]), int(sa["binary"]), int(sa["lm_iters"])))
+        assert d <= 1e-6, per_sweep
+        assert abs(sa["cost1"] - sb["cost1"]) <= 1e-5 * max(1.0, abs(sb["cost1"]))
+        odo.import_state(*ref.export_state())  # re-synchronise: the next sweep starts from the oracle's states
+
+    _feed(odo, ref, msgs, imu, on_sweep)
+    print(name, "per sweep (number, worst sample-state difference, sliding surfels, binary correspondences, LM iterations)", per_sweep)
+    assert len(per_sweep) == cc.SWEEPS
+    # once data has been added the configuration is fixed
+    with pytest.raises(lib.WildcatError):
+        odo.set_config(imu_factor_weight=0.01)
+    assert odo.config() == ref.config()
+    odo.close()
+    ref.close()

@@ -45,11 +45,50 @@ extern "C" void wc_params_default(wc_params *p) {
   p->exact_sums = 0;
 }
 
+// the first field of p that nothing can run with, and the rule it breaks (include/wildcat_hip.h: wc_params_check); nullptr: none.
+// A value that would put a NaN or an infinity into a kernel's arithmetic - 1 / imu_dt, 1 / cauchy_a^2, 1 / surfel_sigma0, the
+// matcher's features scaled by 1 / center_scale and 1 / angular_scale, the voxel index of a point - is stopped here, on the host.
+static const char *first_bad_param(const wc_params *p, const char **rule) {
+  auto fin = [](double v) { return std::isfinite(v); };
+  const char *finite_pos = "must be finite and > 0", *finite_nonneg = "must be finite and >= 0", *finite = "must be finite";
+  const char *finite_nonzero = "must be finite and not 0", *no_nan = "must not be NaN";
+#define WC_RULE(field, ok, text) \
+  if (!(ok)) return *rule = (text), field
+  WC_RULE("voxel_size", fin(p->voxel_size) && p->voxel_size > 0, finite_pos);
+  WC_RULE("max_layer", p->max_layer >= 0 && p->max_layer <= 2, "must be 0..2");
+  WC_RULE("min_points", p->min_points >= 0, "must be >= 0");
+  WC_RULE("planer_threshold", fin(p->planer_threshold) && p->planer_threshold >= 0, finite_nonneg);
+  WC_RULE("min_plane_likeness", fin(p->min_plane_likeness), finite);
+  WC_RULE("view_point", fin(p->view_point[0]) && fin(p->view_point[1]) && fin(p->view_point[2]), finite);
+  WC_RULE("cluster_gap", fin(p->cluster_gap) && p->cluster_gap >= 0, finite_nonneg);
+  WC_RULE("cluster_min_points", p->cluster_min_points >= 1, "must be >= 1");
+  WC_RULE("center_scale", fin(p->center_scale) && p->center_scale != 0, finite_nonzero);
+  WC_RULE("angular_scale", fin(p->angular_scale) && p->angular_scale != 0, finite_nonzero);
+  WC_RULE("surfel_dist_max", !std::isnan(p->surfel_dist_max), no_nan);
+  WC_RULE("knn_k", p->knn_k >= 1 && p->knn_k <= 16, "must be 1..16");
+  WC_RULE("time_diff_min", !std::isnan(p->time_diff_min), no_nan);
+  WC_RULE("surfel_sigma0", fin(p->surfel_sigma0) && p->surfel_sigma0 > 0, finite_pos);
+  WC_RULE("cauchy_a", fin(p->cauchy_a) && p->cauchy_a > 0, finite_pos);
+  WC_RULE("w_gyr", fin(p->w_gyr) && p->w_gyr >= 0, finite_nonneg);
+  WC_RULE("w_acc", fin(p->w_acc) && p->w_acc >= 0, finite_nonneg);
+  WC_RULE("w_bg", fin(p->w_bg) && p->w_bg >= 0, finite_nonneg);
+  WC_RULE("w_ba", fin(p->w_ba) && p->w_ba >= 0, finite_nonneg);
+  WC_RULE("imu_dt", fin(p->imu_dt) && p->imu_dt > 0, finite_pos);
+  WC_RULE("max_iterations", p->max_iterations >= 0, "must be >= 0");
+#undef WC_RULE
+  return nullptr;
+}
+
+extern "C" int wc_params_check(const wc_params *p, const char **field) {
+  const char *rule = nullptr;
+  const char *bad = p ? first_bad_param(p, &rule) : "params";
+  if (field) *field = bad;
+  return bad ? WC_ERR_ARG : WC_OK;
+}
+
 static int check_params(wc_ctx *ctx, const wc_params *p) {
-  if (p->max_layer < 0 || p->max_layer > 2) return wc_fail(ctx, WC_ERR_ARG, "max_layer must be 0..2");
-  if (!(p->voxel_size > 0)) return wc_fail(ctx, WC_ERR_ARG, "voxel_size must be positive");
-  if (p->cluster_min_points < 1 || p->min_points < 0) return wc_fail(ctx, WC_ERR_ARG, "bad point thresholds");
-  if (p->knn_k < 1 || p->knn_k > 16) return wc_fail(ctx, WC_ERR_ARG, "knn_k must be 1..16");
+  const char *rule = nullptr;
+  if (const char *bad = first_bad_param(p, &rule)) return wc_fail(ctx, WC_ERR_ARG, "%s %s", bad, rule);
   return WC_OK;
 }
 
@@ -134,6 +173,7 @@ void wc_pool_release(int device, hipMemPool_t pool) {
 extern "C" int wc_ctx_create(const wc_params *params, int device, wc_ctx **out) {
   if (!out) return WC_ERR_ARG;
   *out = nullptr;
+  if (params && wc_params_check(params, nullptr) != WC_OK) return WC_ERR_ARG;  // (before the device is looked at: refused with or without one)
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) return WC_ERR_NOGPU;
   wc_ctx *ctx = new wc_ctx;
@@ -259,6 +299,12 @@ extern "C" int wc_ctx_set_params(wc_ctx *ctx, const wc_params *params) {
   WC_TRY(check_params(ctx, params));
   ctx->P = *params;
   ex_reset_backoff(ctx->ex_mem);  // new parameters: the adaptive path choice of the extraction starts afresh
+  return WC_OK;
+}
+
+extern "C" int wc_ctx_get_params(const wc_ctx *ctx, wc_params *out) {
+  if (!ctx || !out) return WC_ERR_ARG;
+  *out = ctx->P;
   return WC_OK;
 }
 

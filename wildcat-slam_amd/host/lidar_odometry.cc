@@ -119,14 +119,22 @@ void FillMisses(Rec *hits, size_t n) {
 
 LidarOdometry::LidarOdometry() : LidarOdometry(0) {}
 
-// the library parameters that follow LioConfig: solver iterations, the quirk Jacobians (Q1 / Q3) and the extraction arithmetic
-static void ParamsFromConfig(const LioConfig &c, wc_params *P) {
+// the library parameters that follow LioConfig: the four IMU cost weights (lio_config.h:42-45, the expressions and operation order of
+// wc_params_default, so that the default LioConfig gives wc_params_default's bytes), imu_dt, solver iterations, the quirk Jacobians
+// (Q1 / Q3) and the extraction arithmetic
+void WcParamsFromConfig(const LioConfig &c, wc_params *P) {
   wc_params_default(P);
+  const double rate = c.imu_rate, k = c.imu_factor_weight;
+  P->w_gyr = 1 / (c.gyroscope_noise_density * std::sqrt(rate)) * k;
+  P->w_acc = 1 / (c.accelerometer_noise_density * std::sqrt(rate)) * k;
+  P->w_bg = 1 / (c.gyroscope_random_walk / std::sqrt(rate)) * k;
+  P->w_ba = 1 / (c.accelerometer_random_walk / std::sqrt(rate)) * k;
+  P->imu_dt = 1 / rate;
   P->max_iterations = c.inner_iter_num_max;
   P->reference_quirks = c.reference_quirks ? 1 : 0;
   P->exact_sums = c.exact_sums ? 1 : 0;
-  P->imu_dt = 1 / c.imu_rate;
 }
+static void ParamsFromConfig(const LioConfig &c, wc_params *P) { WcParamsFromConfig(c, P); }
 
 LidarOdometry::LidarOdometry(int device) {
   wc_params P;
@@ -150,6 +158,50 @@ void LidarOdometry::ApplyConfig() {
   ParamsFromConfig(config_, &P);
   WC_CALL(wc_ctx_set_params(ctx_, &P));
   stq(ext_quat_, quat_from_matrix(config_.ext_rotation));
+}
+
+// a whole configuration at once, checked before anything of it is taken: false - config() and the context's parameters as they were,
+// config_error() says why - once IMU or lidar data has been added (a change in mid-stream is not supported), when a window or timing value
+// cannot be run with, or when wc_params_check refuses the parameters derived from c (a zero noise density gives an infinite weight,
+// imu_rate = 0 an infinite imu_dt)
+bool LidarOdometry::SetConfig(const LioConfig &c) {
+  config_error_.clear();
+  if (data_added_) {
+    config_error_ = "the configuration cannot change once IMU or lidar data has been added";
+    return false;
+  }
+  const struct {
+    const char *name;
+    double v;
+  } positive[] = {{"imu_rate", c.imu_rate},
+                  {"sample_dt", c.sample_dt},
+                  {"sweep_duration", c.sweep_duration},
+                  {"sliding_window_duration", c.sliding_window_duration},
+                  {"fixed_window_duration", c.fixed_window_duration},
+                  {"gravity_norm", c.gravity_norm},
+                  {"max_range", c.max_range}};
+  for (const auto &f : positive)
+    if (!(std::isfinite(f.v) && f.v > 0)) {
+      config_error_ = std::string(f.name) + " must be finite and > 0";
+      return false;
+    }
+  bool finite = std::isfinite(c.min_range);
+  for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(c.blind_min[i]) && std::isfinite(c.blind_max[i]) && std::isfinite(c.ext_translation[i]);
+  for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(c.ext_rotation[i]);
+  if (!finite || c.outer_iter_num_max < 0) {
+    config_error_ = !finite ? "min_range, the blind box and the extrinsics must be finite" : "outer_iter_num_max must be >= 0";
+    return false;
+  }
+  wc_params P;
+  ParamsFromConfig(c, &P);
+  const char *field = nullptr;
+  if (wc_params_check(&P, &field) != WC_OK) {
+    config_error_ = std::string("the derived parameter ") + (field ? field : "?") + " is refused (wc_params_check)";
+    return false;
+  }
+  config_ = c;
+  ApplyConfig();
+  return true;
 }
 
 // test hook (not in the reference): overwrite the window's sample states and IMU states with another run's (23 doubles per
@@ -182,7 +234,10 @@ LidarOdometry::~LidarOdometry() {
   wc_ctx_destroy(ctx_);
 }
 
-void LidarOdometry::AddImuData(const ImuData &msg) { imu_buff_.push_back(msg); }  // :607-611
+void LidarOdometry::AddImuData(const ImuData &msg) {  // :607-611
+  data_added_ = true;
+  imu_buff_.push_back(msg);
+}
 
 bool LidarOdometry::latest_state(SampleStateView *out) const {
   return !samples_.empty() && sample_state(samples_.size() - 1, out);
@@ -1040,6 +1095,7 @@ void LidarOdometry::ShrinkToFit() {
 void LidarOdometry::AddLidarScan(const pcl::PointCloud<hilti_ros::Point>::Ptr &msg) {
   // lidar frame -> imu frame, range / blind-box filter (:489-496): on the device, the points stay there
   const auto t_entry = std::chrono::steady_clock::now();
+  data_added_ = true;
   AppendScanOnDevice(*msg);
   if (!SyncHeadingMsgs()) return;
 

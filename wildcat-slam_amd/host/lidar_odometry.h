@@ -23,6 +23,10 @@
 #include "lio_config.h"
 #include "wire_formats.h"
 
+// the wc_params a configuration stands for (needs no context): wc_params_default with the IMU cost weights of lio_config.h:42-45 formed
+// from c's noise model, imu_rate and imu_factor_weight, imu_dt = 1 / imu_rate, max_iterations = inner_iter_num_max and the two switches
+void WcParamsFromConfig(const LioConfig &c, wc_params *P);
+
 class LidarOdometry {
  public:
   LidarOdometry();
@@ -195,7 +199,11 @@ class LidarOdometry {
   // which waits too).  Not part of last_stage_ms()
   double last_map_ms() const { return last_map_ms_; }
   LioConfig &config() { return config_; }
-  void ApplyConfig();  // push config() changes (quirks, extraction arithmetic, iteration cap, extrinsics) into the device context
+  void ApplyConfig();  // push config() changes (IMU model, quirks, extraction arithmetic, iteration cap, extrinsics) into the device context
+  // replace the whole configuration, checked first: false - nothing changed, config_error() says why - after the first AddImuData /
+  // AddLidarScan, for a window or timing value that is not finite and positive, or when the derived wc_params fail wc_params_check
+  bool SetConfig(const LioConfig &c);
+  const std::string &config_error() const { return config_error_; }
   bool ImportState(const double *samples23, size_t ns, const wc_imu_state *imu, size_t n_imu);  // test hook, see .cc
 
  private:
@@ -221,6 +229,8 @@ class LidarOdometry {
   void Fatal(const char *what, int rc) const;
 
   LioConfig config_;
+  std::string config_error_;
+  bool data_added_ = false;  // an IMU or lidar message has arrived: SetConfig is refused from then on
   wc_ctx *ctx_ = nullptr;
  public:
   // the library context behind this object (tests and profiling scripts set development options on it: wc_ctx_set_dev_option)

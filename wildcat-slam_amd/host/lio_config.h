@@ -61,3 +61,45 @@ struct LioConfig {
   uint32_t map_carve_shell = 1;
   uint32_t map_carve_min_rays = 2;
 };
+
+// LioConfig's reference fields (lio_config.h:8-41) as a plain C struct: what wc_odom_get_config / wc_odom_set_config of the flat C
+// wrapper (odom_c_api.cc) exchange.  The switches that are not in the reference keep their own setters.
+extern "C" {
+typedef struct wc_odom_config {
+  double gyroscope_noise_density, accelerometer_noise_density, gyroscope_random_walk, accelerometer_random_walk, imu_factor_weight;
+  double max_range, min_range;
+  double blind_min[3], blind_max[3];
+  double ext_translation[3];
+  double ext_rotation[9];  // row-major, lidar -> imu
+  double imu_rate, sample_dt, fixed_window_duration, sliding_window_duration, sweep_duration;
+  double gravity_norm;
+  int32_t outer_iter_num_max, inner_iter_num_max;
+} wc_odom_config;
+}
+
+inline void ConfigToC(const LioConfig &c, wc_odom_config *o) {
+  o->gyroscope_noise_density = c.gyroscope_noise_density, o->accelerometer_noise_density = c.accelerometer_noise_density;
+  o->gyroscope_random_walk = c.gyroscope_random_walk, o->accelerometer_random_walk = c.accelerometer_random_walk;
+  o->imu_factor_weight = c.imu_factor_weight;
+  o->max_range = c.max_range, o->min_range = c.min_range;
+  for (int i = 0; i < 3; ++i) o->blind_min[i] = c.blind_min[i], o->blind_max[i] = c.blind_max[i], o->ext_translation[i] = c.ext_translation[i];
+  for (int i = 0; i < 9; ++i) o->ext_rotation[i] = c.ext_rotation[i];
+  o->imu_rate = c.imu_rate, o->sample_dt = c.sample_dt, o->fixed_window_duration = c.fixed_window_duration;
+  o->sliding_window_duration = c.sliding_window_duration, o->sweep_duration = c.sweep_duration;
+  o->gravity_norm = c.gravity_norm;
+  o->outer_iter_num_max = c.outer_iter_num_max, o->inner_iter_num_max = c.inner_iter_num_max;
+}
+
+// the reference fields of *c from o; every other field of *c stays
+inline void ConfigFromC(const wc_odom_config &o, LioConfig *c) {
+  c->gyroscope_noise_density = o.gyroscope_noise_density, c->accelerometer_noise_density = o.accelerometer_noise_density;
+  c->gyroscope_random_walk = o.gyroscope_random_walk, c->accelerometer_random_walk = o.accelerometer_random_walk;
+  c->imu_factor_weight = o.imu_factor_weight;
+  c->max_range = o.max_range, c->min_range = o.min_range;
+  for (int i = 0; i < 3; ++i) c->blind_min[i] = o.blind_min[i], c->blind_max[i] = o.blind_max[i], c->ext_translation[i] = o.ext_translation[i];
+  for (int i = 0; i < 9; ++i) c->ext_rotation[i] = o.ext_rotation[i];
+  c->imu_rate = o.imu_rate, c->sample_dt = o.sample_dt, c->fixed_window_duration = o.fixed_window_duration;
+  c->sliding_window_duration = o.sliding_window_duration, c->sweep_duration = o.sweep_duration;
+  c->gravity_norm = o.gravity_norm;
+  c->outer_iter_num_max = o.outer_iter_num_max, c->inner_iter_num_max = o.inner_iter_num_max;
+}

@@ -102,6 +102,30 @@ void wc_odom_set_exact_sums(void *h, int on) {
   ((LidarOdometry *)h)->config().exact_sums = on != 0;
   ((LidarOdometry *)h)->ApplyConfig();
 }
+// ---- the configuration (host/lio_config.h: wc_odom_config = LioConfig's reference fields) --------------------------------------------
+void wc_odom_get_config(void *h, wc_odom_config *out) { ConfigToC(((LidarOdometry *)h)->config(), out); }
+// 0: taken - the context's wc_params re-derived (IMU cost weights, imu_dt, iteration cap) and the extrinsic quaternion with them.
+// WC_ERR_ARG: refused and nothing changed - IMU or lidar data has been added already, a window or timing value is not finite and positive,
+// or wc_params_check refuses the derived parameters; wc_odom_config_error says which
+int wc_odom_set_config(void *h, const wc_odom_config *c) {
+  LidarOdometry *o = (LidarOdometry *)h;
+  if (!c) return WC_ERR_ARG;
+  LioConfig next = o->config();
+  ConfigFromC(*c, &next);
+  return o->SetConfig(next) ? WC_OK : WC_ERR_ARG;
+}
+const char *wc_odom_config_error(void *h) { return ((LidarOdometry *)h)->config_error().c_str(); }
+// the wc_params the facade's context holds
+int wc_odom_ctx_params(void *h, wc_params *out) { return wc_ctx_get_params(((LidarOdometry *)h)->gpu_context(), out); }
+// the wc_params a configuration stands for, without a context (c NULL: the default LioConfig); the return value is wc_params_check's
+int wc_host_params_from_config(const wc_odom_config *c, wc_params *out) {
+  LioConfig cfg;
+  if (c) ConfigFromC(*c, &cfg);
+  WcParamsFromConfig(cfg, out);
+  return wc_params_check(out, nullptr);
+}
+void wc_host_default_config(wc_odom_config *out) { ConfigToC(LioConfig(), out); }
+
 // the reference's residual log (PrintSurfelResiduals / PrintImuResiduals, lidar_odometry.cc:56-94): switch + the last sweep's text
 void wc_odom_set_residual_log(void *h, int on) { ((LidarOdometry *)h)->config().log_residual_histograms = on != 0; }
 uint64_t wc_odom_residual_log(void *h, char *out, uint64_t cap) {

@@ -19,6 +19,7 @@ _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include")
 _LIB = None
 
 WC_OK, WC_ERR_CAPACITY = 0, 1
+WC_ERR_ARG = 11
 
 
 class WildcatError(RuntimeError):
@@ -54,6 +55,33 @@ def default_params():
     p = R.Params()
     load().wc_params_default(C.byref(p))
     return p
+
+
+def params_check(params):
+    """wc_params_check (host only, no context) -> (return code, name of the first refused field or None)"""
+    field = C.c_char_p()
+    rc = load().wc_params_check(C.byref(params), C.byref(field))
+    return rc, field.value.decode() if field.value else None
+
+
+def _odom_lib():
+    load()
+    return C.CDLL(os.path.join(os.path.dirname(_CSRC), "host", "libwildcat_odometry.so"))
+
+
+def default_config():
+    """the default LioConfig's reference fields (records.OdomConfig); needs no GPU"""
+    c = R.OdomConfig()
+    _odom_lib().wc_host_default_config(C.byref(c))
+    return c
+
+
+def host_params_from_config(config=None):
+    """the wc_params the facade derives from a configuration (records.OdomConfig, None = the default), without a context ->
+    (Params, wc_params_check's return code)"""
+    p = R.Params()
+    rc = _odom_lib().wc_host_params_from_config(C.byref(config) if config is not None else None, C.byref(p))
+    return p, rc
 
 
 def rccl_unique_id():
@@ -138,8 +166,15 @@ class Context:
             raise WildcatError(rc, self.lib.wc_last_error(self.h).decode())
 
     def set_params(self, params):
-        self.params = params
+        """wc_ctx_set_params; parameters that fail wc_params_check raise WildcatError(11) and the context keeps what it had"""
         self._ck(self.lib.wc_ctx_set_params(self.h, C.byref(params)))
+        self.params = params
+
+    def get_params(self):
+        """a copy of the parameters the context holds (wc_ctx_get_params)"""
+        p = R.Params()
+        self._ck(self.lib.wc_ctx_get_params(self.h, C.byref(p)))
+        return p
 
     def selftest_factor32(self, a, variant, reps=5):
         """-> (L, L^-1, shader clocks, ok) of the 32 x 32 SPD matrix a by the solve's diagonal-block kernel (wc_selftest_factor32)"""
@@ -1745,6 +1780,31 @@ class Odometry:
 
     def set_quirks(self, on):
         self.lib.wc_odom_set_quirks(self.h, C.c_int(1 if on else 0))
+
+    def config(self):
+        """LioConfig's reference fields as a dict (wc_odom_get_config)"""
+        c = R.OdomConfig()
+        self.lib.wc_odom_get_config(self.h, C.byref(c))
+        return c.to_dict()
+
+    def set_config(self, **fields):
+        """change the named fields of the configuration (wc_odom_set_config): the IMU noise model, ranges, blind box, extrinsics, imu_rate,
+        sample_dt, the durations, gravity_norm, the iteration limits.  Only before the first add_imu / add_scan.  Refused - WildcatError(11),
+        nothing changed - when the parameters derived from it fail wc_params_check or a timing value is not finite and positive"""
+        c = R.OdomConfig()
+        self.lib.wc_odom_get_config(self.h, C.byref(c))
+        c.update(**fields)
+        rc = self.lib.wc_odom_set_config(self.h, C.byref(c))
+        if rc != WC_OK:
+            self.lib.wc_odom_config_error.restype = C.c_char_p
+            raise WildcatError(rc, self.lib.wc_odom_config_error(self.h).decode())
+
+    def ctx_params(self):
+        """a copy of the wc_params the facade's context holds"""
+        p = R.Params()
+        rc = self.lib.wc_odom_ctx_params(self.h, C.byref(p))
+        assert rc == WC_OK, rc
+        return p
 
     def set_exact_sums(self, on):
         self.lib.wc_odom_set_exact_sums(self.h, C.c_int(1 if on else 0))

@@ -112,6 +112,49 @@ class Params(C.Structure):
     ]
 
 
+class OdomConfig(C.Structure):
+    """wc_odom_config (host/lio_config.h): LioConfig's reference fields; the oracle's wco_odom_config has the same layout."""
+
+    _fields_ = [
+        ("gyroscope_noise_density", C.c_double),
+        ("accelerometer_noise_density", C.c_double),
+        ("gyroscope_random_walk", C.c_double),
+        ("accelerometer_random_walk", C.c_double),
+        ("imu_factor_weight", C.c_double),
+        ("max_range", C.c_double),
+        ("min_range", C.c_double),
+        ("blind_min", C.c_double * 3),
+        ("blind_max", C.c_double * 3),
+        ("ext_translation", C.c_double * 3),
+        ("ext_rotation", C.c_double * 9),
+        ("imu_rate", C.c_double),
+        ("sample_dt", C.c_double),
+        ("fixed_window_duration", C.c_double),
+        ("sliding_window_duration", C.c_double),
+        ("sweep_duration", C.c_double),
+        ("gravity_norm", C.c_double),
+        ("outer_iter_num_max", C.c_int32),
+        ("inner_iter_num_max", C.c_int32),
+    ]
+
+    def to_dict(self):
+        return dict((k, list(getattr(self, k)) if hasattr(getattr(self, k), "__len__") else getattr(self, k)) for k, _ in self._fields_)
+
+    def update(self, **fields):
+        """set the named fields (arrays from any sequence of the right length); an unknown name is a TypeError"""
+        known = dict(self._fields_)
+        for k, v in fields.items():
+            if k not in known:
+                raise TypeError("no configuration field %r" % k)
+            if hasattr(getattr(self, k), "__len__"):
+                v = [float(a) for a in np.asarray(v, np.float64).reshape(-1)]
+                assert len(v) == len(getattr(self, k)), k
+                setattr(self, k, known[k](*v))
+            else:
+                setattr(self, k, v)
+        return self
+
+
 COMM_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
 COMM_ALLTOALLV = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64))
 COMM_ALLGATHERV = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64))
