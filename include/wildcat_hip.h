@@ -167,8 +167,13 @@ int wc_selftest_factor32(wc_ctx *ctx, int variant, int reps, const double *h_A, 
  * finite point) and finite points with a stamp outside the hint remain WC_ERR_ARG. */
 int wc_extract_surfels(wc_ctx *ctx, const wc_points *pts, double t_lo, double t_hi, wc_surfel *d_out,
                        wc_surfel_id *d_ids, uint64_t cap, uint64_t *h_n_out);
-/* asynchronous split of the same call for pipelined / benchmarked use: enqueue does no host synchronisation,
- * finish waits for the stream and returns the count and status. */
+/* asynchronous split of the same call for pipelined / benchmarked use: enqueue does no host synchronisation; finish returns once
+ * the sweep's count and status are final.  d_out / d_ids are then complete IN THE ORDER OF THE CONTEXT'S STREAM - the sweep's last
+ * kernel may still be copying surfels when finish returns.  Every library call on the context sees them complete (wc_d2h*, wc_d2d,
+ * the next enqueue, wc_match*, the window calls and their side streams, which wait on events of the ctx stream; wc_dev_free waits for
+ * the stream).  Whoever reads or frees the buffers any other way - a kernel or copy on another stream, another device or process, a
+ * framework's allocator - calls wc_sync(ctx) first.  wc_extract_surfels, the one-call form above, is complete on return for any
+ * reader, and so are the batch calls; the development option ex_sync = 1 makes finish wait for the stream as well. */
 int wc_extract_surfels_enqueue(wc_ctx *ctx, const wc_points *pts, double t_lo, double t_hi, wc_surfel *d_out,
                                wc_surfel_id *d_ids, uint64_t cap);
 int wc_extract_surfels_finish(wc_ctx *ctx, uint64_t *h_n_out);

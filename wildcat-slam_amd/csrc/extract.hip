@@ -29,7 +29,7 @@
 // Host side: what a sweep runs is an ExPath (extract_plan.h) - default or exact pipeline, 32- or 64-bit keys, run-binned or
 // radix point sort (k_keygen + rocPRIM + k_heads + k_roots_banks: sweeps without run structure or with overfull bins), time
 // bins or a radix sort of the slot keys.  wc_extract_surfels_enqueue takes ex_first_path(), finish() waits for the sweep's
-// completion ticket and repeats the sweep on ex_next_path() while the flags it raised ask for it; every decision, size and
+// early count (or the stream) and repeats the sweep on ex_next_path() while the flags it raised ask for it; every decision, size and
 // the state kept between sweeps is in that header, this file only launches (enqueue_path) and waits (ex_wait).
 // The path is HBM/latency bound (20 B read per point, 144 B written per surfel); no MFMA.
 #include <hip/hip_runtime.h>
@@ -138,7 +138,7 @@ struct KeyTraits<uint64_t> {
 // Flags and the final counts reach the host without a copy kernel: status words [8, 9] hold the device-visible address of
 // the context's pinned host mailbox (written by k_init); a flag is raised in HBM (for the kernels that test it) AND as a
 // plain store of 1 into mailbox word 8 + log2(flag) (idempotent, no PCIe atomic); k_slot_emit leaves the surfel count and
-// the layer-2 queue length in mailbox words 0 and 4.  The 32-byte hipMemcpyAsync this replaces was a 4 us blit kernel.
+// the layer-2 queue length in mailbox words 0 and 4 - or, under a ticket, in the two words of the early count (SlotEmitArgs).  The 32-byte hipMemcpyAsync this replaces was a 4 us blit kernel.
 __device__ __forceinline__ uint32_t *host_mailbox(const uint32_t *status) {
   return (uint32_t *)(((unsigned long long)status[9] << 32) | (unsigned long long)status[8]);
 }
@@ -1288,6 +1288,11 @@ struct SlotEmitArgs {
   uint64_t cap;
   uint32_t *next_ctrl;
   uint32_t next_words;
+  // the early count (extract_plan.h).  ticket != 0: the last workgroup's thread 0 stores the two words at mail[0], mail[1] (pinned host
+  // memory) once it knows them - before any copy work - and NO other store of the kernel goes to host memory: when the host has seen both
+  // words it may clear the mailbox for the next sweep while this kernel still runs.  0: no ticket, the plain mailbox words as ever.
+  uint32_t ticket;
+  unsigned long long *mail;
 };
 // (bid / nblk: the workgroup's index and the grid of ITS sweep - the kernel proper, or one sweep's share of a batched launch)
 __device__ __forceinline__ void slot_emit_body(const SlotEmitArgs &E, const uint32_t bid, const uint32_t nblk) {
@@ -1308,7 +1313,7 @@ __device__ __forceinline__ void slot_emit_body(const SlotEmitArgs &E, const uint
     if (i < next_words) next_ctrl[i] = (i == 8u || i == 9u) ? status[i] : 0u;  // (words 8, 9: the mailbox address)
   }
   __shared__ uint32_t s_sorted[4][kSlotBinMax];
-  __shared__ uint32_t s_red[4];
+  __shared__ uint32_t s_red[4], s_over[4];
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
   const uint32_t b0 = bid * 4u;
   // everything this workgroup reads before it knows its counts goes out in ONE round of loads: the counts in front of it
@@ -1326,15 +1331,42 @@ __device__ __forceinline__ void slot_emit_body(const SlotEmitArgs &E, const uint
   const uint4 own = c4[bid];
   const uint64_t *bin = bins + (size_t)(b0 + w) * bin_cap;
   const uint64_t first = (uint32_t)lane < bin_cap ? bin[lane] : 0ull;
+  // the publishing workgroup (the last one: it loads every count): the layer-2 queue's words travel in the same round of loads, and
+  // "some count > bin_cap" - kFlagSlotBinOverflow, the only flag this kernel raises - rides on the reduction's barrier
+  const uint32_t ticket = E.ticket;
+  const bool publish = ticket != 0u && bid == nblk - 1;
+  uint32_t queued = 0;
+  if (publish && t == 0) {
+    queued = status[4];  // roots queued for the layer-2 pass (every emitting kernel has finished)
+    const uint32_t *fxc = counts + kBuckets;  // fast path: layer-2 node sub-counters (extract_fast.inc)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) queued += fxc[(16 + j) * 32];
+  }
   uint32_t part = 0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) part += v[k].x + v[k].y + v[k].z + v[k].w;
   for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off);
   if (lane == 0) s_red[w] = part;
+  if (publish) {
+    uint32_t mx = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) mx = max(max(mx, max(v[k].x, v[k].y)), max(v[k].z, v[k].w));
+    const bool any = __ballot(mx > bin_cap) != 0ull;
+    if (lane == 0) s_over[w] = any ? 1u : 0u;
+  }
   __syncthreads();
   uint32_t base = s_red[0] + s_red[1] + s_red[2] + s_red[3];
   const uint32_t c0 = own.x, c1 = own.y, c2 = own.z, c3 = own.w;
-  if (bid == nblk - 1 && t == 0) {
+  if (publish) {
+    if (t == 0) {
+      const uint32_t total = base + c0 + c1 + c2 + c3;
+      const bool over = (s_over[0] | s_over[1] | s_over[2] | s_over[3]) != 0u || max(max(c0, c1), max(c2, c3)) > bin_cap;
+      // one aligned 64-bit store each, relaxed, system scope: no release, no fence - nothing but these two values is promised
+      __hip_atomic_store(E.mail + 0, (unsigned long long)ex_mail_pack_count(ticket, total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(E.mail + 1, (unsigned long long)ex_mail_pack_queue(ticket, over, queued), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      status[0] = total;  // surfels emitted (the device's copy: what finish() reads if the words never arrive)
+    }
+  } else if (bid == nblk - 1 && t == 0) {
     status[0] = base + c0 + c1 + c2 + c3;  // surfels emitted
     uint32_t *hm = host_mailbox(status);
     if (hm) {
@@ -1350,7 +1382,12 @@ __device__ __forceinline__ void slot_emit_body(const SlotEmitArgs &E, const uint
   const uint32_t c = w == 0 ? c0 : (w == 1 ? c1 : (w == 2 ? c2 : c3));
   if (c == 0) return;
   if (c > bin_cap) {
-    if (lane == 0) raise_flag(status, kFlagSlotBinOverflow);
+    if (lane == 0) {
+      if (ticket)
+        atomicOr(&status[1], kFlagSlotBinOverflow);  // (the host has the flag from word B; the mailbox may be the next sweep's by now)
+      else
+        raise_flag(status, kFlagSlotBinOverflow);
+    }
     return;
   }
   // equal keys: the time stamps themselves (a key of the fast path is a 32-bit fraction of the sweep), then - equal
@@ -1428,8 +1465,8 @@ __device__ __forceinline__ void slot_emit_body(const SlotEmitArgs &E, const uint
 __global__ void __launch_bounds__(256) k_slot_emit(const uint32_t *__restrict__ counts, const uint64_t *__restrict__ bins, uint32_t bin_cap,
                                                   const wc_surfel *__restrict__ slots, const wc_surfel_id *__restrict__ slot_ids,
                                                   uint32_t *status, wc_surfel *out, wc_surfel_id *out_ids, uint64_t cap, uint32_t *next_ctrl,
-                                                  uint32_t next_words) {
-  const SlotEmitArgs E{counts, bins, bin_cap, slots, slot_ids, status, out, out_ids, cap, next_ctrl, next_words};
+                                                  uint32_t next_words, uint32_t ticket, unsigned long long *mail) {
+  const SlotEmitArgs E{counts, bins, bin_cap, slots, slot_ids, status, out, out_ids, cap, next_ctrl, next_words, ticket, mail};
   slot_emit_body(E, blockIdx.x, gridDim.x);
 }
 // K sweeps' time ordering in one launch: kBuckets / 4 workgroups per sweep
@@ -1954,11 +1991,6 @@ int run_pipeline_fast(wc_ctx *ctx) {
   return fx_tail(ctx, P.max_layer >= 2 && M.last_splits > 0);
 }
 
-constexpr int kMailTicket = 120;  // word of the pinned mailbox (ctx->h_status) that carries the extraction's completion ticket
-__global__ void k_ex_ticket(uint32_t *host_word, uint32_t ticket) {
-  __hip_atomic_store(host_word, ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // layer-2 pair (optional), time order + gather
 int fx_tail(wc_ctx *ctx, bool layer2) {
   hipStream_t st = ctx->stream;
@@ -1980,19 +2012,18 @@ int fx_tail(wc_ctx *ctx, bool layer2) {
   ex_mark(ctx, 4);
   uint32_t *next_ctrl = (uint32_t *)ctx->b_fx[5].p + (size_t)(M.fx_parity ^ 1) * kCtrlWords;
   static_assert(kCtrlWords <= (kBuckets / 4) * 256, "k_slot_emit's grid covers the control block");
+  // the early count (extract_plan.h): what finish() hands its caller - surfel count, layer-2 queue length, flags - is final when
+  // k_slot_emit STARTS, so the kernel's last workgroup stores it to the pinned mailbox under this sweep's ticket before it copies a
+  // surfel, and finish() reads host memory instead of waiting for the stream.  Nothing about the kernel's completion is published (no
+  // count of workgroups, no fence): the surfels are complete in the order of the ctx stream, which is where every reader of the
+  // library is.  No ticket with the stage events, with ex_sync and for a sweep of a batch: those finish on the idle stream.
+  ctx->ex.ticket = 0;
+  if (ctx->h_status_dev && !ctx->ex_prof && !ctx->dev.ex_sync && !ctx->ex.deferred) ctx->ex.ticket = M.ticket_seq = ex_mail_next_ticket(M.ticket_seq);
   k_slot_emit<<<kBuckets / 4, 256, 0, st>>>(A.slot_counts, A.slot_bins, A.slot_bin_cap, (const wc_surfel *)ctx->b_slots.p,
                                            (const wc_surfel_id *)ctx->b_slot_ids.p, A.status, ctx->ex.d_out, ctx->ex.d_ids, ctx->ex.cap, next_ctrl,
-                                           kCtrlWords);
+                                           kCtrlWords, ctx->ex.ticket,
+                                           ctx->ex.ticket ? (unsigned long long *)ctx->h_status_dev + kExMailCount : nullptr);
   ex_mark(ctx, 5);
-  // the completion ticket: ONE thread behind the sweep's last kernel stores it to the pinned mailbox and wc_extract_surfels_finish reads
-  // host memory instead of waiting for the stream (the LM loop's wait_mail).  Behind a kernel boundary nothing has to be fenced inside
-  // k_slot_emit (what round 3's last-workgroup ticket paid for): every store of the sweep has left its L2 when this kernel starts.
-  ctx->ex.ticket = 0;
-  if (ctx->h_status_dev && !ctx->ex_prof && !ctx->dev.ex_sync) {
-    if (++M.ticket_seq == 0u) ++M.ticket_seq;
-    ctx->ex.ticket = M.ticket_seq;
-    k_ex_ticket<<<1, 1, 0, st>>>(ctx->h_status_dev + kMailTicket, ctx->ex.ticket);
-  }
   static const bool fx_dbg = wc_log_env("WC_FX_DEBUG");
   if (fx_dbg) fprintf(stderr, "[fx] k_slot_emit (layer2=%d) ... %s\n", (int)layer2, hipGetErrorString(hipStreamSynchronize(st)));
   WC_HIP(ctx, hipGetLastError());
@@ -2023,7 +2054,7 @@ int pipeline_tail(wc_ctx *ctx, bool layer2) {
   ex_mark(ctx, 4);
   if (fast_slots) {
     k_slot_emit<<<kBuckets / 4, 256, 0, st>>>(A.slot_counts, A.slot_bins, A.slot_bin_cap, (const wc_surfel *)ctx->b_slots.p,
-                                             (const wc_surfel_id *)ctx->b_slot_ids.p, status, ctx->ex.d_out, ctx->ex.d_ids, cap, nullptr, 0u);
+                                             (const wc_surfel_id *)ctx->b_slot_ids.p, status, ctx->ex.d_out, ctx->ex.d_ids, cap, nullptr, 0u, 0u, nullptr);
   } else {
     k_iota<<<(unsigned)((total_slots + 255) / 256), 256, 0, st>>>((uint32_t *)ctx->b_slot_idx[0].p, total_slots);
     WC_TRY(sort_pairs<uint64_t>(ctx, (uint64_t *)ctx->b_slot_keys[0].p, (uint64_t *)ctx->b_slot_keys[1].p,
@@ -2166,19 +2197,39 @@ int enqueue_path(wc_ctx *ctx, const ExPath &path) {
   return rc;
 }
 
-// the sweep is done (its ticket has arrived, or the stream is idle); folds the mailbox flag words (raise_flag) into h_status[1]
+// the sweep's count, queue length and flags are final: its early count has arrived (fx_tail; k_slot_emit may still be copying surfels),
+// or the stream is idle.  Folds the mailbox flag words (raise_flag) into h_status[1]: with a ticket they all come from kernels in front
+// of k_slot_emit, behind a kernel boundary, so they have landed when its words have.
 int ex_wait(wc_ctx *ctx) {
-  bool arrived = false;
-  if (const uint32_t ticket = ctx->ex.ticket) {  // (fx_tail: the ticket kernel was the last thing enqueued)
-    ctx->ex.ticket = 0;
-    const uint32_t *w = (const uint32_t *)ctx->h_status + kMailTicket;
+  const uint32_t ticket = ctx->ex.ticket;
+  ctx->ex.ticket = 0;
+  if (ticket) {
+    const unsigned long long *w = (const unsigned long long *)ctx->h_status;
+    unsigned long long a = 0, b = 0;
+    bool arrived = false;
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t spin = 0; !arrived; ++spin) {
-      arrived = __atomic_load_n(w, __ATOMIC_ACQUIRE) == ticket;
+      a = __atomic_load_n(w + kExMailCount, __ATOMIC_ACQUIRE), b = __atomic_load_n(w + kExMailQueue, __ATOMIC_ACQUIRE);
+      arrived = ex_mail_arrived(a, b, ticket);
       if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) break;
     }
+    uint32_t count = ex_mail_count(a), queued = ex_mail_queued(b);
+    bool over = ex_mail_overflow(b);
+    if (!arrived) {  // never seen (20 ms): wait for the stream and read what the kernel left on the device - it wrote no plain mailbox word
+      FxArgs A;
+      std::memcpy(&A, ctx->ex.roots_args, sizeof(A));
+      uint32_t st8[8], cnt[16 * 32];  // status words; the layer-2 node sub-counters (banks 16 .. 31 of the counter block, 32 words apart)
+      WC_HIP(ctx, hipMemcpyAsync(st8, A.status, sizeof(st8), hipMemcpyDeviceToHost, ctx->stream));
+      WC_HIP(ctx, hipMemcpyAsync(cnt, A.cnt + 16 * 32, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
+      WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      count = st8[0], queued = st8[4], over = (st8[1] & kFlagSlotBinOverflow) != 0u;
+      for (int j = 0; j < 16; ++j) queued += cnt[j * 32];
+    }
+    ctx->h_status[0] = count, ctx->h_status[4] = queued;
+    if (over) ctx->h_status[8 + 4] = 1u;  // kFlagSlotBinOverflow's mailbox word, folded below (the kernel itself leaves the mailbox alone)
+  } else {
+    WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
-  if (!arrived) WC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (int i = 0; i < 7; ++i)
     if (ctx->h_status[8 + i]) ctx->h_status[1] |= 1u << i;
   return WC_OK;
@@ -2239,11 +2290,13 @@ extern "C" int wc_extract_surfels_finish(wc_ctx *ctx, uint64_t *h_n_out) {
   S.active = false;
   if (h_n_out) *h_n_out = 0;
   if (S.pts.n == 0) return WC_OK;
-  // The wait reads the completion ticket that k_ex_ticket, one thread behind the sweep's last kernel, stores to the pinned
-  // mailbox (fx_tail); without a ticket it waits for the stream.  (Round 3, tried: the ticket stored by k_slot_emit's last
-  // workgroup.  "Last of 1 024 workgroups" needs a count with a device-scope release in front of every workgroup's increment, and
-  // on this chip - one L2 per XCD - that fence writes the XCD's L2 back: 43 -> 70 us per sweep with a two-stage count, 130 us with
-  // one counter.  Without the fences a copy on another stream could read the surfels before they have left L2.)
+  // The wait reads the early count that k_slot_emit stores to the pinned mailbox as it starts (fx_tail); without a ticket it waits
+  // for the stream.  On return count, status and queue length are final; the surfels are complete IN THE ORDER OF THE CTX STREAM -
+  // k_slot_emit may still be copying them - which is where wc_d2h*, the next enqueue and every other library call read them;
+  // anyone else calls wc_sync first.  (Round 3, tried: k_slot_emit's last workgroup announcing the kernel's COMPLETION.  "Last of
+  // 1 024 workgroups" needs a count with a device-scope release in front of every workgroup's increment, and on this chip - one L2
+  // per XCD - that fence writes the XCD's L2 back: 43 -> 70 us per sweep with a two-stage count, 130 us with one counter.  The early
+  // count announces nothing of the kind: its values are final before the kernel starts, and no workgroup counts or fences.)
   WC_TRY(ex_wait(ctx));
   if (S.path.fx) {
     // layer-2 nodes were queued but the pair of launches was skipped (the previous sweep had none): run it now
@@ -2288,7 +2341,11 @@ extern "C" int wc_extract_surfels(wc_ctx *ctx, const wc_points *pts, double t_lo
                                   wc_surfel_id *d_ids, uint64_t cap, uint64_t *h_n_out) {
   wc_dev_guard dg_(ctx);
   WC_TRY(wc_extract_surfels_enqueue(ctx, pts, t_lo, t_hi, d_out, d_ids, cap));
-  return wc_extract_surfels_finish(ctx, h_n_out);
+  const int rc = wc_extract_surfels_finish(ctx, h_n_out);
+  // the one-call form is complete on return, for any reader: finish() may come back while k_slot_emit is still copying
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (rc == WC_OK && e != hipSuccess) return wc_fail(ctx, WC_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+  return rc;
 }
 
 // ---- K sweeps through ONE launch chain (include/wildcat_hip.h) ------------------------------------------------------------------
@@ -2349,7 +2406,7 @@ extern "C" int wc_extract_surfels_batch_enqueue(wc_ctx *ctx, const wc_sweep_job 
     any_merge = any_merge || (f & 2u);
     uint32_t *next_ctrl = (uint32_t *)sub->b_fx[5].p + (size_t)(sub->ex_mem.fx_parity ^ 1) * kCtrlWords;
     emit[Kd++] = SlotEmitArgs{A.slot_counts, A.slot_bins, A.slot_bin_cap, (const wc_surfel *)sub->b_slots.p, (const wc_surfel_id *)sub->b_slot_ids.p,
-                              A.status, sub->ex.d_out, sub->ex.d_ids, sub->ex.cap, next_ctrl, (uint32_t)kCtrlWords};
+                              A.status, sub->ex.d_out, sub->ex.d_ids, sub->ex.cap, next_ctrl, (uint32_t)kCtrlWords, 0u, nullptr};  // (no ticket)
   }
   if (Kd == 0) return WC_OK;
   WC_TRY(wc_ensure(ctx, ctx->b_batch, bytes));

@@ -44,7 +44,7 @@ struct ExSweep {
   uint64_t cap = 0;
   ExPath path;                 // the pipeline the last enqueue of this sweep ran on
   uint32_t runs = 0;           // pipelines enqueued for this sweep so far (1: no repeat)
-  uint32_t ticket = 0;         // completion ticket finish() waits for in the pinned mailbox (0: none - it waits for the stream)
+  uint32_t ticket = 0;         // ticket of the early count finish() waits for in the pinned mailbox (0: none - it waits for the stream)
   // the tail of the pipeline (layer-2 pass, surfel order, count / ticket) is run again by finish() when the enqueue skipped the
   // layer-2 launch and roots were queued for it after all
   int (*tail)(wc_ctx *, bool) = nullptr;
@@ -72,7 +72,7 @@ struct ExMemory {
   bool fx_ctrl_ready = false;    // the default path's two control blocks are initialised
   bool precleared = false;       // the exact path's control block has been cleared (on the stream) by the previous finish()
   bool bucket_attr_set = false;  // hipFuncSetAttribute(k_pt_bucket) done on this context's device
-  uint32_t ticket_seq = 0;       // last completion ticket handed out
+  uint32_t ticket_seq = 0;       // last ticket handed out (ex_mail_next_ticket)
   uint32_t fx_fallbacks = 0;     // sweeps the default path handed to the exact path so far
   uint32_t fx_last_flags = 0;    // status flags of the last default-path sweep
   uint32_t fx_last_why = 0;      // bit i: call site i of fx_fallback() fired in the last sweep that fell back
@@ -147,6 +147,30 @@ inline bool ex_next_path(ExPath &p, uint32_t flags, const uint32_t *why_words, E
 inline void ex_learn_unordered(ExMemory &m, const ExPath &p, uint32_t run_count, uint64_t n) {
   if (p.run_sort && run_count > 0) m.unordered = (uint64_t)run_count * 4 > n;
 }
+
+// ---- the early count: what k_slot_emit publishes as it starts and finish() waits for --------------------------------------------
+// Surfel count, layer-2 queue length and the bin-overflow flag are final when k_slot_emit starts (functions of what the node stage
+// left behind), so its last workgroup stores them to the pinned mailbox before it copies a surfel: two 64-bit words, each with the
+// sweep's ticket in its upper half.  A word is one aligned store, so it is either the old word or the new one, and since each
+// carries the ticket itself no order between the two is needed.  (constexpr: the kernel packs with the same functions.)
+constexpr int kExMailTicket = 120;                 // 32-bit word of the pinned mailbox (ctx->h_status) where the two words start ...
+constexpr int kExMailCount = kExMailTicket / 2;      // ... word A, as a 64-bit index: ticket << 32 | count
+constexpr int kExMailQueue = kExMailTicket / 2 + 1;  // ... word B: ticket << 32 | overflow << 31 | queued
+static_assert(kExMailTicket % 2 == 0, "the two words are 8-byte aligned");
+constexpr uint64_t ex_mail_pack_count(uint32_t ticket, uint32_t count) { return ((uint64_t)ticket << 32) | count; }
+// (a queue of 2^31 or more nodes cannot exist - the node blocks would not fit the card - and is reported as 2^31 - 1)
+constexpr uint64_t ex_mail_pack_queue(uint32_t ticket, bool overflow, uint32_t queued) {
+  return ((uint64_t)ticket << 32) | (overflow ? 0x80000000ull : 0ull) | (queued < 0x7FFFFFFFu ? queued : 0x7FFFFFFFu);
+}
+// both words are this sweep's (ticket 0 means "none" and never arrives; a stale ticket in either word is not arrival)
+constexpr bool ex_mail_arrived(uint64_t a, uint64_t b, uint32_t ticket) {
+  return ticket != 0u && (uint32_t)(a >> 32) == ticket && (uint32_t)(b >> 32) == ticket;
+}
+constexpr uint32_t ex_mail_count(uint64_t a) { return (uint32_t)a; }
+constexpr uint32_t ex_mail_queued(uint64_t b) { return (uint32_t)b & 0x7FFFFFFFu; }
+constexpr bool ex_mail_overflow(uint64_t b) { return ((uint32_t)b >> 31) != 0u; }
+// the ticket after `seq`: the sequence skips 0 when it wraps
+constexpr uint32_t ex_mail_next_ticket(uint32_t seq) { return seq + 1u != 0u ? seq + 1u : 1u; }
 
 // ---- sizes -----------------------------------------------------------------------------------------------------------------------
 // slots: the most surfels n points can give (`floor`: the default path hands slots out in kFxSub sub-ranges, never fewer than 256 each)

@@ -408,6 +408,17 @@ void wc_host_ex_sizes(uint64_t n, int max_layer, int cluster_min, uint64_t floor
   out5[3] = ex_fx_node_grid(n);
   out5[4] = ex_fx_layer2_grid((unsigned)out5[3], last_splits);
 }
+// ... and the early count's two mailbox words (tests/test_extract_mail_cpu.py).  pack: out2 = word A (ticket, count), word B (ticket,
+// overflow, queued).  unpack: out3 = count, queued, overflow; returns ex_mail_arrived(a, b, ticket).  next_ticket: the sequence.
+void wc_host_ex_mail_pack(uint32_t ticket, uint32_t count, uint32_t queued, int overflow, uint64_t out2[2]) {
+  out2[0] = ex_mail_pack_count(ticket, count);
+  out2[1] = ex_mail_pack_queue(ticket, overflow != 0, queued);
+}
+int wc_host_ex_mail_unpack(uint64_t a, uint64_t b, uint32_t ticket, uint32_t out3[3]) {
+  out3[0] = ex_mail_count(a), out3[1] = ex_mail_queued(b), out3[2] = ex_mail_overflow(b) ? 1u : 0u;
+  return ex_mail_arrived(a, b, ticket) ? 1 : 0;
+}
+uint32_t wc_host_ex_mail_next_ticket(uint32_t seq) { return ex_mail_next_ticket(seq); }
 
 // csrc/lm_loop.h - the decisions of the window solver's LM loop - driven step by step over a caller-owned state block
 // (tests/test_lm_loop_cpu.py).  op -1: -> the block's size in bytes.  op 0, lm_begin: in = max_iterations, lm_radius0,
